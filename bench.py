@@ -23,7 +23,22 @@ count, boxes, scores, anchors) are all-gathered over RCCL; pixels stay local.
 Rank 0 prints one JSON line.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--precision fp32]
+                    [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K
+timed steps, the result line. Everything else -- the per-kernel HIP-event pass and
+its rooflines, the other precisions (`modes`), the host-frame and JPEG pipelines,
+the CPU baseline and `parity` -- runs only with `--full`, where `--no-timing`,
+`--compare`, `--host-pipeline` and `--no-cpu-baseline` trim it as before.
+
+`--dump-outputs DIR` writes what the headline's last timed step returned to its
+caller (rank 0's shard) as DIR/<name>.npy: `frames_row_sums` (float64 [n, H, 3],
+every output pixel summed along x), `frames_sample` (float32, the output pixels at
+DUMP_SAMPLE seeded positions, or all of them when there are fewer), and per box list
+(`faces_`, `plates_`) `count`, `xyxy`, `xyxy_f`, `score`, `label` as float32 with the
+entries past each frame's count zeroed. Frames and weights are seeded, so two
+builds run with the same arguments can be compared array by array.
 
 `python bench.py --gpus N` (N > 1) with no WORLD_SIZE in the environment starts the
 N ranks itself: the parent makes no GPU call, runs torch.distributed.run as a child
@@ -51,6 +66,7 @@ sys.path.insert(0, ROOT)
 # 3-term bf16 split, six products) -> 2500 / 6; fp32_exact: v_mfma_f32_16x16x4_f32.
 PEAK_TFLOPS = {"bf16": 2500.0, "fp16": 2500.0, "fp32": 2500.0 / 3, "fp32_x6": 2500.0 / 6, "fp32_exact": 157.3}
 PEAK_HBM_GBS = 8000.0                           # MI355X_MICROARCH.md: HBM3E spec
+DUMP_SAMPLE = 1 << 22                           # --dump-outputs: output pixels sampled (16 MB as float32)
 
 
 def parse(argv=None):
@@ -65,6 +81,12 @@ def parse(argv=None):
                     help="noise: counter-hash frames at full size; up2: hash frames at half size, 2x nearest "
                          "upsampled (the ratio-2 / ratio-6 letterboxes of 720p / 4K then see structure and the "
                          "seeded weights detect faces; raw noise at those ratios averages out to none)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: per-kernel timing and rooflines, the --compare "
+                         "precisions, host / JPEG pipelines, CPU baseline, parity (a plain run skips them all)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 saves what the last timed step of the headline returned (mosaicked frames as row "
+                         "sums + a seeded pixel sample, face / plate box lists) as DIR/<name>.npy")
     ap.add_argument("--precision", default="fp32", choices=["bf16", "fp16", "fp32", "fp32_x6", "fp32_exact"])
     ap.add_argument("--compare", default="fp32_x6,fp32_exact,bf16,fp16",
                     help="extra precisions measured on the same frames at N=1 (',' separated; '' = none)")
@@ -217,6 +239,46 @@ def pmc_traffic(precision):
     return d.get("traffic_bytes_per_launch"), os.path.join("profiles", os.path.basename(f)), blur
 
 
+def hash_frames(n, h, w, start):
+    """synth.frames(n, h, w, seed=0, start=start), the frames made on a few threads
+    (numpy releases the GIL in the hash; one thread takes ~10 s for 64 1080p frames)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from vdmi import synth
+    out = np.empty((n, h, w, 3), np.uint8)
+
+    def one(i):
+        out[i] = synth.frame(h, w, start + i, 0)
+    with ThreadPoolExecutor(max_workers=min(8, len(os.sched_getaffinity(0)))) as ex:
+        list(ex.map(one, range(n)))
+    return out
+
+
+def dump_outputs(path, out, faces, plates, n):
+    """--dump-outputs: the arrays the last timed step returned, as <path>/<name>.npy.
+    out: uint8 [frames, H, W, 3] mosaicked frames on the device (None without mosaic);
+    faces / plates: the DeviceBoxes of the last batch (n frames), or None."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    if out is not None:
+        rows = torch.stack([f.sum(dim=1, dtype=torch.int64) for f in out])      # [frames, H, 3]
+        np.save(os.path.join(path, "frames_row_sums.npy"), rows.cpu().numpy().astype(np.float64))
+        flat = out.reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), DUMP_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(path, "frames_sample.npy"), flat.cpu().numpy().astype(np.float32))
+    for name, b in (("faces", faces), ("plates", plates)):
+        if b is None:
+            continue
+        cnt = b.count[:n].cpu().numpy()
+        live = np.arange(b.cap)[None, :] < cnt[:, None]          # entries past a frame's count: stale
+        np.save(os.path.join(path, f"{name}_count.npy"), cnt.astype(np.float32))
+        for k in ("xyxy", "xyxy_f", "score", "label"):
+            v = getattr(b, k)[:n].cpu().numpy().astype(np.float32)
+            v = np.where(live.reshape(live.shape + (1,) * (v.ndim - 2)), v, np.float32(0))
+            np.save(os.path.join(path, f"{name}_{k}.npy"), v)
+
+
 def frame_lists(ctx, n):
     """Complete per-frame (anchor keep list, int boxes) of the last call."""
     from vdmi import _lib
@@ -326,6 +388,10 @@ def main():
     a = parse(argv)
     if a.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if not a.full:   # plain run: the headline's set-up, warm-up and timed steps alone
+        a.no_timing, a.compare, a.host_pipeline, a.no_cpu_baseline = True, "", 0, True
     if "WORLD_SIZE" not in os.environ and (a.gpus > 1 or a.force_dist):
         # not started by torchrun: start the ranks now, before anything touches the GPU
         sys.exit(launch_ranks(argv, a.gpus))
@@ -375,9 +441,9 @@ def main():
     start = f0 if a.scaling == "weak" else 0
     nhost = max(1, min(B, nloc if a.scaling == "weak" else total))
     if a.frames_src == "up2":
-        host = np.repeat(np.repeat(synth.frames(nhost, H // 2, W // 2, seed=0, start=start), 2, axis=1), 2, axis=2)
+        host = np.repeat(np.repeat(hash_frames(nhost, H // 2, W // 2, start), 2, axis=1), 2, axis=2)
     else:
-        host = synth.frames(nhost, H, W, seed=0, start=start)
+        host = hash_frames(nhost, H, W, start)
     frames = torch.from_numpy(host).to(dev)
     if a.scaling == "strong":
         frames = frames[torch.arange(f0, f0 + nloc, device=dev) % nhost].contiguous()
@@ -426,6 +492,10 @@ def main():
         # `value`: K steps with nothing but the work in the stream (no per-launch events)
         dt = timed(mode)
         res = {"value": round(total * a.steps / dt, 2), "ms_per_step": round(dt / a.steps * 1e3, 3)}
+        if a.dump_outputs and rank == 0 and precision == a.precision:
+            _, o, fb, pb = mode.current(out)        # the slot of the last timed step
+            dump_outputs(a.dump_outputs, o if mode.flags & _lib.VD_PROC_MOSAIC else None,
+                         fb if mode.flags & _lib.VD_PROC_FACES else None, pb, batches[-1][1] if batches else 0)
         if not a.no_timing:
             res.update(instrumented(mode, precision))
             rf = res["roofline"]
@@ -445,7 +515,7 @@ def main():
                                    f"{mode.face_groups}: every other kernel of the step, the plate net included, "
                                    "counted against the convs)")
         res["faces_per_frame"] = round(float(mode.faces.count.float().mean().item()), 2)
-        lists = frame_lists(mode.ctx, batches[-1][1]) if batches and a.faces else []
+        lists = frame_lists(mode.ctx, batches[-1][1]) if a.full and batches and a.faces else []   # for `parity`
         if world == 1 and precision == a.precision and a.host_pipeline:
             res["host_pipeline"] = host_pipeline(mode)
             res["jpeg_pipeline"] = jpeg_pipeline(mode)

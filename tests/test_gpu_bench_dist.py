@@ -82,6 +82,48 @@ def test_bench_rccl_world1_equals_no_dist(gpu, tmp_path):
     assert r2 == r1
 
 
+def test_bench_plain_line_and_dump_outputs(gpu, tmp_path):
+    """A plain run (no --full) prints the headline line alone, with `ms_per_step` over
+    exactly --steps steps, and --dump-outputs writes what the last timed step returned
+    as float .npy files (<= 64 MB in all) whose box lists equal that step's records."""
+    import json
+    from vdmi.dist import unpack_records
+    rec, dump = str(tmp_path / "one.npy"), tmp_path / "dump"
+    out = _run([sys.executable, "bench.py", "--scaling", "strong", "--frames", "6", "--batch", "6", "--steps", "2",
+                "--warmup", "0", "--dump-outputs", str(dump)], rec)
+    line = json.loads([x for x in out.splitlines() if x.startswith("{")][-1])
+    assert line["steps"] == 2 and line["unit"] == "frames/s" and line["higher_is_better"] is True
+    assert line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] * 1e-3 - 6) < 0.06
+    for k in ("roofline", "blur_roofline", "modes", "cpu_baseline", "parity", "host_pipeline", "jpeg_pipeline"):
+        assert k not in line, k
+    arrs = {f[:-4]: np.load(dump / f) for f in sorted(os.listdir(dump)) if f.endswith(".npy")}
+    assert {"frames_row_sums", "frames_sample", "faces_count", "faces_xyxy", "faces_score", "faces_label",
+            "plates_count", "plates_xyxy"} <= set(arrs)
+    assert all(v.dtype in (np.float32, np.float64) for v in arrs.values())
+    assert sum(v.nbytes for v in arrs.values()) <= 64 << 20
+    assert arrs["frames_row_sums"].shape == (6, 1080, 3) and arrs["frames_sample"].max() <= 255
+    r = unpack_records(np.load(rec))
+    assert sum(v[3] for v in r.values()) > 0
+    for f in range(6):
+        boxes, scores, anchors, count = r[f]
+        k = len(boxes)
+        assert arrs["faces_count"][f] == count
+        assert [tuple(int(v) for v in b) for b in arrs["faces_xyxy"][f, :k]] == boxes
+        assert arrs["faces_score"][f, :k].tolist() == scores and arrs["faces_label"][f, :k].astype(int).tolist() == anchors
+
+
+def test_bench_full_keeps_the_extra_blocks(gpu, tmp_path):
+    """--full runs what a plain run leaves out (here: the HIP-event pass with its
+    rooflines and one compared precision; the slow legs switched off as before)."""
+    import json
+    out = _run([sys.executable, "bench.py", "--full", "--batch", "2", "--steps", "1", "--warmup", "0", "--compare", "fp16",
+                "--host-pipeline", "0", "--no-cpu-baseline"], str(tmp_path / "one.npy"))
+    line = json.loads([x for x in out.splitlines() if x.startswith("{")][-1])
+    assert line["ms_per_step"] > 0 and line["dtype"] == "fp32"
+    assert line["roofline"]["bound"] == "mfma" and line["blur_roofline"]["bound"] == "hbm"
+    assert "fp16" in line["modes"] and "fp16_vs_fp32" in line["parity"]
+
+
 @pytest.mark.parametrize("dist", [False, True])
 def test_bench_inflight_records_equal_single_slot(gpu, tmp_path, dist):
     """bench.py --inflight 2 (two contexts taking consecutive steps on their own streams;
