@@ -481,26 +481,6 @@ def test_heads_fp32_chain_matches_unfused(gpu, chain, gpw):
         np.testing.assert_array_equal(a, b)
 
 
-def test_heads_fp32_tail_split_bit_identical(gpu):
-    """fp32 plan: the big-tile layers' last partial round runs as a second launch of a
-    narrower tile (conv_x6.hip launch_x6_big, option x6_tail). The split is along N
-    only, so every output keeps its K order and MFMA form: heads bit-identical to the
-    unsplit launches. x6_slots=8 makes every big-tile layer of a 3-frame batch split."""
-    import vdmi
-    fr = _frames(3, 1080, 1920, seed=31)
-    heads = {}
-    for tail in (0, 1, 2):
-        ctx = vdmi.Context(precision="fp32", max_batch=3, options={"x6_tail": tail, "x6_slots": 8})
-        try:
-            ctx.load_weights(0, face_weights("default"))
-            heads[tail] = ctx.forward_heads(fr)
-        finally:
-            ctx.close()
-    for t in (1, 2):
-        for a, b in zip(heads[t], heads[0]):
-            np.testing.assert_array_equal(a, b)
-
-
 def test_heads_fp32_halo_tr_bit_identical(gpu):
     """fp32 plan: the halo 3x3 tiles with the MFMA operands exchanged (D^T accumulators,
     weight rows permuted in the DMA, register epilogue; option x6_halo_tr, 1 = the
@@ -528,21 +508,21 @@ def test_heads_fp32_pipelined_b_reads_bit_identical(gpu):
     barrier, 1 after the MFMAs, 2 between groups, default); the streaming 1x1 layers
     with a residual load it beside the MFMAs (x6_stream_rl, default 1); the 1x1 GEMM
     loop issues the same loads every K tile with one barrier per tile (x6_gemm_uni 2,
-    default; 1 keeps two barriers). Schedule only:
+    default). Schedule only:
     the same products in the same order, heads bit-identical to the round-5 schedule."""
     import vdmi
     fr = _frames(2, 1080, 1920, seed=43)
     heads = {}
     for key, opts in (("r5", {"x6_halo_pf": 0, "x6_gemm_pf": 0, "x6_halo_dma": 0, "x6_stream_rl": 0,
                               "x6_gemm_uni": 0}), ("pf", {}),
-                      ("d1", {"x6_halo_dma": 1}), ("u1", {"x6_gemm_uni": 1})):
+                      ("d1", {"x6_halo_dma": 1})):
         ctx = vdmi.Context(precision="fp32", max_batch=2, options=opts)
         try:
             ctx.load_weights(0, face_weights("default"))
             heads[key] = ctx.forward_heads(fr)
         finally:
             ctx.close()
-    for k in ("pf", "d1", "u1"):
+    for k in ("pf", "d1"):
         for a, b in zip(heads[k], heads["r5"]):
             np.testing.assert_array_equal(a, b)
 

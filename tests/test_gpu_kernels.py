@@ -521,6 +521,13 @@ TR_CASES = [
     (3, 19, 23, 512, 128, 1, 1, 0, 1, 0),
     (1, 21, 19, 256, 384, 1, 1, 0, 2, 2),
     (2, 45, 47, 512, 2048, 1, 1, 0, 1, 1),
+    # the one-barrier loop against the general loop at the shapes its race was seen on
+    (2, 21, 19, 2048, 256, 1, 1, 0, 0, 0),    # FPN lateral from layer4: 256 x 128 tile, 64 K tiles, M tail
+    (1, 23, 25, 1024, 256, 1, 1, 0, 1, 0),    # layer3 conv1 form
+    (1, 17, 15, 2048, 512, 1, 1, 0, 1, 0),    # layer4 conv1 form
+    (1, 77, 79, 1024, 2048, 1, 1, 0, 1, 1),   # 256 x 256 tile, 24 x 8 = 192 tiles, K = 1024, residual
+    (1, 19, 23, 96, 128, 1, 1, 0, 1, 0),      # 3 K tiles: the odd tail after whole rounds of register sets
+    (1, 19, 23, 32, 128, 1, 1, 0, 1, 0),      # 1 K tile: every prologue load past the end is the clamped last tile
 ]
 
 
@@ -528,7 +535,9 @@ TR_CASES = [
 def test_conv_tr_tiles_bit_identical(gpu, face_ctx_factory, case):
     """The TR tiles (D^T accumulators, register epilogue) compute the same products in
     the same order as the untransposed tiles: outputs (and the per-frame max slots the
-    hook checks) are bit-identical, and within the fp32 tolerance of torch."""
+    hook checks) are bit-identical, and within the fp32 tolerance of torch. The TR tiles'
+    one-barrier K loop (option x6_gemm_uni = 2, default) and the general loop (0) issue
+    the same products in the same order: bit-identical too."""
     n, h, w, cin, cout, k, s, p, act, res_mode = case
     rng = np.random.default_rng(cin + 3 * cout)
     x = np.maximum(rng.standard_normal((n, h, w, cin)), 0).astype(F32)
@@ -542,6 +551,8 @@ def test_conv_tr_tiles_bit_identical(gpu, face_ctx_factory, case):
         ctx = face_ctx_factory("fp32", 8, options=(("x6_gemm1x1", tr), ("x6_stream", 0)))
         outs.append(ctx.conv2d(x, wt, s, p, scale, shift, act, 0.1, res, res_mode))
     assert np.array_equal(outs[0], outs[1])
+    ctx = face_ctx_factory("fp32", 8, options=(("x6_gemm1x1", 1), ("x6_gemm_uni", 0), ("x6_stream", 0)))
+    assert np.array_equal(ctx.conv2d(x, wt, s, p, scale, shift, act, 0.1, res, res_mode), outs[1])
     test_conv_matches_torch(gpu, face_ctx_factory, "fp32", case, options=dict(x6_gemm1x1=1, x6_stream=0))
 
 

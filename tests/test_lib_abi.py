@@ -93,7 +93,8 @@ def test_host_boxes_struct():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["x6_dbg", "block32_dbg", "mosaic_copy", "face_group_lag", "plate_prio",
-                                  "plate_cus"])
+                                  "plate_cus", "x6_tail", "x6_slots", "x6_adepth", "x6_halo_n64",
+                                  "x6_tr_epi"])
 def test_set_option_refuses_debug_and_removed_switches(gpu, name):
     """The timing-only switches that skip work (wrong results) are not vd_set_option
     names -- only the test entry vdt_set_debug takes them -- and the dead experiment
@@ -110,6 +111,22 @@ def test_set_option_refuses_debug_and_removed_switches(gpu, name):
             with pytest.raises(_lib.VdError, match="unknown debug switch"):
                 ctx.set_debug(name, 0)
         ctx.set_option("face_groups", 2)              # a production switch still takes
+    finally:
+        ctx.close()
+
+
+@pytest.mark.gpu
+def test_set_option_refuses_retired_gemm_loop_mode(gpu):
+    """x6_gemm_uni keeps 0 (the general K loop) and 2 (the one-barrier 1x1 loop); the
+    two-barrier uniform loop (1) is gone and vd_set_option says so."""
+    import vdmi
+    from vdmi import _lib
+    ctx = vdmi.Context(precision="fp32", max_batch=1)
+    try:
+        with pytest.raises(_lib.VdError, match="x6_gemm_uni must be 0 or 2"):
+            ctx.set_option("x6_gemm_uni", 1)
+        ctx.set_option("x6_gemm_uni", 0)
+        ctx.set_option("x6_gemm_uni", 2)
     finally:
         ctx.close()
 

@@ -7,7 +7,9 @@
 //         -Ivideo-desensitization_amd/csrc -Iinclude -Lvideo-desensitization_amd/vdmi -lvdmi \
 //         -Wl,-rpath,$PWD/video-desensitization_amd/vdmi -o tools/x6bench
 //   tools/x6bench [reps] [layer-substring|all] [tune=value ...]
-// tune names: the VdTune fields listed in kTune below (kernel selection / experiments).
+// tune names: the VdTune fields listed in kTune below (kernel selection / experiments). The fields are
+// written directly, past vd_set_option's checks, so values the library no longer has are refused here:
+// x6_gemm_uni takes 0 or 2, x6_dbg only its timing-only bits (1, 4, 8, 16, 32).
 #include "vd_common.h"
 
 #include <cmath>
@@ -46,10 +48,12 @@ static const Layer kLayers[] = {
 struct TuneField { const char* name; int VdTune::*f; };
 static const TuneField kTune[] = {
     {"x6_stream", &VdTune::x6_stream},   {"x6_stream256", &VdTune::x6_stream256}, {"x6_bn256", &VdTune::x6_bn256},
-    {"x6_mid", &VdTune::x6_mid},         {"x6_mf32", &VdTune::x6_mf32},           {"x6_tail", &VdTune::x6_tail},
-    {"x6_halo", &VdTune::x6_halo},       {"x6_halo_s2", &VdTune::x6_halo_s2}, {"x6_adepth", &VdTune::x6_adepth},       {"x6_small_k", &VdTune::x6_small_k},
-    {"x6_small_tiles", &VdTune::x6_small_tiles}, {"x6_gemm1x1", &VdTune::x6_gemm1x1}, {"x6_dbg", &VdTune::x6_dbg},
-    {"x6_halo_tr", &VdTune::x6_halo_tr}, {"x6_halo_dma", &VdTune::x6_halo_dma}, {"x6_halo_pf", &VdTune::x6_halo_pf}, {"x6_gemm_pf", &VdTune::x6_gemm_pf}, {"x6_gemm_uni", &VdTune::x6_gemm_uni}, {"x6_halo_1b", &VdTune::x6_halo_1b}, {"x6_stream_rl", &VdTune::x6_stream_rl}, {"x6_tr_epi", &VdTune::x6_tr_epi}, {"x6_halo_n64", &VdTune::x6_halo_n64}, {"x6_one", &VdTune::x6_one},
+    {"x6_mid", &VdTune::x6_mid},         {"x6_halo", &VdTune::x6_halo},           {"x6_halo_s2", &VdTune::x6_halo_s2},
+    {"x6_small_k", &VdTune::x6_small_k}, {"x6_small_tiles", &VdTune::x6_small_tiles}, {"x6_gemm1x1", &VdTune::x6_gemm1x1},
+    {"x6_dbg", &VdTune::x6_dbg},         {"x6_halo_tr", &VdTune::x6_halo_tr},     {"x6_halo_dma", &VdTune::x6_halo_dma},
+    {"x6_halo_pf", &VdTune::x6_halo_pf}, {"x6_gemm_pf", &VdTune::x6_gemm_pf},     {"x6_gemm_uni", &VdTune::x6_gemm_uni},
+    {"x6_halo_1b", &VdTune::x6_halo_1b}, {"x6_stream_rl", &VdTune::x6_stream_rl}, {"x6_one", &VdTune::x6_one},
+    {"x6_mf32", &VdTune::x6_mf32},
 };
 
 static float frand(uint32_t& st) {
@@ -167,6 +171,11 @@ int main(int argc, char** argv) {
         for (const TuneField& t : kTune)
             if (k == t.name) { tune.*(t.f) = atoi(eq + 1); ok = true; }
         if (!ok) { fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
+        if (k == "x6_gemm_uni" && tune.x6_gemm_uni != 0 && tune.x6_gemm_uni != 2) {
+            fprintf(stderr, "x6_gemm_uni must be 0 or 2\n");
+            return 2;
+        }
+        if (k == "x6_dbg" && (tune.x6_dbg & ~0x3d)) { fprintf(stderr, "x6_dbg: unknown bits in %d\n", tune.x6_dbg); return 2; }
     }
     double tot = 0;
     for (const Layer& L : kLayers) {

@@ -260,7 +260,7 @@ __device__ __forceinline__ void x6_epilogue(const ConvArgs& a, AccT (&acc)[S::TM
                                             int wn, int tid, int lane, char* smem, int amax_off) {
     constexpr int BM = S::BM, BN = S::BNV, NT = S::NT, TM = S::TM, TN = S::TN, TERMS = S::TERMSV;
     const int ohw = a.yh * a.yw;
-    if (a.dbg & 1) {                                   // timing experiment: main loop only
+    if (a.dbg & 1) {                                   // timing-only (x6_dbg bit 0): main loop only
         if (acc[0][0][0] == 1234.5f) ((float*)a.y)[tid] = 1.f;
         return;
     }
@@ -478,80 +478,6 @@ __device__ __forceinline__ void x6_epilogue_tr(const ConvArgs& a, f32x4_t (&acc)
     }
 }
 
-// the round-5 form (option x6_tr_epi = 0): residual and BN rows loaded row by row behind the stores
-template <class S>
-__device__ __forceinline__ void x6_epilogue_tr_r5(const ConvArgs& a, f32x4_t (&acc)[S::TM][S::TN], int m0, int n0,
-                                               int wm, int wn, int lane, unsigned* s_amax) {
-    constexpr int TM = S::TM, TN = S::TN;
-    static_assert(TN % 2 == 0, "TR tiles pair the channel blocks");
-    const int ohw = a.yh * a.yw;
-    const int q = lane >> 4, pl = lane & 15;
-    const int cb = n0 + wn * S::WTN + 8 * q;
-    int mrow[TM], fbs[TM];
-    float inv[TM], vmax[TM];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        const int m = m0 + wm * S::WTM + 16 * i + pl;
-        mrow[i] = m;
-        fbs[i] = m < a.M ? m / ohw : -1;
-        inv[i] = __builtin_ldexpf(1.f, -act_scale_exp(a, fbs[i] < 0 ? 0 : fbs[i]));
-        vmax[i] = 0.f;
-    }
-#pragma unroll
-    for (int jp = 0; jp < TN / 2; ++jp) {
-        const int c = cb + 32 * jp;
-        if (c >= a.cout) continue;
-        const float4 s0 = *(const float4*)(a.scale + c), s1 = *(const float4*)(a.scale + c + 4);
-        const float4 h0 = *(const float4*)(a.shift + c), h1 = *(const float4*)(a.shift + c + 4);
-        const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-        const float sh[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int m = mrow[i];
-            if (m >= a.M) continue;
-            float rv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (a.res_mode != VD_RES_NONE) {
-                size_t roff;
-                if (a.res_up) {
-                    const int b = fbs[i], rem = m - b * ohw;
-                    const int oy = rem / a.yw, ox = rem - oy * a.yw;
-                    roff = ((size_t)(b * a.rh + (oy >> 1)) * a.rw + (ox >> 1)) * a.res_ld;
-                } else {
-                    roff = (size_t)m * a.res_ld;
-                }
-                roff += a.res_coff + c;
-                const float4 r0 = *(const float4*)((const float*)a.res + roff);
-                const float4 r1 = *(const float4*)((const float*)a.res + roff + 4);
-                rv[0] = r0.x; rv[1] = r0.y; rv[2] = r0.z; rv[3] = r0.w;
-                rv[4] = r1.x; rv[5] = r1.y; rv[6] = r1.z; rv[7] = r1.w;
-            }
-            float v[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float ev = e < 4 ? acc[i][2 * jp][e] : acc[i][2 * jp + 1][e - 4];
-                float t = (ev * inv[i]) * sc[e] + sh[e];
-                if (a.res_mode == VD_RES_PRE_ACT) t += rv[e];
-                t = act_apply(t, a.act, a.slope);
-                if (a.res_mode == VD_RES_POST_ACT) t += rv[e];
-                v[e] = t;
-                vmax[i] = fmaxf(vmax[i], fabsf(t));
-            }
-            float* yp = (float*)a.y + (size_t)m * a.ldy + a.ycoff + c;
-            *(float4*)yp = make_float4(v[0], v[1], v[2], v[3]);
-            *(float4*)(yp + 4) = make_float4(v[4], v[5], v[6], v[7]);
-        }
-    }
-    if (a.ymax) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i) amax_lds_add(s_amax, fbs[i], vmax[i]);
-        __syncthreads();
-        amax_lds_flush(s_amax, a.ymax, a.B);
-    }
-}
-
-// LDS row -> weight row of a TR tile: row 16 j + i of each 32-row group holds channel
-// 8 (i >> 2) + 4 (j & 1) + (i & 3) of the group, so blocks 2jp, 2jp+1 give a lane 8
-// consecutive channels (conv1x1_x6_kernel's permutation)
 // the register epilogue (x6_epilogue_tr) addresses y and the residual by 32-bit buffer offsets
 static bool tr_bytes_ok(const ConvArgs& a) {
     const double lim = 2147483647.0;
@@ -560,13 +486,16 @@ static bool tr_bytes_ok(const ConvArgs& a) {
     return true;
 }
 
+// LDS row -> weight row of a TR tile: row 16 j + i of each 32-row group holds channel
+// 8 (i >> 2) + 4 (j & 1) + (i & 3) of the group, so blocks 2jp, 2jp+1 give a lane 8
+// consecutive channels (conv1x1_x6_kernel's permutation)
 __device__ __forceinline__ int x6_tr_row(int row) {
     const int j = (row >> 4) & 1, i = row & 15;
     return (row & ~31) + 8 * (i >> 2) + 4 * j + (i & 3);
 }
 
-template <int BM, int BN, int NT, int NST, int TERMS, int MF, int NA, bool TR = false, bool PF = false>
-// NA: A register sets (K tiles of A loads in flight: NA - 1 besides the one being split)
+template <int BM, int BN, int NT, int NST, int TERMS, int MF, bool TR = false, bool PF = false>
+// MF: MFMA form of the fp16 pairs, 16 = 16x16x32, 32 = 32x32x16 (option x6_mf32)
 // 8 waves: two workgroups' worth of waves per SIMD pair (256 VGPRs each); 4 waves (one
 // per SIMD, 128 x 128 wave tiles): the whole 512-register file per wave, the
 // accumulators in AGPRs
@@ -576,6 +505,7 @@ __global__ __launch_bounds__(NT, NT == 256 && BM == 256 ? 1 : 2) void conv_x6_ke
     static_assert(MF == 16 || (MF == 32 && TERMS == 2), "32x32x16 form: fp16 pairs only");
     static_assert(!TR || (MF == 16 && TERMS == 2), "TR tiles: fp16 pairs on 16x16x32");
     using S = X6Shape<BM, BN, NT, NST, TERMS, MF>;
+    constexpr int NA = 2;   // A register sets (K tiles of A loads in flight: NA - 1 besides the one being split)
     constexpr int STAGE = S::STAGE, PL_A = S::PL_A, PL_B = S::PL_B, TM = S::TM, TN = S::TN, WAVES = S::WAVES;
     constexpr int AROWS = S::AROWS, AIT = S::AITEMS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -587,7 +517,7 @@ __global__ __launch_bounds__(NT, NT == 256 && BM == 256 ? 1 : 2) void conv_x6_ke
     const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
     const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
     const int tn = wg % a.ntiles_n, tm = wg / a.ntiles_n;
-    const int m0 = a.mbase + tm * BM, n0 = tn * BN;
+    const int m0 = tm * BM, n0 = tn * BN;
 
     // ---- A staging: thread = (row, k-pair) items; item i: row = (tid >> 2) + AROWS i, pair = tid & 3 (k 8p..8p+7)
     const int apair = tid & 3, arow = tid >> 2;
@@ -620,7 +550,7 @@ __global__ __launch_bounds__(NT, NT == 256 && BM == 256 ? 1 : 2) void conv_x6_ke
     // 1x1 convs without K padding (option x6_one): K tile kt of a row is bytes
     // [128 kt, 128 kt + 128) past the row's pixel, so each load is the row's byte offset
     // (rows past M: out of range) plus a scalar offset -- no per-tile tap stepping
-    const bool one = (a.dbg & 4) && a.kh == 1 && a.kw == 1 && a.pad == 0 &&
+    const bool one = a.one && a.kh == 1 && a.kw == 1 && a.pad == 0 &&
                      a.kpad == a.cin_pad && a.cin_pad % KT == 0;
     if (one) {
 #pragma unroll
@@ -628,14 +558,8 @@ __global__ __launch_bounds__(NT, NT == 256 && BM == 256 ? 1 : 2) void conv_x6_ke
             pix0[i] = m0 + arow + AROWS * i < a.M ? pix0[i] * 4 + apair * 32 : (int)0x80000000;
     }
     int lk = 0;                                     // K tiles loaded so far (one: the scalar offset)
-    // The two-stage main loop on 1x1 convs (UNI) issues the same loads and DMAs every
-    // iteration (past nk: the last tile again, L2 hits), branch-free, so that the
-    // compiler's own waits on the A registers count every younger op -- with the refills
-    // under `if`s (and the runtime `one` branch) it assumed none and waited for the NEXT
-    // tile's loads (just issued) in the middle of the MFMAs
-
-    // two register sets of A (8 f32 of each of 2 rows): tile t lives in set t & 1,
-    // loaded two iterations before it is split into LDS
+    // NA register sets of A (8 f32 of each of AIT rows): tile t lives in set t % NA,
+    // loaded NA iterations before it is split into LDS
     u32x4 ra[NA][AIT][2];                           // [set][item][half]
     // per half h: the (dy, dx, c) of this thread's 4-channel chunk kt*8 + 2*apair + h,
     // advanced by 32 channels per load_a call (tiles are loaded in order): no
@@ -718,7 +642,7 @@ __global__ __launch_bounds__(NT, NT == 256 && BM == 256 ? 1 : 2) void conv_x6_ke
                 const int row = r0 + (lane >> 2), slot = lane & 3;
                 const int chunk = slot ^ (((row >> 3) & 1) * 3);
                 const int wrow = TR ? x6_tr_row(row) : row;
-                const int ktc = kt < nk ? kt : nk - 1;     // UNI tail: the last tile again (a scalar min)
+                const int ktc = kt < nk ? kt : nk - 1;     // one-barrier tail: the last tile again (a scalar min)
                 const unsigned off = (unsigned)((((long)(n0 + wrow) * nk + ktc) * S::TB + p) * 64 + chunk * 16);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (lds_void_t*)(Bs + p * PL_B + r0 * 64), 16, off, 0,
                                                          0, 0);
@@ -847,23 +771,62 @@ __global__ __launch_bounds__(NT, NT == 256 && BM == 256 ? 1 : 2) void conv_x6_ke
     };
 
     if constexpr (NST == 2) {
-    // ---- main loop. A(t) lives in register set t % NA. Per thread VMEM issue order at
+    // ---- main loop, two forms. A(t) lives in register set t % NA.
+    // The general loop (every KxK conv; 1x1 convs with option x6_gemm_uni = 0 or on tiles
+    // without whole DMA rounds): two barriers per K tile. Per thread VMEM issue order at
     // the end of iteration t: A(t+1+NA) loads (2 AIT, into the set A(t+1) just left),
     // B(t+2) DMA (my_dma); the prologue issues A(0) (split at once), A(1..NA-1), B(0),
     // A(NA), B(1), i.e. the ends of iterations -2 and -1. At the top of iteration t the
     // ops younger than B(t) are those of iteration t-1's end, and A(t+1) is older than
     // B(t), so both retire at vmcnt(2 AIT + my_dma) (fewer when the tail issued less).
-    // UNI (default; option x6_gemm_uni 0 = the round-5 loop): every iteration issues its
-    // loads and DMA (past nk: out of range), the loop runs whole rounds of NA iterations
-    // and a tail after it, so the compiler's waits on the A registers see every younger op
-    // ONEB (option x6_gemm_uni 2): one barrier per K tile -- B(kt+1)'s DMA and A(kt+NA)'s
-    // loads issued right after tile kt's barrier (stage (kt+1) & 1 was last read by tile
-    // kt-1, which every wave has finished there), so the barrier after the MFMAs goes
-    auto main_loop = [&](auto mode_tag) {
-    constexpr int MODE = decltype(mode_tag)::value;
-    constexpr bool UNI = MODE >= 1;
-    auto load_a = [&](u32x4 (&r)[AIT][2]) {
-        if constexpr (UNI) {                                  // 1x1 (one): no tap stepping, no branch
+    auto main_loop = [&]() {
+        load_a_any(ra[0]);
+#pragma unroll
+        for (int q = 0; q < AIT; ++q) store_item(0, ra[0], q);
+#pragma unroll
+        for (int j = 1; j < NA; ++j)
+            if (j < nk) load_a_any(ra[j]);
+        dma_b(0, 0);
+        if (NA < nk) load_a_any(ra[0]);
+        if (nk > 1) dma_b(1, 1);
+        auto iter = [&](int kt, const u32x4 (&rnext)[AIT][2], u32x4 (&rfree)[AIT][2]) {
+            if constexpr (S::NDMA % WAVES == 0) {   // immediates: no runtime wait_vm branch tree
+                constexpr int MYD = S::NDMA / WAVES;
+                if (kt + NA < nk) wait_vm_k<2 * AIT + MYD>();
+                else if (kt + 1 < nk) wait_vm_k<MYD>();
+                else wait_vm_k<0>();
+            } else {
+                wait_vm((kt + NA < nk ? 2 * AIT : 0) + (kt + 1 < nk ? my_dma : 0));
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this thread's A(kt) ds_writes
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            compute(kt & 1, kt + 1 < nk, (kt + 1) & 1, rnext);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();                        // everyone done reading stage kt & 1
+            asm volatile("" ::: "memory");
+            if (kt + 1 + NA < nk) load_a_any(rfree);              // A(kt+1+NA) into the set A(kt+1) just left
+            if (kt + 2 < nk) dma_b(kt + 2, kt & 1);
+        };
+        // Raw barriers with counted waits: __syncthreads() would add vmcnt(0) and drain
+        // the prefetch. Unrolled by NA so the register sets are indexed statically.
+        for (int kt = 0; kt < nk; kt += NA) {
+#pragma unroll
+            for (int u = 0; u < NA; ++u)
+                if (kt + u < nk) iter(kt + u, ra[(u + 1) % NA], ra[(u + 1) % NA]);
+        }
+    };
+    // The one-barrier loop (1x1 convs, `one`; option x6_gemm_uni = 2, default; tiles with
+    // whole DMA rounds): every iteration issues the same loads and DMA (past nk: the last
+    // tile again, L2 hits), branch-free, and the loop runs whole rounds of NA iterations and
+    // a tail after it, so the compiler's own waits on the A registers count every younger op
+    // -- with the refills under `if`s (and the runtime `one` branch) it assumed none and
+    // waited for the NEXT tile's loads (just issued) in the middle of the MFMAs. B(kt+1)'s DMA and
+    // A(kt+NA)'s loads are issued right after tile kt's barrier (stage (kt+1) & 1 was last
+    // read by tile kt-1, which every wave has finished there), so the barrier after the
+    // MFMAs goes.
+    auto main_loop_1b = [&]() {
+        auto load_a = [&](u32x4 (&r)[AIT][2]) {                  // no tap stepping, no branch
             const int so = (lk < nk ? lk : nk - 1) * (KT * 4);
 #pragma unroll
             for (int i = 0; i < AIT; ++i) {
@@ -871,14 +834,10 @@ __global__ __launch_bounds__(NT, NT == 256 && BM == 256 ? 1 : 2) void conv_x6_ke
                 r[i][1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, pix0[i] + 16, so, 0));
             }
             ++lk;
-        } else {
-            load_a_any(r);
-        }
-    };
-    load_a(ra[0]);
+        };
+        load_a(ra[0]);
 #pragma unroll
-    for (int q = 0; q < AIT; ++q) store_item(0, ra[0], q);
-    if constexpr (MODE == 2) {
+        for (int q = 0; q < AIT; ++q) store_item(0, ra[0], q);
         // VMEM order: A(1..NA-2), B(0), A(NA-1) | per tile kt after its barrier: B(kt+1),
         // A(kt+NA). Younger than B(kt) at the top of kt: A(kt-1+NA) only.
 #pragma unroll
@@ -909,63 +868,12 @@ __global__ __launch_bounds__(NT, NT == 256 && BM == 256 ? 1 : 2) void conv_x6_ke
         for (int u = 0; u < NA - 1; ++u)
             if (kt + u < nk) iterb(kt + u, ra[(u + 1) % NA], ra[u]);
         wait_vm_k<0>();                                          // the tail's DMA / loads (past nk)
-        return;
-    }
-#pragma unroll
-    for (int j = 1; j < NA; ++j)
-        if (UNI || j < nk) load_a(ra[j]);
-    dma_b(0, 0);
-    if (UNI || NA < nk) load_a(ra[0]);
-    if (UNI || nk > 1) dma_b(1, 1);
-    auto iter = [&](int kt, const u32x4 (&rnext)[AIT][2], u32x4 (&rfree)[AIT][2]) {
-        if (S::NDMA % WAVES == 0 && !(a.dbg & 2)) {   // immediates: no runtime wait_vm branch tree
-            constexpr int MYD = S::NDMA % WAVES == 0 ? S::NDMA / WAVES : 0;
-            if (UNI || kt + NA < nk) wait_vm_k<2 * AIT + MYD>();
-            else if (kt + 1 < nk) wait_vm_k<MYD>();
-            else wait_vm_k<0>();
-        } else {
-            wait_vm(UNI ? 2 * AIT + my_dma : (kt + NA < nk ? 2 * AIT : 0) + (kt + 1 < nk ? my_dma : 0));
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this thread's A(kt) ds_writes
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        compute(kt & 1, kt + 1 < nk, (kt + 1) & 1, rnext);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                        // everyone done reading stage kt & 1
-        asm volatile("" ::: "memory");
-        if (UNI || kt + 1 + NA < nk) load_a(rfree);           // A(kt+1+NA) into the set A(kt+1) just left
-        if (UNI || kt + 2 < nk) dma_b(kt + 2, kt & 1);
     };
-    // Raw barriers with counted waits: __syncthreads() would add vmcnt(0) and drain
-    // the prefetch. Unrolled by NA so the register sets are indexed statically.
-    if constexpr (UNI) {
-        int kt = 0;
-        for (; kt + NA <= nk; kt += NA) {
-#pragma unroll
-            for (int u = 0; u < NA; ++u) iter(kt + u, ra[(u + 1) % NA], ra[(u + 1) % NA]);
-        }
-#pragma unroll
-        for (int u = 0; u < NA - 1; ++u)
-            if (kt + u < nk) iter(kt + u, ra[(u + 1) % NA], ra[(u + 1) % NA]);
-        wait_vm_k<0>();                                       // the out-of-range tail ops
-    } else {
-        for (int kt = 0; kt < nk; kt += NA) {
-#pragma unroll
-            for (int u = 0; u < NA; ++u)
-                if (kt + u < nk) iter(kt + u, ra[(u + 1) % NA], ra[(u + 1) % NA]);
-        }
-    }
-    };
-    bool looped = false;
     if constexpr (S::NDMA % WAVES == 0) {
-        if (one && (a.dbg & 2048)) {
-            main_loop(std::integral_constant<int, 2>{});
-            looped = true;
-        }
-    }
-    if (!looped) {
-        if (one && !(a.dbg & 1024)) main_loop(std::integral_constant<int, 1>{});
-        else main_loop(std::integral_constant<int, 0>{});
+        if (one && a.gemm_1b) main_loop_1b();
+        else main_loop();
+    } else {
+        main_loop();
     }
     } else {
     // ---- one LDS stage: per tile, B(kt) DMA and the split A(kt) write, then
@@ -992,12 +900,11 @@ __global__ __launch_bounds__(NT, NT == 256 && BM == 256 ? 1 : 2) void conv_x6_ke
     }
     }
     if constexpr (TR) {
-        if (a.dbg & 1) {                               // timing experiment: main loop only
+        if (a.dbg & 1) {                               // timing-only (x6_dbg bit 0): main loop only
             if (acc[0][0][0] == 1234.5f) ((float*)a.y)[tid] = 1.f;
             return;
         }
-        if (a.dbg & 512) x6_epilogue_tr_r5<S>(a, acc, m0, n0, wm, wn, lane, (unsigned*)(smem + S::LDS));
-        else x6_epilogue_tr<S>(a, acc, m0, n0, wm, wn, lane, (unsigned*)(smem + S::LDS));
+        x6_epilogue_tr<S>(a, acc, m0, n0, wm, wn, lane, (unsigned*)(smem + S::LDS));
     } else {
         __syncthreads();
         x6_epilogue<S, MF>(a, acc, m0, n0, wm, wn, tid, lane, smem, S::LDS);
@@ -1062,7 +969,7 @@ __global__ __launch_bounds__(512, BN <= 64 ? 4 : 2) void conv_x6_halo_kernel(Con
     const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
     const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
     const int tn = wg % a.ntiles_n, tm = wg / a.ntiles_n;
-    const int m0 = a.mbase + tm * BM, n0 = tn * BN;
+    const int m0 = tm * BM, n0 = tn * BN;
     static_assert(!S2 || (NSB == 3 && S::NDMA % WAVES == 0), "stride-2 halo: three B stages, whole DMA rounds");
     const int W = a.yw, H = a.yh, HW = H * W;
     const int HR = S2 ? BM + W + 1 : BM + 2 * W + 2, HP = HR + 1;   // halo rows + one zero row (index HR)
@@ -1152,10 +1059,10 @@ __global__ __launch_bounds__(512, BN <= 64 ? 4 : 2) void conv_x6_halo_kernel(Con
     // where a step issues the DMA of step s + 2 (option x6_halo_dma, whole DMA rounds only):
     // 0 right after the step's barrier, 1 after its MFMAs, 2 one piece between MFMA groups
     constexpr int MYD = S::NDMA % WAVES == 0 ? S::NDMA / WAVES : 0;
-    const int hdma = MYD ? (a.dbg >> 3) & 3 : 0;
+    const int hdma = MYD ? a.halo_dma & 3 : 0;
     // timing-only skips (x6_dbg bits 2-5 via vdt_set_debug / x6bench; WRONG results): 1 no B DMA
     // past the prologue, 2 no halo reload, 8 no main-loop barriers
-    const int hdbg = (a.dbg >> 5) & 15;
+    const int hdbg = (a.dbg >> 2) & 15;
 
     // ---- per-lane A rows: this lane's output row of each fragment i, its halo row for
     // tap (0, 0) and which neighbours exist (bit 0 y-1, 1 y+1, 2 x-1, 3 x+1, 4 row < M)
@@ -1270,7 +1177,7 @@ __global__ __launch_bounds__(512, BN <= 64 ? 4 : 2) void conv_x6_halo_kernel(Con
     store_halo();
     if (tid < 8) *(u32x4*)(Ah + (tid >> 2) * PL_H + swzh(HR, tid & 3)) = u32x4{0u, 0u, 0u, 0u};
     dma_b(0, 0);
-    const bool one_bar = NSB == 2 && MYD > 0 && !(a.dbg & 4096);
+    const bool one_bar = NSB == 2 && MYD > 0 && a.halo_1b;
     if (nsteps > 1 && !one_bar) dma_b(1, 1);
     if (nhalo > 1) load_halo(1);
     // Per thread VMEM issue order: ... [halo loads of chunk c+2 at the end of step
@@ -1344,7 +1251,7 @@ __global__ __launch_bounds__(512, BN <= 64 ? 4 : 2) void conv_x6_halo_kernel(Con
                 if (s + 2 < nsteps) dma_b(s + 2, (s + 2) % 3);
             }
         }
-    } else if (MYD > 0 && !(a.dbg & 4096)) {
+    } else if (one_bar) {
         // two B stages, ONE barrier per step (option x6_halo_1b): B(s+1)'s DMA is issued
         // after step s's barrier (its stage was last read by step s-1, which every wave has
         // finished there); a halo refill (tap 8) takes a second barrier. Younger than B(s)
@@ -1397,8 +1304,7 @@ __global__ __launch_bounds__(512, BN <= 64 ? 4 : 2) void conv_x6_halo_kernel(Con
     }
     }
     if constexpr (TR) {
-        if (a.dbg & 512) x6_epilogue_tr_r5<S>(a, acc, m0, n0, wm, wn, lane, (unsigned*)(smem + amax_off));
-        else x6_epilogue_tr<S>(a, acc, m0, n0, wm, wn, lane, (unsigned*)(smem + amax_off));
+        x6_epilogue_tr<S>(a, acc, m0, n0, wm, wn, lane, (unsigned*)(smem + amax_off));
     } else {
         __syncthreads();
         x6_epilogue<S, 16>(a, acc, m0, n0, wm, wn, tid, lane, smem, amax_off);
@@ -1665,7 +1571,7 @@ void conv1x1_x6_kernel(ConvArgs a, int nchunks, int groups) {
             }
         }
         float vmax = 0.f;
-        if (a.dbg & 1) {                                   // timing experiment: no epilogue
+        if (a.dbg & 1) {                                   // timing-only (x6_dbg bit 0): no epilogue
             if (acc[0][0] == 1234.5f) ((float*)a.y)[tid] = 1.f;
         } else if (mu < a.M) {
             const int m = mu;
@@ -1910,10 +1816,8 @@ hipError_t launch_stream_x6(const ConvArgs& a, hipStream_t s) {
     // option x6_stream_rl (default 1): the RL form for the layers with a residual (layer3
     // conv3 330 -> 299 us, layer2 conv3 416 -> 404 in x6bench); without one it measured
     // slower (layer2.0 conv1 577 -> 603), so those keep the two-set form
-    if constexpr (!TAPS && !RL && NTT >= 2 && TERMS == 2) {
-        // x6_stream_rl 2: also the layers without a residual
-        if (a.tune && (RES != VD_RES_NONE ? a.tune->x6_stream_rl : a.tune->x6_stream_rl >= 2))
-            return launch_stream_x6<KS, NTT, ACT, RES, TERMS, false, true>(a, s);
+    if constexpr (!TAPS && !RL && NTT >= 2 && TERMS == 2 && RES != VD_RES_NONE) {
+        if (a.tune && a.tune->x6_stream_rl) return launch_stream_x6<KS, NTT, ACT, RES, TERMS, false, true>(a, s);
     }
     constexpr int NCH = 16 * NTT;
     constexpr int lds = (TERMS == 1 ? 2 : TERMS) * KS * NCH * 64 + 2 * NCH * 4;
@@ -2007,21 +1911,15 @@ bool vd_conv_x6_ok(const ConvArgs& a) {
            xbytes < 2147483647.0;
 }
 
-// rows [mbase, M) of the conv (mbase a multiple of the caller's tile rows)
-template <int BM, int BN, int NT, int NST, int TERMS, int MF = 16, int NA = 2, bool TR = false, bool PF = false>
-static hipError_t launch_x6(const ConvArgs& a0, hipStream_t s, int mbase = 0, int mtiles = -1) {
-    if constexpr (NA == 2 && BM == 256 && BN <= 128 && NST == 2 && TERMS == 2 && MF == 16 && !TR && !PF) {
-        // option x6_adepth: four A register sets (three K tiles of A loads in flight) on
-        // the 256 x {128, 64, 32} tiles, whose accumulators leave the registers for them
-        if (a0.tune && a0.tune->x6_adepth >= 4) return launch_x6<BM, BN, NT, NST, TERMS, MF, 4>(a0, s, mbase, mtiles);
-    }
-    if constexpr (!PF && MF == 16 && NST == 2 && X6Shape<BM, BN, NT, NST, TERMS, MF>::TN > X6Shape<BM, BN, NT, NST, TERMS, MF>::TM) {
-        // option x6_gemm_pf: the wide-wave tiles with pipelined B-fragment reads
-        if (a0.tune && a0.tune->x6_gemm_pf) return launch_x6<BM, BN, NT, NST, TERMS, MF, NA, TR, true>(a0, s, mbase, mtiles);
-    }
+template <int BM, int BN, int NT, int NST, int TERMS, int MF = 16, bool TR = false, bool PF = false>
+static hipError_t launch_x6(const ConvArgs& a0, hipStream_t s) {
     using S = X6Shape<BM, BN, NT, NST, TERMS, MF>;
+    if constexpr (!PF && MF == 16 && NST == 2 && S::TN > S::TM) {
+        // option x6_gemm_pf: the wide-wave tiles with pipelined B-fragment reads
+        if (a0.tune && a0.tune->x6_gemm_pf) return launch_x6<BM, BN, NT, NST, TERMS, MF, TR, true>(a0, s);
+    }
     static const bool attr = [] {
-        (void)hipFuncSetAttribute((const void*)conv_x6_kernel<BM, BN, NT, NST, TERMS, MF, NA, TR, PF>,
+        (void)hipFuncSetAttribute((const void*)conv_x6_kernel<BM, BN, NT, NST, TERMS, MF, TR, PF>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, S::LDS + 4 * kAmaxFrames);
         return true;
     }();
@@ -2029,47 +1927,10 @@ static hipError_t launch_x6(const ConvArgs& a0, hipStream_t s, int mbase = 0, in
     ConvArgs a = a0;
     a.w = a.wx3;                                   // the kernel reads the split planes
     a.ntiles_n = (a.cout + BN - 1) / BN;
-    a.mbase = mbase;
-    const int mt = mtiles >= 0 ? mtiles : (a.M - mbase + BM - 1) / BM;
+    const int mt = (a.M + BM - 1) / BM;
     const int lds = S::LDS + (a.ymax ? 4 * a.B : 0);
-    hipLaunchKernelGGL((conv_x6_kernel<BM, BN, NT, NST, TERMS, MF, NA, TR, PF>), dim3(mt * a.ntiles_n), dim3(NT), lds, s, a);
+    hipLaunchKernelGGL((conv_x6_kernel<BM, BN, NT, NST, TERMS, MF, TR, PF>), dim3(mt * a.ntiles_n), dim3(NT), lds, s, a);
     return hipGetLastError();
-}
-
-static int device_cus() {
-    static const int cus = [] {
-        int dev = 0, n = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return std::max(1, n);
-    }();
-    return cus;
-}
-
-// The 256 x BN two-stage tile runs one workgroup per CU, so a grid of R full rounds
-// plus a partial one leaves most CUs idle during the last round (400 tiles of layer3:
-// 1.56 rounds on 256 CUs take 2). Tail split: the whole rounds as usual, then the
-// remaining rows in one more launch of a narrower tile (BN / 2 or BN / 4 columns),
-// 2-4x as many workgroups, each a fraction of the time. Splitting N (never K) leaves
-// every output's sum in the same K order on the same MFMA form, so the result is
-// bit-identical to the unsplit launch.
-template <int BN, int TERMS, int MF = 16>
-static hipError_t launch_x6_big(const ConvArgs& a, hipStream_t s) {
-    const int tail = a.tune ? a.tune->x6_tail : 0;
-    const int nt = (a.cout + BN - 1) / BN, mt = (a.M + 255) / 256;
-    const int slots = a.tune && a.tune->x6_slots > 0 ? a.tune->x6_slots : device_cus();
-    const long total = (long)mt * nt;
-    if (TERMS != 2 || MF != 16 || !tail || total <= slots || total % slots == 0 || slots % nt) {
-        return launch_x6<256, BN, 512, 2, TERMS, MF>(a, s);
-    }
-    const int mt_main = (int)(total / slots) * (slots / nt);
-    if (mt_main <= 0 || mt_main >= mt) return launch_x6<256, BN, 512, 2, TERMS, MF>(a, s);
-    hipError_t e = launch_x6<256, BN, 512, 2, TERMS, MF>(a, s, 0, mt_main);
-    if (e != hipSuccess) return e;
-    const int mb = mt_main * 256;
-    constexpr int BN1 = BN == 192 ? 64 : BN / 2, BN2 = BN == 192 ? 64 : BN / 4;
-    if (tail == 1 || BN2 < 32) return launch_x6<256, BN1, 512, 2, TERMS, MF>(a, s, mb);
-    return launch_x6<256, BN2, 512, 2, TERMS, MF>(a, s, mb);
 }
 
 template <int BN, int NSB>
@@ -2084,7 +1945,6 @@ static hipError_t launch_x6_halo_pf(const ConvArgs& a0, hipStream_t s) {
     ConvArgs a = a0;
     a.w = a.wx3;
     a.ntiles_n = (a.cout + BN - 1) / BN;
-    a.mbase = 0;
     static const bool attr = [] {
         (void)hipFuncSetAttribute((const void*)conv_x6_halo_kernel<BN, NSB, TR, S2, PF>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -2186,9 +2046,9 @@ static hipError_t launch_tr(const ConvArgs& a, hipStream_t s) {
     const long t256 = (long)((a.M + 255) / 256) * (a.cout / 256);
     // (Measured and not kept, round 6: Cout >= 512 1x1 layers with K <= 512-2048 on the
     // 128 x 128 tile at two workgroups per CU -- level to 8 % slower, tools/runs/r06y.sh)
-    if (a.cout % 256 == 0 && t256 >= 192) return launch_x6<256, 256, 512, 2, 2, 16, 2, true>(a, s);
-    if (a.cout == 128 && a.tune->x6_mid && a.kpad <= a.tune->x6_mid) return launch_x6<128, 128, 256, 2, 2, 16, 2, true>(a, s);
-    return launch_x6<256, 128, 512, 2, 2, 16, 2, true>(a, s);
+    if (a.cout % 256 == 0 && t256 >= 192) return launch_x6<256, 256, 512, 2, 2, 16, true>(a, s);
+    if (a.cout == 128 && a.tune->x6_mid && a.kpad <= a.tune->x6_mid) return launch_x6<128, 128, 256, 2, 2, 16, true>(a, s);
+    return launch_x6<256, 128, 512, 2, 2, 16, true>(a, s);
 }
 
 template <int TERMS>
@@ -2219,11 +2079,6 @@ static hipError_t launch_terms(const ConvArgs& a0, hipStream_t s) {
 #undef VD_SILU
             }
         }
-    }
-    if constexpr (TERMS == 2) {
-        // option x6_gemm1x1 = 2 (experiments): the K <= 256 layers of the streaming form on the
-        // TR tiles as well (measured 20-35 % slower than the streaming form)
-        if (a.tune && a.tune->x6_gemm1x1 == 2 && x6_tr_ok(a)) return launch_tr(a, s);
     }
     if (const int nch = stream_x6_nch(a, TERMS)) {
         if constexpr (TERMS == 2) {   // 256-channel slices: each pixel read by half as many workgroups
@@ -2280,25 +2135,20 @@ static hipError_t launch_terms(const ConvArgs& a0, hipStream_t s) {
         if (a.tune && a.tune->x6_bn256 && a.cout % 256 == 0 && t256 >= 192) {
             if (x6_halo_ok(a)) return launch_x6_halo<256>(a, s);
             if (a.tune->x6_mf32) return launch_x6<256, 256, 512, 2, TERMS, 32>(a, s);
-            return launch_x6_big<256, TERMS>(a, s);
+            return launch_x6<256, 256, 512, 2, TERMS>(a, s);
         }
         // Cout 192 (the fused SSH conv5X5_1 + conv3X3): one 192-wide N tile instead of two
         // 128-wide ones with a quarter of the MFMAs on padding rows (level 0 1716 -> 1264 us,
         // level 1 526 -> 396; not for level 2's 100 tiles: 137 -> 178)
         if (a.tune && a.tune->x6_bn256 && a.cout == 192 && (a.M + 255) / 256 >= 192) {
             if (x6_halo_ok(a)) return launch_x6_halo<192>(a, s);
-            return launch_x6_big<192, TERMS>(a, s);
+            return launch_x6<256, 192, 512, 2, TERMS>(a, s);
         }
-        // every eligible layer on the halo form whatever the batch (its K order differs);
-        // option x6_halo_n64: Cout-128 layers with K <= x6_halo_n64 as two 64-wide N tiles,
-        // two workgroups per CU (one's prologue / epilogue beside the other's main loop)
-        if (x6_halo_ok(a)) {
-            if (a.tune && a.cout == 128 && a.kpad <= a.tune->x6_halo_n64 && a.stride == 1) return launch_x6_halo<64>(a, s);
-            return launch_x6_halo<128>(a, s);
-        }
+        // every eligible layer on the halo form whatever the batch (its K order differs)
+        if (x6_halo_ok(a)) return launch_x6_halo<128>(a, s);
         if (a.tune && a.tune->x6_mf32) return launch_x6<256, 128, 512, 2, TERMS, 32>(a, s);
     }
-    return launch_x6_big<128, TERMS>(a, s);
+    return launch_x6<256, 128, 512, 2, TERMS>(a, s);
 }
 
 // fp16 pairs: bottleneck conv3 (1x1, K 64 / 128, ReLU) + downsample (1x1, K 64 / 256,
@@ -2316,10 +2166,11 @@ bool vd_conv1x1_x6_dual_ok(const ConvArgs& a) {
 
 hipError_t vd_launch_conv_x6(const ConvArgs& a0, hipStream_t s) {
     ConvArgs a = a0;
-    a.dbg = a.tune ? (a.tune->x6_dbg & 3) | (a.tune->x6_one ? 4 : 0) | ((a.tune->x6_halo_dma & 3) << 3) |
-                     (((a.tune->x6_dbg >> 2) & 15) << 5) | (a.tune->x6_tr_epi ? 0 : 512) |
-                     (a.tune->x6_gemm_uni ? 0 : 1024) | (a.tune->x6_gemm_uni == 2 ? 2048 : 0) |
-                     (a.tune->x6_halo_1b ? 0 : 4096) : 0;
+    a.one = a.tune && a.tune->x6_one;
+    a.halo_dma = a.tune ? a.tune->x6_halo_dma & 3 : 0;
+    a.gemm_1b = a.tune && a.tune->x6_gemm_uni == 2;
+    a.halo_1b = a.tune && a.tune->x6_halo_1b;
+    a.dbg = a.tune ? a.tune->x6_dbg & 0x3d : 0;        // timing-only skips: bits 0 and 2-5
     if (a.grp_co) {   // grouped: the halo form only, one 64-wide N tile per group
         if (a.grp_co != 64 || a.f32_split != 2 || !a.wx3 || !a.tune || !x6_halo_ok(a) || (a.ymax && a.B > kAmaxFrames))
             return hipErrorInvalidValue;

@@ -1124,18 +1124,39 @@ int vd_set_option(vd_ctx* h, const char* name, int value) {
         {"conv_dual", &VdTune::conv_dual}, {"conv_taps", &VdTune::conv_taps}, {"conv_n192", &VdTune::conv_n192},
         {"conv_small", &VdTune::conv_small}, {"conv_big", &VdTune::conv_big},
         {"conv_big_kmin", &VdTune::conv_big_kmin}, {"stream_ntt", &VdTune::stream_ntt},
-        {"lb_pair", &VdTune::lb_pair}, {"mosaic_map", &VdTune::mosaic_map}, {"mosaic_nt", &VdTune::mosaic_nt}, {"mosaic_cells", &VdTune::mosaic_cells}, {"mosaic_fused", &VdTune::mosaic_fused}, {"mosaic_rows", &VdTune::mosaic_rows}, {"mosaic_gather", &VdTune::mosaic_gather}, {"block_fuse", &VdTune::block_fuse},
-        {"chain", &VdTune::chain}, {"stem_pool", &VdTune::stem_pool}, {"ssh_fuse", &VdTune::ssh_fuse},
-        {"plate_s2d", &VdTune::plate_s2d}, {"f32_split", &VdTune::f32_split},
-        {"x6_small_k", &VdTune::x6_small_k}, {"x6_small_tiles", &VdTune::x6_small_tiles},
-        {"x6_stream", &VdTune::x6_stream}, {"x6_small_k2", &VdTune::x6_small_k2}, {"x6_bn256", &VdTune::x6_bn256},
-        {"x6_exact", &VdTune::x6_exact}, {"x6_mid", &VdTune::x6_mid}, {"block_fuse32", &VdTune::block_fuse32}, {"x6_mf32", &VdTune::x6_mf32}, {"x6_tail", &VdTune::x6_tail}, {"x6_stream_silu", &VdTune::x6_stream_silu}, {"x6_stream_rl", &VdTune::x6_stream_rl}, {"x6_gemm_uni", &VdTune::x6_gemm_uni}, {"x6_halo_1b", &VdTune::x6_halo_1b}, {"x6_slots", &VdTune::x6_slots}, {"x6_halo", &VdTune::x6_halo}, {"x6_halo_narrow", &VdTune::x6_halo_narrow}, {"x6_halo_s2", &VdTune::x6_halo_s2}, {"x6_adepth", &VdTune::x6_adepth}, {"x6_gemm1x1", &VdTune::x6_gemm1x1}, {"x6_taps", &VdTune::x6_taps}, {"x6_halo_tr", &VdTune::x6_halo_tr}, {"x6_tr_epi", &VdTune::x6_tr_epi}, {"x6_halo_dma", &VdTune::x6_halo_dma}, {"x6_halo_pf", &VdTune::x6_halo_pf}, {"x6_halo_n64", &VdTune::x6_halo_n64}, {"x6_gemm_pf", &VdTune::x6_gemm_pf}, {"x6_stream256", &VdTune::x6_stream256}, {"plate_stage", &VdTune::plate_stage}, {"plate_detect_early", &VdTune::plate_detect_early}, {"mosaic_early", &VdTune::mosaic_early}, {"ssh_side", &VdTune::ssh_side}, {"face_groups", &VdTune::face_groups}, {"plate_s2d32", &VdTune::plate_s2d32}, {"det_group", &VdTune::det_group}, {"chain_gpw", &VdTune::chain_gpw}, {"block32_xd", &VdTune::block32_xd}, {"block32_pipe", &VdTune::block32_pipe}, {"x6_one", &VdTune::x6_one},
-        {"jenc_gpu", &VdTune::jenc_gpu}, {"jdec_gpu", &VdTune::jdec_gpu}, {"jdec_chunk", &VdTune::jdec_chunk}, {"jdec_sync", &VdTune::jdec_sync}, {"jdec_group", &VdTune::jdec_group},
+        {"lb_pair", &VdTune::lb_pair}, {"mosaic_map", &VdTune::mosaic_map}, {"mosaic_nt", &VdTune::mosaic_nt},
+        {"mosaic_cells", &VdTune::mosaic_cells}, {"mosaic_fused", &VdTune::mosaic_fused},
+        {"mosaic_rows", &VdTune::mosaic_rows}, {"mosaic_gather", &VdTune::mosaic_gather},
+        {"block_fuse", &VdTune::block_fuse}, {"block_fuse32", &VdTune::block_fuse32},
+        {"block32_xd", &VdTune::block32_xd}, {"block32_pipe", &VdTune::block32_pipe}, {"chain", &VdTune::chain},
+        {"chain_gpw", &VdTune::chain_gpw}, {"stem_pool", &VdTune::stem_pool}, {"ssh_fuse", &VdTune::ssh_fuse},
+        {"ssh_side", &VdTune::ssh_side},
+        {"plate_s2d", &VdTune::plate_s2d}, {"plate_s2d32", &VdTune::plate_s2d32},
+        {"plate_stage", &VdTune::plate_stage}, {"plate_detect_early", &VdTune::plate_detect_early},
+        {"mosaic_early", &VdTune::mosaic_early}, {"face_groups", &VdTune::face_groups},
+        {"det_group", &VdTune::det_group}, {"f32_split", &VdTune::f32_split},
+        {"x6_small_k", &VdTune::x6_small_k}, {"x6_small_k2", &VdTune::x6_small_k2},
+        {"x6_small_tiles", &VdTune::x6_small_tiles}, {"x6_bn256", &VdTune::x6_bn256},
+        {"x6_exact", &VdTune::x6_exact}, {"x6_mid", &VdTune::x6_mid}, {"x6_mf32", &VdTune::x6_mf32},
+        {"x6_one", &VdTune::x6_one},
+        {"x6_stream", &VdTune::x6_stream}, {"x6_stream_silu", &VdTune::x6_stream_silu},
+        {"x6_stream_rl", &VdTune::x6_stream_rl}, {"x6_stream256", &VdTune::x6_stream256},
+        {"x6_taps", &VdTune::x6_taps},
+        {"x6_gemm1x1", &VdTune::x6_gemm1x1}, {"x6_gemm_uni", &VdTune::x6_gemm_uni},
+        {"x6_gemm_pf", &VdTune::x6_gemm_pf},
+        {"x6_halo", &VdTune::x6_halo}, {"x6_halo_narrow", &VdTune::x6_halo_narrow},
+        {"x6_halo_s2", &VdTune::x6_halo_s2}, {"x6_halo_tr", &VdTune::x6_halo_tr},
+        {"x6_halo_dma", &VdTune::x6_halo_dma}, {"x6_halo_pf", &VdTune::x6_halo_pf},
+        {"x6_halo_1b", &VdTune::x6_halo_1b},
+        {"jenc_gpu", &VdTune::jenc_gpu}, {"jdec_gpu", &VdTune::jdec_gpu}, {"jdec_chunk", &VdTune::jdec_chunk},
+        {"jdec_sync", &VdTune::jdec_sync}, {"jdec_group", &VdTune::jdec_group},
     };
     for (const Opt& o : opts)
         if (strcmp(o.n, name) == 0) {
             if (!strcmp(name, "stream_ntt") && value != 8 && value != 16)
                 return vd_set_error(VD_ERR_ARG, "stream_ntt must be 8 or 16");
+            if (!strcmp(name, "x6_gemm_uni") && value != 0 && value != 2)
+                return vd_set_error(VD_ERR_ARG, "x6_gemm_uni must be 0 or 2");
             ctx->tune.*(o.f) = value;
             return VD_OK;
         }

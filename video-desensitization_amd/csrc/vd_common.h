@@ -96,7 +96,6 @@ struct VdTune {
     int x6_stream = 1;        // fp32 split: streaming 1x1 kernel for K in {64, 128, 256}
     int x6_stream_rl = 1;     //   streaming 1x1 with a residual: one input register set refilled per k-step, the
                               //   residual loaded at the top of each pixel group (beside the MFMAs), not in the epilogue
-                              //   (2: also the layers without a residual -- measured level, r06ag)
     int x6_stream_silu = 1;   //   fp16 pairs: also SiLU 1x1 convs (YOLO C2f / SPPF) with K in {32..256}
     int x6_stream256 = 2;     //   fp16 pairs, Cout % 256 == 0: 256-channel slices for K = 64 (2: and K = 128;
                               //   each pixel read by half as many workgroups: faces 27.31 -> 26.96 ms/step)
@@ -107,35 +106,26 @@ struct VdTune {
     int x6_exact = 1;         // fp16 pairs: one A plane for inputs exact in fp16 (the face stem)
     int x6_mid = 512;         // fp16 pairs: 1x1 Cout-128 convs with K <= this on the 128 x 128 two-stage tile (0: off)
     int x6_mf32 = 0;          // fp16 pairs: 256 x {256,128} tiles on v_mfma_f32_32x32x16_f16 (else 16x16x32)
-    int x6_tail = 0;          // fp16 pairs, big tiles: rows past the last full round of 256-row tiles on
-                              //   narrower tiles (1: BN/2, 2: BN/4 columns, 0: off); N splits keep every
-                              //   output's K order, so results do not depend on the split. Measured
-                              //   slower (27.6 -> 28.5 / 28.9 ms per step for 1 / 2): the narrow tiles
-                              //   fetch more per FLOP, and a partial round's workgroups run faster alone
     int x6_halo = 2;          // fp16 pairs, 3x3 stride-1 convs: input split once per 32-channel chunk
                               //   over the tile's linear halo (conv_x6_halo_kernel); 2: three B stages, 1: two
     int x6_halo_narrow = 1;   // ... also for Cout <= 64 (N tiles of 32 / 64)
     int x6_halo_s2 = 1;       // ... also 3x3 stride-2 convs (phase halos; Cout > 32)
-    int x6_adepth = 2;        // A register sets of the 256 x {128, 64, 32} fp16-pair tiles (2 or 4; 4 measured level)
-    int x6_slots = 0;         //   workgroup slots of one round (0: the CU count; tests force small values)
     int x6_halo_1b = 1;       // halo tiles with two B stages (wide frames): one barrier per step (0: two)
-    int x6_gemm_uni = 2;      // 1x1 GEMM two-stage loop: the same loads / DMAs every K tile (past the end: the
-                              //   last tile again), so the compiler's register waits stay off the next tile
-                              //   (0: round-5 loop; 2: also one barrier per K tile)
+    int x6_gemm_uni = 2;      // 1x1 GEMM two-stage loop: 2 = the same loads / DMAs every K tile (past the end: the
+                              //   last tile again), so the compiler's register waits stay off the next tile, and
+                              //   one barrier per K tile; 0 = the general loop (vd_set_option refuses 1)
     int x6_gemm_pf = 1;       // GEMM tiles with wide wave tiles (TN > TM): the same pipelined B-fragment reads
-    int x6_halo_n64 = 0;      //   halo tiles: Cout-128 3x3 layers with K <= this as two 64-wide N tiles (0: off)
     int x6_halo_pf = 1;       //   halo tiles (128-256 wide): B fragments of block j + 1 read before block j's MFMAs
     int x6_halo_dma = 2;      //   halo tiles: where a K step issues the B DMA two steps ahead (0 after the
                               //   barrier, 1 after the step's MFMAs, 2 one piece between MFMA groups)
-    int x6_tr_epi = 1;        // TR register epilogue: 1 = residual / BN rows of column pair jp + 1 loaded before pair
-                              //   jp's stores (buffer ops, straight-line), 0 = the round-5 row-by-row form
     int x6_halo_tr = 2;       // fp32 plan: halo 3x3 tiles with D^T accumulators and the register epilogue
                               //   (1: the 128-256-wide tiles, 2: all; bit-identical)
     int x6_one = 1;           // fp16 pairs, GEMM tiles: 1x1 convs load A at row offset + scalar K offset (no tap stepping)
     int x6_taps = 1;          // fp32 plan: narrow KxK YOLO layers (K <= 288) on the streaming TAPS form
-    int x6_gemm1x1 = 1;       // fp16 pairs: GEMM 1x1 convs on the TR tiles (D^T accumulators, register epilogue;
-                              //   2: also the streaming form's K <= 256 layers, 0: off)
-    int x6_dbg = 0;           // experiments (vdt_set_debug / tools/x6bench): 1 = no epilogue (WRONG results), 2 = runtime vmcnt waits
+    int x6_gemm1x1 = 1;       // fp16 pairs: GEMM 1x1 convs on the TR tiles (D^T accumulators, register epilogue; 0: off)
+    int x6_dbg = 0;           // timing-only (vdt_set_debug / tools/x6bench, never vd_set_option; WRONG results): bit 0 = no
+                              //   epilogue; halo tiles: bit 2 = no B DMA past the prologue, 3 = no halo reload, 5 = no
+                              //   main-loop barriers
     int f32_split = 2;        // plan (fp32, at weight load): 2 = operands scaled by powers of two
                               //   and split into fp16 pairs, 3 products on the f16 matrix cores;
                               //   1 = exact 3-term bf16 split, 6 products (conv_x6.hip);
@@ -176,9 +166,12 @@ struct ConvArgs {
     const void* wx3_2; const float* scale2_x;
     const unsigned* x2max; float x2bound;
     int x_exact;                                 // fp16 pairs: input values exact in fp16 (integer canvas)
-    int mbase;                                   // conv_x6 tiles: first output row of the launch (tail split)
-    int dbg;                                     // VdTune::x6_dbg (bits 0-1, timing experiments; 0 in production),
-                                                 // bit 2: VdTune::x6_one, bits 3-4: VdTune::x6_halo_dma
+    // conv_x6 tiles: the schedule selectors of VdTune, filled by vd_launch_conv_x6 (results do not depend on them)
+    int one;                                     //   x6_one: 1x1 A loads at row offset + scalar K offset
+    int halo_dma;                                //   x6_halo_dma: where a halo step issues the B DMA (0-2)
+    int gemm_1b;                                 //   x6_gemm_uni == 2: 1x1 convs on the one-barrier K loop
+    int halo_1b;                                 //   x6_halo_1b: two-stage halo tiles with one barrier per step
+    int dbg;                                     // timing-only skips (VdTune::x6_dbg bits 0, 2-5; WRONG results; 0 in production)
     int grp_co, grp_ci;                          // grouped conv (fp32 halo tiles): output channels n read input
                                                  //   channels (n / grp_co) * grp_ci + [0, cin); 0: dense
 };
