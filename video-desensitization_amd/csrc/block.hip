@@ -24,31 +24,16 @@
 //            registers, 16-B stores of 8 consecutive channels per lane.
 // LDS: W1 image (CIN x 64) + t1 (192 x 64) + t2 (128 x 64) bf16 + BN tables, 54-75 KB:
 // two workgroups per CU, so one tile's loads overlap the other's MFMAs.
-#include "vd_common.h"
+#include "vd_kernel.h"
 
 #include <cstdlib>
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int TH = 8, TW = 16;                  // output tile
 constexpr int HWD = TW + 2;                     // halo width
 constexpr int HROWS = (TH + 2) * HWD;           // 180 halo pixels
 constexpr int P = 64, CO = 256;                 // bottleneck width, output channels
-
-// t1 / t2 images: 128-B rows of 64 channels, 16-B chunk c of row r at chunk
-// c ^ (2 * ((r >> 1) & 3)). Conflict-free ds_read_b128 for ANY 16 consecutive rows
-// (stage 2 reads windows shifted by the tap offsets): each 16-lane LDS group holds
-// all 16 rows once, 8 of them at chunk c and 8 at c ^ 1 in a cyclic block of 4 row
-// pairs, and this XOR keeps the 8 even (and the 8 odd) rows on distinct 16-B slots
-// for every block position (exhaustive check; the (r >> 1) & 7 swizzle is 2-way here)
-__device__ __forceinline__ int lds_off(int row, int chunk) {
-    return row * 128 + ((chunk ^ (((row >> 1) & 3) << 1)) << 4);
-}
-
-typedef __attribute__((address_space(3))) void lds_void_t;
 
 // physical 16-B chunk of logical chunk c in row r of the x halo image: 512-B rows
 // (CIN 256) XOR the low 4 chunk bits with r&15, 128-B rows (CIN 64) with (r>>1)&7 --
@@ -58,9 +43,6 @@ __device__ __forceinline__ int lx_chunk(int r, int c) {
     if constexpr (CIN == 256) return c ^ (r & 15);
     else return c ^ ((r >> 1) & 7);
 }
-
-constexpr int VMCNT0 = 0x0F70;                  // s_waitcnt vmcnt(0) (expcnt / lgkmcnt: no wait)
-constexpr int VMCNT8 = 0x0F78;                  // s_waitcnt vmcnt(8)
 
 // F16: the fp16 plan (VD_PREC_FP16) -- the same kernel on fp16 operands / activations
 template <int CIN, bool DS, bool F16>
@@ -207,7 +189,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck_kernel(BlockArgs a) {
         // vmcnt counts loads, stores and LDS-DMA together in issue order: the previous
         // tile's 8 output stores per thread are the only ops younger than this tile's x
         // DMA (and the W1 reload), so vmcnt(8) has them landed without waiting for the stores
-        __builtin_amdgcn_s_waitcnt(VMCNT8);
+        __builtin_amdgcn_s_waitcnt(vmcnt_imm(8));
         VD_STAMP(0);
         __syncthreads();
         VD_STAMP(1);
@@ -243,7 +225,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck_kernel(BlockArgs a) {
                 const float v2 = acc[k][2] * s1v.z + h1v.z, v3 = acc[k][3] * s1v.w + h1v.w;
                 const t16x4_t o = {(E16)(in && v0 > 0.f ? v0 : 0.f), (E16)(in && v1 > 0.f ? v1 : 0.f),
                                    (E16)(in && v2 > 0.f ? v2 : 0.f), (E16)(in && v3 > 0.f ? v3 : 0.f)};
-                *(t16x4_t*)(lt1 + lds_off(r, 2 * jn + (g >> 1)) + (g & 1) * 8) = o;
+                *(t16x4_t*)(lt1 + swz128_any(r, 2 * jn + (g >> 1)) + (g & 1) * 8) = o;
             }
         }
         // the stage-3 identity, x at this wave's 32 channels for the 8 tile rows, taken
@@ -280,7 +262,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck_kernel(BlockArgs a) {
 #define VD_T1READ(Q)                                                                               \
             do {                                                                                   \
                 const int hh_ = (Q) / 6, hf_ = ((Q) / 3) & 1, dx_ = (Q) % 3;                       \
-                tf[(Q) % (PD + 1)] = *(const u32x4*)(lt1 + lds_off((4 * half + hh_) * HWD + li + dx_, 4 * hf_ + g)); \
+                tf[(Q) % (PD + 1)] = *(const u32x4*)(lt1 + swz128_any((4 * half + hh_) * HWD + li + dx_, 4 * hf_ + g)); \
             } while (0)
 #pragma unroll
             for (int q = 0; q < PD; ++q) VD_T1READ(q);
@@ -307,7 +289,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck_kernel(BlockArgs a) {
                 const float v2 = acc[m][2] * s2v.z + h2v.z, v3 = acc[m][3] * s2v.w + h2v.w;
                 const t16x4_t o = {(E16)(v0 > 0.f ? v0 : 0.f), (E16)(v1 > 0.f ? v1 : 0.f),
                                    (E16)(v2 > 0.f ? v2 : 0.f), (E16)(v3 > 0.f ? v3 : 0.f)};
-                *(t16x4_t*)(lt2 + lds_off(16 * (4 * half + m) + li, 2 * jn + (g >> 1)) + (g & 1) * 8) = o;
+                *(t16x4_t*)(lt2 + swz128_any(16 * (4 * half + m) + li, 2 * jn + (g >> 1)) + (g & 1) * 8) = o;
             }
         }
         VD_STAMP(4);
@@ -330,7 +312,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck_kernel(BlockArgs a) {
 #define VD_T2READ(M, BUF)                                                                          \
             do {                                                                                   \
                 _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_)                                   \
-                    fr[BUF][s_] = *(const u32x4*)(lt2 + lds_off(16 * (M) + li, 4 * s_ + g));       \
+                    fr[BUF][s_] = *(const u32x4*)(lt2 + swz128_any(16 * (M) + li, 4 * s_ + g));   \
                 if constexpr (DS) {   /* downsample input: the tile's own pixels from LX */        \
                     const int r_ = ((M) + 1) * HWD + li + 1;                                       \
                     _Pragma("unroll") for (int s_ = 0; s_ < KS1; ++s_)                             \

@@ -39,12 +39,9 @@
 //            per lane, per-frame max |out| into the output's slots.
 // LDS: W1 planes (CIN x 64 x 2 fp16, 16 / 64 KB) + t1 planes (192 x 64 x 2 fp16, 48 KB)
 // + t2 planes (128 x 64 x 2 fp16, 32 KB; the stage-2 partials before that) + BN tables.
-#include "vd_common.h"
+#include "vd_kernel.h"
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int TH = 8, TW = 16;                  // output tile
 constexpr int HWD = TW + 2;                     // halo width
@@ -52,63 +49,6 @@ constexpr int HROWS = (TH + 2) * HWD;           // 180 halo pixels
 constexpr int CO = 256;
 constexpr int T1PL = 192 * 128;                 // one t1 plane: 192 rows x 64 fp16
 constexpr int T2PL = 128 * 128;                 // one t2 plane
-
-// 128-B rows of 64 fp16 channels, 16-B chunk c of row r at c ^ (2 * ((r >> 1) & 3)):
-// conflict-free ds_read_b128 for any 16 consecutive rows (block.hip)
-__device__ __forceinline__ int lds_off(int row, int chunk) {
-    return row * 128 + ((chunk ^ (((row >> 1) & 3) << 1)) << 4);
-}
-// 64-B rows (32 fp16 of one k-step) of the W1 image: conv_x6.hip's swizzle
-__device__ __forceinline__ int swz64(int row, int chunk) { return row * 64 + ((chunk ^ (((row >> 3) & 1) * 3)) << 4); }
-
-__device__ __forceinline__ f32x4_t mfma_pair(const u32x4 (&a)[2], const u32x4 (&b)[2], f32x4_t acc) {
-    // (a_hi + a_lo)(b_hi + b_lo) without a_lo b_lo, small terms first
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a[1]), __builtin_bit_cast(f16x8_t, b[0]),
-                                                 acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a[0]), __builtin_bit_cast(f16x8_t, b[1]),
-                                                 acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a[0]), __builtin_bit_cast(f16x8_t, b[0]),
-                                                 acc, 0, 0, 0);
-    return acc;
-}
-
-// 8 f32 (already in registers as two u32x4) -> fp16 hi / lo planes of x * sa
-__device__ __forceinline__ void split8(const u32x4& a, const u32x4& b, float sa, u32x4 (&o)[2]) {
-    unsigned h[8], l[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float x = __uint_as_float(j < 4 ? a[j] : b[j - 4]);
-        const _Float16 x0 = (_Float16)__builtin_fmaf(x, sa, 0.f);
-        const _Float16 x1 = (_Float16)__builtin_fmaf(x, sa, -(float)x0);
-        h[j] = __builtin_bit_cast(unsigned short, x0);
-        l[j] = __builtin_bit_cast(unsigned short, x1);
-    }
-    o[0] = u32x4{h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
-    o[1] = u32x4{l[0] | (l[1] << 16), l[2] | (l[3] << 16), l[4] | (l[5] << 16), l[6] | (l[7] << 16)};
-}
-
-// 4 f32 -> 4 fp16 hi and 4 fp16 lo (8 B each)
-__device__ __forceinline__ void split4(const float (&v)[4], float sa, u32x2& hi, u32x2& lo) {
-    unsigned h[4], l[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const _Float16 x0 = (_Float16)__builtin_fmaf(v[j], sa, 0.f);
-        const _Float16 x1 = (_Float16)__builtin_fmaf(v[j], sa, -(float)x0);
-        h[j] = __builtin_bit_cast(unsigned short, x0);
-        l[j] = __builtin_bit_cast(unsigned short, x1);
-    }
-    hi = u32x2{h[0] | (h[1] << 16), h[2] | (h[3] << 16)};
-    lo = u32x2{l[0] | (l[1] << 16), l[2] | (l[3] << 16)};
-}
-
-// power-of-two exponent k with m * 2^k in [2^14, 2^15) (act_scale_exp's rule)
-__device__ __forceinline__ int scale_exp(float m) {
-    if (!(m > 0.f) || !(m < 3.0e38f)) return 0;
-    int e;
-    (void)frexpf(m, &e);
-    const int k = 15 - e;
-    return k < -100 ? -100 : (k > 100 ? 100 : k);
-}
 
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
@@ -211,7 +151,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck32_kernel(Block32Args a) {
         const int b = t / tpf, r0 = t - b * tpf;
         const int ty = r0 / a.tiles_x, tx = r0 - ty * a.tiles_x;
         const int oy0 = ty * TH, ox0 = tx * TW;
-        const int kx = scale_exp(__uint_as_float(a.xmax[b]));
+        const int kx = act_scale_exp_of(__uint_as_float(a.xmax[b]));
         const float sax = __builtin_ldexpf(1.f, kx), invx = __builtin_ldexpf(1.f, -kx);
         const __amdgpu_buffer_rsrc_t rx = frame_rsrc(b);
         __syncthreads();   // B0: the previous tile is done with t1 / t2 / the max slots
@@ -239,8 +179,8 @@ __global__ __launch_bounds__(512, 1) void bottleneck32_kernel(Block32Args a) {
             for (int s = 0; s < KS1; ++s) {
                 if (s + XD - 1 < KS1) ldx(rx, offA, offB, s + XD - 1, xa[(s + XD - 1) % XD], xb[(s + XD - 1) % XD]);
                 u32x4 pa[2], pb[2];
-                split8(xa[s % XD][0], xa[s % XD][1], sax, pa);
-                split8(xb[s % XD][0], xb[s % XD][1], sax, pb);
+                split_pair8_or(xa[s % XD][0], xa[s % XD][1], sax, pa);
+                split_pair8_or(xb[s % XD][0], xb[s % XD][1], sax, pb);
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     u32x4 wf[2];
@@ -277,11 +217,11 @@ __global__ __launch_bounds__(512, 1) void bottleneck32_kernel(Block32Args a) {
         __syncthreads();   // B1: the tile's t1 max is complete
         {
             const int pB = 8 + (w >> 1), hB = w & 1;
-            const float sa1 = __builtin_ldexpf(1.f, scale_exp(__uint_as_float(s_max[0])));
+            const float sa1 = __builtin_ldexpf(1.f, act_scale_exp_of(__uint_as_float(s_max[0])));
             auto store = [&](const float (&v)[4], int c, int p) {
                 u32x2 hi, lo;
-                split4(v, sa1, hi, lo);
-                const int off = lds_off(16 * p + li, 2 * c + (g >> 1)) + (g & 1) * 8;
+                split_pair4_or(v, sa1, hi, lo);
+                const int off = swz128_any(16 * p + li, 2 * c + (g >> 1)) + (g & 1) * 8;
                 *(u32x2*)(lt1 + off) = hi;
                 *(u32x2*)(lt1 + T1PL + off) = lo;
             };
@@ -291,7 +231,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck32_kernel(Block32Args a) {
             for (int c = 0; c < 2; ++c) store(vB[c], 2 * hB + c, pB);
             if (tid == 0) s_max[1] = 0u;             // t2's max: last read before this tile's B0
         }
-        const int k1 = scale_exp(__uint_as_float(s_max[0]));
+        const int k1 = act_scale_exp_of(__uint_as_float(s_max[0]));
         __syncthreads();   // B2: t1 planes complete
         if (tid == 0) s_max[0] = 0u;                 // read by every wave before B2
 
@@ -307,7 +247,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck32_kernel(Block32Args a) {
 #define VD_T1READ(Q)                                                                                   \
             do {                                                                                       \
                 const int hh_ = (Q) / 3, dx_ = (Q) % 3;                                                \
-                const int off_ = lds_off(hh_ * HWD + li + dx_, 4 * hf + g);                            \
+                const int off_ = swz128_any(hh_ * HWD + li + dx_, 4 * hf + g);                        \
                 tf[(Q) % (PD + 1)][0] = *(const u32x4*)(lt1 + off_);                                   \
                 tf[(Q) % (PD + 1)][1] = *(const u32x4*)(lt1 + T1PL + off_);                            \
             } while (0)
@@ -358,7 +298,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck32_kernel(Block32Args a) {
             if (lane == 0 && m2 > 0.f) atomicMax(s_max + 1, __float_as_uint(m2));
         }
         __syncthreads();   // B4: partials consumed, t2 max complete
-        const int k2 = scale_exp(__uint_as_float(s_max[1]));
+        const int k2 = act_scale_exp_of(__uint_as_float(s_max[1]));
         if (hf == 0) {
             const float sa2 = __builtin_ldexpf(1.f, k2);
 #pragma unroll
@@ -366,8 +306,8 @@ __global__ __launch_bounds__(512, 1) void bottleneck32_kernel(Block32Args a) {
                 u32x2 hi, lo;
                 const f32x4_t v = v2s[m * 64];
                 const float vv[4] = {v[0], v[1], v[2], v[3]};
-                split4(vv, sa2, hi, lo);
-                const int off = lds_off(16 * m + li, 2 * jn + (g >> 1)) + (g & 1) * 8;
+                split_pair4_or(vv, sa2, hi, lo);
+                const int off = swz128_any(16 * m + li, 2 * jn + (g >> 1)) + (g & 1) * 8;
                 *(u32x2*)(lt2 + off) = hi;
                 *(u32x2*)(lt2 + T2PL + off) = lo;
             }
@@ -434,7 +374,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck32_kernel(Block32Args a) {
                 u32x4 tfr[2][2];
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    const int off = lds_off(16 * m + li, 4 * s + g);
+                    const int off = swz128_any(16 * m + li, 4 * s + g);
                     tfr[s][0] = *(const u32x4*)(lt2 + off);
                     tfr[s][1] = *(const u32x4*)(lt2 + T2PL + off);
                 }
@@ -460,7 +400,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck32_kernel(Block32Args a) {
 #pragma unroll
                     for (int s = 0; s < 2; ++s) {
                         u32x4 px[2];
-                        split8(xc[2 * s], xc[2 * s + 1], sax, px);
+                        split_pair8_or(xc[2 * s], xc[2 * s + 1], sax, px);
 #pragma unroll
                         for (int j = 0; j < 2; ++j) accd[j] = mfma_pair(wdf[j][s], px, accd[j]);
                     }
@@ -632,7 +572,7 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
                 // ---- stage 1: t1 of halo pixel tiles 3w..3w+2, all 64 channels ----
                 int b, oy0, ox0;
                 tile_of(j, b, oy0, ox0);
-                const int kx = scale_exp(__uint_as_float(a.xmax[b]));
+                const int kx = act_scale_exp_of(__uint_as_float(a.xmax[b]));
                 const float sax = __builtin_ldexpf(1.f, kx), invx = __builtin_ldexpf(1.f, -kx);
                 const __amdgpu_buffer_rsrc_t rx = frame_rsrc(b);
                 int li = li0, g = g0;
@@ -660,7 +600,7 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
                     if (ks + XS - 1 < KS1) ldx(rx, off, ks + XS - 1, xs[(ks + XS - 1) % XS]);
                     u32x4 px[NP][2];
 #pragma unroll
-                    for (int i = 0; i < NP; ++i) split8(xs[ks % XS][i][0], xs[ks % XS][i][1], sax, px[i]);
+                    for (int i = 0; i < NP; ++i) split_pair8_or(xs[ks % XS][i][0], xs[ks % XS][i][1], sax, px[i]);
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         u32x4 wf[2];
@@ -707,7 +647,7 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
                 if (lane == 0 && m > 0.f) atomicMax(s_t1max + (j & 3), __float_as_uint(m));
                 post_flag(s_flag + 4, lane);
                 wait_flag(s_flag + 4, 4 * (j + 1));
-                const float sa1 = __builtin_ldexpf(1.f, scale_exp(__uint_as_float(s_t1max[j & 3])));
+                const float sa1 = __builtin_ldexpf(1.f, act_scale_exp_of(__uint_as_float(s_t1max[j & 3])));
                 if (j >= 1) wait_flag(s_flag + 1, 4 * j);  // consumers are done with the t1 planes
 #pragma unroll
                 for (int i = 0; i < NP; ++i)
@@ -715,8 +655,8 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
                     for (int c = 0; c < 4; ++c) {
                         const float v[4] = {acc[i][c][0], acc[i][c][1], acc[i][c][2], acc[i][c][3]};
                         u32x2 hi, lo;
-                        split4(v, sa1, hi, lo);
-                        const int off = lds_off(16 * (NP * w + i) + li, 2 * c + (g >> 1)) + (g & 1) * 8;
+                        split_pair4_or(v, sa1, hi, lo);
+                        const int off = swz128_any(16 * (NP * w + i) + li, 2 * c + (g >> 1)) + (g & 1) * 8;
                         *(u32x2*)(lt1 + off) = hi;
                         *(u32x2*)(lt1 + T1PL + off) = lo;
                     }
@@ -747,7 +687,7 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
             u32x4 w2f[9][2];
             ldw2(0, 0, 9, w2f);
             wait_flag(s_flag + 0, 4 * (j + 1));            // t1 of tile j written
-            const int k1 = scale_exp(__uint_as_float(s_t1max[j & 3]));
+            const int k1 = act_scale_exp_of(__uint_as_float(s_t1max[j & 3]));
             if (jn == 0 && lane == 0 && j >= 2) s_t1max[(j - 2) & 3] = 0u;   // read by every consumer already
             const float inv1 = __builtin_ldexpf(1.f, -k1);
             int li = li0, g = g0;
@@ -762,7 +702,7 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
                 const int hf = i / 30, q = i % 30;
                 int l = li;                                // address computed here, not hoisted (registers)
                 asm volatile("" : "+v"(l));
-                const int off = lds_off((q / 3) * HWD + l + q % 3, 4 * hf + g);
+                const int off = swz128_any((q / 3) * HWD + l + q % 3, 4 * hf + g);
                 d[0] = *(const u32x4*)(lt1 + off);
                 d[1] = *(const u32x4*)(lt1 + T1PL + off);
             };
@@ -802,14 +742,14 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
                 if (lane == 0 && m2 > 0.f) atomicMax(s_t2max + (j & 3), __float_as_uint(m2));
                 post_flag(s_flag + 5, lane);               // the tile's t2 max over the four consumers
                 wait_flag(s_flag + 5, 4 * (j + 1));
-                const float sa2 = __builtin_ldexpf(1.f, scale_exp(__uint_as_float(s_t2max[j & 3])));
+                const float sa2 = __builtin_ldexpf(1.f, act_scale_exp_of(__uint_as_float(s_t2max[j & 3])));
                 if (j >= 1) wait_flag(s_flag + 3, 4 * j);  // every consumer is done with the t2 planes
 #pragma unroll
                 for (int m = 0; m < 8; ++m) {
                     const float v[4] = {acc2[m][0], acc2[m][1], acc2[m][2], acc2[m][3]};
                     u32x2 hi, lo;
-                    split4(v, sa2, hi, lo);
-                    const int off = lds_off(16 * m + li, 2 * jn + (g >> 1)) + (g & 1) * 8;
+                    split_pair4_or(v, sa2, hi, lo);
+                    const int off = swz128_any(16 * m + li, 2 * jn + (g >> 1)) + (g & 1) * 8;
                     *(u32x2*)(lt2 + off) = hi;
                     *(u32x2*)(lt2 + T2PL + off) = lo;
                 }
@@ -871,7 +811,7 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
                 }
                 if (h == 0) {
                     wait_flag(s_flag + 2, 4 * (j + 1));    // t2 of tile j written
-                    k2 = scale_exp(__uint_as_float(s_t2max[j & 3]));
+                    k2 = act_scale_exp_of(__uint_as_float(s_t2max[j & 3]));
                     if (jn == 0 && lane == 0 && j >= 2) s_t2max[(j - 2) & 3] = 0u;   // read by every Q wave
                     inv2 = __builtin_ldexpf(1.f, -k2);
                 }
@@ -881,7 +821,7 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
                     u32x4 tf[2][2];
 #pragma unroll
                     for (int s = 0; s < 2; ++s) {
-                        const int off = lds_off(16 * m + li, 4 * s + g);
+                        const int off = swz128_any(16 * m + li, 4 * s + g);
                         tf[s][0] = *(const u32x4*)(lt2 + off);
                         tf[s][1] = *(const u32x4*)(lt2 + T2PL + off);
                     }

@@ -31,31 +31,17 @@
 // issues exactly 3 DMA and 3 store instructions per group (tails: the DMA
 // re-reads the last pixel, stores go past the buffer's num_records and are
 // dropped), so the wait for group i's DMA is a fixed count once the ring is full.
-#include "vd_common.h"
+#include "vd_kernel.h"
 
 #include <cstdlib>
 
 namespace {
-
-// s_barrier after this wave's LDS ops retire (no global-memory fence)
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void lds_void_t;
-
 
 constexpr int C_MID = 128, C_OUT = 512;   // layer2 widths
 constexpr int D = 3;                      // groups in flight ahead of the computing one
 constexpr int R = D + 1;                  // ring slots
 constexpr int SLOT_T2 = 16 * 256;         // t2 rows of a group (4 KB)
 constexpr int SLOT = SLOT_T2 + 16 * 1024; // + identity rows (16 KB)
-// s_waitcnt vmcnt(N) with expcnt / lgkmcnt left alone (gfx9 encoding: vmcnt[3:0] | vmcnt[5:4] << 14)
-constexpr int vmcnt_imm(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0F70 & ~15; }
 
 // F16: the fp16 plan (VD_PREC_FP16) on fp16 operands / activations
 template <bool F16>

@@ -32,13 +32,9 @@
 // vmcnt counts LDS-DMA, loads and stores together in issue order; every wave issues the
 // same count of each per chunk (8 DMA, 4 identity loads, 4 y stores), so the waits are
 // fixed immediates.
-#include "vd_common.h"
+#include "vd_kernel.h"
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void lds_void_t;
 
 // Shapes: layer2 (t2 128 -> y 512 -> t1' 128; weight chunks of 64 conv3 channels) and
 // layer3 (256 -> 1024 -> 256; chunks of 32). Either way a chunk is 32 KB of W3 rows and
@@ -64,53 +60,6 @@ template <int CM_, int CO_, int NCH_, int GPW_, int WAVES_ = 8> struct ChainShap
 using L2Shape = ChainShape<128, 512, 64, 1>;    // 8 waves of 16 pixels: 128-pixel super-groups
 using L2Shape2 = ChainShape<128, 512, 64, 2>;   // option chain_gpw=2: 32 pixels per wave (~55 VGPRs spill)
 using L3Shape = ChainShape<256, 1024, 32, 1>;
-
-// s_waitcnt vmcnt(N), expcnt / lgkmcnt left alone (gfx9 encoding)
-constexpr int vmcnt_imm(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0F70; }
-
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-// 8 f32 -> fp16 hi / lo planes of x * sa (conv_x6.hip split_pair8: the same roundings)
-__device__ __forceinline__ void split8(const float (&e)[8], float sa, u32x4& H, u32x4& L) {
-    unsigned hv[4], lv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        half2_t h, l;
-        h[0] = (_Float16)__builtin_fmaf(e[2 * j], sa, 0.f);
-        h[1] = (_Float16)__builtin_fmaf(e[2 * j + 1], sa, 0.f);
-        l[0] = (_Float16)__builtin_fmaf(e[2 * j], sa, -(float)h[0]);
-        l[1] = (_Float16)__builtin_fmaf(e[2 * j + 1], sa, -(float)h[1]);
-        hv[j] = __builtin_bit_cast(unsigned, h);
-        lv[j] = __builtin_bit_cast(unsigned, l);
-    }
-    H = u32x4{hv[0], hv[1], hv[2], hv[3]};
-    L = u32x4{lv[0], lv[1], lv[2], lv[3]};
-}
-
-// w_lo x_hi + w_hi x_lo + w_hi x_hi (conv_x6.hip mfma_terms<2>, small terms first)
-__device__ __forceinline__ f32x4_t mfma3(const u32x4& wh, const u32x4& wl, const u32x4& xh, const u32x4& xl,
-                                         f32x4_t acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, wl), __builtin_bit_cast(f16x8_t, xh), acc,
-                                                 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, wh), __builtin_bit_cast(f16x8_t, xl), acc,
-                                                 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, wh), __builtin_bit_cast(f16x8_t, xh), acc,
-                                                 0, 0, 0);
-    return acc;
-}
-
-// power-of-two exponent k with m * 2^k in [2^14, 2^15) (act_scale_exp's rule)
-__device__ __forceinline__ int pow2_exp(float m) {
-    if (!(m > 0.f) || !(m < 3.0e38f)) return 0;
-    int e;
-    (void)frexpf(m, &e);
-    const int k = 15 - e;
-    return k < -100 ? -100 : (k > 100 ? 100 : k);
-}
 
 template <class S>
 __global__ __launch_bounds__(S::THREADS, 1) void chain32_kernel(Chain32Args a) {
@@ -227,7 +176,7 @@ __global__ __launch_bounds__(S::THREADS, 1) void chain32_kernel(Chain32Args a) {
             ok[u] = m[u] < a.M;
             fb[u] = (ok[u] ? m[u] : a.M - 1) / a.hw;        // this lane's pixel's frame
             const float mx = a.xmax ? __uint_as_float(a.xmax[fb[u]]) : a.xbound;
-            const int kx = pow2_exp(mx);
+            const int kx = act_scale_exp_of(mx);
             const float sa = __builtin_ldexpf(1.f, kx);
             inv_sa[u] = __builtin_ldexpf(1.f, -kx);
 #pragma unroll
@@ -235,7 +184,7 @@ __global__ __launch_bounds__(S::THREADS, 1) void chain32_kernel(Chain32Args a) {
                 float e8[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) e8[e] = __uint_as_float(xr[u][s][e >> 2][e & 3]);
-                split8(e8, sa, xb[u][s][0], xb[u][s][1]);
+                split_pair8(e8, sa, xb[u][s][0], xb[u][s][1]);
             }
         }
         f32x4_t acc1[GPW][T1];
@@ -278,10 +227,10 @@ __global__ __launch_bounds__(S::THREADS, 1) void chain32_kernel(Chain32Args a) {
 #pragma unroll
                 for (int j = 0; j < T3; ++j) {
                     const char* row = w3s + (16 * j + p) * RB3;
-                    const u32x4 wh = *(const u32x4*)(row + ((((2 * s) * 4 + q) ^ p) << 4));
-                    const u32x4 wl = *(const u32x4*)(row + ((((2 * s + 1) * 4 + q) ^ p) << 4));
+                    const u32x4 wf[2] = {*(const u32x4*)(row + ((((2 * s) * 4 + q) ^ p) << 4)),
+                                         *(const u32x4*)(row + ((((2 * s + 1) * 4 + q) ^ p) << 4))};
 #pragma unroll
-                    for (int u = 0; u < GPW; ++u) acc3[u][j] = mfma3(wh, wl, xb[u][s][0], xb[u][s][1], acc3[u][j]);
+                    for (int u = 0; u < GPW; ++u) acc3[u][j] = mfma_pair(wf, xb[u][s], acc3[u][j]);
                 }
                 // GPW = 2: keep each k-step's fragment reads next to its MFMAs (read ahead,
                 // the whole chunk's fragments would need another 128 VGPRs)
@@ -317,7 +266,7 @@ __global__ __launch_bounds__(S::THREADS, 1) void chain32_kernel(Chain32Args a) {
                 cmax = fmaxf(cmax, __shfl_xor(cmax, 32));   // the pixel's max over the chunk's NCH channels
                 // the pixel's conv1' sum runs at scale 2^ks: re-based exactly (a power of
                 // two) when this chunk's split scale differs; an all-zero chunk keeps it
-                const int ky = cmax > 0.f ? pow2_exp(cmax) : ks[u];
+                const int ky = cmax > 0.f ? act_scale_exp_of(cmax) : ks[u];
                 const float rebase = __builtin_ldexpf(1.f, ky - ks[u]);
                 ks[u] = ky;
                 const float sy = __builtin_ldexpf(1.f, ky);
@@ -329,7 +278,7 @@ __global__ __launch_bounds__(S::THREADS, 1) void chain32_kernel(Chain32Args a) {
                 for (int i = 0; i < KC; ++i) {
                     const float e8[8] = {yv[2 * i][0], yv[2 * i][1], yv[2 * i][2], yv[2 * i][3],
                                          yv[2 * i + 1][0], yv[2 * i + 1][1], yv[2 * i + 1][2], yv[2 * i + 1][3]};
-                    split8(e8, sy, yb[u][i][0], yb[u][i][1]);
+                    split_pair8(e8, sy, yb[u][i][0], yb[u][i][1]);
                 }
             }
             // ---- conv1' over the chunk's NCH input channels, into the running sums ----
@@ -339,10 +288,10 @@ __global__ __launch_bounds__(S::THREADS, 1) void chain32_kernel(Chain32Args a) {
                 for (int j = 0; j < T1; ++j) {
                     const int r = 16 * j + p, key = (r / R1PL) & (C1 - 1);
                     const char* row = w1s + r * RB1;
-                    const u32x4 wh = *(const u32x4*)(row + ((((2 * i) * 4 + q) ^ key) << 4));
-                    const u32x4 wl = *(const u32x4*)(row + ((((2 * i + 1) * 4 + q) ^ key) << 4));
+                    const u32x4 wf[2] = {*(const u32x4*)(row + ((((2 * i) * 4 + q) ^ key) << 4)),
+                                         *(const u32x4*)(row + ((((2 * i + 1) * 4 + q) ^ key) << 4))};
 #pragma unroll
-                    for (int u = 0; u < GPW; ++u) acc1[u][j] = mfma3(wh, wl, yb[u][i][0], yb[u][i][1], acc1[u][j]);
+                    for (int u = 0; u < GPW; ++u) acc1[u][j] = mfma_pair(wf, yb[u][i], acc1[u][j]);
                     if constexpr (GPW > 1 || T1 > 8) {
                         if ((j & 1) == 1) __builtin_amdgcn_sched_barrier(0);
                     }

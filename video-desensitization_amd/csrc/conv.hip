@@ -24,29 +24,16 @@
 //   activation (ReLU / LeakyReLU / SiLU), store at a channel offset.
 //   Block -> tile mapping is XCD-aware: blocks that share an A (pixel) panel
 //   are placed on one XCD so the panel is fetched into that XCD's L2 once.
-#include "vd_common.h"
+#include "vd_kernel.h"
 #include <algorithm>
 #include <type_traits>
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));   // native vector (HIP's uint4 is a struct)
-
 template <typename T> struct Elem;
 template <> struct Elem<__bf16> { static constexpr int VEC = 8; };
 template <> struct Elem<_Float16> { static constexpr int VEC = 8; };
 template <> struct Elem<float>  { static constexpr int VEC = 4; };
-
-__device__ __forceinline__ int lds_off(int row, int chunk) {
-    return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
-}
-
-__device__ __forceinline__ float act_apply(float v, int act, float slope) {
-    if (act == VD_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == VD_ACT_LEAKY) return v > 0.f ? v : v * slope;
-    if (act == VD_ACT_SILU) return v / (1.0f + __expf(-v));
-    return v;
-}
 
 template <typename T>
 __device__ __forceinline__ float load_elem(const void* p, size_t off) {
@@ -56,8 +43,6 @@ __device__ __forceinline__ float load_elem(const void* p, size_t off) {
 
 // 16 zero bytes: the LDS-DMA source of padding taps (conv zero padding, K padding).
 __device__ __attribute__((aligned(16))) unsigned vd_zero16[4] = {0u, 0u, 0u, 0u};
-
-typedef __attribute__((address_space(3))) void lds_void_t;
 
 // NT threads (4 waves); two LDS stages: one K tile in flight, two barriers per K tile.
 template <typename T, int BM, int BN, int NT, int STAGES, bool DENSE>
@@ -187,9 +172,9 @@ __global__ __launch_bounds__(NT) void conv_igemm_kernel(ConvArgs a) {
             const int ch = ks * 4 + (lane >> 4);                                          \
             u32x4 af[TM], bfr[TN];                                                        \
             _Pragma("unroll") for (int i = 0; i < TM; ++i)                                \
-                af[i] = *(const u32x4*)(As + lds_off(wm * WTM + i * 16 + (lane & 15), ch)); \
+                af[i] = *(const u32x4*)(As + swz128(wm * WTM + i * 16 + (lane & 15), ch)); \
             _Pragma("unroll") for (int j = 0; j < TN; ++j)                                \
-                bfr[j] = *(const u32x4*)(Bs + lds_off(wn * WTN + j * 16 + (lane & 15), ch)); \
+                bfr[j] = *(const u32x4*)(Bs + swz128(wn * WTN + j * 16 + (lane & 15), ch)); \
             _Pragma("unroll") for (int i = 0; i < TM; ++i)                                \
             _Pragma("unroll") for (int j = 0; j < TN; ++j) {                              \
                 if constexpr (std::is_same<T, float>::value) {                            \

@@ -17,26 +17,11 @@
 //   are permuted in LDS so that tiles 2i and 2i+1 give a lane 8 CONSECUTIVE
 //   channels (32i + 8q .. +8), and the epilogue stores 16 B (bf16) per lane
 //   without an LDS pass, reading the residual in the same shape.
-#include "vd_common.h"
+#include "vd_kernel.h"
 #include <algorithm>
 #include <cstdlib>
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int lds_off(int row, int chunk) {
-    return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
-}
-
-template <int ACT>
-__device__ __forceinline__ float act_apply(float v, float slope) {
-    if constexpr (ACT == VD_ACT_RELU) return v > 0.f ? v : 0.f;
-    if constexpr (ACT == VD_ACT_LEAKY) return v > 0.f ? v : v * slope;
-    if constexpr (ACT == VD_ACT_SILU) return v / (1.0f + __expf(-v));
-    return v;
-}
-
 
 // KS: K / 32 (k-steps), NTT: 16-channel tiles per wave (NCH = 16 * NTT channels per
 // workgroup), ACT / RES: activation and residual mode (compile-time: no per-element branches).
@@ -79,7 +64,7 @@ __global__ __launch_bounds__(512) void conv1x1_stream_kernel(ConvArgs a, int nch
             const int j = row >> 4, ii = row & 15;
             const int chn = NTT == 1 ? row : 32 * (j >> 1) + 8 * (ii >> 2) + 4 * (j & 1) + (ii & 3);
             const u32x4 v = *(const u32x4*)(w + (size_t)(n0 + chn) * a.kpad + c * 8);
-            *(u32x4*)(smem + (c >> 3) * (NCH * 128) + lds_off(row, c & 7)) = v;
+            *(u32x4*)(smem + (c >> 3) * (NCH * 128) + swz128(row, c & 7)) = v;
         }
         for (int i = tid; i < NCH; i += 512) {
             s_scale[i] = a.scale[n0 + i];
@@ -93,7 +78,7 @@ __global__ __launch_bounds__(512) void conv1x1_stream_kernel(ConvArgs a, int nch
                 const int j = row >> 4, ii = row & 15;
                 const int chn = NTT == 1 ? row : 32 * (j >> 1) + 8 * (ii >> 2) + 4 * (j & 1) + (ii & 3);
                 const u32x4 v = *(const u32x4*)(w2 + (size_t)(n0 + chn) * a.kpad2 + c * 8);
-                *(u32x4*)(smem2 + (c >> 3) * (NCH * 128) + lds_off(row, c & 7)) = v;
+                *(u32x4*)(smem2 + (c >> 3) * (NCH * 128) + swz128(row, c & 7)) = v;
             }
             for (int i = tid; i < NCH; i += 512) {
                 s_scale2[i] = a.scale2[n0 + i];
@@ -192,7 +177,7 @@ __global__ __launch_bounds__(512) void conv1x1_stream_kernel(ConvArgs a, int nch
                 const int ch = (ks & 1) * 4 + q;
 #pragma unroll
                 for (int j = 0; j < NTT; ++j) {
-                    const u32x4 wf = *(const u32x4*)(wt + lds_off(16 * j + p_lane, ch));
+                    const u32x4 wf = *(const u32x4*)(wt + swz128(16 * j + p_lane, ch));
                     acc2[j] = HT::mfma(wf, xf2[ks], acc2[j]);
                 }
             }
@@ -203,7 +188,7 @@ __global__ __launch_bounds__(512) void conv1x1_stream_kernel(ConvArgs a, int nch
             const int ch = (ks & 1) * 4 + q;
 #pragma unroll
             for (int j = 0; j < NTT; ++j) {
-                const u32x4 wf = *(const u32x4*)(wt + lds_off(16 * j + p_lane, ch));
+                const u32x4 wf = *(const u32x4*)(wt + swz128(16 * j + p_lane, ch));
                 acc[j] = HT::mfma(wf, xf[ks], acc[j]);
             }
         }

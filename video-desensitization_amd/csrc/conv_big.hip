@@ -19,13 +19,10 @@
 //     counted s_waitcnt vmcnt (never 0 in steady state); a slot is refilled only
 //     two phases after its last read (the skew rule; proof in DESIGN.md).
 //   * Epilogue: the f32 tile goes through LDS 64 rows at a time, 16-B stores.
-#include "vd_common.h"
+#include "vd_kernel.h"
 #include <algorithm>
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void_t;
 
 __device__ __attribute__((aligned(16))) unsigned vdb_zero16[4] = {0u, 0u, 0u, 0u};
 
@@ -49,17 +46,6 @@ constexpr int HT = 16384;          // half-tile bytes: 128 rows x 128 B
 constexpr int LDS_BYTES = 8 * HT;  // 2 stages x {A0, B0, B1, A1}
 constexpr int EPLD = 256 + 4;      // f32 epilogue row stride
 
-__device__ __forceinline__ int lds_off(int row, int chunk) {
-    return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
-}
-
-__device__ __forceinline__ float act_apply(float v, int act, float slope) {
-    if (act == VD_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == VD_ACT_LEAKY) return v > 0.f ? v : v * slope;
-    if (act == VD_ACT_SILU) return v / (1.0f + __expf(-v));
-    return v;
-}
-
 // s_waitcnt vmcnt(2*n) for a runtime n in [0, 4]
 __device__ __forceinline__ void wait_halves(int n) {
     switch (n) {
@@ -72,7 +58,7 @@ __device__ __forceinline__ void wait_halves(int n) {
 }
 
 // s_waitcnt vmcnt(2*n) only (LDS reads stay in flight)
-__device__ __forceinline__ void wait_vm(int n) {
+__device__ __forceinline__ void wait_halves_vm(int n) {
     switch (n) {
         case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
         case 1: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
@@ -198,17 +184,17 @@ __global__ __launch_bounds__(512) void conv_big_kernel(ConvArgs a) {
             const char* As_ = st_ + ((MH) ? 3 : 0) * HT;                                       \
             _Pragma("unroll") for (int i = 0; i < 4; ++i)                                      \
             _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                   \
-                af[i][ks] = *(const u32x4*)(As_ + lds_off(wr * 64 + i * 16 + (lane & 15), ks * 4 + (lane >> 4))); \
+                af[i][ks] = *(const u32x4*)(As_ + swz128(wr * 64 + i * 16 + (lane & 15), ks * 4 + (lane >> 4))); \
         }                                                                                      \
         if ((RB0) && VDB_DIAG_READ) {                                                          \
             _Pragma("unroll") for (int j = 0; j < 2; ++j)                                      \
             _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                   \
-                b0[j][ks] = *(const u32x4*)(st_ + HT + lds_off(wc * 32 + j * 16 + (lane & 15), ks * 4 + (lane >> 4))); \
+                b0[j][ks] = *(const u32x4*)(st_ + HT + swz128(wc * 32 + j * 16 + (lane & 15), ks * 4 + (lane >> 4))); \
         }                                                                                      \
         if ((RB1) && VDB_DIAG_READ) {                                                          \
             _Pragma("unroll") for (int j = 0; j < 2; ++j)                                      \
             _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                   \
-                b1[j][ks] = *(const u32x4*)(st_ + 2 * HT + lds_off(wc * 32 + j * 16 + (lane & 15), ks * 4 + (lane >> 4))); \
+                b1[j][ks] = *(const u32x4*)(st_ + 2 * HT + swz128(wc * 32 + j * 16 + (lane & 15), ks * 4 + (lane >> 4))); \
         }                                                                                      \
         VDB_STAMP();                                                                           \
         if (STEADY) {                                                                          \
@@ -217,7 +203,7 @@ __global__ __launch_bounds__(512) void conv_big_kernel(ConvArgs a) {
         } else if (p + 1 < nh_total) {                                                         \
             const int q = p + 1;                                                               \
             const int need = 4 * (q >> 2) + ((q & 3) == 0 ? 1 : ((q & 3) == 1 ? 2 : 3));       \
-            wait_vm(min(p + 5, nh_total - 1) - need);                                          \
+            wait_halves_vm(min(p + 5, nh_total - 1) - need);                                   \
         }                                                                                      \
         VDB_STAMP();                                                                           \
         __builtin_amdgcn_s_barrier();                                                          \
@@ -242,7 +228,7 @@ __global__ __launch_bounds__(512) void conv_big_kernel(ConvArgs a) {
 #endif
     {
         for (int h = 0; h < 6 && h < nh_total; ++h) VDB_ISSUE(h);   // prologue: half-tiles 0..5
-        wait_vm(min(5, nh_total - 1) - 1);                          // A0(0), B0(0) landed
+        wait_halves_vm(min(5, nh_total - 1) - 1);                   // A0(0), B0(0) landed
         __builtin_amdgcn_s_barrier();
         if (wr == 1) __builtin_amdgcn_s_barrier();                  // the skew
         asm volatile("" ::: "memory");

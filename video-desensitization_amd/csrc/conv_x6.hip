@@ -1,17 +1,24 @@
-// conv_x6.hip — fp32 convolution on the bf16 matrix cores by exact operand
-// decomposition (VD_PREC_FP32 with option f32_split = 1, the default).
+// conv_x6.hip — fp32 convolution on the 16-bit matrix cores by operand decomposition
+// (VD_PREC_FP32). Three forms, template parameter TERMS:
+//   2  fp16 pairs, the default (option f32_split = 2): activations scaled per frame by
+//      a power of two, both operands split into fp16 hi / lo, three products on
+//      v_mfma_f32_16x16x32_f16. The contract (scale, split, product order) is
+//      vd_kernel.h's; the weights' side is vd_pack_x3h below.
+//   1  the same pair weights on inputs exact in fp16 (the integer-valued stem canvases,
+//      ConvArgs::x_exact): one A plane, two products.
+//   3  exact bf16 triples (f32_split = 1), six products on v_mfma_f32_16x16x32_bf16:
 //
 // Every f32 operand is split EXACTLY into three bf16 terms, x = x0 + x1 + x2
 // (x0 = the top 8 significand bits, x1 the next 8, x2 the last 8: each residual
 // is exact in f32 and fits the next term), and the product is the sum of the six
 // cross terms with i + j <= 2:
 //     a*b ~= a0 b0 + a0 b1 + a1 b0 + a0 b2 + a1 b1 + a2 b0
-// Each term is an exact 16-bit product accumulated in f32 by
-// v_mfma_f32_16x16x32_bf16; the dropped terms (a1 b2, a2 b1, a2 b2) are below
-// 2^-22 |ab|, so a K-long dot product carries the same error as an f32 fma chain
-// (measured in tests/test_gpu_kernels.py against float64: error at the level of
-// the exact-f32 MFMA path). Six bf16 MFMAs (96 cycles per 16x16x32 block) replace
-// eight exact-f32 v_mfma_f32_16x16x4_f32 (256 cycles): 2.67x the f32 MFMA rate.
+// Each term is an exact 16-bit product accumulated in f32; the dropped terms
+// (a1 b2, a2 b1, a2 b2) are below 2^-22 |ab|, so a K-long dot product carries the
+// same error as an f32 fma chain (measured in tests/test_gpu_kernels.py against
+// float64: error at the level of the exact-f32 MFMA path). Six bf16 MFMAs (96 cycles
+// per 16x16x32 block) replace eight exact-f32 v_mfma_f32_16x16x4_f32 (256 cycles):
+// 2.67x the f32 MFMA rate; the pair form halves that again.
 //
 // Same conv contract as conv.hip (NHWC f32 activations, K = (kh, kw, c) with c
 // fastest, fused BN scale/shift + residual + activation, channel-sliced
@@ -28,16 +35,13 @@
 //     bf16; LDS-DMA straight into the stage (source-side swizzle).
 //   * 64-B LDS rows, chunk' = chunk ^ (((row >> 3) & 1) * 3): conflict-free
 //     ds_read_b128 fragment reads for the 16-row MFMA operand pattern.
-#include "vd_common.h"
+#include "vd_kernel.h"
 #include <algorithm>
 #include <type_traits>
 #include <cmath>
 #include <cstring>
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void_t;
 
 constexpr int KT = 32;                          // K per tile (one bf16 MFMA k-step)
 constexpr int kAmaxFrames = 1024;               // LDS reserved for per-frame max slots (frames per launch)
@@ -66,8 +70,6 @@ template <int BM_, int BN, int NT_, int NST, int TERMS, int MF = 16> struct X6Sh
     static constexpr int AITEMS = BM / AROWS;                  // A items (row, 8 k) per thread: 2 (8 waves), 4 (4 waves)
     static_assert(BM % AROWS == 0 && (AITEMS == 2 || AITEMS == 4), "A items per thread");
 };
-
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 64 + ((chunk ^ (((row >> 3) & 1) * 3)) << 4); }
 
 // s_waitcnt vmcnt(n) for n in [0, 23] (immediate operand)
 __device__ __forceinline__ void wait_vm(int n) {
@@ -109,13 +111,6 @@ __device__ __forceinline__ void wait_vm_k() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-__device__ __forceinline__ float act_apply(float v, int act, float slope) {
-    if (act == VD_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == VD_ACT_LEAKY) return v > 0.f ? v : v * slope;
-    if (act == VD_ACT_SILU) return v / (1.0f + __expf(-v));
-    return v;
-}
-
 // x = hi + mid + lo exactly (truncation split: each term keeps 8 significand bits)
 __device__ __forceinline__ void split3(float x, unsigned& h, unsigned& m, unsigned& l) {
     const unsigned u = __float_as_uint(x);
@@ -129,69 +124,23 @@ __device__ __forceinline__ void split3(float x, unsigned& h, unsigned& m, unsign
     l = __float_as_uint(r2) >> 16;
 }
 
-// x = hi + lo (+ below 2^-24 |x|) with both terms fp16, round to nearest: the
-// scaled operand (|x| < 2^15, see act_scale) keeps 22-24 significand bits
-__device__ __forceinline__ void split2h(float x, float sa, unsigned& h, unsigned& l) {
-    // x * sa is exact (a power of two), so each term is ONE rounding of a fused
-    // multiply-add to fp16 (v_fma_mixlo_f16): hi = RNE(x sa), lo = RNE(x sa - hi)
-    const _Float16 x0 = (_Float16)__builtin_fmaf(x, sa, 0.f);
-    const _Float16 x1 = (_Float16)__builtin_fmaf(x, sa, -(float)x0);   // the residual is exact in f32
-    h = __builtin_bit_cast(unsigned short, x0);
-    l = __builtin_bit_cast(unsigned short, x1);
-}
-
+// The products of one 16x16x32 block on TERMS planes, small terms first: 3 = the six
+// bf16 cross terms, 2 = the fp16 pair (vd_kernel.h), 1 = pair weights on one exact A plane
 template <int TERMS>
-__device__ __forceinline__ f32x4_t mfma_terms(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x4_t acc);
-
-template <>
-__device__ __forceinline__ f32x4_t mfma_terms<3>(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x4_t acc) {
-#define VDX_MFMA(pa, pb)                                                                                 \
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a[pa]),                  \
-                                                  __builtin_bit_cast(bf16x8_t, b[pb]), acc, 0, 0, 0)
-    // small terms first
-    VDX_MFMA(2, 0);
-    VDX_MFMA(1, 1);
-    VDX_MFMA(0, 2);
-    VDX_MFMA(1, 0);
-    VDX_MFMA(0, 1);
-    VDX_MFMA(0, 0);
-#undef VDX_MFMA
-    return acc;
-}
-
-template <>
-__device__ __forceinline__ f32x4_t mfma_terms<1>(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x4_t acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a[0]), __builtin_bit_cast(f16x8_t, b[1]),
-                                                 acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a[0]), __builtin_bit_cast(f16x8_t, b[0]),
-                                                 acc, 0, 0, 0);
-    return acc;
-}
-
-template <>
-__device__ __forceinline__ f32x4_t mfma_terms<2>(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x4_t acc) {
-#define VDH_MFMA(pa, pb)                                                                                 \
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a[pa]),                    \
-                                                 __builtin_bit_cast(f16x8_t, b[pb]), acc, 0, 0, 0)
-    VDH_MFMA(1, 0);
-    VDH_MFMA(0, 1);
-    VDH_MFMA(0, 0);
-#undef VDH_MFMA
-    return acc;
-}
-
-// The same three products in the same order with the operands exchanged: the MFMA
-// computes D^T (rows = weight rows / output channels, columns = pixels), so a lane's
-// accumulator holds 4 consecutive channels of one pixel (register epilogue, TR tiles)
-__device__ __forceinline__ f32x4_t mfma_pair_tr(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x4_t acc) {
-#define VDT_MFMA(pa, pb)                                                                                 \
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, b[pb]),                    \
-                                                 __builtin_bit_cast(f16x8_t, a[pa]), acc, 0, 0, 0)
-    VDT_MFMA(1, 0);
-    VDT_MFMA(0, 1);
-    VDT_MFMA(0, 0);
-#undef VDT_MFMA
-    return acc;
+__device__ __forceinline__ f32x4_t mfma_terms(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x4_t acc) {
+    if constexpr (TERMS == 2) {
+        return mfma_pair(a, b, acc);
+    } else if constexpr (TERMS == 1) {
+        acc = Half16<true>::mfma(a[0], b[1], acc);
+        return Half16<true>::mfma(a[0], b[0], acc);
+    } else {
+        acc = Half16<false>::mfma(a[2], b[0], acc);
+        acc = Half16<false>::mfma(a[1], b[1], acc);
+        acc = Half16<false>::mfma(a[0], b[2], acc);
+        acc = Half16<false>::mfma(a[1], b[0], acc);
+        acc = Half16<false>::mfma(a[0], b[1], acc);
+        return Half16<false>::mfma(a[0], b[0], acc);
+    }
 }
 
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
@@ -210,27 +159,6 @@ __device__ __forceinline__ f32x16_t mfma_pair32(const u32x4 (&a)[3], const u32x4
     return acc;
 }
 
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-
-// 8 f32 -> the scaled fp16 pair as two packed 16-B planes, element pairs built in
-// half2 registers (v_fma_mixlo / v_fma_mixhi write the halves in place: no shifts or
-// ORs); the same roundings as split2h
-__device__ __forceinline__ void split_pair8(const float (&e)[8], float sa, u32x4& H, u32x4& L) {
-    unsigned hv[4], lv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        half2_t h, l;
-        h[0] = (_Float16)__builtin_fmaf(e[2 * j], sa, 0.f);
-        h[1] = (_Float16)__builtin_fmaf(e[2 * j + 1], sa, 0.f);
-        l[0] = (_Float16)__builtin_fmaf(e[2 * j], sa, -(float)h[0]);
-        l[1] = (_Float16)__builtin_fmaf(e[2 * j + 1], sa, -(float)h[1]);
-        hv[j] = __builtin_bit_cast(unsigned, h);
-        lv[j] = __builtin_bit_cast(unsigned, l);
-    }
-    H = u32x4{hv[0], hv[1], hv[2], hv[3]};
-    L = u32x4{lv[0], lv[1], lv[2], lv[3]};
-}
-
 // 8 f32 -> TERMS packed 16-B planes (bf16 truncation split, or scaled fp16 pair)
 template <int TERMS>
 __device__ __forceinline__ void split_pack(const float (&e)[8], float sa, u32x4 (&o)[3]) {
@@ -242,8 +170,7 @@ __device__ __forceinline__ void split_pack(const float (&e)[8], float sa, u32x4 
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         if constexpr (TERMS == 3) split3(e[j], hv[j], mv[j], lv[j]);
-        else if constexpr (TERMS == 2) { split2h(e[j], sa, hv[j], mv[j]); lv[j] = 0; }
-        else { hv[j] = __builtin_bit_cast(unsigned short, (_Float16)__builtin_fmaf(e[j], sa, 0.f)); mv[j] = lv[j] = 0; }
+        else { hv[j] = __builtin_bit_cast(unsigned short, pair_hi(e[j], sa)); mv[j] = lv[j] = 0; }
     }
     o[0] = u32x4{hv[0] | (hv[1] << 16), hv[2] | (hv[3] << 16), hv[4] | (hv[5] << 16), hv[6] | (hv[7] << 16)};
     if constexpr (TERMS >= 2)
@@ -621,7 +548,7 @@ __global__ __launch_bounds__(NT, NT == 256 && BM == 256 ? 1 : 2) void conv_x6_ke
         }
         u32x4 o[3];
         split_pack<TERMS>(e, sa[i], o);
-        const int off = swz(arow + AROWS * i, apair);
+        const int off = swz64(arow + AROWS * i, apair);
 #pragma unroll
         for (int p = 0; p < S::TA; ++p) *(u32x4*)(A + p * PL_A + off) = o[p];
     };
@@ -674,13 +601,13 @@ __global__ __launch_bounds__(NT, NT == 256 && BM == 256 ? 1 : 2) void conv_x6_ke
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int p = 0; p < 2; ++p)
-                        af[i][p] = *(const u32x4*)(A + p * PL_A + swz(wm * S::WTM + i * 32 + r32, 2 * sk + c32));
+                        af[i][p] = *(const u32x4*)(A + p * PL_A + swz64(wm * S::WTM + i * 32 + r32, 2 * sk + c32));
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     u32x4 bf[3];
 #pragma unroll
                     for (int p = 0; p < 2; ++p)
-                        bf[p] = *(const u32x4*)(Bs + p * PL_B + swz(wn * S::WTN + j * 32 + r32, 2 * sk + c32));
+                        bf[p] = *(const u32x4*)(Bs + p * PL_B + swz64(wn * S::WTN + j * 32 + r32, 2 * sk + c32));
 #pragma unroll
                     for (int i = 0; i < TM; ++i) acc[i][j] = mfma_pair32(af[i], bf, acc[i][j]);
 #pragma unroll
@@ -696,16 +623,16 @@ __global__ __launch_bounds__(NT, NT == 256 && BM == 256 ? 1 : 2) void conv_x6_ke
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int p = 0; p < S::TA; ++p)
-                    af[i][p] = *(const u32x4*)(A + p * PL_A + swz(wm * S::WTM + i * 16 + (lane & 15), ch));
+                    af[i][p] = *(const u32x4*)(A + p * PL_A + swz64(wm * S::WTM + i * 16 + (lane & 15), ch));
 #pragma unroll
-            for (int p = 0; p < S::TB; ++p) bq[0][p] = *(const u32x4*)(Bs + p * PL_B + swz(wn * S::WTN + (lane & 15), ch));
+            for (int p = 0; p < S::TB; ++p) bq[0][p] = *(const u32x4*)(Bs + p * PL_B + swz64(wn * S::WTN + (lane & 15), ch));
             __builtin_amdgcn_sched_group_barrier(0x0100, TM * S::TA + S::TB, 0);
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 if (j + 1 < TN) {
 #pragma unroll
                     for (int p = 0; p < S::TB; ++p)
-                        bq[(j + 1) & 1][p] = *(const u32x4*)(Bs + p * PL_B + swz(wn * S::WTN + (j + 1) * 16 + (lane & 15), ch));
+                        bq[(j + 1) & 1][p] = *(const u32x4*)(Bs + p * PL_B + swz64(wn * S::WTN + (j + 1) * 16 + (lane & 15), ch));
                     __builtin_amdgcn_sched_group_barrier(0x0100, S::TB, 0);
                 }
 #pragma unroll
@@ -724,13 +651,13 @@ __global__ __launch_bounds__(NT, NT == 256 && BM == 256 ? 1 : 2) void conv_x6_ke
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int p = 0; p < S::TA; ++p)
-                    af[i][p] = *(const u32x4*)(A + p * PL_A + swz(wm * S::WTM + i * 16 + (lane & 15), ch));
+                    af[i][p] = *(const u32x4*)(A + p * PL_A + swz64(wm * S::WTM + i * 16 + (lane & 15), ch));
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 u32x4 bf[3];
 #pragma unroll
                 for (int p = 0; p < S::TB; ++p)
-                    bf[p] = *(const u32x4*)(Bs + p * PL_B + swz(wn * S::WTN + j * 16 + (lane & 15), ch));
+                    bf[p] = *(const u32x4*)(Bs + p * PL_B + swz64(wn * S::WTN + j * 16 + (lane & 15), ch));
 #pragma unroll
                 for (int i = 0; i < TM; ++i) {
                     if constexpr (TR) acc[i][j] = mfma_pair_tr(af[i], bf, acc[i][j]);
@@ -746,13 +673,13 @@ __global__ __launch_bounds__(NT, NT == 256 && BM == 256 ? 1 : 2) void conv_x6_ke
             for (int j = 0; j < TN; ++j)
 #pragma unroll
                 for (int p = 0; p < S::TB; ++p)
-                    bf[j][p] = *(const u32x4*)(Bs + p * PL_B + swz(wn * S::WTN + j * 16 + (lane & 15), ch));
+                    bf[j][p] = *(const u32x4*)(Bs + p * PL_B + swz64(wn * S::WTN + j * 16 + (lane & 15), ch));
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 u32x4 af[3];
 #pragma unroll
                 for (int p = 0; p < S::TA; ++p)
-                    af[p] = *(const u32x4*)(A + p * PL_A + swz(wm * S::WTM + i * 16 + (lane & 15), ch));
+                    af[p] = *(const u32x4*)(A + p * PL_A + swz64(wm * S::WTM + i * 16 + (lane & 15), ch));
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     if constexpr (TR) acc[i][j] = mfma_pair_tr(af, bf[j], acc[i][j]);
@@ -1097,8 +1024,8 @@ __global__ __launch_bounds__(512, BN <= 64 ? 4 : 2) void conv_x6_halo_kernel(Con
             u32x4 bf[TN][3];
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
-                bf[j][0] = *(const u32x4*)(Bs + swz(wn * S::WTN + j * 16 + (lane & 15), ch));
-                bf[j][1] = *(const u32x4*)(Bs + PL_B + swz(wn * S::WTN + j * 16 + (lane & 15), ch));
+                bf[j][0] = *(const u32x4*)(Bs + swz64(wn * S::WTN + j * 16 + (lane & 15), ch));
+                bf[j][1] = *(const u32x4*)(Bs + PL_B + swz64(wn * S::WTN + j * 16 + (lane & 15), ch));
             }
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
@@ -1110,7 +1037,7 @@ __global__ __launch_bounds__(512, BN <= 64 ? 4 : 2) void conv_x6_halo_kernel(Con
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     if constexpr (TR) acc[i][j] = mfma_pair_tr(af, bf[j], acc[i][j]);
-                    else acc[i][j] = mfma_terms<2>(af, bf[j], acc[i][j]);
+                    else acc[i][j] = mfma_pair(af, bf[j], acc[i][j]);
                 }
             }
         } else if constexpr (PF) {
@@ -1125,20 +1052,20 @@ __global__ __launch_bounds__(512, BN <= 64 ? 4 : 2) void conv_x6_halo_kernel(Con
                 af[i][0] = *(const u32x4*)(Ah + o);
                 af[i][1] = *(const u32x4*)(Ah + PL_H + o);
             }
-            bq[0][0] = *(const u32x4*)(Bs + swz(wn * S::WTN + (lane & 15), ch));
-            bq[0][1] = *(const u32x4*)(Bs + PL_B + swz(wn * S::WTN + (lane & 15), ch));
+            bq[0][0] = *(const u32x4*)(Bs + swz64(wn * S::WTN + (lane & 15), ch));
+            bq[0][1] = *(const u32x4*)(Bs + PL_B + swz64(wn * S::WTN + (lane & 15), ch));
             __builtin_amdgcn_sched_group_barrier(0x0100, 2 * TM + 2, 0);
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 if (j + 1 < TN) {
-                    bq[(j + 1) & 1][0] = *(const u32x4*)(Bs + swz(wn * S::WTN + (j + 1) * 16 + (lane & 15), ch));
-                    bq[(j + 1) & 1][1] = *(const u32x4*)(Bs + PL_B + swz(wn * S::WTN + (j + 1) * 16 + (lane & 15), ch));
+                    bq[(j + 1) & 1][0] = *(const u32x4*)(Bs + swz64(wn * S::WTN + (j + 1) * 16 + (lane & 15), ch));
+                    bq[(j + 1) & 1][1] = *(const u32x4*)(Bs + PL_B + swz64(wn * S::WTN + (j + 1) * 16 + (lane & 15), ch));
                     __builtin_amdgcn_sched_group_barrier(0x0100, 2, 0);
                 }
 #pragma unroll
                 for (int i = 0; i < TM; ++i) {
                     if constexpr (TR) acc[i][j] = mfma_pair_tr(af[i], bq[j & 1], acc[i][j]);
-                    else acc[i][j] = mfma_terms<2>(af[i], bq[j & 1], acc[i][j]);
+                    else acc[i][j] = mfma_pair(af[i], bq[j & 1], acc[i][j]);
                 }
                 __builtin_amdgcn_sched_group_barrier(0x0008, 3 * TM, 0);
                 if constexpr (MYD > 0 && TN % MYD == 0) {   // x6_halo_dma = 2: a DMA piece per group
@@ -1157,12 +1084,12 @@ __global__ __launch_bounds__(512, BN <= 64 ? 4 : 2) void conv_x6_halo_kernel(Con
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 u32x4 bf[3];
-                bf[0] = *(const u32x4*)(Bs + swz(wn * S::WTN + j * 16 + (lane & 15), ch));
-                bf[1] = *(const u32x4*)(Bs + PL_B + swz(wn * S::WTN + j * 16 + (lane & 15), ch));
+                bf[0] = *(const u32x4*)(Bs + swz64(wn * S::WTN + j * 16 + (lane & 15), ch));
+                bf[1] = *(const u32x4*)(Bs + PL_B + swz64(wn * S::WTN + j * 16 + (lane & 15), ch));
 #pragma unroll
                 for (int i = 0; i < TM; ++i) {
                     if constexpr (TR) acc[i][j] = mfma_pair_tr(af[i], bf, acc[i][j]);
-                    else acc[i][j] = mfma_terms<2>(af[i], bf, acc[i][j]);
+                    else acc[i][j] = mfma_pair(af[i], bf, acc[i][j]);
                 }
                 if constexpr (MYD > 0 && TN % MYD == 0) {   // x6_halo_dma = 2: a DMA piece per group
                     if (dstep >= 0 && j % (TN / MYD) == 0) dma_piece(dstep, dstep % NSB, j / (TN / MYD));
@@ -1354,7 +1281,7 @@ void conv1x1_x6_kernel(ConvArgs a, int nchunks, int groups) {
             const int j = row >> 4, ii = row & 15;
             const int chn = NTT == 1 ? row : 32 * (j >> 1) + 8 * (ii >> 2) + 4 * (j & 1) + (ii & 3);
             const u32x4 v = *(const u32x4*)((const char*)a.wx3 + ((((size_t)(n0 + chn) * nk + ks) * WT + p) * 64 + c * 16));
-            *(u32x4*)(smem + p * PL + ks * NCH * 64 + swz(row, c)) = v;
+            *(u32x4*)(smem + p * PL + ks * NCH * 64 + swz64(row, c)) = v;
         }
         for (int i = tid; i < NCH; i += 512) {
             s_scale[i] = a.scale[n0 + i];
@@ -1491,7 +1418,7 @@ void conv1x1_x6_kernel(ConvArgs a, int nchunks, int groups) {
                     u32x4 wf[3];
 #pragma unroll
                     for (int p = 0; p < WT; ++p)
-                        wf[p] = *(const u32x4*)(smem + p * PL + ks * NCH * 64 + swz(16 * j + p_lane, q));
+                        wf[p] = *(const u32x4*)(smem + p * PL + ks * NCH * 64 + swz64(16 * j + p_lane, q));
                     acc[j] = mfma_terms<TERMS>(wf, xb, acc[j]);
                 }
             }
@@ -1559,7 +1486,7 @@ void conv1x1_x6_kernel(ConvArgs a, int nchunks, int groups) {
                 u32x4 wf[3];
 #pragma unroll
                 for (int p = 0; p < WT; ++p)
-                    wf[p] = *(const u32x4*)(smem + p * PL + ks * NCH * 64 + swz(16 * j + p_lane, q));
+                    wf[p] = *(const u32x4*)(smem + p * PL + ks * NCH * 64 + swz64(16 * j + p_lane, q));
                 if constexpr (TERMS == 1) {   // w_lo x + w_hi x (x exact on one plane)
                     acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, wf[1]),
                                                                     __builtin_bit_cast(f16x8_t, xb[0]), acc[j], 0, 0, 0);
@@ -1677,7 +1604,7 @@ __global__ __launch_bounds__(512) void conv1x1_x6_dual_kernel(ConvArgs a, int nc
             const int j = row >> 4, ii = row & 15;
             const int chn = 32 * (j >> 1) + 8 * (ii >> 2) + 4 * (j & 1) + (ii & 3);
             const u32x4 v = *(const u32x4*)((const char*)wsrc + ((((size_t)(n0 + chn) * nk + ks) * 2 + p) * 64 + c * 16));
-            *(u32x4*)(dst + p * pl + ks * NCH * 64 + swz(row, c)) = v;
+            *(u32x4*)(dst + p * pl + ks * NCH * 64 + swz64(row, c)) = v;
         }
     };
     stage_w(a.wx3, a.kpad, KS, smem, PL);
@@ -1727,8 +1654,8 @@ __global__ __launch_bounds__(512) void conv1x1_x6_dual_kernel(ConvArgs a, int nc
             for (int j = 0; j < NTT; ++j) {
                 u32x4 wf[3];
 #pragma unroll
-                for (int p = 0; p < 2; ++p) wf[p] = *(const u32x4*)(wl + p * pl + ks * NCH * 64 + swz(16 * j + p_lane, q));
-                acc[j] = mfma_terms<2>(wf, xb, acc[j]);
+                for (int p = 0; p < 2; ++p) wf[p] = *(const u32x4*)(wl + p * pl + ks * NCH * 64 + swz64(16 * j + p_lane, q));
+                acc[j] = mfma_pair(wf, xb, acc[j]);
             }
         }
     };
@@ -2213,9 +2140,10 @@ void vd_pack_x6(const float* w, int npad, int kpad, uint16_t* out) {
             }
 }
 
-// Host: the fp16-pair layout [npad][kpad / 32][2][32] fp16 for f32_split = 2. Row n
-// is scaled by 2^e[n] so its largest |w| lies in [2^14, 2^15) (hi = RNE(w 2^e),
-// lo = RNE(w 2^e - hi)); row_inv[n] = 2^-e[n] is folded into the BN scale.
+// Host: the fp16-pair layout [npad][kpad / 32][2][32] fp16 for f32_split = 2: the pair
+// contract of vd_kernel.h on the weight rows. Row n is scaled by 2^e[n] so its largest
+// |w| lies in [2^14, 2^15) (hi = RNE(w 2^e), lo = RNE(w 2^e - hi)); row_inv[n] = 2^-e[n]
+// is folded into the BN scale.
 void vd_pack_x3h(const float* w, int npad, int kpad, uint16_t* out, float* row_inv) {
     const int nk = kpad / KT;
     for (int n = 0; n < npad; ++n) {

@@ -8,23 +8,14 @@
 // per 8 channels, mostly L2 hits, one 16-B store): one thread per (pixel, 16-B
 // channel vector), f32 accumulation over the taps in (dy, dx) order, the same
 // acc*scale + shift + activation epilogue as the dense convs.
-#include "vd_common.h"
+#include "vd_kernel.h"
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 template <typename T> struct DwVec;
 template <> struct DwVec<__bf16> { static constexpr int N = 8; };
 template <> struct DwVec<_Float16> { static constexpr int N = 8; };
 template <> struct DwVec<float>  { static constexpr int N = 4; };
-
-__device__ __forceinline__ float act_apply(float v, int act, float slope) {
-    if (act == VD_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == VD_ACT_LEAKY) return v > 0.f ? v : v * slope;
-    if (act == VD_ACT_SILU) return v / (1.0f + __expf(-v));
-    return v;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void dwconv3x3_kernel(DwConvArgs a) {

@@ -25,7 +25,7 @@
 //                      rows); every output byte is written once, by 16-B vector
 //                      stores in contiguous 1-KB wave spans (details at the kernel).
 // HBM traffic = read + write of every frame (2*W*H*3 bytes) + cell gathers (L2).
-#include "vd_common.h"
+#include "vd_kernel.h"
 #include "vd_math.h"
 
 #include <algorithm>
@@ -57,7 +57,6 @@ struct MosaicArgs {
     int map_on;                                      // bit 0: fast path on (option mosaic_map=0 forces the generic
                                                      // path); bit 1: non-temporal output stores, bit 2: loads
 };
-typedef unsigned mos_u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ int frame_boxes(const MosaicArgs& a, int f, int& n0) {
     n0 = a.cnt0 ? min(max(a.cnt0[f], 0), a.cap0) : 0;
@@ -802,11 +801,11 @@ __global__ __launch_bounds__(256) void mosaic_out_kernel(MosaicArgs a) {
         uint4 v0{}, v1{}, v2{}, v3{};
         const bool nt_st = a.map_on & 2, nt_ld = a.map_on & 4;
         auto ld = [&](int jj) -> uint4 {
-            if (nt_ld) return __builtin_bit_cast(uint4, __builtin_nontemporal_load((const mos_u32x4*)(s4 + jj)));
+            if (nt_ld) return __builtin_bit_cast(uint4, __builtin_nontemporal_load((const u32x4*)(s4 + jj)));
             return s4[jj];
         };
         auto st = [&](int jj, const uint4& v) {
-            if (nt_st) __builtin_nontemporal_store(__builtin_bit_cast(mos_u32x4, v), (mos_u32x4*)(d4 + jj));
+            if (nt_st) __builtin_nontemporal_store(__builtin_bit_cast(u32x4, v), (u32x4*)(d4 + jj));
             else d4[jj] = v;
         };
         auto load4 = [&](int jj, uint4& x0, uint4& x1, uint4& x2, uint4& x3) {

@@ -24,7 +24,7 @@ struct Act {          // NHWC activation buffer sized for cfg.max_batch frames
     int h = 0, w = 0, c = 0;   // c = channel stride
     bool f32 = false;
     // fp16-pair plan (f32_split = 2): per-frame running max |x| [max_batch] that every
-    // producer folds its outputs into (conv_x6.hip AmaxTrack), or a static bound
+    // producer folds its outputs into (vd_kernel.h AmaxTrack), or a static bound
     // for the letterboxed canvas (amax NULL)
     unsigned* amax = nullptr;
     float bound = 0.f;

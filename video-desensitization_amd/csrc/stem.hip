@@ -19,14 +19,11 @@
 //   - stage B: the 3x3/2 max of 64 pool pixels x 8 channel chunks (bf16 values >= 0
 //     after the ReLU compare as their bit patterns; zero padding = the -inf padding
 //     of the pool over non-negative inputs), 16-B stores.
-#include "vd_common.h"
+#include "vd_kernel.h"
 
 #include <cstdlib>
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void_t;
 
 constexpr int PT = 8;                     // pool tile (PT x PT outputs)
 constexpr int SE = 2 * PT + 1;            // stem tile edge (17)
@@ -38,12 +35,6 @@ constexpr int NDMA = (XP * 32 + 1023) / 1024;
 constexpr int DPW = (NDMA + 3) / 4;       // DMA instructions per wave (padded, see block.hip)
 constexpr int XBUF = NDMA * 1024;
 constexpr int STB = NG * 16 * 128;        // stem tile image: 304 rows x 64 channels bf16
-constexpr int VMCNT2 = 0x0F72;            // s_waitcnt vmcnt(2) (expcnt / lgkmcnt: no wait)
-
-__device__ __forceinline__ int st_off(int row, int chunk) {
-    return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
-}
-
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
 // max of two pairs of non-negative bf16 -- or fp16: both formats' non-negative bit
@@ -130,7 +121,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(StemPoolArgs a) {
         const char* lxc = lx + buf * XBUF;
         // this tile's X' (DMA): vmcnt counts loads, stores and LDS-DMA together in issue
         // order, and the previous tile's 2 stores per thread are the only younger ops
-        __builtin_amdgcn_s_waitcnt(VMCNT2);
+        __builtin_amdgcn_s_waitcnt(vmcnt_imm(2));
         __syncthreads();
         if (NXB == 2 && t + tstep < tend) issue_x(t + tstep, buf ^ 1);   // no register loads follow
         int li = li0, g = g0;
@@ -161,7 +152,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(StemPoolArgs a) {
                 const float v = acc[e >> 2][e & 3] * sc[e] + sh[e];
                 o[e] = (E16)(in && v > 0.f ? v : 0.f);
             }
-            *(typename HT::V8*)(lst + st_off(p, 4 * np + g)) = o;
+            *(typename HT::V8*)(lst + swz128(p, 4 * np + g)) = o;
         }
         __syncthreads();
         if (NXB == 1 && t + tstep < tend) issue_x(t + tstep, 0);   // X' buffer free once stage A is done
@@ -181,7 +172,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(StemPoolArgs a) {
                 for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
                     for (int dx = 0; dx < 3; ++dx) {
-                        const u32x4 v = *(const u32x4*)(lst + st_off((2 * pi + dy) * SE + 2 * pj + dx, ch));
+                        const u32x4 v = *(const u32x4*)(lst + swz128((2 * pi + dy) * SE + 2 * pj + dx, ch));
 #pragma unroll
                         for (int e = 0; e < 4; ++e) m[e] = max_bf16x2(m[e], v[e]);
                     }
@@ -248,7 +239,6 @@ constexpr int NDMA3 = (XP3 * 32 + 1023) / 1024;
 constexpr int DPW3 = (NDMA3 + 3) / 4;
 constexpr int XBUF3 = NDMA3 * 1024;
 constexpr int STB3 = NG3 * 16 * 256;       // 176 rows x 64 channels f32
-constexpr int VMCNT4 = 0x0F74;             // s_waitcnt vmcnt(4)
 
 // chunk: 16 B = 4 channels, 0..15. Key x ^ bit1(x) of x = row & 15: 16 consecutive
 // rows (stage A's 16 lanes) get 16 distinct keys, and rows r, r + 2 (stage B's two
@@ -335,7 +325,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool32_kernel(StemPoolArgs a) {
         const int sy0 = 2 * PT3 * ty - 1, sx0 = 2 * PT3 * tx - 1;
         // this tile's X' (DMA, issued a whole tile ago); the previous tile's 4 stores per
         // thread are the only younger ops
-        __builtin_amdgcn_s_waitcnt(VMCNT4);
+        __builtin_amdgcn_s_waitcnt(vmcnt_imm(4));
         __syncthreads();
         // the next tile's X' into the other buffer (stage A of the previous tile, its
         // last reader, finished before the barrier above)

@@ -1,42 +1,10 @@
-// vd_common.h — internal types shared by the HIP kernels and the runtime.
+// vd_common.h — what the host code and the kernels exchange: argument structs, VdTune,
+// launcher prototypes. Device helpers shared by the kernel files: vd_kernel.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 #include <stddef.h>
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-typedef unsigned vd_u32x4 __attribute__((ext_vector_type(4)));
-
-// The 16-bit operand type of the bf16 plan (F16 = false) and the fp16 plan (VD_PREC_FP16,
-// F16 = true): element type, 8-vector, the 16x16x32 matrix-core product, and the two
-// elements of a packed 32-bit word as f32. Conversions to T are round-to-nearest-even.
-template <bool F16> struct Half16;
-template <> struct Half16<false> {
-    typedef __bf16 T;
-    typedef bf16x8_t V8;
-    static __device__ __forceinline__ f32x4_t mfma(const vd_u32x4& a, const vd_u32x4& b, const f32x4_t& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b),
-                                                       c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ float lo(unsigned u) { return __uint_as_float(u << 16); }
-    static __device__ __forceinline__ float hi(unsigned u) { return __uint_as_float(u & 0xFFFF0000u); }
-};
-template <> struct Half16<true> {
-    typedef _Float16 T;
-    typedef f16x8_t V8;
-    static __device__ __forceinline__ f32x4_t mfma(const vd_u32x4& a, const vd_u32x4& b, const f32x4_t& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b),
-                                                      c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ float lo(unsigned u) {
-        return (float)__builtin_bit_cast(_Float16, (unsigned short)(u & 0xFFFFu));
-    }
-    static __device__ __forceinline__ float hi(unsigned u) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(u >> 16)); }
-};
 
 enum VdAct { VD_ACT_NONE = 0, VD_ACT_RELU = 1, VD_ACT_LEAKY = 2, VD_ACT_SILU = 3 };
 enum VdResMode { VD_RES_NONE = 0, VD_RES_PRE_ACT = 1, VD_RES_POST_ACT = 2 };
@@ -347,80 +315,6 @@ struct JpegArgs {
     int fx[3], fy[3], dw[3], dh[3];             // per component: upsampling factors, downsampled size
                                                 // (vd_launch_jpeg fills them)
 };
-
-// TERMS = 2 (fp16 pair): each frame's activations are scaled by a power of two so
-// their largest magnitude (the producer's per-frame running max, or a static bound
-// for the letterboxed canvas) lands in [2^14, 2^15): fp16 never overflows and the
-// low term stays normal down to 2^-2 of that. A row (pixel) keeps one scale over
-// all of K, so the accumulator is scaled back per row in the epilogue (exact:
-// powers of two), and a frame's result does not depend on the rest of its batch.
-// Returns the exponent k (operand * 2^k) for frame b.
-// the exponent from a frame's max |x| already loaded (act_scale_exp split for prefetching)
-__device__ __forceinline__ int act_scale_exp_of(float m) {
-    if (!(m > 0.f) || !(m < 3.0e38f)) return 0;
-    int e;
-    (void)frexpf(m, &e);                              // m < 2^e
-    const int k = 15 - e;
-    return k < -100 ? -100 : (k > 100 ? 100 : k);
-}
-
-__device__ __forceinline__ int act_scale_exp(const ConvArgs& a, int b) {
-    const float m = a.xmax ? __uint_as_float(a.xmax[b]) : a.xbound;
-    if (!(m > 0.f) || !(m < 3.0e38f)) return 0;
-    int e;
-    (void)frexpf(m, &e);                              // m < 2^e
-    const int k = 15 - e;
-    return k < -100 ? -100 : (k > 100 ? 100 : k);
-}
-
-// Per-frame running max |y| into the output's slots (non-negative floats order as
-// their bit patterns; NaNs are ignored). A lane folds its outputs into (frame, max)
-// and flushes on a frame change (rows only ascend, so rarely); at the end the wave
-// merges the lanes of its lowest frame into one atomic.
-struct AmaxTrack {
-    int b = -1;
-    float m = 0.f;
-    __device__ __forceinline__ void add(unsigned* slot, int fb, float v) {
-        if (fb != b) {
-            if (b >= 0 && m > 0.f) atomicMax(slot + b, __float_as_uint(m));
-            b = fb;
-            m = 0.f;
-        }
-        m = fmaxf(m, v);
-    }
-    __device__ __forceinline__ void publish(unsigned* slot) {
-        int lo = b >= 0 ? b : 0x7fffffff;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) lo = min(lo, __shfl_xor(lo, o));
-        float v = (b == lo) ? m : 0.f;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-        if ((threadIdx.x & 63) == 0 && lo != 0x7fffffff && v > 0.f) atomicMax(slot + lo, __float_as_uint(v));
-        if (b >= 0 && b != lo && m > 0.f) atomicMax(slot + b, __float_as_uint(m));
-    }
-};
-
-// Workgroup-local form for the conv kernels (one launch touches every frame, so
-// per-lane global atomics would serialise on 64 addresses): every lane of a wave
-// calls amax_lds_add convergently with its output's frame (-1: none) and max |y|;
-// the wave merges its lowest frame into one LDS atomic (other frames: rare, per
-// lane), and amax_lds_flush moves the workgroup's nonzero slots to global.
-__device__ __forceinline__ void amax_lds_add(unsigned* s, int fb, float v) {
-    int lo = fb >= 0 ? fb : 0x7fffffff;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) lo = min(lo, __shfl_xor(lo, o));
-    if (lo == 0x7fffffff) return;                     // wave-uniform
-    float m = (fb == lo) ? v : 0.f;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(s + lo, __float_as_uint(m));
-    if (fb >= 0 && fb != lo && v > 0.f) atomicMax(s + fb, __float_as_uint(v));
-}
-
-__device__ __forceinline__ void amax_lds_flush(const unsigned* s, unsigned* g, int nframes) {
-    for (int f = threadIdx.x; f < nframes; f += blockDim.x)
-        if (s[f]) atomicMax(g + f, s[f]);
-}
 
 // Device entropy decode (jpeg_dec.hip). JLds: one Huffman table set as the kernels
 // hold it in LDS (jpeg_host.cpp build_huff tables): 11-bit lookahead (len << 8 | sym)
