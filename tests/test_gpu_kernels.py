@@ -218,22 +218,15 @@ CONV_CASES = [
 ]
 
 
-@pytest.mark.parametrize("prec", ["fp32", "fp32-big", "fp32-mf32", "fp32-mid", "fp32-small", "fp32-halo1", "fp32-exact", "fp32-x6",
-                                  "fp32-x6-big", "fp32-x6-small", "fp32-s128", "fp32-s256", "bf16", "fp16", "bf16-gemm64",
-                                  "bf16-gemm128"])
-@pytest.mark.parametrize("case", CONV_CASES)
-def test_conv_matches_torch(gpu, face_ctx_factory, prec, case, options=None):
-    """fp32: the default fp32 plan (conv_x6.hip, scaled fp16 pairs on the f16 matrix
-    cores: streaming 1x1 for K in {64,128,256}, else the tiled GEMM; -big / -small
-    force its 256-row two-stage / 128-row one-stage tile; the hook also checks the
-    kernel's per-frame output max slots against the host max of the result);
-    fp32-exact: exact-f32 MFMA (option f32_split=0); fp32-x6(-big/-small): the exact
-    3-term bf16 split (option f32_split=1); bf16: the default dispatch
-    (streaming 1x1 / streaming taps / phased / GEMM); bf16-gemm64 / -gemm128: the
-    implicit GEMM with 64- and 128-row tiles forced through vd_set_option. The default
-    fp32 plan runs the 3x3 stride-1 shapes (Cin % 32 == 0, W <= 126) on the halo form
-    (three B stages; fp32-halo1: two); -big / -small / -mf32 switch it off so the
-    tap-major tiles keep their coverage on those shapes."""
+CONV_PRECS = ["fp32", "fp32-big", "fp32-mf32", "fp32-mid", "fp32-small", "fp32-halo1", "fp32-exact", "fp32-x6",
+              "fp32-x6-big", "fp32-x6-small", "fp32-s128", "fp32-s256", "bf16", "fp16", "bf16-gemm64", "bf16-gemm128"]
+# relative to max|y|, by context precision (test_conv_matches_torch)
+CONV_TOL = {"fp32": 2e-5, "fp16": 1e-3, "bf16": 2e-2}
+
+
+def conv_plan(prec, options=None):
+    """A prec name of CONV_PRECS (plus the caller's options) -> (context precision, options):
+    the plan each name selects is described in test_conv_matches_torch."""
     options = dict(options or {})
     if prec == "fp32-halo1":
         options.update(x6_halo=1)
@@ -262,6 +255,24 @@ def test_conv_matches_torch(gpu, face_ctx_factory, prec, case, options=None):
     if prec.startswith("bf16-gemm"):
         options.update(conv_taps=0, conv_stream=0, conv_big=0, conv_small=100000000 if prec == "bf16-gemm64" else 0)
         prec = "bf16"
+    return prec, options
+
+
+@pytest.mark.parametrize("prec", CONV_PRECS)
+@pytest.mark.parametrize("case", CONV_CASES)
+def test_conv_matches_torch(gpu, face_ctx_factory, prec, case, options=None):
+    """fp32: the default fp32 plan (conv_x6.hip, scaled fp16 pairs on the f16 matrix
+    cores: streaming 1x1 for K in {64,128,256}, else the tiled GEMM; -big / -small
+    force its 256-row two-stage / 128-row one-stage tile; the hook also checks the
+    kernel's per-frame output max slots against the host max of the result);
+    fp32-exact: exact-f32 MFMA (option f32_split=0); fp32-x6(-big/-small): the exact
+    3-term bf16 split (option f32_split=1); bf16: the default dispatch
+    (streaming 1x1 / streaming taps / phased / GEMM); bf16-gemm64 / -gemm128: the
+    implicit GEMM with 64- and 128-row tiles forced through vd_set_option. The default
+    fp32 plan runs the 3x3 stride-1 shapes (Cin % 32 == 0, W <= 126) on the halo form
+    (three B stages; fp32-halo1: two); -big / -small / -mf32 switch it off so the
+    tap-major tiles keep their coverage on those shapes."""
+    prec, options = conv_plan(prec, options)
     n, h, w, cin, cout, k, s, p, act, res_mode = case
     ctx = face_ctx_factory(prec, 8, options=tuple(sorted(options.items())))
     rng = np.random.default_rng(cin * 7 + cout)
@@ -286,7 +297,7 @@ def test_conv_matches_torch(gpu, face_ctx_factory, prec, case, options=None):
          3: lambda v: v / (1 + np.exp(-v))}[act](y)
     if res_mode == 2:
         y = y + res
-    tol = {"fp32": 2e-5, "fp16": 1e-3}.get(prec, 2e-2)
+    tol = CONV_TOL[prec]
     err = np.abs(got - y).max() / (np.abs(y).max() + 1e-6)
     assert got.shape == y.shape
     assert err < tol, f"rel err {err}"
@@ -325,7 +336,10 @@ BIG_CASES = [
 
 @pytest.mark.parametrize("case", BIG_CASES)
 def test_conv_big_matches_torch(gpu, face_ctx_factory, case):
-    """Force the phased 256x256 kernel onto small shapes (option conv_big = min tiles)."""
+    """The phased 256x256 kernel's options on small shapes (option conv_big = min tiles).
+    Through this hook the shapes stay on the implicit GEMM: vdt_conv2d asks for the f32
+    accumulator (out_f32 = 1), which vd_conv_big_ok refuses (conv_big.hip stores 16-bit
+    outputs only). Only whole-network runs of the 16-bit plans can reach the phased kernel."""
     test_conv_matches_torch(gpu, face_ctx_factory, "bf16", case,
                             options=dict(conv_big=1, conv_big_kmin=0, conv_stream=0))
 
