@@ -53,7 +53,7 @@ static const TuneField kTune[] = {
     {"x6_dbg", &VdTune::x6_dbg},         {"x6_halo_tr", &VdTune::x6_halo_tr},     {"x6_halo_dma", &VdTune::x6_halo_dma},
     {"x6_halo_pf", &VdTune::x6_halo_pf}, {"x6_gemm_pf", &VdTune::x6_gemm_pf},     {"x6_gemm_uni", &VdTune::x6_gemm_uni},
     {"x6_halo_1b", &VdTune::x6_halo_1b}, {"x6_stream_rl", &VdTune::x6_stream_rl}, {"x6_one", &VdTune::x6_one},
-    {"x6_mf32", &VdTune::x6_mf32},
+    {"x6_mf32", &VdTune::x6_mf32},       {"x6_small_k2", &VdTune::x6_small_k2},
 };
 
 static float frand(uint32_t& st) {

@@ -61,7 +61,7 @@ struct VdTune {
     int plate_stage = 3;      // plate branch starts after face stage N (0: with the stem; 1-4: after
                               //   layerN; 5: after the whole face net). After layer3 its HBM-bound
                               //   convs overlap the MFMA-bound late face layers: 30.8 -> 30.0 ms/step
-    int x6_stream = 1;        // fp32 split: streaming 1x1 kernel for K in {64, 128, 256}
+    int x6_stream = 1;        // fp32 split: streaming 1x1 kernel for K in {64, 128, 256} (conv_x6_stream.hip)
     int x6_stream_rl = 1;     //   streaming 1x1 with a residual: one input register set refilled per k-step, the
                               //   residual loaded at the top of each pixel group (beside the MFMAs), not in the epilogue
     int x6_stream_silu = 1;   //   fp16 pairs: also SiLU 1x1 convs (YOLO C2f / SPPF) with K in {32..256}
@@ -75,7 +75,7 @@ struct VdTune {
     int x6_mid = 512;         // fp16 pairs: 1x1 Cout-128 convs with K <= this on the 128 x 128 two-stage tile (0: off)
     int x6_mf32 = 0;          // fp16 pairs: 256 x {256,128} tiles on v_mfma_f32_32x32x16_f16 (else 16x16x32)
     int x6_halo = 2;          // fp16 pairs, 3x3 stride-1 convs: input split once per 32-channel chunk
-                              //   over the tile's linear halo (conv_x6_halo_kernel); 2: three B stages, 1: two
+                              //   over the tile's linear halo (conv_x6_halo.hip); 2: three B stages, 1: two
     int x6_halo_narrow = 1;   // ... also for Cout <= 64 (N tiles of 32 / 64)
     int x6_halo_s2 = 1;       // ... also 3x3 stride-2 convs (phase halos; Cout > 32)
     int x6_halo_1b = 1;       // halo tiles with two B stages (wide frames): one barrier per step (0: two)
@@ -389,8 +389,8 @@ bool vd_conv1x1_dual_ok(const ConvArgs& a);
 hipError_t vd_launch_conv_taps(const ConvArgs& a, hipStream_t s);
 hipError_t vd_launch_conv(const ConvArgs& a, bool f32, hipStream_t s);
 bool vd_conv_x6_ok(const ConvArgs& a);
-bool vd_conv1x1_x6_dual_ok(const ConvArgs& a);
-hipError_t vd_launch_conv_x6(const ConvArgs& a, hipStream_t s);
+bool vd_conv1x1_x6_dual_ok(const ConvArgs& a);   // conv_x6_stream.hip; launched through vd_launch_conv_x6 (a.x2)
+hipError_t vd_launch_conv_x6(const ConvArgs& a, hipStream_t s);   // a.tune set; the family's own entries: conv_x6.h
 void vd_pack_x6(const float* w, int npad, int kpad, uint16_t* out);   // host: f32 [npad][kpad] -> split planes
 void vd_pack_x3h(const float* w, int npad, int kpad, uint16_t* out, float* row_inv);   // ... fp16 pairs
 bool vd_block_ok(int cin, bool ds, int h, int w);
