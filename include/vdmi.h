@@ -14,6 +14,9 @@
  *                                                                    combine_detect.py:217
  *   vd_mosaic                    <- mosaic_rectangle_region_single  combine_detect.py:138-161,
  *                                   applied per box in order at     combine_detect.py:246-249
+ *   vd_blur                      <- the same loop with cv2.GaussianBlur(region, (k, k), sigma) in
+ *                                   place of the resize pair (BASELINE.json names it; the
+ *                                   reference has no such function)
  *   vd_process                   <- the per-batch body of batch_process_images
  *                                                                    combine_detect.py:214-251
  *   vd_jpeg_decode / vd_jpeg_info <- cv2.imread(path) + cvtColor(BGR2RGB) of the ffmpeg-split
@@ -80,6 +83,11 @@ extern "C" {
 /* vd_mosaic modes */
 #define VD_MOSAIC_OUT_OF_PLACE 0   /* out = in with boxes applied (reference new-array semantics) */
 
+/* vd_cfg.blur_mode: the anonymisation vd_process applies under VD_PROC_MOSAIC */
+#define VD_BLUR_PIXELATE 0         /* INTER_NEAREST down/up mosaic (combine_detect.py:138-161), the default */
+#define VD_BLUR_GAUSSIAN 1         /* Gaussian blur of each clipped box (vd_blur) */
+#define VD_BLUR_KSIZE_MAX 127
+
 /* vd_process flags */
 #define VD_PROC_FACES        1     /* run the RetinaFace branch */
 #define VD_PROC_PLATES       2     /* run the YOLOv8n branch (forward + NMS) */
@@ -104,7 +112,14 @@ typedef struct vd_cfg {
     float   plate_conf;            /* combine_detect.py:217 conf=0.5 */
     double  plate_iou;             /* ultralytics default 0.7 [ext] */
     int32_t plate_max_det;         /* ultralytics default 300 [ext] */
-    int32_t reserved[8];
+    /* the former reserved[8], offsets unchanged: zero in every field = the behaviour before
+     * they were named (no micro-batching, pixelation) */
+    int32_t microbatch;            /* frames per depth-first backbone micro-batch (0 = off) */
+    int32_t microbatch_stage;      /* micro-batch through layer<stage> (0 -> 2) */
+    int32_t blur_mode;             /* VD_BLUR_*: what vd_process's VD_PROC_MOSAIC applies to the boxes */
+    int32_t blur_ksize;            /* VD_BLUR_GAUSSIAN: odd kernel size in [3, 127]; 0 -> 31 */
+    float   blur_sigma;            /* VD_BLUR_GAUSSIAN: sigma; <= 0 -> 0.3*((k-1)*0.5 - 1) + 0.8 (cv2's rule) */
+    int32_t reserved[3];
 } vd_cfg;
 
 /* Per-frame box lists, caller-allocated. Frame f's boxes live at
@@ -162,6 +177,26 @@ int vd_detect_plates(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w, si
  * in separate device buffers, so host in == out is allowed there. */
 int vd_mosaic(vd_ctx* ctx, const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch,
               int where, const vd_boxes* boxes, int level, int mode);
+/* Gaussian blur of caller box lists: the Gaussian counterpart of vd_mosaic, with its
+ * staging rules (host frames / host boxes staged, VD_ERR_CAPACITY for a host list with
+ * count[f] > cap, VD_ERR_ARG for out == in or overlapping device ranges). Per box, in
+ * list order: clip to the frame (combine_detect.py:145-151), replace the clipped region
+ * by GaussianBlur(region, (ksize, ksize), sigma) of the region ALONE -- the border is
+ * BORDER_REFLECT_101 at the clipped box's edges (any number of reflections: boxes may be
+ * narrower than the radius) -- and box j reads the output of box j-1. Fixed point, so the
+ * result is defined to the bit (r = ksize / 2):
+ *   weights (host, double): w_i = exp(-(i-r)^2 / (2 sigma^2)) / sum; q_i = floor(w_i * 2^20 + 0.5)
+ *                           for i != r, q_r = 2^20 - sum of the others (vdt_blur_weights)
+ *   horizontal, per channel: t = sum_i q_i * px(y, refl(x+i-r, bw)); h = (t + 2^15) >> 16   (Q8.4)
+ *   vertical:                s = sum_i q_i * h(refl(y+i-r, bh), x);  out = (s + 2^23) >> 24
+ * which stays within 0.5925 of the real-valued Gaussian (|delta| <= 1 after rounding).
+ * ksize odd in [3, VD_BLUR_KSIZE_MAX]; sigma <= 0: 0.3*((ksize-1)*0.5 - 1) + 0.8; a NaN or
+ * infinite sigma, an even or out-of-range ksize: VD_ERR_ARG. */
+int vd_blur(vd_ctx* ctx, const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch,
+            int where, const vd_boxes* boxes, int ksize, float sigma);
+/* With VD_PROC_MOSAIC and cfg.blur_mode == VD_BLUR_GAUSSIAN the boxes are blurred as by
+ * vd_blur(cfg.blur_ksize, cfg.blur_sigma) instead of pixelated: the same complete keep
+ * lists, faces then plates; detection outputs are the same either way. */
 int vd_process(vd_ctx* ctx, const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch,
                int where, int flags, vd_boxes* faces, vd_boxes* plates);
 /* Baseline JPEG frames -> RGB frames: the frame read of the reference's loop
@@ -202,7 +237,7 @@ int vd_read_boxes(vd_ctx* ctx, int net, int n, vd_boxes* out);
  * on the context stream; vd_timing_read returns the summed duration (ms), the
  * launch count and the summed algorithmic work (FLOP or bytes) since the last
  * reset. Families: 0 = RetinaFace conv (implicit GEMM / streaming 1x1), 1 = mosaic
- * output pass, 2 = letterbox, 3 = post (decode/NMS), 4 = other, 5 = YOLOv8n plate
+ * output pass (or the Gaussian blur's launches), 2 = letterbox, 3 = post (decode/NMS), 4 = other, 5 = YOLOv8n plate
  * conv, 6 = mosaic cell table (box prep + walked cell colours). */
 int vd_timing_enable(vd_ctx* ctx, int on);
 int vd_timing_reset(vd_ctx* ctx);
@@ -266,6 +301,10 @@ int vd_record_repack_h265(const char* record_dir, const char* videos_dir, const 
 /* The last vd_jpeg_decode's device entropy stage: synchronisation passes run (pass 0
  * included; 0 when the host entropy stage ran). */
 int vdt_jdec_stats(vd_ctx* ctx, int* passes);
+
+/* The Q20 tap weights q[ksize] of vd_blur (host only: no context, no GPU): the routine the
+ * launch path itself calls. VD_ERR_ARG for an even / out-of-range ksize or a non-finite sigma. */
+int vdt_blur_weights(int ksize, float sigma, uint32_t* q);
 
 #ifdef __cplusplus
 }

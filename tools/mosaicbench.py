@@ -6,6 +6,10 @@ time of one vd_mosaic call (HIP events around it) and the HBM rate over the
 algorithmic 2*W*H*3 bytes per frame.
 
     python tools/mosaicbench.py [--iters 50]
+    python tools/mosaicbench.py --mode gaussian [--ksize 31] [--sigma 0] [--json PATH]
+
+--mode gaussian times vd_blur on the same box sets beside vd_mosaic in the same run (the
+pixelation is the yardstick) and reports the ratio per box set.
 """
 import argparse
 import json
@@ -20,11 +24,21 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
+def _area(bx, bc, H, W):
+    """Summed clipped area of the listed boxes (pixels, overlaps counted twice)."""
+    return sum(int(max(0, min(W, b[2]) - max(0, b[0])) * max(0, min(H, b[3]) - max(0, b[1])))
+               for f in range(len(bc)) for b in bx[f, :bc[f]])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--option", action="append", default=[], help="name=value (vd_set_option)")
+    ap.add_argument("--mode", choices=("pixelate", "gaussian"), default="pixelate")
+    ap.add_argument("--ksize", type=int, default=31)
+    ap.add_argument("--sigma", type=float, default=0.0)
+    ap.add_argument("--json", help="also write the result line to this file")
     a = ap.parse_args()
     import vdmi
     from vdmi import _lib, synth, weights
@@ -37,7 +51,10 @@ def main():
         ctx.set_option(k, int(v))
     frames = torch.from_numpy(synth.frames(B, H, W, seed=0)).to(dev)
     out = torch.empty_like(frames)
-    stream = torch.cuda.current_stream(dev)
+    # a stream of its own: the default stream's handle is 0, which vd_set_stream reads as
+    # "the library's own stream" -- the events below would then time nothing
+    stream = torch.cuda.Stream(dev)
+    torch.cuda.synchronize()
     ctx.set_stream(stream.cuda_stream)
     faces = vdmi.DeviceBoxes(B, 256, dev)
     ctx.process(frames, out, faces=faces, flags=_lib.VD_PROC_FACES)
@@ -63,17 +80,34 @@ def main():
             _lib.check(ctx._lib.vd_mosaic(ctx._h, frames.data_ptr(), out.data_ptr(), B, H, W, W * 3,
                                           _lib.VD_DEVICE, __import__("ctypes").byref(s), 8,
                                           _lib.VD_MOSAIC_OUT_OF_PLACE))
-        for _ in range(3):
-            call()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.iters):
-            call()
-        e1.record()
-        torch.cuda.synchronize()
-        us = e0.elapsed_time(e1) / a.iters * 1e3
-        res[name] = {"us": round(us, 1), "GB/s": round(2.0 * B * H * W * 3 / (us * 1e-6) / 1e9, 1)}
-    print(json.dumps(res), flush=True)
+
+        def call_blur():
+            _lib.check(ctx._lib.vd_blur(ctx._h, frames.data_ptr(), out.data_ptr(), B, H, W, W * 3,
+                                        _lib.VD_DEVICE, __import__("ctypes").byref(s), a.ksize, a.sigma))
+
+        def timed(fn):
+            for _ in range(3):
+                fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(a.iters):
+                fn()
+            e1.record(stream)
+            torch.cuda.synchronize()
+            us = e0.elapsed_time(e1) / a.iters * 1e3
+            return {"us": round(us, 1), "GB/s": round(2.0 * B * H * W * 3 / (us * 1e-6) / 1e9, 1)}
+        res[name] = timed(call)
+        if a.mode == "gaussian":
+            g = timed(call_blur)
+            res[name] = {"pixelate": res[name], "gaussian": g, "ratio": round(g["us"] / res[name]["us"], 3),
+                         "box_area_per_frame": _area(bx, bc, H, W) / B}
+    if a.mode == "gaussian":
+        res.update(mode="gaussian", ksize=a.ksize, sigma=a.sigma, batch=B, frame=[H, W])
+    line = json.dumps(res)
+    print(line, flush=True)
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(line + "\n")
     ctx.close()
 
 

@@ -189,6 +189,7 @@ struct Ctx {
     void* stage_box = nullptr; size_t stage_box_bytes = 0;
     void* stage_box2 = nullptr; size_t stage_box2_bytes = 0;
     void* mosaic_table = nullptr; size_t mosaic_table_bytes = 0;
+    void* blur_table = nullptr; size_t blur_table_bytes = 0;   // Gaussian mode: box plan + dependent-box scratch
     // JPEG frame decode (jpeg_host.cpp): pinned host staging, device copy, planes
     void* jpeg_host = nullptr; size_t jpeg_host_bytes = 0;
     void* jpeg_dev = nullptr; size_t jpeg_dev_bytes = 0;
@@ -267,6 +268,8 @@ struct Ctx {
     int face_post(int n, int img_h, int img_w, const BoxTargets& t);
     int launch_mosaic(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
                       const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int level);
+    int launch_blur(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
+                    const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int ksize, float sigma);
 };
 
 int vd_alloc_post(Ctx& ctx, PostScratch& ps, int A, int kcap);

@@ -871,8 +871,8 @@ void Ctx::face_letterbox_args(const uint8_t* dframes, int n, int h, int w, size_
 }
 
 int Ctx::face_forward(int n) {
-    const int mb = cfg.reserved[0];                       // frames per micro-batch (0 = off)
-    const int stage = cfg.reserved[1] > 0 ? cfg.reserved[1] : 2;   // micro-batch through layer<stage>
+    const int mb = cfg.microbatch;                        // frames per micro-batch (0 = off)
+    const int stage = cfg.microbatch_stage > 0 ? cfg.microbatch_stage : 2;   // micro-batch through layer<stage>
     const int split = face.net.stage_end[std::min(std::max(stage, 0), 4)];
     const int G = std::min(std::min(tune.face_groups, 4), n);
     if (G >= 2 && mb <= 0 && lane_ev.empty()) {
@@ -977,6 +977,25 @@ int Ctx::launch_mosaic(const uint8_t* in, uint8_t* out, int n, int h, int w, siz
     return VD_OK;
 }
 
+// Gaussian mode: plan kernel, band pass (copy + independent boxes), dependent-box pass,
+// bracketed as one family-1 interval with the mosaic's algorithmic bytes.
+int Ctx::launch_blur(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
+                     const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int ksize, float sigma) {
+    uint32_t q[VD_BLUR_KSIZE_MAX];
+    if (vd_blur_weights(ksize, sigma, q))
+        return vd_set_error(VD_ERR_ARG, "blur: ksize must be odd in [3, %d] (got %d) and sigma finite",
+                            VD_BLUR_KSIZE_MAX, ksize);
+    const int tcap = (cnt0 ? cap0 : 0) + (cnt1 ? cap1 : 0);
+    int rc = ensure_staging(&blur_table, &blur_table_bytes, vd_blur_table_bytes(n, h, pitch, tcap));
+    if (rc) return rc;
+    t_begin(1, 2.0 * n * (double)h * w * 3);
+    hipError_t e = vd_launch_blur(in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, ksize, q, blur_table,
+                                  stream);
+    t_end();
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "blur: %s", hipGetErrorString(e));
+    return VD_OK;
+}
+
 // ----------------------------------------------------------------------------
 // C-ABI
 // ----------------------------------------------------------------------------
@@ -1020,6 +1039,15 @@ int vd_create(const vd_cfg* cfg, int device, vd_ctx** out) {
     if (c.precision != VD_PREC_BF16 && c.precision != VD_PREC_FP32 && c.precision != VD_PREC_FP16)
         return vd_set_error(VD_ERR_ARG, "cfg: bad precision");
     if (c.mosaic_level <= 0) c.mosaic_level = 8;
+    if (c.blur_mode != VD_BLUR_PIXELATE && c.blur_mode != VD_BLUR_GAUSSIAN)
+        return vd_set_error(VD_ERR_ARG, "cfg: bad blur_mode %d", c.blur_mode);
+    if (c.blur_mode == VD_BLUR_GAUSSIAN) {
+        if (c.blur_ksize == 0) c.blur_ksize = 31;
+        uint32_t q[VD_BLUR_KSIZE_MAX];
+        if (vd_blur_weights(c.blur_ksize, c.blur_sigma, q))
+            return vd_set_error(VD_ERR_ARG, "cfg: blur_ksize must be odd in [3, %d] (got %d) and blur_sigma finite",
+                                VD_BLUR_KSIZE_MAX, c.blur_ksize);
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
         return vd_set_error(VD_ERR_HIP, "no HIP device %d (count %d)", device, ndev);
@@ -1061,6 +1089,7 @@ int vd_destroy(vd_ctx* h) {
     if (ctx->stage_box) hipFree(ctx->stage_box);
     if (ctx->stage_box2) hipFree(ctx->stage_box2);
     if (ctx->mosaic_table) hipFree(ctx->mosaic_table);
+    if (ctx->blur_table) hipFree(ctx->blur_table);
     if (ctx->jpeg_dev) hipFree(ctx->jpeg_dev);
     if (ctx->jpeg_planes) hipFree(ctx->jpeg_planes);
     if (ctx->jpeg_host) hipHostFree(ctx->jpeg_host);
@@ -1274,6 +1303,62 @@ int vd_mosaic(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw,
     return VD_OK;
 }
 
+int vd_blur(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw, size_t pitch, int where,
+            const vd_boxes* boxes, int ksize, float sigma) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    {
+        uint32_t q[VD_BLUR_KSIZE_MAX];
+        if (vd_blur_weights(ksize, sigma, q))
+            return vd_set_error(VD_ERR_ARG, "vd_blur: ksize must be odd in [3, %d] (got %d) and sigma finite",
+                                VD_BLUR_KSIZE_MAX, ksize);
+    }
+    if (!in || !out || !boxes || !boxes->count || !boxes->xyxy || boxes->cap <= 0)
+        return vd_set_error(VD_ERR_ARG, "vd_blur: null argument");
+    if (n <= 0 || fh <= 0 || fw <= 0 || pitch < (size_t)fw * 3)
+        return vd_set_error(VD_ERR_ARG, "vd_blur: bad geometry");
+    if ((const void*)in == (const void*)out ||
+        (where == VD_DEVICE && vd_ranges_overlap(in, out, (size_t)n * fh * pitch)))
+        return vd_set_error(VD_ERR_ARG, "vd_blur: out-of-place only (out must not overlap in)");
+    int rc = VD_OK;
+    const uint8_t* din = in;
+    uint8_t* dout = out;
+    size_t bytes = (size_t)n * fh * pitch;
+    if (where == VD_HOST) {
+        if ((rc = ctx->ensure_staging(&ctx->stage_in, &ctx->stage_in_bytes, bytes))) return rc;
+        if ((rc = ctx->ensure_staging(&ctx->stage_out, &ctx->stage_out_bytes, bytes))) return rc;
+        VD_CHECK_HIP(hipMemcpyAsync(ctx->stage_in, in, bytes, hipMemcpyHostToDevice, ctx->stream));
+        din = (const uint8_t*)ctx->stage_in;
+        dout = (uint8_t*)ctx->stage_out;
+    }
+    const int* cnt = boxes->count;
+    const int* xy = boxes->xyxy;
+    if (boxes->where == VD_HOST)   // a count past cap means boxes the caller does not hold: never skip them silently
+        for (int i = 0; i < n; ++i)
+            if (boxes->count[i] > boxes->cap)
+                return vd_set_error(VD_ERR_CAPACITY, "vd_blur: frame %d has count %d > cap %d (read the complete "
+                                    "list with vd_read_boxes)", i, boxes->count[i], boxes->cap);
+    if (boxes->where == VD_HOST) {
+        size_t nb = (size_t)n * boxes->cap;
+        if ((rc = ctx->ensure_staging(&ctx->stage_box2, &ctx->stage_box2_bytes, n * 4 + nb * 16 + 16))) return rc;
+        int* dc = (int*)ctx->stage_box2;
+        int* dx = dc + ((n + 3) / 4) * 4;
+        VD_CHECK_HIP(hipMemcpyAsync(dc, boxes->count, n * 4, hipMemcpyHostToDevice, ctx->stream));
+        VD_CHECK_HIP(hipMemcpyAsync(dx, boxes->xyxy, nb * 16, hipMemcpyHostToDevice, ctx->stream));
+        cnt = dc;
+        xy = dx;
+    }
+    if ((rc = ctx->launch_blur(din, dout, n, fh, fw, pitch, cnt, xy, boxes->cap, nullptr, nullptr, 0, ksize, sigma)))
+        return rc;
+    if (where == VD_HOST) {
+        VD_CHECK_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    } else if (boxes->where == VD_HOST) {
+        VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // staging reused by the next call
+    }
+    return VD_OK;
+}
+
 int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw, size_t pitch, int where,
                int flags, vd_boxes* faces, vd_boxes* plates) {
     Ctx* ctx = (Ctx*)h;
@@ -1371,10 +1456,15 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
         // may hold fewer: cap), faces in NMS order then plates (combine_detect.py:241-249)
         const PostScratch& fp = ctx->face.post;
         const PostScratch& pp = ctx->plate.post;
-        int r = ctx->launch_mosaic(d, dout, n, fh, fw, pitch, do_faces ? fp.kcount : nullptr,
-                                   do_faces ? fp.kxyxy : nullptr, do_faces ? fp.kcap : 0,
-                                   mosaic_plates ? pp.kcount : nullptr, mosaic_plates ? pp.kxyxy : nullptr,
-                                   mosaic_plates ? pp.kcap : 0, ctx->cfg.mosaic_level);
+        const int* c0 = do_faces ? fp.kcount : nullptr;
+        const int* x0 = do_faces ? fp.kxyxy : nullptr;
+        const int* c1 = mosaic_plates ? pp.kcount : nullptr;
+        const int* x1 = mosaic_plates ? pp.kxyxy : nullptr;
+        const int k0 = do_faces ? fp.kcap : 0, k1 = mosaic_plates ? pp.kcap : 0;
+        int r = ctx->cfg.blur_mode == VD_BLUR_GAUSSIAN
+                    ? ctx->launch_blur(d, dout, n, fh, fw, pitch, c0, x0, k0, c1, x1, k1, ctx->cfg.blur_ksize,
+                                       ctx->cfg.blur_sigma)
+                    : ctx->launch_mosaic(d, dout, n, fh, fw, pitch, c0, x0, k0, c1, x1, k1, ctx->cfg.mosaic_level);
         if (r) return r;
         if (where == VD_HOST) VD_CHECK_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
         return VD_OK;
@@ -1415,6 +1505,14 @@ int vd_read_boxes(vd_ctx* h, int net, int n, vd_boxes* out) {
     if (out->label)
         VD_CHECK_HIP(hipMemcpy2DAsync(out->label, dp * 4, ps->klabel, sp * 4, (size_t)w * 4, n, kind, ctx->stream));
     if (out->where == VD_HOST) VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    return VD_OK;
+}
+
+int vdt_blur_weights(int ksize, float sigma, uint32_t* q) {
+    if (!q) return vd_set_error(VD_ERR_ARG, "vdt_blur_weights: null q");
+    if (vd_blur_weights(ksize, sigma, q))
+        return vd_set_error(VD_ERR_ARG, "vdt_blur_weights: ksize must be odd in [3, %d] (got %d) and sigma finite",
+                            VD_BLUR_KSIZE_MAX, ksize);
     return VD_OK;
 }
 

@@ -421,6 +421,14 @@ hipError_t vd_launch_mosaic(const uint8_t* in, uint8_t* out, int n, int h, int w
                             const int* cnt1, const int* xy1, int cap1, int level, void* table,
                             int stages, int map_on, int cell_blocks, hipStream_t s);   // stages: 1 = cell table, 2 = output pass, 4 = copy
 size_t vd_mosaic_table_bytes(int n, int tcap);
+// Gaussian blur of box lists (blur.hip): plan + band pass + dependent-box pass on `s`.
+// q: the ksize Q20 weights of vd_blur_weights; table: vd_blur_table_bytes(n, h, pitch, tcap) bytes.
+hipError_t vd_launch_blur(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch,
+                          const int* cnt0, const int* xy0, int cap0,
+                          const int* cnt1, const int* xy1, int cap1, int ksize, const uint32_t* q,
+                          void* table, hipStream_t s);
+size_t vd_blur_table_bytes(int n, int h, size_t pitch, int tcap);
+int vd_blur_weights(int ksize, float sigma, uint32_t* q);   // host; 0, or -1 for a refused ksize / sigma
 
 #define VD_CHECK_HIP(expr)                                                     \
     do {                                                                       \

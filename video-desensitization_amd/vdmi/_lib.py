@@ -19,6 +19,8 @@ VD_PREC_BF16, VD_PREC_FP32, VD_PREC_FP16 = 0, 1, 2
 VD_NET_RETINAFACE, VD_NET_YOLOV8N = 0, 1
 VD_WEIGHTS_VDW1 = 1
 VD_MOSAIC_OUT_OF_PLACE = 0
+VD_BLUR_PIXELATE, VD_BLUR_GAUSSIAN = 0, 1
+VD_BLUR_KSIZE_MAX = 127
 VD_PROC_FACES, VD_PROC_PLATES, VD_PROC_MOSAIC, VD_PROC_MOSAIC_PLATES = 1, 2, 4, 8
 FAM_CONV, FAM_MOSAIC, FAM_LETTERBOX, FAM_POST, FAM_OTHER, FAM_PLATE_CONV, FAM_MOSAIC_CELLS = 0, 1, 2, 3, 4, 5, 6
 
@@ -46,7 +48,10 @@ class vd_cfg(ctypes.Structure):
                 ("plate_imgsz", ctypes.c_int32), ("plate_nc", ctypes.c_int32),
                 ("plate_conf", ctypes.c_float), ("plate_iou", ctypes.c_double),
                 ("plate_max_det", ctypes.c_int32),
-                ("reserved", ctypes.c_int32 * 8)]
+                ("microbatch", ctypes.c_int32), ("microbatch_stage", ctypes.c_int32),
+                ("blur_mode", ctypes.c_int32), ("blur_ksize", ctypes.c_int32),
+                ("blur_sigma", ctypes.c_float),
+                ("reserved", ctypes.c_int32 * 3)]
 
 
 class vd_boxes(ctypes.Structure):
@@ -72,6 +77,7 @@ SIGNATURES = [
     ("vd_detect", _I, [_P, _P, _I, _I, _I, _SZ, _I, ctypes.POINTER(vd_boxes)]),
     ("vd_detect_plates", _I, [_P, _P, _I, _I, _I, _SZ, _I, ctypes.POINTER(vd_boxes)]),
     ("vd_mosaic", _I, [_P, _P, _P, _I, _I, _I, _SZ, _I, ctypes.POINTER(vd_boxes), _I, _I]),
+    ("vd_blur", _I, [_P, _P, _P, _I, _I, _I, _SZ, _I, ctypes.POINTER(vd_boxes), _I, _F]),
     ("vd_process", _I, [_P, _P, _P, _I, _I, _I, _SZ, _I, _I, ctypes.POINTER(vd_boxes),
                         ctypes.POINTER(vd_boxes)]),
     ("vd_read_boxes", _I, [_P, _I, _I, ctypes.POINTER(vd_boxes)]),
@@ -92,6 +98,7 @@ SIGNATURES = [
     ("vdt_jpeg_coefficients", _I, [_P, _SZ, _P, _SZ, ctypes.POINTER(_I)]),
     ("vdt_jdec_stats", _I, [_P, ctypes.POINTER(_I)]),
     ("vdt_set_debug", _I, [_P, ctypes.c_char_p, _I]),
+    ("vdt_blur_weights", _I, [_I, _F, _P]),
     ("vd_record_extract_h265", _I, [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_I)]),
     ("vd_record_repack_h265", _I, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_I)]),
 ]
@@ -144,6 +151,15 @@ def default_cfg():
     c = vd_cfg()
     check(load().vd_default_cfg(ctypes.byref(c)))
     return c
+
+
+def blur_weights(ksize, sigma=0.0):
+    """The Q20 tap weights of the Gaussian mode (vdt_blur_weights: host only, the routine the
+    launch path uses) as uint32 [ksize]; VdError for an even / out-of-range ksize or a
+    non-finite sigma."""
+    q = np.zeros(VD_BLUR_KSIZE_MAX, np.uint32)
+    check(load().vdt_blur_weights(int(ksize), float(sigma), ptr(q)))
+    return q[:int(ksize)].copy()
 
 
 class HostBoxes:

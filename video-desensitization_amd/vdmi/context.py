@@ -16,11 +16,24 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
-def _frames_arg(frames):
-    """-> (pointer, n, h, w, pitch, where, keepalive)."""
+def _row_padded(t):
+    """A torch [n,h,w,3] view whose rows are padded (t = big[:, :, :w]): packed pixels,
+    row pitch stride(1) >= 3w, frame i at base + i*h*pitch -- the C-ABI's frame layout."""
+    n, h, w, _ = t.shape
+    st = t.stride()
+    return st[3] == 1 and st[2] == 3 and st[1] >= 3 * w and (n == 1 or st[0] == h * st[1])
+
+
+def _frames_arg(frames, pitched=False):
+    """-> (pointer, n, h, w, pitch, where, keepalive). pitched: a torch view with padded
+    rows is passed as it is (its row pitch) instead of being packed into a copy."""
     if _is_torch(frames):
         if frames.dtype.__str__() != "torch.uint8" or frames.dim() != 4 or frames.shape[3] != 3:
             raise ValueError("frames must be uint8 [n,h,w,3]")
+        if pitched and not frames.is_contiguous() and _row_padded(frames):
+            n, h, w, _ = frames.shape
+            where = _lib.VD_DEVICE if frames.is_cuda else _lib.VD_HOST
+            return frames.data_ptr(), n, h, w, frames.stride(1), where, frames
         if not frames.is_contiguous():
             frames = frames.contiguous()
         n, h, w, _ = frames.shape
@@ -79,12 +92,22 @@ class DeviceBoxes:
         return v
 
 
+BLUR_MODES = {"pixelate": _lib.VD_BLUR_PIXELATE, "gaussian": _lib.VD_BLUR_GAUSSIAN}
+
+
 class Context:
     """vd_create/vd_destroy with the reference-facing knobs as keyword args."""
 
     def __init__(self, device=0, precision="bf16", max_batch=64, input_shape=(640, 640), confidence=0.5,
                  nms_iou=0.4, max_boxes=256, mosaic_level=8, plate_nc=1, plate_conf=0.5, plate_iou=0.7,
-                 plate_max_det=300, plate_imgsz=640, microbatch=0, microbatch_stage=2, options=None):
+                 plate_max_det=300, plate_imgsz=640, microbatch=0, microbatch_stage=2, options=None,
+                 blur="pixelate", blur_ksize=31, blur_sigma=0.0):
+        """blur: what process() applies to the kept boxes: "pixelate" (the reference's
+        INTER_NEAREST mosaic, the default) or "gaussian" (GaussianBlur(region, (blur_ksize,
+        blur_ksize), blur_sigma) per clipped box, in list order; blur_ksize odd in [3, 127],
+        blur_sigma <= 0: cv2's rule from the kernel size)."""
+        if blur not in BLUR_MODES:
+            raise ValueError(f"blur {blur!r}: expected 'pixelate' or 'gaussian'")
         lib = _lib.load()
         cfg = _lib.default_cfg()
         cfg.input_h, cfg.input_w = int(input_shape[0]), int(input_shape[1])
@@ -103,8 +126,11 @@ class Context:
         cfg.mosaic_level = int(mosaic_level)
         cfg.plate_nc, cfg.plate_conf, cfg.plate_iou = int(plate_nc), float(plate_conf), float(plate_iou)
         cfg.plate_max_det, cfg.plate_imgsz = int(plate_max_det), int(plate_imgsz)
-        # depth-first micro-batching of the backbone through layer<stage> (reserved[0..1])
-        cfg.reserved[0], cfg.reserved[1] = int(microbatch), int(microbatch_stage)
+        # depth-first micro-batching of the backbone through layer<stage>
+        cfg.microbatch, cfg.microbatch_stage = int(microbatch), int(microbatch_stage)
+        cfg.blur_mode = BLUR_MODES[blur]
+        if cfg.blur_mode == _lib.VD_BLUR_GAUSSIAN:      # pixelate leaves the fields zero
+            cfg.blur_ksize, cfg.blur_sigma = int(blur_ksize), float(blur_sigma)
         self.cfg = cfg
         self.device = int(device)
         self.precision = {_lib.VD_PREC_FP32: "fp32", _lib.VD_PREC_FP16: "fp16"}.get(cfg.precision, "bf16")
@@ -223,6 +249,44 @@ class Context:
         optr = out.data_ptr() if _is_torch(out) else ptr(out)
         check(self._lib.vd_mosaic(self._h, p, optr, n, h, w, pitch, where, ctypes.byref(s),
                                   int(level or self.cfg.mosaic_level), _lib.VD_MOSAIC_OUT_OF_PLACE))
+        return out
+
+    def blur(self, frames, boxes_xyxy, counts=None, ksize=None, sigma=None, out=None):
+        """Out-of-place Gaussian blur of the boxes (vd_blur), the counterpart of mosaic():
+        the same frames / boxes_xyxy / counts forms. ksize / sigma default to the context's
+        blur_ksize / blur_sigma (31 / 0 in a pixelate context). A torch view with padded
+        rows (big[:, :, :w]) is read and written at its own row pitch."""
+        p, n, h, w, pitch, where, src = _frames_arg(frames, pitched=True)
+        if isinstance(boxes_xyxy, (_lib.HostBoxes, DeviceBoxes)):
+            s = boxes_xyxy.struct()
+        else:
+            xy = np.ascontiguousarray(boxes_xyxy, np.int32).reshape(n, -1, 4)
+            cnt = np.ascontiguousarray(counts if counts is not None else np.full(n, xy.shape[1]), np.int32)
+            cap = max(1, xy.shape[1])
+            if xy.shape[1] == 0:
+                xy = np.zeros((n, 1, 4), np.int32)
+            s = _lib.vd_boxes(cap, _lib.VD_HOST, ptr(cnt), ptr(xy), None, None, None)
+        if out is None:
+            if pitch != w * 3:
+                raise ValueError("frames with padded rows need out= (a view with the same row pitch)")
+            if where == _lib.VD_HOST:
+                out = np.empty((n, h, w, 3), np.uint8)
+            else:
+                import torch
+                out = torch.empty_like(src)
+        if _is_torch(out):
+            packed = out.is_contiguous()
+            if tuple(out.shape) != (n, h, w, 3) or not (packed or _row_padded(out)) or \
+                    (w * 3 if packed else out.stride(1)) != pitch:
+                raise ValueError("out must be uint8 [n,h,w,3] with the frames' row pitch")
+            optr = out.data_ptr()
+        else:
+            optr = ptr(out)
+        if ksize is None:
+            ksize = self.cfg.blur_ksize or 31
+        if sigma is None:
+            sigma = self.cfg.blur_sigma
+        check(self._lib.vd_blur(self._h, p, optr, n, h, w, pitch, where, ctypes.byref(s), int(ksize), float(sigma)))
         return out
 
     def process(self, frames, out=None, faces=None, plates=None, flags=None):

@@ -21,7 +21,9 @@ Differences, all deliberate:
   within 6e-6 of the torch-CPU fp32 forward; option ``f32_split=0`` runs exact-f32
   MFMA instead; "bf16" / "fp16" trade box parity for 2-3x throughput, see
   INTEGRATION.md), ``max_batch``, ``device_ids`` / ``device_index``, ``seed``,
-  ``weights`` (a state_dict, or "random"), ``options`` (kernel-selection switches).
+  ``weights`` (a state_dict, or "random"), ``options`` (kernel-selection switches),
+  ``blur`` / ``blur_ksize`` / ``blur_sigma`` (Context's: "gaussian" makes the fused
+  ``batch_process_images`` path blur the boxes instead of pixelating them).
 * Devices (face.py:55-56 wraps the net in ``nn.DataParallel``: every forward is
   split over ALL visible GPUs, the weights re-broadcast each time): one context per
   device, weights uploaded once each; ``detect_images`` cuts the image list into
@@ -89,6 +91,10 @@ class Retinaface(object):
         "seed": 0,
         "weights": None,
         "max_boxes": 256,
+        # what a fused vd_process (vdmi.pipeline) applies to the boxes: Context(blur=...)
+        "blur": "pixelate",
+        "blur_ksize": 31,
+        "blur_sigma": 0.0,
     }
 
     @classmethod
@@ -115,7 +121,8 @@ class Retinaface(object):
         self.options = getattr(self, "options", None)
         self.ctxs = [Context(device=d, precision=self.precision, max_batch=self.max_batch,
                              input_shape=self.input_shape[:2], confidence=self.confidence, nms_iou=self.nms_iou,
-                             max_boxes=self.max_boxes, options=self.options) for d in self.device_ids]
+                             max_boxes=self.max_boxes, options=self.options, blur=self.blur,
+                             blur_ksize=self.blur_ksize, blur_sigma=self.blur_sigma) for d in self.device_ids]
         self.ctx = self.ctxs[0]
         self.generate()
 

@@ -31,7 +31,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import _lib
-from .mosaic import mosaic_frames
+from .mosaic import blur_frames, mosaic_frames
 
 IMAGE_EXT = (".png", ".jpg", ".jpeg")
 
@@ -471,10 +471,21 @@ def _new_fused_context(fd, pd, batch_size, dev):
                   input_shape=fd.input_shape[:2], confidence=fd.confidence, nms_iou=fd.nms_iou,
                   max_boxes=fd.max_boxes, plate_nc=pd.nc, plate_conf=pd.ctx.cfg.plate_conf,
                   plate_iou=pd.ctx.cfg.plate_iou, plate_max_det=pd.ctx.cfg.plate_max_det,
-                  plate_imgsz=pd.ctx.cfg.plate_imgsz, options=getattr(fd, "options", None))
+                  plate_imgsz=pd.ctx.cfg.plate_imgsz, options=getattr(fd, "options", None),
+                  blur="gaussian" if fd.ctx.cfg.blur_mode == _lib.VD_BLUR_GAUSSIAN else "pixelate",
+                  blur_ksize=fd.ctx.cfg.blur_ksize or 31, blur_sigma=fd.ctx.cfg.blur_sigma)
     ctx.load_weights(_lib.VD_NET_RETINAFACE, fd.state_dict)
     ctx.load_weights(_lib.VD_NET_YOLOV8N, pd.state_dict)
     return ctx
+
+
+def _blur_matches(cfg, blur, ksize, sigma):
+    """The context's vd_process applies exactly this anonymisation."""
+    import ctypes
+    if blur == "pixelate":
+        return cfg.blur_mode == _lib.VD_BLUR_PIXELATE
+    return (cfg.blur_mode == _lib.VD_BLUR_GAUSSIAN and (cfg.blur_ksize or 31) == int(ksize)
+            and cfg.blur_sigma == ctypes.c_float(sigma).value)
 
 
 def _is_vdmi_pair(face_detector, plate_detector):
@@ -511,7 +522,8 @@ def _shard_mode(shard, face_detector, group, fused):
 
 def batch_process_images(input_dir, output_dir, face_detector, plate_detector, batch_size=16,
                          loader=None, saver=None, mosaic_plates=False, mosaic_level=8, num_workers=6,
-                         gpu_codec="auto", jpeg_quality=95, shard="auto", group=None, records=None):
+                         gpu_codec="auto", jpeg_quality=95, shard="auto", group=None, records=None,
+                         blur="pixelate", blur_ksize=31, blur_sigma=0.0):
     """combine_detect.py:183-277. Returns (total_processed, total_faces, total_plates).
 
     gpu_codec ("auto" | True | False): with vdmi detectors, no custom loader/saver and
@@ -519,6 +531,13 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     read as bytes, decoded on the GPU (vd_jpeg_decode), processed and encoded on the
     GPU (vd_jpeg_encode, cv2.imwrite's quality 95 / 4:2:0), so pixels never cross
     PCIe; the bytes written equal libjpeg-turbo's encode of the processed frames.
+
+    blur ("pixelate" | "gaussian"): what hides each box: the reference's mosaic of
+    `mosaic_level`, or GaussianBlur(region, (blur_ksize, blur_ksize), blur_sigma) of each
+    clipped box (vd_blur). The one-call vd_process path is taken when the face detector's
+    context was built with the same blur settings (Retinaface(blur=..., blur_ksize=...,
+    blur_sigma=...)); otherwise the detectors run on their own and the boxes are blurred
+    by one launch per same-size group of frames.
 
     shard: how the frames use several GPUs (the reference's nn.DataParallel,
     face.py:55-56, splits every forward over all of them):
@@ -547,14 +566,18 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     saver = saver or save_output_image
     image_paths = [os.path.join(input_dir, f) for f in os.listdir(input_dir) if f.lower().endswith(IMAGE_EXT)]
     os.makedirs(output_dir, exist_ok=True)
-    fused = _is_vdmi_pair(face_detector, plate_detector) and mosaic_level == face_detector.ctx.cfg.mosaic_level
+    if blur not in ("pixelate", "gaussian"):
+        raise ValueError(f"blur {blur!r}: expected 'pixelate' or 'gaussian'")
+    fused = (_is_vdmi_pair(face_detector, plate_detector) and mosaic_level == face_detector.ctx.cfg.mosaic_level
+             and _blur_matches(face_detector.ctx.cfg, blur, blur_ksize, blur_sigma))
     all_jpeg = all(p.lower().endswith((".jpg", ".jpeg")) for p in image_paths)
     codec = fused and gpu_codec and (gpu_codec is True or (not custom_io and all_jpeg))
     mode = _shard_mode(shard, face_detector, group, fused)
     run = dict(output_dir=output_dir, face_detector=face_detector, plate_detector=plate_detector,
                batch_size=batch_size, loader=loader, saver=saver, mosaic_plates=mosaic_plates,
                mosaic_level=mosaic_level, num_workers=num_workers, fused=fused, codec=codec,
-               jpeg_quality=jpeg_quality, logger=logger)
+               jpeg_quality=jpeg_quality, logger=logger,
+               blur=(blur, int(blur_ksize), float(blur_sigma)))
     want_rec = records is not None or mode == "ranks"
     if mode == "ranks":
         res, rec = _rank_shard(sorted(image_paths), group, run)
@@ -615,7 +638,7 @@ def _local(paths, first, device, want_rec, run, slot=0):
         else:
             res = _threaded_batches(batches, run["output_dir"], fd, run["plate_detector"], run["loader"],
                                     run["saver"], run["mosaic_plates"], run["mosaic_level"], io, run["logger"],
-                                    sink, ids)
+                                    sink, ids, run["blur"])
     finally:
         io.shutdown(wait=True)
     if sink is not None and sink.device.type == "cuda":
@@ -801,7 +824,7 @@ def _gpu_codec_batches(batches, output_dir, face_detector, plate_detector, batch
 
 
 def _threaded_batches(batches, output_dir, face_detector, plate_detector, loader, saver, mosaic_plates,
-                      mosaic_level, io, logger, sink=None, ids=None):
+                      mosaic_level, io, logger, sink=None, ids=None, blur=("pixelate", 31, 0.0)):
     """Generic detectors: the reference's two-thread face || plate submission, then
     one batched mosaic launch per same-size group."""
     total = faces = plates = 0
@@ -834,7 +857,7 @@ def _threaded_batches(batches, output_dir, face_detector, plate_detector, loader
             plates += len(plate_boxes)
         if sink is not None:
             sink.add_lists([ids[f][0] for f in files], [ids[f][1] for f in files], fl, pl)
-        processed = _mosaic_grouped(batch_images, per_frame, mosaic_level)
+        processed = _mosaic_grouped(batch_images, per_frame, mosaic_level, blur)
         for path, img in zip(files, processed):
             out = os.path.join(output_dir, f"processed_{os.path.basename(path)}")
             save_futs.append(io.submit(saver, img, out))
@@ -843,14 +866,17 @@ def _threaded_batches(batches, output_dir, face_detector, plate_detector, loader
     return total, faces, plates
 
 
-def _mosaic_grouped(images, boxes, level):
-    """One mosaic launch per same-size group of frames."""
+def _mosaic_grouped(images, boxes, level, blur=("pixelate", 31, 0.0)):
+    """One mosaic (or Gaussian blur) launch per same-size group of frames."""
     out = [None] * len(images)
     groups = {}
     for i, im in enumerate(images):
         groups.setdefault(im.shape, []).append(i)
     for idx in groups.values():
-        res = mosaic_frames(np.stack([images[i] for i in idx]), [boxes[i] for i in idx], level)
+        if blur[0] == "gaussian":
+            res = blur_frames(np.stack([images[i] for i in idx]), [boxes[i] for i in idx], blur[1], blur[2])
+        else:
+            res = mosaic_frames(np.stack([images[i] for i in idx]), [boxes[i] for i in idx], level)
         for k, i in enumerate(idx):
             out[i] = res[k]
     return out
