@@ -22,6 +22,8 @@
  *   vd_jpeg_decode / vd_jpeg_info <- cv2.imread(path) + cvtColor(BGR2RGB) of the ffmpeg-split
  *                                   frames                         combine_detect.py:167-172,
  *                                   (frames from convert_video_to_frames :279-476)
+ *   vd_hold / vd_hold_reset / vd_read_held: boxes held across frames (cfg.hold_frames; no
+ *                                   reference equivalent: the reference treats every frame alone)
  *   vd_read_boxes                <- the complete per-frame box lists the reference's
  *                                   loop iterates (combine_detect.py:241-249), past any cap
  *   vd_sync / vd_last_error / vd_destroy: runtime plumbing (no reference equivalent;
@@ -88,6 +90,8 @@ extern "C" {
 #define VD_BLUR_GAUSSIAN 1         /* Gaussian blur of each clipped box (vd_blur) */
 #define VD_BLUR_KSIZE_MAX 127
 
+#define VD_HOLD_MAX 8              /* largest vd_cfg.hold_frames */
+
 /* vd_process flags */
 #define VD_PROC_FACES        1     /* run the RetinaFace branch */
 #define VD_PROC_PLATES       2     /* run the YOLOv8n branch (forward + NMS) */
@@ -119,7 +123,10 @@ typedef struct vd_cfg {
     int32_t blur_mode;             /* VD_BLUR_*: what vd_process's VD_PROC_MOSAIC applies to the boxes */
     int32_t blur_ksize;            /* VD_BLUR_GAUSSIAN: odd kernel size in [3, 127]; 0 -> 31 */
     float   blur_sigma;            /* VD_BLUR_GAUSSIAN: sigma; <= 0 -> 0.3*((k-1)*0.5 - 1) + 0.8 (cv2's rule) */
-    int32_t reserved[3];
+    int32_t hold_frames;           /* box hold: frames a box stays in the blur list after its last match,
+                                    * in [0, VD_HOLD_MAX]; 0 = off (every frame alone, no extra launch) */
+    int32_t hold_iou_pct;          /* box hold: match threshold P in [1, 100] (100 * inter >= P * union); 0 -> 30 */
+    int32_t reserved[1];
 } vd_cfg;
 
 /* Per-frame box lists, caller-allocated. Frame f's boxes live at
@@ -197,6 +204,7 @@ int vd_blur(vd_ctx* ctx, const uint8_t* in, uint8_t* out, int n, int h, int w, s
 /* With VD_PROC_MOSAIC and cfg.blur_mode == VD_BLUR_GAUSSIAN the boxes are blurred as by
  * vd_blur(cfg.blur_ksize, cfg.blur_sigma) instead of pixelated: the same complete keep
  * lists, faces then plates; detection outputs are the same either way. */
+/* With cfg.hold_frames > 0 the blurred list is B_t = D_t ++ H_t (box hold, below). */
 int vd_process(vd_ctx* ctx, const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch,
                int where, int flags, vd_boxes* faces, vd_boxes* plates);
 /* Baseline JPEG frames -> RGB frames: the frame read of the reference's loop
@@ -232,12 +240,54 @@ int vd_jpeg_encode(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w, size
  * context stream after that call; host targets return when the copy is done. */
 int vd_read_boxes(vd_ctx* ctx, int net, int n, vd_boxes* out);
 
+/* ---- box hold: boxes carried across frames ----------------------------------
+ * A context created with cfg.hold_frames = K > 0 treats its calls as ONE stream of
+ * consecutive frames t = 0, 1, 2, ... (since its last reset) and keeps a box in the blur
+ * list for up to K frames after the last frame that matched it, so a face detected in
+ * frames t-1 and t+1 and missed in frame t is never shown in the clear. Integers only, so
+ * the result is defined to the bit:
+ *   D_t      frame t's own boxes as vd_process blurs them: the complete face keep list in
+ *            NMS order, then (VD_PROC_MOSAIC_PLATES) the plate keep list;
+ *   clip(b)  b clipped to [0, w] x [0, h] as the mosaic clips it (combine_detect.py:145-148);
+ *            a box that is empty after clipping never matches and is never held;
+ *   match    two non-empty clipped boxes match iff 100 * inter >= P * union, in 64-bit
+ *            (union = area_a + area_b - inter; P = cfg.hold_iou_pct; inclusive);
+ *   H_t      for a = 1..K (t - a >= 0) and, within each a, in the order of D_{t-a}: box b of
+ *            D_{t-a}, unclipped as stored, iff it matches NO box of D_t, .., D_{t-a+1} -- the
+ *            most recent sighting of anything not seen since; every candidate is judged on
+ *            its own (no greedy chain);
+ *   B_t      = D_t ++ H_t, the list frame t is blurred with (vd_process with VD_PROC_MOSAIC).
+ * The history -- the D lists of the last K frames, in device memory -- is carried across
+ * calls, updated by EVERY vd_process that runs detection in such a context (with or without
+ * VD_PROC_MOSAIC: running the K frames before a shard's first frame without it warms the
+ * shard up) and by vd_hold; a call of n < K frames shifts it (history = the last K of old
+ * history ++ the call's frames). It is cleared by vd_hold_reset and by a call whose (h, w)
+ * differs from the previous call's. Detection outputs (faces, plates, vd_read_boxes) are
+ * the detections only, exactly as without hold. One extra launch per call (timing family
+ * 3); the merged rows hold (K + 1) x (face + plate keep capacity) boxes per frame, so no
+ * box is ever dropped (DESIGN.md gives the bytes). hold_frames == 0: no launch, no memory.
+ *
+ * vd_hold: the same step for callers with their own detectors. det: the D lists of n
+ * consecutive h x w frames (host or device; a host list with count[f] > cap is refused,
+ * VD_ERR_CAPACITY, as by vd_mosaic). out (may be NULL): B_t per frame under the vd_boxes
+ * contract (count complete, arrays truncated at cap); label = age (0: the frame's own
+ * box, a: held from frame t - a); score and xyxy_f are not written. Same kernel and same
+ * history as vd_process. VD_ERR_STATE in a context with hold_frames == 0. */
+int vd_hold(vd_ctx* ctx, const vd_boxes* det, int n, int h, int w, vd_boxes* out);
+/* Forget the history: the next frame is frame 0 of a new stream (a cut, a new video, a
+ * dropped batch). VD_OK and no effect in a context with hold_frames == 0. */
+int vd_hold_reset(vd_ctx* ctx);
+/* H_t (the held boxes alone, label = age) of frames [0, n) of the last vd_process / vd_hold
+ * call, under the vd_boxes contract; ordered on the context stream like vd_read_boxes.
+ * VD_ERR_STATE with hold_frames == 0 or before the first holding call. */
+int vd_read_held(vd_ctx* ctx, int n, vd_boxes* out);
+
 /* ---- instrumentation (bench / profiling) ---------------------------------- */
 /* When enabled, every launch of kernel family `fam` is bracketed by HIP events
  * on the context stream; vd_timing_read returns the summed duration (ms), the
  * launch count and the summed algorithmic work (FLOP or bytes) since the last
  * reset. Families: 0 = RetinaFace conv (implicit GEMM / streaming 1x1), 1 = mosaic
- * output pass (or the Gaussian blur's launches), 2 = letterbox, 3 = post (decode/NMS), 4 = other, 5 = YOLOv8n plate
+ * output pass (or the Gaussian blur's launches), 2 = letterbox, 3 = post (decode/NMS, box hold), 4 = other, 5 = YOLOv8n plate
  * conv, 6 = mosaic cell table (box prep + walked cell colours). */
 int vd_timing_enable(vd_ctx* ctx, int on);
 int vd_timing_reset(vd_ctx* ctx);

@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/vdmi.h"
 #include "vd_common.h"
+#include "hold_state.h"
 
 #include <mutex>
 #include <string>
@@ -190,6 +191,13 @@ struct Ctx {
     void* stage_box2 = nullptr; size_t stage_box2_bytes = 0;
     void* mosaic_table = nullptr; size_t mosaic_table_bytes = 0;
     void* blur_table = nullptr; size_t blur_table_bytes = 0;   // Gaussian mode: box plan + dependent-box scratch
+    // box hold (hold.hip; cfg.hold_frames > 0 only, allocated by the first holding call)
+    HoldState hold;                               // K, P, valid history slots, current buffer, last frame size
+    int* hold_hist[2] = {nullptr, nullptr};       // ping-pong history: [K] counts, then (64-B aligned) [K][hcap][4]
+    int hold_hcap = 0;                            // history row capacity (boxes)
+    void* hold_rows = nullptr; size_t hold_rows_bytes = 0;   // the last call's merged rows, ages, |B|, |D|
+    HoldArgs hold_last{};                         // the last launch (merged-row pointers for the readers)
+    int hold_n = 0;                               // frames of the last holding call
     // JPEG frame decode (jpeg_host.cpp): pinned host staging, device copy, planes
     void* jpeg_host = nullptr; size_t jpeg_host_bytes = 0;
     void* jpeg_dev = nullptr; size_t jpeg_dev_bytes = 0;
@@ -270,6 +278,11 @@ struct Ctx {
                       const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int level);
     int launch_blur(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
                     const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int ksize, float sigma);
+    // B = D ++ H of n consecutive frames into hold_last's merged rows, and the history update
+    int launch_hold(int n, int h, int w, const int* cnt0, const int* xy0, int cap0, const int* cnt1, const int* xy1,
+                    int cap1);
+    int hold_history(int hcap);                   // history buffers of at least this row capacity
+    int hold_read(int n, int held_only, vd_boxes* out);   // merged rows -> caller lists (label = age)
 };
 
 int vd_alloc_post(Ctx& ctx, PostScratch& ps, int A, int kcap);

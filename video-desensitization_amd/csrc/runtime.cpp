@@ -996,6 +996,94 @@ int Ctx::launch_blur(const uint8_t* in, uint8_t* out, int n, int h, int w, size_
     return VD_OK;
 }
 
+// ---- box hold (hold.hip, hold_state.h) ----
+// History buffers of at least `hcap` boxes per slot; the valid slots of a smaller pair are
+// carried over (weights loaded, or a wider vd_hold list, after the first holding call).
+int Ctx::hold_history(int hcap) {
+    if (hcap <= hold_hcap) return VD_OK;
+    const int K = hold.K;
+    const size_t bytes = 64 + (size_t)K * hcap * 16;
+    int* nb[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; ++i)
+        if (hipMalloc((void**)&nb[i], bytes) != hipSuccess) {
+            if (nb[0]) hipFree(nb[0]);
+            return vd_set_error(VD_ERR_NOMEM, "hipMalloc(%zu) failed (hold history)", bytes);
+        }
+    for (int i = 0; i < 2; ++i) VD_CHECK_HIP(hipMemsetAsync(nb[i], 0, 64, stream));
+    if (hold_hist[0] && hold.hn > 0) {
+        const int c = hold.cur;
+        VD_CHECK_HIP(hipMemcpyAsync(nb[c], hold_hist[c], (size_t)K * 4, hipMemcpyDeviceToDevice, stream));
+        VD_CHECK_HIP(hipMemcpy2DAsync((char*)nb[c] + 64, (size_t)hcap * 16, (const char*)hold_hist[c] + 64,
+                                      (size_t)hold_hcap * 16, (size_t)hold_hcap * 16, K, hipMemcpyDeviceToDevice,
+                                      stream));
+    }
+    VD_CHECK_HIP(hipStreamSynchronize(stream));
+    for (int i = 0; i < 2; ++i) {
+        if (hold_hist[i]) hipFree(hold_hist[i]);
+        hold_hist[i] = nb[i];
+    }
+    hold_hcap = hcap;
+    return VD_OK;
+}
+
+int Ctx::launch_hold(int n, int h, int w, const int* cnt0, const int* xy0, int cap0, const int* cnt1, const int* xy1,
+                     int cap1) {
+    const int K = hold.K;
+    // rows sized for the loaded detectors' complete keep lists (vd_process never regrows them)
+    // and for this call's lists; (K + 1) rows of that size hold D and K complete older lists
+    const int nets = (face.loaded ? face.post.kcap : 0) + (plate.loaded ? plate.post.kcap : 0);
+    const int need = std::max(std::max((cnt0 ? cap0 : 0) + (cnt1 ? cap1 : 0), nets), 1);
+    int rc = hold_history(need);
+    if (rc) return rc;
+    const size_t mcap = (size_t)(K + 1) * hold_hcap;
+    if (mcap > 0x7fffffffu) return vd_set_error(VD_ERR_ARG, "hold: list capacity too large");
+    const size_t nb = (size_t)n * mcap;
+    if ((rc = ensure_staging(&hold_rows, &hold_rows_bytes, nb * 16 + nb * 4 + (size_t)n * 8 + 64))) return rc;
+    hold.begin(h, w);
+    HoldArgs a{};
+    a.n = n; a.h = h; a.w = w; a.K = K; a.P = hold.P;
+    a.cnt0 = cnt0; a.xy0 = xy0; a.cap0 = cap0;
+    a.cnt1 = cnt1; a.xy1 = xy1; a.cap1 = cap1;
+    a.hist_cnt = hold_hist[hold.cur]; a.hist_xy = hold_hist[hold.cur] + 16;
+    a.next_cnt = hold_hist[hold.cur ^ 1]; a.next_xy = hold_hist[hold.cur ^ 1] + 16;
+    a.hcap = hold_hcap; a.hn = hold.hn;
+    a.m_xy = (int*)hold_rows; a.m_age = a.m_xy + nb * 4; a.m_count = a.m_age + nb; a.m_own = a.m_count + n;
+    a.mcap = (int)mcap;
+    t_begin(3, (double)n * (K + 1) * 16);
+    hipError_t e = vd_launch_hold(a, stream);
+    t_end();
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "hold: %s", hipGetErrorString(e));
+    hold.end(n);
+    hold_last = a;
+    hold_n = n;
+    return VD_OK;
+}
+
+int Ctx::hold_read(int n, int held_only, vd_boxes* out) {
+    if (!hold.K) return vd_set_error(VD_ERR_STATE, "context created with hold_frames == 0");
+    if (!hold_n) return vd_set_error(VD_ERR_STATE, "no holding call yet");
+    if (!out || !out->count || !out->xyxy || out->cap <= 0) return vd_set_error(VD_ERR_ARG, "vd_boxes needs count, xyxy, cap>0");
+    if (n <= 0 || n > hold_n) return vd_set_error(VD_ERR_ARG, "n=%d outside [1, %d frames of the last call]", n, hold_n);
+    BoxTargets t{};
+    if (out->where == VD_DEVICE) {
+        t.count = out->count; t.xyxy = out->xyxy; t.label = out->label;
+    } else {
+        int rc = host_box_staging(&stage_box, &stage_box_bytes, out->cap, n, t);
+        if (rc) return rc;
+        if (!out->label) t.label = nullptr;
+    }
+    hipError_t e = vd_launch_hold_gather(hold_last, n, held_only, t.count, t.xyxy, t.label, out->cap, stream);
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "hold gather: %s", hipGetErrorString(e));
+    if (out->where == VD_DEVICE) return VD_OK;
+    // arrays past min(count, cap) are not written by the gather: copy whole arrays as box_finish does
+    const size_t nbx = (size_t)n * out->cap;
+    VD_CHECK_HIP(hipMemcpyAsync(out->count, t.count, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+    VD_CHECK_HIP(hipMemcpyAsync(out->xyxy, t.xyxy, nbx * 16, hipMemcpyDeviceToHost, stream));
+    if (out->label) VD_CHECK_HIP(hipMemcpyAsync(out->label, t.label, nbx * 4, hipMemcpyDeviceToHost, stream));
+    VD_CHECK_HIP(hipStreamSynchronize(stream));
+    return VD_OK;
+}
+
 // ----------------------------------------------------------------------------
 // C-ABI
 // ----------------------------------------------------------------------------
@@ -1048,6 +1136,10 @@ int vd_create(const vd_cfg* cfg, int device, vd_ctx** out) {
             return vd_set_error(VD_ERR_ARG, "cfg: blur_ksize must be odd in [3, %d] (got %d) and blur_sigma finite",
                                 VD_BLUR_KSIZE_MAX, c.blur_ksize);
     }
+    if (c.hold_frames < 0 || c.hold_frames > VD_HOLD_MAX || c.hold_iou_pct < 0 || c.hold_iou_pct > 100)
+        return vd_set_error(VD_ERR_ARG, "cfg: hold_frames in [0, %d] and hold_iou_pct in [0, 100] required (got %d, %d)",
+                            VD_HOLD_MAX, c.hold_frames, c.hold_iou_pct);
+    if (c.hold_iou_pct == 0) c.hold_iou_pct = 30;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
         return vd_set_error(VD_ERR_HIP, "no HIP device %d (count %d)", device, ndev);
@@ -1057,6 +1149,8 @@ int vd_create(const vd_cfg* cfg, int device, vd_ctx** out) {
     ctx->device = device;
     ctx->f32 = c.precision == VD_PREC_FP32;
     ctx->f16 = c.precision == VD_PREC_FP16;
+    ctx->hold.K = c.hold_frames;
+    ctx->hold.P = c.hold_iou_pct;
     if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) {
         delete ctx;
         return vd_set_error(VD_ERR_HIP, "hipStreamCreate failed");
@@ -1090,6 +1184,9 @@ int vd_destroy(vd_ctx* h) {
     if (ctx->stage_box2) hipFree(ctx->stage_box2);
     if (ctx->mosaic_table) hipFree(ctx->mosaic_table);
     if (ctx->blur_table) hipFree(ctx->blur_table);
+    if (ctx->hold_rows) hipFree(ctx->hold_rows);
+    for (int* p : ctx->hold_hist)
+        if (p) hipFree(p);
     if (ctx->jpeg_dev) hipFree(ctx->jpeg_dev);
     if (ctx->jpeg_planes) hipFree(ctx->jpeg_planes);
     if (ctx->jpeg_host) hipHostFree(ctx->jpeg_host);
@@ -1444,6 +1541,25 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
     // combine_detect.py:239): otherwise it runs on the face stream before the plate branch
     // joins, beside the branch's last launches (option mosaic_early)
     const bool mosaic_first = do_mosaic && fork && !mosaic_plates && ctx->tune.mosaic_early;
+    // every kept box, from the library's complete keep lists (the caller's arrays
+    // may hold fewer: cap), faces in NMS order then plates (combine_detect.py:241-249)
+    const PostScratch& fp = ctx->face.post;
+    const PostScratch& pp = ctx->plate.post;
+    const int* c0 = do_faces ? fp.kcount : nullptr;
+    const int* x0 = do_faces ? fp.kxyxy : nullptr;
+    const int* c1 = mosaic_plates ? pp.kcount : nullptr;
+    const int* x1 = mosaic_plates ? pp.kxyxy : nullptr;
+    int k0 = do_faces ? fp.kcap : 0, k1 = mosaic_plates ? pp.kcap : 0;
+    // box hold: the blur list becomes B = D ++ H in merged rows (one launch, after the lists
+    // it reads are complete); the history is updated whether or not anything is blurred
+    auto hold = [&]() -> int {
+        if (!ctx->hold.K || (!c0 && !c1)) return VD_OK;
+        int r = ctx->launch_hold(n, fh, fw, c0, x0, k0, c1, x1, k1);
+        if (r) return r;
+        c0 = ctx->hold_last.m_count; x0 = ctx->hold_last.m_xy; k0 = ctx->hold_last.mcap;
+        c1 = x1 = nullptr; k1 = 0;
+        return VD_OK;
+    };
     auto mosaic = [&]() -> int {
         uint8_t* dout = out;
         size_t bytes = (size_t)n * fh * pitch;
@@ -1452,15 +1568,6 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
             if (r) return r;
             dout = (uint8_t*)ctx->stage_out;
         }
-        // every kept box, from the library's complete keep lists (the caller's arrays
-        // may hold fewer: cap), faces in NMS order then plates (combine_detect.py:241-249)
-        const PostScratch& fp = ctx->face.post;
-        const PostScratch& pp = ctx->plate.post;
-        const int* c0 = do_faces ? fp.kcount : nullptr;
-        const int* x0 = do_faces ? fp.kxyxy : nullptr;
-        const int* c1 = mosaic_plates ? pp.kcount : nullptr;
-        const int* x1 = mosaic_plates ? pp.kxyxy : nullptr;
-        const int k0 = do_faces ? fp.kcap : 0, k1 = mosaic_plates ? pp.kcap : 0;
         int r = ctx->cfg.blur_mode == VD_BLUR_GAUSSIAN
                     ? ctx->launch_blur(d, dout, n, fh, fw, pitch, c0, x0, k0, c1, x1, k1, ctx->cfg.blur_ksize,
                                        ctx->cfg.blur_sigma)
@@ -1469,12 +1576,12 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
         if (where == VD_HOST) VD_CHECK_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
         return VD_OK;
     };
-    if (mosaic_first && (rc = mosaic())) return rc;
+    if (mosaic_first && ((rc = hold()) || (rc = mosaic()))) return rc;
     if (fork) {
         VD_CHECK_HIP(hipEventRecord(ctx->ev_join, plate_stream));
         VD_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
     }
-    if (do_mosaic && !mosaic_first && (rc = mosaic())) return rc;
+    if (!mosaic_first && ((rc = hold()) || (do_mosaic && (rc = mosaic())))) return rc;
     int rc2 = VD_OK;
     if (do_faces) rc2 = ctx->box_finish(faces, n, tf);
     if (do_plates) {
@@ -1506,6 +1613,55 @@ int vd_read_boxes(vd_ctx* h, int net, int n, vd_boxes* out) {
         VD_CHECK_HIP(hipMemcpy2DAsync(out->label, dp * 4, ps->klabel, sp * 4, (size_t)w * 4, n, kind, ctx->stream));
     if (out->where == VD_HOST) VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     return VD_OK;
+}
+
+int vd_hold(vd_ctx* h, const vd_boxes* det, int n, int fh, int fw, vd_boxes* out) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (!ctx->hold.K) return vd_set_error(VD_ERR_STATE, "vd_hold: context created with hold_frames == 0");
+    if (!det || !det->count || !det->xyxy || det->cap <= 0) return vd_set_error(VD_ERR_ARG, "vd_hold: null argument");
+    if (n <= 0 || fh <= 0 || fw <= 0) return vd_set_error(VD_ERR_ARG, "vd_hold: bad geometry");
+    if (out && (!out->count || !out->xyxy || out->cap <= 0))
+        return vd_set_error(VD_ERR_ARG, "vd_boxes needs count, xyxy, cap>0");
+    const bool host = det->where == VD_HOST;
+    if (host)   // a count past cap means boxes the caller does not hold: never skip them silently
+        for (int i = 0; i < n; ++i)
+            if (det->count[i] > det->cap)
+                return vd_set_error(VD_ERR_CAPACITY, "vd_hold: frame %d has count %d > cap %d", i, det->count[i],
+                                    det->cap);
+    const int* cnt = det->count;
+    const int* xy = det->xyxy;
+    int rc;
+    const bool staged = host || ((uintptr_t)det->xyxy & 15);   // the kernel reads boxes as 16-B vectors
+    if (staged) {
+        const size_t nb = (size_t)n * det->cap;
+        if ((rc = ctx->ensure_staging(&ctx->stage_box2, &ctx->stage_box2_bytes, n * 4 + nb * 16 + 16))) return rc;
+        int* dc = (int*)ctx->stage_box2;
+        int* dx = dc + ((n + 3) / 4) * 4;
+        const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+        VD_CHECK_HIP(hipMemcpyAsync(dc, det->count, (size_t)n * 4, kind, ctx->stream));
+        VD_CHECK_HIP(hipMemcpyAsync(dx, det->xyxy, nb * 16, kind, ctx->stream));
+        cnt = dc;
+        xy = dx;
+    }
+    if ((rc = ctx->launch_hold(n, fh, fw, cnt, xy, det->cap, nullptr, nullptr, 0))) return rc;
+    if (out && (rc = ctx->hold_read(n, 0, out))) return rc;
+    if (staged && !(out && out->where == VD_HOST))
+        VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // staging reused by the next call
+    return VD_OK;
+}
+
+int vd_hold_reset(vd_ctx* h) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    ctx->hold.reset();
+    return VD_OK;
+}
+
+int vd_read_held(vd_ctx* h, int n, vd_boxes* out) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    return ctx->hold_read(n, 1, out);
 }
 
 int vdt_blur_weights(int ksize, float sigma, uint32_t* q) {

@@ -430,6 +430,24 @@ hipError_t vd_launch_blur(const uint8_t* in, uint8_t* out, int n, int h, int w, 
 size_t vd_blur_table_bytes(int n, int h, size_t pitch, int tcap);
 int vd_blur_weights(int ksize, float sigma, uint32_t* q);   // host; 0, or -1 for a refused ksize / sigma
 
+// Box hold (hold.hip): frame f's blur list B = D ++ H in merged rows, and the next history.
+// Lists 0 / 1 as the mosaic takes them (list 1 optional); xy pointers 16-B aligned.
+struct HoldArgs {
+    int n, h, w, K, P;                               // frames, frame size, hold_frames, hold_iou_pct
+    const int* cnt0; const int* xy0; int cap0;       // this call's D lists: list 0 (faces)
+    const int* cnt1; const int* xy1; int cap1;       //   list 1 (plates, optional)
+    const int* hist_cnt; const int* hist_xy;         // history read: [K], [K][hcap][4] (hold_state.h)
+    int* next_cnt; int* next_xy;                     // history written: the other buffer
+    int hcap, hn;                                    // history row capacity (>= cap0 + cap1), valid slots
+    int* m_xy; int* m_age; int* m_count; int* m_own; // merged rows [n][mcap][4], ages [n][mcap], |B| [n], |D| [n]
+    int mcap;                                        // (K + 1) * hcap: D plus K complete older lists always fit
+};
+hipError_t vd_launch_hold(const HoldArgs& a, hipStream_t s);
+// Rows of merged lists into caller-shaped arrays [n][cap] (count complete, arrays truncated at cap,
+// scalar stores: no alignment assumed); held_only: H alone (skip each row's own |D| boxes).
+hipError_t vd_launch_hold_gather(const HoldArgs& a, int n, int held_only, int* out_count, int* out_xyxy,
+                                 int* out_label, int cap, hipStream_t s);
+
 #define VD_CHECK_HIP(expr)                                                     \
     do {                                                                       \
         hipError_t _e = (expr);                                                \

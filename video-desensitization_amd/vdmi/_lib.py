@@ -21,6 +21,7 @@ VD_WEIGHTS_VDW1 = 1
 VD_MOSAIC_OUT_OF_PLACE = 0
 VD_BLUR_PIXELATE, VD_BLUR_GAUSSIAN = 0, 1
 VD_BLUR_KSIZE_MAX = 127
+VD_HOLD_MAX = 8
 VD_PROC_FACES, VD_PROC_PLATES, VD_PROC_MOSAIC, VD_PROC_MOSAIC_PLATES = 1, 2, 4, 8
 FAM_CONV, FAM_MOSAIC, FAM_LETTERBOX, FAM_POST, FAM_OTHER, FAM_PLATE_CONV, FAM_MOSAIC_CELLS = 0, 1, 2, 3, 4, 5, 6
 
@@ -51,7 +52,8 @@ class vd_cfg(ctypes.Structure):
                 ("microbatch", ctypes.c_int32), ("microbatch_stage", ctypes.c_int32),
                 ("blur_mode", ctypes.c_int32), ("blur_ksize", ctypes.c_int32),
                 ("blur_sigma", ctypes.c_float),
-                ("reserved", ctypes.c_int32 * 3)]
+                ("hold_frames", ctypes.c_int32), ("hold_iou_pct", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 1)]
 
 
 class vd_boxes(ctypes.Structure):
@@ -81,6 +83,9 @@ SIGNATURES = [
     ("vd_process", _I, [_P, _P, _P, _I, _I, _I, _SZ, _I, _I, ctypes.POINTER(vd_boxes),
                         ctypes.POINTER(vd_boxes)]),
     ("vd_read_boxes", _I, [_P, _I, _I, ctypes.POINTER(vd_boxes)]),
+    ("vd_hold", _I, [_P, ctypes.POINTER(vd_boxes), _I, _I, _I, ctypes.POINTER(vd_boxes)]),
+    ("vd_hold_reset", _I, [_P]),
+    ("vd_read_held", _I, [_P, _I, ctypes.POINTER(vd_boxes)]),
     ("vd_jpeg_decode", _I, [_P, ctypes.POINTER(_P), ctypes.POINTER(_SZ), _I, _P, _I, _I, _SZ, _I]),
     ("vd_jpeg_info", _I, [_P, _SZ, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     ("vd_jpeg_encode", _I, [_P, _P, _I, _I, _I, _SZ, _I, _I, _I, _P, _SZ, ctypes.POINTER(_SZ)]),
@@ -151,6 +156,16 @@ def default_cfg():
     c = vd_cfg()
     check(load().vd_default_cfg(ctypes.byref(c)))
     return c
+
+
+def check_hold(hold, hold_iou_pct):
+    """(hold_frames, hold_iou_pct) as ints; ValueError outside [0, VD_HOLD_MAX] / [1, 100]."""
+    hold, pct = int(hold), int(hold_iou_pct)
+    if not 0 <= hold <= VD_HOLD_MAX:
+        raise ValueError(f"hold {hold}: expected 0 (off) .. {VD_HOLD_MAX} frames")
+    if not 1 <= pct <= 100:
+        raise ValueError(f"hold_iou_pct {pct}: expected 1 .. 100")
+    return hold, pct
 
 
 def blur_weights(ksize, sigma=0.0):

@@ -101,13 +101,19 @@ class Context:
     def __init__(self, device=0, precision="bf16", max_batch=64, input_shape=(640, 640), confidence=0.5,
                  nms_iou=0.4, max_boxes=256, mosaic_level=8, plate_nc=1, plate_conf=0.5, plate_iou=0.7,
                  plate_max_det=300, plate_imgsz=640, microbatch=0, microbatch_stage=2, options=None,
-                 blur="pixelate", blur_ksize=31, blur_sigma=0.0):
+                 blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30):
         """blur: what process() applies to the kept boxes: "pixelate" (the reference's
         INTER_NEAREST mosaic, the default) or "gaussian" (GaussianBlur(region, (blur_ksize,
         blur_ksize), blur_sigma) per clipped box, in list order; blur_ksize odd in [3, 127],
-        blur_sigma <= 0: cv2's rule from the kernel size)."""
+        blur_sigma <= 0: cv2's rule from the kernel size).
+        hold: box hold (include/vdmi.h): the context's calls are one stream of consecutive
+        frames, and a box stays in process()'s blur list for up to `hold` frames (0 = off,
+        at most 8) after the last frame in which a box matched it (100 * inter >=
+        hold_iou_pct * union on the clipped boxes), so a missed detection never shows a
+        face in the clear; hold_reset() starts a new stream."""
         if blur not in BLUR_MODES:
             raise ValueError(f"blur {blur!r}: expected 'pixelate' or 'gaussian'")
+        hold, hold_iou_pct = _lib.check_hold(hold, hold_iou_pct)   # before the library is touched
         lib = _lib.load()
         cfg = _lib.default_cfg()
         cfg.input_h, cfg.input_w = int(input_shape[0]), int(input_shape[1])
@@ -131,6 +137,8 @@ class Context:
         cfg.blur_mode = BLUR_MODES[blur]
         if cfg.blur_mode == _lib.VD_BLUR_GAUSSIAN:      # pixelate leaves the fields zero
             cfg.blur_ksize, cfg.blur_sigma = int(blur_ksize), float(blur_sigma)
+        if hold:                                        # off leaves the fields zero
+            cfg.hold_frames, cfg.hold_iou_pct = hold, hold_iou_pct
         self.cfg = cfg
         self.device = int(device)
         self.precision = {_lib.VD_PREC_FP32: "fp32", _lib.VD_PREC_FP16: "fp16"}.get(cfg.precision, "bf16")
@@ -316,6 +324,67 @@ class Context:
         if flags & _lib.VD_PROC_PLATES:
             plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
         return out, faces, plates
+
+    # -- box hold ----------------------------------------------------------------
+    def hold(self, boxes, h, w, out=None):
+        """vd_hold: the hold step alone, for callers with their own detectors. boxes: the
+        detections of consecutive h x w frames -- a HostBoxes / DeviceBoxes, or a list with
+        one int [k][4] array per frame. Returns `out` (default: HostBoxes sized for the
+        largest list) holding every frame's blur list, the frame's own boxes then the held
+        ones, label = age (0: own; a: last seen a frames ago). The context's history is
+        updated as by process()."""
+        if isinstance(boxes, (_lib.HostBoxes, DeviceBoxes)):
+            det = boxes
+        else:
+            lists = [np.asarray(b, np.int32).reshape(-1, 4) for b in boxes]
+            det = _lib.HostBoxes(len(lists), max(1, max((len(b) for b in lists), default=1)))
+            for i, b in enumerate(lists):
+                det.count[i] = len(b)
+                det.xyxy[i, :len(b)] = b
+        n = det.n
+        ds = det.struct()
+        if out is not None:
+            s = out.struct()
+            check(self._lib.vd_hold(self._h, ctypes.byref(ds), n, int(h), int(w), ctypes.byref(s)))
+            return out
+        # sizes are not known before the step and the step must run once: take it without a
+        # target, read the held boxes (complete), and put each frame's own boxes in front
+        check(self._lib.vd_hold(self._h, ctypes.byref(ds), n, int(h), int(w), None))
+        held = self.read_held(n)
+        host = lambda t: t.cpu().numpy() if _is_torch(t) else t
+        own = np.minimum(host(det.count), det.cap)
+        xy = host(det.xyxy)
+        out = _lib.HostBoxes(n, max(1, int((own + held.count).max())))
+        for i in range(n):
+            k, m = int(own[i]), int(held.count[i])
+            out.count[i] = k + m
+            out.xyxy[i, :k] = xy[i, :k]
+            out.xyxy[i, k:k + m] = held.xyxy[i, :m]
+            out.label[i, k:k + m] = held.label[i, :m]
+        return out
+
+    def hold_reset(self):
+        """vd_hold_reset: forget the history; the next frame starts a new stream."""
+        check(self._lib.vd_hold_reset(self._h))
+
+    def read_held(self, n, cap=None, out=None):
+        """The held boxes H (label = age) of frames [0, n) of the last process() / hold()
+        call (vd_read_held) as HostBoxes; cap defaults to the largest count. out: a
+        HostBoxes / DeviceBoxes to fill instead (a device target is queued on the
+        context stream, no host wait)."""
+        if out is not None:
+            s = out.struct()
+            check(self._lib.vd_read_held(self._h, n, ctypes.byref(s)))
+            return out
+        if cap is None:
+            cnt = _lib.HostBoxes(n, 1)
+            s = cnt.struct()
+            check(self._lib.vd_read_held(self._h, n, ctypes.byref(s)))
+            cap = max(1, int(cnt.count.max()))
+        boxes = _lib.HostBoxes(n, cap)
+        s = boxes.struct()
+        check(self._lib.vd_read_held(self._h, n, ctypes.byref(s)))
+        return boxes
 
     # -- frame I/O ------------------------------------------------------------
     def jpeg_decode(self, jpegs, out=None):

@@ -95,6 +95,9 @@ class Retinaface(object):
         "blur": "pixelate",
         "blur_ksize": 31,
         "blur_sigma": 0.0,
+        # box hold across frames in the fused vd_process: Context(hold=..., hold_iou_pct=...)
+        "hold": 0,
+        "hold_iou_pct": 30,
     }
 
     @classmethod
@@ -122,7 +125,8 @@ class Retinaface(object):
         self.ctxs = [Context(device=d, precision=self.precision, max_batch=self.max_batch,
                              input_shape=self.input_shape[:2], confidence=self.confidence, nms_iou=self.nms_iou,
                              max_boxes=self.max_boxes, options=self.options, blur=self.blur,
-                             blur_ksize=self.blur_ksize, blur_sigma=self.blur_sigma) for d in self.device_ids]
+                             blur_ksize=self.blur_ksize, blur_sigma=self.blur_sigma, hold=self.hold,
+                             hold_iou_pct=self.hold_iou_pct) for d in self.device_ids]
         self.ctx = self.ctxs[0]
         self.generate()
 

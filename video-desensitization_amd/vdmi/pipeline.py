@@ -121,6 +121,7 @@ class FramePipeline:
         self.ev_up, self.ev_comp, self.ev_down = ev(), ev(), ev()
         self.used = [False] * self.depth
         self.seq = 0
+        self.held = [] if ctx.cfg.hold_frames else None   # per batch: device lists carrying the held-box counts
 
     def next_input(self, n):
         """Pinned host buffer [n,h,w,3] of the next slot, free to be written (a decoder
@@ -159,6 +160,8 @@ class FramePipeline:
         # stream that waited on this slot's upload is the one the library must run on
         self.ctx.set_stream(self.s_comp.cuda_stream)
         self.ctx.process(self.d_in[k, :n], self.d_out[k, :n], faces=faces, plates=plates, flags=self.flags)
+        if self.held is not None:
+            self.held.append(_held_counts(self.ctx, n, self.dev))
         self.ev_comp[k].record(self.s_comp)
         with torch.cuda.stream(self.s_down):
             self.s_down.wait_event(self.ev_comp[k])
@@ -270,6 +273,7 @@ class GpuJpegStages:
         self.ev_dec = [torch.cuda.Event() for _ in range(self.depth)]
         self.ev_proc = [torch.cuda.Event() for _ in range(self.depth)]
         self.buf = {}                                   # (h, w) -> ([d_in] * depth, [d_out] * depth)
+        self.held = [] if ctx.cfg.hold_frames else None # per size group: the same, as in FramePipeline
         self.dpool, self.epool = ThreadPoolExecutor(1), ThreadPoolExecutor(1)
         self.stats = {"decode_wait": 0.0, "encode_wait": 0.0, "queue": 0.0, "decode": 0.0, "encode": 0.0,
                       "decode_fetch": 0.0, "decode_call": 0.0}
@@ -407,6 +411,8 @@ class GpuJpegStages:
                     try:
                         fv, pv = self.faces[slot].view(off, n), self.plates[slot].view(off, n)
                         self.ctx.process(din[slot][:n], dout[slot][:n], faces=fv, plates=pv, flags=self.flags)
+                        if self.held is not None:
+                            self.held.append(_held_counts(self.ctx, n, self.dev))
                         if on_processed is not None:
                             on_processed(key, idx, fv, pv, self.ctx.stream())
                         ok.append((idx, h, w, off))
@@ -443,6 +449,26 @@ class GpuJpegStages:
         self.ectx.close()
 
 
+def _held_counts(ctx, n, dev):
+    """Held-box counts of the process() just queued, in device lists of one box per frame (no
+    host wait). The caller keeps the whole object until the stream has run: the gather also
+    writes its box and label arrays, and torch would hand freed ones to someone else."""
+    import torch
+    from .context import DeviceBoxes
+    t = DeviceBoxes.__new__(DeviceBoxes)     # uninitialised storage: a zero fill on torch's stream
+    t.n, t.cap = n, 1                        # would race the gather on the context's stream
+    t.count = torch.empty(n, dtype=torch.int32, device=dev)
+    t.xyxy = torch.empty((n, 1, 4), dtype=torch.int32, device=dev)
+    t.label = torch.empty((n, 1), dtype=torch.int32, device=dev)
+    t.xyxy_f = torch.empty((n, 1, 4), dtype=torch.float32, device=dev)
+    t.score = torch.empty((n, 1), dtype=torch.float32, device=dev)
+    return ctx.read_held(n, out=t)
+
+
+def _held_total(held):
+    return sum(int(t.count.sum().item()) for t in held) if held else 0
+
+
 _FUSED_LOCK = threading.Lock()
 
 
@@ -473,7 +499,8 @@ def _new_fused_context(fd, pd, batch_size, dev):
                   plate_iou=pd.ctx.cfg.plate_iou, plate_max_det=pd.ctx.cfg.plate_max_det,
                   plate_imgsz=pd.ctx.cfg.plate_imgsz, options=getattr(fd, "options", None),
                   blur="gaussian" if fd.ctx.cfg.blur_mode == _lib.VD_BLUR_GAUSSIAN else "pixelate",
-                  blur_ksize=fd.ctx.cfg.blur_ksize or 31, blur_sigma=fd.ctx.cfg.blur_sigma)
+                  blur_ksize=fd.ctx.cfg.blur_ksize or 31, blur_sigma=fd.ctx.cfg.blur_sigma,
+                  hold=fd.ctx.cfg.hold_frames, hold_iou_pct=fd.ctx.cfg.hold_iou_pct or 30)
     ctx.load_weights(_lib.VD_NET_RETINAFACE, fd.state_dict)
     ctx.load_weights(_lib.VD_NET_YOLOV8N, pd.state_dict)
     return ctx
@@ -486,6 +513,11 @@ def _blur_matches(cfg, blur, ksize, sigma):
         return cfg.blur_mode == _lib.VD_BLUR_PIXELATE
     return (cfg.blur_mode == _lib.VD_BLUR_GAUSSIAN and (cfg.blur_ksize or 31) == int(ksize)
             and cfg.blur_sigma == ctypes.c_float(sigma).value)
+
+
+def _hold_matches(cfg, hold, pct):
+    """The context's vd_process holds boxes exactly so (hold 0: not at all)."""
+    return cfg.hold_frames == hold and (hold == 0 or cfg.hold_iou_pct == pct)
 
 
 def _is_vdmi_pair(face_detector, plate_detector):
@@ -523,7 +555,7 @@ def _shard_mode(shard, face_detector, group, fused):
 def batch_process_images(input_dir, output_dir, face_detector, plate_detector, batch_size=16,
                          loader=None, saver=None, mosaic_plates=False, mosaic_level=8, num_workers=6,
                          gpu_codec="auto", jpeg_quality=95, shard="auto", group=None, records=None,
-                         blur="pixelate", blur_ksize=31, blur_sigma=0.0):
+                         blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30):
     """combine_detect.py:183-277. Returns (total_processed, total_faces, total_plates).
 
     gpu_codec ("auto" | True | False): with vdmi detectors, no custom loader/saver and
@@ -538,6 +570,19 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     context was built with the same blur settings (Retinaface(blur=..., blur_ksize=...,
     blur_sigma=...)); otherwise the detectors run on their own and the boxes are blurred
     by one launch per same-size group of frames.
+
+    hold (0..8) / hold_iou_pct (1..100): box hold (include/vdmi.h, Context(hold=...)): the
+    frames are ONE video in the order of their sorted names, and a box stays blurred for up to
+    `hold` frames after the last frame in which a detection matched it, so a single missed
+    detection never leaves a face in the clear. It needs the vdmi Retinaface / YOLO pair and a
+    face detector built with the same settings (Retinaface(hold=..., hold_iou_pct=...)), else
+    ValueError. The history starts empty at every call and again after a dropped batch; a
+    shard that starts at frame b > 0 first runs frames [max(0, b - hold), b) through the
+    detectors alone (host-decoded, nothing written), so sharded output equals one device's.
+    Frames of several sizes: the history clears at every size change, and a batch that mixes
+    sizes is processed per size group, as without hold. The returned totals and `records`
+    are the detections only; the number of held boxes is logged. hold=0 (the default)
+    changes nothing: the directory order of os.listdir, no reset, no extra launch.
 
     shard: how the frames use several GPUs (the reference's nn.DataParallel,
     face.py:55-56, splits every forward over all of them):
@@ -564,12 +609,20 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
         raise ValueError("gpu_codec=True reads and writes JPEG bytes itself: it cannot use a custom loader/saver")
     loader = loader or load_image_rgb
     saver = saver or save_output_image
+    hold, hold_iou_pct = _lib.check_hold(hold, hold_iou_pct)
     image_paths = [os.path.join(input_dir, f) for f in os.listdir(input_dir) if f.lower().endswith(IMAGE_EXT)]
+    if hold:
+        image_paths.sort()               # the frames of one video, in order
     os.makedirs(output_dir, exist_ok=True)
     if blur not in ("pixelate", "gaussian"):
         raise ValueError(f"blur {blur!r}: expected 'pixelate' or 'gaussian'")
     fused = (_is_vdmi_pair(face_detector, plate_detector) and mosaic_level == face_detector.ctx.cfg.mosaic_level
-             and _blur_matches(face_detector.ctx.cfg, blur, blur_ksize, blur_sigma))
+             and _blur_matches(face_detector.ctx.cfg, blur, blur_ksize, blur_sigma)
+             and _hold_matches(face_detector.ctx.cfg, hold, hold_iou_pct))
+    if hold and not fused:
+        raise ValueError("hold > 0 needs the vdmi Retinaface / YOLO drop-ins and a face detector built with the "
+                         "same mosaic_level, blur and hold settings (Retinaface(hold=..., hold_iou_pct=...)); "
+                         "other detectors call Context.hold themselves")
     all_jpeg = all(p.lower().endswith((".jpg", ".jpeg")) for p in image_paths)
     codec = fused and gpu_codec and (gpu_codec is True or (not custom_io and all_jpeg))
     mode = _shard_mode(shard, face_detector, group, fused)
@@ -577,7 +630,7 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
                batch_size=batch_size, loader=loader, saver=saver, mosaic_plates=mosaic_plates,
                mosaic_level=mosaic_level, num_workers=num_workers, fused=fused, codec=codec,
                jpeg_quality=jpeg_quality, logger=logger,
-               blur=(blur, int(blur_ksize), float(blur_sigma)))
+               blur=(blur, int(blur_ksize), float(blur_sigma)), hold=hold)
     want_rec = records is not None or mode == "ranks"
     if mode == "ranks":
         res, rec = _rank_shard(sorted(image_paths), group, run)
@@ -588,7 +641,8 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
 
         def one(i, span):
             b, e = span
-            return _local(image_paths[b:e], b, devs[i], want_rec, run, slot=i)
+            return _local(image_paths[b:e], b, devs[i], want_rec, run, slot=i,
+                          warm=image_paths[max(0, b - hold):b])
         outs = run_on_devices(one, spans, devices=devs)
         res = tuple(sum(o[0][k] for o in outs) for k in range(3))
         rec = _concat_records([o[1] for o in outs]) if want_rec else None
@@ -611,12 +665,16 @@ def _concat_records(recs):
     return torch.cat([r.cpu() for r in recs if r is not None]) if any(r is not None for r in recs) else None
 
 
-def _local(paths, first, device, want_rec, run, slot=0):
+def _local(paths, first, device, want_rec, run, slot=0, warm=()):
     """One device over `paths` (global frame ids first, first + 1, ...): the fused /
     GPU-codec / generic loop; `slot`: the shard's own fused context (devices mode).
+    warm (box hold): the frames just before the shard, run through the detectors first.
     Returns ((processed, faces, plates), records or None)."""
     from .dist import RecordSink
     fd = run["face_detector"]
+    if run.get("hold"):
+        _hold_start(fused_context(fd, run["plate_detector"], run["batch_size"], device, slot), warm,
+                    run["loader"], run["mosaic_plates"])
     io = ThreadPoolExecutor(max_workers=run["num_workers"])
     sink = None
     if want_rec:
@@ -647,6 +705,23 @@ def _local(paths, first, device, want_rec, run, slot=0):
     return res, (sink.rec if sink is not None else None)
 
 
+def _hold_start(ctx, warm, loader, mosaic_plates):
+    """Box hold at the start of a shard: an empty history (fused contexts are cached across
+    calls), then the frames before the shard through vd_process WITHOUT the mosaic -- D_t
+    does not depend on the history, so the shard's first frames hold what one device
+    processing the whole list would."""
+    ctx.hold_reset()
+    flags = _lib.VD_PROC_FACES | _lib.VD_PROC_PLATES | (_lib.VD_PROC_MOSAIC_PLATES if mosaic_plates else 0)
+    imgs = [np.ascontiguousarray(loader(p), np.uint8) for p in warm]
+    i = 0
+    while i < len(imgs):                 # consecutive frames of one size, at most max_batch per call
+        j = i + 1
+        while j < len(imgs) and imgs[j].shape == imgs[i].shape and j - i < ctx.cfg.max_batch:
+            j += 1
+        ctx.process(np.stack(imgs[i:j]), flags=flags)
+        i = j
+
+
 def _rank_shard(paths, group, run):
     """This rank's contiguous shard of the (sorted) list through _local, then ONE
     all-gather of the box records of every rank (RCCL for device records). Totals and
@@ -661,7 +736,8 @@ def _rank_shard(paths, group, run):
     fd = run["face_detector"]
     err, res, rec = None, (0, 0, 0), None
     try:
-        res, rec = _local(paths[b:e], b, None, True, run)
+        hold = run.get("hold", 0)          # box hold: the frames before the shard warm it up
+        res, rec = _local(paths[b:e], b, None, True, run, **({"warm": paths[max(0, b - hold):b]} if hold else {}))
     except Exception as ex:      # noqa: BLE001 -- re-raised after the collective
         err = ex
     dev = f"cuda:{fd.device_ids[0]}" if run["fused"] else None
@@ -717,6 +793,7 @@ def _fused_batches(batches, output_dir, face_detector, plate_detector, batch_siz
             out, fcnt, _, pcnt, _ = pipe.collect(ticket)
         except Exception as e:           # a fault surfacing at the sync: the batch is dropped
             logger.error(f"parallel inference failed: {e}")
+            _hold_dropped(ctx)
             return
         for path, img in zip(files, out):
             dst = os.path.join(output_dir, f"processed_{os.path.basename(path)}")
@@ -742,7 +819,15 @@ def _fused_batches(batches, output_dir, face_detector, plate_detector, batch_siz
         for pipe in pipes.values():
             pipe.close()
         _save_all(save_futs, logger)
+    if ctx.cfg.hold_frames:
+        logger.info(f"box hold: {sum(_held_total(p.held) for p in pipes.values())} held boxes blurred")
     return tuple(totals)
+
+
+def _hold_dropped(ctx):
+    """A batch was dropped: boxes a batch old must not be held over the gap."""
+    if ctx.cfg.hold_frames:
+        ctx.hold_reset()
 
 
 def _submit_groups(files, imgs, pipes, ctx, batch_size, mosaic_plates, pending, finish, logger, sink=None, ids=None):
@@ -763,6 +848,7 @@ def _submit_groups(files, imgs, pipes, ctx, batch_size, mosaic_plates, pending, 
             cur = (pipe, ticket, [f for f, _ in items])
         except Exception as e:       # combine_detect.py:226-228: the batch is dropped
             logger.error(f"parallel inference failed: {e}")
+            _hold_dropped(ctx)
             cur = None
         if pending is not None:
             finish(pending)
@@ -812,14 +898,19 @@ def _gpu_codec_batches(batches, output_dir, face_detector, plate_detector, batch
     def processed(files, idx, faces, plates, stream):
         sink.add([ids[files[k]][0] for k in idx], [ids[files[k]][1] for k in idx], faces, plates, stream=stream)
 
+    def dropped(files, e):
+        logger.error(f"parallel inference failed: {e}")
+        _hold_dropped(ctx)
+
     stages = GpuJpegStages(ctx, max(int(batch_size), 1), flags, quality=quality, subsampling=2)
     try:
-        stages.run((job(files) for files in batches), done,
-                   on_error=lambda files, e: logger.error(f"parallel inference failed: {e}"),
+        stages.run((job(files) for files in batches), done, on_error=dropped,
                    on_processed=processed if sink is not None else None)
     finally:
         stages.close()
         _save_all(save_futs, logger)
+    if ctx.cfg.hold_frames:
+        logger.info(f"box hold: {_held_total(stages.held)} held boxes blurred")
     return tuple(totals)
 
 
