@@ -22,7 +22,7 @@
  *   vd_jpeg_decode / vd_jpeg_info <- cv2.imread(path) + cvtColor(BGR2RGB) of the ffmpeg-split
  *                                   frames                         combine_detect.py:167-172,
  *                                   (frames from convert_video_to_frames :279-476)
- *   vd_hold / vd_hold_reset / vd_read_held: boxes held across frames (cfg.hold_frames; no
+ *   vd_hold / vd_hold_reset / vd_hold_motion / vd_read_held: boxes held across frames (cfg.hold_frames; no
  *                                   reference equivalent: the reference treats every frame alone)
  *   vd_read_boxes                <- the complete per-frame box lists the reference's
  *                                   loop iterates (combine_detect.py:241-249), past any cap
@@ -267,6 +267,24 @@ int vd_read_boxes(vd_ctx* ctx, int net, int n, vd_boxes* out);
  * 3); the merged rows hold (K + 1) x (face + plate keep capacity) boxes per frame, so no
  * box is ever dropped (DESIGN.md gives the bytes). hold_frames == 0: no launch, no memory.
  *
+ * Motion (vd_hold_motion, VD_HOLD_MOTION_LINEAR; off by default): membership, order and ages
+ * of H_t are exactly the above; only the coordinates of a held box change. It is stretched
+ * along the displacement the face showed between its last two sightings, so it covers where
+ * the face was and where it is heading. For b = D_{t-a}[i] held with age a, c = clip(b):
+ *   predecessor  among the boxes p of D_{t-a-1}, the frame before the sighting, with
+ *            non-empty clip(p) and match(c, clip(p)) under the same P: the one of greatest
+ *            IoU on the clipped boxes, compared exactly (p1 beats p2 iff inter1 * union2 >
+ *            inter2 * union1 in 64-bit integers), ties to the lowest list index (faces then
+ *            plates, as stored); none if that frame does not exist (before the stream's
+ *            start or the last reset) or nothing matches;
+ *   velocity v = c - clip(p) and prediction q = c + a * v, per coordinate (q may be inverted);
+ *   held     = (min(b.x1, q.x1), min(b.y1, q.y1), max(b.x2, q.x2), max(b.y2, q.y2)): the hull
+ *            of the box as stored and its extrapolation, which always contains b; without a
+ *            predecessor held = b.
+ * With P = 100 a predecessor equals c, so nothing moves. Motion mode needs h, w <= 32768
+ * (VD_ERR_ARG otherwise; inter * union <= 2^61 is then exact, and |q| <= 9 * 32768 fits
+ * int32) and keeps K + 1 frames of history, so a shard warms up on K + 1 frames.
+ *
  * vd_hold: the same step for callers with their own detectors. det: the D lists of n
  * consecutive h x w frames (host or device; a host list with count[f] > cap is refused,
  * VD_ERR_CAPACITY, as by vd_mosaic). out (may be NULL): B_t per frame under the vd_boxes
@@ -277,6 +295,13 @@ int vd_hold(vd_ctx* ctx, const vd_boxes* det, int n, int h, int w, vd_boxes* out
 /* Forget the history: the next frame is frame 0 of a new stream (a cut, a new video, a
  * dropped batch). VD_OK and no effect in a context with hold_frames == 0. */
 int vd_hold_reset(vd_ctx* ctx);
+/* The motion model of held boxes (above): VD_HOLD_MOTION_OFF (the default) or
+ * VD_HOLD_MOTION_LINEAR; any other mode is VD_ERR_ARG. A change of mode forgets the history
+ * as vd_hold_reset does; setting the mode the context already has changes nothing. In a
+ * context with hold_frames == 0: VD_ERR_STATE for LINEAR, VD_OK and no effect for OFF. */
+#define VD_HOLD_MOTION_OFF 0
+#define VD_HOLD_MOTION_LINEAR 1
+int vd_hold_motion(vd_ctx* ctx, int mode);
 /* H_t (the held boxes alone, label = age) of frames [0, n) of the last vd_process / vd_hold
  * call, under the vd_boxes contract; ordered on the context stream like vd_read_boxes.
  * VD_ERR_STATE with hold_frames == 0 or before the first holding call. */

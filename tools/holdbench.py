@@ -1,7 +1,7 @@
 """Cost of box hold at the bench shape: Context.process on 64 synthetic 1080p frames already
 in HBM (fp32, faces | plates | mosaic, as bench.py's flagship step) with hold 0 / 2 / 8.
 
-    python tools/holdbench.py [--steps 20] [--warmup 3] [--json PATH]
+    python tools/holdbench.py [--steps 20] [--warmup 3] [--motion] [--json PATH]
 
 Per setting: ms/step (warm-up first, then the steps ended by one synchronise), held boxes
 per frame, and the hold launch's own time -- timing family 3 (post: decode, NMS, hold) of a
@@ -11,6 +11,13 @@ matches it by chance: the heavy case for the hold kernel and for the mosaic behi
 video holds a box only where a detection went missing). The first holding call also
 allocates the merged rows and the larger mosaic table; it is part of the warm-up, not of the
 timed steps.
+
+--motion: every hold > 0 is also run with hold_motion=True (the linear motion model: a
+predecessor search per held box, a history one frame deeper), reported as hold_<K>_motion,
+and the hold step alone (Context.hold on device lists, no detector) is timed on a synthetic
+sequence of MOVING boxes -- `--tracks` boxes per frame drifting a few pixels per frame, each
+missing from one frame in four -- where nearly every held box has a predecessor, which the
+noise frames exercise only by chance: moving_hold_<K> / moving_hold_<K>_motion.
 """
 import argparse
 import json
@@ -31,6 +38,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--holds", default="0,2,8")
+    ap.add_argument("--post-steps", type=int, default=5, help="event-timed steps behind the post family's figures")
+    ap.add_argument("--motion", action="store_true", help="also hold_motion=True, and the moving-box vd_hold run")
+    ap.add_argument("--tracks", type=int, default=32, help="boxes per frame of the moving-box run")
     ap.add_argument("--json", help="also write the result line to this file")
     a = ap.parse_args()
     import vdmi
@@ -42,10 +52,12 @@ def main():
     flags = _lib.VD_PROC_FACES | _lib.VD_PROC_PLATES | _lib.VD_PROC_MOSAIC
     fw, pw = weights.retinaface_state_dict(0), weights.yolov8n_state_dict(0)
     res = {"batch": B, "frame": [H, W], "precision": "fp32", "steps": a.steps, "warmup": a.warmup,
+           "post_steps": a.post_steps,
            "note": "noise frames: a box of the last `hold` frames is held unless matched by chance (heavy case)"}
     base_post = None
-    for hold in [int(v) for v in a.holds.split(",")]:
-        ctx = vdmi.Context(device=0, precision="fp32", max_batch=B, hold=hold)
+    holds = [int(v) for v in a.holds.split(",")]
+    for hold, motion in [(k, m) for k in holds for m in ((False, True) if a.motion and k else (False,))]:
+        ctx = vdmi.Context(device=0, precision="fp32", max_batch=B, hold=hold, hold_motion=motion)
         ctx.load_weights(_lib.VD_NET_RETINAFACE, fw)
         ctx.load_weights(_lib.VD_NET_YOLOV8N, pw)
         faces, plates = vdmi.DeviceBoxes(B, 256, dev), vdmi.DeviceBoxes(B, 256, dev)
@@ -66,24 +78,75 @@ def main():
         # the post family alone, in steps of their own (events around every launch slow the step)
         ctx.timing(True)
         ctx.timing_reset()
-        for _ in range(5):
+        for _ in range(a.post_steps):
             step()
         post_ms, launches, _ = ctx.timing_read(_lib.FAM_POST)
         ctx.timing(False)
-        r["post_ms_per_step"] = round(post_ms / 5, 4)
-        r["post_launches_per_step"] = launches / 5
+        r["post_ms_per_step"] = round(post_ms / a.post_steps, 4)
+        r["post_launches_per_step"] = launches / a.post_steps
         if hold == 0:
-            base_post = post_ms / 5
+            base_post = post_ms / a.post_steps
         elif base_post is not None:
-            r["hold_launch_ms"] = round(post_ms / 5 - base_post, 4)
-        res[f"hold_{hold}"] = r
+            r["hold_launch_ms"] = round(post_ms / a.post_steps - base_post, 4)
+        res[f"hold_{hold}" + ("_motion" if motion else "")] = r
         ctx.close()
+    if a.motion:
+        res.update(moving_boxes(vdmi, _lib, dev, B, H, W, a.tracks, [k for k in holds if k], a.steps, a.warmup))
     line = json.dumps(res)
     print(line, flush=True)
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
             f.write(line + "\n")
+
+
+def moving_boxes(vdmi, _lib, dev, B, H, W, tracks, holds, steps, warmup):
+    """Context.hold alone on B frames of `tracks` drifting boxes (device lists in, device lists
+    out): the hold launch's own time (timing family 3) and what it held, motion off and on."""
+    import numpy as np
+    rng = np.random.default_rng(0)
+    x0, y0 = rng.integers(0, W - 200, tracks), rng.integers(0, H - 200, tracks)
+    vx, vy = rng.integers(-6, 7, tracks), rng.integers(-4, 5, tracks)
+    sz = rng.integers(40, 160, tracks)
+    det = _lib.HostBoxes(B, tracks)
+    for t in range(B):
+        k = 0
+        for i in range(tracks):
+            if (t + i) % 4 == 3:                      # a missed detection, one frame in four
+                continue
+            x, y = int(x0[i] + vx[i] * t), int(y0[i] + vy[i] * t)
+            det.xyxy[t, k] = (x, y, x + int(sz[i]), y + int(sz[i]))
+            k += 1
+        det.count[t] = k
+    dbox = vdmi.DeviceBoxes(B, tracks, dev)
+    dbox.count.copy_(torch.from_numpy(det.count))
+    dbox.xyxy.copy_(torch.from_numpy(det.xyxy))
+    torch.cuda.synchronize()
+    res = {}
+    for K in holds:
+        stored = None
+        for motion in (False, True):
+            ctx = vdmi.Context(device=0, precision="fp32", max_batch=B, hold=K, hold_motion=motion)
+            out = vdmi.DeviceBoxes(B, tracks * (K + 1), dev)
+            for _ in range(max(warmup, 1)):
+                ctx.hold(dbox, H, W, out=out)
+            ctx.timing(True)
+            ctx.timing_reset()
+            for _ in range(steps):
+                ctx.hold(dbox, H, W, out=out)
+            ms, launches, _ = ctx.timing_read(_lib.FAM_POST)
+            ctx.timing(False)
+            held = ctx.read_held(B)
+            r = {"hold_launch_ms": round(ms / steps, 4), "launches_per_call": launches / steps,
+                 "boxes_per_frame": float(det.count.mean()), "held_per_frame": float(held.count.mean())}
+            rows = [held.xyxy[f, :int(held.count[f])].copy() for f in range(B)]
+            if not motion:
+                stored = rows
+            else:
+                r["moved_per_frame"] = sum(int((m != s).any(1).sum()) for m, s in zip(rows, stored)) / B
+            res[f"moving_hold_{K}" + ("_motion" if motion else "")] = r
+            ctx.close()
+    return res
 
 
 if __name__ == "__main__":

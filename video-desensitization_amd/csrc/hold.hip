@@ -8,7 +8,18 @@
 // iff 100 * inter >= P * union in 64-bit integers. Every candidate's predicate stands alone
 // (no greedy chain), so the kernel is data-parallel over candidates.
 //
-// hold_kernel, one launch per call, n + K workgroups of 256 threads (4 waves of 64):
+// Motion mode (vd_hold_motion, HoldArgs::motion; the kernel is instantiated on it, and the
+// mode-0 instantiation is the code as it was): membership, order and ages of H_t are unchanged,
+// but a kept candidate b = D_{t-a}[i] with clipped box c looks in D_{t-a-1} for its predecessor
+// -- among the boxes p whose clip matches c, the one of greatest IoU, compared exactly as
+// inter1 * union2 > inter2 * union1 in 64 bits (h, w <= 32768: at most 2^61), lowest list index
+// on ties -- and is stored as the hull of b and q = c + a * (c - clip(p)). No predecessor
+// (no such frame, or nothing matches): b as stored. The history is K + 1 frames deep then, and
+// the clipped boxes of ages 0..K are staged in LDS where they fit (age K + 1, the predecessor
+// frame of an age-K candidate, is read and clipped from global memory).
+//
+// hold_kernel, one launch per call, n + depth workgroups (depth = K, motion: K + 1) of 256
+// threads (4 waves of 64):
 //   workgroup f < n    frame f. The lists of frames f, f-1, .., f-K come from this call's two
 //                      keep lists or, before frame 0, from the history (hold_state.h). The clipped
 //                      boxes of frames f .. f-K+1 -- everything a candidate is compared against,
@@ -32,7 +43,6 @@ namespace {
 constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / 64;
 constexpr int LDS_BOXES = 2048;        // 32 KB of clipped reference boxes
-constexpr int FR = VD_HOLD_MAX + 1;    // frames a workgroup may name: ages 0..K
 
 struct Seg {                           // one frame's list: part A then part B
     const int4* a; const int4* b;
@@ -77,12 +87,26 @@ __device__ __forceinline__ bool boxes_match(int4 q, long long aq, int4 r, int P)
     return 100 * inter >= (long long)P * uni;
 }
 
+// motion mode: the same test, handing out inter and union for the best-IoU comparison
+__device__ __forceinline__ bool boxes_match_iou(int4 q, long long aq, int4 r, int P, long long* inter_out,
+                                                long long* uni_out) {
+    const int iw = min(q.z, r.z) - max(q.x, r.x), ih = min(q.w, r.w) - max(q.y, r.y);
+    if (iw <= 0 || ih <= 0) return false;
+    const long long inter = (long long)iw * ih;
+    const long long uni = aq + (long long)(r.z - r.x) * (r.w - r.y) - inter;
+    *inter_out = inter;
+    *uni_out = uni;
+    return 100 * inter >= (long long)P * uni;
+}
+
+template <int MOTION>
 __global__ __launch_bounds__(THREADS) void hold_kernel(HoldArgs p) {
+    constexpr int FRM = VD_HOLD_MAX + 1 + MOTION;         // frames a workgroup may name: ages 0..K (motion: 0..K + 1)
     __shared__ __attribute__((aligned(16))) int4 s_ref[LDS_BOXES];
-    __shared__ const int4* s_pa[FR];
-    __shared__ const int4* s_pb[FR];
-    __shared__ int s_na[FR], s_nb[FR];
-    __shared__ int s_off[FR + 1];
+    __shared__ const int4* s_pa[FRM];
+    __shared__ const int4* s_pb[FRM];
+    __shared__ int s_na[FRM], s_nb[FRM];
+    __shared__ int s_off[FRM + 1];
     __shared__ int s_wsum[WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int f = blockIdx.x;
@@ -97,22 +121,25 @@ __global__ __launch_bounds__(THREADS) void hold_kernel(HoldArgs p) {
         return;
     }
 
-    if (tid <= p.K) {
+    const int last = p.K + MOTION;                        // the oldest frame named: age K (motion: K + 1)
+    if (tid <= last) {
         const Seg s = seg_of(p, f, tid);
         s_pa[tid] = s.a; s_pb[tid] = s.b; s_na[tid] = s.na; s_nb[tid] = s.nb;
     }
     __syncthreads();
     if (tid == 0) {
         int o = 0;
-        for (int j = 0; j <= p.K; ++j) { s_off[j] = o; o += s_na[j] + s_nb[j]; }
-        s_off[p.K + 1] = o;
+        for (int j = 0; j <= last; ++j) { s_off[j] = o; o += s_na[j] + s_nb[j]; }
+        s_off[last + 1] = o;
     }
     __syncthreads();
     auto load = [&](int j, int i) -> int4 { return i < s_na[j] ? s_pa[j][i] : s_pb[j][i - s_na[j]]; };
 
-    const bool in_lds = s_off[p.K] <= LDS_BOXES;          // reference boxes: frames of age 0..K-1
+    // reference boxes in LDS: frames of age 0..K-1 (motion: 0..K, the predecessor frames of ages 1..K-1 too)
+    const int staged = p.K + MOTION;
+    const bool in_lds = s_off[staged] <= LDS_BOXES;
     if (in_lds)
-        for (int j = 0; j < p.K; ++j) {
+        for (int j = 0; j < staged; ++j) {
             const int nj = s_na[j] + s_nb[j], o = s_off[j];
             for (int i = tid; i < nj; i += THREADS) s_ref[o + i] = clip_box(load(j, i), p.w, p.h);
         }
@@ -151,6 +178,29 @@ __global__ __launch_bounds__(THREADS) void hold_kernel(HoldArgs p) {
                     }
                 }
             }
+            if constexpr (MOTION) {
+                if (keep) {                                // keep implies c < nc and q non-empty
+                    const int4 q = clip_box(raw, p.w, p.h);
+                    const long long aq = (long long)(q.z - q.x) * (q.w - q.y);
+                    const int pj = a + 1;                  // the frame before the sighting
+                    const int np = s_na[pj] + s_nb[pj];    // 0: no such frame
+                    const bool pl = in_lds && pj < staged;
+                    const int po = s_off[pj];
+                    long long bi = 0, bu = 1;              // best inter / union so far (bi == 0: none)
+                    int4 best = q;
+                    for (int i = 0; i < np; ++i) {
+                        const int4 r = pl ? s_ref[po + i] : clip_box(load(pj, i), p.w, p.h);
+                        long long in_, un_;
+                        if (boxes_match_iou(q, aq, r, p.P, &in_, &un_) && in_ * bu > bi * un_) {
+                            bi = in_; bu = un_; best = r;  // strictly greater: ties keep the lowest index
+                        }
+                    }
+                    // q + a * (q - best) per coordinate; |.| <= 9 * 32768
+                    const int px1 = q.x + a * (q.x - best.x), py1 = q.y + a * (q.y - best.y);
+                    const int px2 = q.z + a * (q.z - best.z), py2 = q.w + a * (q.w - best.w);
+                    raw = make_int4(min(raw.x, px1), min(raw.y, py1), max(raw.z, px2), max(raw.w, py2));
+                }
+            }
             const uint64_t bal = __ballot(keep);
             if (lane == 0) s_wsum[wid] = __popcll(bal);
             __syncthreads();
@@ -164,7 +214,7 @@ __global__ __launch_bounds__(THREADS) void hold_kernel(HoldArgs p) {
             if (keep) {
                 const int pos = base + before + __popcll(bal & ((1ULL << lane) - 1ULL));
                 if (pos < p.mcap) {                        // always: mcap = (K + 1) * hcap (vd_common.h)
-                    row[pos] = raw;                        // unclipped, as stored
+                    row[pos] = raw;                        // unclipped, as stored (motion: the hull)
                     age_row[pos] = a;
                 }
             }
@@ -200,10 +250,14 @@ __global__ __launch_bounds__(THREADS) void hold_gather_kernel(const int* m_xy, c
 }  // namespace
 
 hipError_t vd_launch_hold(const HoldArgs& a, hipStream_t s) {
-    if (a.n <= 0 || a.K <= 0 || a.K > VD_HOLD_MAX) return hipErrorInvalidValue;
+    if (a.n <= 0 || a.K <= 0 || a.K > VD_HOLD_MAX || (a.motion != 0 && a.motion != 1)) return hipErrorInvalidValue;
+    if (a.motion && (a.h > 32768 || a.w > 32768)) return hipErrorInvalidValue;   // inter * union exact in 64 bits
     if ((a.cnt0 ? a.cap0 : 0) + (a.cnt1 ? a.cap1 : 0) > a.hcap || a.mcap < (a.K + 1) * a.hcap)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(hold_kernel, dim3(a.n + a.K), dim3(THREADS), 0, s, a);
+    if (a.motion)
+        hipLaunchKernelGGL(hold_kernel<1>, dim3(a.n + a.K + 1), dim3(THREADS), 0, s, a);
+    else
+        hipLaunchKernelGGL(hold_kernel<0>, dim3(a.n + a.K), dim3(THREADS), 0, s, a);
     return hipGetLastError();
 }
 

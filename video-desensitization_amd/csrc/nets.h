@@ -192,8 +192,8 @@ struct Ctx {
     void* mosaic_table = nullptr; size_t mosaic_table_bytes = 0;
     void* blur_table = nullptr; size_t blur_table_bytes = 0;   // Gaussian mode: box plan + dependent-box scratch
     // box hold (hold.hip; cfg.hold_frames > 0 only, allocated by the first holding call)
-    HoldState hold;                               // K, P, valid history slots, current buffer, last frame size
-    int* hold_hist[2] = {nullptr, nullptr};       // ping-pong history: [K] counts, then (64-B aligned) [K][hcap][4]
+    HoldState hold;                               // K, P, motion mode, valid history slots, current buffer, last frame size
+    int* hold_hist[2] = {nullptr, nullptr};       // ping-pong history: [depth] counts, then (64-B aligned) [depth][hcap][4]
     int hold_hcap = 0;                            // history row capacity (boxes)
     void* hold_rows = nullptr; size_t hold_rows_bytes = 0;   // the last call's merged rows, ages, |B|, |D|
     HoldArgs hold_last{};                         // the last launch (merged-row pointers for the readers)
@@ -282,6 +282,7 @@ struct Ctx {
     int launch_hold(int n, int h, int w, const int* cnt0, const int* xy0, int cap0, const int* cnt1, const int* xy1,
                     int cap1);
     int hold_history(int hcap);                   // history buffers of at least this row capacity
+    int hold_set_motion(int mode);                // vd_hold_motion: a change forgets the history and its buffers
     int hold_read(int n, int held_only, vd_boxes* out);   // merged rows -> caller lists (label = age)
 };
 

@@ -1001,7 +1001,7 @@ int Ctx::launch_blur(const uint8_t* in, uint8_t* out, int n, int h, int w, size_
 // carried over (weights loaded, or a wider vd_hold list, after the first holding call).
 int Ctx::hold_history(int hcap) {
     if (hcap <= hold_hcap) return VD_OK;
-    const int K = hold.K;
+    const int K = hold.depth();                   // slots: hold_frames, one more in motion mode
     const size_t bytes = 64 + (size_t)K * hcap * 16;
     int* nb[2] = {nullptr, nullptr};
     for (int i = 0; i < 2; ++i)
@@ -1026,9 +1026,26 @@ int Ctx::hold_history(int hcap) {
     return VD_OK;
 }
 
+// The buffers are sized by the depth (K or K + 1 slots), so a change of mode drops them; the
+// next holding call allocates them anew. The last call's merged rows stay readable.
+int Ctx::hold_set_motion(int mode) {
+    if (mode == hold.motion) return VD_OK;
+    VD_CHECK_HIP(hipStreamSynchronize(stream));   // a queued launch may still read the history
+    for (int i = 0; i < 2; ++i) {
+        if (hold_hist[i]) hipFree(hold_hist[i]);
+        hold_hist[i] = nullptr;
+    }
+    hold_hcap = 0;
+    hold.motion = mode;
+    hold.reset();
+    return VD_OK;
+}
+
 int Ctx::launch_hold(int n, int h, int w, const int* cnt0, const int* xy0, int cap0, const int* cnt1, const int* xy1,
                      int cap1) {
     const int K = hold.K;
+    if (hold.motion && (h > 32768 || w > 32768))  // inter * union <= 2^61 stays exact in 64 bits
+        return vd_set_error(VD_ERR_ARG, "hold motion: frames of at most 32768 x 32768 (got %d x %d)", h, w);
     // rows sized for the loaded detectors' complete keep lists (vd_process never regrows them)
     // and for this call's lists; (K + 1) rows of that size hold D and K complete older lists
     const int nets = (face.loaded ? face.post.kcap : 0) + (plate.loaded ? plate.post.kcap : 0);
@@ -1041,7 +1058,7 @@ int Ctx::launch_hold(int n, int h, int w, const int* cnt0, const int* xy0, int c
     if ((rc = ensure_staging(&hold_rows, &hold_rows_bytes, nb * 16 + nb * 4 + (size_t)n * 8 + 64))) return rc;
     hold.begin(h, w);
     HoldArgs a{};
-    a.n = n; a.h = h; a.w = w; a.K = K; a.P = hold.P;
+    a.n = n; a.h = h; a.w = w; a.K = K; a.P = hold.P; a.motion = hold.motion;
     a.cnt0 = cnt0; a.xy0 = xy0; a.cap0 = cap0;
     a.cnt1 = cnt1; a.xy1 = xy1; a.cap1 = cap1;
     a.hist_cnt = hold_hist[hold.cur]; a.hist_xy = hold_hist[hold.cur] + 16;
@@ -1656,6 +1673,18 @@ int vd_hold_reset(vd_ctx* h) {
     VD_ENTRY(ctx);
     ctx->hold.reset();
     return VD_OK;
+}
+
+int vd_hold_motion(vd_ctx* h, int mode) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (mode != VD_HOLD_MOTION_OFF && mode != VD_HOLD_MOTION_LINEAR)
+        return vd_set_error(VD_ERR_ARG, "vd_hold_motion: mode %d (expected 0 = off or 1 = linear)", mode);
+    if (!ctx->hold.K) {
+        if (mode) return vd_set_error(VD_ERR_STATE, "vd_hold_motion: context created with hold_frames == 0");
+        return VD_OK;
+    }
+    return ctx->hold_set_motion(mode);
 }
 
 int vd_read_held(vd_ctx* h, int n, vd_boxes* out) {

@@ -434,9 +434,10 @@ int vd_blur_weights(int ksize, float sigma, uint32_t* q);   // host; 0, or -1 fo
 // Lists 0 / 1 as the mosaic takes them (list 1 optional); xy pointers 16-B aligned.
 struct HoldArgs {
     int n, h, w, K, P;                               // frames, frame size, hold_frames, hold_iou_pct
+    int motion;                                      // vd_hold_motion mode; history depth = K + motion slots
     const int* cnt0; const int* xy0; int cap0;       // this call's D lists: list 0 (faces)
     const int* cnt1; const int* xy1; int cap1;       //   list 1 (plates, optional)
-    const int* hist_cnt; const int* hist_xy;         // history read: [K], [K][hcap][4] (hold_state.h)
+    const int* hist_cnt; const int* hist_xy;         // history read: [depth], [depth][hcap][4] (hold_state.h)
     int* next_cnt; int* next_xy;                     // history written: the other buffer
     int hcap, hn;                                    // history row capacity (>= cap0 + cap1), valid slots
     int* m_xy; int* m_age; int* m_count; int* m_own; // merged rows [n][mcap][4], ages [n][mcap], |B| [n], |D| [n]

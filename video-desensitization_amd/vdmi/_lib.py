@@ -22,6 +22,7 @@ VD_MOSAIC_OUT_OF_PLACE = 0
 VD_BLUR_PIXELATE, VD_BLUR_GAUSSIAN = 0, 1
 VD_BLUR_KSIZE_MAX = 127
 VD_HOLD_MAX = 8
+VD_HOLD_MOTION_OFF, VD_HOLD_MOTION_LINEAR = 0, 1
 VD_PROC_FACES, VD_PROC_PLATES, VD_PROC_MOSAIC, VD_PROC_MOSAIC_PLATES = 1, 2, 4, 8
 FAM_CONV, FAM_MOSAIC, FAM_LETTERBOX, FAM_POST, FAM_OTHER, FAM_PLATE_CONV, FAM_MOSAIC_CELLS = 0, 1, 2, 3, 4, 5, 6
 
@@ -85,6 +86,7 @@ SIGNATURES = [
     ("vd_read_boxes", _I, [_P, _I, _I, ctypes.POINTER(vd_boxes)]),
     ("vd_hold", _I, [_P, ctypes.POINTER(vd_boxes), _I, _I, _I, ctypes.POINTER(vd_boxes)]),
     ("vd_hold_reset", _I, [_P]),
+    ("vd_hold_motion", _I, [_P, _I]),
     ("vd_read_held", _I, [_P, _I, ctypes.POINTER(vd_boxes)]),
     ("vd_jpeg_decode", _I, [_P, ctypes.POINTER(_P), ctypes.POINTER(_SZ), _I, _P, _I, _I, _SZ, _I]),
     ("vd_jpeg_info", _I, [_P, _SZ, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
@@ -158,13 +160,16 @@ def default_cfg():
     return c
 
 
-def check_hold(hold, hold_iou_pct):
-    """(hold_frames, hold_iou_pct) as ints; ValueError outside [0, VD_HOLD_MAX] / [1, 100]."""
+def check_hold(hold, hold_iou_pct, hold_motion=False):
+    """(hold_frames, hold_iou_pct) as ints; ValueError outside [0, VD_HOLD_MAX] / [1, 100],
+    and for hold_motion (vd_hold_motion's linear mode) without hold."""
     hold, pct = int(hold), int(hold_iou_pct)
     if not 0 <= hold <= VD_HOLD_MAX:
         raise ValueError(f"hold {hold}: expected 0 (off) .. {VD_HOLD_MAX} frames")
     if not 1 <= pct <= 100:
         raise ValueError(f"hold_iou_pct {pct}: expected 1 .. 100")
+    if hold_motion and not hold:
+        raise ValueError("hold_motion moves held boxes: it needs hold > 0")
     return hold, pct
 
 

@@ -101,7 +101,8 @@ class Context:
     def __init__(self, device=0, precision="bf16", max_batch=64, input_shape=(640, 640), confidence=0.5,
                  nms_iou=0.4, max_boxes=256, mosaic_level=8, plate_nc=1, plate_conf=0.5, plate_iou=0.7,
                  plate_max_det=300, plate_imgsz=640, microbatch=0, microbatch_stage=2, options=None,
-                 blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30):
+                 blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30,
+                 hold_motion=False):
         """blur: what process() applies to the kept boxes: "pixelate" (the reference's
         INTER_NEAREST mosaic, the default) or "gaussian" (GaussianBlur(region, (blur_ksize,
         blur_ksize), blur_sigma) per clipped box, in list order; blur_ksize odd in [3, 127],
@@ -110,10 +111,15 @@ class Context:
         frames, and a box stays in process()'s blur list for up to `hold` frames (0 = off,
         at most 8) after the last frame in which a box matched it (100 * inter >=
         hold_iou_pct * union on the clipped boxes), so a missed detection never shows a
-        face in the clear; hold_reset() starts a new stream."""
+        face in the clear; hold_reset() starts a new stream.
+        hold_motion (needs hold > 0): a held box is stretched along the displacement between
+        its last two sightings (vd_hold_motion's linear mode): the hull of the stored box and
+        its extrapolation `age` frames on, so it also covers a face that keeps moving. Same
+        membership, order and ages; frames of at most 32768 x 32768. Kept as self.hold_motion
+        (it is no vd_cfg field); set_hold_motion() changes it."""
         if blur not in BLUR_MODES:
             raise ValueError(f"blur {blur!r}: expected 'pixelate' or 'gaussian'")
-        hold, hold_iou_pct = _lib.check_hold(hold, hold_iou_pct)   # before the library is touched
+        hold, hold_iou_pct = _lib.check_hold(hold, hold_iou_pct, hold_motion)   # before the library is touched
         lib = _lib.load()
         cfg = _lib.default_cfg()
         cfg.input_h, cfg.input_w = int(input_shape[0]), int(input_shape[1])
@@ -146,6 +152,9 @@ class Context:
         check(lib.vd_create(ctypes.byref(cfg), self.device, ctypes.byref(h)))
         self._h = h
         self._lib = lib
+        self.hold_motion = False
+        if hold_motion:
+            self.set_hold_motion(True)
         for k, v in dict(options or {}).items():   # kernel-selection switches (vd_set_option)
             self.set_option(k, v)
 
@@ -366,6 +375,13 @@ class Context:
     def hold_reset(self):
         """vd_hold_reset: forget the history; the next frame starts a new stream."""
         check(self._lib.vd_hold_reset(self._h))
+
+    def set_hold_motion(self, on):
+        """vd_hold_motion: held boxes follow the motion of their last two sightings (True) or
+        stay where they were last seen (False). A change forgets the history."""
+        mode = _lib.VD_HOLD_MOTION_LINEAR if on else _lib.VD_HOLD_MOTION_OFF
+        check(self._lib.vd_hold_motion(self._h, mode))
+        self.hold_motion = bool(on)
 
     def read_held(self, n, cap=None, out=None):
         """The held boxes H (label = age) of frames [0, n) of the last process() / hold()

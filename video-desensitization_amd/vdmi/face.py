@@ -95,9 +95,10 @@ class Retinaface(object):
         "blur": "pixelate",
         "blur_ksize": 31,
         "blur_sigma": 0.0,
-        # box hold across frames in the fused vd_process: Context(hold=..., hold_iou_pct=...)
+        # box hold across frames in the fused vd_process: Context(hold=..., hold_iou_pct=..., hold_motion=...)
         "hold": 0,
         "hold_iou_pct": 30,
+        "hold_motion": False,
     }
 
     @classmethod
@@ -126,7 +127,8 @@ class Retinaface(object):
                              input_shape=self.input_shape[:2], confidence=self.confidence, nms_iou=self.nms_iou,
                              max_boxes=self.max_boxes, options=self.options, blur=self.blur,
                              blur_ksize=self.blur_ksize, blur_sigma=self.blur_sigma, hold=self.hold,
-                             hold_iou_pct=self.hold_iou_pct) for d in self.device_ids]
+                             hold_iou_pct=self.hold_iou_pct, hold_motion=self.hold_motion)
+                     for d in self.device_ids]
         self.ctx = self.ctxs[0]
         self.generate()
 

@@ -500,7 +500,8 @@ def _new_fused_context(fd, pd, batch_size, dev):
                   plate_imgsz=pd.ctx.cfg.plate_imgsz, options=getattr(fd, "options", None),
                   blur="gaussian" if fd.ctx.cfg.blur_mode == _lib.VD_BLUR_GAUSSIAN else "pixelate",
                   blur_ksize=fd.ctx.cfg.blur_ksize or 31, blur_sigma=fd.ctx.cfg.blur_sigma,
-                  hold=fd.ctx.cfg.hold_frames, hold_iou_pct=fd.ctx.cfg.hold_iou_pct or 30)
+                  hold=fd.ctx.cfg.hold_frames, hold_iou_pct=fd.ctx.cfg.hold_iou_pct or 30,
+                  hold_motion=fd.ctx.hold_motion)
     ctx.load_weights(_lib.VD_NET_RETINAFACE, fd.state_dict)
     ctx.load_weights(_lib.VD_NET_YOLOV8N, pd.state_dict)
     return ctx
@@ -515,9 +516,12 @@ def _blur_matches(cfg, blur, ksize, sigma):
             and cfg.blur_sigma == ctypes.c_float(sigma).value)
 
 
-def _hold_matches(cfg, hold, pct):
-    """The context's vd_process holds boxes exactly so (hold 0: not at all)."""
-    return cfg.hold_frames == hold and (hold == 0 or cfg.hold_iou_pct == pct)
+def _hold_matches(ctx, hold, pct, motion=False):
+    """The context's vd_process holds boxes exactly so (hold 0: not at all). The motion mode
+    is no cfg field: the Context keeps it."""
+    cfg = ctx.cfg
+    return cfg.hold_frames == hold and (hold == 0 or (cfg.hold_iou_pct == pct
+                                                     and bool(ctx.hold_motion) == bool(motion)))
 
 
 def _is_vdmi_pair(face_detector, plate_detector):
@@ -555,7 +559,8 @@ def _shard_mode(shard, face_detector, group, fused):
 def batch_process_images(input_dir, output_dir, face_detector, plate_detector, batch_size=16,
                          loader=None, saver=None, mosaic_plates=False, mosaic_level=8, num_workers=6,
                          gpu_codec="auto", jpeg_quality=95, shard="auto", group=None, records=None,
-                         blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30):
+                         blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30,
+                         hold_motion=False):
     """combine_detect.py:183-277. Returns (total_processed, total_faces, total_plates).
 
     gpu_codec ("auto" | True | False): with vdmi detectors, no custom loader/saver and
@@ -575,8 +580,11 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     frames are ONE video in the order of their sorted names, and a box stays blurred for up to
     `hold` frames after the last frame in which a detection matched it, so a single missed
     detection never leaves a face in the clear. It needs the vdmi Retinaface / YOLO pair and a
-    face detector built with the same settings (Retinaface(hold=..., hold_iou_pct=...)), else
-    ValueError. The history starts empty at every call and again after a dropped batch; a
+    face detector built with the same settings (Retinaface(hold=..., hold_iou_pct=...,
+    hold_motion=...)), else ValueError. hold_motion (needs hold > 0): a held box is stretched
+    along the displacement between its last two sightings (Context(hold_motion=True)); a
+    shard then warms up on hold + 1 frames, the depth of the history.
+    The history starts empty at every call and again after a dropped batch; a
     shard that starts at frame b > 0 first runs frames [max(0, b - hold), b) through the
     detectors alone (host-decoded, nothing written), so sharded output equals one device's.
     Frames of several sizes: the history clears at every size change, and a batch that mixes
@@ -609,7 +617,8 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
         raise ValueError("gpu_codec=True reads and writes JPEG bytes itself: it cannot use a custom loader/saver")
     loader = loader or load_image_rgb
     saver = saver or save_output_image
-    hold, hold_iou_pct = _lib.check_hold(hold, hold_iou_pct)
+    hold, hold_iou_pct = _lib.check_hold(hold, hold_iou_pct, hold_motion)
+    warm_frames = hold + 1 if hold_motion else hold      # the history's depth
     image_paths = [os.path.join(input_dir, f) for f in os.listdir(input_dir) if f.lower().endswith(IMAGE_EXT)]
     if hold:
         image_paths.sort()               # the frames of one video, in order
@@ -618,10 +627,10 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
         raise ValueError(f"blur {blur!r}: expected 'pixelate' or 'gaussian'")
     fused = (_is_vdmi_pair(face_detector, plate_detector) and mosaic_level == face_detector.ctx.cfg.mosaic_level
              and _blur_matches(face_detector.ctx.cfg, blur, blur_ksize, blur_sigma)
-             and _hold_matches(face_detector.ctx.cfg, hold, hold_iou_pct))
+             and _hold_matches(face_detector.ctx, hold, hold_iou_pct, hold_motion))
     if hold and not fused:
         raise ValueError("hold > 0 needs the vdmi Retinaface / YOLO drop-ins and a face detector built with the "
-                         "same mosaic_level, blur and hold settings (Retinaface(hold=..., hold_iou_pct=...)); "
+                         "same mosaic_level, blur and hold settings (Retinaface(hold=..., hold_iou_pct=..., hold_motion=...)); "
                          "other detectors call Context.hold themselves")
     all_jpeg = all(p.lower().endswith((".jpg", ".jpeg")) for p in image_paths)
     codec = fused and gpu_codec and (gpu_codec is True or (not custom_io and all_jpeg))
@@ -630,7 +639,7 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
                batch_size=batch_size, loader=loader, saver=saver, mosaic_plates=mosaic_plates,
                mosaic_level=mosaic_level, num_workers=num_workers, fused=fused, codec=codec,
                jpeg_quality=jpeg_quality, logger=logger,
-               blur=(blur, int(blur_ksize), float(blur_sigma)), hold=hold)
+               blur=(blur, int(blur_ksize), float(blur_sigma)), hold=hold, hold_warm=warm_frames)
     want_rec = records is not None or mode == "ranks"
     if mode == "ranks":
         res, rec = _rank_shard(sorted(image_paths), group, run)
@@ -642,7 +651,7 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
         def one(i, span):
             b, e = span
             return _local(image_paths[b:e], b, devs[i], want_rec, run, slot=i,
-                          warm=image_paths[max(0, b - hold):b])
+                          warm=image_paths[max(0, b - warm_frames):b])
         outs = run_on_devices(one, spans, devices=devs)
         res = tuple(sum(o[0][k] for o in outs) for k in range(3))
         rec = _concat_records([o[1] for o in outs]) if want_rec else None
@@ -736,7 +745,7 @@ def _rank_shard(paths, group, run):
     fd = run["face_detector"]
     err, res, rec = None, (0, 0, 0), None
     try:
-        hold = run.get("hold", 0)          # box hold: the frames before the shard warm it up
+        hold = run.get("hold_warm", 0)     # box hold: the frames before the shard warm it up
         res, rec = _local(paths[b:e], b, None, True, run, **({"warm": paths[max(0, b - hold):b]} if hold else {}))
     except Exception as ex:      # noqa: BLE001 -- re-raised after the collective
         err = ex
