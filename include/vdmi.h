@@ -24,6 +24,8 @@
  *                                   (frames from convert_video_to_frames :279-476)
  *   vd_hold / vd_hold_reset / vd_hold_motion / vd_read_held: boxes held across frames (cfg.hold_frames; no
  *                                   reference equivalent: the reference treats every frame alone)
+ *   vd_mask / vd_mask_boxes: where the blur lies (a margin around every box, an elliptical mask inside it;
+ *                                   no reference equivalent: the reference blurs the detector's rectangle)
  *   vd_read_boxes                <- the complete per-frame box lists the reference's
  *                                   loop iterates (combine_detect.py:241-249), past any cap
  *   vd_sync / vd_last_error / vd_destroy: runtime plumbing (no reference equivalent;
@@ -307,12 +309,66 @@ int vd_hold_motion(vd_ctx* ctx, int mode);
  * VD_ERR_STATE with hold_frames == 0 or before the first holding call. */
 int vd_read_held(vd_ctx* ctx, int n, vd_boxes* out);
 
+/* ---- mask shaping: grow the blurred boxes by a margin, blur ellipses -------------
+ * A context has a mask setting (shape, g). The default (VD_MASK_RECT, 0) blurs the boxes as
+ * stored: no extra launch, no extra memory. With any other setting every list L the context is
+ * about to blur -- vd_process with VD_PROC_MOSAIC (the complete keep lists, or B_t = D_t ++ H_t
+ * under hold), vd_mosaic, vd_blur -- is shaped first. Integers only, so the result is defined
+ * to the bit:
+ *   grow(b, g)  b = (x1, y1, x2, y2) as stored, unclipped; W = x2 - x1, H = y2 - y1. W <= 0 or
+ *            H <= 0: b unchanged (an empty box stays empty). Otherwise gx = (W*g + 199) / 200 and
+ *            gy = (H*g + 199) / 200 in 64 bits (floor division of non-negative numbers: the
+ *            ceiling of half the growth, so a grown box never covers less than the real-valued
+ *            one) and b' = (x1-gx, y1-gy, x2+gx, y2+gy), each coordinate clamped to
+ *            [-2^30, 2^30]. g is a percentage in [0, VD_MASK_GROW_MAX]: a side becomes about
+ *            (1 + g/100) times as long.
+ *   R        L' = grow(L) -- counts and order kept: faces, then plates, then held boxes -- goes
+ *            through the rectangular pass of vd_mosaic / vd_blur unchanged (clip, box j reads box
+ *            j-1, every output byte written). VD_MASK_RECT: out = R.
+ *   ellipse  for a grown box b' with W, H > 0 (64-bit) and a pixel (x, y) of b' clipped to the
+ *            frame: inside iff dx*dx*H*H + dy*dy*W*W <= W*W*H*H with dx = 2x + 1 - (x1 + x2),
+ *            dy = 2y + 1 - (y1 + y2): the pixel centre against the ellipse inscribed in the
+ *            UNCLIPPED grown box. In the clipped box |dx| <= W and |dy| <= H, so for W, H <= 32768
+ *            both sides stay at or below 2^61. A box with W > 32768 or H > 32768 counts as inside
+ *            everywhere in its clipped rectangle (it covers more, never less).
+ *   VD_MASK_ELLIPSE  E_k = the pixels of box k's clipped rectangle inside its ellipse;
+ *            out(p) = R(p) if p lies in some E_k, else in(p). A pixel in the corner of one box but
+ *            inside another box's ellipse stays hidden; for a single box this is
+ *            blur-the-rectangle, composite-by-ellipse.
+ * Coverage: with g >= 42 every pixel of the box as stored lies inside the grown box's ellipse
+ * (the corner pixel is the worst: ((W-1) / (W+2gx))^2 + ((H-1) / (H+2gy))^2 <= 2 / 1.42^2 < 1), for
+ * every box size and wherever the frame clips it -- clipping removes pixels of the box, it moves
+ * neither the ellipse nor the pixels left -- so ("ellipse", g >= 42) hides at least what the
+ * default hides. At g = 41 corner pixels of larger boxes fall outside.
+ * Squares of side <= 3 are wholly inside their ellipse; a 4 x 4 box loses its four corners.
+ * Detection outputs, vd_read_boxes, vd_read_held, vd_hold outputs, hold matching and history work
+ * on the detections as stored: shaping happens after the hold merge and only on the list being
+ * blurred. The VD_ERR_CAPACITY / VD_ERR_ARG rules of the three blurring calls are unchanged.
+ * Launches (mask.hip): one grow launch per blurring call (timing family 3; merged rows of the
+ * lists' capacity) and, under VD_MASK_ELLIPSE, one restore launch after the rectangular pass
+ * (family 1) that copies in -> out the pixels of the clipped boxes outside every ellipse; for
+ * host frames it reads the staged input. */
+#define VD_MASK_RECT 0
+#define VD_MASK_ELLIPSE 1
+#define VD_MASK_GROW_MAX 200
+/* Unknown shape or grow_pct outside [0, VD_MASK_GROW_MAX]: VD_ERR_ARG (setting unchanged). Takes
+ * effect from the next blurring call. */
+int vd_mask(vd_ctx* ctx, int shape, int grow_pct);
+/* grow() of caller lists by the context's g, under the vd_boxes contract: out->count = in->count
+ * (complete counts, as given), out->xyxy = the grown boxes (min(count, in->cap, out->cap) per
+ * frame); xyxy_f, score and label are not written. in / out may be host or device, each on its
+ * own; a host `in` with count[f] > cap is VD_ERR_CAPACITY. The kernel of the blur path, so a
+ * caller can log or draw what was actually hidden. */
+int vd_mask_boxes(vd_ctx* ctx, const vd_boxes* in, int n, vd_boxes* out);
+
 /* ---- instrumentation (bench / profiling) ---------------------------------- */
 /* When enabled, every launch of kernel family `fam` is bracketed by HIP events
  * on the context stream; vd_timing_read returns the summed duration (ms), the
  * launch count and the summed algorithmic work (FLOP or bytes) since the last
  * reset. Families: 0 = RetinaFace conv (implicit GEMM / streaming 1x1), 1 = mosaic
- * output pass (or the Gaussian blur's launches), 2 = letterbox, 3 = post (decode/NMS, box hold), 4 = other, 5 = YOLOv8n plate
+ * output pass (or the Gaussian blur's launches; the mask's restore pass, work 0: its bytes follow
+ * from the boxes), 2 = letterbox, 3 = post (decode/NMS, box hold,
+ * mask grow), 4 = other, 5 = YOLOv8n plate
  * conv, 6 = mosaic cell table (box prep + walked cell colours). */
 int vd_timing_enable(vd_ctx* ctx, int on);
 int vd_timing_reset(vd_ctx* ctx);

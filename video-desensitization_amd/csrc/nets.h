@@ -198,6 +198,10 @@ struct Ctx {
     void* hold_rows = nullptr; size_t hold_rows_bytes = 0;   // the last call's merged rows, ages, |B|, |D|
     HoldArgs hold_last{};                         // the last launch (merged-row pointers for the readers)
     int hold_n = 0;                               // frames of the last holding call
+    // mask shaping (mask.hip; vd_mask): nothing is allocated or launched while the setting is the default
+    int mask_shape = VD_MASK_RECT, mask_grow = 0;
+    void* mask_rows = nullptr; size_t mask_rows_bytes = 0;   // grown merged rows: [n][mcap][4], then counts [n]
+    MaskArgs mask_last{};                         // the last grow launch (row pointers for the restore pass)
     // JPEG frame decode (jpeg_host.cpp): pinned host staging, device copy, planes
     void* jpeg_host = nullptr; size_t jpeg_host_bytes = 0;
     void* jpeg_dev = nullptr; size_t jpeg_dev_bytes = 0;
@@ -278,6 +282,16 @@ struct Ctx {
                       const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int level);
     int launch_blur(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
                     const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int ksize, float sigma);
+    bool mask_on() const { return mask_shape != VD_MASK_RECT || mask_grow != 0; }
+    // lists 0 / 1 grown by mask_grow into mask_last's merged rows (zero_tail: entries past the count zeroed)
+    int launch_mask_grow(int n, const int* cnt0, const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1,
+                         int zero_tail = 0);
+    // VD_MASK_ELLIPSE: out <- in outside every ellipse of mask_last's rows, after the rectangular pass
+    int launch_mask_restore(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch);
+    // the rectangular pass of the blurring calls behind the mask setting: grow, blur / mosaic, restore
+    int launch_shaped(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
+                      const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, bool gaussian, int level,
+                      int ksize, float sigma);
     // B = D ++ H of n consecutive frames into hold_last's merged rows, and the history update
     int launch_hold(int n, int h, int w, const int* cnt0, const int* xy0, int cap0, const int* cnt1, const int* xy1,
                     int cap1);

@@ -996,6 +996,62 @@ int Ctx::launch_blur(const uint8_t* in, uint8_t* out, int n, int h, int w, size_
     return VD_OK;
 }
 
+// ---- mask shaping (mask.hip) ----
+// Merged rows of the lists grown by mask_grow; the row capacity is the lists' capacity, so the
+// scratch and the grid depend on n and the capacities only (the counts stay on the device).
+int Ctx::launch_mask_grow(int n, const int* cnt0, const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1,
+                          int zero_tail) {
+    const size_t mcap = std::max<size_t>((size_t)(cnt0 ? cap0 : 0) + (size_t)(cnt1 ? cap1 : 0), 1);
+    if (mcap > 0x7fffffffu) return vd_set_error(VD_ERR_ARG, "mask: list capacity too large");
+    const size_t nb = (size_t)n * mcap;
+    int rc = ensure_staging(&mask_rows, &mask_rows_bytes, nb * 16 + (size_t)n * 4 + 64);
+    if (rc) return rc;
+    MaskArgs a{};
+    a.n = n;
+    a.cnt0 = cnt0; a.xy0 = xy0; a.cap0 = cap0;
+    a.cnt1 = cnt1; a.xy1 = xy1; a.cap1 = cap1;
+    a.g = mask_grow; a.zero_tail = zero_tail;
+    a.m_xy = (int*)mask_rows; a.m_cnt = a.m_xy + nb * 4; a.mcap = (int)mcap;
+    t_begin(3, (double)nb * 16);                  // the rows' bytes: the counts are known to the device only
+    hipError_t e = vd_launch_mask_grow(a, stream);
+    t_end();
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "mask grow: %s", hipGetErrorString(e));
+    mask_last = a;
+    return VD_OK;
+}
+
+int Ctx::launch_mask_restore(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch) {
+    MaskArgs a = mask_last;
+    a.in = in; a.out = out; a.n = n; a.h = h; a.w = w; a.pitch = pitch;
+    // the bytes moved follow from the boxes (6 B per pixel of a clipped box outside every
+    // ellipse), which the host does not see: time and launches only
+    t_begin(1, 0);
+    hipError_t e = vd_launch_mask_restore(a, stream);
+    t_end();
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "mask restore: %s", hipGetErrorString(e));
+    return VD_OK;
+}
+
+// What the three blurring calls launch. Default mask: the rectangular pass alone, exactly as
+// before. Otherwise the lists are grown into one merged row per frame, the rectangular pass
+// runs on that row (its second list null), and the ellipse composite follows it.
+int Ctx::launch_shaped(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
+                       const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, bool gaussian, int level,
+                       int ksize, float sigma) {
+    const bool shaped = mask_on() && (cnt0 || cnt1);
+    if (shaped) {
+        int rc = launch_mask_grow(n, cnt0, xy0, cap0, cnt1, xy1, cap1);
+        if (rc) return rc;
+        cnt0 = mask_last.m_cnt; xy0 = mask_last.m_xy; cap0 = mask_last.mcap;
+        cnt1 = xy1 = nullptr; cap1 = 0;
+    }
+    int rc = gaussian ? launch_blur(in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, ksize, sigma)
+                      : launch_mosaic(in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, level);
+    if (rc) return rc;
+    if (shaped && mask_shape == VD_MASK_ELLIPSE) return launch_mask_restore(in, out, n, h, w, pitch);
+    return VD_OK;
+}
+
 // ---- box hold (hold.hip, hold_state.h) ----
 // History buffers of at least `hcap` boxes per slot; the valid slots of a smaller pair are
 // carried over (weights loaded, or a wider vd_hold list, after the first holding call).
@@ -1202,6 +1258,7 @@ int vd_destroy(vd_ctx* h) {
     if (ctx->mosaic_table) hipFree(ctx->mosaic_table);
     if (ctx->blur_table) hipFree(ctx->blur_table);
     if (ctx->hold_rows) hipFree(ctx->hold_rows);
+    if (ctx->mask_rows) hipFree(ctx->mask_rows);
     for (int* p : ctx->hold_hist)
         if (p) hipFree(p);
     if (ctx->jpeg_dev) hipFree(ctx->jpeg_dev);
@@ -1406,7 +1463,8 @@ int vd_mosaic(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw,
         cnt = dc;
         xy = dx;
     }
-    if ((rc = ctx->launch_mosaic(din, dout, n, fh, fw, pitch, cnt, xy, boxes->cap, nullptr, nullptr, 0, level)))
+    if ((rc = ctx->launch_shaped(din, dout, n, fh, fw, pitch, cnt, xy, boxes->cap, nullptr, nullptr, 0, false, level,
+                                 0, 0.f)))
         return rc;
     if (where == VD_HOST) {
         VD_CHECK_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -1462,7 +1520,8 @@ int vd_blur(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw, s
         cnt = dc;
         xy = dx;
     }
-    if ((rc = ctx->launch_blur(din, dout, n, fh, fw, pitch, cnt, xy, boxes->cap, nullptr, nullptr, 0, ksize, sigma)))
+    if ((rc = ctx->launch_shaped(din, dout, n, fh, fw, pitch, cnt, xy, boxes->cap, nullptr, nullptr, 0, true, 0,
+                                 ksize, sigma)))
         return rc;
     if (where == VD_HOST) {
         VD_CHECK_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -1585,10 +1644,10 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
             if (r) return r;
             dout = (uint8_t*)ctx->stage_out;
         }
-        int r = ctx->cfg.blur_mode == VD_BLUR_GAUSSIAN
-                    ? ctx->launch_blur(d, dout, n, fh, fw, pitch, c0, x0, k0, c1, x1, k1, ctx->cfg.blur_ksize,
-                                       ctx->cfg.blur_sigma)
-                    : ctx->launch_mosaic(d, dout, n, fh, fw, pitch, c0, x0, k0, c1, x1, k1, ctx->cfg.mosaic_level);
+        // mask shaping (vd_mask) acts here, after the hold merge, on the list being blurred only
+        int r = ctx->launch_shaped(d, dout, n, fh, fw, pitch, c0, x0, k0, c1, x1, k1,
+                                   ctx->cfg.blur_mode == VD_BLUR_GAUSSIAN, ctx->cfg.mosaic_level,
+                                   ctx->cfg.blur_ksize, ctx->cfg.blur_sigma);
         if (r) return r;
         if (where == VD_HOST) VD_CHECK_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
         return VD_OK;
@@ -1685,6 +1744,54 @@ int vd_hold_motion(vd_ctx* h, int mode) {
         return VD_OK;
     }
     return ctx->hold_set_motion(mode);
+}
+
+int vd_mask(vd_ctx* h, int shape, int grow_pct) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (shape != VD_MASK_RECT && shape != VD_MASK_ELLIPSE)
+        return vd_set_error(VD_ERR_ARG, "vd_mask: shape %d (expected 0 = rect or 1 = ellipse)", shape);
+    if (grow_pct < 0 || grow_pct > VD_MASK_GROW_MAX)
+        return vd_set_error(VD_ERR_ARG, "vd_mask: grow_pct %d outside [0, %d]", grow_pct, VD_MASK_GROW_MAX);
+    ctx->mask_shape = shape;
+    ctx->mask_grow = grow_pct;
+    return VD_OK;
+}
+
+int vd_mask_boxes(vd_ctx* h, const vd_boxes* in, int n, vd_boxes* out) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (!in || !in->count || !in->xyxy || in->cap <= 0 || !out || !out->count || !out->xyxy || out->cap <= 0)
+        return vd_set_error(VD_ERR_ARG, "vd_mask_boxes: vd_boxes needs count, xyxy, cap>0");
+    if (n <= 0) return vd_set_error(VD_ERR_ARG, "vd_mask_boxes: n=%d", n);
+    const bool host = in->where == VD_HOST;
+    if (host)   // a count past cap means boxes the caller does not hold
+        for (int i = 0; i < n; ++i)
+            if (in->count[i] > in->cap)
+                return vd_set_error(VD_ERR_CAPACITY, "vd_mask_boxes: frame %d has count %d > cap %d", i,
+                                    in->count[i], in->cap);
+    const int* cnt = in->count;
+    const int* xy = in->xyxy;
+    int rc;
+    if (host) {
+        const size_t nb = (size_t)n * in->cap;
+        if ((rc = ctx->ensure_staging(&ctx->stage_box2, &ctx->stage_box2_bytes, n * 4 + nb * 16 + 16))) return rc;
+        int* dc = (int*)ctx->stage_box2;
+        int* dx = dc + ((n + 3) / 4) * 4;
+        VD_CHECK_HIP(hipMemcpyAsync(dc, in->count, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+        VD_CHECK_HIP(hipMemcpyAsync(dx, in->xyxy, nb * 16, hipMemcpyHostToDevice, ctx->stream));
+        cnt = dc;
+        xy = dx;
+    }
+    // the blur path's kernel; whole rows are copied out, so entries past the count are zeroed
+    if ((rc = ctx->launch_mask_grow(n, cnt, xy, in->cap, nullptr, nullptr, 0, 1))) return rc;
+    const hipMemcpyKind kind = out->where == VD_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const size_t wb = (size_t)std::min(in->cap, out->cap) * 16;
+    VD_CHECK_HIP(hipMemcpyAsync(out->count, cnt, (size_t)n * 4, kind, ctx->stream));   // complete counts, as given
+    VD_CHECK_HIP(hipMemcpy2DAsync(out->xyxy, (size_t)out->cap * 16, ctx->mask_last.m_xy, (size_t)in->cap * 16, wb, n,
+                                  kind, ctx->stream));
+    if (host || out->where == VD_HOST) VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // staging reused, host results
+    return VD_OK;
 }
 
 int vd_read_held(vd_ctx* h, int n, vd_boxes* out) {

@@ -449,7 +449,23 @@ hipError_t vd_launch_hold(const HoldArgs& a, hipStream_t s);
 hipError_t vd_launch_hold_gather(const HoldArgs& a, int n, int held_only, int* out_count, int* out_xyxy,
                                  int* out_label, int cap, hipStream_t s);
 
-#define VD_CHECK_HIP(expr)                                                     \
+// Mask shaping (mask.hip). Grow: lists 0 / 1 as the mosaic takes them (list 1 optional, scalar
+// reads: no alignment assumed) -> merged rows of grown boxes. Restore (VD_MASK_ELLIPSE, after the
+// rectangular pass on the same stream): pixels of the rows' clipped boxes outside every ellipse
+// are copied in -> out.
+struct MaskArgs {
+    const uint8_t* in; uint8_t* out; int n, h, w; size_t pitch;   // restore only
+    const int* cnt0; const int* xy0; int cap0;       // grow only: list 0 (faces)
+    const int* cnt1; const int* xy1; int cap1;       //   list 1 (plates, optional)
+    int g;                                           // grow percentage in [0, VD_MASK_GROW_MAX]
+    int zero_tail;                                   // grow: entries past the count are zeroed (vd_mask_boxes)
+    int* m_cnt; int* m_xy;                           // merged rows: counts [n], boxes [n][mcap][4], 16-B aligned
+    int mcap;                                        // row capacity >= cap0 + cap1
+};
+hipError_t vd_launch_mask_grow(const MaskArgs& a, hipStream_t s);
+hipError_t vd_launch_mask_restore(const MaskArgs& a, hipStream_t s);
+
+#define VD_CHECK_HIP(expr)                                                   \
     do {                                                                       \
         hipError_t _e = (expr);                                                \
         if (_e != hipSuccess) {                                                \

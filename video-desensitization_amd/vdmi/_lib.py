@@ -23,6 +23,9 @@ VD_BLUR_PIXELATE, VD_BLUR_GAUSSIAN = 0, 1
 VD_BLUR_KSIZE_MAX = 127
 VD_HOLD_MAX = 8
 VD_HOLD_MOTION_OFF, VD_HOLD_MOTION_LINEAR = 0, 1
+VD_MASK_RECT, VD_MASK_ELLIPSE = 0, 1
+VD_MASK_GROW_MAX = 200
+MASK_SHAPES = {"rect": VD_MASK_RECT, "ellipse": VD_MASK_ELLIPSE}
 VD_PROC_FACES, VD_PROC_PLATES, VD_PROC_MOSAIC, VD_PROC_MOSAIC_PLATES = 1, 2, 4, 8
 FAM_CONV, FAM_MOSAIC, FAM_LETTERBOX, FAM_POST, FAM_OTHER, FAM_PLATE_CONV, FAM_MOSAIC_CELLS = 0, 1, 2, 3, 4, 5, 6
 
@@ -88,6 +91,8 @@ SIGNATURES = [
     ("vd_hold_reset", _I, [_P]),
     ("vd_hold_motion", _I, [_P, _I]),
     ("vd_read_held", _I, [_P, _I, ctypes.POINTER(vd_boxes)]),
+    ("vd_mask", _I, [_P, _I, _I]),
+    ("vd_mask_boxes", _I, [_P, ctypes.POINTER(vd_boxes), _I, ctypes.POINTER(vd_boxes)]),
     ("vd_jpeg_decode", _I, [_P, ctypes.POINTER(_P), ctypes.POINTER(_SZ), _I, _P, _I, _I, _SZ, _I]),
     ("vd_jpeg_info", _I, [_P, _SZ, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     ("vd_jpeg_encode", _I, [_P, _P, _I, _I, _I, _SZ, _I, _I, _I, _P, _SZ, ctypes.POINTER(_SZ)]),
@@ -171,6 +176,17 @@ def check_hold(hold, hold_iou_pct, hold_motion=False):
     if hold_motion and not hold:
         raise ValueError("hold_motion moves held boxes: it needs hold > 0")
     return hold, pct
+
+
+def check_mask(mask, mask_grow):
+    """(shape name, grow percentage as int); ValueError for an unknown shape name or a grow
+    outside [0, VD_MASK_GROW_MAX]."""
+    if mask not in MASK_SHAPES:
+        raise ValueError(f"mask {mask!r}: expected 'rect' or 'ellipse'")
+    grow = int(mask_grow)
+    if not 0 <= grow <= VD_MASK_GROW_MAX:
+        raise ValueError(f"mask_grow {grow}: expected 0 .. {VD_MASK_GROW_MAX} percent")
+    return mask, grow
 
 
 def blur_weights(ksize, sigma=0.0):

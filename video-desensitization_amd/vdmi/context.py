@@ -102,7 +102,7 @@ class Context:
                  nms_iou=0.4, max_boxes=256, mosaic_level=8, plate_nc=1, plate_conf=0.5, plate_iou=0.7,
                  plate_max_det=300, plate_imgsz=640, microbatch=0, microbatch_stage=2, options=None,
                  blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30,
-                 hold_motion=False):
+                 hold_motion=False, mask="rect", mask_grow=0):
         """blur: what process() applies to the kept boxes: "pixelate" (the reference's
         INTER_NEAREST mosaic, the default) or "gaussian" (GaussianBlur(region, (blur_ksize,
         blur_ksize), blur_sigma) per clipped box, in list order; blur_ksize odd in [3, 127],
@@ -116,10 +116,17 @@ class Context:
         its last two sightings (vd_hold_motion's linear mode): the hull of the stored box and
         its extrapolation `age` frames on, so it also covers a face that keeps moving. Same
         membership, order and ages; frames of at most 32768 x 32768. Kept as self.hold_motion
-        (it is no vd_cfg field); set_hold_motion() changes it."""
+        (it is no vd_cfg field); set_hold_motion() changes it.
+        mask / mask_grow: mask shaping (include/vdmi.h at vd_mask) of every list the context
+        blurs (process(), mosaic(), blur()): each box grown by mask_grow percent (0..200; a side
+        becomes about 1 + mask_grow/100 times as long) and, with mask="ellipse", only the
+        ellipse inscribed in the grown box hidden (with mask_grow >= 42 that still covers every
+        pixel of the box as detected). The default ("rect", 0) blurs the detector's rectangle.
+        Kept as self.mask / self.mask_grow (no vd_cfg fields); set_mask() changes them."""
         if blur not in BLUR_MODES:
             raise ValueError(f"blur {blur!r}: expected 'pixelate' or 'gaussian'")
         hold, hold_iou_pct = _lib.check_hold(hold, hold_iou_pct, hold_motion)   # before the library is touched
+        mask, mask_grow = _lib.check_mask(mask, mask_grow)
         lib = _lib.load()
         cfg = _lib.default_cfg()
         cfg.input_h, cfg.input_w = int(input_shape[0]), int(input_shape[1])
@@ -155,6 +162,9 @@ class Context:
         self.hold_motion = False
         if hold_motion:
             self.set_hold_motion(True)
+        self.mask, self.mask_grow = "rect", 0
+        if (mask, mask_grow) != ("rect", 0):
+            self.set_mask(mask, mask_grow)
         for k, v in dict(options or {}).items():   # kernel-selection switches (vd_set_option)
             self.set_option(k, v)
 
@@ -401,6 +411,35 @@ class Context:
         s = boxes.struct()
         check(self._lib.vd_read_held(self._h, n, ctypes.byref(s)))
         return boxes
+
+    # -- mask shaping -----------------------------------------------------------
+    def set_mask(self, mask="rect", mask_grow=0):
+        """vd_mask: the shape ("rect" | "ellipse") and the margin (percent, 0..200) of what the
+        next blurring call hides; ("rect", 0) is the detector's rectangle."""
+        mask, mask_grow = _lib.check_mask(mask, mask_grow)
+        check(self._lib.vd_mask(self._h, _lib.MASK_SHAPES[mask], mask_grow))
+        self.mask, self.mask_grow = mask, mask_grow
+
+    def mask_boxes(self, boxes, out=None):
+        """vd_mask_boxes: the boxes as the context's blurring calls grow them (mask_grow; the
+        shape plays no part), by the kernel of the blur path. boxes: a HostBoxes / DeviceBoxes,
+        or a list with one int [k][4] array per frame. Returns `out` (default: host lists for
+        host boxes, a DeviceBoxes for device boxes, of the same cap): counts as given, xyxy
+        grown, nothing else written."""
+        if isinstance(boxes, (_lib.HostBoxes, DeviceBoxes)):
+            src = boxes
+        else:
+            lists = [np.asarray(b, np.int32).reshape(-1, 4) for b in boxes]
+            src = _lib.HostBoxes(len(lists), max(1, max((len(b) for b in lists), default=1)))
+            for i, b in enumerate(lists):
+                src.count[i] = len(b)
+                src.xyxy[i, :len(b)] = b
+        if out is None:
+            out = (DeviceBoxes(src.n, src.cap, src.xyxy.device) if isinstance(src, DeviceBoxes)
+                   else _lib.HostBoxes(src.n, src.cap))
+        ss, os_ = src.struct(), out.struct()
+        check(self._lib.vd_mask_boxes(self._h, ctypes.byref(ss), src.n, ctypes.byref(os_)))
+        return out
 
     # -- frame I/O ------------------------------------------------------------
     def jpeg_decode(self, jpegs, out=None):

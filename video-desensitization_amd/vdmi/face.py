@@ -99,6 +99,9 @@ class Retinaface(object):
         "hold": 0,
         "hold_iou_pct": 30,
         "hold_motion": False,
+        # mask shaping of what the fused vd_process blurs: Context(mask=..., mask_grow=...)
+        "mask": "rect",
+        "mask_grow": 0,
     }
 
     @classmethod
@@ -111,6 +114,7 @@ class Retinaface(object):
             setattr(self, name, value)
         if self.backbone not in ("resnet50", "mobilenet"):   # face.py:35: cfg_mnet / cfg_re50
             raise ValueError(f"backbone must be 'resnet50' or 'mobilenet', got {self.backbone!r}")
+        _lib.check_mask(self.mask, self.mask_grow)          # before a device or the library is touched
         if not self.letterbox_image:
             raise ValueError("Batch inference requires letterbox_image=True for shape alignment.")  # face.py:80
         if not self.cuda:
@@ -127,7 +131,8 @@ class Retinaface(object):
                              input_shape=self.input_shape[:2], confidence=self.confidence, nms_iou=self.nms_iou,
                              max_boxes=self.max_boxes, options=self.options, blur=self.blur,
                              blur_ksize=self.blur_ksize, blur_sigma=self.blur_sigma, hold=self.hold,
-                             hold_iou_pct=self.hold_iou_pct, hold_motion=self.hold_motion)
+                             hold_iou_pct=self.hold_iou_pct, hold_motion=self.hold_motion,
+                             mask=self.mask, mask_grow=self.mask_grow)
                      for d in self.device_ids]
         self.ctx = self.ctxs[0]
         self.generate()

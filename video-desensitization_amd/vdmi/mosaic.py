@@ -8,16 +8,18 @@ import numpy as np
 
 from .context import Context
 
-_ctx = None
+_ctxs = {}
 _ctx_lock = threading.Lock()
 
 
-def _default_ctx():
-    global _ctx
+def _default_ctx(mask="rect", mask_grow=0):
+    """One shared context per mask setting (the setting is a context's state, and the
+    callers are threads)."""
+    key = (mask, int(mask_grow))
     with _ctx_lock:
-        if _ctx is None:
-            _ctx = Context(max_batch=64)
-        return _ctx
+        if key not in _ctxs:
+            _ctxs[key] = Context(max_batch=64, mask=mask, mask_grow=mask_grow)
+        return _ctxs[key]
 
 
 def mosaic_rectangle_region_single(img, x1, y1, x2, y2, mosaic_level=8):
@@ -40,12 +42,14 @@ def _box_arrays(n, boxes):
     return xy, cnt
 
 
-def mosaic_frames(frames, boxes, mosaic_level=8, ctx=None):
+def mosaic_frames(frames, boxes, mosaic_level=8, ctx=None, mask="rect", mask_grow=0):
     """frames: uint8 [n,h,w,3]; boxes: list (per frame) of (x1,y1,x2,y2) int tuples.
-    Equivalent to applying mosaic_rectangle_region_single per box in order."""
+    Equivalent to applying mosaic_rectangle_region_single per box in order. mask /
+    mask_grow: the mask shaping (Context(mask=..., mask_grow=...)) of the shared context
+    used when no ctx is given; a given ctx applies its own."""
     frames = np.ascontiguousarray(frames, np.uint8)
     xy, cnt = _box_arrays(frames.shape[0], boxes)
-    return (ctx or _default_ctx()).mosaic(frames, xy, cnt, level=mosaic_level)
+    return (ctx or _default_ctx(mask, mask_grow)).mosaic(frames, xy, cnt, level=mosaic_level)
 
 
 def gaussian_blur_region_single(img, x1, y1, x2, y2, ksize=31, sigma=0.0):
@@ -58,9 +62,10 @@ def gaussian_blur_region_single(img, x1, y1, x2, y2, ksize=31, sigma=0.0):
     return _default_ctx().blur(a[None], box, np.ones(1, np.int32), ksize=ksize, sigma=sigma)[0]
 
 
-def blur_frames(frames, boxes, ksize=31, sigma=0.0, ctx=None):
+def blur_frames(frames, boxes, ksize=31, sigma=0.0, ctx=None, mask="rect", mask_grow=0):
     """frames: uint8 [n,h,w,3]; boxes: list (per frame) of (x1,y1,x2,y2) int tuples.
-    Equivalent to applying gaussian_blur_region_single per box in order."""
+    Equivalent to applying gaussian_blur_region_single per box in order; mask / mask_grow
+    as in mosaic_frames."""
     frames = np.ascontiguousarray(frames, np.uint8)
     xy, cnt = _box_arrays(frames.shape[0], boxes)
-    return (ctx or _default_ctx()).blur(frames, xy, cnt, ksize=ksize, sigma=sigma)
+    return (ctx or _default_ctx(mask, mask_grow)).blur(frames, xy, cnt, ksize=ksize, sigma=sigma)

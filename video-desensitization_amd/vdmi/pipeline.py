@@ -481,7 +481,9 @@ def fused_context(face_detector, plate_detector, batch_size, device=None, slot=0
     from .context import Context
     fd, pd = face_detector, plate_detector
     dev = fd.device_ids[0] if device is None else int(device)
-    key = (id(plate_detector), int(batch_size), dev, int(slot))
+    # the face detector's mask setting can change after it was built (Context.set_mask): a
+    # cached context with another mask is never reused
+    key = (id(plate_detector), int(batch_size), dev, int(slot), fd.ctx.mask, fd.ctx.mask_grow)
     with _FUSED_LOCK:
         cache = fd.__dict__.setdefault("_fused_ctx", {})
         if key in cache:
@@ -501,7 +503,7 @@ def _new_fused_context(fd, pd, batch_size, dev):
                   blur="gaussian" if fd.ctx.cfg.blur_mode == _lib.VD_BLUR_GAUSSIAN else "pixelate",
                   blur_ksize=fd.ctx.cfg.blur_ksize or 31, blur_sigma=fd.ctx.cfg.blur_sigma,
                   hold=fd.ctx.cfg.hold_frames, hold_iou_pct=fd.ctx.cfg.hold_iou_pct or 30,
-                  hold_motion=fd.ctx.hold_motion)
+                  hold_motion=fd.ctx.hold_motion, mask=fd.ctx.mask, mask_grow=fd.ctx.mask_grow)
     ctx.load_weights(_lib.VD_NET_RETINAFACE, fd.state_dict)
     ctx.load_weights(_lib.VD_NET_YOLOV8N, pd.state_dict)
     return ctx
@@ -522,6 +524,12 @@ def _hold_matches(ctx, hold, pct, motion=False):
     cfg = ctx.cfg
     return cfg.hold_frames == hold and (hold == 0 or (cfg.hold_iou_pct == pct
                                                      and bool(ctx.hold_motion) == bool(motion)))
+
+
+def _mask_matches(ctx, mask, mask_grow):
+    """The context's blurring calls shape their lists exactly so (no cfg fields: the Context
+    keeps the setting)."""
+    return (ctx.mask, ctx.mask_grow) == (mask, mask_grow)
 
 
 def _is_vdmi_pair(face_detector, plate_detector):
@@ -560,7 +568,7 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
                          loader=None, saver=None, mosaic_plates=False, mosaic_level=8, num_workers=6,
                          gpu_codec="auto", jpeg_quality=95, shard="auto", group=None, records=None,
                          blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30,
-                         hold_motion=False):
+                         hold_motion=False, mask="rect", mask_grow=0):
     """combine_detect.py:183-277. Returns (total_processed, total_faces, total_plates).
 
     gpu_codec ("auto" | True | False): with vdmi detectors, no custom loader/saver and
@@ -575,6 +583,12 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     context was built with the same blur settings (Retinaface(blur=..., blur_ksize=...,
     blur_sigma=...)); otherwise the detectors run on their own and the boxes are blurred
     by one launch per same-size group of frames.
+
+    mask ("rect" | "ellipse") / mask_grow (0..200 percent): mask shaping (include/vdmi.h at
+    vd_mask, Context(mask=..., mask_grow=...)): every blurred box is grown by the margin and,
+    with "ellipse", only the ellipse inscribed in the grown box is hidden. As with blur, the
+    one-call path needs a face detector built with the same settings (Retinaface(mask=...,
+    mask_grow=...)); otherwise the boxes are shaped and blurred by the per-group launches.
 
     hold (0..8) / hold_iou_pct (1..100): box hold (include/vdmi.h, Context(hold=...)): the
     frames are ONE video in the order of their sorted names, and a box stays blurred for up to
@@ -618,6 +632,7 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     loader = loader or load_image_rgb
     saver = saver or save_output_image
     hold, hold_iou_pct = _lib.check_hold(hold, hold_iou_pct, hold_motion)
+    mask, mask_grow = _lib.check_mask(mask, mask_grow)
     warm_frames = hold + 1 if hold_motion else hold      # the history's depth
     image_paths = [os.path.join(input_dir, f) for f in os.listdir(input_dir) if f.lower().endswith(IMAGE_EXT)]
     if hold:
@@ -627,10 +642,11 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
         raise ValueError(f"blur {blur!r}: expected 'pixelate' or 'gaussian'")
     fused = (_is_vdmi_pair(face_detector, plate_detector) and mosaic_level == face_detector.ctx.cfg.mosaic_level
              and _blur_matches(face_detector.ctx.cfg, blur, blur_ksize, blur_sigma)
-             and _hold_matches(face_detector.ctx, hold, hold_iou_pct, hold_motion))
+             and _hold_matches(face_detector.ctx, hold, hold_iou_pct, hold_motion)
+             and _mask_matches(face_detector.ctx, mask, mask_grow))
     if hold and not fused:
         raise ValueError("hold > 0 needs the vdmi Retinaface / YOLO drop-ins and a face detector built with the "
-                         "same mosaic_level, blur and hold settings (Retinaface(hold=..., hold_iou_pct=..., hold_motion=...)); "
+                         "same mosaic_level, blur, mask and hold settings (Retinaface(hold=..., hold_iou_pct=..., hold_motion=...)); "
                          "other detectors call Context.hold themselves")
     all_jpeg = all(p.lower().endswith((".jpg", ".jpeg")) for p in image_paths)
     codec = fused and gpu_codec and (gpu_codec is True or (not custom_io and all_jpeg))
@@ -639,7 +655,8 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
                batch_size=batch_size, loader=loader, saver=saver, mosaic_plates=mosaic_plates,
                mosaic_level=mosaic_level, num_workers=num_workers, fused=fused, codec=codec,
                jpeg_quality=jpeg_quality, logger=logger,
-               blur=(blur, int(blur_ksize), float(blur_sigma)), hold=hold, hold_warm=warm_frames)
+               blur=(blur, int(blur_ksize), float(blur_sigma)), hold=hold, hold_warm=warm_frames,
+               mask=(mask, mask_grow))
     want_rec = records is not None or mode == "ranks"
     if mode == "ranks":
         res, rec = _rank_shard(sorted(image_paths), group, run)
@@ -705,7 +722,7 @@ def _local(paths, first, device, want_rec, run, slot=0, warm=()):
         else:
             res = _threaded_batches(batches, run["output_dir"], fd, run["plate_detector"], run["loader"],
                                     run["saver"], run["mosaic_plates"], run["mosaic_level"], io, run["logger"],
-                                    sink, ids, run["blur"])
+                                    sink, ids, run["blur"], run["mask"])
     finally:
         io.shutdown(wait=True)
     if sink is not None and sink.device.type == "cuda":
@@ -924,7 +941,7 @@ def _gpu_codec_batches(batches, output_dir, face_detector, plate_detector, batch
 
 
 def _threaded_batches(batches, output_dir, face_detector, plate_detector, loader, saver, mosaic_plates,
-                      mosaic_level, io, logger, sink=None, ids=None, blur=("pixelate", 31, 0.0)):
+                      mosaic_level, io, logger, sink=None, ids=None, blur=("pixelate", 31, 0.0), mask=("rect", 0)):
     """Generic detectors: the reference's two-thread face || plate submission, then
     one batched mosaic launch per same-size group."""
     total = faces = plates = 0
@@ -957,7 +974,7 @@ def _threaded_batches(batches, output_dir, face_detector, plate_detector, loader
             plates += len(plate_boxes)
         if sink is not None:
             sink.add_lists([ids[f][0] for f in files], [ids[f][1] for f in files], fl, pl)
-        processed = _mosaic_grouped(batch_images, per_frame, mosaic_level, blur)
+        processed = _mosaic_grouped(batch_images, per_frame, mosaic_level, blur, mask)
         for path, img in zip(files, processed):
             out = os.path.join(output_dir, f"processed_{os.path.basename(path)}")
             save_futs.append(io.submit(saver, img, out))
@@ -966,7 +983,7 @@ def _threaded_batches(batches, output_dir, face_detector, plate_detector, loader
     return total, faces, plates
 
 
-def _mosaic_grouped(images, boxes, level, blur=("pixelate", 31, 0.0)):
+def _mosaic_grouped(images, boxes, level, blur=("pixelate", 31, 0.0), mask=("rect", 0)):
     """One mosaic (or Gaussian blur) launch per same-size group of frames."""
     out = [None] * len(images)
     groups = {}
@@ -974,9 +991,11 @@ def _mosaic_grouped(images, boxes, level, blur=("pixelate", 31, 0.0)):
         groups.setdefault(im.shape, []).append(i)
     for idx in groups.values():
         if blur[0] == "gaussian":
-            res = blur_frames(np.stack([images[i] for i in idx]), [boxes[i] for i in idx], blur[1], blur[2])
+            res = blur_frames(np.stack([images[i] for i in idx]), [boxes[i] for i in idx], blur[1], blur[2],
+                              mask=mask[0], mask_grow=mask[1])
         else:
-            res = mosaic_frames(np.stack([images[i] for i in idx]), [boxes[i] for i in idx], level)
+            res = mosaic_frames(np.stack([images[i] for i in idx]), [boxes[i] for i in idx], level,
+                                mask=mask[0], mask_grow=mask[1])
         for k, i in enumerate(idx):
             out[i] = res[k]
     return out
