@@ -463,6 +463,23 @@ __global__ __launch_bounds__(512, 1) void bottleneck32_kernel(Block32Args a) {
 // replace the workgroup barriers. Stage 2 sums each output's 18 k-steps in one
 // accumulator instead of two K halves (f32 rounding; tests/test_gpu_e2e.py,
 // test_gpu_kernels.py).
+//
+// Downsample variant (DS, option block32_pipe_ds, default 1; layer1.0, CIN = 64): the
+// same groups and counters, bit-identical to the one-group kernel:
+//   P: two k-steps (XS = 2, PRE = 1), otherwise as above;
+//   C: the two 32-channel K halves keep separate accumulators and are added at the end,
+//      hf = 0's sum plus hf = 1's, as the one-group kernel adds its LDS partials;
+//   Q: out = W3 . t2 + Wd . x. Wave jn reads x of output rows 2jn, 2jn + 1 (f32 from L2:
+//      P pulled the halo through two tiles earlier), splits it with the frame's scale and
+//      writes the pairs into a fourth LDS plane buffer (xs, laid out as t2), once per
+//      tile and before it waits for t2; then every Q wave reads the rows' t2 and xs
+//      fragments from LDS. W3 and Wd fragments per 32-channel group from L2, two
+//      accumulators, the downsample term formed and rounded as the one-group kernel's.
+//      The only global loads behind a tile's stores are the next tile's 8 x loads per
+//      lane and the two groups' weight fragments.
+//   Two more counters: xs ready (bumped by each Q wave after its two rows are written,
+//   every Q wave waits for 4 (j + 1)) and xs free (bumped after a wave's last xs read of
+//   tile j; a wave waits for 4 j before it writes tile j's rows).
 
 __device__ __forceinline__ int lds_load_flag(int* f) {
     return __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -479,7 +496,7 @@ __device__ __forceinline__ void post_flag(int* f, int lane) {
     asm volatile("" ::: "memory");
 }
 
-template <int CIN, int XS, int PRE>
+template <int CIN, int XS, int PRE, bool DS>
 __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
     constexpr int KS1 = CIN / 32;
     constexpr int W1PL = KS1 * 64 * 64;                   // one W1 plane
@@ -488,13 +505,27 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
     char* lw1 = smem;                                     // W1 planes (as the one-group kernel)
     char* lt1 = lw1 + 2 * W1PL;                           // t1 hi / lo planes (as the one-group kernel)
     char* lt2 = lt1 + 2 * T1PL;                           // t2 hi / lo planes
-    float* s_bn = (float*)(lt2 + 2 * T2PL);               // s1 h1 s2 h2 (64 each), s3 h3 (256 each)
-    int* s_flag = (int*)(s_bn + 768);                     // t1 ready, t1 free, t2 ready, t2 free, P max, C max
+    char* lxs = lt2 + 2 * T2PL;                           // DS: hi / lo planes of the tile's x (rows as t2)
+    constexpr int NBN = 256 + 512 * (DS ? 2 : 1);
+    float* s_bn = (float*)(lxs + (DS ? 2 * T2PL : 0));    // s1 h1 s2 h2 (64 each), s3 h3 (sd hd) (256 each)
+    int* s_flag = (int*)(s_bn + NBN);                     // t1 ready, t1 free, t2 ready, t2 free, P max, C max,
+                                                          // (DS) xs ready, xs free
     unsigned* s_t1max = (unsigned*)(s_flag + 8);          // [4] per-tile max |t1| (slot = tile & 3)
     unsigned* s_t2max = s_t1max + 4;                      // [4]
 
-    const int tid = threadIdx.x, lane = tid & 63, li0 = lane & 15, g0 = lane >> 4;
+    const int tid = threadIdx.x;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // a group's lane coordinates. DS: derived inside each group from an opaque copy of tid, so
+    // none of them is held across the other groups' code (the variant sits at the register
+    // limit of three waves per SIMD)
+    auto group_lanes = [&](int& lane, int& li0, int& g0, unsigned& lo16) {
+        int t = tid;
+        if constexpr (DS) asm volatile("" : "+v"(t));
+        lane = t & 63;
+        li0 = lane & 15;
+        g0 = lane >> 4;
+        lo16 = (unsigned)lane * 16u;
+    };
     const int tpf = a.tiles_x * a.tiles_y, T = a.B * tpf;
     const int G = gridDim.x, bid = blockIdx.x;
     int t0, tstep, tend;
@@ -513,7 +544,7 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
         const u32x4 v = *(const u32x4*)((const char*)a.w1 + ((size_t)(p * KS1 + ks) * 64 + row) * 64 + c * 16);
         *(u32x4*)(lw1 + p * W1PL + ks * 4096 + swz64(row, c)) = v;
     }
-    for (int i = tid; i < 768; i += 768) s_bn[i] = a.bn[i];
+    for (int i = tid; i < NBN; i += 768) s_bn[i] = a.bn[i];
     if (tid < 16) s_flag[tid] = 0;                        // counters and both max slot rings
     __syncthreads();
     const float* s1 = s_bn;
@@ -523,7 +554,8 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
     const float* s3 = s_bn + 256;
     const float* h3 = s_bn + 512;
     const size_t fpx = (size_t)a.H * a.W;
-    const unsigned lo16 = (unsigned)lane * 16u;
+    int lane, li0, g0;
+    unsigned lo16;
     auto frame_rsrc = [&](int b) {
         return __builtin_amdgcn_make_buffer_rsrc((void*)((const float*)a.x + (size_t)b * fpx * CIN), 0,
                                                  (int)(fpx * CIN * 4), 0x00020000);
@@ -538,6 +570,7 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
 
     if (w < 4) {
         // ================= producer: stage 1 of tile j =================
+        group_lanes(lane, li0, g0, lo16);
         // x of halo pixel tile 3w + i (lane: pixel 16 (3w + i) + li, channels 8g..), k-step s
         auto xoff = [&](int oy0, int ox0, int i, int li, int g) {
             const int r = 16 * (NP * w + i) + li;
@@ -665,6 +698,7 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
         }
     } else if (w < 8) {
         // ================= C: stage 2 of tile j =================
+        group_lanes(lane, li0, g0, lo16);
         const int jn = w - 4;
         const __amdgpu_buffer_rsrc_t rw2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.w2, 0, 0x7fffffff, 0x00020000);
         // W2 fragments of K half hf (9 taps x 2 planes), re-read per tile from L2 (all of W2
@@ -684,6 +718,7 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
         for (int j = 0; j < ntile; ++j) {
             int b, oy0, ox0;
             tile_of(j, b, oy0, ox0);
+            if constexpr (DS) group_lanes(lane, li0, g0, lo16);   // per tile: not held beside two accumulator sets
             u32x4 w2f[9][2];
             ldw2(0, 0, 9, w2f);
             wait_flag(s_flag + 0, 4 * (j + 1));            // t1 of tile j written
@@ -692,9 +727,13 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
             const float inv1 = __builtin_ldexpf(1.f, -k1);
             int li = li0, g = g0;
             asm volatile("" : "+v"(li), "+v"(g));
-            f32x4_t acc2[8];
+            // DS: one accumulator per K half (the one-group kernel's summation order)
+            constexpr int NA = DS ? 2 : 1;
+            f32x4_t acc2[NA][8];
 #pragma unroll
-            for (int m = 0; m < 8; ++m) acc2[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+            for (int k = 0; k < NA; ++k)
+#pragma unroll
+                for (int m = 0; m < 8; ++m) acc2[k][m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
             // step i = (K half hf = i / 30, window q = i % 30), one step ahead; a window (halo
             // row hh, shift dx) feeds the output rows m = hh - dy it touches
             u32x4 tr[2][2];                                // [buffer][plane]
@@ -722,7 +761,8 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
 #pragma unroll
                 for (int dy = 0; dy < 3; ++dy) {
                     const int m = hh - dy;
-                    if (m >= 0 && m < 8 && !(a.dbg & 2)) acc2[m] = mfma_pair(w2f[3 * dy + dx], tr[i & 1], acc2[m]);
+                    if (m >= 0 && m < 8 && !(a.dbg & 2))
+                        acc2[DS ? hf : 0][m] = mfma_pair(w2f[3 * dy + dx], tr[i & 1], acc2[DS ? hf : 0][m]);
                 }
             }
             // BN + ReLU (values stay in acc2 until the t2 buffer is free); tile max into its slot
@@ -734,9 +774,11 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
                 for (int m = 0; m < 8; ++m)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const float y = (acc2[m][e] * inv1) * scv[e] + shv[e];
-                        acc2[m][e] = y > 0.f ? y : 0.f;
-                        m2 = fmaxf(m2, acc2[m][e]);
+                        float sum = acc2[0][m][e];
+                        if constexpr (DS) sum = sum + acc2[1][m][e];
+                        const float y = (sum * inv1) * scv[e] + shv[e];
+                        acc2[0][m][e] = y > 0.f ? y : 0.f;
+                        m2 = fmaxf(m2, acc2[0][m][e]);
                     }
                 m2 = wave_max(m2);
                 if (lane == 0 && m2 > 0.f) atomicMax(s_t2max + (j & 3), __float_as_uint(m2));
@@ -746,7 +788,7 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
                 if (j >= 1) wait_flag(s_flag + 3, 4 * j);  // every consumer is done with the t2 planes
 #pragma unroll
                 for (int m = 0; m < 8; ++m) {
-                    const float v[4] = {acc2[m][0], acc2[m][1], acc2[m][2], acc2[m][3]};
+                    const float v[4] = {acc2[0][m][0], acc2[0][m][1], acc2[0][m][2], acc2[0][m][3]};
                     u32x2 hi, lo;
                     split_pair4_or(v, sa2, hi, lo);
                     const int off = swz128_any(16 * m + li, 2 * jn + (g >> 1)) + (g & 1) * 8;
@@ -756,12 +798,175 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
                 post_flag(s_flag + 2, lane);               // this wave's t2 channels written
             }
         }
+    } else if constexpr (DS) {
+        // ================= Q, downsample variant: stage 3 of tile j =================
+        // out = relu(bn3(W3 . t2) + bnd(Wd . x)); the wave owns output channels 64jn.. as two
+        // 32-channel groups (W3 / Wd fragments per group from L2). x of the tile's 128 pixels
+        // is split once: wave jn loads rows 2jn, 2jn + 1 and writes their pairs to the xs
+        // planes (counter barrier among the four Q waves), before it waits for t2
+        group_lanes(lane, li0, g0, lo16);
+        const int jn = w - 8;
+        const float* sd = s_bn + 768;
+        const float* hd = s_bn + 1024;
+        const __amdgpu_buffer_rsrc_t rw3 = __builtin_amdgcn_make_buffer_rsrc((void*)a.w3, 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rwd = __builtin_amdgcn_make_buffer_rsrc((void*)a.wd, 0, 0x7fffffff, 0x00020000);
+        int ob = -1;
+        float om = 0.f;
+#pragma unroll 1
+        for (int j = 0; j < ntile; ++j) {
+            int b, oy0, ox0;
+            tile_of(j, b, oy0, ox0);
+            const int kx = act_scale_exp_of(__uint_as_float(a.xmax[b]));   // this tile's frame (two behind P's)
+            const float sax = __builtin_ldexpf(1.f, kx), invx = __builtin_ldexpf(1.f, -kx);
+            const __amdgpu_buffer_rsrc_t rx = frame_rsrc(b);
+            const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
+                (void*)((float*)a.y + (size_t)b * fpx * CO), 0, (int)(fpx * CO * 4), 0x00020000);
+            // ---- x of output rows 2jn, 2jn + 1: channels 32 s + 8 g .. (2 k-steps x 2 x 16 B) ----
+            {
+                int li = li0, g = g0;
+                asm volatile("" : "+v"(li), "+v"(g));
+                const int ox = ox0 + li;
+                u32x4 xr[2][4];
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    const int oy = oy0 + 2 * jn + r;
+                    const unsigned o = (oy < a.H && ox < a.W && !(a.dbg & 16))
+                                           ? (unsigned)((oy * a.W + ox) * CIN + 8 * g) * 4u : 0x80000000u;
+#pragma unroll
+                    for (int s = 0; s < 2; ++s)
+#pragma unroll
+                        for (int q = 0; q < 2; ++q)
+                            xr[r][2 * s + q] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                rx, o, s * 128 + 16 * q, 0));
+                }
+                if (j >= 1) wait_flag(s_flag + 7, 4 * j);  // every Q wave is done with the xs planes
+#pragma unroll
+                for (int r = 0; r < 2; ++r)
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) {
+                        u32x4 px[2];
+                        split_pair8_or(xr[r][2 * s], xr[r][2 * s + 1], sax, px);
+                        const int off = swz128_any(16 * (2 * jn + r) + li, 4 * s + g);
+                        *(u32x4*)(lxs + off) = px[0];
+                        *(u32x4*)(lxs + T2PL + off) = px[1];
+                    }
+                post_flag(s_flag + 6, lane);               // this wave's two xs rows written
+            }
+            int k2 = 0;
+            float inv2 = 1.f;
+            float om_t = 0.f;
+#pragma unroll 1
+            for (int h = 0; h < 2; ++h) {
+                u32x4 w3f[2][2][2], wdf[2][2][2];          // [tile][k-step][plane]
+                {
+                    unsigned lo = lo16;
+                    asm volatile("" : "+v"(lo));
+#pragma unroll
+                    for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+                        for (int s = 0; s < 2; ++s)
+#pragma unroll
+                            for (int p = 0; p < 2; ++p) {
+                                const int so = (((((2 * jn + h) * 2 + jt) * 2 + s) * 2 + p) * 64) * 16;
+                                w3f[jt][s][p] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rw3, lo, so, 0));
+                                wdf[jt][s][p] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rwd, lo, so, 0));
+                            }
+                }
+                if (h == 0) {
+                    wait_flag(s_flag + 6, 4 * (j + 1));    // xs of tile j written by the four Q waves
+                    wait_flag(s_flag + 2, 4 * (j + 1));    // t2 of tile j written
+                    k2 = act_scale_exp_of(__uint_as_float(s_t2max[j & 3]));
+                    if (jn == 0 && lane == 0 && j >= 2) s_t2max[(j - 2) & 3] = 0u;   // read by every Q wave
+                    inv2 = __builtin_ldexpf(1.f, -k2);
+                }
+                const int cb0 = 64 * jn + 32 * h;
+                // lane coordinates opaque per group: the rows' LDS / store offsets are recomputed
+                // here, not held over both groups (registers)
+                int li = li0, g = g0;
+                asm volatile("" : "+v"(li), "+v"(g));
+                const int ox = ox0 + li;
+                // rows as a real loop: they are kept apart anyway (sched_barrier), and unrolled
+                // the eight rows' register assignments do not fit beside the 64 fragment registers
+#pragma unroll 1
+                for (int m = 0; m < 8; ++m) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    u32x4 tf[2][2], xf[2][2];
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) {
+                        const int off = swz128_any(16 * m + li, 4 * s + g);
+                        tf[s][0] = *(const u32x4*)(lt2 + off);
+                        tf[s][1] = *(const u32x4*)(lt2 + T2PL + off);
+                        xf[s][0] = *(const u32x4*)(lxs + off);
+                        xf[s][1] = *(const u32x4*)(lxs + T2PL + off);
+                    }
+                    f32x4_t acc[2] = {f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}};
+                    f32x4_t accd[2] = {f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}};
+                    if (!(a.dbg & 4)) {
+#pragma unroll
+                        for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+                            for (int s = 0; s < 2; ++s) acc[jt] = mfma_pair(w3f[jt][s], tf[s], acc[jt]);
+#pragma unroll
+                        for (int s = 0; s < 2; ++s)
+#pragma unroll
+                            for (int jt = 0; jt < 2; ++jt) accd[jt] = mfma_pair(wdf[jt][s], xf[s], accd[jt]);
+                    }
+                    int cb = cb0 + 8 * g;
+                    asm volatile("" : "+v"(cb));
+                    float v[8];
+                    {
+                        const float4 sa = *(const float4*)(s3 + cb), sb = *(const float4*)(s3 + cb + 4);
+                        const float4 ha = *(const float4*)(h3 + cb), hb = *(const float4*)(h3 + cb + 4);
+                        const float scv[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
+                        const float shv[8] = {ha.x, ha.y, ha.z, ha.w, hb.x, hb.y, hb.z, hb.w};
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) v[e] = (acc[e >> 2][e & 3] * inv2) * scv[e] + shv[e];
+                    }
+                    __builtin_amdgcn_sched_barrier(0);     // sd / hd are read once tf / xf are dead (registers)
+                    {   // + bn_d(downsample(x)), rounded to f32 first (as the one-group kernel)
+                        const float4 sa = *(const float4*)(sd + cb), sb = *(const float4*)(sd + cb + 4);
+                        const float4 ha = *(const float4*)(hd + cb), hb = *(const float4*)(hd + cb + 4);
+                        const float scv[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
+                        const float shv[8] = {ha.x, ha.y, ha.z, ha.w, hb.x, hb.y, hb.z, hb.w};
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) v[e] += (accd[e >> 2][e & 3] * invx) * scv[e] + shv[e];
+                    }
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        v[e] = v[e] > 0.f ? v[e] : 0.f;
+                        om_t = fmaxf(om_t, v[e]);
+                    }
+                    const int oy = oy0 + m;
+                    const unsigned so = (oy < a.H && ox < a.W && !(a.dbg & 8)) ? (unsigned)((oy * a.W + ox) * CO + cb) * 4u
+                                                                               : 0x80000000u;
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4_t{v[0], v[1], v[2], v[3]}),
+                                                           ry, so, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4_t{v[4], v[5], v[6], v[7]}),
+                                                           ry, so, 16, 0);
+                }
+                // t2 and xs read completely. Posted after the row loop, not inside its last
+                // row as the identity form does: a branch there costs this variant spills
+                if (h == 1) {
+                    post_flag(s_flag + 3, lane);
+                    post_flag(s_flag + 7, lane);
+                }
+            }
+            om_t = wave_max(om_t);
+            if (b != ob) {
+                if (ob >= 0 && lane == 0 && om > 0.f) atomicMax(a.ymax + ob, __float_as_uint(om));
+                ob = b;
+                om = 0.f;
+            }
+            om = fmaxf(om, om_t);
+        }
+        if (ob >= 0 && lane == 0 && om > 0.f) atomicMax(a.ymax + ob, __float_as_uint(om));
     } else {
         // ================= Q: stage 3 of tile j =================
         // the wave's 64 output channels as two 32-channel groups, one after the other (t2 read
         // once per group): W3 fragments of the group re-read per tile from L2, the identity of
         // all eight rows issued at the group's start (CDNA4's vmcnt retires loads and stores in
         // issue order: a load issued behind the stores of earlier rows would wait for them)
+        group_lanes(lane, li0, g0, lo16);
         const int jn = w - 8;
         const __amdgpu_buffer_rsrc_t rw3 = __builtin_amdgcn_make_buffer_rsrc((void*)a.w3, 0, 0x7fffffff, 0x00020000);
         int ob = -1;
@@ -866,11 +1071,13 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
     }
 }
 
-template <int CIN, int XS, int PRE>
+template <int CIN, int XS, int PRE, bool DS>
 hipError_t launch_pipe(const Block32Args& a, hipStream_t s) {
-    constexpr size_t lds = (size_t)2 * (CIN / 32) * 4096 + 2 * T1PL + 2 * T2PL + 768 * 4 + 16 * 4;
+    // W1, t1, t2 (DS: and xs) planes, BN tables (DS: with sd / hd), 8 counters + 2 x 4 max slots
+    constexpr size_t lds = (size_t)2 * (CIN / 32) * 4096 + 2 * T1PL + 2 * T2PL * (DS ? 2 : 1) +
+                           (256 + 512 * (DS ? 2 : 1)) * 4 + 16 * 4;
     static const int cus = [] {
-        (void)hipFuncSetAttribute((const void*)bottleneck32p_kernel<CIN, XS, PRE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute((const void*)bottleneck32p_kernel<CIN, XS, PRE, DS>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds);
         int dev = 0, n = 256;
         (void)hipGetDevice(&dev);
@@ -879,7 +1086,7 @@ hipError_t launch_pipe(const Block32Args& a, hipStream_t s) {
     }();
     const int tiles = a.B * a.tiles_x * a.tiles_y;
     const int grid = tiles < cus ? tiles : cus;
-    hipLaunchKernelGGL((bottleneck32p_kernel<CIN, XS, PRE>), dim3(grid), dim3(768), lds, s, a);
+    hipLaunchKernelGGL((bottleneck32p_kernel<CIN, XS, PRE, DS>), dim3(grid), dim3(768), lds, s, a);
     return hipGetLastError();
 }
 
@@ -911,14 +1118,17 @@ hipError_t vd_launch_block32(const Block32Args& a, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
     if (!a.xmax || !a.ymax) return hipErrorInvalidValue;
     if (a.cin == 256 && !a.ds) {
-        if (a.pipe == 4) return launch_pipe<256, 4, 2>(a, s);   // option block32_pipe: stage-1 x sets
-        if (a.pipe == 5) return launch_pipe<256, 5, 2>(a, s);
-        if (a.pipe == 6) return launch_pipe<256, 6, 3>(a, s);
-        if (a.pipe) return launch_pipe<256, 3, 1>(a, s);
+        if (a.pipe == 4) return launch_pipe<256, 4, 2, false>(a, s);   // option block32_pipe: stage-1 x sets
+        if (a.pipe == 5) return launch_pipe<256, 5, 2, false>(a, s);
+        if (a.pipe == 6) return launch_pipe<256, 6, 3, false>(a, s);
+        if (a.pipe) return launch_pipe<256, 3, 1, false>(a, s);
         if (a.xdepth == 3) return launch<256, false, 3>(a, s);
         if (a.xdepth == 4) return launch<256, false, 4>(a, s);
         return launch<256, false, 2>(a, s);
     }
-    if (a.cin == 64 && a.ds) return launch<64, true, 2>(a, s);
+    if (a.cin == 64 && a.ds) {
+        if (a.pipe_ds) return launch_pipe<64, 2, 1, true>(a, s);   // option block32_pipe_ds
+        return launch<64, true, 2>(a, s);
+    }
     return hipErrorInvalidValue;
 }

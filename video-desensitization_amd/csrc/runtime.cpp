@@ -1328,7 +1328,8 @@ int vd_set_option(vd_ctx* h, const char* name, int value) {
         {"mosaic_cells", &VdTune::mosaic_cells}, {"mosaic_fused", &VdTune::mosaic_fused},
         {"mosaic_rows", &VdTune::mosaic_rows}, {"mosaic_gather", &VdTune::mosaic_gather},
         {"block_fuse", &VdTune::block_fuse}, {"block_fuse32", &VdTune::block_fuse32},
-        {"block32_xd", &VdTune::block32_xd}, {"block32_pipe", &VdTune::block32_pipe}, {"chain", &VdTune::chain},
+        {"block32_xd", &VdTune::block32_xd}, {"block32_pipe", &VdTune::block32_pipe},
+        {"block32_pipe_ds", &VdTune::block32_pipe_ds}, {"chain", &VdTune::chain},
         {"chain_gpw", &VdTune::chain_gpw}, {"stem_pool", &VdTune::stem_pool}, {"ssh_fuse", &VdTune::ssh_fuse},
         {"ssh_side", &VdTune::ssh_side},
         {"plate_s2d", &VdTune::plate_s2d}, {"plate_s2d32", &VdTune::plate_s2d32},
