@@ -361,14 +361,68 @@ int vd_mask(vd_ctx* ctx, int shape, int grow_pct);
  * caller can log or draw what was actually hidden. */
 int vd_mask_boxes(vd_ctx* ctx, const vd_boxes* in, int n, vd_boxes* out);
 
+/* ---- tiled face detection: small faces in high-resolution frames -----------------
+ * Every frame is letterboxed onto the one input_h x input_w canvas (detect_face/face.py:77-78),
+ * so a 3840x2160 frame is shrunk 6x and a face 40 px wide reaches the net about 7 px wide, below
+ * its smallest anchor. A context has a tiling setting (R, C, O): R rows and C columns in [1, 4], O
+ * percent of overlap in [0, 50]. R*C == 1 (the default) is off: no extra launch, no extra memory,
+ * every output as before. Otherwise each h x w frame gives T = 1 + R*C net inputs -- input 0 the
+ * whole frame, input 1 + r*C + c tile (r, c) -- and all tiles have one size, so one letterbox
+ * geometry serves them. Integers, defined to the bit; per axis of length L cut into K tiles
+ * (h, R give th and y0; w, C give tw and x0; floor division throughout):
+ *   t   = min(L, (L*(100+O) + 100*K - 1) / (100*K))      the tile's extent
+ *   o_k = 0 if K == 1, else (k*(L - t)) / (K - 1)         the origin of tile k
+ * The first tile starts at 0, the last ends at L, origins never decrease, consecutive tiles leave
+ * no gap, and whenever t < L neighbours overlap by at least floor(L*O/(100*K)); on very small
+ * frames tiles may coincide (the merge removes the duplicates). 3840x2160 with (2, 2, 20): tiles
+ * of 2304x1296 at x 0, 1536 and y 0, 864.
+ * vd_detect and vd_process (VD_PROC_FACES) then:
+ *   capacity   n*T <= cfg.max_batch, else VD_ERR_ARG (the message names the largest n);
+ *   letterbox  one launch fills the n*T canvases, frame f's inputs at rows f*T .. f*T+T-1, canvas
+ *              f*T+t bit-identical to the letterbox of a frame holding exactly that rectangle;
+ *   net, post  unchanged over n*T inputs: the per-input keep lists are exactly what vd_detect
+ *              returns for each rectangle as a frame of its own;
+ *   merge      per frame (one launch, timing family 3): box i of input t moves by the tile's
+ *              origin, X = x + (float)x0_t and Y = y + (float)y0_t on both corners (one float32
+ *              add each, no FMA; input 0 unchanged); the boxes are ordered by descending score
+ *              (bit pattern), ties to the lower t, then to the lower position in that input's
+ *              list; greedy NMS over that order on the mapped boxes, the rule and the op order of
+ *              the per-input NMS (IoU in float32 against cfg.nms_iou as a double, area =
+ *              (x2 - x1) * (y2 - y1)); each kept box gives xyxy_f = the mapped box, xyxy = int()
+ *              of it, its score, and label = t*A + anchor (A = the net's anchor count, so
+ *              whole-frame boxes keep their labels). The merged rows hold T*A boxes per frame:
+ *              nothing is ever dropped.
+ * No border rule drops tile boxes near a tile edge: a face cut by a tile edge gives a partial box,
+ * which the merge suppresses or keeps beside the full one -- for an anonymiser covering more is
+ * harmless. The merged lists ARE the face detections of the call: the caller's `faces` (vd_boxes
+ * contract), vd_read_boxes(VD_NET_RETINAFACE), D_t of the box hold, and what the blur hides.
+ * Plates are detected on the whole frame as before (tiling the plate branch is out of scope), and
+ * the paired face+plate letterbox is not used while tiling is on. */
+#define VD_TILES_MAX 4
+/* The rectangles (x, y, w, h) of an h x w frame: xywh[0] the frame, xywh[1 + r*cols + c] tile
+ * (r, c); *count = 1 + rows*cols (either pointer may be NULL). Host only, no context, no GPU: the
+ * routine the launch path itself calls. VD_ERR_ARG outside the ranges above or for h, w <= 0. */
+int vd_tile_rects(int h, int w, int rows, int cols, int overlap_pct, int32_t* xywh, int* count);
+/* The context's tiling setting. Bad values: VD_ERR_ARG, setting unchanged. Takes effect from the
+ * next call; a change forgets the hold history as vd_hold_reset does (the merged rows change
+ * capacity); setting the value the context already has changes nothing. */
+int vd_tiles(vd_ctx* ctx, int rows, int cols, int overlap_pct);
+/* The merge step alone on caller lists, by the kernel of the detect path. lists: n*T rows, frame
+ * f's input t at row f*T+t, boxes relative to their rectangle of an h x w frame; xyxy_f and score
+ * are required, label is optional and read as 0, xyxy is not read; host or device; cap at most
+ * the net's anchor count. A host list with count > cap: VD_ERR_CAPACITY. out: n rows under the
+ * vd_boxes contract (may be NULL: vd_read_boxes hands the rows out). VD_ERR_STATE with tiling off
+ * or before the RetinaFace weights are loaded; n*T > cfg.max_batch: VD_ERR_ARG. */
+int vd_tiles_merge(vd_ctx* ctx, const vd_boxes* lists, int n, int h, int w, vd_boxes* out);
+
 /* ---- instrumentation (bench / profiling) ---------------------------------- */
 /* When enabled, every launch of kernel family `fam` is bracketed by HIP events
  * on the context stream; vd_timing_read returns the summed duration (ms), the
  * launch count and the summed algorithmic work (FLOP or bytes) since the last
  * reset. Families: 0 = RetinaFace conv (implicit GEMM / streaming 1x1), 1 = mosaic
  * output pass (or the Gaussian blur's launches; the mask's restore pass, work 0: its bytes follow
- * from the boxes), 2 = letterbox, 3 = post (decode/NMS, box hold,
- * mask grow), 4 = other, 5 = YOLOv8n plate
+ * from the boxes), 2 = letterbox (the tile letterbox too), 3 = post (decode/NMS, box hold,
+ * mask grow, tile merge), 4 = other, 5 = YOLOv8n plate
  * conv, 6 = mosaic cell table (box prep + walked cell colours). */
 int vd_timing_enable(vd_ctx* ctx, int on);
 int vd_timing_reset(vd_ctx* ctx);
@@ -378,6 +432,10 @@ int vd_timing_read(vd_ctx* ctx, int fam, double* ms, int64_t* launches, double* 
 /* Letterboxed RetinaFace input, NHWC with cpad channels (f32 regardless of precision). */
 int vdt_letterbox(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w, size_t pitch,
                   int where, float* out_nhwc, int cpad);
+/* vdt_letterbox for the n*T canvases of a tiling context (vd_tiles; VD_ERR_STATE when off), by
+ * the tile letterbox kernel of the detect path: out_nhwc [n*T][H][W][cpad], canvas f*T+t. */
+int vdt_letterbox_tiles(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w, size_t pitch,
+                        int where, float* out_nhwc, int cpad);
 /* Raw head outputs after the forward, host f32: loc [n][A][4], conf logits [n][A][2],
  * landm [n][A][10], A = number of anchors. */
 int vdt_forward_heads(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w, size_t pitch,

@@ -202,6 +202,27 @@ struct Ctx {
     int mask_shape = VD_MASK_RECT, mask_grow = 0;
     void* mask_rows = nullptr; size_t mask_rows_bytes = 0;   // grown merged rows: [n][mcap][4], then counts [n]
     MaskArgs mask_last{};                         // the last grow launch (row pointers for the restore pass)
+    // tiled face detection (tiles.hip, pre.hip letterbox_tiles_kernel; vd_tiles): nothing is allocated
+    // or launched while rows * cols == 1
+    int tile_rows = 1, tile_cols = 1, tile_overlap = 0;
+    void* tiles_buf = nullptr; size_t tiles_buf_bytes = 0;   // merged rows + spill scratch, floor(max_batch / T) frames
+    void* tiles_in = nullptr; size_t tiles_in_bytes = 0;     // vd_tiles_merge: host / unaligned caller lists staged
+    TileMergeArgs tiles_last{};                   // the last merge (merged-row pointers for the readers)
+    int tiles_kn = 0;                             // frames of the last merge
+    bool face_rows_merged = false;                // the last face call's lists are tiles_last's rows, not face.post's
+    bool tiles_on() const { return tile_rows * tile_cols > 1; }
+    int tiles_T() const { return 1 + tile_rows * tile_cols; }
+    int tiles_set(int rows, int cols, int overlap_pct);
+    int tiles_grid(int h, int w, TileGrid* g);    // the setting's rectangles of an h x w frame
+    int face_letterbox_tiles(const uint8_t* dframes, int n, int h, int w, size_t pitch, const TileGrid& g);
+    // the T lists of each of n frames (rows of icap, device) -> tiles_last's merged rows and the caller's targets
+    int tiles_merge(int n, const TileGrid& g, const int* cnt, const float* xyxy_f, const float* score, const int* label,
+                    int icap, const BoxTargets& t);
+    int tiles_check(int n, int h, int w, TileGrid* g);   // the grid, and n * T <= max_batch
+    // after face_forward(n * T): per-input post (sizes per input) + merge into the caller's targets
+    int face_post_tiled(int n, int h, int w, const TileGrid& g, const BoxTargets& t);
+    // the face lists a call leaves for the blur / the hold / vd_read_boxes: per-net keep lists or merged rows
+    int face_rows_cap() const { return tiles_on() ? tiles_T() * face.post.kcap : face.post.kcap; }
     // JPEG frame decode (jpeg_host.cpp): pinned host staging, device copy, planes
     void* jpeg_host = nullptr; size_t jpeg_host_bytes = 0;
     void* jpeg_dev = nullptr; size_t jpeg_dev_bytes = 0;
@@ -277,7 +298,8 @@ struct Ctx {
     int face_letterbox(const uint8_t* dframes, int n, int h, int w, size_t pitch);
     void face_letterbox_args(const uint8_t* dframes, int n, int h, int w, size_t pitch, LetterboxArgs* a);
     int face_forward(int n);
-    int face_post(int n, int img_h, int img_w, const BoxTargets& t);
+    // tiles: net input b is a tile of tiles->th x tiles->tw source pixels unless b % tiles->T == 0
+    int face_post(int n, int img_h, int img_w, const BoxTargets& t, const TileGrid* tiles = nullptr);
     int launch_mosaic(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
                       const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int level);
     int launch_blur(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,

@@ -28,11 +28,12 @@
 //    transform. Up to LDS_CAND candidates live in LDS, more in global scratch.
 #include "vd_common.h"
 #include "vd_math.h"
+#include "vd_nms.h"
 
 namespace {
 
-constexpr int NMS_THREADS = 1024;
-constexpr int LDS_CAND = 2048;
+constexpr int NMS_THREADS = VD_NMS_THREADS;
+constexpr int LDS_CAND = VD_NMS_LDS_CAND;
 
 __device__ __forceinline__ int level_of(const PostArgs& p, int a) {
     return a >= p.loff[2] ? 2 : (a >= p.loff[1] ? 1 : 0);
@@ -113,14 +114,7 @@ __global__ __launch_bounds__(256) void yolo_candidates_kernel(PostArgs p) {
     p.cand_keys[(size_t)b * p.A + pos] = ((uint64_t)(0xFFFFFFFFu - __float_as_uint(best)) << 32) | (uint32_t)a;
 }
 
-__device__ __forceinline__ int trunc_i32(float v) {
-    // int(x) of a Python float; values beyond int32 are clamped (the mosaic clips
-    // to the frame first, combine_detect.py:145-148, so the output is unchanged).
-    if (!(v == v)) return 0;
-    if (v >= 2147483520.0f) return 2147483647;
-    if (v <= -2147483648.0f) return (-2147483647 - 1);
-    return (int)v;   // truncation toward zero
-}
+__device__ __forceinline__ int trunc_i32(float v) { return vd_trunc_i32(v); }   // vd_nms.h
 
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
@@ -132,11 +126,16 @@ __device__ void emit(const PostArgs& p, int b, int pos, float4 bx, uint64_t key)
     const int a = (int)(key & 0xFFFFFFFFu);
     if (p.mode == POST_FACE) {
         // (box - offset) * scale, then * [w, h, w, h]  (utils_bbox.py:137, face.py:145)
-        const float iw = (float)p.img_w, ih = (float)p.img_h;
-        X1 = VD_FMUL(VD_FMUL(VD_FSUB(bx.x, p.offx), p.scx), iw);
-        Y1 = VD_FMUL(VD_FMUL(VD_FSUB(bx.y, p.offy), p.scy), ih);
-        X2 = VD_FMUL(VD_FMUL(VD_FSUB(bx.z, p.offx), p.scx), iw);
-        Y2 = VD_FMUL(VD_FMUL(VD_FSUB(bx.w, p.offy), p.scy), ih);
+        // tiled detection: net input b is a tile unless b % tile_T == 0, and the tiles share
+        // one source size with its own factors (the same host arithmetic on (th, tw))
+        const bool tl = p.tile_T > 0 && b % p.tile_T != 0;
+        const float iw = (float)(tl ? p.tile_w : p.img_w), ih = (float)(tl ? p.tile_h : p.img_h);
+        const float offx = tl ? p.tile_offx : p.offx, offy = tl ? p.tile_offy : p.offy;
+        const float scx = tl ? p.tile_scx : p.scx, scy = tl ? p.tile_scy : p.scy;
+        X1 = VD_FMUL(VD_FMUL(VD_FSUB(bx.x, offx), scx), iw);
+        Y1 = VD_FMUL(VD_FMUL(VD_FSUB(bx.y, offy), scy), ih);
+        X2 = VD_FMUL(VD_FMUL(VD_FSUB(bx.z, offx), scx), iw);
+        Y2 = VD_FMUL(VD_FMUL(VD_FSUB(bx.w, offy), scy), ih);
     } else {
         // scale_boxes: (box - pad) * (1/gain), clip to the source frame [ext]
         X1 = clampf(VD_FMUL(VD_FSUB(bx.x, (float)p.padx), p.inv_gain), 0.f, (float)p.img_w);
@@ -167,25 +166,13 @@ __device__ void emit(const PostArgs& p, int b, int pos, float4 bx, uint64_t key)
 
 __device__ void nms_frame(const PostArgs& p, int b, int M, uint64_t* keys, float4* box, float* area, uint8_t* supp,
                           uint64_t* chunk_keep, int* nkept_s) {
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = threadIdx.x;
     int P = 1;
     while (P < M) P <<= 1;
     const uint64_t* src = p.cand_keys + (size_t)b * p.A;
     for (int i = tid; i < P; i += NMS_THREADS) keys[i] = i < M ? src[i] : ~0ULL;
     __syncthreads();
-    for (int k = 2; k <= P; k <<= 1) {            // bitonic sort, ascending
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < P; i += NMS_THREADS) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const uint64_t ki = keys[i], kj = keys[ixj];
-                    const bool up = (i & k) == 0;
-                    if ((ki > kj) == up) { keys[i] = kj; keys[ixj] = ki; }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    vd_nms_sort(keys, P);                         // bitonic sort, ascending (vd_nms.h)
     for (int i = tid; i < M; i += NMS_THREADS) {
         const int a = (int)(keys[i] & 0xFFFFFFFFu);
         float4 bx = p.scratch_box[(size_t)b * p.A + a];
@@ -201,60 +188,9 @@ __device__ void nms_frame(const PostArgs& p, int b, int M, uint64_t* keys, float
     __syncthreads();
 
     const int limit = p.max_det > 0 ? min(p.max_det, p.kcap) : p.kcap;   // kcap >= every possible keep count
-    for (int c0 = 0; c0 < M; c0 += 64) {
-        if (wid == 0) {
-            const int j = c0 + lane;
-            const bool valid = j < M;
-            const float4 bj = valid ? box[j] : make_float4(0, 0, 0, 0);
-            const float aj = valid ? area[j] : 0.f;
-            const bool alive = valid && !supp[j];
-            uint64_t mask = 0;
-            const int lim = min(64, M - c0);
-            for (int k = lane + 1; k < lim; ++k) {
-                const float4 bk = box[c0 + k];
-                if (vd_iou_gt(bj.x, bj.y, bj.z, bj.w, aj, bk.x, bk.y, bk.z, bk.w, area[c0 + k], p.iou))
-                    mask |= 1ULL << k;
-            }
-            uint64_t alive_bits = __ballot(alive);
-            const uint32_t mlo = (uint32_t)mask, mhi = (uint32_t)(mask >> 32);
-            for (int i = 0; i < lim; ++i) {
-                if ((alive_bits >> i) & 1ULL) {
-                    const uint64_t mi = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)mhi, i) << 32) |
-                                        (uint32_t)__builtin_amdgcn_readlane((int)mlo, i);
-                    alive_bits &= ~mi;
-                }
-            }
-            const int base = *nkept_s;
-            if ((alive_bits >> lane) & 1ULL) {
-                const int pos = base + __popcll(alive_bits & ((1ULL << lane) - 1ULL));
-                if (pos < limit) emit(p, b, pos, p.mode == POST_FACE ? bj : p.scratch_box[(size_t)b * p.A + (int)(keys[j] & 0xFFFFFFFFu)], keys[j]);
-            }
-            if (lane == 0) {
-                *nkept_s = base + __popcll(alive_bits);
-                *chunk_keep = alive_bits;
-            }
-        }
-        __syncthreads();
-        const uint64_t kb = *chunk_keep;
-        if (kb) {
-            for (int j = c0 + 64 + tid; j < M; j += NMS_THREADS) {
-                if (supp[j]) continue;
-                const float4 bj = box[j];
-                const float aj = area[j];
-                uint64_t bits = kb;
-                while (bits) {
-                    const int i = __ffsll((long long)bits) - 1;
-                    bits &= bits - 1;
-                    const float4 bi = box[c0 + i];
-                    if (vd_iou_gt(bi.x, bi.y, bi.z, bi.w, area[c0 + i], bj.x, bj.y, bj.z, bj.w, aj, p.iou)) {
-                        supp[j] = 1;
-                        break;
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
+    vd_nms_greedy(M, box, area, supp, chunk_keep, nkept_s, p.iou, limit, [&](int pos, int j, const float4& bj) {
+        emit(p, b, pos, p.mode == POST_FACE ? bj : p.scratch_box[(size_t)b * p.A + (int)(keys[j] & 0xFFFFFFFFu)], keys[j]);
+    });
     if (tid == 0) {
         const int n = *nkept_s;
         const int kept = p.max_det > 0 ? min(n, p.max_det) : n;   // i = i[:max_det]

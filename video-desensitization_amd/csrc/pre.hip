@@ -104,13 +104,10 @@ __device__ __forceinline__ void store_s2d(const LetterboxArgs& a, size_t idx, co
 }
 
 // Space-to-depth form (a.s2d): one thread per 2x2 canvas block, 32 B out.
-__global__ __launch_bounds__(256) void letterbox_s2d_kernel(LetterboxArgs a) {
-    const int X = blockIdx.x * 256 + threadIdx.x;
-    const int Y = blockIdx.y;
-    const int f = blockIdx.z;
+// (img: the frame's pixels; f: the canvas index in a.out)
+__device__ __forceinline__ void lb_s2d_block(const LetterboxArgs& a, const uint8_t* img, int f, int Y, int X) {
     const int OW = a.ow / 2 + 1, OH = a.oh / 2 + 1;
     if (X >= OW) return;
-    const uint8_t* img = a.src + (size_t)f * a.ih * a.pitch;
     float t[16];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -121,6 +118,11 @@ __global__ __launch_bounds__(256) void letterbox_s2d_kernel(LetterboxArgs a) {
         t[4 * s + 3] = 0.f;
     }
     store_s2d(a, ((size_t)f * OH + Y) * OW + X, t);
+}
+
+__global__ __launch_bounds__(256) void letterbox_s2d_kernel(LetterboxArgs a) {
+    const int f = blockIdx.z;
+    lb_s2d_block(a, a.src + (size_t)f * a.ih * a.pitch, f, blockIdx.y, blockIdx.x * 256 + threadIdx.x);
 }
 
 // Space-to-depth form with the source rows staged in LDS: one workgroup per
@@ -181,11 +183,9 @@ __device__ __forceinline__ void lb_px_lds(const LetterboxArgs& a, const uint8_t*
     }
 }
 
-__global__ __launch_bounds__(256) void letterbox_s2d_lds_kernel(LetterboxArgs a) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t lrow[];   // 4 staged rows of RS bytes
-    const int Y = blockIdx.x, f = blockIdx.y;
+// block row Y of canvas f from the frame at img; lrow: 4 staged rows of RS bytes
+__device__ __forceinline__ void lb_s2d_lds_row(const LetterboxArgs& a, const uint8_t* img, int f, int Y, uint8_t* lrow) {
     const int OW = a.ow / 2 + 1, OH = a.oh / 2 + 1;
-    const uint8_t* img = a.src + (size_t)f * a.ih * a.pitch;
     int rows[4];
     Tap ty[2];
     bool rin[2];
@@ -224,6 +224,12 @@ __global__ __launch_bounds__(256) void letterbox_s2d_lds_kernel(LetterboxArgs a)
         }
         store_s2d(a, ((size_t)f * OH + Y) * OW + X, t);
     }
+}
+
+__global__ __launch_bounds__(256) void letterbox_s2d_lds_kernel(LetterboxArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lrow[];   // 4 staged rows of RS bytes
+    const int f = blockIdx.y;
+    lb_s2d_lds_row(a, a.src + (size_t)f * a.ih * a.pitch, f, blockIdx.x, lrow);
 }
 
 // Two space-to-depth canvases of the same frames in one pass (the face and the
@@ -296,12 +302,8 @@ __global__ __launch_bounds__(256) void letterbox_s2d_pair_kernel(LetterboxArgs a
     }
 }
 
-__global__ __launch_bounds__(256) void letterbox_kernel(LetterboxArgs a) {
-    const int x = blockIdx.x * 256 + threadIdx.x;
-    const int y = blockIdx.y;
-    const int f = blockIdx.z;
+__device__ __forceinline__ void lb_nhwc_px(const LetterboxArgs& a, const uint8_t* img, int f, int y, int x) {
     if (x >= a.ow) return;
-    const uint8_t* img = a.src + (size_t)f * a.ih * a.pitch;
     float v[3];
     canvas_px(a, img, y, x, v);
     const size_t o = (((size_t)f * a.oh + y) * a.ow + x) * a.cpad;
@@ -324,6 +326,34 @@ __global__ __launch_bounds__(256) void letterbox_kernel(LetterboxArgs a) {
         for (int c = 3; c < 8; ++c) tmp[c] = (__bf16)0.f;
         *(uint4*)out = *(const uint4*)tmp;
         for (int c = 8; c < a.cpad; c += 8) *(uint4*)(out + c) = make_uint4(0, 0, 0, 0);
+    }
+}
+
+__global__ __launch_bounds__(256) void letterbox_kernel(LetterboxArgs a) {
+    const int f = blockIdx.z;
+    lb_nhwc_px(a, a.src + (size_t)f * a.ih * a.pitch, f, blockIdx.y, blockIdx.x * 256 + threadIdx.x);
+}
+
+// Tiled detection (tiles.hip, include/vdmi.h at vd_tiles): the n * T canvases of n frames in one
+// launch, the net input on grid axis y. Input i = f * T + t is frame f's rectangle t -- the
+// whole frame (t = 0, geometry w) or a tile (geometry tl, all tiles one size) -- read in place
+// at the frame's pitch: a rectangle of a pitched frame IS a pitched frame, so each canvas goes
+// through the very device functions of the three kernels above and is bit-identical to what
+// they write for a standalone frame holding those pixels. Grid axis x: the canvas's block rows
+// (space-to-depth) or rows; a workgroup walks its row 256 pixels at a time, so the source rows
+// are read along the row (staged in LDS with 16-B loads where the row start is aligned).
+__global__ __launch_bounds__(256) void letterbox_tiles_kernel(LetterboxArgs w, LetterboxArgs tl, TileGrid g) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lrow[];
+    const int i = blockIdx.y, f = i / g.T, t = i - f * g.T;
+    const LetterboxArgs& a = t ? tl : w;
+    const uint8_t* img = w.src + ((size_t)f * w.ih + g.y0[t]) * w.pitch + (size_t)g.x0[t] * 3;
+    const int Y = blockIdx.x;
+    if (a.s2d && a.iw * 3 <= LB_LDS_MAX) {
+        lb_s2d_lds_row(a, img, i, Y, lrow);
+    } else if (a.s2d) {
+        for (int X = threadIdx.x; X < a.ow / 2 + 1; X += 256) lb_s2d_block(a, img, i, Y, X);
+    } else {
+        for (int x = threadIdx.x; x < a.ow; x += 256) lb_nhwc_px(a, img, i, Y, x);
     }
 }
 
@@ -462,6 +492,32 @@ hipError_t vd_launch_letterbox(const LetterboxArgs& a0, hipStream_t s) {
     }
     dim3 grid((a.ow + 255) / 256, a.oh, a.n);
     hipLaunchKernelGGL(letterbox_kernel, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t vd_launch_letterbox_tiles(const LetterboxArgs& w0, const LetterboxArgs& t0, const TileGrid& g,
+                                     hipStream_t s) {
+    LetterboxArgs w = w0, t = t0;
+    if (g.T < 2 || g.T > VD_TILE_INPUTS_MAX || w.n <= 0 || w.s2d != t.s2d || w.oh != t.oh || w.ow != t.ow ||
+        t.ih != g.th || t.iw != g.tw)
+        return hipErrorInvalidValue;
+    for (int k = 0; k < g.T; ++k)   // every rectangle inside the frame
+        if (g.x0[k] < 0 || g.y0[k] < 0 || g.x0[k] + (k ? g.tw : w.iw) > w.iw || g.y0[k] + (k ? g.th : w.ih) > w.ih)
+            return hipErrorInvalidValue;
+    lb_set_gather(w);
+    lb_set_gather(t);
+    static const bool attr = [] {
+        (void)hipFuncSetAttribute((const void*)letterbox_tiles_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  4 * LB_LDS_MAX);
+        return true;
+    }();
+    (void)attr;
+    size_t lds = 0;
+    if (w.s2d)
+        for (const LetterboxArgs* a : {&w, &t})
+            if (a->iw * 3 <= LB_LDS_MAX) lds = std::max(lds, 4 * (size_t)((a->iw * 3 + 15) / 16 * 16));
+    const dim3 grid(w.s2d ? w.oh / 2 + 1 : w.oh, w.n * g.T);
+    hipLaunchKernelGGL(letterbox_tiles_kernel, grid, dim3(256), lds, s, w, t, g);
     return hipGetLastError();
 }
 

@@ -911,7 +911,8 @@ int Ctx::face_forward(int n) {
     return run_net(face.net, n, mb, split);
 }
 
-int Ctx::face_post(int n, int img_h, int img_w, const BoxTargets& t) {
+int Ctx::face_post(int n, int img_h, int img_w, const BoxTargets& t, const TileGrid* tiles) {
+    face_rows_merged = false;
     PostArgs p{};
     p.mode = POST_FACE;
     for (int l = 0; l < 3; ++l) {
@@ -937,6 +938,17 @@ int Ctx::face_post(int n, int img_h, int img_w, const BoxTargets& t) {
     p.offx = ((inw - nw) / 2.0f) / inw;
     p.scy = inh / nh;
     p.scx = inw / nw;
+    if (tiles) {   // the same factors for a tile as a frame of its own
+        const float th = (float)tiles->th, tw = (float)tiles->tw;
+        const float trh = inh / th, trw = inw / tw;
+        const float tmn = trh < trw ? trh : trw;
+        const float tnh = th * tmn, tnw = tw * tmn;
+        p.tile_T = tiles->T; p.tile_h = tiles->th; p.tile_w = tiles->tw;
+        p.tile_offy = ((inh - tnh) / 2.0f) / inh;
+        p.tile_offx = ((inw - tnw) / 2.0f) / inw;
+        p.tile_scy = inh / tnh;
+        p.tile_scx = inw / tnw;
+    }
     p.cap = t.cap; p.out_count = t.count; p.out_xyxy = t.xyxy; p.out_xyxy_f = t.xyxy_f;
     p.out_score = t.score; p.out_label = t.label;
     vd_post_keep_args(face.post, p, n);
@@ -945,6 +957,101 @@ int Ctx::face_post(int n, int img_h, int img_w, const BoxTargets& t) {
     t_end();
     if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "face post: %s", hipGetErrorString(e));
     return VD_OK;
+}
+
+// ---- tiled face detection (tiles.hip, pre.hip letterbox_tiles_kernel) ----
+int Ctx::tiles_set(int rows, int cols, int overlap_pct) {
+    if (rows < 1 || rows > VD_TILES_MAX || cols < 1 || cols > VD_TILES_MAX || overlap_pct < 0 || overlap_pct > 50)
+        return vd_set_error(VD_ERR_ARG, "vd_tiles: rows, cols in [1, %d] and overlap_pct in [0, 50] required (got %d, "
+                            "%d, %d)", VD_TILES_MAX, rows, cols, overlap_pct);
+    if (rows == tile_rows && cols == tile_cols && overlap_pct == tile_overlap) return VD_OK;
+    VD_CHECK_HIP(hipStreamSynchronize(stream));   // a queued launch may still read the merged rows
+    tile_rows = rows; tile_cols = cols; tile_overlap = overlap_pct;
+    tiles_kn = 0;
+    face_rows_merged = false;
+    hold.reset();                                 // the merged rows change capacity: a new stream
+    return VD_OK;
+}
+
+int Ctx::tiles_grid(int h, int w, TileGrid* g) {
+    int32_t r[VD_TILE_INPUTS_MAX][4];
+    int cnt = 0;
+    if (vd_tile_rects_host(h, w, tile_rows, tile_cols, tile_overlap, &r[0][0], &cnt))
+        return vd_set_error(VD_ERR_ARG, "tiles: bad frame geometry %dx%d", w, h);
+    *g = TileGrid{};
+    g->T = cnt; g->tw = r[1][2]; g->th = r[1][3];
+    for (int k = 0; k < cnt; ++k) { g->x0[k] = r[k][0]; g->y0[k] = r[k][1]; }
+    return VD_OK;
+}
+
+int Ctx::face_letterbox_tiles(const uint8_t* dframes, int n, int h, int w, size_t pitch, const TileGrid& g) {
+    LetterboxArgs wa, ta;
+    face_letterbox_args(dframes, n, h, w, pitch, &wa);
+    face_letterbox_args(dframes, n, g.th, g.tw, pitch, &ta);
+    const double canvas = (double)wa.oh * wa.ow * wa.cpad * (f32 ? 4 : 2);
+    t_begin(2, (double)n * (wa.nh * (double)w * 3 + (g.T - 1) * (ta.nh * (double)g.tw * 3) + g.T * canvas));
+    hipError_t e = vd_launch_letterbox_tiles(wa, ta, g, stream);
+    t_end();
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "tile letterbox: %s", hipGetErrorString(e));
+    return VD_OK;
+}
+
+// Merged rows and spill scratch for the floor(max_batch / T) frames a call can carry: T * kcap
+// boxes per frame, so the bytes do not grow with T (the sort keys alone round up to a power of two).
+int Ctx::tiles_merge(int n, const TileGrid& g, const int* cnt, const float* xyxy_f, const float* score, const int* label,
+                     int icap, const BoxTargets& t) {
+    const size_t F = std::max(cfg.max_batch / g.T, 1);
+    const size_t mcap = (size_t)g.T * face.post.kcap;
+    if ((size_t)n > F || icap > face.post.kcap || mcap > 0x3fffffffu)
+        return vd_set_error(VD_ERR_ARG, "tiles merge: n=%d frames of lists of cap %d outside [1, %zu] x [1, %d]", n, icap,
+                            F, face.post.kcap);
+    size_t sort_cap = 1;
+    while (sort_cap < mcap) sort_cap <<= 1;
+    const size_t rows = F * mcap;
+    const size_t need = rows * (16 + 16 + 16 + 4 + 4 + 4 + 1) + F * sort_cap * 8 + F * 4 + 256;
+    int rc = ensure_staging(&tiles_buf, &tiles_buf_bytes, need);
+    if (rc) return rc;
+    TileMergeArgs a{};
+    a.n = n; a.g = g; a.A = face.A; a.iou = cfg.nms_iou;
+    a.cnt = cnt; a.xyxy_f = xyxy_f; a.score = score; a.label = label; a.icap = icap;
+    char* p = (char*)tiles_buf;
+    a.m_xyxy = (int*)p; p += rows * 16;
+    a.m_xyxy_f = (float*)p; p += rows * 16;
+    a.s_box = (float4*)p; p += rows * 16;
+    a.s_keys = (uint64_t*)p; p += F * sort_cap * 8;
+    a.m_score = (float*)p; p += rows * 4;
+    a.m_label = (int*)p; p += rows * 4;
+    a.s_area = (float*)p; p += rows * 4;
+    a.m_count = (int*)p; p += (F * 4 + 15) / 16 * 16;
+    a.s_supp = (uint8_t*)p;
+    a.sort_cap = (int)sort_cap; a.mcap = (int)mcap;
+    a.cap = t.cap; a.out_count = t.count; a.out_xyxy = t.xyxy; a.out_xyxy_f = t.xyxy_f;
+    a.out_score = t.score; a.out_label = t.label;
+    t_begin(3, (double)n * g.T * icap * 24);      // the lists' capacity: the counts are known to the device only
+    hipError_t e = vd_launch_tiles_merge(a, stream);
+    t_end();
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "tiles merge: %s", hipGetErrorString(e));
+    tiles_last = a;
+    tiles_kn = n;
+    face_rows_merged = true;
+    return VD_OK;
+}
+
+int Ctx::tiles_check(int n, int h, int w, TileGrid* g) {
+    int rc = tiles_grid(h, w, g);
+    if (rc) return rc;
+    if ((long long)n * g->T > cfg.max_batch)
+        return vd_set_error(VD_ERR_ARG, "tiles: n=%d frames x %d net inputs exceed max_batch=%d (largest n: %d)", n,
+                            g->T, cfg.max_batch, cfg.max_batch / g->T);
+    return VD_OK;
+}
+
+// after face_forward(n * T): the per-input keep lists (face.post, no caller copy), then their merge
+int Ctx::face_post_tiled(int n, int h, int w, const TileGrid& g, const BoxTargets& t) {
+    int rc = face_post(n * g.T, h, w, BoxTargets{}, &g);
+    if (rc) return rc;
+    const PostScratch& ps = face.post;
+    return tiles_merge(n, g, ps.kcount, ps.kxyxy_f, ps.kscore, ps.klabel, ps.kcap, t);
 }
 
 int Ctx::launch_mosaic(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
@@ -1104,7 +1211,7 @@ int Ctx::launch_hold(int n, int h, int w, const int* cnt0, const int* xy0, int c
         return vd_set_error(VD_ERR_ARG, "hold motion: frames of at most 32768 x 32768 (got %d x %d)", h, w);
     // rows sized for the loaded detectors' complete keep lists (vd_process never regrows them)
     // and for this call's lists; (K + 1) rows of that size hold D and K complete older lists
-    const int nets = (face.loaded ? face.post.kcap : 0) + (plate.loaded ? plate.post.kcap : 0);
+    const int nets = (face.loaded ? face_rows_cap() : 0) + (plate.loaded ? plate.post.kcap : 0);
     const int need = std::max(std::max((cnt0 ? cap0 : 0) + (cnt1 ? cap1 : 0), nets), 1);
     int rc = hold_history(need);
     if (rc) return rc;
@@ -1259,6 +1366,8 @@ int vd_destroy(vd_ctx* h) {
     if (ctx->blur_table) hipFree(ctx->blur_table);
     if (ctx->hold_rows) hipFree(ctx->hold_rows);
     if (ctx->mask_rows) hipFree(ctx->mask_rows);
+    if (ctx->tiles_buf) hipFree(ctx->tiles_buf);
+    if (ctx->tiles_in) hipFree(ctx->tiles_in);
     for (int* p : ctx->hold_hist)
         if (p) hipFree(p);
     if (ctx->jpeg_dev) hipFree(ctx->jpeg_dev);
@@ -1396,11 +1505,20 @@ int vd_detect(vd_ctx* h, const uint8_t* frames, int n, int fh, int fw, size_t pi
     if (!ctx->face.loaded) return vd_set_error(VD_ERR_STATE, "RetinaFace weights not loaded");
     int rc = ctx->check_frames(n, fh, fw, pitch);
     if (rc) return rc;
+    const bool tiled = ctx->tiles_on();
+    TileGrid g;
+    if (tiled && (rc = ctx->tiles_check(n, fh, fw, &g))) return rc;
     BoxTargets t;
     rc = ctx->box_targets(faces, n, t);
     if (rc) return rc;
     const uint8_t* d = ctx->frames_to_device(frames, n, fh, pitch, where, &rc);
     if (rc) return rc;
+    if (tiled) {   // T net inputs per frame, merged into one list (tiles.hip)
+        if ((rc = ctx->face_letterbox_tiles(d, n, fh, fw, pitch, g))) return rc;
+        if ((rc = ctx->face_forward(n * g.T))) return rc;
+        if ((rc = ctx->face_post_tiled(n, fh, fw, g, t))) return rc;
+        return ctx->box_finish(faces, n, t);
+    }
     if ((rc = ctx->face_letterbox(d, n, fh, fw, pitch))) return rc;
     if ((rc = ctx->face_forward(n))) return rc;
     if ((rc = ctx->face_post(n, fh, fw, t))) return rc;
@@ -1545,6 +1663,10 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
     if (do_mosaic && !out) return vd_set_error(VD_ERR_ARG, "MOSAIC needs an output buffer");
     int rc = ctx->check_frames(n, fh, fw, pitch);
     if (rc) return rc;
+    // tiled detection: T net inputs per frame through the face net, merged before anything reads them
+    const bool tiled = do_faces && ctx->tiles_on();
+    TileGrid tg;
+    if (tiled && (rc = ctx->tiles_check(n, fh, fw, &tg))) return rc;
     // the mosaic is out of place (combine_detect.py:142 blurs a copy; each box reads the
     // previous box's output, :247-249): its one-launch output pass gathers cell colours
     // from `in` anywhere in the frame while other workgroups write `out`, so device
@@ -1572,7 +1694,7 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
     // Both canvases from one read of the frames where the geometry allows (pre.hip
     // letterbox_s2d_pair_kernel); the plate branch then forks after it.
     bool paired = false;
-    if (fork) {
+    if (fork && !tiled) {   // tiling: the tile letterbox fills the face canvases, the plate branch its own
         LetterboxArgs fa, pa;
         ctx->face_letterbox_args(d, n, fh, fw, pitch, &fa);
         if (ctx->tune.lb_pair && vd_plate_letterbox_args(*ctx, d, n, fh, fw, pitch, &pa) == VD_OK &&
@@ -1598,13 +1720,17 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
         VD_CHECK_HIP(hipStreamWaitEvent(plate_stream, ctx->ev_fork, 0));
     }
     if (do_faces) {
-        if (!paired && (rc = ctx->face_letterbox(d, n, fh, fw, pitch))) return rc;
-        if ((rc = ctx->face_forward(n))) return rc;
+        if (tiled) {
+            if ((rc = ctx->face_letterbox_tiles(d, n, fh, fw, pitch, tg))) return rc;
+        } else if (!paired && (rc = ctx->face_letterbox(d, n, fh, fw, pitch))) {
+            return rc;
+        }
+        if ((rc = ctx->face_forward(tiled ? n * tg.T : n))) return rc;
         if (ctx->fork_at > 0) {
             ctx->fork_at = -1;
             VD_CHECK_HIP(hipStreamWaitEvent(plate_stream, ctx->ev_fork, 0));
         }
-        if ((rc = ctx->face_post(n, fh, fw, tf))) return rc;
+        if ((rc = tiled ? ctx->face_post_tiled(n, fh, fw, tg, tf) : ctx->face_post(n, fh, fw, tf))) return rc;
     }
     if (do_plates) {
         hipStream_t main = ctx->stream;
@@ -1622,11 +1748,12 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
     // may hold fewer: cap), faces in NMS order then plates (combine_detect.py:241-249)
     const PostScratch& fp = ctx->face.post;
     const PostScratch& pp = ctx->plate.post;
-    const int* c0 = do_faces ? fp.kcount : nullptr;
-    const int* x0 = do_faces ? fp.kxyxy : nullptr;
+    const TileMergeArgs& tm = ctx->tiles_last;   // tiling: the merged rows are the face list
+    const int* c0 = do_faces ? (tiled ? tm.m_count : fp.kcount) : nullptr;
+    const int* x0 = do_faces ? (tiled ? tm.m_xyxy : fp.kxyxy) : nullptr;
     const int* c1 = mosaic_plates ? pp.kcount : nullptr;
     const int* x1 = mosaic_plates ? pp.kxyxy : nullptr;
-    int k0 = do_faces ? fp.kcap : 0, k1 = mosaic_plates ? pp.kcap : 0;
+    int k0 = do_faces ? (tiled ? tm.mcap : fp.kcap) : 0, k1 = mosaic_plates ? pp.kcap : 0;
     // box hold: the blur list becomes B = D ++ H in merged rows (one launch, after the lists
     // it reads are complete); the history is updated whether or not anything is blurred
     auto hold = [&]() -> int {
@@ -1676,18 +1803,27 @@ int vd_read_boxes(vd_ctx* h, int net, int n, vd_boxes* out) {
     if (!ps) return vd_set_error(VD_ERR_ARG, "unknown net %d", net);
     if (!ps->kcount) return vd_set_error(VD_ERR_STATE, "net %d not loaded", net);
     if (!out || !out->count || !out->xyxy || out->cap <= 0) return vd_set_error(VD_ERR_ARG, "vd_boxes needs count, xyxy, cap>0");
-    if (n <= 0 || n > ps->kn) return vd_set_error(VD_ERR_ARG, "n=%d outside [1, %d frames of the last call]", n, ps->kn);
+    // tiled detection: the face lists of the last call are the merged rows (tiles.hip)
+    const bool mg = net == VD_NET_RETINAFACE && ctx->face_rows_merged;
+    const TileMergeArgs& tm = ctx->tiles_last;
+    const int kn = mg ? ctx->tiles_kn : ps->kn, kcap = mg ? tm.mcap : ps->kcap;
+    const int* kcount = mg ? tm.m_count : ps->kcount;
+    const int* kxyxy = mg ? tm.m_xyxy : ps->kxyxy;
+    const float* kxyxy_f = mg ? tm.m_xyxy_f : ps->kxyxy_f;
+    const float* kscore = mg ? tm.m_score : ps->kscore;
+    const int* klabel = mg ? tm.m_label : ps->klabel;
+    if (n <= 0 || n > kn) return vd_set_error(VD_ERR_ARG, "n=%d outside [1, %d frames of the last call]", n, kn);
     const hipMemcpyKind kind = out->where == VD_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const int w = std::min(out->cap, ps->kcap);   // boxes per frame copied (beyond kcap nothing is ever kept)
-    const size_t dp = (size_t)out->cap, sp = (size_t)ps->kcap;
-    VD_CHECK_HIP(hipMemcpyAsync(out->count, ps->kcount, (size_t)n * 4, kind, ctx->stream));
-    VD_CHECK_HIP(hipMemcpy2DAsync(out->xyxy, dp * 16, ps->kxyxy, sp * 16, (size_t)w * 16, n, kind, ctx->stream));
+    const int w = std::min(out->cap, kcap);   // boxes per frame copied (beyond kcap nothing is ever kept)
+    const size_t dp = (size_t)out->cap, sp = (size_t)kcap;
+    VD_CHECK_HIP(hipMemcpyAsync(out->count, kcount, (size_t)n * 4, kind, ctx->stream));
+    VD_CHECK_HIP(hipMemcpy2DAsync(out->xyxy, dp * 16, kxyxy, sp * 16, (size_t)w * 16, n, kind, ctx->stream));
     if (out->xyxy_f)
-        VD_CHECK_HIP(hipMemcpy2DAsync(out->xyxy_f, dp * 16, ps->kxyxy_f, sp * 16, (size_t)w * 16, n, kind, ctx->stream));
+        VD_CHECK_HIP(hipMemcpy2DAsync(out->xyxy_f, dp * 16, kxyxy_f, sp * 16, (size_t)w * 16, n, kind, ctx->stream));
     if (out->score)
-        VD_CHECK_HIP(hipMemcpy2DAsync(out->score, dp * 4, ps->kscore, sp * 4, (size_t)w * 4, n, kind, ctx->stream));
+        VD_CHECK_HIP(hipMemcpy2DAsync(out->score, dp * 4, kscore, sp * 4, (size_t)w * 4, n, kind, ctx->stream));
     if (out->label)
-        VD_CHECK_HIP(hipMemcpy2DAsync(out->label, dp * 4, ps->klabel, sp * 4, (size_t)w * 4, n, kind, ctx->stream));
+        VD_CHECK_HIP(hipMemcpy2DAsync(out->label, dp * 4, klabel, sp * 4, (size_t)w * 4, n, kind, ctx->stream));
     if (out->where == VD_HOST) VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     return VD_OK;
 }
@@ -1801,6 +1937,68 @@ int vd_read_held(vd_ctx* h, int n, vd_boxes* out) {
     return ctx->hold_read(n, 1, out);
 }
 
+int vd_tile_rects(int fh, int fw, int rows, int cols, int overlap_pct, int32_t* xywh, int* count) {
+    if (vd_tile_rects_host(fh, fw, rows, cols, overlap_pct, xywh, count))
+        return vd_set_error(VD_ERR_ARG, "vd_tile_rects: h, w > 0, rows, cols in [1, %d] and overlap_pct in [0, 50] "
+                            "required (got %d x %d, %d, %d, %d)", VD_TILES_MAX, fw, fh, rows, cols, overlap_pct);
+    return VD_OK;
+}
+
+int vd_tiles(vd_ctx* h, int rows, int cols, int overlap_pct) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    return ctx->tiles_set(rows, cols, overlap_pct);
+}
+
+int vd_tiles_merge(vd_ctx* h, const vd_boxes* lists, int n, int fh, int fw, vd_boxes* out) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (!ctx->tiles_on()) return vd_set_error(VD_ERR_STATE, "vd_tiles_merge: tiling is off (vd_tiles)");
+    if (!ctx->face.loaded) return vd_set_error(VD_ERR_STATE, "vd_tiles_merge: RetinaFace weights not loaded");
+    if (!lists || !lists->count || !lists->xyxy_f || !lists->score || lists->cap <= 0)
+        return vd_set_error(VD_ERR_ARG, "vd_tiles_merge: lists need count, xyxy_f, score, cap>0");
+    if (n <= 0 || fh <= 0 || fw <= 0) return vd_set_error(VD_ERR_ARG, "vd_tiles_merge: bad geometry");
+    TileGrid g;
+    int rc = ctx->tiles_check(n, fh, fw, &g);
+    if (rc) return rc;
+    if (lists->cap > ctx->face.post.kcap)
+        return vd_set_error(VD_ERR_ARG, "vd_tiles_merge: lists of cap %d (at most the net's %d anchors)", lists->cap,
+                            ctx->face.post.kcap);
+    const int rows = n * g.T;
+    const bool host = lists->where == VD_HOST;
+    if (host)   // a count past cap means boxes the caller does not hold: never skip them silently
+        for (int i = 0; i < rows; ++i)
+            if (lists->count[i] > lists->cap)
+                return vd_set_error(VD_ERR_CAPACITY, "vd_tiles_merge: list %d has count %d > cap %d", i,
+                                    lists->count[i], lists->cap);
+    BoxTargets t;
+    if ((rc = ctx->box_targets(out, n, t))) return rc;
+    const int* cnt = lists->count;
+    const float* xf = lists->xyxy_f;
+    const float* sc = lists->score;
+    const int* lab = lists->label;
+    if (host) {
+        const size_t nb = (size_t)rows * lists->cap;
+        const size_t c16 = ((size_t)rows * 4 + 15) / 16 * 16;
+        if ((rc = ctx->ensure_staging(&ctx->tiles_in, &ctx->tiles_in_bytes, c16 + nb * 24))) return rc;
+        char* p = (char*)ctx->tiles_in;
+        int* dc = (int*)p; p += c16;
+        float* dx = (float*)p; p += nb * 16;
+        float* ds = (float*)p; p += nb * 4;
+        int* dl = (int*)p;
+        VD_CHECK_HIP(hipMemcpyAsync(dc, lists->count, (size_t)rows * 4, hipMemcpyHostToDevice, ctx->stream));
+        VD_CHECK_HIP(hipMemcpyAsync(dx, lists->xyxy_f, nb * 16, hipMemcpyHostToDevice, ctx->stream));
+        VD_CHECK_HIP(hipMemcpyAsync(ds, lists->score, nb * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (lab) VD_CHECK_HIP(hipMemcpyAsync(dl, lists->label, nb * 4, hipMemcpyHostToDevice, ctx->stream));
+        cnt = dc; xf = dx; sc = ds; lab = lab ? dl : nullptr;
+    }
+    if ((rc = ctx->tiles_merge(n, g, cnt, xf, sc, lab, lists->cap, t))) return rc;
+    if ((rc = ctx->box_finish(out, n, t))) return rc;
+    if (host && !(out && out->where == VD_HOST))
+        VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // staging reused by the next call
+    return VD_OK;
+}
+
 int vdt_blur_weights(int ksize, float sigma, uint32_t* q) {
     if (!q) return vd_set_error(VD_ERR_ARG, "vdt_blur_weights: null q");
     if (vd_blur_weights(ksize, sigma, q))
@@ -1846,6 +2044,24 @@ int vd_timing_read(vd_ctx* h, int fam, double* ms, int64_t* launches, double* wo
 }
 
 // ---- test hooks ----
+static int letterbox_readback(Ctx* ctx, int n, float* out, int cpad);
+
+int vdt_letterbox_tiles(vd_ctx* h, const uint8_t* frames, int n, int fh, int fw, size_t pitch, int where, float* out,
+                        int cpad) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (!ctx->face.loaded) return vd_set_error(VD_ERR_STATE, "RetinaFace weights not loaded");
+    if (!ctx->tiles_on()) return vd_set_error(VD_ERR_STATE, "vdt_letterbox_tiles: tiling is off (vd_tiles)");
+    int rc = ctx->check_frames(n, fh, fw, pitch);
+    if (rc) return rc;
+    TileGrid g;
+    if ((rc = ctx->tiles_check(n, fh, fw, &g))) return rc;
+    const uint8_t* d = ctx->frames_to_device(frames, n, fh, pitch, where, &rc);
+    if (rc) return rc;
+    if ((rc = ctx->face_letterbox_tiles(d, n, fh, fw, pitch, g))) return rc;
+    return letterbox_readback(ctx, n * g.T, out, cpad);
+}
+
 int vdt_letterbox(vd_ctx* h, const uint8_t* frames, int n, int fh, int fw, size_t pitch, int where, float* out,
                   int cpad) {
     Ctx* ctx = (Ctx*)h;
@@ -1856,6 +2072,11 @@ int vdt_letterbox(vd_ctx* h, const uint8_t* frames, int n, int fh, int fw, size_
     const uint8_t* d = ctx->frames_to_device(frames, n, fh, pitch, where, &rc);
     if (rc) return rc;
     if ((rc = ctx->face_letterbox(d, n, fh, fw, pitch))) return rc;
+    return letterbox_readback(ctx, n, out, cpad);
+}
+
+// the first n face canvases as host f32 [n][H][W][cpad], whatever form the plan keeps them in
+static int letterbox_readback(Ctx* ctx, int n, float* out, int cpad) {
     const Act& in = ctx->face.input;
     size_t px = (size_t)n * in.h * in.w;
     std::vector<uint16_t> hb;

@@ -263,6 +263,10 @@ struct PostArgs {
     int sort_cap;            // power of two >= A
     int img_h, img_w;        // source frame size (all frames of a call share it)
     float offx, offy, scx, scy;   // face correction (utils_bbox.py:118-132, float32)
+    // tiled face detection (tile_T = 1 + rows * cols > 1; 0: off): net input b is the whole frame
+    // when b % tile_T == 0, else a tile of tile_h x tile_w source pixels with its own factors
+    int tile_T, tile_h, tile_w;
+    float tile_offx, tile_offy, tile_scx, tile_scy;
     int padx, pady; float inv_gain;  // yolo scale_boxes
     int cap;                 // caller's capacity per frame (out_* may all be NULL)
     int kcap;                // complete keep list capacity per frame (>= any keep count)
@@ -466,6 +470,40 @@ struct MaskArgs {
 };
 hipError_t vd_launch_mask_grow(const MaskArgs& a, hipStream_t s);
 hipError_t vd_launch_mask_restore(const MaskArgs& a, hipStream_t s);
+
+// Tiled face detection (include/vdmi.h at vd_tiles). T = 1 + rows * cols net inputs per frame:
+// input 0 the whole frame, input 1 + r * cols + c tile (r, c); every tile is tw x th pixels.
+#ifndef VD_TILES_MAX
+#define VD_TILES_MAX 4   // include/vdmi.h: rows, cols in [1, VD_TILES_MAX]
+#endif
+constexpr int VD_TILE_INPUTS_MAX = 1 + VD_TILES_MAX * VD_TILES_MAX;
+struct TileGrid {
+    int T, th, tw;
+    int x0[VD_TILE_INPUTS_MAX], y0[VD_TILE_INPUTS_MAX];   // origin of input t in the frame ([0] = 0)
+};
+// host, integers: xywh[1 + rows * cols][4] of an h x w frame; 0, or -1 outside the ranges
+int vd_tile_rects_host(int h, int w, int rows, int cols, int overlap_pct, int32_t* xywh, int* count);
+// The n * T canvases of n frames in one launch (pre.hip): canvas f * T + t is what
+// vd_launch_letterbox writes for a frame holding input t's rectangle. `whole` / `tile`: the
+// letterbox geometry of the frame / of a tile as a frame of its own (src, n, pitch, out from
+// `whole`; both of one canvas form).
+hipError_t vd_launch_letterbox_tiles(const LetterboxArgs& whole, const LetterboxArgs& tile, const TileGrid& g,
+                                     hipStream_t s);
+// Cross-tile merge (tiles.hip): per frame, the T keep lists -> one list in merged rows.
+struct TileMergeArgs {
+    int n; TileGrid g;
+    int A;                                           // the net's anchor count: label = t * A + label_in
+    double iou;
+    const int* cnt; const float* xyxy_f; const float* score; const int* label;   // [n * T] rows of icap (label optional)
+    int icap;
+    uint64_t* s_keys; float4* s_box; float* s_area; uint8_t* s_supp;   // per-frame spill scratch: [n][sort_cap], [n][mcap] x 3
+    int sort_cap;                                    // power of two >= mcap
+    int mcap;                                        // merged row capacity >= T * icap
+    int* m_count; int* m_xyxy; float* m_xyxy_f; float* m_score; int* m_label;   // merged rows [n][mcap]
+    int cap;                                         // caller's capacity per frame (out_* may all be NULL)
+    int* out_count; int* out_xyxy; float* out_xyxy_f; float* out_score; int* out_label;
+};
+hipError_t vd_launch_tiles_merge(const TileMergeArgs& a, hipStream_t s);
 
 #define VD_CHECK_HIP(expr)                                                   \
     do {                                                                       \

@@ -25,6 +25,7 @@ VD_HOLD_MAX = 8
 VD_HOLD_MOTION_OFF, VD_HOLD_MOTION_LINEAR = 0, 1
 VD_MASK_RECT, VD_MASK_ELLIPSE = 0, 1
 VD_MASK_GROW_MAX = 200
+VD_TILES_MAX = 4
 MASK_SHAPES = {"rect": VD_MASK_RECT, "ellipse": VD_MASK_ELLIPSE}
 VD_PROC_FACES, VD_PROC_PLATES, VD_PROC_MOSAIC, VD_PROC_MOSAIC_PLATES = 1, 2, 4, 8
 FAM_CONV, FAM_MOSAIC, FAM_LETTERBOX, FAM_POST, FAM_OTHER, FAM_PLATE_CONV, FAM_MOSAIC_CELLS = 0, 1, 2, 3, 4, 5, 6
@@ -93,6 +94,9 @@ SIGNATURES = [
     ("vd_read_held", _I, [_P, _I, ctypes.POINTER(vd_boxes)]),
     ("vd_mask", _I, [_P, _I, _I]),
     ("vd_mask_boxes", _I, [_P, ctypes.POINTER(vd_boxes), _I, ctypes.POINTER(vd_boxes)]),
+    ("vd_tile_rects", _I, [_I, _I, _I, _I, _I, _P, ctypes.POINTER(_I)]),
+    ("vd_tiles", _I, [_P, _I, _I, _I]),
+    ("vd_tiles_merge", _I, [_P, ctypes.POINTER(vd_boxes), _I, _I, _I, ctypes.POINTER(vd_boxes)]),
     ("vd_jpeg_decode", _I, [_P, ctypes.POINTER(_P), ctypes.POINTER(_SZ), _I, _P, _I, _I, _SZ, _I]),
     ("vd_jpeg_info", _I, [_P, _SZ, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     ("vd_jpeg_encode", _I, [_P, _P, _I, _I, _I, _SZ, _I, _I, _I, _P, _SZ, ctypes.POINTER(_SZ)]),
@@ -101,6 +105,7 @@ SIGNATURES = [
     ("vd_timing_read", _I, [_P, _I, ctypes.POINTER(_D), ctypes.POINTER(ctypes.c_int64),
                             ctypes.POINTER(_D)]),
     ("vdt_letterbox", _I, [_P, _P, _I, _I, _I, _SZ, _I, _P, _I]),
+    ("vdt_letterbox_tiles", _I, [_P, _P, _I, _I, _I, _SZ, _I, _P, _I]),
     ("vdt_forward_heads", _I, [_P, _P, _I, _I, _I, _SZ, _I, _P, _P, _P]),
     ("vdt_postprocess", _I, [_P, _P, _P, _I, _P, ctypes.POINTER(vd_boxes)]),
     ("vdt_conv2d", _I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _F, _P, _I, _P,
@@ -187,6 +192,32 @@ def check_mask(mask, mask_grow):
     if not 0 <= grow <= VD_MASK_GROW_MAX:
         raise ValueError(f"mask_grow {grow}: expected 0 .. {VD_MASK_GROW_MAX} percent")
     return mask, grow
+
+
+def check_tiles(tiles, tile_overlap):
+    """((rows, cols), overlap percentage) as ints; ValueError outside [1, VD_TILES_MAX]^2 / [0, 50]."""
+    try:
+        rows, cols = (int(v) for v in tiles)
+    except (TypeError, ValueError):
+        raise ValueError(f"tiles {tiles!r}: expected (rows, cols)") from None
+    ov = int(tile_overlap)
+    if not (1 <= rows <= VD_TILES_MAX and 1 <= cols <= VD_TILES_MAX):
+        raise ValueError(f"tiles {(rows, cols)}: expected rows, cols in 1 .. {VD_TILES_MAX}")
+    if not 0 <= ov <= 50:
+        raise ValueError(f"tile_overlap {ov}: expected 0 .. 50 percent")
+    return (rows, cols), ov
+
+
+def tile_rects(h, w, tiles, tile_overlap=20):
+    """vd_tile_rects (host only: the routine the launch path uses): int32 [1 + rows * cols][4] of
+    (x, y, w, h), row 0 the whole frame, row 1 + r * cols + c tile (r, c). VdError outside the
+    header's ranges."""
+    rows, cols = (int(v) for v in tiles)
+    n = max(1, 1 + rows * cols) if 0 < rows < 64 and 0 < cols < 64 else 1
+    out = np.zeros((n, 4), np.int32)
+    cnt = ctypes.c_int(0)
+    check(load().vd_tile_rects(int(h), int(w), rows, cols, int(tile_overlap), ptr(out), ctypes.byref(cnt)))
+    return out[:cnt.value].copy()
 
 
 def blur_weights(ksize, sigma=0.0):

@@ -92,6 +92,31 @@ class DeviceBoxes:
         return v
 
 
+def _rows(boxes, start, n):
+    """Frames [start, start + n) of caller lists, sharing their storage (None stays None)."""
+    if boxes is None:
+        return None
+    if isinstance(boxes, DeviceBoxes):
+        return boxes.view(start, n)
+    v = _lib.HostBoxes.__new__(_lib.HostBoxes)
+    v.n, v.cap = n, boxes.cap
+    for k in ("count", "xyxy", "xyxy_f", "score", "label"):
+        setattr(v, k, getattr(boxes, k)[start:start + n])
+    return v
+
+
+def _host_concat(parts):
+    """Library-allocated host lists of consecutive sub-batches as one HostBoxes."""
+    out = _lib.HostBoxes(sum(p.n for p in parts), max(p.cap for p in parts))
+    r = 0
+    for p in parts:
+        out.count[r:r + p.n] = p.count
+        for k in ("xyxy", "xyxy_f", "score", "label"):
+            getattr(out, k)[r:r + p.n, :p.cap] = getattr(p, k)
+        r += p.n
+    return out
+
+
 BLUR_MODES = {"pixelate": _lib.VD_BLUR_PIXELATE, "gaussian": _lib.VD_BLUR_GAUSSIAN}
 
 
@@ -102,7 +127,7 @@ class Context:
                  nms_iou=0.4, max_boxes=256, mosaic_level=8, plate_nc=1, plate_conf=0.5, plate_iou=0.7,
                  plate_max_det=300, plate_imgsz=640, microbatch=0, microbatch_stage=2, options=None,
                  blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30,
-                 hold_motion=False, mask="rect", mask_grow=0):
+                 hold_motion=False, mask="rect", mask_grow=0, tiles=(1, 1), tile_overlap=20):
         """blur: what process() applies to the kept boxes: "pixelate" (the reference's
         INTER_NEAREST mosaic, the default) or "gaussian" (GaussianBlur(region, (blur_ksize,
         blur_ksize), blur_sigma) per clipped box, in list order; blur_ksize odd in [3, 127],
@@ -122,11 +147,19 @@ class Context:
         becomes about 1 + mask_grow/100 times as long) and, with mask="ellipse", only the
         ellipse inscribed in the grown box hidden (with mask_grow >= 42 that still covers every
         pixel of the box as detected). The default ("rect", 0) blurs the detector's rectangle.
-        Kept as self.mask / self.mask_grow (no vd_cfg fields); set_mask() changes them."""
+        Kept as self.mask / self.mask_grow (no vd_cfg fields); set_mask() changes them.
+        tiles / tile_overlap: tiled face detection (include/vdmi.h at vd_tiles): with tiles=(R, C),
+        R * C > 1, every frame goes through the face net as the whole frame plus R x C crops at
+        their native scale that overlap by tile_overlap percent, and the lists are merged by one
+        more NMS, so faces too small for the letterboxed frame are still found. T = 1 + R * C net
+        inputs per frame: a call carries max_batch // T frames, and detect() / process() split a
+        longer batch. (1, 1) (the default) is off. Kept as self.tiles / self.tile_overlap;
+        set_tiles() changes them."""
         if blur not in BLUR_MODES:
             raise ValueError(f"blur {blur!r}: expected 'pixelate' or 'gaussian'")
         hold, hold_iou_pct = _lib.check_hold(hold, hold_iou_pct, hold_motion)   # before the library is touched
         mask, mask_grow = _lib.check_mask(mask, mask_grow)
+        tiles, tile_overlap = _lib.check_tiles(tiles, tile_overlap)
         lib = _lib.load()
         cfg = _lib.default_cfg()
         cfg.input_h, cfg.input_w = int(input_shape[0]), int(input_shape[1])
@@ -165,6 +198,9 @@ class Context:
         self.mask, self.mask_grow = "rect", 0
         if (mask, mask_grow) != ("rect", 0):
             self.set_mask(mask, mask_grow)
+        self.tiles, self.tile_overlap = (1, 1), tile_overlap
+        if tiles != (1, 1):
+            self.set_tiles(tiles, tile_overlap)
         for k, v in dict(options or {}).items():   # kernel-selection switches (vd_set_option)
             self.set_option(k, v)
 
@@ -239,11 +275,21 @@ class Context:
 
     def detect(self, frames, boxes=None):
         p, n, h, w, pitch, where, keep = _frames_arg(frames)
+        step = self.frames_per_call()
+        if n > step and self.tiles != (1, 1):          # tiling: max_batch // T frames per call
+            parts = [self.detect(keep[s0:s0 + step], _rows(boxes, s0, min(step, n - s0)))
+                     for s0 in range(0, n, step)]
+            return boxes if boxes is not None else _host_concat(parts)
         auto = boxes is None
         boxes = self._boxes(boxes, n)
         s = boxes.struct()
         check(self._lib.vd_detect(self._h, p, n, h, w, pitch, where, ctypes.byref(s)))
         return self._complete(boxes, _lib.VD_NET_RETINAFACE, auto)
+
+    def frames_per_call(self):
+        """Frames one detect() / process() call carries: max_batch, or max_batch // T under tiling."""
+        r, c = self.tiles
+        return self.cfg.max_batch if r * c == 1 else max(1, self.cfg.max_batch // (1 + r * c))
 
     def detect_plates(self, frames, boxes=None):
         p, n, h, w, pitch, where, keep = _frames_arg(frames)
@@ -326,6 +372,20 @@ class Context:
             else:
                 import torch
                 out = torch.empty_like(frames)
+        step = self.frames_per_call()
+        if n > step and self.tiles != (1, 1) and flags & _lib.VD_PROC_FACES:   # tiling: consecutive calls (exact under hold:
+            pf, pp = [], []                            # the history carries across calls)
+            for s0 in range(0, n, step):
+                k = min(step, n - s0)
+                _, f, q = self.process(keep[s0:s0 + k], None if out is None else out[s0:s0 + k],
+                                       _rows(faces, s0, k), _rows(plates, s0, k), flags)
+                pf.append(f)
+                pp.append(q)
+            if faces is None:
+                faces = _host_concat(pf)
+            if plates is None and flags & _lib.VD_PROC_PLATES:
+                plates = _host_concat(pp)
+            return out, faces, plates
         fs = ps = None
         auto_f, auto_p = faces is None, plates is None
         if flags & _lib.VD_PROC_FACES:
@@ -439,6 +499,43 @@ class Context:
                    else _lib.HostBoxes(src.n, src.cap))
         ss, os_ = src.struct(), out.struct()
         check(self._lib.vd_mask_boxes(self._h, ctypes.byref(ss), src.n, ctypes.byref(os_)))
+        return out
+
+    # -- tiled detection -----------------------------------------------------------
+    def set_tiles(self, tiles=(1, 1), tile_overlap=20):
+        """vd_tiles: the tiling (rows, cols) and the overlap percentage (0..50) of the face
+        detection from the next call on; (1, 1) is off. A change forgets the hold history."""
+        tiles, tile_overlap = _lib.check_tiles(tiles, tile_overlap)
+        check(self._lib.vd_tiles(self._h, tiles[0], tiles[1], tile_overlap))
+        self.tiles, self.tile_overlap = tiles, tile_overlap
+
+    def tile_rects(self, h, w):
+        """The net inputs' rectangles (x, y, w, h) of an h x w frame under the context's tiling
+        (vd_tile_rects): int32 [T][4], row 0 the whole frame."""
+        return _lib.tile_rects(h, w, self.tiles, self.tile_overlap)
+
+    def tiles_merge(self, lists, h, w, out=None):
+        """vd_tiles_merge: the cross-tile merge alone. lists: a HostBoxes / DeviceBoxes of n * T
+        rows (frame f's input t at row f * T + t; xyxy_f, score, label read), boxes relative to
+        their rectangle of an h x w frame. Returns `out` (default: HostBoxes with the complete
+        merged lists): the mapped boxes in merged order, label = t * A + the input's label."""
+        T = 1 + self.tiles[0] * self.tiles[1]
+        n = lists.n // T
+        ls = lists.struct()
+        if out is not None:
+            s = out.struct()
+            check(self._lib.vd_tiles_merge(self._h, ctypes.byref(ls), n, int(h), int(w), ctypes.byref(s)))
+            return out
+        check(self._lib.vd_tiles_merge(self._h, ctypes.byref(ls), n, int(h), int(w), None))
+        return self.read_boxes(_lib.VD_NET_RETINAFACE, n)
+
+    def letterbox_tiles(self, frames, cpad=4):
+        """vdt_letterbox_tiles: letterbox() for the n * T canvases of a tiling context, canvas
+        f * T + t; a torch view with padded rows is read at its own row pitch."""
+        p, n, h, w, pitch, where, keep = _frames_arg(frames, pitched=True)
+        T = 1 + self.tiles[0] * self.tiles[1]
+        out = np.zeros((n * T, self.cfg.input_h, self.cfg.input_w, cpad), np.float32)
+        check(self._lib.vdt_letterbox_tiles(self._h, p, n, h, w, pitch, where, ptr(out), cpad))
         return out
 
     # -- frame I/O ------------------------------------------------------------

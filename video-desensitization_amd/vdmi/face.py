@@ -23,7 +23,9 @@ Differences, all deliberate:
   INTEGRATION.md), ``max_batch``, ``device_ids`` / ``device_index``, ``seed``,
   ``weights`` (a state_dict, or "random"), ``options`` (kernel-selection switches),
   ``blur`` / ``blur_ksize`` / ``blur_sigma`` (Context's: "gaussian" makes the fused
-  ``batch_process_images`` path blur the boxes instead of pixelating them).
+  ``batch_process_images`` path blur the boxes instead of pixelating them), ``tiles`` /
+  ``tile_overlap`` (Context's tiled detection: the frame plus R x C overlapping crops at
+  their native scale, merged by one more NMS, for faces too small for the letterboxed frame).
 * Devices (face.py:55-56 wraps the net in ``nn.DataParallel``: every forward is
   split over ALL visible GPUs, the weights re-broadcast each time): one context per
   device, weights uploaded once each; ``detect_images`` cuts the image list into
@@ -102,6 +104,9 @@ class Retinaface(object):
         # mask shaping of what the fused vd_process blurs: Context(mask=..., mask_grow=...)
         "mask": "rect",
         "mask_grow": 0,
+        # tiled face detection for small faces in large frames: Context(tiles=(R, C), tile_overlap=...)
+        "tiles": (1, 1),
+        "tile_overlap": 20,
     }
 
     @classmethod
@@ -115,6 +120,7 @@ class Retinaface(object):
         if self.backbone not in ("resnet50", "mobilenet"):   # face.py:35: cfg_mnet / cfg_re50
             raise ValueError(f"backbone must be 'resnet50' or 'mobilenet', got {self.backbone!r}")
         _lib.check_mask(self.mask, self.mask_grow)          # before a device or the library is touched
+        self.tiles, self.tile_overlap = _lib.check_tiles(self.tiles, self.tile_overlap)
         if not self.letterbox_image:
             raise ValueError("Batch inference requires letterbox_image=True for shape alignment.")  # face.py:80
         if not self.cuda:
@@ -132,7 +138,8 @@ class Retinaface(object):
                              max_boxes=self.max_boxes, options=self.options, blur=self.blur,
                              blur_ksize=self.blur_ksize, blur_sigma=self.blur_sigma, hold=self.hold,
                              hold_iou_pct=self.hold_iou_pct, hold_motion=self.hold_motion,
-                             mask=self.mask, mask_grow=self.mask_grow)
+                             mask=self.mask, mask_grow=self.mask_grow, tiles=self.tiles,
+                             tile_overlap=self.tile_overlap)
                      for d in self.device_ids]
         self.ctx = self.ctxs[0]
         self.generate()

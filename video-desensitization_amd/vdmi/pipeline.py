@@ -483,7 +483,9 @@ def fused_context(face_detector, plate_detector, batch_size, device=None, slot=0
     dev = fd.device_ids[0] if device is None else int(device)
     # the face detector's mask setting can change after it was built (Context.set_mask): a
     # cached context with another mask is never reused
-    key = (id(plate_detector), int(batch_size), dev, int(slot), fd.ctx.mask, fd.ctx.mask_grow)
+    # ... and so can its tiling (Context.set_tiles)
+    key = (id(plate_detector), int(batch_size), dev, int(slot), fd.ctx.mask, fd.ctx.mask_grow, fd.ctx.tiles,
+           fd.ctx.tile_overlap)
     with _FUSED_LOCK:
         cache = fd.__dict__.setdefault("_fused_ctx", {})
         if key in cache:
@@ -495,7 +497,9 @@ def fused_context(face_detector, plate_detector, batch_size, device=None, slot=0
 
 def _new_fused_context(fd, pd, batch_size, dev):
     from .context import Context
-    ctx = Context(device=dev, precision=fd.precision, max_batch=max(int(batch_size), 1),
+    # tiling: T net inputs per frame; a context holds at least one frame's (process() splits a batch)
+    T = 1 + fd.ctx.tiles[0] * fd.ctx.tiles[1] if fd.ctx.tiles != (1, 1) else 1
+    ctx = Context(device=dev, precision=fd.precision, max_batch=max(int(batch_size), T),
                   input_shape=fd.input_shape[:2], confidence=fd.confidence, nms_iou=fd.nms_iou,
                   max_boxes=fd.max_boxes, plate_nc=pd.nc, plate_conf=pd.ctx.cfg.plate_conf,
                   plate_iou=pd.ctx.cfg.plate_iou, plate_max_det=pd.ctx.cfg.plate_max_det,
@@ -503,7 +507,8 @@ def _new_fused_context(fd, pd, batch_size, dev):
                   blur="gaussian" if fd.ctx.cfg.blur_mode == _lib.VD_BLUR_GAUSSIAN else "pixelate",
                   blur_ksize=fd.ctx.cfg.blur_ksize or 31, blur_sigma=fd.ctx.cfg.blur_sigma,
                   hold=fd.ctx.cfg.hold_frames, hold_iou_pct=fd.ctx.cfg.hold_iou_pct or 30,
-                  hold_motion=fd.ctx.hold_motion, mask=fd.ctx.mask, mask_grow=fd.ctx.mask_grow)
+                  hold_motion=fd.ctx.hold_motion, mask=fd.ctx.mask, mask_grow=fd.ctx.mask_grow,
+                  tiles=fd.ctx.tiles, tile_overlap=fd.ctx.tile_overlap)
     ctx.load_weights(_lib.VD_NET_RETINAFACE, fd.state_dict)
     ctx.load_weights(_lib.VD_NET_YOLOV8N, pd.state_dict)
     return ctx
@@ -530,6 +535,11 @@ def _mask_matches(ctx, mask, mask_grow):
     """The context's blurring calls shape their lists exactly so (no cfg fields: the Context
     keeps the setting)."""
     return (ctx.mask, ctx.mask_grow) == (mask, mask_grow)
+
+
+def _tiles_matches(ctx, tiles, tile_overlap):
+    """The context detects faces with exactly this tiling (off: any overlap)."""
+    return ctx.tiles == tiles and (tiles == (1, 1) or ctx.tile_overlap == tile_overlap)
 
 
 def _is_vdmi_pair(face_detector, plate_detector):
@@ -568,7 +578,7 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
                          loader=None, saver=None, mosaic_plates=False, mosaic_level=8, num_workers=6,
                          gpu_codec="auto", jpeg_quality=95, shard="auto", group=None, records=None,
                          blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30,
-                         hold_motion=False, mask="rect", mask_grow=0):
+                         hold_motion=False, mask="rect", mask_grow=0, tiles=(1, 1), tile_overlap=20):
     """combine_detect.py:183-277. Returns (total_processed, total_faces, total_plates).
 
     gpu_codec ("auto" | True | False): with vdmi detectors, no custom loader/saver and
@@ -589,6 +599,14 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     with "ellipse", only the ellipse inscribed in the grown box is hidden. As with blur, the
     one-call path needs a face detector built with the same settings (Retinaface(mask=...,
     mask_grow=...)); otherwise the boxes are shaped and blurred by the per-group launches.
+
+    tiles ((rows, cols), each 1..4) / tile_overlap (0..50 percent): tiled face detection
+    (include/vdmi.h at vd_tiles, Context(tiles=..., tile_overlap=...)): every frame goes through
+    the face net whole and as rows x cols overlapping crops at their native scale, merged by one
+    more NMS, so faces too small for the letterboxed frame are found. It is a property of the
+    detector: the face detector must be the vdmi Retinaface built with the same setting
+    (Retinaface(tiles=..., tile_overlap=...)), else ValueError. Plates are detected on the whole
+    frame. (1, 1) (the default) changes nothing.
 
     hold (0..8) / hold_iou_pct (1..100): box hold (include/vdmi.h, Context(hold=...)): the
     frames are ONE video in the order of their sorted names, and a box stays blurred for up to
@@ -633,6 +651,11 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     saver = saver or save_output_image
     hold, hold_iou_pct = _lib.check_hold(hold, hold_iou_pct, hold_motion)
     mask, mask_grow = _lib.check_mask(mask, mask_grow)
+    tiles, tile_overlap = _lib.check_tiles(tiles, tile_overlap)
+    fctx = getattr(face_detector, "ctx", None)
+    if not (_tiles_matches(fctx, tiles, tile_overlap) if hasattr(fctx, "tiles") else tiles == (1, 1)):
+        raise ValueError("tiles needs the vdmi Retinaface built with the same setting "
+                         "(Retinaface(tiles=..., tile_overlap=...))")
     warm_frames = hold + 1 if hold_motion else hold      # the history's depth
     image_paths = [os.path.join(input_dir, f) for f in os.listdir(input_dir) if f.lower().endswith(IMAGE_EXT)]
     if hold:
