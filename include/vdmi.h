@@ -26,6 +26,8 @@
  *                                   reference equivalent: the reference treats every frame alone)
  *   vd_mask / vd_mask_boxes: where the blur lies (a margin around every box, an elliptical mask inside it;
  *                                   no reference equivalent: the reference blurs the detector's rectangle)
+ *   vd_cells / vd_smooth / vd_cell_level: blur strength that follows the box size (at most N cells across a
+ *                                   box; no reference equivalent: the reference's cell is level px for every box)
  *   vd_read_boxes                <- the complete per-frame box lists the reference's
  *                                   loop iterates (combine_detect.py:241-249), past any cap
  *   vd_sync / vd_last_error / vd_destroy: runtime plumbing (no reference equivalent;
@@ -361,6 +363,60 @@ int vd_mask(vd_ctx* ctx, int shape, int grow_pct);
  * caller can log or draw what was actually hidden. */
 int vd_mask_boxes(vd_ctx* ctx, const vd_boxes* in, int n, vd_boxes* out);
 
+/* ---- box-scaled strength: at most N cells across a face -------------------------
+ * The strength of the hiding is otherwise a constant number of pixels (a mosaic cell of about
+ * `level` px, a Gaussian of blur_ksize taps), so the largest faces are hidden worst. A context has
+ * a cells setting N: 0 (the default) is off -- no extra launch, every byte as before -- or N in
+ * [VD_CELLS_MIN, VD_CELLS_MAX]. Integers only, so the result is defined to the bit.
+ *   L(b)     the cell level of a box b = (x1, y1, x2, y2) of the list being blurred, as stored and
+ *            unclipped, after mask growth if any: W = x2 - x1, H = y2 - y1 in 64 bits, `level` the
+ *            call's base level (cfg.mosaic_level in vd_process);
+ *              L(b) = level                                                  if N == 0, W <= 0 or H <= 0
+ *              L(b) = max(level, min(32768, (max(W, H) + N - 1) / N))        otherwise (floor division).
+ *            Never below `level`; a box longer than level * N px gets at most N cells along each
+ *            side; the level follows the face, not its clipped remainder.
+ *   pixelation (vd_mosaic, vd_process under VD_BLUR_PIXELATE): exactly the mosaic above with L(b)
+ *            in place of `level` for box b: sw = max(1, bw / L(b)), sh = max(1, bh / L(b)); the
+ *            clipping, the resizeNN maps and "box j reads the output of box j-1" are unchanged.
+ *   smooth   (vd_smooth, vd_process under VD_BLUR_GAUSSIAN): the scaled smooth blur. For box k with
+ *            the non-empty clipped rectangle (cx1, cy1, cx2, cy2), bw = cx2 - cx1, bh = cy2 - cy1,
+ *            f = L(k):
+ *              cells  cell (i, j) covers columns [cx1 + i*f, min(cx1 + (i+1)*f, cx2)) and rows
+ *                     likewise; sw = ceil(bw / f), sh = ceil(bh / f), both at most N;
+ *              mean   a(i, j) = (16 * S + n / 2) / n per channel (Q8.4), S the sum of the cell's
+ *                     pixels of `in`, n their number;
+ *              across for x in [0, bw): u = 2x + 1 - f, i0 = floor(u / 2f) (toward minus infinity),
+ *                     r = u - 2f * i0, i0 and i0 + 1 each clamped to [0, sw - 1]:
+ *                     t(x, j) = ((2f - r) * a(i0, j) + r * a(i0 + 1, j) + f) / (2f);
+ *              down   for y in [0, bh): j0, j1, s the same from v = 2y + 1 - f:
+ *                     out = ((2f - s) * t(x, j0) + s * t(x, j1) + 16f) / (32f).
+ *            Every box reads `in`. A pixel takes the value of the box with the largest f among the
+ *            boxes whose clipped rectangle contains it, ties to the lowest list index (faces before
+ *            plates before held boxes); a pixel in no box is out = in: a small weak box over a large
+ *            face never re-exposes it at fine scale, and no box waits for another. f = 1 is the
+ *            identity and a constant region stays constant. Needs h, w <= 32768 and 1 <= level <=
+ *            32768 (VD_ERR_ARG otherwise). The cost does not grow with the strength: every box
+ *            pixel is read once and written once.
+ * Order: merge lists, hold merge, mask growth, L from the grown boxes, the rectangular pass; the
+ * ellipse restore pass runs afterwards, unchanged. Detection outputs, vd_read_boxes, vd_read_held
+ * and the hold history are untouched. vd_blur stays the fixed-kernel Gaussian. Launches
+ * (smooth.hip): the copy in -> out and the box pass, both timing family 1; no scratch memory. */
+#define VD_CELLS_MIN 2
+#define VD_CELLS_MAX 64
+/* 0 is off; a value outside {0} and [VD_CELLS_MIN, VD_CELLS_MAX]: VD_ERR_ARG (setting unchanged).
+ * Takes effect from the next blurring call: vd_process with VD_PROC_MOSAIC in both blur modes,
+ * and vd_mosaic. */
+int vd_cells(vd_ctx* ctx, int cells);
+/* The scaled smooth blur of caller box lists: the counterpart of vd_mosaic and vd_blur, with their
+ * staging rules (host frames / host boxes staged, VD_ERR_CAPACITY for a host list with count[f] >
+ * cap, VD_ERR_ARG for out == in or overlapping device ranges). cells in [VD_CELLS_MIN,
+ * VD_CELLS_MAX]; the context's mask setting applies to it as to the other two. */
+int vd_smooth(vd_ctx* ctx, const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch,
+              int where, const vd_boxes* boxes, int level, int cells);
+/* L of a W x H box (host only: no context, no GPU): the routine the launch path itself calls.
+ * VD_ERR_ARG (negative) for level < 1 or cells outside {0} and [VD_CELLS_MIN, VD_CELLS_MAX]. */
+int vd_cell_level(int W, int H, int level, int cells);
+
 /* ---- tiled face detection: small faces in high-resolution frames -----------------
  * Every frame is letterboxed onto the one input_h x input_w canvas (detect_face/face.py:77-78),
  * so a 3840x2160 frame is shrunk 6x and a face 40 px wide reaches the net about 7 px wide, below
@@ -420,7 +476,7 @@ int vd_tiles_merge(vd_ctx* ctx, const vd_boxes* lists, int n, int h, int w, vd_b
  * on the context stream; vd_timing_read returns the summed duration (ms), the
  * launch count and the summed algorithmic work (FLOP or bytes) since the last
  * reset. Families: 0 = RetinaFace conv (implicit GEMM / streaming 1x1), 1 = mosaic
- * output pass (or the Gaussian blur's launches; the mask's restore pass, work 0: its bytes follow
+ * output pass (or the Gaussian blur's launches, or the smooth blur's copy and box pass; the mask's restore pass, work 0: its bytes follow
  * from the boxes), 2 = letterbox (the tile letterbox too), 3 = post (decode/NMS, box hold,
  * mask grow, tile merge), 4 = other, 5 = YOLOv8n plate
  * conv, 6 = mosaic cell table (box prep + walked cell colours). */

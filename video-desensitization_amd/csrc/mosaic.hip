@@ -25,6 +25,9 @@
 //                      rows); every output byte is written once, by 16-B vector
 //                      stores in contiguous 1-KB wave spans (details at the kernel).
 // HBM traffic = read + write of every frame (2*W*H*3 bytes) + cell gathers (L2).
+// Box-scaled strength (vd_cells, MosaicArgs::ncells > 0): box b takes the level L(b) of
+// vd_cell_level_hd in place of `level` at the two sites that derive sw / sh (prep_box,
+// clip_rect); everything else is as above. ncells == 0: `level` for every box, as before.
 #include "vd_kernel.h"
 #include "vd_math.h"
 
@@ -50,6 +53,7 @@ struct MosaicArgs {
     const int* cnt0; const int* xy0; int cap0;      // list 0 (faces)
     const int* cnt1; const int* xy1; int cap1;      // list 1 (plates, optional)
     int level;
+    int ncells;                                      // vd_cells: 0 = every box at `level`, else the level follows the box (box_level)
     int vec_ok;                                      // 16-B aligned rows -> vector loads/stores
     MBox* table; int tcap;                           // [n][tcap] prepared boxes
     int* cpref;                                      // [n][BOX_FAST+1] prefix sums of box cells sw*sh
@@ -64,6 +68,11 @@ __device__ __forceinline__ int frame_boxes(const MosaicArgs& a, int f, int& n0) 
     return n0 + n1;
 }
 
+// L(b) of the box as stored, unclipped (include/vdmi.h at vd_cells); ncells == 0: a.level
+__device__ __forceinline__ int box_level(const MosaicArgs& a, const int* src) {
+    return vd_cell_level_hd((long long)src[2] - src[0], (long long)src[3] - src[1], a.level, a.ncells);
+}
+
 __device__ MBox prep_box(const MosaicArgs& a, int f, int k, int n0) {
     const int* src = k < n0 ? a.xy0 + ((size_t)f * a.cap0 + k) * 4 : a.xy1 + ((size_t)f * a.cap1 + (k - n0)) * 4;
     MBox m{};
@@ -74,8 +83,9 @@ __device__ MBox prep_box(const MosaicArgs& a, int f, int k, int n0) {
     m.valid = (m.x2 > m.x1 && m.y2 > m.y1) ? 1 : 0;
     if (m.valid) {
         const int bw = m.x2 - m.x1, bh = m.y2 - m.y1;
-        m.sw = max(1, bw / a.level);              // :153-154
-        m.sh = max(1, bh / a.level);
+        const int level = box_level(a, src);
+        m.sw = max(1, bw / level);                // :153-154
+        m.sh = max(1, bh / level);
         // resizeNN [ext]: ifx = 1. / ((double)dst / src)
         m.fux = __ddiv_rn(1.0, __ddiv_rn((double)bw, (double)m.sw));   // up:   dst=bw, src=sw
         m.fdx = __ddiv_rn(1.0, __ddiv_rn((double)m.sw, (double)bw));   // down: dst=sw, src=bw
@@ -105,7 +115,8 @@ __device__ __forceinline__ int4 clip_rect(const MosaicArgs& a, int f, int k, int
     const int* src = k < n0 ? a.xy0 + ((size_t)f * a.cap0 + k) * 4 : a.xy1 + ((size_t)f * a.cap1 + (k - n0)) * 4;
     const int x1 = max(0, src[0]), y1 = max(0, src[1]), x2 = min(a.w, src[2]), y2 = min(a.h, src[3]);
     if (!(x2 > x1 && y2 > y1)) { sz = 1u | (1u << 16); return make_int4(0, 0, 0, 0); }   // :150-151
-    sz = (uint32_t)max(1, (x2 - x1) / a.level) | ((uint32_t)max(1, (y2 - y1) / a.level) << 16);   // :153-154
+    const int level = box_level(a, src);
+    sz = (uint32_t)max(1, (x2 - x1) / level) | ((uint32_t)max(1, (y2 - y1) / level) << 16);   // :153-154
     return make_int4(x1, y1, x2, y2);
 }
 
@@ -864,7 +875,7 @@ size_t vd_mosaic_table_bytes(int n, int tcap) {
 hipError_t vd_launch_mosaic(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch,
                             const int* cnt0, const int* xy0, int cap0,
                             const int* cnt1, const int* xy1, int cap1, int level, void* table,
-                            int stages, int map_on, int cell_blocks, hipStream_t s) {
+                            int stages, int map_on, int cell_blocks, hipStream_t s, int cells) {
     if (n <= 0 || h <= 0 || w <= 0) return hipSuccess;
     cell_blocks = std::min(std::max(cell_blocks, 1), 256);
     const int vec_ok = (pitch % 16 == 0) && ((uintptr_t)in % 16 == 0) && ((uintptr_t)out % 16 == 0);
@@ -872,7 +883,7 @@ hipError_t vd_launch_mosaic(const uint8_t* in, uint8_t* out, int n, int h, int w
     char* cpre = (char*)table + (size_t)n * tcap * sizeof(MBox);
     char* cel = cpre + (size_t)n * (BOX_FAST + 1) * 4;
     cel += (16 - ((uintptr_t)cel & 15)) & 15;
-    MosaicArgs a{in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, level, vec_ok, (MBox*)table, tcap,
+    MosaicArgs a{in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, level, cells, vec_ok, (MBox*)table, tcap,
                  (int*)cpre, (uint32_t*)cel, 1};
     a.map_on = map_on;
     if (stages & 1) hipLaunchKernelGGL(mosaic_cell_kernel, dim3(cell_blocks, n), dim3(256), 0, s, a);

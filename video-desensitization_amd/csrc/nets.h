@@ -202,6 +202,8 @@ struct Ctx {
     int mask_shape = VD_MASK_RECT, mask_grow = 0;
     void* mask_rows = nullptr; size_t mask_rows_bytes = 0;   // grown merged rows: [n][mcap][4], then counts [n]
     MaskArgs mask_last{};                         // the last grow launch (row pointers for the restore pass)
+    // box-scaled strength (vd_cells): 0 = off, every launch and byte as before
+    int cells = 0;
     // tiled face detection (tiles.hip, pre.hip letterbox_tiles_kernel; vd_tiles): nothing is allocated
     // or launched while rows * cols == 1
     int tile_rows = 1, tile_cols = 1, tile_overlap = 0;
@@ -301,7 +303,10 @@ struct Ctx {
     // tiles: net input b is a tile of tiles->th x tiles->tw source pixels unless b % tiles->T == 0
     int face_post(int n, int img_h, int img_w, const BoxTargets& t, const TileGrid* tiles = nullptr);
     int launch_mosaic(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
-                      const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int level);
+                      const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int level, int cells);
+    // the scaled smooth blur (smooth.hip): the copy and the box pass, family 1
+    int launch_smooth(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
+                      const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int level, int cells);
     int launch_blur(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
                     const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int ksize, float sigma);
     bool mask_on() const { return mask_shape != VD_MASK_RECT || mask_grow != 0; }
@@ -310,10 +315,11 @@ struct Ctx {
                          int zero_tail = 0);
     // VD_MASK_ELLIPSE: out <- in outside every ellipse of mask_last's rows, after the rectangular pass
     int launch_mask_restore(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch);
-    // the rectangular pass of the blurring calls behind the mask setting: grow, blur / mosaic, restore
+    // the rectangular pass of the blurring calls behind the mask setting: grow, blur / mosaic / smooth, restore
+    enum { RECT_MOSAIC = 0, RECT_GAUSSIAN = 1, RECT_SMOOTH = 2 };
     int launch_shaped(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
-                      const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, bool gaussian, int level,
-                      int ksize, float sigma);
+                      const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int pass, int level,
+                      int ksize, float sigma, int cells);
     // B = D ++ H of n consecutive frames into hold_last's merged rows, and the history update
     int launch_hold(int n, int h, int w, const int* cnt0, const int* xy0, int cap0, const int* cnt1, const int* xy1,
                     int cap1);

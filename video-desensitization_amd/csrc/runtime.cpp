@@ -1055,14 +1055,14 @@ int Ctx::face_post_tiled(int n, int h, int w, const TileGrid& g, const BoxTarget
 }
 
 int Ctx::launch_mosaic(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
-                       const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int level) {
+                       const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int level, int cells) {
     const int tcap = (cnt0 ? cap0 : 0) + (cnt1 ? cap1 : 0);
     int rc = ensure_staging(&mosaic_table, &mosaic_table_bytes, vd_mosaic_table_bytes(n, tcap) + 64);
     if (rc) return rc;
     const int map_on = tune.mosaic_map | (tune.mosaic_nt << 1) | (tune.mosaic_gather ? 16 : 0) | ((tune.mosaic_rows & 63) << 8);
     auto launch = [&](int stages) {
         return vd_launch_mosaic(in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, level, mosaic_table, stages,
-                                map_on, tune.mosaic_cells, stream);
+                                map_on, tune.mosaic_cells, stream, cells);
     };
     hipError_t e = hipSuccess;
     if (tune.mosaic_fused) {
@@ -1081,6 +1081,26 @@ int Ctx::launch_mosaic(const uint8_t* in, uint8_t* out, int n, int h, int w, siz
         }
     }
     if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "mosaic: %s", hipGetErrorString(e));
+    return VD_OK;
+}
+
+// The scaled smooth blur (vd_cells in a Gaussian-mode context, vd_smooth): the copy in -> out,
+// then the box pass; no scratch (the cell sums live in LDS). Two family-1 intervals: the copy
+// carries the frames' bytes, the box pass's bytes follow from the boxes.
+int Ctx::launch_smooth(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
+                       const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int level, int cells) {
+    if (h > 32768 || w > 32768 || level < 1 || level > 32768)
+        return vd_set_error(VD_ERR_ARG, "smooth blur: h, w <= 32768 and level in [1, 32768] required (got %d x %d, "
+                            "level %d)", w, h, level);
+    if (cells < VD_CELLS_MIN || cells > VD_CELLS_MAX)
+        return vd_set_error(VD_ERR_ARG, "smooth blur: cells %d outside [%d, %d]", cells, VD_CELLS_MIN, VD_CELLS_MAX);
+    hipError_t e = hipSuccess;
+    for (int stage = 0; stage < 2 && e == hipSuccess; ++stage) {
+        t_begin(1, stage == 0 ? 2.0 * n * (double)h * w * 3 : 0);
+        e = vd_launch_smooth(in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, level, cells, stage, stream);
+        t_end();
+    }
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "smooth: %s", hipGetErrorString(e));
     return VD_OK;
 }
 
@@ -1143,8 +1163,8 @@ int Ctx::launch_mask_restore(const uint8_t* in, uint8_t* out, int n, int h, int 
 // before. Otherwise the lists are grown into one merged row per frame, the rectangular pass
 // runs on that row (its second list null), and the ellipse composite follows it.
 int Ctx::launch_shaped(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
-                       const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, bool gaussian, int level,
-                       int ksize, float sigma) {
+                       const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int pass, int level,
+                       int ksize, float sigma, int cells) {
     const bool shaped = mask_on() && (cnt0 || cnt1);
     if (shaped) {
         int rc = launch_mask_grow(n, cnt0, xy0, cap0, cnt1, xy1, cap1);
@@ -1152,8 +1172,10 @@ int Ctx::launch_shaped(const uint8_t* in, uint8_t* out, int n, int h, int w, siz
         cnt0 = mask_last.m_cnt; xy0 = mask_last.m_xy; cap0 = mask_last.mcap;
         cnt1 = xy1 = nullptr; cap1 = 0;
     }
-    int rc = gaussian ? launch_blur(in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, ksize, sigma)
-                      : launch_mosaic(in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, level);
+    // the cell levels come from the boxes as this pass receives them: grown, when a mask is set
+    int rc = pass == RECT_GAUSSIAN ? launch_blur(in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, ksize, sigma)
+             : pass == RECT_SMOOTH ? launch_smooth(in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, level, cells)
+                                   : launch_mosaic(in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, level, cells);
     if (rc) return rc;
     if (shaped && mask_shape == VD_MASK_ELLIPSE) return launch_mask_restore(in, out, n, h, w, pitch);
     return VD_OK;
@@ -1582,8 +1604,8 @@ int vd_mosaic(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw,
         cnt = dc;
         xy = dx;
     }
-    if ((rc = ctx->launch_shaped(din, dout, n, fh, fw, pitch, cnt, xy, boxes->cap, nullptr, nullptr, 0, false, level,
-                                 0, 0.f)))
+    if ((rc = ctx->launch_shaped(din, dout, n, fh, fw, pitch, cnt, xy, boxes->cap, nullptr, nullptr, 0,
+                                 Ctx::RECT_MOSAIC, level, 0, 0.f, ctx->cells)))
         return rc;
     if (where == VD_HOST) {
         VD_CHECK_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -1639,8 +1661,62 @@ int vd_blur(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw, s
         cnt = dc;
         xy = dx;
     }
-    if ((rc = ctx->launch_shaped(din, dout, n, fh, fw, pitch, cnt, xy, boxes->cap, nullptr, nullptr, 0, true, 0,
-                                 ksize, sigma)))
+    if ((rc = ctx->launch_shaped(din, dout, n, fh, fw, pitch, cnt, xy, boxes->cap, nullptr, nullptr, 0,
+                                 Ctx::RECT_GAUSSIAN, 0, ksize, sigma, 0)))
+        return rc;
+    if (where == VD_HOST) {
+        VD_CHECK_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    } else if (boxes->where == VD_HOST) {
+        VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // staging reused by the next call
+    }
+    return VD_OK;
+}
+
+int vd_smooth(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw, size_t pitch, int where,
+              const vd_boxes* boxes, int level, int cells) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (cells < VD_CELLS_MIN || cells > VD_CELLS_MAX)
+        return vd_set_error(VD_ERR_ARG, "vd_smooth: cells %d outside [%d, %d]", cells, VD_CELLS_MIN, VD_CELLS_MAX);
+    if (level < 1 || level > 32768) return vd_set_error(VD_ERR_ARG, "vd_smooth: level %d outside [1, 32768]", level);
+    if (!in || !out || !boxes || !boxes->count || !boxes->xyxy || boxes->cap <= 0)
+        return vd_set_error(VD_ERR_ARG, "vd_smooth: null argument");
+    if (n <= 0 || fh <= 0 || fw <= 0 || fh > 32768 || fw > 32768 || pitch < (size_t)fw * 3)
+        return vd_set_error(VD_ERR_ARG, "vd_smooth: bad geometry (h, w in [1, 32768])");
+    if ((const void*)in == (const void*)out ||
+        (where == VD_DEVICE && vd_ranges_overlap(in, out, (size_t)n * fh * pitch)))
+        return vd_set_error(VD_ERR_ARG, "vd_smooth: out-of-place only (out must not overlap in)");
+    int rc = VD_OK;
+    const uint8_t* din = in;
+    uint8_t* dout = out;
+    size_t bytes = (size_t)n * fh * pitch;
+    if (where == VD_HOST) {
+        if ((rc = ctx->ensure_staging(&ctx->stage_in, &ctx->stage_in_bytes, bytes))) return rc;
+        if ((rc = ctx->ensure_staging(&ctx->stage_out, &ctx->stage_out_bytes, bytes))) return rc;
+        VD_CHECK_HIP(hipMemcpyAsync(ctx->stage_in, in, bytes, hipMemcpyHostToDevice, ctx->stream));
+        din = (const uint8_t*)ctx->stage_in;
+        dout = (uint8_t*)ctx->stage_out;
+    }
+    const int* cnt = boxes->count;
+    const int* xy = boxes->xyxy;
+    if (boxes->where == VD_HOST)   // a count past cap means boxes the caller does not hold: never skip them silently
+        for (int i = 0; i < n; ++i)
+            if (boxes->count[i] > boxes->cap)
+                return vd_set_error(VD_ERR_CAPACITY, "vd_smooth: frame %d has count %d > cap %d (read the complete "
+                                    "list with vd_read_boxes)", i, boxes->count[i], boxes->cap);
+    if (boxes->where == VD_HOST) {
+        size_t nb = (size_t)n * boxes->cap;
+        if ((rc = ctx->ensure_staging(&ctx->stage_box2, &ctx->stage_box2_bytes, n * 4 + nb * 16 + 16))) return rc;
+        int* dc = (int*)ctx->stage_box2;
+        int* dx = dc + ((n + 3) / 4) * 4;
+        VD_CHECK_HIP(hipMemcpyAsync(dc, boxes->count, n * 4, hipMemcpyHostToDevice, ctx->stream));
+        VD_CHECK_HIP(hipMemcpyAsync(dx, boxes->xyxy, nb * 16, hipMemcpyHostToDevice, ctx->stream));
+        cnt = dc;
+        xy = dx;
+    }
+    if ((rc = ctx->launch_shaped(din, dout, n, fh, fw, pitch, cnt, xy, boxes->cap, nullptr, nullptr, 0,
+                                 Ctx::RECT_SMOOTH, level, 0, 0.f, cells)))
         return rc;
     if (where == VD_HOST) {
         VD_CHECK_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -1661,6 +1737,10 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
     if (do_plates && !ctx->plate.loaded) return vd_set_error(VD_ERR_STATE, "plate weights not loaded");
     if (mosaic_plates && !do_plates) return vd_set_error(VD_ERR_ARG, "MOSAIC_PLATES needs PLATES");
     if (do_mosaic && !out) return vd_set_error(VD_ERR_ARG, "MOSAIC needs an output buffer");
+    if (do_mosaic && ctx->cells && ctx->cfg.blur_mode == VD_BLUR_GAUSSIAN &&
+        (fh > 32768 || fw > 32768 || ctx->cfg.mosaic_level < 1 || ctx->cfg.mosaic_level > 32768))
+        return vd_set_error(VD_ERR_ARG, "vd_process: the smooth blur (vd_cells) needs h, w <= 32768 and mosaic_level "
+                            "in [1, 32768]");
     int rc = ctx->check_frames(n, fh, fw, pitch);
     if (rc) return rc;
     // tiled detection: T net inputs per frame through the face net, merged before anything reads them
@@ -1773,9 +1853,12 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
             dout = (uint8_t*)ctx->stage_out;
         }
         // mask shaping (vd_mask) acts here, after the hold merge, on the list being blurred only
-        int r = ctx->launch_shaped(d, dout, n, fh, fw, pitch, c0, x0, k0, c1, x1, k1,
-                                   ctx->cfg.blur_mode == VD_BLUR_GAUSSIAN, ctx->cfg.mosaic_level,
-                                   ctx->cfg.blur_ksize, ctx->cfg.blur_sigma);
+        // box-scaled strength (vd_cells): pixelation takes its level per box, the Gaussian mode
+        // becomes the scaled smooth blur
+        const bool gaussian = ctx->cfg.blur_mode == VD_BLUR_GAUSSIAN;
+        const int pass = !gaussian ? Ctx::RECT_MOSAIC : (ctx->cells ? Ctx::RECT_SMOOTH : Ctx::RECT_GAUSSIAN);
+        int r = ctx->launch_shaped(d, dout, n, fh, fw, pitch, c0, x0, k0, c1, x1, k1, pass, ctx->cfg.mosaic_level,
+                                   ctx->cfg.blur_ksize, ctx->cfg.blur_sigma, ctx->cells);
         if (r) return r;
         if (where == VD_HOST) VD_CHECK_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
         return VD_OK;
@@ -1893,6 +1976,23 @@ int vd_mask(vd_ctx* h, int shape, int grow_pct) {
     ctx->mask_shape = shape;
     ctx->mask_grow = grow_pct;
     return VD_OK;
+}
+
+int vd_cells(vd_ctx* h, int cells) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (cells != 0 && (cells < VD_CELLS_MIN || cells > VD_CELLS_MAX))
+        return vd_set_error(VD_ERR_ARG, "vd_cells: %d (expected 0 = off or [%d, %d])", cells, VD_CELLS_MIN,
+                            VD_CELLS_MAX);
+    ctx->cells = cells;
+    return VD_OK;
+}
+
+int vd_cell_level(int W, int H, int level, int cells) {
+    if (level < 1 || (cells != 0 && (cells < VD_CELLS_MIN || cells > VD_CELLS_MAX)))
+        return vd_set_error(VD_ERR_ARG, "vd_cell_level: level >= 1 and cells 0 or in [%d, %d] required (got %d, %d)",
+                            VD_CELLS_MIN, VD_CELLS_MAX, level, cells);
+    return vd_cell_level_hd((long long)W, (long long)H, level, cells);
 }
 
 int vd_mask_boxes(vd_ctx* h, const vd_boxes* in, int n, vd_boxes* out) {

@@ -1,0 +1,334 @@
+// smooth.hip — the box-scaled smooth blur (vd_smooth, and vd_process with cfg.blur_mode =
+// VD_BLUR_GAUSSIAN in a context with vd_cells on): what a Gaussian-mode context applies when the
+// strength follows the box size.
+//
+// Definition (include/vdmi.h at vd_cells, DESIGN.md "Box-scaled strength"), integers only. Box k
+// with the non-empty clipped rectangle (cx1, cy1, cx2, cy2), bw x bh pixels, f = L(k)
+// (vd_cell_level of the box as stored):
+//   cells     f x f pixels anchored at the clipped origin, sw = ceil(bw / f) by sh = ceil(bh / f)
+//             of them (both at most `cells`); the last of a row or column may be partial
+//   mean      a(i, j) = (16 * S + n / 2) / n per channel: Q8.4, S the cell's sum over `in`, n its
+//             pixel count
+//   across    u = 2x + 1 - f, i0 = floor(u / 2f), r = u - 2f * i0, i0 and i0 + 1 clamped to
+//             [0, sw - 1]:  t(x, j) = ((2f - r) * a(i0, j) + r * a(i0 + 1, j) + f) / (2f)
+//   down      the same from v = 2y + 1 - f (j0, j1, s):
+//             out = ((2f - s) * t(x, j0) + s * t(x, j1) + 16f) / (32f)
+//   boxes     every box reads `in`; a pixel takes the value of the box with the largest f among
+//             those whose clipped rectangle holds it, ties to the lowest list index; a pixel in
+//             no box is out = in.
+// Every intermediate but the mean's numerator fits uint32 (4080 * 2 * 32768 < 2^32).
+//
+// Two launches per call, ordered by the stream alone:
+//   smooth_copy_kernel  in -> out, one workgroup per (frame, band of CR rows), 16-B vectors.
+//   smooth_box_kernel   grid (SLOTS, frames); the workgroup of slot s takes the frame's boxes
+//                       s, s + SLOTS, ... one after the other, so any number of boxes is served
+//                       and the grid follows from n alone. A box of more than PART_PX pixels is
+//                       shared among up to PARTS workgroups (grid z): each writes a band of whole
+//                       cell rows and sums that band and one cell row on either side, which is all
+//                       its rows interpolate between; a small box is part 0's alone. Per box: (1) the boxes that beat it
+//                       (larger f, or equal f and a lower index) and meet it are collected in
+//                       LDS; (2) the box's rows are read once, a thread walking down one byte
+//                       column (consecutive lanes = consecutive bytes of a row) with its sum in
+//                       a register for the rows of one cell row, then one LDS atomic per cell row
+//                       -- the sw x sh x 3 sums are the only state, cells^2 * 12 bytes of LDS,
+//                       and a cell hundreds of pixels wide is just many threads adding to one
+//                       sum; (3) the sums become the Q8.4 means in place; (4) the same walk
+//                       writes: t(x, j0) and t(x, j1) live in registers and are recomputed when
+//                       the row enters the next cell row (one division by 2f per column and cell
+//                       row). Between two cell-row centres the numerator is linear in y, so the
+//                       quotient by 32f and its remainder are carried from row to row (exact: an
+//                       add, and one carry at most); a byte costs no division.
+//                       A pixel inside a beating box is skipped, so every output pixel of the
+//                       pass has exactly one writer (its owner) and overlapping boxes cannot
+//                       race; all reads are of `in`. Usually no box beats another and the test
+//                       is one uniform branch. More beating boxes than the LDS list holds: the
+//                       pixel is tested against the frame's whole list instead.
+// Sums: 255 * f^2 fits uint32 up to f = 4096. A larger f means at most 8 x 8 cells (h, w <=
+// 32768), whose sums are kept in 64 bits in the same LDS. Integer adds in any order give the
+// same sums, so two runs give the same bytes.
+// HBM traffic = read + write of every frame (2*W*H*3 bytes) + one read and one write of every
+// clipped box.
+#include "vd_kernel.h"
+#include "vdmi.h"
+
+#include <algorithm>
+
+namespace {
+
+constexpr int THREADS = 256;
+constexpr int CR = 8;            // rows per copy band
+constexpr int SLOTS = 32;        // box-pass workgroups per frame
+constexpr int PARTS = 8;         // workgroups a large box is shared among (bands of whole cell rows)
+constexpr int PART_PX = 16384;   // ... one per this many pixels of the clipped box
+constexpr int BEAT_CAP = 128;    // beating boxes listed in LDS; more: the global list is walked per pixel
+constexpr int F32_MAX = 4096;    // largest f whose cell sums fit uint32
+
+struct SmoothArgs {
+    const uint8_t* in; uint8_t* out; int n, h, w; size_t pitch;
+    const int* cnt0; const int* xy0; int cap0;      // list 0 (faces)
+    const int* cnt1; const int* xy1; int cap1;      // list 1 (plates, optional)
+    int level, cells;
+};
+
+__device__ __forceinline__ int frame_boxes(const SmoothArgs& a, int f, int& n0) {
+    n0 = a.cnt0 ? min(max(a.cnt0[f], 0), a.cap0) : 0;
+    const int n1 = a.cnt1 ? min(max(a.cnt1[f], 0), a.cap1) : 0;
+    return n0 + n1;
+}
+
+__device__ __forceinline__ int4 raw_box(const SmoothArgs& a, int f, int k, int n0) {
+    const int* src = k < n0 ? a.xy0 + ((size_t)f * a.cap0 + k) * 4 : a.xy1 + ((size_t)f * a.cap1 + (k - n0)) * 4;
+    return make_int4(src[0], src[1], src[2], src[3]);
+}
+
+// combine_detect.py:145-148 clip, :150-151 empty check, as the other rectangular passes clip
+__device__ __forceinline__ bool clip_box(int4 b, int w, int h, int4& c) {
+    c = make_int4(max(0, b.x), max(0, b.y), min(w, b.z), min(h, b.w));
+    return c.z > c.x && c.w > c.y;
+}
+
+__device__ __forceinline__ int box_level(const SmoothArgs& a, int4 b) {
+    return vd_cell_level_hd((long long)b.z - b.x, (long long)b.w - b.y, a.level, a.cells);
+}
+
+// `nbytes` bytes s -> d: a head up to d's 16-B boundary, vectors, a tail (s and d congruent mod 16)
+__device__ __forceinline__ void copy_span(uint8_t* d, const uint8_t* s, size_t nbytes, int tid) {
+    const size_t head = std::min(nbytes, (size_t)((16 - ((uintptr_t)s & 15)) & 15));
+    if ((size_t)tid < head) d[tid] = s[tid];
+    const size_t nv = (nbytes - head) >> 4;
+    const u32x4* s4 = (const u32x4*)(s + head);
+    u32x4* d4 = (u32x4*)(d + head);
+    for (size_t i = tid; i < nv; i += 4 * THREADS) {
+        u32x4 v0{}, v1{}, v2{}, v3{};
+        v0 = s4[i];
+        if (i + THREADS < nv) v1 = s4[i + THREADS];
+        if (i + 2 * THREADS < nv) v2 = s4[i + 2 * THREADS];
+        if (i + 3 * THREADS < nv) v3 = s4[i + 3 * THREADS];
+        d4[i] = v0;
+        if (i + THREADS < nv) d4[i + THREADS] = v1;
+        if (i + 2 * THREADS < nv) d4[i + 2 * THREADS] = v2;
+        if (i + 3 * THREADS < nv) d4[i + 3 * THREADS] = v3;
+    }
+    const size_t tail = head + (nv << 4);
+    if (tail + tid < nbytes) d[tail + tid] = s[tail + tid];
+}
+
+__global__ __launch_bounds__(THREADS) void smooth_copy_kernel(SmoothArgs a, int vec_ok) {
+    const int f = blockIdx.y, y0 = blockIdx.x * CR, tid = threadIdx.x;
+    const int rows = min(CR, a.h - y0);
+    const size_t row_bytes = (size_t)a.w * 3;
+    const uint8_t* src = a.in + ((size_t)f * a.h + y0) * a.pitch;
+    uint8_t* dst = a.out + ((size_t)f * a.h + y0) * a.pitch;
+    if (!vec_ok) {                                         // in and out differ mod 16: bytes
+        for (int r = 0; r < rows; ++r)
+            for (size_t i = tid; i < row_bytes; i += THREADS) dst[r * a.pitch + i] = src[r * a.pitch + i];
+        return;
+    }
+    // the band itself: one span when the rows are packed, else row by row (padding untouched)
+    if (a.pitch == row_bytes) {
+        copy_span(dst, src, (size_t)rows * row_bytes, tid);
+    } else {
+        for (int r = 0; r < rows; ++r) copy_span(dst + r * a.pitch, src + r * a.pitch, row_bytes, tid);
+    }
+}
+
+// t(x, j) of the definition for one channel: the row of means j, the two clamped cell columns
+// and the weight r of the second
+__device__ __forceinline__ uint32_t across(const uint32_t* mean, int j, int sw, int ia, int ib, uint32_t r,
+                                           uint32_t f, int ch) {
+    const uint32_t va = mean[(j * sw + ia) * 3 + ch], vb = mean[(j * sw + ib) * 3 + ch];
+    return ((2u * f - r) * va + r * vb + f) / (2u * f);
+}
+
+__global__ __launch_bounds__(THREADS) void smooth_box_kernel(SmoothArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_cell[];   // [sh][sw][3] sums, then Q8.4 means
+    __shared__ int4 s_beat[BEAT_CAP];                   // clipped rectangles of the boxes beating this one
+    __shared__ int s_nbeat;
+    const int fr = blockIdx.y, tid = threadIdx.x, part = blockIdx.z;
+    int n0;
+    const int nb = frame_boxes(a, fr, n0);
+    const uint8_t* src = a.in + (size_t)fr * a.h * a.pitch;
+    uint8_t* dst = a.out + (size_t)fr * a.h * a.pitch;
+
+    for (int k = blockIdx.x; k < nb; k += gridDim.x) {     // uniform over the workgroup
+        const int4 b = raw_box(a, fr, k, n0);
+        int4 c;
+        if (!clip_box(b, a.w, a.h, c)) continue;
+        const int f = box_level(a, b);
+        const int bw = c.z - c.x, bh = c.w - c.y;
+        const int sw = (bw + f - 1) / f, sh = (bh + f - 1) / f;
+        const int ncell = sw * sh * 3;
+        const bool wide = f > F32_MAX;                     // 64-bit sums, at most 8 x 8 cells
+        if (sw > a.cells || sh > a.cells || (wide && ncell > THREADS)) continue;   // the LDS holds cells^2: cannot happen for h, w <= 32768
+        // a large box is cut into bands of whole cell rows, one per part (blockIdx.z)
+        const int nparts = min(min(PARTS, sh), max(1, (int)(((long long)bw * bh) / PART_PX)));
+        if (part >= nparts) continue;
+        unsigned long long* s_cell64 = (unsigned long long*)s_cell;
+
+        __syncthreads();                                   // the previous box's reads of the LDS are done
+        for (int i = tid; i < (wide ? 2 * ncell : ncell); i += THREADS) s_cell[i] = 0;
+        if (tid == 0) s_nbeat = 0;
+        __syncthreads();
+
+        // (1) the boxes that beat this one and meet it
+        for (int m = tid; m < nb; m += THREADS) {
+            if (m == k) continue;
+            const int4 bm = raw_box(a, fr, m, n0);
+            int4 cm;
+            if (!clip_box(bm, a.w, a.h, cm)) continue;
+            if (cm.x >= c.z || cm.z <= c.x || cm.y >= c.w || cm.w <= c.y) continue;
+            const int fm = box_level(a, bm);
+            if (fm > f || (fm == f && m < k)) {
+                const int i = atomicAdd(&s_nbeat, 1);
+                if (i < BEAT_CAP) s_beat[i] = cm;
+            }
+        }
+
+        // thread layout of both walks: a row has nbx bytes; a narrow box is cut into RG groups of
+        // consecutive rows walked side by side, a wide one is walked CP byte columns at a time
+        const int nbx = bw * 3;
+        const int CP = nbx < THREADS ? nbx : THREADS;
+        const int RG = nbx < THREADS ? THREADS / nbx : 1;
+        const int rg = tid / CP, col0 = tid - rg * CP;
+        // this thread's rows of [lo, hi)
+        auto my_rows = [&](int lo, int hi, int& ya, int& yb) {
+            const int chunk = (hi - lo + RG - 1) / RG;
+            ya = min(lo + rg * chunk, hi);
+            yb = rg < RG ? min(ya + chunk, hi) : ya;
+        };
+        // the part's band: it writes cell rows [jA, jB) and needs the means of one more on either side
+        const int jA = part * sh / nparts, jB = (part + 1) * sh / nparts;
+        int ya, yb;
+        my_rows(max(jA - 1, 0) * f, min((jB + 1) * f, bh), ya, yb);
+        const uint8_t* sbox = src + (size_t)c.y * a.pitch + (size_t)c.x * 3;
+        uint8_t* dbox = dst + (size_t)c.y * a.pitch + (size_t)c.x * 3;
+
+        // (2) cell sums
+        if (ya < yb)
+            for (int bc = col0; bc < nbx; bc += CP) {
+                const int x = bc / 3, ch = bc - 3 * x, i = x / f;
+                for (int j = ya / f; j * f < yb; ++j) {
+                    const int y0 = max(ya, j * f), y1 = min(yb, j * f + f);
+                    uint32_t acc = 0;                      // at most 255 * 32768
+                    const uint8_t* p = sbox + (size_t)y0 * a.pitch + bc;
+#pragma unroll 8
+                    for (int y = y0; y < y1; ++y, p += a.pitch) acc += *p;
+                    const int e = (j * sw + i) * 3 + ch;
+                    if (wide) atomicAdd(&s_cell64[e], (unsigned long long)acc);
+                    else atomicAdd(&s_cell[e], acc);
+                }
+            }
+        __syncthreads();
+
+        // (3) sums -> Q8.4 means, in place
+        auto mean_of = [&](int e, unsigned long long S) -> uint32_t {
+            const int cell = e / 3, j = cell / sw, i = cell - j * sw;
+            const uint32_t n = (uint32_t)(min(i * f + f, bw) - i * f) * (uint32_t)(min(j * f + f, bh) - j * f);
+            if ((S >> 27) == 0) return (16u * (uint32_t)S + n / 2) / n;
+            return (uint32_t)((16ULL * S + n / 2) / n);
+        };
+        if (wide) {
+            const unsigned long long S = tid < ncell ? s_cell64[tid] : 0;
+            __syncthreads();
+            if (tid < ncell) s_cell[tid] = mean_of(tid, S);
+        } else {
+            for (int e = tid; e < ncell; e += THREADS) s_cell[e] = mean_of(e, s_cell[e]);
+        }
+        __syncthreads();
+        const int nbeat = s_nbeat;
+
+        // (4) interpolate and write what this box owns
+        my_rows(jA * f, min(jB * f, bh), ya, yb);
+        if (ya < yb) {
+            const uint32_t uf = (uint32_t)f, f2 = 2u * uf, d = 32u * uf;
+            for (int bc = col0; bc < nbx; bc += CP) {
+                const int x = bc / 3, ch = bc - 3 * x;
+                const int u = 2 * x + 1 - f;               // > -2f
+                const int i0 = u < 0 ? -1 : (int)((uint32_t)u / f2);
+                const uint32_t r = (uint32_t)(u - (int)f2 * i0);
+                const int ia = min(max(i0, 0), sw - 1), ib = min(max(i0 + 1, 0), sw - 1);
+                const int v = 2 * ya + 1 - f;
+                int j0 = v < 0 ? -1 : (int)((uint32_t)v / f2);
+                uint32_t s = (uint32_t)(v - (int)f2 * j0);
+                // Between two cell-row centres T = (2f - s) t0 + s t1 is linear in y: the quotient
+                // (T + 16f) / 32f = o and its remainder are carried from row to row, exactly,
+                // o += dq, rem += dr with (dq, dr) = floor-divmod(2 (t1 - t0), 32f), one carry at most
+                uint32_t o = 0, rem = 0, dr = 0;
+                int dq = 0;
+                auto cell_rows = [&]() {
+                    const int ja = min(max(j0, 0), sh - 1), jb = min(max(j0 + 1, 0), sh - 1);
+                    const uint32_t t0 = across(s_cell, ja, sw, ia, ib, r, uf, ch);
+                    const uint32_t t1 = jb == ja ? t0 : across(s_cell, jb, sw, ia, ib, r, uf, ch);
+                    const uint32_t T = (f2 - s) * t0 + s * t1 + 16u * uf;
+                    o = T / d;
+                    rem = T - o * d;
+                    const int delta = 2 * ((int)t1 - (int)t0);
+                    dq = delta >= 0 ? (int)((uint32_t)delta / d) : -(int)(((uint32_t)(-delta) + d - 1) / d);
+                    dr = (uint32_t)(delta - dq * (int)d);      // in [0, 32f)
+                };
+                cell_rows();
+                const int gx = c.x + x;
+                uint8_t* p = dbox + (size_t)ya * a.pitch + bc;
+                for (int y = ya; y < yb; ++y, p += a.pitch) {
+                    bool mine = true;
+                    if (nbeat) {
+                        const int gy = c.y + y;
+                        if (nbeat <= BEAT_CAP) {
+                            for (int q = 0; q < nbeat; ++q) {
+                                const int4 m = s_beat[q];
+                                if (gx >= m.x && gx < m.z && gy >= m.y && gy < m.w) mine = false;
+                            }
+                        } else {
+                            for (int m = 0; m < nb && mine; ++m) {
+                                if (m == k) continue;
+                                const int4 bm = raw_box(a, fr, m, n0);
+                                int4 cm;
+                                if (!clip_box(bm, a.w, a.h, cm)) continue;
+                                if (gx < cm.x || gx >= cm.z || gy < cm.y || gy >= cm.w) continue;
+                                const int fm = box_level(a, bm);
+                                if (fm > f || (fm == f && m < k)) mine = false;
+                            }
+                        }
+                    }
+                    if (mine) *p = (uint8_t)o;
+                    s += 2;
+                    if (s >= f2) {                         // the next row lies past cell row j0 + 1's centre
+                        s -= f2;
+                        ++j0;
+                        cell_rows();
+                    } else {
+                        o += dq;
+                        rem += dr;
+                        if (rem >= d) { rem -= d; ++o; }
+                    }
+                }
+            }
+        }
+    }
+}
+
+}  // namespace
+
+size_t vd_smooth_lds_bytes(int cells) {
+    const int c8 = std::min(cells, 8);
+    return std::max((size_t)cells * cells * 3 * 4, (size_t)c8 * c8 * 3 * 8);
+}
+
+hipError_t vd_launch_smooth(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch,
+                            const int* cnt0, const int* xy0, int cap0,
+                            const int* cnt1, const int* xy1, int cap1, int level, int cells, int stage,
+                            hipStream_t s) {
+    if (n <= 0 || h <= 0 || w <= 0) return hipSuccess;
+    if (h > 32768 || w > 32768 || level < 1 || level > 32768 || cells < VD_CELLS_MIN || cells > VD_CELLS_MAX ||
+        n > 65535 || pitch < (size_t)w * 3)
+        return hipErrorInvalidValue;
+    SmoothArgs a{in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, level, cells};
+    if (stage == 0) {
+        // vectors need in and out congruent mod 16 (then every row's spans are, at one pitch)
+        const int vec_ok = (((uintptr_t)in ^ (uintptr_t)out) & 15) == 0;
+        hipLaunchKernelGGL(smooth_copy_kernel, dim3((h + CR - 1) / CR, n), dim3(THREADS), 0, s, a, vec_ok);
+    } else if (cnt0 || cnt1) {
+        hipLaunchKernelGGL(smooth_box_kernel, dim3(SLOTS, n, PARTS), dim3(THREADS), vd_smooth_lds_bytes(cells), s, a);
+    }
+    return hipGetLastError();
+}

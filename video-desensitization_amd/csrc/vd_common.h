@@ -425,8 +425,26 @@ hipError_t vd_launch_jpeg(const JpegArgs& a, hipStream_t s);
 hipError_t vd_launch_mosaic(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch,
                             const int* cnt0, const int* xy0, int cap0,
                             const int* cnt1, const int* xy1, int cap1, int level, void* table,
-                            int stages, int map_on, int cell_blocks, hipStream_t s);   // stages: 1 = cell table, 2 = output pass, 4 = copy
+                            int stages, int map_on, int cell_blocks, hipStream_t s, int cells = 0);   // stages: 1 = cell table, 2 = output pass, 4 = copy; cells: vd_cells (0 = off)
 size_t vd_mosaic_table_bytes(int n, int tcap);
+// Box-scaled strength (include/vdmi.h at vd_cells): the cell level L of a box of unclipped size
+// W x H under the base level and the cells setting. cells == 0 or an empty box: the base level;
+// otherwise max(level, min(32768, ceil(max(W, H) / cells))). The one routine of the kernels
+// (mosaic.hip, smooth.hip) and of the host call vd_cell_level.
+__host__ __device__ inline int vd_cell_level_hd(long long W, long long H, int level, int cells) {
+    if (cells == 0 || W <= 0 || H <= 0) return level;
+    const long long m = W > H ? W : H;
+    // int32 coordinates: m < 2^32. Past 32768 * cells the clamp binds, below it 32 bits do
+    const int q = m > 32768LL * cells ? 32768 : (int)(((unsigned)m + (unsigned)cells - 1u) / (unsigned)cells);
+    return q > level ? q : level;
+}
+// Scaled smooth blur of box lists (smooth.hip). stage 0: the copy in -> out; stage 1: the box
+// pass (reads `in`, writes the boxes' pixels of `out`; after stage 0 on the same stream).
+// h, w <= 32768, 1 <= level <= 32768, cells in [VD_CELLS_MIN, VD_CELLS_MAX].
+hipError_t vd_launch_smooth(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch,
+                            const int* cnt0, const int* xy0, int cap0,
+                            const int* cnt1, const int* xy1, int cap1, int level, int cells, int stage,
+                            hipStream_t s);
 // Gaussian blur of box lists (blur.hip): plan + band pass + dependent-box pass on `s`.
 // q: the ksize Q20 weights of vd_blur_weights; table: vd_blur_table_bytes(n, h, pitch, tcap) bytes.
 hipError_t vd_launch_blur(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch,

@@ -26,6 +26,7 @@ VD_HOLD_MOTION_OFF, VD_HOLD_MOTION_LINEAR = 0, 1
 VD_MASK_RECT, VD_MASK_ELLIPSE = 0, 1
 VD_MASK_GROW_MAX = 200
 VD_TILES_MAX = 4
+VD_CELLS_MIN, VD_CELLS_MAX = 2, 64
 MASK_SHAPES = {"rect": VD_MASK_RECT, "ellipse": VD_MASK_ELLIPSE}
 VD_PROC_FACES, VD_PROC_PLATES, VD_PROC_MOSAIC, VD_PROC_MOSAIC_PLATES = 1, 2, 4, 8
 FAM_CONV, FAM_MOSAIC, FAM_LETTERBOX, FAM_POST, FAM_OTHER, FAM_PLATE_CONV, FAM_MOSAIC_CELLS = 0, 1, 2, 3, 4, 5, 6
@@ -94,6 +95,9 @@ SIGNATURES = [
     ("vd_read_held", _I, [_P, _I, ctypes.POINTER(vd_boxes)]),
     ("vd_mask", _I, [_P, _I, _I]),
     ("vd_mask_boxes", _I, [_P, ctypes.POINTER(vd_boxes), _I, ctypes.POINTER(vd_boxes)]),
+    ("vd_cells", _I, [_P, _I]),
+    ("vd_smooth", _I, [_P, _P, _P, _I, _I, _I, _SZ, _I, ctypes.POINTER(vd_boxes), _I, _I]),
+    ("vd_cell_level", _I, [_I, _I, _I, _I]),
     ("vd_tile_rects", _I, [_I, _I, _I, _I, _I, _P, ctypes.POINTER(_I)]),
     ("vd_tiles", _I, [_P, _I, _I, _I]),
     ("vd_tiles_merge", _I, [_P, ctypes.POINTER(vd_boxes), _I, _I, _I, ctypes.POINTER(vd_boxes)]),
@@ -192,6 +196,24 @@ def check_mask(mask, mask_grow):
     if not 0 <= grow <= VD_MASK_GROW_MAX:
         raise ValueError(f"mask_grow {grow}: expected 0 .. {VD_MASK_GROW_MAX} percent")
     return mask, grow
+
+
+def check_cells(cells):
+    """cells as int; ValueError outside {0} and [VD_CELLS_MIN, VD_CELLS_MAX]."""
+    c = int(cells)
+    if c != 0 and not VD_CELLS_MIN <= c <= VD_CELLS_MAX:
+        raise ValueError(f"cells {c}: expected 0 (off) or {VD_CELLS_MIN} .. {VD_CELLS_MAX}")
+    return c
+
+
+def cell_level(W, H, level, cells):
+    """vd_cell_level (host only: the routine the launch path uses): the cell level L of a box of
+    unclipped size W x H under the base level and the cells setting. VdError for level < 1 or a
+    cells value outside the header's range."""
+    rc = load().vd_cell_level(int(W), int(H), int(level), int(cells))
+    if rc < 0:
+        check(rc)
+    return rc
 
 
 def check_tiles(tiles, tile_overlap):

@@ -127,7 +127,7 @@ class Context:
                  nms_iou=0.4, max_boxes=256, mosaic_level=8, plate_nc=1, plate_conf=0.5, plate_iou=0.7,
                  plate_max_det=300, plate_imgsz=640, microbatch=0, microbatch_stage=2, options=None,
                  blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30,
-                 hold_motion=False, mask="rect", mask_grow=0, tiles=(1, 1), tile_overlap=20):
+                 hold_motion=False, mask="rect", mask_grow=0, tiles=(1, 1), tile_overlap=20, cells=0):
         """blur: what process() applies to the kept boxes: "pixelate" (the reference's
         INTER_NEAREST mosaic, the default) or "gaussian" (GaussianBlur(region, (blur_ksize,
         blur_ksize), blur_sigma) per clipped box, in list order; blur_ksize odd in [3, 127],
@@ -154,12 +154,19 @@ class Context:
         more NMS, so faces too small for the letterboxed frame are still found. T = 1 + R * C net
         inputs per frame: a call carries max_batch // T frames, and detect() / process() split a
         longer batch. (1, 1) (the default) is off. Kept as self.tiles / self.tile_overlap;
-        set_tiles() changes them."""
+        set_tiles() changes them.
+        cells: box-scaled strength (include/vdmi.h at vd_cells): with cells = N in 2..64 every box
+        is hidden with at most N cells along its longer side instead of a constant number of
+        pixels -- pixelation picks its level per box (never below mosaic_level), and a
+        "gaussian" context applies the scaled smooth blur (cell means interpolated across the
+        box) in place of the fixed kernel, in process() and mosaic(); blur() stays the
+        fixed-kernel Gaussian. 0 (the default) is off. Kept as self.cells; set_cells() changes it."""
         if blur not in BLUR_MODES:
             raise ValueError(f"blur {blur!r}: expected 'pixelate' or 'gaussian'")
         hold, hold_iou_pct = _lib.check_hold(hold, hold_iou_pct, hold_motion)   # before the library is touched
         mask, mask_grow = _lib.check_mask(mask, mask_grow)
         tiles, tile_overlap = _lib.check_tiles(tiles, tile_overlap)
+        cells = _lib.check_cells(cells)
         lib = _lib.load()
         cfg = _lib.default_cfg()
         cfg.input_h, cfg.input_w = int(input_shape[0]), int(input_shape[1])
@@ -201,6 +208,9 @@ class Context:
         self.tiles, self.tile_overlap = (1, 1), tile_overlap
         if tiles != (1, 1):
             self.set_tiles(tiles, tile_overlap)
+        self.cells = 0
+        if cells:
+            self.set_cells(cells)
         for k, v in dict(options or {}).items():   # kernel-selection switches (vd_set_option)
             self.set_option(k, v)
 
@@ -362,6 +372,44 @@ class Context:
         check(self._lib.vd_blur(self._h, p, optr, n, h, w, pitch, where, ctypes.byref(s), int(ksize), float(sigma)))
         return out
 
+    def smooth(self, frames, boxes_xyxy, counts=None, level=None, cells=None, out=None):
+        """Out-of-place scaled smooth blur of the boxes (vd_smooth), the counterpart of mosaic()
+        and blur(): the same frames / boxes_xyxy / counts forms, a torch view with padded rows
+        (big[:, :, :w]) read and written at its own row pitch. level defaults to the context's
+        mosaic_level, cells to the context's setting (ValueError if that is 0: off)."""
+        cells = _lib.check_cells(self.cells if cells is None else cells)
+        if cells == 0:
+            raise ValueError("smooth() needs cells in 2 .. 64 (the context's setting is 0: off)")
+        p, n, h, w, pitch, where, src = _frames_arg(frames, pitched=True)
+        if isinstance(boxes_xyxy, (_lib.HostBoxes, DeviceBoxes)):
+            s = boxes_xyxy.struct()
+        else:
+            xy = np.ascontiguousarray(boxes_xyxy, np.int32).reshape(n, -1, 4)
+            cnt = np.ascontiguousarray(counts if counts is not None else np.full(n, xy.shape[1]), np.int32)
+            cap = max(1, xy.shape[1])
+            if xy.shape[1] == 0:
+                xy = np.zeros((n, 1, 4), np.int32)
+            s = _lib.vd_boxes(cap, _lib.VD_HOST, ptr(cnt), ptr(xy), None, None, None)
+        if out is None:
+            if pitch != w * 3:
+                raise ValueError("frames with padded rows need out= (a view with the same row pitch)")
+            if where == _lib.VD_HOST:
+                out = np.empty((n, h, w, 3), np.uint8)
+            else:
+                import torch
+                out = torch.empty_like(src)
+        if _is_torch(out):
+            packed = out.is_contiguous()
+            if tuple(out.shape) != (n, h, w, 3) or not (packed or _row_padded(out)) or \
+                    (w * 3 if packed else out.stride(1)) != pitch:
+                raise ValueError("out must be uint8 [n,h,w,3] with the frames' row pitch")
+            optr = out.data_ptr()
+        else:
+            optr = ptr(out)
+        check(self._lib.vd_smooth(self._h, p, optr, n, h, w, pitch, where, ctypes.byref(s),
+                                  int(level or self.cfg.mosaic_level), cells))
+        return out
+
     def process(self, frames, out=None, faces=None, plates=None, flags=None):
         p, n, h, w, pitch, where, keep = _frames_arg(frames)
         if flags is None:
@@ -500,6 +548,14 @@ class Context:
         ss, os_ = src.struct(), out.struct()
         check(self._lib.vd_mask_boxes(self._h, ctypes.byref(ss), src.n, ctypes.byref(os_)))
         return out
+
+    # -- box-scaled strength -------------------------------------------------------
+    def set_cells(self, cells=0):
+        """vd_cells: at most `cells` (2..64) cells across every box from the next blurring call
+        on; 0 is off (the constant mosaic_level / blur_ksize)."""
+        cells = _lib.check_cells(cells)
+        check(self._lib.vd_cells(self._h, cells))
+        self.cells = cells
 
     # -- tiled detection -----------------------------------------------------------
     def set_tiles(self, tiles=(1, 1), tile_overlap=20):

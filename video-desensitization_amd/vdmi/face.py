@@ -107,6 +107,8 @@ class Retinaface(object):
         # tiled face detection for small faces in large frames: Context(tiles=(R, C), tile_overlap=...)
         "tiles": (1, 1),
         "tile_overlap": 20,
+        # box-scaled strength of what the fused vd_process blurs: Context(cells=...)
+        "cells": 0,
     }
 
     @classmethod
@@ -121,6 +123,7 @@ class Retinaface(object):
             raise ValueError(f"backbone must be 'resnet50' or 'mobilenet', got {self.backbone!r}")
         _lib.check_mask(self.mask, self.mask_grow)          # before a device or the library is touched
         self.tiles, self.tile_overlap = _lib.check_tiles(self.tiles, self.tile_overlap)
+        self.cells = _lib.check_cells(self.cells)
         if not self.letterbox_image:
             raise ValueError("Batch inference requires letterbox_image=True for shape alignment.")  # face.py:80
         if not self.cuda:
@@ -139,7 +142,7 @@ class Retinaface(object):
                              blur_ksize=self.blur_ksize, blur_sigma=self.blur_sigma, hold=self.hold,
                              hold_iou_pct=self.hold_iou_pct, hold_motion=self.hold_motion,
                              mask=self.mask, mask_grow=self.mask_grow, tiles=self.tiles,
-                             tile_overlap=self.tile_overlap)
+                             tile_overlap=self.tile_overlap, cells=self.cells)
                      for d in self.device_ids]
         self.ctx = self.ctxs[0]
         self.generate()

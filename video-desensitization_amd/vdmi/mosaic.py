@@ -12,13 +12,13 @@ _ctxs = {}
 _ctx_lock = threading.Lock()
 
 
-def _default_ctx(mask="rect", mask_grow=0):
-    """One shared context per mask setting (the setting is a context's state, and the
-    callers are threads)."""
-    key = (mask, int(mask_grow))
+def _default_ctx(mask="rect", mask_grow=0, cells=0):
+    """One shared context per mask and cells setting (the settings are a context's state, and
+    the callers are threads)."""
+    key = (mask, int(mask_grow), int(cells))
     with _ctx_lock:
         if key not in _ctxs:
-            _ctxs[key] = Context(max_batch=64, mask=mask, mask_grow=mask_grow)
+            _ctxs[key] = Context(max_batch=64, mask=mask, mask_grow=mask_grow, cells=cells)
         return _ctxs[key]
 
 
@@ -42,14 +42,26 @@ def _box_arrays(n, boxes):
     return xy, cnt
 
 
-def mosaic_frames(frames, boxes, mosaic_level=8, ctx=None, mask="rect", mask_grow=0):
+def mosaic_frames(frames, boxes, mosaic_level=8, ctx=None, mask="rect", mask_grow=0, cells=0):
     """frames: uint8 [n,h,w,3]; boxes: list (per frame) of (x1,y1,x2,y2) int tuples.
     Equivalent to applying mosaic_rectangle_region_single per box in order. mask /
     mask_grow: the mask shaping (Context(mask=..., mask_grow=...)) of the shared context
-    used when no ctx is given; a given ctx applies its own."""
+    used when no ctx is given; a given ctx applies its own. cells: box-scaled strength
+    (Context(cells=...)) of that shared context: the level follows each box, never below
+    mosaic_level."""
     frames = np.ascontiguousarray(frames, np.uint8)
     xy, cnt = _box_arrays(frames.shape[0], boxes)
-    return (ctx or _default_ctx(mask, mask_grow)).mosaic(frames, xy, cnt, level=mosaic_level)
+    return (ctx or _default_ctx(mask, mask_grow, cells)).mosaic(frames, xy, cnt, level=mosaic_level)
+
+
+def smooth_frames(frames, boxes, mosaic_level=8, cells=16, ctx=None, mask="rect", mask_grow=0):
+    """frames: uint8 [n,h,w,3]; boxes: list (per frame) of (x1,y1,x2,y2) int tuples. The scaled
+    smooth blur (vd_smooth) of every box: at most `cells` cells along its longer side, their
+    means interpolated across the box; where boxes overlap the strongest wins. mask / mask_grow
+    as in mosaic_frames."""
+    frames = np.ascontiguousarray(frames, np.uint8)
+    xy, cnt = _box_arrays(frames.shape[0], boxes)
+    return (ctx or _default_ctx(mask, mask_grow)).smooth(frames, xy, cnt, level=mosaic_level, cells=cells)
 
 
 def gaussian_blur_region_single(img, x1, y1, x2, y2, ksize=31, sigma=0.0):

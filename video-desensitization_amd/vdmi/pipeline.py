@@ -31,7 +31,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import _lib
-from .mosaic import blur_frames, mosaic_frames
+from .mosaic import blur_frames, mosaic_frames, smooth_frames
 
 IMAGE_EXT = (".png", ".jpg", ".jpeg")
 
@@ -484,8 +484,9 @@ def fused_context(face_detector, plate_detector, batch_size, device=None, slot=0
     # the face detector's mask setting can change after it was built (Context.set_mask): a
     # cached context with another mask is never reused
     # ... and so can its tiling (Context.set_tiles)
+    # ... and its cells setting (Context.set_cells)
     key = (id(plate_detector), int(batch_size), dev, int(slot), fd.ctx.mask, fd.ctx.mask_grow, fd.ctx.tiles,
-           fd.ctx.tile_overlap)
+           fd.ctx.tile_overlap, fd.ctx.cells)
     with _FUSED_LOCK:
         cache = fd.__dict__.setdefault("_fused_ctx", {})
         if key in cache:
@@ -508,7 +509,7 @@ def _new_fused_context(fd, pd, batch_size, dev):
                   blur_ksize=fd.ctx.cfg.blur_ksize or 31, blur_sigma=fd.ctx.cfg.blur_sigma,
                   hold=fd.ctx.cfg.hold_frames, hold_iou_pct=fd.ctx.cfg.hold_iou_pct or 30,
                   hold_motion=fd.ctx.hold_motion, mask=fd.ctx.mask, mask_grow=fd.ctx.mask_grow,
-                  tiles=fd.ctx.tiles, tile_overlap=fd.ctx.tile_overlap)
+                  tiles=fd.ctx.tiles, tile_overlap=fd.ctx.tile_overlap, cells=fd.ctx.cells)
     ctx.load_weights(_lib.VD_NET_RETINAFACE, fd.state_dict)
     ctx.load_weights(_lib.VD_NET_YOLOV8N, pd.state_dict)
     return ctx
@@ -535,6 +536,12 @@ def _mask_matches(ctx, mask, mask_grow):
     """The context's blurring calls shape their lists exactly so (no cfg fields: the Context
     keeps the setting)."""
     return (ctx.mask, ctx.mask_grow) == (mask, mask_grow)
+
+
+def _cells_matches(ctx, cells):
+    """The context's blurring calls scale their strength exactly so (no cfg field: the Context
+    keeps the setting)."""
+    return ctx.cells == cells
 
 
 def _tiles_matches(ctx, tiles, tile_overlap):
@@ -578,7 +585,7 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
                          loader=None, saver=None, mosaic_plates=False, mosaic_level=8, num_workers=6,
                          gpu_codec="auto", jpeg_quality=95, shard="auto", group=None, records=None,
                          blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30,
-                         hold_motion=False, mask="rect", mask_grow=0, tiles=(1, 1), tile_overlap=20):
+                         hold_motion=False, mask="rect", mask_grow=0, tiles=(1, 1), tile_overlap=20, cells=0):
     """combine_detect.py:183-277. Returns (total_processed, total_faces, total_plates).
 
     gpu_codec ("auto" | True | False): with vdmi detectors, no custom loader/saver and
@@ -599,6 +606,13 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     with "ellipse", only the ellipse inscribed in the grown box is hidden. As with blur, the
     one-call path needs a face detector built with the same settings (Retinaface(mask=...,
     mask_grow=...)); otherwise the boxes are shaped and blurred by the per-group launches.
+
+    cells (0 | 2..64): box-scaled strength (include/vdmi.h at vd_cells, Context(cells=...)): every
+    box is hidden with at most `cells` cells along its longer side -- pixelation takes its level
+    per box, and blur="gaussian" becomes the scaled smooth blur (vd_smooth) in place of the
+    fixed kernel. As with mask, the one-call path needs a face detector built with the same
+    setting (Retinaface(cells=...)); otherwise the per-group launches apply it. 0 (the default)
+    changes nothing.
 
     tiles ((rows, cols), each 1..4) / tile_overlap (0..50 percent): tiled face detection
     (include/vdmi.h at vd_tiles, Context(tiles=..., tile_overlap=...)): every frame goes through
@@ -652,6 +666,7 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     hold, hold_iou_pct = _lib.check_hold(hold, hold_iou_pct, hold_motion)
     mask, mask_grow = _lib.check_mask(mask, mask_grow)
     tiles, tile_overlap = _lib.check_tiles(tiles, tile_overlap)
+    cells = _lib.check_cells(cells)
     fctx = getattr(face_detector, "ctx", None)
     if not (_tiles_matches(fctx, tiles, tile_overlap) if hasattr(fctx, "tiles") else tiles == (1, 1)):
         raise ValueError("tiles needs the vdmi Retinaface built with the same setting "
@@ -666,10 +681,11 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     fused = (_is_vdmi_pair(face_detector, plate_detector) and mosaic_level == face_detector.ctx.cfg.mosaic_level
              and _blur_matches(face_detector.ctx.cfg, blur, blur_ksize, blur_sigma)
              and _hold_matches(face_detector.ctx, hold, hold_iou_pct, hold_motion)
-             and _mask_matches(face_detector.ctx, mask, mask_grow))
+             and _mask_matches(face_detector.ctx, mask, mask_grow)
+             and _cells_matches(face_detector.ctx, cells))
     if hold and not fused:
         raise ValueError("hold > 0 needs the vdmi Retinaface / YOLO drop-ins and a face detector built with the "
-                         "same mosaic_level, blur, mask and hold settings (Retinaface(hold=..., hold_iou_pct=..., hold_motion=...)); "
+                         "same mosaic_level, blur, mask, cells and hold settings (Retinaface(hold=..., hold_iou_pct=..., hold_motion=...)); "
                          "other detectors call Context.hold themselves")
     all_jpeg = all(p.lower().endswith((".jpg", ".jpeg")) for p in image_paths)
     codec = fused and gpu_codec and (gpu_codec is True or (not custom_io and all_jpeg))
@@ -679,7 +695,7 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
                mosaic_level=mosaic_level, num_workers=num_workers, fused=fused, codec=codec,
                jpeg_quality=jpeg_quality, logger=logger,
                blur=(blur, int(blur_ksize), float(blur_sigma)), hold=hold, hold_warm=warm_frames,
-               mask=(mask, mask_grow))
+               mask=(mask, mask_grow), cells=cells)
     want_rec = records is not None or mode == "ranks"
     if mode == "ranks":
         res, rec = _rank_shard(sorted(image_paths), group, run)
@@ -745,7 +761,7 @@ def _local(paths, first, device, want_rec, run, slot=0, warm=()):
         else:
             res = _threaded_batches(batches, run["output_dir"], fd, run["plate_detector"], run["loader"],
                                     run["saver"], run["mosaic_plates"], run["mosaic_level"], io, run["logger"],
-                                    sink, ids, run["blur"], run["mask"])
+                                    sink, ids, run["blur"], run["mask"], run["cells"])
     finally:
         io.shutdown(wait=True)
     if sink is not None and sink.device.type == "cuda":
@@ -964,7 +980,8 @@ def _gpu_codec_batches(batches, output_dir, face_detector, plate_detector, batch
 
 
 def _threaded_batches(batches, output_dir, face_detector, plate_detector, loader, saver, mosaic_plates,
-                      mosaic_level, io, logger, sink=None, ids=None, blur=("pixelate", 31, 0.0), mask=("rect", 0)):
+                      mosaic_level, io, logger, sink=None, ids=None, blur=("pixelate", 31, 0.0), mask=("rect", 0),
+                      cells=0):
     """Generic detectors: the reference's two-thread face || plate submission, then
     one batched mosaic launch per same-size group."""
     total = faces = plates = 0
@@ -997,7 +1014,7 @@ def _threaded_batches(batches, output_dir, face_detector, plate_detector, loader
             plates += len(plate_boxes)
         if sink is not None:
             sink.add_lists([ids[f][0] for f in files], [ids[f][1] for f in files], fl, pl)
-        processed = _mosaic_grouped(batch_images, per_frame, mosaic_level, blur, mask)
+        processed = _mosaic_grouped(batch_images, per_frame, mosaic_level, blur, mask, cells)
         for path, img in zip(files, processed):
             out = os.path.join(output_dir, f"processed_{os.path.basename(path)}")
             save_futs.append(io.submit(saver, img, out))
@@ -1006,19 +1023,22 @@ def _threaded_batches(batches, output_dir, face_detector, plate_detector, loader
     return total, faces, plates
 
 
-def _mosaic_grouped(images, boxes, level, blur=("pixelate", 31, 0.0), mask=("rect", 0)):
-    """One mosaic (or Gaussian blur) launch per same-size group of frames."""
+def _mosaic_grouped(images, boxes, level, blur=("pixelate", 31, 0.0), mask=("rect", 0), cells=0):
+    """One mosaic (or Gaussian blur; with cells on, smooth blur) launch per same-size group of frames."""
     out = [None] * len(images)
     groups = {}
     for i, im in enumerate(images):
         groups.setdefault(im.shape, []).append(i)
     for idx in groups.values():
-        if blur[0] == "gaussian":
+        if blur[0] == "gaussian" and cells:
+            res = smooth_frames(np.stack([images[i] for i in idx]), [boxes[i] for i in idx], level, cells,
+                                mask=mask[0], mask_grow=mask[1])
+        elif blur[0] == "gaussian":
             res = blur_frames(np.stack([images[i] for i in idx]), [boxes[i] for i in idx], blur[1], blur[2],
                               mask=mask[0], mask_grow=mask[1])
         else:
             res = mosaic_frames(np.stack([images[i] for i in idx]), [boxes[i] for i in idx], level,
-                                mask=mask[0], mask_grow=mask[1])
+                                mask=mask[0], mask_grow=mask[1], cells=cells)
         for k, i in enumerate(idx):
             out[i] = res[k]
     return out
