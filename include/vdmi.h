@@ -24,6 +24,8 @@
  *                                   (frames from convert_video_to_frames :279-476)
  *   vd_hold / vd_hold_reset / vd_hold_motion / vd_read_held: boxes held across frames (cfg.hold_frames; no
  *                                   reference equivalent: the reference treats every frame alone)
+ *   vd_lead / vd_process_lead / vd_lead_lists / vd_read_lead / vd_lead_pending: boxes blurred before their
+ *                                   first detection (look-ahead hold; no reference equivalent)
  *   vd_mask / vd_mask_boxes: where the blur lies (a margin around every box, an elliptical mask inside it;
  *                                   no reference equivalent: the reference blurs the detector's rectangle)
  *   vd_cells / vd_smooth / vd_cell_level: blur strength that follows the box size (at most N cells across a
@@ -311,6 +313,82 @@ int vd_hold_motion(vd_ctx* ctx, int mode);
  * VD_ERR_STATE with hold_frames == 0 or before the first holding call. */
 int vd_read_held(vd_ctx* ctx, int n, vd_boxes* out);
 
+/* ---- look-ahead hold: a face is blurred before its first detection ----------------
+ * The box hold looks backwards only: a person walking towards the camera is first detected in
+ * some frame t0, and frames t0-1, t0-2, .. show the face in the clear. A context has a lead
+ * setting (J, motion): J in [0, VD_LEAD_MAX], motion VD_HOLD_MOTION_OFF or
+ * VD_HOLD_MOTION_LINEAR. J == 0 (the default) is off: no launch, no memory, every byte as
+ * before. P is cfg.hold_iou_pct (0 -> 30, whether or not hold_frames is set). For a stream
+ * S = D_0 .. D_{T-1} of h x w frames -- T counts the frames between two stream ends; a stream
+ * ends at a flush or a reset -- with clip, match and D_t as in the box hold:
+ *   A_t      ("lead list") is H_{T-1-t} of the reversed stream D_{T-1} .. D_0 under the hold
+ *            definition with K = J and the same P, h, w. Written out: for a = 1..J (t + a < T)
+ *            and, within each a, in the order of D_{t+a}: box b of D_{t+a}, unclipped as
+ *            stored, iff it is non-empty after clipping and matches NO box of D_t, ..,
+ *            D_{t+a-1}; every candidate is judged on its own; a box that is empty after
+ *            clipping is never led;
+ *   motion   membership, order and ages are the same; only the coordinates change. The
+ *            predecessor of c = clip(b) is sought in D_{t+a+1} by the rules of vd_hold_motion
+ *            (best exact IoU among the matches, ties to the lowest index, none if that frame
+ *            does not exist); the stored box is the hull of b and q = c + a * (c - clip(p)):
+ *            it stretches backwards along the way the face came. Needs h, w <= 32768;
+ *   delay    = J + (motion ? 1 : 0): frame t can be emitted once D_{t+delay} is known, or the
+ *            stream has ended;
+ *   B_t      = D_t ++ H_t ++ A_t, the list frame t is blurred with; H_t is the hold list exactly
+ *            as above, empty when hold_frames == 0. The order matters (pixelation: box j reads
+ *            box j-1; smooth blur: ties to the lower index) and is fixed as written. Mask
+ *            growth, cells and the ellipse restore act on B_t as they act on D_t ++ H_t.
+ * Detection outputs (faces, plates, vd_read_boxes, vd_read_held) and the hold history are
+ * untouched. The result does not depend on how the stream is cut into calls, calls of fewer
+ * than `delay` frames and of one frame included.
+ *
+ * What the library keeps between calls: the last `delay` input frames in a device ring of its
+ * own, allocated on first use (no caller pointer is retained past a call), those frames' D
+ * lists, and their already merged D ++ H rows (H_t depends only on the past, so it is final
+ * when frame t is pushed). One list launch per lead call (lead.hip, timing family 3); the
+ * merged rows hold (K + 1 + J) x (face + plate keep capacity) boxes per frame, so no box is
+ * ever dropped; the pixel ring is updated by device-to-device copies on the context stream
+ * (family 4). DESIGN.md gives the bytes.
+ *
+ * vd_lead: the setting. Bad J, bad motion, or motion with J == 0: VD_ERR_ARG. A change while
+ * frames are pending: VD_ERR_STATE; the setting the context already has changes nothing.
+ * vd_hold_motion and vd_tiles that would change state while frames are pending, vd_hold and
+ * vd_process while frames are pending: VD_ERR_STATE. vd_process with VD_PROC_MOSAIC in a
+ * context with J > 0 is VD_ERR_STATE (it would silently skip A_t); without the flag it stays
+ * legal while nothing is pending, which is how a shard warms up. vd_hold_reset is the explicit
+ * "abandon": it drops the pending frames unemitted and forgets both histories.
+ *
+ * vd_process_lead pushes n frames, frames [p, p + n) of the stream: detection and the hold
+ * step run exactly as in vd_process, faces / plates are the detections of the PUSHED frames,
+ * and the m oldest unemitted frames go to out[0..m), blurred with B_t. m = max(0, pending + n
+ * - delay), or pending + n with `flush` (the stream ends); *n_out = m, computed on the host
+ * from counts, so an all-device call stays asynchronous. Emitted frames come partly from the
+ * ring and partly from `in`; `out` (m frames of h * pitch bytes) must overlap neither `in` nor
+ * itself. n == 0 is allowed only with flush; `in` may then be NULL, and h, w, pitch are those
+ * of the pending frames. flags must include VD_PROC_MOSAIC (VD_ERR_ARG). Refusals, each checked
+ * before any state changes: m > out_cap VD_ERR_CAPACITY; J == 0 VD_ERR_STATE; (h, w, pitch)
+ * differing from the pending frames' VD_ERR_STATE (flush first); frames pending from
+ * vd_lead_lists VD_ERR_STATE; motion with h or w > 32768 VD_ERR_ARG.
+ *
+ * vd_lead_lists: the same step for callers with their own detectors, lists only, by the same
+ * kernel. det: the D lists of n consecutive h x w frames as for vd_hold (a host list with
+ * count[f] > cap: VD_ERR_CAPACITY); det may be NULL when n == 0 (flush). out (may be NULL;
+ * room for pending + n frames): B_t of the m emitted frames under the vd_boxes contract, label
+ * 0 for an own box, +a for a box held from frame t - a, -a for a box led from frame t + a;
+ * score and xyxy_f are not written. The hold history advances as by vd_hold. Frames pending
+ * from vd_process_lead: VD_ERR_STATE.
+ *
+ * vd_read_lead: the lists of emitted frames [0, n) of the last lead call under the vd_boxes
+ * contract, which 0: A_t alone (labels -a), 1: B_t; ordered on the context stream like
+ * vd_read_held. VD_ERR_STATE with J == 0 or when the last lead call emitted nothing. */
+#define VD_LEAD_MAX 8
+int vd_lead(vd_ctx* ctx, int frames, int motion);
+int vd_lead_pending(vd_ctx* ctx, int* frames);
+int vd_process_lead(vd_ctx* ctx, const uint8_t* in, int n, int h, int w, size_t pitch, int where, int flags,
+                    vd_boxes* faces, vd_boxes* plates, uint8_t* out, int out_cap, int flush, int* n_out);
+int vd_lead_lists(vd_ctx* ctx, const vd_boxes* det, int n, int h, int w, int flush, vd_boxes* out, int* n_out);
+int vd_read_lead(vd_ctx* ctx, int n, int which, vd_boxes* out);   /* which 0: A_t alone, 1: B_t */
+
 /* ---- mask shaping: grow the blurred boxes by a margin, blur ellipses -------------
  * A context has a mask setting (shape, g). The default (VD_MASK_RECT, 0) blurs the boxes as
  * stored: no extra launch, no extra memory. With any other setting every list L the context is
@@ -478,7 +556,7 @@ int vd_tiles_merge(vd_ctx* ctx, const vd_boxes* lists, int n, int h, int w, vd_b
  * reset. Families: 0 = RetinaFace conv (implicit GEMM / streaming 1x1), 1 = mosaic
  * output pass (or the Gaussian blur's launches, or the smooth blur's copy and box pass; the mask's restore pass, work 0: its bytes follow
  * from the boxes), 2 = letterbox (the tile letterbox too), 3 = post (decode/NMS, box hold,
- * mask grow, tile merge), 4 = other, 5 = YOLOv8n plate
+ * look-ahead lists, mask grow, tile merge), 4 = other (the look-ahead pixel ring's copies), 5 = YOLOv8n plate
  * conv, 6 = mosaic cell table (box prep + walked cell colours). */
 int vd_timing_enable(vd_ctx* ctx, int on);
 int vd_timing_reset(vd_ctx* ctx);

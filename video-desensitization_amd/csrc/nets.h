@@ -3,6 +3,7 @@
 #include "../../include/vdmi.h"
 #include "vd_common.h"
 #include "hold_state.h"
+#include "lead_state.h"
 
 #include <mutex>
 #include <string>
@@ -198,6 +199,15 @@ struct Ctx {
     void* hold_rows = nullptr; size_t hold_rows_bytes = 0;   // the last call's merged rows, ages, |B|, |D|
     HoldArgs hold_last{};                         // the last launch (merged-row pointers for the readers)
     int hold_n = 0;                               // frames of the last holding call
+    // look-ahead hold (lead.hip; vd_lead with J > 0 only, allocated by the first lead call)
+    LeadState lead;                               // J, motion, pending frames, current list buffer, pending geometry
+    int* lead_ring[2] = {nullptr, nullptr};       // ping-pong pending lists (vd_common.h LeadArgs gives the layout)
+    int lead_hcap = 0;                            // D-list capacity of a ring slot (boxes); rows: (K + 1) * lead_hcap
+    int lead_slots = 0;                           // slots the ring buffers were sized for (= delay)
+    void* lead_pix = nullptr; size_t lead_pix_bytes = 0;     // pixel ring: delay frames, oldest first
+    void* lead_rows = nullptr; size_t lead_rows_bytes = 0;   // the last call's merged rows, labels, |B|, |D|, |D ++ H|
+    LeadArgs lead_last{};                         // the last launch (merged-row pointers for the readers)
+    int lead_m = 0;                               // frames the last lead call emitted
     // mask shaping (mask.hip; vd_mask): nothing is allocated or launched while the setting is the default
     int mask_shape = VD_MASK_RECT, mask_grow = 0;
     void* mask_rows = nullptr; size_t mask_rows_bytes = 0;   // grown merged rows: [n][mcap][4], then counts [n]
@@ -326,6 +336,19 @@ struct Ctx {
     int hold_history(int hcap);                   // history buffers of at least this row capacity
     int hold_set_motion(int mode);                // vd_hold_motion: a change forgets the history and its buffers
     int hold_read(int n, int held_only, vd_boxes* out);   // merged rows -> caller lists (label = age)
+    // look-ahead hold: the list capacity a lead call over lists of cap0 + cap1 needs, the refusals shared by
+    // both lead calls, and the ring buffers (a narrower pair's pending slots are carried over)
+    int lead_need(int cap0, int cap1) const;
+    int lead_check(const char* who, int mode, int n, int h, int w, size_t pitch, int flush);
+    int lead_buffers(int need, size_t frame_bytes);
+    void lead_free();                             // vd_lead: a change of setting drops the rings
+    // One lead step: the n pushed frames' D lists (and, under hold, hold_last's rows) join the window, the m
+    // oldest frames get B = D ++ H ++ A in lead_last's merged rows, the rest becomes the next ring. With
+    // pixels (din / dout device pointers, dout for m frames) the emitted frames are blurred and the pixel
+    // ring is updated. The state advances only when everything was queued.
+    int lead_step(int mode, const uint8_t* din, uint8_t* dout, int n, int h, int w, size_t pitch, int flush,
+                  const int* cnt0, const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1);
+    int lead_read(int n, int which, vd_boxes* out);   // merged rows -> caller lists (label 0, +a, -a)
 };
 
 int vd_alloc_post(Ctx& ctx, PostScratch& ps, int A, int kcap);

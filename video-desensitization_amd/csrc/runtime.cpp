@@ -965,6 +965,8 @@ int Ctx::tiles_set(int rows, int cols, int overlap_pct) {
         return vd_set_error(VD_ERR_ARG, "vd_tiles: rows, cols in [1, %d] and overlap_pct in [0, 50] required (got %d, "
                             "%d, %d)", VD_TILES_MAX, rows, cols, overlap_pct);
     if (rows == tile_rows && cols == tile_cols && overlap_pct == tile_overlap) return VD_OK;
+    if (lead.pend)
+        return vd_set_error(VD_ERR_STATE, "vd_tiles: %d frames are pending in the look-ahead ring (flush first)", lead.pend);
     VD_CHECK_HIP(hipStreamSynchronize(stream));   // a queued launch may still read the merged rows
     tile_rows = rows; tile_cols = cols; tile_overlap = overlap_pct;
     tiles_kn = 0;
@@ -1286,10 +1288,188 @@ int Ctx::hold_read(int n, int held_only, vd_boxes* out) {
     return VD_OK;
 }
 
+// ---- look-ahead hold (lead.hip, lead_state.h) ----
+// The D-list capacity of a ring slot: the loaded detectors' complete keep lists, this call's
+// lists, and whatever the hold history already carries (its rows are copied into the ring).
+int Ctx::lead_need(int cap0, int cap1) const {
+    const int nets = (face.loaded ? face_rows_cap() : 0) + (plate.loaded ? plate.post.kcap : 0);
+    return std::max(std::max(std::max(cap0 + cap1, nets), hold.K ? hold_hcap : 0), 1);
+}
+
+// Everything a lead call can be refused for, before any state changes.
+int Ctx::lead_check(const char* who, int mode, int n, int h, int w, size_t pitch, int flush) {
+    if (!lead.J) return vd_set_error(VD_ERR_STATE, "%s: look-ahead hold is off (vd_lead)", who);
+    if (n < 0 || (n == 0 && !flush)) return vd_set_error(VD_ERR_ARG, "%s: n == 0 is allowed only with flush", who);
+    if (h <= 0 || w <= 0) return vd_set_error(VD_ERR_ARG, "%s: bad geometry %dx%d", who, w, h);
+    if ((lead.motion || (hold.K && hold.motion)) && (h > 32768 || w > 32768))
+        return vd_set_error(VD_ERR_ARG, "%s: motion needs frames of at most 32768 x 32768 (got %d x %d)", who, w, h);
+    if (lead.pend) {
+        if (lead.mode != mode)
+            return vd_set_error(VD_ERR_STATE, "%s: %d frames are pending from %s (flush first)", who, lead.pend,
+                                lead.mode == VD_LEAD_MODE_PIXELS ? "vd_process_lead" : "vd_lead_lists");
+        if (lead.h != h || lead.w != w || (mode == VD_LEAD_MODE_PIXELS && lead.pitch != (unsigned long long)pitch))
+            return vd_set_error(VD_ERR_STATE, "%s: %d frames of %dx%d (pitch %llu) are pending; got %dx%d (pitch %zu): "
+                                "flush first", who, lead.pend, lead.w, lead.h, lead.pitch, w, h, pitch);
+    }
+    return VD_OK;
+}
+
+void Ctx::lead_free() {
+    for (int i = 0; i < 2; ++i) {
+        if (lead_ring[i]) hipFree(lead_ring[i]);
+        lead_ring[i] = nullptr;
+    }
+    if (lead_pix) hipFree(lead_pix);
+    lead_pix = nullptr;
+    lead_pix_bytes = 0;
+    lead_hcap = lead_slots = 0;
+}
+
+// Ring buffers of at least `need` boxes per D list, and (frame_bytes > 0) the pixel ring. The
+// pending slots of a narrower pair are carried over (a wider vd_lead_lists list, or weights
+// loaded, while frames are pending); the slot count changes only while nothing is pending.
+int Ctx::lead_buffers(int need, size_t frame_bytes) {
+    const int slots = lead.delay();
+    if (need > lead_hcap || slots != lead_slots) {
+        const size_t rcap = (size_t)(hold.K + 1) * need;
+        if (rcap + (size_t)lead.J * need > 0x7fffffffu) return vd_set_error(VD_ERR_ARG, "lead: list capacity too large");
+        const size_t bytes = vd_lead_ring_ints(slots, need, (int)rcap) * 4;
+        int* nb[2] = {nullptr, nullptr};
+        for (int i = 0; i < 2; ++i)
+            if (hipMalloc((void**)&nb[i], bytes) != hipSuccess) {
+                if (nb[0]) hipFree(nb[0]);
+                return vd_set_error(VD_ERR_NOMEM, "hipMalloc(%zu) failed (lead ring)", bytes);
+            }
+        for (int i = 0; i < 2; ++i) VD_CHECK_HIP(hipMemsetAsync(nb[i], 0, VD_LEAD_RING_HEAD * 4, stream));
+        if (lead_ring[0] && lead.pend > 0 && slots == lead_slots) {
+            const int c = lead.cur, oh = lead_hcap;
+            const size_t orc = (size_t)(hold.K + 1) * oh, S = (size_t)slots;
+            const char* src = (const char*)lead_ring[c];
+            char* dst = (char*)nb[c];
+            const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
+            VD_CHECK_HIP(hipMemcpyAsync(dst, src, VD_LEAD_RING_HEAD * 4, dd, stream));
+            src += VD_LEAD_RING_HEAD * 4; dst += VD_LEAD_RING_HEAD * 4;
+            VD_CHECK_HIP(hipMemcpy2DAsync(dst, (size_t)need * 16, src, (size_t)oh * 16, (size_t)oh * 16, S, dd, stream));
+            src += S * oh * 16; dst += S * need * 16;
+            VD_CHECK_HIP(hipMemcpy2DAsync(dst, rcap * 16, src, orc * 16, orc * 16, S, dd, stream));
+            src += S * orc * 16; dst += S * rcap * 16;
+            VD_CHECK_HIP(hipMemcpy2DAsync(dst, rcap * 4, src, orc * 4, orc * 4, S, dd, stream));
+        }
+        VD_CHECK_HIP(hipStreamSynchronize(stream));   // a queued launch may still read the old ring
+        for (int i = 0; i < 2; ++i) {
+            if (lead_ring[i]) hipFree(lead_ring[i]);
+            lead_ring[i] = nb[i];
+        }
+        lead_hcap = need;
+        lead_slots = slots;
+    }
+    if (frame_bytes) {
+        if (lead_pix_bytes < frame_bytes * slots) VD_CHECK_HIP(hipStreamSynchronize(stream));
+        int rc = ensure_staging(&lead_pix, &lead_pix_bytes, frame_bytes * slots);
+        if (rc) return rc;
+    }
+    return VD_OK;
+}
+
+int Ctx::lead_step(int mode, const uint8_t* din, uint8_t* dout, int n, int h, int w, size_t pitch, int flush,
+                   const int* cnt0, const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1) {
+    const bool pixels = mode == VD_LEAD_MODE_PIXELS;
+    const size_t fb = pixels ? (size_t)h * pitch : 0;
+    int rc = lead_buffers(std::max(lead_hcap, lead_need(cnt0 ? cap0 : 0, cnt1 ? cap1 : 0)), fb);
+    if (rc) return rc;
+    const int delay = lead.delay(), pend = lead.pend, m = lead.emit(n, flush), keep = pend + n - m;
+    const int K = hold.K;
+    const size_t rcap = (size_t)(K + 1) * lead_hcap, mcap = rcap + (size_t)lead.J * lead_hcap;
+    const size_t nb = (size_t)std::max(m, 1) * mcap;
+    if ((rc = ensure_staging(&lead_rows, &lead_rows_bytes, nb * 16 + nb * 4 + (size_t)std::max(m, 1) * 12 + 64))) return rc;
+    LeadArgs a{};
+    a.n = n; a.m = m; a.pend = pend; a.keep = keep;
+    a.h = h; a.w = w; a.J = lead.J; a.P = hold.P; a.motion = lead.motion;
+    if (n > 0) {
+        a.cnt0 = cnt0; a.xy0 = xy0; a.cap0 = cnt0 ? cap0 : 0;
+        a.cnt1 = cnt1; a.xy1 = xy1; a.cap1 = cnt1 ? cap1 : 0;
+        if (K) {   // the hold launch of this call ran over exactly these n frames
+            a.dh_xy = hold_last.m_xy; a.dh_age = hold_last.m_age; a.dh_count = hold_last.m_count;
+            a.dh_own = hold_last.m_own; a.dh_cap = hold_last.mcap;
+        }
+    }
+    a.ring = lead_ring[lead.cur]; a.next = lead_ring[lead.cur ^ 1];
+    a.hcap = lead_hcap; a.rcap = (int)rcap; a.slots = delay;
+    a.m_xy = (int*)lead_rows; a.m_age = a.m_xy + nb * 4; a.m_count = a.m_age + nb;
+    a.m_own = a.m_count + std::max(m, 1); a.m_dh = a.m_own + std::max(m, 1);
+    a.mcap = (int)mcap;
+    if (m + keep > 0) {
+        t_begin(3, (double)(m + keep) * (K + 1 + lead.J) * 16);
+        hipError_t e = vd_launch_lead(a, stream);
+        t_end();
+        if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "lead: %s", hipGetErrorString(e));
+    }
+    if (pixels) {
+        // the emitted frames: the first min(m, pend) from the ring, the rest from `in`
+        const int mr = std::min(m, pend), mi = m - mr;
+        const bool gaussian = cfg.blur_mode == VD_BLUR_GAUSSIAN;
+        const int pass = !gaussian ? RECT_MOSAIC : (cells ? RECT_SMOOTH : RECT_GAUSSIAN);
+        if (mr && (rc = launch_shaped((const uint8_t*)lead_pix, dout, mr, h, w, pitch, a.m_count, a.m_xy, a.mcap, nullptr,
+                                      nullptr, 0, pass, cfg.mosaic_level, cfg.blur_ksize, cfg.blur_sigma, cells)))
+            return rc;
+        if (mi && (rc = launch_shaped(din, dout + (size_t)mr * fb, mi, h, w, pitch, a.m_count + mr,
+                                      a.m_xy + (size_t)mr * mcap * 4, a.mcap, nullptr, nullptr, 0, pass,
+                                      cfg.mosaic_level, cfg.blur_ksize, cfg.blur_sigma, cells)))
+            return rc;
+        // the pixel ring, in stream order behind the passes that read it: the frames that stay
+        // move down by the number that left (frame by frame, ascending: source and target of one
+        // copy never overlap), then this call's kept frames follow them
+        uint8_t* ring = (uint8_t*)lead_pix;
+        const int stay = pend - mr;
+        t_begin(4, (double)keep * fb * 2);
+        if (mr)
+            for (int j = 0; j < stay; ++j)
+                VD_CHECK_HIP(hipMemcpyAsync(ring + (size_t)j * fb, ring + (size_t)(j + mr) * fb, fb,
+                                            hipMemcpyDeviceToDevice, stream));
+        if (keep - stay > 0)
+            VD_CHECK_HIP(hipMemcpyAsync(ring + (size_t)stay * fb, din + (size_t)mi * fb, (size_t)(keep - stay) * fb,
+                                        hipMemcpyDeviceToDevice, stream));
+        t_end();
+    }
+    lead.end(n, flush, mode, h, w, pitch);
+    lead_last = a;
+    lead_m = m;
+    return VD_OK;
+}
+
+int Ctx::lead_read(int n, int which, vd_boxes* out) {
+    if (!lead.J) return vd_set_error(VD_ERR_STATE, "look-ahead hold is off (vd_lead)");
+    if (which != 0 && which != 1) return vd_set_error(VD_ERR_ARG, "which=%d (expected 0 = led boxes, 1 = blur list)", which);
+    if (!out || !out->count || !out->xyxy || out->cap <= 0) return vd_set_error(VD_ERR_ARG, "vd_boxes needs count, xyxy, cap>0");
+    if (n <= 0 || n > lead_m)
+        return vd_set_error(lead_m ? VD_ERR_ARG : VD_ERR_STATE, "n=%d outside [1, %d frames emitted by the last lead call]",
+                            n, lead_m);
+    BoxTargets t{};
+    if (out->where == VD_DEVICE) {
+        t.count = out->count; t.xyxy = out->xyxy; t.label = out->label;
+    } else {
+        int rc = host_box_staging(&stage_box, &stage_box_bytes, out->cap, n, t);
+        if (rc) return rc;
+        if (!out->label) t.label = nullptr;
+    }
+    HoldArgs g{};                                 // the hold's gather: rows, labels, counts and the offset to skip
+    g.m_xy = lead_last.m_xy; g.m_age = lead_last.m_age; g.m_count = lead_last.m_count;
+    g.m_own = lead_last.m_dh; g.mcap = lead_last.mcap;
+    hipError_t e = vd_launch_hold_gather(g, n, which == 0, t.count, t.xyxy, t.label, out->cap, stream);
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "lead gather: %s", hipGetErrorString(e));
+    if (out->where == VD_DEVICE) return VD_OK;
+    const size_t nbx = (size_t)n * out->cap;
+    VD_CHECK_HIP(hipMemcpyAsync(out->count, t.count, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+    VD_CHECK_HIP(hipMemcpyAsync(out->xyxy, t.xyxy, nbx * 16, hipMemcpyDeviceToHost, stream));
+    if (out->label) VD_CHECK_HIP(hipMemcpyAsync(out->label, t.label, nbx * 4, hipMemcpyDeviceToHost, stream));
+    VD_CHECK_HIP(hipStreamSynchronize(stream));
+    return VD_OK;
+}
+
 // ----------------------------------------------------------------------------
 // C-ABI
 // ----------------------------------------------------------------------------
-#define VD_ENTRY(ctx)                                                          \
+#define VD_ENTRY(ctx)                                                         \
     if (!(ctx)) return vd_set_error(VD_ERR_ARG, "null context");              \
     std::lock_guard<std::mutex> _lk((ctx)->mu);                                \
     if (hipSetDevice((ctx)->device) != hipSuccess)                             \
@@ -1387,6 +1567,8 @@ int vd_destroy(vd_ctx* h) {
     if (ctx->mosaic_table) hipFree(ctx->mosaic_table);
     if (ctx->blur_table) hipFree(ctx->blur_table);
     if (ctx->hold_rows) hipFree(ctx->hold_rows);
+    if (ctx->lead_rows) hipFree(ctx->lead_rows);
+    ctx->lead_free();
     if (ctx->mask_rows) hipFree(ctx->mask_rows);
     if (ctx->tiles_buf) hipFree(ctx->tiles_buf);
     if (ctx->tiles_in) hipFree(ctx->tiles_in);
@@ -1727,16 +1909,20 @@ int vd_smooth(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw,
     return VD_OK;
 }
 
-int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw, size_t pitch, int where,
-               int flags, vd_boxes* faces, vd_boxes* plates) {
-    Ctx* ctx = (Ctx*)h;
-    VD_ENTRY(ctx);
+// A vd_process_lead call's part in the body it shares with vd_process: the blur step becomes
+// the lead step (lists, blur of the m emitted frames, ring update).
+struct LeadCall {
+    int flush, m;
+};
+
+static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh, int fw, size_t pitch, int where,
+                        int flags, vd_boxes* faces, vd_boxes* plates, const LeadCall* lc) {
     const bool do_faces = flags & VD_PROC_FACES, do_plates = flags & VD_PROC_PLATES;
     const bool do_mosaic = flags & VD_PROC_MOSAIC, mosaic_plates = flags & VD_PROC_MOSAIC_PLATES;
     if (do_faces && !ctx->face.loaded) return vd_set_error(VD_ERR_STATE, "RetinaFace weights not loaded");
     if (do_plates && !ctx->plate.loaded) return vd_set_error(VD_ERR_STATE, "plate weights not loaded");
     if (mosaic_plates && !do_plates) return vd_set_error(VD_ERR_ARG, "MOSAIC_PLATES needs PLATES");
-    if (do_mosaic && !out) return vd_set_error(VD_ERR_ARG, "MOSAIC needs an output buffer");
+    if (!lc && do_mosaic && !out) return vd_set_error(VD_ERR_ARG, "MOSAIC needs an output buffer");
     if (do_mosaic && ctx->cells && ctx->cfg.blur_mode == VD_BLUR_GAUSSIAN &&
         (fh > 32768 || fw > 32768 || ctx->cfg.mosaic_level < 1 || ctx->cfg.mosaic_level > 32768))
         return vd_set_error(VD_ERR_ARG, "vd_process: the smooth blur (vd_cells) needs h, w <= 32768 and mosaic_level "
@@ -1751,7 +1937,7 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
     // previous box's output, :247-249): its one-launch output pass gathers cell colours
     // from `in` anywhere in the frame while other workgroups write `out`, so device
     // frames that overlap would race (host frames are staged in separate buffers)
-    if (do_mosaic && where == VD_DEVICE && vd_ranges_overlap(in, out, (size_t)n * fh * pitch))
+    if (!lc && do_mosaic && where == VD_DEVICE && vd_ranges_overlap(in, out, (size_t)n * fh * pitch))
         return vd_set_error(VD_ERR_ARG, "vd_process: MOSAIC is out-of-place (out must not overlap in)");
     BoxTargets tf{}, tp{};
     if (do_faces && (rc = ctx->box_targets(faces, n, tf))) return rc;
@@ -1834,6 +2020,8 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
     const int* c1 = mosaic_plates ? pp.kcount : nullptr;
     const int* x1 = mosaic_plates ? pp.kxyxy : nullptr;
     int k0 = do_faces ? (tiled ? tm.mcap : fp.kcap) : 0, k1 = mosaic_plates ? pp.kcap : 0;
+    const int* const dc0 = c0; const int* const dx0 = x0; const int* const dc1 = c1; const int* const dx1 = x1;
+    const int dk0 = k0, dk1 = k1;                  // D as detected: what the lead step matches on
     // box hold: the blur list becomes B = D ++ H in merged rows (one launch, after the lists
     // it reads are complete); the history is updated whether or not anything is blurred
     auto hold = [&]() -> int {
@@ -1846,11 +2034,18 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
     };
     auto mosaic = [&]() -> int {
         uint8_t* dout = out;
-        size_t bytes = (size_t)n * fh * pitch;
+        size_t bytes = (size_t)(lc ? lc->m : n) * fh * pitch;
         if (where == VD_HOST) {
-            int r = ctx->ensure_staging(&ctx->stage_out, &ctx->stage_out_bytes, bytes);
+            int r = ctx->ensure_staging(&ctx->stage_out, &ctx->stage_out_bytes, std::max(bytes, (size_t)1));
             if (r) return r;
             dout = (uint8_t*)ctx->stage_out;
+        }
+        if (lc) {   // look-ahead hold: B = D ++ H ++ A of the frames whose look-ahead is complete
+            int r = ctx->lead_step(VD_LEAD_MODE_PIXELS, d, dout, n, fh, fw, pitch, lc->flush, dc0, dx0, dk0, dc1, dx1, dk1);
+            if (r) return r;
+            if (where == VD_HOST && bytes)
+                VD_CHECK_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
+            return VD_OK;
         }
         // mask shaping (vd_mask) acts here, after the hold merge, on the list being blurred only
         // box-scaled strength (vd_cells): pixelation takes its level per box, the Gaussian mode
@@ -1877,6 +2072,149 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
     }
     if (where == VD_HOST) VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     return rc2;
+}
+
+int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw, size_t pitch, int where,
+               int flags, vd_boxes* faces, vd_boxes* plates) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (ctx->lead.J && (flags & VD_PROC_MOSAIC))
+        return vd_set_error(VD_ERR_STATE, "vd_process: MOSAIC in a look-ahead context would skip the led boxes "
+                            "(use vd_process_lead)");
+    if (ctx->lead.pend)
+        return vd_set_error(VD_ERR_STATE, "vd_process: %d frames are pending in the look-ahead ring (flush first)",
+                            ctx->lead.pend);
+    return process_impl(ctx, in, out, n, fh, fw, pitch, where, flags, faces, plates, nullptr);
+}
+
+int vd_lead(vd_ctx* h, int frames, int motion) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (frames < 0 || frames > VD_LEAD_MAX)
+        return vd_set_error(VD_ERR_ARG, "vd_lead: frames %d outside [0, %d]", frames, VD_LEAD_MAX);
+    if (motion != VD_HOLD_MOTION_OFF && motion != VD_HOLD_MOTION_LINEAR)
+        return vd_set_error(VD_ERR_ARG, "vd_lead: motion %d (expected 0 = off or 1 = linear)", motion);
+    if (motion && !frames) return vd_set_error(VD_ERR_ARG, "vd_lead: motion needs frames > 0");
+    if (frames == ctx->lead.J && motion == ctx->lead.motion) return VD_OK;
+    if (ctx->lead.pend)
+        return vd_set_error(VD_ERR_STATE, "vd_lead: %d frames are pending (flush first)", ctx->lead.pend);
+    VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // a queued launch may still read the rings
+    ctx->lead_free();
+    ctx->lead.J = frames;
+    ctx->lead.motion = motion;
+    ctx->lead.reset();
+    ctx->lead_m = 0;
+    return VD_OK;
+}
+
+int vd_lead_pending(vd_ctx* h, int* frames) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (!frames) return vd_set_error(VD_ERR_ARG, "vd_lead_pending: null argument");
+    *frames = ctx->lead.pend;
+    return VD_OK;
+}
+
+int vd_process_lead(vd_ctx* h, const uint8_t* in, int n, int fh, int fw, size_t pitch, int where, int flags,
+                    vd_boxes* faces, vd_boxes* plates, uint8_t* out, int out_cap, int flush, int* n_out) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    const char* who = "vd_process_lead";
+    if (!ctx->lead.J) return vd_set_error(VD_ERR_STATE, "%s: look-ahead hold is off (vd_lead)", who);
+    if (!(flags & VD_PROC_MOSAIC)) return vd_set_error(VD_ERR_ARG, "%s: flags must include VD_PROC_MOSAIC", who);
+    if (!(flags & VD_PROC_FACES) && !(flags & VD_PROC_MOSAIC_PLATES))
+        return vd_set_error(VD_ERR_ARG, "%s: nothing to blur (FACES or MOSAIC_PLATES needed)", who);
+    if (where != VD_HOST && where != VD_DEVICE) return vd_set_error(VD_ERR_ARG, "%s: bad where", who);
+    if (out_cap < 0 || (n > 0 && !in)) return vd_set_error(VD_ERR_ARG, "%s: null input / negative out_cap", who);
+    if (pitch < (size_t)(fw > 0 ? fw : 0) * 3) return vd_set_error(VD_ERR_ARG, "%s: bad pitch", who);
+    if (n == 0 && flush && !ctx->lead.pend) {      // the end of an empty stream
+        if (n_out) *n_out = 0;
+        return VD_OK;
+    }
+    int rc = ctx->lead_check(who, VD_LEAD_MODE_PIXELS, n, fh, fw, pitch, flush);
+    if (rc) return rc;
+    const int m = ctx->lead.emit(n, flush);
+    if (m > out_cap)
+        return vd_set_error(VD_ERR_CAPACITY, "%s: %d frames to emit, out holds %d", who, m, out_cap);
+    if (m > 0 && !out) return vd_set_error(VD_ERR_ARG, "%s: MOSAIC needs an output buffer", who);
+    const size_t fb = (size_t)fh * pitch;
+    if (where == VD_DEVICE && n > 0 && m > 0) {
+        const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
+        if (a < b + (size_t)m * fb && b < a + (size_t)n * fb)
+            return vd_set_error(VD_ERR_ARG, "%s: out must not overlap in", who);
+    }
+    const LeadCall lc{flush, m};
+    if (n > 0) {
+        rc = process_impl(ctx, in, out, n, fh, fw, pitch, where, flags, faces, plates, &lc);
+    } else {      // flush alone: the pending frames leave, no detection
+        uint8_t* dout = out;
+        const size_t bytes = (size_t)m * fb;
+        if (where == VD_HOST) {
+            if ((rc = ctx->ensure_staging(&ctx->stage_out, &ctx->stage_out_bytes, bytes))) return rc;
+            dout = (uint8_t*)ctx->stage_out;
+        }
+        rc = ctx->lead_step(VD_LEAD_MODE_PIXELS, nullptr, dout, 0, fh, fw, pitch, 1, nullptr, nullptr, 0, nullptr, nullptr, 0);
+        if (!rc && where == VD_HOST) {
+            VD_CHECK_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
+            VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+        }
+    }
+    if (rc) return rc;
+    if (n_out) *n_out = m;
+    return VD_OK;
+}
+
+int vd_lead_lists(vd_ctx* h, const vd_boxes* det, int n, int fh, int fw, int flush, vd_boxes* out, int* n_out) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    const char* who = "vd_lead_lists";
+    if (!ctx->lead.J) return vd_set_error(VD_ERR_STATE, "%s: look-ahead hold is off (vd_lead)", who);
+    if (n > 0 && (!det || !det->count || !det->xyxy || det->cap <= 0))
+        return vd_set_error(VD_ERR_ARG, "%s: null argument", who);
+    if (out && (!out->count || !out->xyxy || out->cap <= 0))
+        return vd_set_error(VD_ERR_ARG, "vd_boxes needs count, xyxy, cap>0");
+    if (n == 0 && flush && !ctx->lead.pend) {
+        if (n_out) *n_out = 0;
+        return VD_OK;
+    }
+    int rc = ctx->lead_check(who, VD_LEAD_MODE_LISTS, n, fh, fw, 0, flush);
+    if (rc) return rc;
+    const bool host = n > 0 && det->where == VD_HOST;
+    if (host)   // a count past cap means boxes the caller does not hold: never skip them silently
+        for (int i = 0; i < n; ++i)
+            if (det->count[i] > det->cap)
+                return vd_set_error(VD_ERR_CAPACITY, "%s: frame %d has count %d > cap %d", who, i, det->count[i], det->cap);
+    const int* cnt = n > 0 ? det->count : nullptr;
+    const int* xy = n > 0 ? det->xyxy : nullptr;
+    const bool staged = n > 0 && (host || ((uintptr_t)det->xyxy & 15));   // the kernels read boxes as 16-B vectors
+    if (staged) {
+        const size_t nb = (size_t)n * det->cap;
+        if ((rc = ctx->ensure_staging(&ctx->stage_box2, &ctx->stage_box2_bytes, n * 4 + nb * 16 + 16))) return rc;
+        int* dc = (int*)ctx->stage_box2;
+        int* dx = dc + ((n + 3) / 4) * 4;
+        const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+        VD_CHECK_HIP(hipMemcpyAsync(dc, det->count, (size_t)n * 4, kind, ctx->stream));
+        VD_CHECK_HIP(hipMemcpyAsync(dx, det->xyxy, nb * 16, kind, ctx->stream));
+        cnt = dc;
+        xy = dx;
+    }
+    const int m = ctx->lead.emit(n, flush);
+    // the hold step exactly as vd_hold runs it: H_t is final when frame t is pushed
+    if (n > 0 && ctx->hold.K && (rc = ctx->launch_hold(n, fh, fw, cnt, xy, det->cap, nullptr, nullptr, 0))) return rc;
+    if ((rc = ctx->lead_step(VD_LEAD_MODE_LISTS, nullptr, nullptr, n, fh, fw, 0, flush, cnt, xy, n > 0 ? det->cap : 0,
+                             nullptr, nullptr, 0)))
+        return rc;
+    if (out && m > 0 && (rc = ctx->lead_read(m, 1, out))) return rc;
+    if (staged && !(out && m > 0 && out->where == VD_HOST))
+        VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // staging reused by the next call
+    if (n_out) *n_out = m;
+    return VD_OK;
+}
+
+int vd_read_lead(vd_ctx* h, int n, int which, vd_boxes* out) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    return ctx->lead_read(n, which, out);
 }
 
 int vd_read_boxes(vd_ctx* h, int net, int n, vd_boxes* out) {
@@ -1915,6 +2253,9 @@ int vd_hold(vd_ctx* h, const vd_boxes* det, int n, int fh, int fw, vd_boxes* out
     Ctx* ctx = (Ctx*)h;
     VD_ENTRY(ctx);
     if (!ctx->hold.K) return vd_set_error(VD_ERR_STATE, "vd_hold: context created with hold_frames == 0");
+    if (ctx->lead.pend)
+        return vd_set_error(VD_ERR_STATE, "vd_hold: %d frames are pending in the look-ahead ring (flush first)",
+                            ctx->lead.pend);
     if (!det || !det->count || !det->xyxy || det->cap <= 0) return vd_set_error(VD_ERR_ARG, "vd_hold: null argument");
     if (n <= 0 || fh <= 0 || fw <= 0) return vd_set_error(VD_ERR_ARG, "vd_hold: bad geometry");
     if (out && (!out->count || !out->xyxy || out->cap <= 0))
@@ -1951,6 +2292,7 @@ int vd_hold_reset(vd_ctx* h) {
     Ctx* ctx = (Ctx*)h;
     VD_ENTRY(ctx);
     ctx->hold.reset();
+    ctx->lead.reset();                            // the pending frames are dropped unemitted
     return VD_OK;
 }
 
@@ -1963,6 +2305,9 @@ int vd_hold_motion(vd_ctx* h, int mode) {
         if (mode) return vd_set_error(VD_ERR_STATE, "vd_hold_motion: context created with hold_frames == 0");
         return VD_OK;
     }
+    if (mode != ctx->hold.motion && ctx->lead.pend)
+        return vd_set_error(VD_ERR_STATE, "vd_hold_motion: %d frames are pending in the look-ahead ring (flush first)",
+                            ctx->lead.pend);
     return ctx->hold_set_motion(mode);
 }
 

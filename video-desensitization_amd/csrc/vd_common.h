@@ -473,6 +473,28 @@ hipError_t vd_launch_hold(const HoldArgs& a, hipStream_t s);
 hipError_t vd_launch_hold_gather(const HoldArgs& a, int n, int held_only, int* out_count, int* out_xyxy,
                                  int* out_label, int cap, hipStream_t s);
 
+// Look-ahead hold (lead.hip): the emitted frames' blur lists B = D ++ H ++ A in merged rows, and
+// the next pending ring (lead_state.h: window W = ring ++ call). Lists 0 / 1 as the mosaic takes
+// them (list 1 optional); xy pointers 16-B aligned.
+// A ring buffer, in ints: D counts [slots], D ++ H counts [slots], |D| [slots], padded to
+// VD_LEAD_RING_HEAD; then D lists [slots][hcap][4], D ++ H rows [slots][rcap][4], ages [slots][rcap].
+#define VD_LEAD_RING_HEAD 32
+struct LeadArgs {
+    int n, m, pend, keep;                            // frames pushed, emitted, pending before / after (m + keep = pend + n)
+    int h, w, J, P, motion;                          // frame size, lead frames, hold_iou_pct, vd_lead motion mode
+    const int* cnt0; const int* xy0; int cap0;       // this call's D lists: list 0 (faces)
+    const int* cnt1; const int* xy1; int cap1;       //   list 1 (plates, optional)
+    const int* dh_xy; const int* dh_age;             // this call's D ++ H rows (the hold launch's merged rows);
+    const int* dh_count; const int* dh_own; int dh_cap;   //   dh_xy null without hold: the D lists are the rows
+    const int* ring; int* next;                      // pending ring read / written (the other buffer)
+    int hcap, rcap, slots;                           // D capacity (>= cap0 + cap1), D ++ H capacity, slots = delay
+    int* m_xy; int* m_age; int* m_count;             // merged rows [m][mcap][4], labels [m][mcap] (0, +a, -a), |B| [m]
+    int* m_own; int* m_dh;                           // |D| [m], |D ++ H| [m]
+    int mcap;                                        // rcap + J * hcap: the row plus J complete newer lists always fit
+};
+size_t vd_lead_ring_ints(int slots, int hcap, int rcap);
+hipError_t vd_launch_lead(const LeadArgs& a, hipStream_t s);
+
 // Mask shaping (mask.hip). Grow: lists 0 / 1 as the mosaic takes them (list 1 optional, scalar
 // reads: no alignment assumed) -> merged rows of grown boxes. Restore (VD_MASK_ELLIPSE, after the
 // rectangular pass on the same stream): pixels of the rows' clipped boxes outside every ellipse

@@ -23,6 +23,7 @@ VD_BLUR_PIXELATE, VD_BLUR_GAUSSIAN = 0, 1
 VD_BLUR_KSIZE_MAX = 127
 VD_HOLD_MAX = 8
 VD_HOLD_MOTION_OFF, VD_HOLD_MOTION_LINEAR = 0, 1
+VD_LEAD_MAX = 8
 VD_MASK_RECT, VD_MASK_ELLIPSE = 0, 1
 VD_MASK_GROW_MAX = 200
 VD_TILES_MAX = 4
@@ -93,6 +94,13 @@ SIGNATURES = [
     ("vd_hold_reset", _I, [_P]),
     ("vd_hold_motion", _I, [_P, _I]),
     ("vd_read_held", _I, [_P, _I, ctypes.POINTER(vd_boxes)]),
+    ("vd_lead", _I, [_P, _I, _I]),
+    ("vd_lead_pending", _I, [_P, ctypes.POINTER(_I)]),
+    ("vd_process_lead", _I, [_P, _P, _I, _I, _I, _SZ, _I, _I, ctypes.POINTER(vd_boxes), ctypes.POINTER(vd_boxes),
+                             _P, _I, _I, ctypes.POINTER(_I)]),
+    ("vd_lead_lists", _I, [_P, ctypes.POINTER(vd_boxes), _I, _I, _I, _I, ctypes.POINTER(vd_boxes),
+                           ctypes.POINTER(_I)]),
+    ("vd_read_lead", _I, [_P, _I, _I, ctypes.POINTER(vd_boxes)]),
     ("vd_mask", _I, [_P, _I, _I]),
     ("vd_mask_boxes", _I, [_P, ctypes.POINTER(vd_boxes), _I, ctypes.POINTER(vd_boxes)]),
     ("vd_cells", _I, [_P, _I]),
@@ -185,6 +193,17 @@ def check_hold(hold, hold_iou_pct, hold_motion=False):
     if hold_motion and not hold:
         raise ValueError("hold_motion moves held boxes: it needs hold > 0")
     return hold, pct
+
+
+def check_lead(lead, lead_motion=False):
+    """(lead frames as int, lead_motion as bool); ValueError outside [0, VD_LEAD_MAX], and for
+    lead_motion (vd_lead's linear mode) without lead."""
+    lead = int(lead)
+    if not 0 <= lead <= VD_LEAD_MAX:
+        raise ValueError(f"lead {lead}: expected 0 (off) .. {VD_LEAD_MAX} frames")
+    if lead_motion and not lead:
+        raise ValueError("lead_motion moves led boxes: it needs lead > 0")
+    return lead, bool(lead_motion)
 
 
 def check_mask(mask, mask_grow):

@@ -127,7 +127,8 @@ class Context:
                  nms_iou=0.4, max_boxes=256, mosaic_level=8, plate_nc=1, plate_conf=0.5, plate_iou=0.7,
                  plate_max_det=300, plate_imgsz=640, microbatch=0, microbatch_stage=2, options=None,
                  blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30,
-                 hold_motion=False, mask="rect", mask_grow=0, tiles=(1, 1), tile_overlap=20, cells=0):
+                 hold_motion=False, mask="rect", mask_grow=0, tiles=(1, 1), tile_overlap=20, cells=0,
+                 lead=0, lead_motion=False):
         """blur: what process() applies to the kept boxes: "pixelate" (the reference's
         INTER_NEAREST mosaic, the default) or "gaussian" (GaussianBlur(region, (blur_ksize,
         blur_ksize), blur_sigma) per clipped box, in list order; blur_ksize odd in [3, 127],
@@ -160,13 +161,23 @@ class Context:
         pixels -- pixelation picks its level per box (never below mosaic_level), and a
         "gaussian" context applies the scaled smooth blur (cell means interpolated across the
         box) in place of the fixed kernel, in process() and mosaic(); blur() stays the
-        fixed-kernel Gaussian. 0 (the default) is off. Kept as self.cells; set_cells() changes it."""
+        fixed-kernel Gaussian. 0 (the default) is off. Kept as self.cells; set_cells() changes it.
+        lead / lead_motion: look-ahead hold (include/vdmi.h at vd_lead): a box first seen in one
+        of the next `lead` frames (0 = off, at most 8) and matched by nothing before is already
+        blurred, so a face never shows in the clear because its first detection came late. The
+        definition is the box hold of the time-reversed stream under hold_iou_pct; lead_motion
+        stretches a led box backwards along the way the face came. Such a context blurs through
+        process_lead(), whose output lags its input by lead (+ 1 with lead_motion) frames, and
+        must be flushed at the end of a stream (lead_flush()); process() with the mosaic flag
+        is refused. Kept as self.lead / self.lead_motion (no vd_cfg fields); set_lead() changes
+        them."""
         if blur not in BLUR_MODES:
             raise ValueError(f"blur {blur!r}: expected 'pixelate' or 'gaussian'")
         hold, hold_iou_pct = _lib.check_hold(hold, hold_iou_pct, hold_motion)   # before the library is touched
         mask, mask_grow = _lib.check_mask(mask, mask_grow)
         tiles, tile_overlap = _lib.check_tiles(tiles, tile_overlap)
         cells = _lib.check_cells(cells)
+        lead, lead_motion = _lib.check_lead(lead, lead_motion)
         lib = _lib.load()
         cfg = _lib.default_cfg()
         cfg.input_h, cfg.input_w = int(input_shape[0]), int(input_shape[1])
@@ -192,6 +203,8 @@ class Context:
             cfg.blur_ksize, cfg.blur_sigma = int(blur_ksize), float(blur_sigma)
         if hold:                                        # off leaves the fields zero
             cfg.hold_frames, cfg.hold_iou_pct = hold, hold_iou_pct
+        elif lead:                                      # the lead list matches under the same threshold
+            cfg.hold_iou_pct = hold_iou_pct
         self.cfg = cfg
         self.device = int(device)
         self.precision = {_lib.VD_PREC_FP32: "fp32", _lib.VD_PREC_FP16: "fp16"}.get(cfg.precision, "bf16")
@@ -211,6 +224,9 @@ class Context:
         self.cells = 0
         if cells:
             self.set_cells(cells)
+        self.lead, self.lead_motion = 0, False
+        if lead:
+            self.set_lead(lead, lead_motion)
         for k, v in dict(options or {}).items():   # kernel-selection switches (vd_set_option)
             self.set_option(k, v)
 
@@ -519,6 +535,163 @@ class Context:
         s = boxes.struct()
         check(self._lib.vd_read_held(self._h, n, ctypes.byref(s)))
         return boxes
+
+    # -- look-ahead hold -----------------------------------------------------------
+    def set_lead(self, lead=0, lead_motion=False):
+        """vd_lead: blur a box up to `lead` frames (0 = off, at most 8) before its first
+        detection; lead_motion stretches a led box backwards along the way the face came. A
+        change while frames are pending is refused (lead_flush() or hold_reset() first)."""
+        lead, lead_motion = _lib.check_lead(lead, lead_motion)
+        mode = _lib.VD_HOLD_MOTION_LINEAR if lead_motion else _lib.VD_HOLD_MOTION_OFF
+        check(self._lib.vd_lead(self._h, lead, mode))
+        self.lead, self.lead_motion = lead, lead_motion
+
+    @property
+    def lead_delay(self):
+        """Frames the output lags the input by: lead, one more with lead_motion."""
+        return self.lead + (1 if self.lead_motion else 0)
+
+    def lead_pending(self):
+        """vd_lead_pending: frames pushed and not yet emitted."""
+        k = ctypes.c_int(0)
+        check(self._lib.vd_lead_pending(self._h, ctypes.byref(k)))
+        return k.value
+
+    def read_lead(self, n, which="lead", cap=None, out=None):
+        """The lists of emitted frames [0, n) of the last process_lead() / lead_lists() call
+        (vd_read_lead) as HostBoxes: which="lead" the led boxes A alone (label = -a: first seen
+        a frames later), "all" the blur list B = D ++ H ++ A (labels 0, +a, -a). cap defaults
+        to the largest count; out: a HostBoxes / DeviceBoxes to fill instead."""
+        if which not in ("lead", "all"):
+            raise ValueError(f"which {which!r}: expected 'lead' or 'all'")
+        w = 0 if which == "lead" else 1
+        if out is not None:
+            s = out.struct()
+            check(self._lib.vd_read_lead(self._h, n, w, ctypes.byref(s)))
+            return out
+        if n == 0:
+            return _lib.HostBoxes(0, 1)
+        if cap is None:
+            cnt = _lib.HostBoxes(n, 1)
+            s = cnt.struct()
+            check(self._lib.vd_read_lead(self._h, n, w, ctypes.byref(s)))
+            cap = max(1, int(cnt.count.max()))
+        boxes = _lib.HostBoxes(n, cap)
+        s = boxes.struct()
+        check(self._lib.vd_read_lead(self._h, n, w, ctypes.byref(s)))
+        return boxes
+
+    def lead_lists(self, boxes, h, w, flush=False, out=None):
+        """vd_lead_lists: the look-ahead step alone, for callers with their own detectors.
+        boxes: the detections of consecutive h x w frames -- a HostBoxes / DeviceBoxes, a list
+        with one int [k][4] array per frame, or None / [] (with flush=True: end the stream).
+        Returns the blur lists B = D ++ H ++ A of the m frames this call emits (m = max(0,
+        pending + n - delay), everything pending with flush) as HostBoxes of m rows, label 0 /
+        +a / -a; with out= (room for pending + n rows) that target is filled and (out, m)
+        returned."""
+        if boxes is None:
+            det, n = None, 0
+        elif isinstance(boxes, (_lib.HostBoxes, DeviceBoxes)):
+            det, n = boxes, boxes.n
+        else:
+            lists = [np.asarray(b, np.int32).reshape(-1, 4) for b in boxes]
+            n = len(lists)
+            det = _lib.HostBoxes(n, max(1, max((len(b) for b in lists), default=1))) if n else None
+            for i, b in enumerate(lists):
+                det.count[i] = len(b)
+                det.xyxy[i, :len(b)] = b
+        ds = det.struct() if det is not None else None
+        m = ctypes.c_int(0)
+        os_ = out.struct() if out is not None else None
+        check(self._lib.vd_lead_lists(self._h, ctypes.byref(ds) if ds is not None else None, n, int(h), int(w),
+                                      1 if flush else 0, ctypes.byref(os_) if os_ is not None else None,
+                                      ctypes.byref(m)))
+        if out is not None:
+            return out, m.value
+        return self.read_lead(m.value, "all")
+
+    def process_lead(self, frames, out=None, faces=None, plates=None, flags=None, flush=False):
+        """vd_process_lead: process() for a context with lead > 0. The frames are pushed --
+        faces / plates are THEIR detections -- and the frames whose look-ahead is complete come
+        back blurred with B = D ++ H ++ A: m = max(0, pending + n - delay) of them, everything
+        pending with flush=True (the stream ends). frames may be None with flush=True.
+        -> (out[:m], faces, plates); out defaults to a new array / tensor of pending + n
+        frames. Under tiling a long batch is split into consecutive calls as by process(), and
+        what they emit is concatenated."""
+        if flags is None:
+            flags = _lib.VD_PROC_FACES | _lib.VD_PROC_MOSAIC
+        if frames is None:
+            return self.lead_flush(out), faces, plates
+        p, n, h, w, pitch, where, keep = _frames_arg(frames)
+        room = self.lead_pending() + n
+        if out is None:
+            if where == _lib.VD_HOST:
+                out = np.empty((room, h, w, 3), np.uint8)
+            else:
+                import torch
+                out = torch.empty((room, h, w, 3), dtype=torch.uint8, device=frames.device)
+        if len(out) and tuple(out.shape[1:]) != (h, w, 3):
+            raise ValueError(f"out must be uint8 [m,{h},{w},3]")
+        step = self.frames_per_call()
+        if n > step and self.tiles != (1, 1) and flags & _lib.VD_PROC_FACES:
+            pf, pp, m = [], [], 0
+            for s0 in range(0, n, step):
+                k = min(step, n - s0)
+                o, f, q = self.process_lead(keep[s0:s0 + k], out[m:], _rows(faces, s0, k), _rows(plates, s0, k), flags,
+                                            flush and s0 + k == n)
+                m += len(o)
+                pf.append(f)
+                pp.append(q)
+            if faces is None:
+                faces = _host_concat(pf)
+            if plates is None and flags & _lib.VD_PROC_PLATES:
+                plates = _host_concat(pp)
+            return out[:m], faces, plates
+        fs = ps = None
+        auto_f, auto_p = faces is None, plates is None
+        if flags & _lib.VD_PROC_FACES:
+            faces = self._boxes(faces, n)
+            fs = faces.struct()
+        if flags & _lib.VD_PROC_PLATES:
+            plates = self._boxes(plates, n)
+            ps = plates.struct()
+        optr = out.data_ptr() if _is_torch(out) else ptr(out)
+        m = ctypes.c_int(0)
+        check(self._lib.vd_process_lead(self._h, p, n, h, w, pitch, where, flags,
+                                        ctypes.byref(fs) if fs is not None else None,
+                                        ctypes.byref(ps) if ps is not None else None,
+                                        optr, len(out), 1 if flush else 0, ctypes.byref(m)))
+        if flags & _lib.VD_PROC_FACES:
+            faces = self._complete(faces, _lib.VD_NET_RETINAFACE, auto_f)
+        if flags & _lib.VD_PROC_PLATES:
+            plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
+        self._lead_geom = (h, w, pitch, where, getattr(frames, "device", None))
+        return out[:m.value], faces, plates
+
+    def lead_flush(self, out=None):
+        """End the stream: the pending frames of process_lead() leave, blurred with what is
+        known (vd_process_lead with n == 0 and flush). -> out[:m]; out defaults to a new array
+        / tensor like the frames pushed last."""
+        pend = self.lead_pending()
+        geom = getattr(self, "_lead_geom", None)
+        if pend == 0 or geom is None:
+            if out is not None:
+                return out[:0]
+            return np.empty((0, 0, 0, 3), np.uint8)
+        h, w, pitch, where, dev = geom
+        if out is None:
+            if where == _lib.VD_HOST:
+                out = np.empty((pend, h, w, 3), np.uint8)
+            else:
+                import torch
+                out = torch.empty((pend, h, w, 3), dtype=torch.uint8, device=dev)
+        where = (_lib.VD_DEVICE if out.is_cuda else _lib.VD_HOST) if _is_torch(out) else _lib.VD_HOST
+        optr = out.data_ptr() if _is_torch(out) else ptr(out)
+        m = ctypes.c_int(0)
+        check(self._lib.vd_process_lead(self._h, None, 0, h, w, pitch, where,
+                                        _lib.VD_PROC_FACES | _lib.VD_PROC_MOSAIC, None, None, optr, len(out), 1,
+                                        ctypes.byref(m)))
+        return out[:m.value]
 
     # -- mask shaping -----------------------------------------------------------
     def set_mask(self, mask="rect", mask_grow=0):

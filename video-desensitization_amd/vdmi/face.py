@@ -109,6 +109,9 @@ class Retinaface(object):
         "tile_overlap": 20,
         # box-scaled strength of what the fused vd_process blurs: Context(cells=...)
         "cells": 0,
+        # look-ahead hold in the fused vd_process_lead: Context(lead=..., lead_motion=...)
+        "lead": 0,
+        "lead_motion": False,
     }
 
     @classmethod
@@ -124,6 +127,7 @@ class Retinaface(object):
         _lib.check_mask(self.mask, self.mask_grow)          # before a device or the library is touched
         self.tiles, self.tile_overlap = _lib.check_tiles(self.tiles, self.tile_overlap)
         self.cells = _lib.check_cells(self.cells)
+        self.lead, self.lead_motion = _lib.check_lead(self.lead, self.lead_motion)
         if not self.letterbox_image:
             raise ValueError("Batch inference requires letterbox_image=True for shape alignment.")  # face.py:80
         if not self.cuda:
@@ -142,7 +146,8 @@ class Retinaface(object):
                              blur_ksize=self.blur_ksize, blur_sigma=self.blur_sigma, hold=self.hold,
                              hold_iou_pct=self.hold_iou_pct, hold_motion=self.hold_motion,
                              mask=self.mask, mask_grow=self.mask_grow, tiles=self.tiles,
-                             tile_overlap=self.tile_overlap, cells=self.cells)
+                             tile_overlap=self.tile_overlap, cells=self.cells, lead=self.lead,
+                             lead_motion=self.lead_motion)
                      for d in self.device_ids]
         self.ctx = self.ctxs[0]
         self.generate()

@@ -83,6 +83,13 @@ class FramePipeline:
     reused only after its previous batch's download completed. ``run`` yields
     each batch's results one batch behind the submission, so the next batch's
     upload and compute are already queued while the caller consumes a result.
+
+    Lead-aware mode (a context with lead > 0, include/vdmi.h "look-ahead hold"): a batch
+    goes through vd_process_lead, the output slots have B + delay rows, a ticket carries m,
+    the number of frames the call emitted, and collect() returns those m frames -- the
+    oldest unemitted ones, not the batch's own -- beside the detections of the n pushed
+    frames. submit_filled(n, flush=True) ends the stream with the batch, flush() ends it
+    without one.
     """
 
     def __init__(self, ctx, h, w, max_batch=None, depth=2, plates=True, mosaic_plates=False, cap=256):
@@ -103,10 +110,12 @@ class FramePipeline:
         self.flags = flags
         self.plates = bool(plates)
         shp = (self.depth, self.B, self.h, self.w, 3)
+        self.lead = int(getattr(ctx, "lead", 0))             # look-ahead hold: the output lags by the delay
+        oshp = (self.depth, self.B + (ctx.lead_delay if self.lead else 0), self.h, self.w, 3)
         self.h_in = torch.empty(shp, dtype=torch.uint8).pin_memory()
-        self.h_out = torch.empty(shp, dtype=torch.uint8).pin_memory()
+        self.h_out = torch.empty(oshp, dtype=torch.uint8).pin_memory()
         self.d_in = torch.empty(shp, dtype=torch.uint8, device=dev)
-        self.d_out = torch.empty(shp, dtype=torch.uint8, device=dev)
+        self.d_out = torch.empty(oshp, dtype=torch.uint8, device=dev)
         from .context import DeviceBoxes
         self.d_faces = [DeviceBoxes(self.B, self.cap, dev) for _ in range(self.depth)]
         self.d_plates = [DeviceBoxes(self.B, self.cap, dev) for _ in range(self.depth)] if plates else None
@@ -142,14 +151,23 @@ class FramePipeline:
         self.next_input(frames.shape[0])[...] = frames   # host copy into pinned memory
         return self.submit_filled(frames.shape[0])
 
-    def submit_filled(self, n):
+    def flush(self):
+        """Lead-aware mode: end the stream without a batch; the ticket's frames are the
+        pending ones (collect() gives no detections for it)."""
+        k = self.seq % self.depth
+        if self.used[k]:
+            self.ev_down[k].synchronize()
+        return self.submit_filled(0, flush=True)
+
+    def submit_filled(self, n, flush=False):
         """Queue the batch already written into next_input(n)'s buffer."""
         torch = self.torch
         k = self.seq % self.depth
         with torch.cuda.stream(self.s_up):
             if self.used[k]:
                 self.s_up.wait_event(self.ev_comp[k])      # device input slot no longer read
-            self.d_in[k, :n].copy_(self.h_in[k, :n], non_blocking=True)
+            if n:
+                self.d_in[k, :n].copy_(self.h_in[k, :n], non_blocking=True)
             self.ev_up[k].record(self.s_up)
         self.s_comp.wait_event(self.ev_up[k])
         if self.used[k]:
@@ -158,28 +176,47 @@ class FramePipeline:
         plates = self.d_plates[k] if self.plates else None
         # several pipelines (one per frame size) may share the context: the compute
         # stream that waited on this slot's upload is the one the library must run on
+        # ... and the context's workspace (activations, box lists, the mosaic's cell table) is one
+        # per context, so this call must also wait for the call another pipeline queued last on
+        # ITS compute stream: without it the two run side by side and overwrite each other's tables
+        last = getattr(self.ctx, "_pipe_last", None)
+        if last is not None and last[0] != id(self):
+            self.s_comp.wait_event(last[1])
         self.ctx.set_stream(self.s_comp.cuda_stream)
-        self.ctx.process(self.d_in[k, :n], self.d_out[k, :n], faces=faces, plates=plates, flags=self.flags)
-        if self.held is not None:
+        m = n
+        if self.lead:
+            if n:
+                out, _, _ = self.ctx.process_lead(self.d_in[k, :n], self.d_out[k], faces=faces.view(0, n),
+                                                  plates=plates.view(0, n) if self.plates else None,
+                                                  flags=self.flags, flush=flush)
+            else:
+                out = self.ctx.lead_flush(self.d_out[k])
+            m = len(out)
+        else:
+            self.ctx.process(self.d_in[k, :n], self.d_out[k, :n], faces=faces, plates=plates, flags=self.flags)
+        if self.held is not None and n:
             self.held.append(_held_counts(self.ctx, n, self.dev))
         self.ev_comp[k].record(self.s_comp)
+        self.ctx._pipe_last = (id(self), self.ev_comp[k])
         with torch.cuda.stream(self.s_down):
             self.s_down.wait_event(self.ev_comp[k])
-            self.h_out[k, :n].copy_(self.d_out[k, :n], non_blocking=True)
-            self.h_cnt[k, 0, :n].copy_(faces.count[:n], non_blocking=True)
-            self.h_xy[k, 0, :n].copy_(faces.xyxy[:n], non_blocking=True)
-            if self.plates:
-                self.h_cnt[k, 1, :n].copy_(plates.count[:n], non_blocking=True)
-                self.h_xy[k, 1, :n].copy_(plates.xyxy[:n], non_blocking=True)
+            if m:
+                self.h_out[k, :m].copy_(self.d_out[k, :m], non_blocking=True)
+            if n:
+                self.h_cnt[k, 0, :n].copy_(faces.count[:n], non_blocking=True)
+                self.h_xy[k, 0, :n].copy_(faces.xyxy[:n], non_blocking=True)
+                if self.plates:
+                    self.h_cnt[k, 1, :n].copy_(plates.count[:n], non_blocking=True)
+                    self.h_xy[k, 1, :n].copy_(plates.xyxy[:n], non_blocking=True)
             self.ev_down[k].record(self.s_down)
         self.used[k] = True
         self.seq += 1
-        return (k, n)
+        return (k, n, m) if self.lead else (k, n)
 
     def record(self, ticket, sink, rows, frame_ids):
         """Pack a submitted batch's box records into `sink` (vdmi.dist.RecordSink) on the
         compute stream, right behind its vd_process (no host wait)."""
-        k, n = ticket
+        k, n = ticket[:2]
         sink.add(rows, frame_ids, self.d_faces[k].view(0, n),
                  self.d_plates[k].view(0, n) if self.plates else None, stream=self.s_comp)
 
@@ -187,12 +224,14 @@ class FramePipeline:
         """Wait for a submitted batch: (out uint8 [n,h,w,3], face_counts [n], face_boxes,
         plate_counts, plate_boxes). `out` and the boxes are views of pinned buffers,
         valid until `depth` more batches are submitted. Counts are complete (they may
-        exceed cap; the mosaic always covers every kept box)."""
-        k, n = ticket
+        exceed cap; the mosaic always covers every kept box). Lead-aware mode: `out` holds
+        the ticket's m emitted frames, the lists are those of its n pushed frames."""
+        k, n = ticket[:2]
+        m = ticket[2] if len(ticket) > 2 else n
         self.ev_down[k].synchronize()
         cnt = self.h_cnt[k].numpy()
         xy = self.h_xy[k].numpy()
-        out = self.h_out[k, :n].numpy()
+        out = self.h_out[k, :m].numpy()
         faces = [xy[0, j, :min(int(cnt[0, j]), self.cap)] for j in range(n)]
         plates = [xy[1, j, :min(int(cnt[1, j]), self.cap)] for j in range(n)] if self.plates else [None] * n
         return out, cnt[0, :n].copy(), faces, (cnt[1, :n].copy() if self.plates else None), plates
@@ -211,6 +250,9 @@ class FramePipeline:
 
     def close(self):
         self.torch.cuda.synchronize(self.dev)
+        last = getattr(self.ctx, "_pipe_last", None)
+        if last is not None and last[0] == id(self):
+            self.ctx._pipe_last = None
         self.ctx.set_stream(None)
 
 
@@ -486,7 +528,7 @@ def fused_context(face_detector, plate_detector, batch_size, device=None, slot=0
     # ... and so can its tiling (Context.set_tiles)
     # ... and its cells setting (Context.set_cells)
     key = (id(plate_detector), int(batch_size), dev, int(slot), fd.ctx.mask, fd.ctx.mask_grow, fd.ctx.tiles,
-           fd.ctx.tile_overlap, fd.ctx.cells)
+           fd.ctx.tile_overlap, fd.ctx.cells, fd.ctx.lead, fd.ctx.lead_motion)
     with _FUSED_LOCK:
         cache = fd.__dict__.setdefault("_fused_ctx", {})
         if key in cache:
@@ -509,7 +551,8 @@ def _new_fused_context(fd, pd, batch_size, dev):
                   blur_ksize=fd.ctx.cfg.blur_ksize or 31, blur_sigma=fd.ctx.cfg.blur_sigma,
                   hold=fd.ctx.cfg.hold_frames, hold_iou_pct=fd.ctx.cfg.hold_iou_pct or 30,
                   hold_motion=fd.ctx.hold_motion, mask=fd.ctx.mask, mask_grow=fd.ctx.mask_grow,
-                  tiles=fd.ctx.tiles, tile_overlap=fd.ctx.tile_overlap, cells=fd.ctx.cells)
+                  tiles=fd.ctx.tiles, tile_overlap=fd.ctx.tile_overlap, cells=fd.ctx.cells,
+                  lead=fd.ctx.lead, lead_motion=fd.ctx.lead_motion)
     ctx.load_weights(_lib.VD_NET_RETINAFACE, fd.state_dict)
     ctx.load_weights(_lib.VD_NET_YOLOV8N, pd.state_dict)
     return ctx
@@ -530,6 +573,13 @@ def _hold_matches(ctx, hold, pct, motion=False):
     cfg = ctx.cfg
     return cfg.hold_frames == hold and (hold == 0 or (cfg.hold_iou_pct == pct
                                                      and bool(ctx.hold_motion) == bool(motion)))
+
+
+def _lead_matches(ctx, lead, lead_motion, pct):
+    """The context's vd_process_lead leads boxes exactly so (lead 0: not at all; no cfg
+    fields: the Context keeps the setting; the match threshold is hold's)."""
+    return getattr(ctx, "lead", 0) == lead and (lead == 0 or (bool(ctx.lead_motion) == bool(lead_motion)
+                                                             and (ctx.cfg.hold_iou_pct or 30) == pct))
 
 
 def _mask_matches(ctx, mask, mask_grow):
@@ -585,7 +635,8 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
                          loader=None, saver=None, mosaic_plates=False, mosaic_level=8, num_workers=6,
                          gpu_codec="auto", jpeg_quality=95, shard="auto", group=None, records=None,
                          blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30,
-                         hold_motion=False, mask="rect", mask_grow=0, tiles=(1, 1), tile_overlap=20, cells=0):
+                         hold_motion=False, mask="rect", mask_grow=0, tiles=(1, 1), tile_overlap=20, cells=0,
+                         lead=0, lead_motion=False):
     """combine_detect.py:183-277. Returns (total_processed, total_faces, total_plates).
 
     gpu_codec ("auto" | True | False): with vdmi detectors, no custom loader/saver and
@@ -593,6 +644,20 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     read as bytes, decoded on the GPU (vd_jpeg_decode), processed and encoded on the
     GPU (vd_jpeg_encode, cv2.imwrite's quality 95 / 4:2:0), so pixels never cross
     PCIe; the bytes written equal libjpeg-turbo's encode of the processed frames.
+    With lead > 0 the GPU JPEG codec path is out of scope: "auto" takes the host-codec
+    fused path (frames loaded and saved on host threads), and gpu_codec=True raises
+    ValueError.
+
+    lead (0..8) / lead_motion: look-ahead hold (include/vdmi.h, Context(lead=...)): the
+    directory is one video -- the frames are processed in sorted order, as under hold --
+    and a box first detected in one of the next `lead` frames, and matched by nothing
+    before, is already blurred, matched under hold_iou_pct. Every input frame is written
+    exactly once: the output lags the input by lead (+ 1 with lead_motion) frames inside
+    the call, and the stream is flushed at the end of the list, before a change of frame
+    size, and when a batch is dropped. It needs the one-call path: a face detector built
+    with the same settings (Retinaface(lead=..., lead_motion=..., hold_iou_pct=...)), else
+    ValueError. A shard [b, e) also pushes the frames [e, e + delay) of the next shard --
+    which the next shard writes -- so sharded output equals one device's.
 
     blur ("pixelate" | "gaussian"): what hides each box: the reference's mosaic of
     `mosaic_level`, or GaussianBlur(region, (blur_ksize, blur_ksize), blur_sigma) of each
@@ -667,13 +732,16 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     mask, mask_grow = _lib.check_mask(mask, mask_grow)
     tiles, tile_overlap = _lib.check_tiles(tiles, tile_overlap)
     cells = _lib.check_cells(cells)
+    lead, lead_motion = _lib.check_lead(lead, lead_motion)
+    if lead and gpu_codec is True:
+        raise ValueError("lead > 0: the GPU JPEG codec path is out of scope (use gpu_codec='auto' or False)")
     fctx = getattr(face_detector, "ctx", None)
     if not (_tiles_matches(fctx, tiles, tile_overlap) if hasattr(fctx, "tiles") else tiles == (1, 1)):
         raise ValueError("tiles needs the vdmi Retinaface built with the same setting "
                          "(Retinaface(tiles=..., tile_overlap=...))")
     warm_frames = hold + 1 if hold_motion else hold      # the history's depth
     image_paths = [os.path.join(input_dir, f) for f in os.listdir(input_dir) if f.lower().endswith(IMAGE_EXT)]
-    if hold:
+    if hold or lead:
         image_paths.sort()               # the frames of one video, in order
     os.makedirs(output_dir, exist_ok=True)
     if blur not in ("pixelate", "gaussian"):
@@ -682,20 +750,25 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
              and _blur_matches(face_detector.ctx.cfg, blur, blur_ksize, blur_sigma)
              and _hold_matches(face_detector.ctx, hold, hold_iou_pct, hold_motion)
              and _mask_matches(face_detector.ctx, mask, mask_grow)
-             and _cells_matches(face_detector.ctx, cells))
+             and _cells_matches(face_detector.ctx, cells)
+             and _lead_matches(face_detector.ctx, lead, lead_motion, hold_iou_pct))
+    if lead and not fused:
+        raise ValueError("lead > 0 needs the vdmi Retinaface / YOLO drop-ins and a face detector built with the "
+                         "same mosaic_level, blur, mask, cells, hold and lead settings (Retinaface(lead=..., "
+                         "lead_motion=..., hold_iou_pct=...))")
     if hold and not fused:
         raise ValueError("hold > 0 needs the vdmi Retinaface / YOLO drop-ins and a face detector built with the "
                          "same mosaic_level, blur, mask, cells and hold settings (Retinaface(hold=..., hold_iou_pct=..., hold_motion=...)); "
                          "other detectors call Context.hold themselves")
     all_jpeg = all(p.lower().endswith((".jpg", ".jpeg")) for p in image_paths)
-    codec = fused and gpu_codec and (gpu_codec is True or (not custom_io and all_jpeg))
+    codec = fused and gpu_codec and not lead and (gpu_codec is True or (not custom_io and all_jpeg))
     mode = _shard_mode(shard, face_detector, group, fused)
     run = dict(output_dir=output_dir, face_detector=face_detector, plate_detector=plate_detector,
                batch_size=batch_size, loader=loader, saver=saver, mosaic_plates=mosaic_plates,
                mosaic_level=mosaic_level, num_workers=num_workers, fused=fused, codec=codec,
                jpeg_quality=jpeg_quality, logger=logger,
                blur=(blur, int(blur_ksize), float(blur_sigma)), hold=hold, hold_warm=warm_frames,
-               mask=(mask, mask_grow), cells=cells)
+               mask=(mask, mask_grow), cells=cells, lead=lead, lead_delay=lead + (1 if lead_motion else 0))
     want_rec = records is not None or mode == "ranks"
     if mode == "ranks":
         res, rec = _rank_shard(sorted(image_paths), group, run)
@@ -707,7 +780,8 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
         def one(i, span):
             b, e = span
             return _local(image_paths[b:e], b, devs[i], want_rec, run, slot=i,
-                          warm=image_paths[max(0, b - warm_frames):b])
+                          warm=image_paths[max(0, b - warm_frames):b],
+                          tail=image_paths[e:e + run["lead_delay"]], last=e >= len(image_paths))
         outs = run_on_devices(one, spans, devices=devs)
         res = tuple(sum(o[0][k] for o in outs) for k in range(3))
         rec = _concat_records([o[1] for o in outs]) if want_rec else None
@@ -730,14 +804,17 @@ def _concat_records(recs):
     return torch.cat([r.cpu() for r in recs if r is not None]) if any(r is not None for r in recs) else None
 
 
-def _local(paths, first, device, want_rec, run, slot=0, warm=()):
+def _local(paths, first, device, want_rec, run, slot=0, warm=(), tail=(), last=True):
     """One device over `paths` (global frame ids first, first + 1, ...): the fused /
     GPU-codec / generic loop; `slot`: the shard's own fused context (devices mode).
     warm (box hold): the frames just before the shard, run through the detectors first.
+    tail / last (look-ahead hold): the first `delay` frames after the shard, pushed behind it
+    so that its own last frames are emitted as one device would emit them; last: the shard
+    ends the list, so the stream is flushed instead.
     Returns ((processed, faces, plates), records or None)."""
     from .dist import RecordSink
     fd = run["face_detector"]
-    if run.get("hold"):
+    if run.get("hold") or run.get("lead"):
         _hold_start(fused_context(fd, run["plate_detector"], run["batch_size"], device, slot), warm,
                     run["loader"], run["mosaic_plates"])
     io = ThreadPoolExecutor(max_workers=run["num_workers"])
@@ -755,6 +832,10 @@ def _local(paths, first, device, want_rec, run, slot=0, warm=()):
             res = _gpu_codec_batches(batches, run["output_dir"], fd, run["plate_detector"], bs,
                                      run["mosaic_plates"], io, run["logger"], run["jpeg_quality"], device, sink, ids,
                                      slot)
+        elif run["fused"] and run.get("lead"):
+            res = _lead_batches(batches, run["output_dir"], fd, run["plate_detector"], bs, run["loader"],
+                                run["saver"], run["mosaic_plates"], io, run["logger"], device, sink, ids, slot,
+                                list(tail), last)
         elif run["fused"]:
             res = _fused_batches(batches, run["output_dir"], fd, run["plate_detector"], bs, run["loader"],
                                  run["saver"], run["mosaic_plates"], io, run["logger"], device, sink, ids, slot)
@@ -802,7 +883,10 @@ def _rank_shard(paths, group, run):
     err, res, rec = None, (0, 0, 0), None
     try:
         hold = run.get("hold_warm", 0)     # box hold: the frames before the shard warm it up
-        res, rec = _local(paths[b:e], b, None, True, run, **({"warm": paths[max(0, b - hold):b]} if hold else {}))
+        kw = {"warm": paths[max(0, b - hold):b]} if hold else {}
+        if run.get("lead"):              # look-ahead hold: the frames after the shard complete its last ones
+            kw.update(tail=paths[e:e + run["lead_delay"]], last=e >= n)
+        res, rec = _local(paths[b:e], b, None, True, run, **kw)
     except Exception as ex:      # noqa: BLE001 -- re-raised after the collective
         err = ex
     dev = f"cuda:{fd.device_ids[0]}" if run["fused"] else None
@@ -886,6 +970,113 @@ def _fused_batches(batches, output_dir, face_detector, plate_detector, batch_siz
         _save_all(save_futs, logger)
     if ctx.cfg.hold_frames:
         logger.info(f"box hold: {sum(_held_total(p.held) for p in pipes.values())} held boxes blurred")
+    return tuple(totals)
+
+
+def _lead_batches(batches, output_dir, face_detector, plate_detector, batch_size, loader, saver, mosaic_plates,
+                  io, logger, device=None, sink=None, ids=None, slot=0, tail=(), last=True):
+    """The vdmi path of a look-ahead context (lead > 0): one vd_process_lead per run of
+    consecutive frames of one size (FramePipeline in its lead-aware mode), the loading of the
+    next batch overlapped with it. The output lags the input, so the names of the frames
+    pushed and not yet written wait in a FIFO, popped by m after each collect. The stream is
+    flushed before a change of frame size and at the end of the list; a batch whose inference
+    fails is dropped (combine_detect.py:226-228) after the pending frames are flushed -- the
+    stream ends there -- so every other input frame is still written. tail: the frames after
+    a shard that is not the list's last, pushed so that the shard's last frames see what one
+    device would show them, and never written or counted here."""
+    totals = [0, 0, 0]
+    save_futs = []
+    ctx = fused_context(face_detector, plate_detector, batch_size, device, slot)
+    pipes = {}
+    fifo = []                            # paths pushed and not yet emitted, oldest first (None: a tail frame)
+    state = {"shape": None}              # frame size of the pending frames
+    load = lambda files: list(io.map(loader, files))
+
+    def write(out):
+        for img in out[:len(fifo)]:
+            path = fifo.pop(0)
+            if path is not None:
+                dst = os.path.join(output_dir, f"processed_{os.path.basename(path)}")
+                save_futs.append(io.submit(saver, img.copy(), dst))
+
+    def flush():
+        """The stream ends: the pending frames leave. If that fails too they are lost."""
+        if not fifo:
+            return
+        try:
+            pipe = pipes[state["shape"]]
+            out = pipe.collect(pipe.flush())[0]
+            write(out)
+        except Exception as e:
+            logger.error(f"flushing the pending frames failed: {e}")
+            ctx.hold_reset()
+            del fifo[:]
+        state["shape"] = None
+
+    def push(items, own=True, end=False):
+        shape = items[0][1].shape
+        if state["shape"] is not None and state["shape"] != shape:
+            flush()
+        if shape not in pipes:
+            pipes[shape] = FramePipeline(ctx, shape[0], shape[1], max_batch=batch_size, plates=True,
+                                         mosaic_plates=mosaic_plates)
+        pipe = pipes[shape]
+        files = [f for f, _ in items]
+        try:
+            pipe.next_input(len(items))[...] = np.stack([im for _, im in items])
+            ticket = pipe.submit_filled(len(items), flush=end)
+            if sink is not None and own:
+                pipe.record(ticket, sink, [ids[f][0] for f in files], [ids[f][1] for f in files])
+            out, fcnt, _, pcnt, _ = pipe.collect(ticket)
+        except Exception as e:           # combine_detect.py:226-228: the batch is dropped
+            logger.error(f"parallel inference failed: {e}")
+            flush()                      # what was pending is still written: the stream ends here
+            ctx.hold_reset()
+            return
+        state["shape"] = None if end else shape
+        fifo.extend(files if own else [None] * len(files))
+        write(out)
+        if own:
+            totals[0] += len(files)
+            totals[1] += int(fcnt.sum())
+            if mosaic_plates:            # the reference's tuple check discards plate boxes otherwise
+                totals[2] += int(pcnt.sum())
+
+    def runs(files, imgs):
+        """Consecutive frames of one size."""
+        i = 0
+        while i < len(files):
+            j = i + 1
+            while j < len(files) and imgs[j].shape == imgs[i].shape:
+                j += 1
+            yield list(zip(files[i:j], imgs[i:j]))
+            i = j
+
+    fut = io.submit(load, batches[0]) if batches else None
+    try:
+        for bi, files in enumerate(batches):
+            imgs = fut.result()          # a load failure propagates (combine_detect.py:209-211)
+            fut = io.submit(load, batches[bi + 1]) if bi + 1 < len(batches) else None
+            for items in runs(files, imgs):
+                push(items)
+        if fifo and not last and tail:
+            timgs = load(tail)
+            items = next(runs(list(tail), timgs))
+            if items[0][1].shape == state["shape"]:
+                # fewer than `delay` frames of this size follow: one device's stream ends with them
+                short = len(items) < ctx.lead_delay
+                for c in range(0, len(items), batch_size):
+                    push(items[c:c + batch_size], own=False, end=short and c + batch_size >= len(items))
+        if any(f is not None for f in fifo):
+            flush()
+        del fifo[:]                      # tail frames still pending belong to the next shard
+        ctx.hold_reset()
+    finally:
+        if fut is not None:
+            fut.cancel()
+        for pipe in pipes.values():
+            pipe.close()
+        _save_all(save_futs, logger)
     return tuple(totals)
 
 
