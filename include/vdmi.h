@@ -26,6 +26,8 @@
  *                                   reference equivalent: the reference treats every frame alone)
  *   vd_lead / vd_process_lead / vd_lead_lists / vd_read_lead / vd_lead_pending: boxes blurred before their
  *                                   first detection (look-ahead hold; no reference equivalent)
+ *   vd_rescue / vd_rescue_lists / vd_read_rescue: weak detections that continue a track stay in the blur
+ *                                   list (two thresholds; no reference equivalent)
  *   vd_mask / vd_mask_boxes: where the blur lies (a margin around every box, an elliptical mask inside it;
  *                                   no reference equivalent: the reference blurs the detector's rectangle)
  *   vd_cells / vd_smooth / vd_cell_level: blur strength that follows the box size (at most N cells across a
@@ -389,6 +391,66 @@ int vd_process_lead(vd_ctx* ctx, const uint8_t* in, int n, int h, int w, size_t 
 int vd_lead_lists(vd_ctx* ctx, const vd_boxes* det, int n, int h, int w, int flush, vd_boxes* out, int* n_out);
 int vd_read_lead(vd_ctx* ctx, int n, int which, vd_boxes* out);   /* which 0: A_t alone, 1: B_t */
 
+/* ---- weak-detection rescue: a weak box that continues a track stays hidden ----------
+ * A face that turns to profile, is half occluded or motion-blurred keeps firing the detector
+ * at a score below `confidence` for longer than any hold lasts. A context has a rescue setting
+ * (face_low, plate_low, S); face_low == 0 && plate_low == 0 (the default) is off: no launch, no
+ * memory, every byte as before. A net whose low is 0 has no weak boxes. S, the span, is in
+ * [1, VD_RESCUE_SPAN_MAX]. W = max(1, cfg.hold_frames), P = cfg.hold_iou_pct (0 -> 30); clip and
+ * match are exactly the box hold's. Per frame t of the context's stream (a stream ends at
+ * vd_hold_reset or at a change of (h, w), like the hold's):
+ *   keep list at low: faces: the candidate test is score >= face_low; plates: best > plate_low
+ *            (strict, as the plate test is). Everything else in post -- key, sort, NMS, max_det,
+ *            emit -- is unchanged. A greedy NMS in descending score order has the prefix property:
+ *            this list cut where the score falls below the net's threshold IS the keep list at
+ *            that threshold.
+ *   D_t      (strong) the prefix of that list that passes the net's own threshold (>= confidence,
+ *            > plate_conf): bit-identical to what the context returns with rescue off -- count,
+ *            xyxy, xyxy_f, score, label. The caller's faces / plates, vd_read_boxes, totals and
+ *            records stay D_t only.
+ *   W_t      (weak) the rest of the keep list, in NMS order, per net.
+ *   since    since(e) = 0 for e in D_t. For w in W_t with a non-empty c = clip(w): m(w) = the
+ *            minimum of since(e) + a over a = 1..W (t - a >= 0) and e in E_{t-a} with
+ *            match(c, clip(e)); w is rescued iff such an e exists and m(w) <= S, and then
+ *            since(w) = m(w): the frames since the strong sighting the chain goes back to.
+ *            Rescued boxes are references themselves, so a face that stays weak stays hidden for
+ *            at most S frames after its last strong detection. Faces and plates match each other
+ *            as in the hold. A weak box that is empty after clipping is never rescued; an empty
+ *            reference never matches.
+ *   R_t      the rescued faces in W_t's order, then the rescued plates (plates take part only
+ *            under VD_PROC_MOSAIC_PLATES, as for D_t).
+ *   E_t      = D_t ++ R_t. Wherever the hold, lead, mask, cells and blur definitions say D_t,
+ *            E_t stands: the history the hold keeps, H_t, A_t of vd_process_lead, and the
+ *            blurred list B_t = E_t ++ H_t ++ A_t.
+ * E_t depends on frames [t - S, t] only: a shard that first runs the S frames before its first
+ * frame (plus K, +1 with motion, for the hold) gets the unsharded E_t. The result does not depend
+ * on how the stream is cut into calls. One more timed step of family 3 per call (two kernel
+ * launches: phase 1 parallel over the frames against the strong boxes and the history, phase 2
+ * one workgroup walking the frames against the rescued boxes); the E rows hold face + plate keep
+ * capacity boxes per frame, so no box is ever dropped.
+ *
+ * vd_rescue: the setting. VD_ERR_ARG: a low that is NaN, < 0 or >= that net's threshold
+ * (cfg.confidence, cfg.plate_conf), S out of range. VD_ERR_STATE: a change while lead frames are
+ * pending; rescue on while tiling is on (and vd_tiles in a rescue context). Each is checked before
+ * any state changes. A change forgets the rescue history and the hold history as vd_hold_reset
+ * does (which clears the rescue history too); setting the value the context has changes nothing.
+ *
+ * vd_rescue_lists: the same step for callers with their own detectors, through the same kernels.
+ * strong / weak: D_t and W_t of n consecutive h x w frames, one list per frame (host or device;
+ * a host list with count > cap: VD_ERR_CAPACITY). out (may be NULL): E_t under the vd_boxes
+ * contract with label = since; score and xyxy_f are not written. It advances the rescue history
+ * only: the caller hands E to vd_hold. VD_ERR_STATE with rescue off.
+ *
+ * vd_read_rescue: lists of frames [0, n) of the last vd_process / vd_process_lead call's rescue
+ * step, of one net, under the vd_boxes contract. which 0: R_t of that net with label = since and
+ * the score; which 1: W_t of that net with label and score as in the keep list (of the net's last
+ * call of any kind). VD_ERR_STATE with rescue off, or for which 0 when that net took no part in
+ * the last rescue step. */
+#define VD_RESCUE_SPAN_MAX 255
+int vd_rescue(vd_ctx* ctx, float face_low, float plate_low, int span);
+int vd_rescue_lists(vd_ctx* ctx, const vd_boxes* strong, const vd_boxes* weak, int n, int h, int w, vd_boxes* out);
+int vd_read_rescue(vd_ctx* ctx, int net, int n, int which, vd_boxes* out);   /* which 0: R_t, 1: W_t */
+
 /* ---- mask shaping: grow the blurred boxes by a margin, blur ellipses -------------
  * A context has a mask setting (shape, g). The default (VD_MASK_RECT, 0) blurs the boxes as
  * stored: no extra launch, no extra memory. With any other setting every list L the context is
@@ -604,6 +666,11 @@ int vdt_bottleneck(vd_ctx* ctx, const float* x, int n, int h, int w, int cin,
 int vdt_jpeg_coefficients(const uint8_t* data, size_t size, int16_t* out, size_t cap_blocks, int* nblocks);
 int vdt_plate_raw(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w, size_t pitch,
                   int where, float* out, int* anchors);
+/* Plate post-processing only (score, threshold, DFL decode, NMS, scale_boxes) on caller-provided raw
+ * heads in vdt_plate_raw's layout, host f32 [n][64 + nc][A], for n frames of h x w whose canvas the
+ * context's last plate forward (vdt_plate_raw, vd_detect_plates, vd_process) was run for; honours the
+ * rescue setting like vdt_postprocess. VD_ERR_STATE before such a forward or for another canvas. */
+int vdt_plate_postprocess(vd_ctx* ctx, const float* raw, int n, int h, int w, vd_boxes* plates);
 /* ---- .record container I/O (host; replaces foreign/recordDeal.so) ------------
  * vd_record_extract_h265: every *.record* file of record_dir (sorted; CyberRT
  * segments) -> <out_dir>/hevcs/<camera>.h265 per camera topic

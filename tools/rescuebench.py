@@ -1,0 +1,154 @@
+"""Cost of the weak-detection rescue at the bench shape: Context.process on 64 synthetic 1080p
+frames already in HBM (fp32, faces | plates | mosaic, as bench.py's flagship step) with rescue off
+and with rescue=0.2 on this build, against the PARENT commit's build, all in one session.
+
+    python tools/rescuebench.py --parent-lib PATH/libvdmi.so [--steps 20] [--warmup 3]
+                                [--repeats 3] [--json profiles/rescue_1080p.json]
+
+Every measurement is a child process of its own (a fresh context, a fresh library: the parent's
+build is loaded through VDMI_LIB, where the entry points it lacks are simply not bound), the three
+kinds alternating, `--repeats` of each. Per run: ms/step in the steady state (warm-up first, then
+the steps ended by one synchronise), and the time and the number of timed steps of family 3 (post:
+decode, NMS, the list launches) from event-timed steps of their own. "off" adds no launch, so it
+should equal the parent within the spread of the repeated parent runs; "on" adds the larger
+candidate set of the sort and the NMS (everything above `low`) and the rescue step (two kernels),
+and the mosaic behind it blurs more boxes. The seeded weights fire all over the noise frames: about
+250 weak boxes per frame beside 30 strong ones, and about a third of them overlaps some blurred
+box of the frame before by 30 % and is rescued -- the heavy case: the blur list grows from 30 to
+110 boxes per frame, mostly overlapping ones, which takes the mosaic off its fast path (at most 32
+boxes per band). A video rescues a box only where a track goes on.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "video-desensitization_amd"))
+
+RESCUE_ENTRIES = ("vd_rescue", "vd_rescue_lists", "vd_read_rescue", "vdt_plate_postprocess")
+KINDS = ("parent", "off", "on")
+
+
+def one(a):
+    """A single measurement in this process: --one parent | off | on."""
+    import torch
+    from vdmi import _lib
+    if a.one == "parent":    # the parent's build does not export the rescue entry points
+        _lib.SIGNATURES = [s for s in _lib.SIGNATURES if s[0] not in RESCUE_ENTRIES]
+    import vdmi
+    from vdmi import synth, weights
+    B, H, W = a.batch, 1080, 1920
+    dev = torch.device("cuda:0")
+    frames = torch.from_numpy(synth.frames(B, H, W, seed=0)).to(dev)
+    flags = _lib.VD_PROC_FACES | _lib.VD_PROC_PLATES | _lib.VD_PROC_MOSAIC
+    kw = {"rescue": a.rescue, "rescue_span": a.span} if a.one == "on" else {}
+    ctx = vdmi.Context(device=0, precision="fp32", max_batch=B, **kw)
+    ctx.load_weights(_lib.VD_NET_RETINAFACE, weights.retinaface_state_dict(0))
+    ctx.load_weights(_lib.VD_NET_YOLOV8N, weights.yolov8n_state_dict(0))
+    faces, plates = vdmi.DeviceBoxes(B, 256, dev), vdmi.DeviceBoxes(B, 256, dev)
+    out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+
+    def step():
+        ctx.process(frames, out, faces=faces, plates=plates, flags=flags)
+    for _ in range(max(a.warmup, 1)):
+        step()
+    ctx.sync()
+    t0 = time.perf_counter()
+    for _ in range(a.steps):
+        step()
+    ctx.sync()
+    ms = (time.perf_counter() - t0) * 1e3 / a.steps
+    r = {"ms_per_step": round(ms, 3), "frames_per_s": round(B / ms * 1e3, 1),
+         "faces_per_frame": float(faces.count.float().mean().item())}
+    if a.one == "on":
+        r["weak_per_frame"] = float(ctx.read_rescue(0, B, "weak", cap=1).count.mean())
+        r["rescued_per_frame"] = float(ctx.read_rescue(0, B, "rescued", cap=1).count.mean())
+    ctx.timing(True)         # events around every launch slow the step: steps of their own
+    ctx.timing_reset()
+    for _ in range(a.post_steps):
+        step()
+    t, launches, _ = ctx.timing_read(_lib.FAM_POST)
+    r["post_ms_per_step"] = round(t / a.post_steps, 4)
+    r["post_steps_per_step"] = launches / a.post_steps
+    # every family's event-timed sum (conv, mosaic, letterbox, post, other, plate conv, mosaic cells): where
+    # the rest of a difference lies (the families overlap on their streams, so the sums exceed the step)
+    r["family_ms_per_step"] = [round(ctx.timing_read(f)[0] / a.post_steps, 4) for f in range(7)]
+    ctx.timing(False)
+    ctx.close()
+    print("RESCUEBENCH " + json.dumps(r), flush=True)
+
+
+def child(a, which):
+    env = dict(os.environ)
+    if which == "parent":
+        env["VDMI_LIB"] = os.path.abspath(a.parent_lib)
+    else:
+        env.pop("VDMI_LIB", None)
+    cmd = [sys.executable, os.path.abspath(__file__), "--one", which, "--steps", str(a.steps), "--warmup",
+           str(a.warmup), "--batch", str(a.batch), "--rescue", str(a.rescue), "--span", str(a.span),
+           "--post-steps", str(a.post_steps)]
+    p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=a.child_timeout)
+    if p.returncode != 0:
+        raise RuntimeError(f"{which} run failed ({p.returncode}):\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
+    for line in p.stdout.splitlines():
+        if line.startswith("RESCUEBENCH "):
+            return json.loads(line[len("RESCUEBENCH "):])
+    raise RuntimeError(f"{which} run printed no result:\n{p.stdout[-2000:]}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent-lib", help="libvdmi.so built from the parent commit")
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--rescue", type=float, default=0.2)
+    ap.add_argument("--span", type=int, default=60)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--post-steps", type=int, default=5, help="event-timed steps behind the family figures")
+    ap.add_argument("--child-timeout", type=int, default=240)
+    ap.add_argument("--one", choices=KINDS, help="(internal) one measurement in this process")
+    ap.add_argument("--json", help="also write the result line to this file")
+    a = ap.parse_args()
+    if a.one:
+        return one(a)
+    if not a.parent_lib or not os.path.exists(a.parent_lib):
+        ap.error("--parent-lib: the parent commit's libvdmi.so is needed for the comparison")
+    runs = {k: [] for k in KINDS}
+    for _ in range(a.repeats):                   # parent, off, on, parent, off, on, ...
+        for which in KINDS:
+            runs[which].append(child(a, which))  # a failed child raises: nothing more is started
+    ms = {k: [r["ms_per_step"] for r in runs[k]] for k in KINDS}
+    post = {k: [r["post_ms_per_step"] for r in runs[k]] for k in KINDS}
+    mean = lambda v: round(sum(v) / len(v), 4)
+    res = {"what": f"weak-detection rescue: process with rescue off / rescue={a.rescue} (span {a.span}) vs the "
+                   "parent commit's build",
+           "machine": "one MI355X, the runs alternating in one session, a process each",
+           "batch": a.batch, "frame": [1080, 1920], "precision": "fp32", "steps": a.steps, "warmup": a.warmup,
+           "note": "noise frames, seeded weights: ~250 weak boxes per frame, about a third rescued (heavy case)",
+           "parent_ms_per_step": ms["parent"], "off_ms_per_step": ms["off"], "on_ms_per_step": ms["on"],
+           "parent_mean": mean(ms["parent"]), "off_mean": mean(ms["off"]), "on_mean": mean(ms["on"]),
+           "parent_spread_ms": round(max(ms["parent"]) - min(ms["parent"]), 3),
+           "off_minus_parent_ms": round(mean(ms["off"]) - mean(ms["parent"]), 3),
+           "on_minus_off_ms": round(mean(ms["on"]) - mean(ms["off"]), 3),
+           "parent_post_ms_per_step": post["parent"], "off_post_ms_per_step": post["off"],
+           "on_post_ms_per_step": post["on"],
+           "parent_post_mean": mean(post["parent"]), "off_post_mean": mean(post["off"]), "on_post_mean": mean(post["on"]),
+           "family_ms_per_step": {k: [mean([r["family_ms_per_step"][f] for r in runs[k]]) for f in range(7)]
+                                  for k in KINDS},
+           "parent_runs": runs["parent"], "off_runs": runs["off"], "on_runs": runs["on"]}
+    line = json.dumps(res)
+    print(line, flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -403,6 +403,7 @@ int vd_alloc_post(Ctx& c, PostScratch& ps, int A, int kcap) {
     if ((rc = c.dalloc((void**)&ps.supp, B * A))) return rc;
     ps.kcap = kcap;
     if ((rc = c.dalloc((void**)&ps.kcount, B * 4))) return rc;
+    if ((rc = c.dalloc((void**)&ps.kall, B * 4))) return rc;
     if ((rc = c.dalloc((void**)&ps.kxyxy, B * kcap * 16))) return rc;
     if ((rc = c.dalloc((void**)&ps.kxyxy_f, B * kcap * 16))) return rc;
     if ((rc = c.dalloc((void**)&ps.kscore, B * kcap * 4))) return rc;
@@ -413,6 +414,6 @@ int vd_alloc_post(Ctx& c, PostScratch& ps, int A, int kcap) {
 
 void vd_post_keep_args(PostScratch& ps, PostArgs& p, int n) {
     p.kcap = ps.kcap;
-    p.k_count = ps.kcount; p.k_xyxy = ps.kxyxy; p.k_xyxy_f = ps.kxyxy_f; p.k_score = ps.kscore; p.k_label = ps.klabel;
+    p.k_count = ps.kcount; p.k_all = ps.kall; p.k_xyxy = ps.kxyxy; p.k_xyxy_f = ps.kxyxy_f; p.k_score = ps.kscore; p.k_label = ps.klabel;
     ps.kn = n;
 }

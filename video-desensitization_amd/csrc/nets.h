@@ -109,6 +109,7 @@ struct PostScratch {   // per-net candidate / NMS scratch sized for max_batch x 
     // hands them out
     int kcap = 0;
     int* kcount = nullptr;
+    int* kall = nullptr;               // rescue: the whole keep counts (kcount: the strong prefix)
     int* kxyxy = nullptr;
     float* kxyxy_f = nullptr;
     float* kscore = nullptr;
@@ -208,6 +209,21 @@ struct Ctx {
     void* lead_rows = nullptr; size_t lead_rows_bytes = 0;   // the last call's merged rows, labels, |B|, |D|, |D ++ H|
     LeadArgs lead_last{};                         // the last launch (merged-row pointers for the readers)
     int lead_m = 0;                               // frames the last lead call emitted
+    // weak-detection rescue (rescue.hip; vd_rescue): off = both lows 0, no launch, no memory
+    float rescue_low[2] = {0.f, 0.f};             // face_low, plate_low (0: that net has no weak boxes)
+    int rescue_span = 0;                          // S
+    HoldState rescue_hs;                          // the history bookkeeping of hold_state.h with K = W = max(1, hold_frames)
+    int* rescue_hist[2] = {nullptr, nullptr};     // ping-pong: [W] counts (64 B), [W][hcap][4] boxes, [W][hcap] since
+    int rescue_hcap = 0;
+    void* rescue_rows = nullptr; size_t rescue_rows_bytes = 0;   // the last call's E rows, since, |E|, |D|, |R faces|, w_since
+    RescueArgs rescue_last{};                     // the last launch (row pointers for the readers)
+    int rescue_n = 0;                             // frames of the last rescue call (0: none)
+    bool rescue_on() const { return rescue_low[0] > 0.f || rescue_low[1] > 0.f; }
+    int rescue_set(float face_low, float plate_low, int span);
+    int rescue_history(int hcap);                 // history buffers of at least this row capacity
+    // E = D ++ R of n consecutive frames into rescue_last's rows, and the history update (RescueArgs' lists)
+    int launch_rescue(int n, int h, int w, RescueArgs a);
+    int rescue_read_rows(int n, vd_boxes* out);   // E rows -> caller lists (label = since)
     // mask shaping (mask.hip; vd_mask): nothing is allocated or launched while the setting is the default
     int mask_shape = VD_MASK_RECT, mask_grow = 0;
     void* mask_rows = nullptr; size_t mask_rows_bytes = 0;   // grown merged rows: [n][mcap][4], then counts [n]

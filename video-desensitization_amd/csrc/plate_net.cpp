@@ -434,6 +434,7 @@ int vd_plate_post(Ctx& c, int n, int img_h, int img_w, const BoxTargets& t) {
     p.hstride = P.hstride;
     p.A = P.A; p.B = n; p.nc = P.nc;
     p.conf = c.cfg.plate_conf; p.iou = c.cfg.plate_iou; p.max_det = c.cfg.plate_max_det; p.max_wh = MAX_WH;
+    p.low = c.rescue_low[1]; p.low_on = c.rescue_low[1] > 0.f;   // rescue: the keep list at plate_low
     p.cand_keys = P.post.keys; p.cand_count = P.post.count;
     p.scratch_box = P.post.box; p.scratch_cls = P.post.cls; p.scratch_nbox = P.post.nbox;
     p.scratch_area = P.post.area; p.scratch_keys = P.post.sort; p.scratch_supp = P.post.supp;
@@ -483,4 +484,41 @@ extern "C" int vdt_plate_raw(vd_ctx* h, const uint8_t* frames, int n, int fh, in
                     out[((size_t)b * C + ch) * P.A + P.loff[l] + q] = buf[((size_t)b * px + q) * P.hstride + ch];
     }
     return VD_OK;
+}
+
+extern "C" int vdt_plate_postprocess(vd_ctx* h, const float* raw, int n, int fh, int fw, vd_boxes* plates) {
+    Ctx* ctx = (Ctx*)h;
+    if (!ctx) return vd_set_error(VD_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return vd_set_error(VD_ERR_HIP, "hipSetDevice");
+    PlateNet& P = ctx->plate;
+    if (!P.loaded) return vd_set_error(VD_ERR_STATE, "plate weights not loaded");
+    if (n <= 0 || n > ctx->cfg.max_batch || !raw || fh <= 0 || fw <= 0)
+        return vd_set_error(VD_ERR_ARG, "vdt_plate_postprocess args");
+    if (!P.A || !P.ch || !P.cw) return vd_set_error(VD_ERR_STATE, "vdt_plate_postprocess: no plate forward yet");
+    // the heads keep the geometry of the last forward: the canvas must be this frame size's
+    LetterboxArgs la;
+    int rc = vd_plate_letterbox_args(*ctx, nullptr, n, fh, fw, (size_t)fw * 3, &la);
+    if (rc) return rc;
+    if (la.oh != P.ch || la.ow != P.cw)
+        return vd_set_error(VD_ERR_STATE, "vdt_plate_postprocess: the last plate forward ran on a %d x %d canvas, "
+                            "%d x %d frames need %d x %d", P.cw, P.ch, fw, fh, la.ow, la.oh);
+    VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    const int C = 64 + P.nc;
+    for (int l = 0; l < 3; ++l) {
+        const Act& hd = P.head[l];
+        const size_t px = (size_t)P.lh[l] * P.lw[l];
+        std::vector<float> buf((size_t)n * px * P.hstride, 0.f);
+        for (int b = 0; b < n; ++b)
+            for (size_t q = 0; q < px; ++q)
+                for (int ch = 0; ch < C; ++ch)
+                    buf[((size_t)b * px + q) * P.hstride + ch] = raw[((size_t)b * C + ch) * P.A + P.loff[l] + q];
+        VD_CHECK_HIP(hipMemcpy(hd.p, buf.data(), buf.size() * 4, hipMemcpyHostToDevice));
+    }
+    BoxTargets t;
+    if ((rc = ctx->box_targets(plates, n, t))) return rc;
+    if ((rc = vd_plate_post(*ctx, n, fh, fw, t))) return rc;
+    rc = ctx->box_finish(plates, n, t);
+    VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    return rc;
 }

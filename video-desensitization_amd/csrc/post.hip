@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256) void face_candidates_kernel(PostArgs p) {
     const float e0 = vd_expf(VD_FSUB(c0, m));
     const float e1 = vd_expf(VD_FSUB(c1, m));
     const float s = VD_FDIV(e1, VD_FADD(e0, e1));
-    if (!(s >= p.conf)) return;
+    if (!(s >= (p.low_on ? p.low : p.conf))) return;     // rescue: the candidate test runs at `low`
     // decode (utils_bbox.py:49-59)
     const float* lo = h + 4 * k;
     const float4 pr = *(const float4*)(p.anchors + 4 * (size_t)a);
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256) void yolo_candidates_kernel(PostArgs p) {
         const float sg = VD_FDIV(1.0f, VD_FADD(1.0f, vd_expf(-h[64 + c])));
         if (sg > best) { best = sg; cls = c; }
     }
-    if (!(best > p.conf)) return;            // xc = amax > conf_thres (strict)
+    if (!(best > (p.low_on ? p.low : p.conf))) return;   // xc = amax > conf_thres (strict); rescue: at `low`
     // DFL: softmax over 16 bins per side, expectation with weights 0..15
     float d[4];
     for (int sd = 0; sd < 4; ++sd) {
@@ -120,7 +120,9 @@ __device__ __forceinline__ float clampf(float v, float lo, float hi) { return v 
 
 // Kept box `pos` of frame b: always into the library's complete keep list (what the
 // mosaic reads), and into the caller's arrays while pos < cap.
-__device__ void emit(const PostArgs& p, int b, int pos, float4 bx, uint64_t key) {
+// Rescue (p.low_on): the list holds weak boxes behind the strong ones; the caller's arrays take the
+// strong boxes only, and *nstrong_s ends as the length of the strong prefix.
+__device__ void emit(const PostArgs& p, int b, int pos, float4 bx, uint64_t key, int* nstrong_s) {
     const size_t k = (size_t)b * p.kcap + pos;
     float X1, Y1, X2, Y2;
     const int a = (int)(key & 0xFFFFFFFFu);
@@ -151,6 +153,10 @@ __device__ void emit(const PostArgs& p, int b, int pos, float4 bx, uint64_t key)
     ((float4*)p.k_xyxy_f)[k] = fb;
     p.k_score[k] = sc;
     p.k_label[k] = lab;
+    if (p.low_on) {
+        if (!(p.mode == POST_FACE ? sc >= p.conf : sc > p.conf)) return;
+        atomicMax(nstrong_s, pos + 1);
+    }
     if (pos >= p.cap || !p.out_xyxy) return;
     const size_t o = (size_t)b * p.cap + pos;
     // caller arrays: scalar stores (no alignment assumed)
@@ -165,7 +171,7 @@ __device__ void emit(const PostArgs& p, int b, int pos, float4 bx, uint64_t key)
 }
 
 __device__ void nms_frame(const PostArgs& p, int b, int M, uint64_t* keys, float4* box, float* area, uint8_t* supp,
-                          uint64_t* chunk_keep, int* nkept_s) {
+                          uint64_t* chunk_keep, int* nkept_s, int* nstrong_s) {
     const int tid = threadIdx.x;
     int P = 1;
     while (P < M) P <<= 1;
@@ -184,18 +190,21 @@ __device__ void nms_frame(const PostArgs& p, int b, int M, uint64_t* keys, float
         area[i] = VD_FMUL(VD_FSUB(bx.z, bx.x), VD_FSUB(bx.w, bx.y));
         supp[i] = 0;
     }
-    if (tid == 0) *nkept_s = 0;
+    if (tid == 0) { *nkept_s = 0; *nstrong_s = 0; }
     __syncthreads();
 
     const int limit = p.max_det > 0 ? min(p.max_det, p.kcap) : p.kcap;   // kcap >= every possible keep count
     vd_nms_greedy(M, box, area, supp, chunk_keep, nkept_s, p.iou, limit, [&](int pos, int j, const float4& bj) {
-        emit(p, b, pos, p.mode == POST_FACE ? bj : p.scratch_box[(size_t)b * p.A + (int)(keys[j] & 0xFFFFFFFFu)], keys[j]);
+        emit(p, b, pos, p.mode == POST_FACE ? bj : p.scratch_box[(size_t)b * p.A + (int)(keys[j] & 0xFFFFFFFFu)], keys[j], nstrong_s);
     });
     if (tid == 0) {
         const int n = *nkept_s;
         const int kept = p.max_det > 0 ? min(n, p.max_det) : n;   // i = i[:max_det]
-        p.k_count[b] = kept;
-        if (p.out_count) p.out_count[b] = kept;
+        // the list is in descending score order: the strong boxes are a prefix of it
+        const int own = p.low_on ? min(*nstrong_s, kept) : kept;
+        if (p.low_on) p.k_all[b] = kept;
+        p.k_count[b] = own;
+        if (p.out_count) p.out_count[b] = own;
     }
 }
 
@@ -205,21 +214,23 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(PostArgs p) {
     __shared__ float s_area[LDS_CAND];
     __shared__ uint8_t s_supp[LDS_CAND];
     __shared__ uint64_t s_chunk_keep;
-    __shared__ int s_nkept;
+    __shared__ int s_nkept, s_nstrong;
     const int b = blockIdx.x;
     const int M = p.cand_count[b];
     if (M == 0) {
         if (threadIdx.x == 0) {
             p.k_count[b] = 0;
+            if (p.low_on) p.k_all[b] = 0;
             if (p.out_count) p.out_count[b] = 0;
         }
         return;
     }
     if (M <= LDS_CAND)
-        nms_frame(p, b, M, s_keys, s_box, s_area, s_supp, &s_chunk_keep, &s_nkept);
+        nms_frame(p, b, M, s_keys, s_box, s_area, s_supp, &s_chunk_keep, &s_nkept, &s_nstrong);
     else
         nms_frame(p, b, M, p.scratch_keys + (size_t)b * p.sort_cap, p.scratch_nbox + (size_t)b * p.A,
-                  p.scratch_area + (size_t)b * p.A, p.scratch_supp + (size_t)b * p.A, &s_chunk_keep, &s_nkept);
+                  p.scratch_area + (size_t)b * p.A, p.scratch_supp + (size_t)b * p.A, &s_chunk_keep, &s_nkept,
+                  &s_nstrong);
 }
 
 }  // namespace

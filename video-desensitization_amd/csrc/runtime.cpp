@@ -924,6 +924,7 @@ int Ctx::face_post(int n, int img_h, int img_w, const BoxTargets& t, const TileG
     p.hstride = face.heads[0].c;
     p.anchors = face.anchors; p.A = face.A; p.B = n;
     p.conf = cfg.confidence; p.iou = cfg.nms_iou; p.max_det = 0;
+    p.low = rescue_low[0]; p.low_on = rescue_low[0] > 0.f;       // rescue: the keep list at face_low
     p.cand_keys = face.post.keys; p.cand_count = face.post.count;
     p.scratch_box = face.post.box; p.scratch_cls = face.post.cls; p.scratch_nbox = face.post.nbox;
     p.scratch_area = face.post.area; p.scratch_keys = face.post.sort; p.scratch_supp = face.post.supp;
@@ -965,6 +966,8 @@ int Ctx::tiles_set(int rows, int cols, int overlap_pct) {
         return vd_set_error(VD_ERR_ARG, "vd_tiles: rows, cols in [1, %d] and overlap_pct in [0, 50] required (got %d, "
                             "%d, %d)", VD_TILES_MAX, rows, cols, overlap_pct);
     if (rows == tile_rows && cols == tile_cols && overlap_pct == tile_overlap) return VD_OK;
+    if (rescue_on())
+        return vd_set_error(VD_ERR_STATE, "vd_tiles: tiled detection and rescue (vd_rescue) cannot be combined");
     if (lead.pend)
         return vd_set_error(VD_ERR_STATE, "vd_tiles: %d frames are pending in the look-ahead ring (flush first)", lead.pend);
     VD_CHECK_HIP(hipStreamSynchronize(stream));   // a queued launch may still read the merged rows
@@ -1466,10 +1469,125 @@ int Ctx::lead_read(int n, int which, vd_boxes* out) {
     return VD_OK;
 }
 
+// ---- weak-detection rescue (rescue.hip) ----
+int Ctx::rescue_set(float face_low, float plate_low, int span) {
+    if (!(face_low >= 0.f) || !(plate_low >= 0.f))   // NaN fails both comparisons
+        return vd_set_error(VD_ERR_ARG, "vd_rescue: thresholds must be >= 0 (got %g, %g)", (double)face_low, (double)plate_low);
+    if (face_low >= cfg.confidence || plate_low >= cfg.plate_conf)
+        return vd_set_error(VD_ERR_ARG, "vd_rescue: a low threshold must lie below the net's own (face %g < %g, plate "
+                            "%g < %g required)", (double)face_low, (double)cfg.confidence, (double)plate_low,
+                            (double)cfg.plate_conf);
+    if (span < 1 || span > VD_RESCUE_SPAN_MAX)
+        return vd_set_error(VD_ERR_ARG, "vd_rescue: span %d outside [1, %d]", span, VD_RESCUE_SPAN_MAX);
+    const bool on = face_low > 0.f || plate_low > 0.f;
+    if (!on && !rescue_on()) return VD_OK;
+    if (on && face_low == rescue_low[0] && plate_low == rescue_low[1] && span == rescue_span) return VD_OK;
+    if (lead.pend)
+        return vd_set_error(VD_ERR_STATE, "vd_rescue: %d frames are pending in the look-ahead ring (flush first)", lead.pend);
+    if (on && tiles_on())
+        return vd_set_error(VD_ERR_STATE, "vd_rescue: rescue and tiled detection (vd_tiles) cannot be combined");
+    VD_CHECK_HIP(hipStreamSynchronize(stream));   // a queued launch may still read the history
+    rescue_low[0] = face_low; rescue_low[1] = plate_low;
+    rescue_span = on ? span : 0;
+    rescue_hs.reset();
+    hold.reset();
+    lead.reset();
+    rescue_n = 0;
+    return VD_OK;
+}
+
+// History buffers of at least `hcap` boxes per slot; the valid slots of a smaller pair are carried over.
+int Ctx::rescue_history(int hcap) {
+    if (hcap <= rescue_hcap) return VD_OK;
+    const int W = rescue_hs.K;
+    const size_t bytes = 64 + (size_t)W * hcap * 20;
+    int* nb[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; ++i)
+        if (hipMalloc((void**)&nb[i], bytes) != hipSuccess) {
+            if (nb[0]) hipFree(nb[0]);
+            return vd_set_error(VD_ERR_NOMEM, "hipMalloc(%zu) failed (rescue history)", bytes);
+        }
+    for (int i = 0; i < 2; ++i) VD_CHECK_HIP(hipMemsetAsync(nb[i], 0, 64, stream));
+    if (rescue_hist[0] && rescue_hs.hn > 0) {
+        const int c = rescue_hs.cur;
+        const size_t oh = (size_t)rescue_hcap;
+        VD_CHECK_HIP(hipMemcpyAsync(nb[c], rescue_hist[c], (size_t)W * 4, hipMemcpyDeviceToDevice, stream));
+        VD_CHECK_HIP(hipMemcpy2DAsync((char*)nb[c] + 64, (size_t)hcap * 16, (const char*)rescue_hist[c] + 64, oh * 16,
+                                      oh * 16, W, hipMemcpyDeviceToDevice, stream));
+        VD_CHECK_HIP(hipMemcpy2DAsync((char*)nb[c] + 64 + (size_t)W * hcap * 16, (size_t)hcap * 4,
+                                      (const char*)rescue_hist[c] + 64 + (size_t)W * oh * 16, oh * 4, oh * 4, W,
+                                      hipMemcpyDeviceToDevice, stream));
+    }
+    VD_CHECK_HIP(hipStreamSynchronize(stream));
+    for (int i = 0; i < 2; ++i) {
+        if (rescue_hist[i]) hipFree(rescue_hist[i]);
+        rescue_hist[i] = nb[i];
+    }
+    rescue_hcap = hcap;
+    return VD_OK;
+}
+
+int Ctx::launch_rescue(int n, int h, int w, RescueArgs a) {
+    const int W = rescue_hs.K;
+    const size_t strong = (size_t)(a.cnt0 ? a.cap0 : 0) + (a.cnt1 ? a.cap1 : 0);
+    const size_t weak = a.split ? (size_t)(a.wcnt ? a.wcap : 0) : strong;
+    const size_t ecap = std::max(a.split ? strong + weak : strong, (size_t)1), wtot = std::max(weak, (size_t)1);
+    const size_t nets = (size_t)(face.loaded ? face.post.kcap : 0) + (plate.loaded ? plate.post.kcap : 0);
+    if (std::max(ecap, nets) > 0x3fffffffu) return vd_set_error(VD_ERR_ARG, "rescue: list capacity too large");
+    int rc = rescue_history((int)std::max(ecap, nets));
+    if (rc) return rc;
+    const size_t nb = (size_t)n * ecap;
+    if (rescue_rows_bytes < nb * 20 + (size_t)n * 12 + (size_t)n * wtot * 4 + 64)
+        VD_CHECK_HIP(hipStreamSynchronize(stream));   // a queued reader may still use the old rows
+    if ((rc = ensure_staging(&rescue_rows, &rescue_rows_bytes, nb * 20 + (size_t)n * 12 + (size_t)n * wtot * 4 + 64))) return rc;
+    rescue_hs.begin(h, w);
+    a.n = n; a.h = h; a.w = w; a.W = W; a.P = hold.P; a.S = rescue_span;
+    int* cur = rescue_hist[rescue_hs.cur];
+    int* nxt = rescue_hist[rescue_hs.cur ^ 1];
+    const size_t hx = (size_t)W * rescue_hcap * 4;
+    a.hist_cnt = cur; a.hist_xy = cur + 16; a.hist_since = cur + 16 + hx;
+    a.next_cnt = nxt; a.next_xy = nxt + 16; a.next_since = nxt + 16 + hx;
+    a.hcap = rescue_hcap; a.hn = rescue_hs.hn;
+    a.e_xy = (int*)rescue_rows; a.e_since = a.e_xy + nb * 4; a.e_count = a.e_since + nb; a.e_own = a.e_count + n;
+    a.e_nr0 = a.e_own + n; a.w_since = a.e_nr0 + n;
+    a.ecap = (int)ecap; a.wtot = (int)wtot;
+    t_begin(3, (double)n * (W + 1) * 16);
+    hipError_t e = vd_launch_rescue(a, stream);
+    t_end();
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "rescue: %s", hipGetErrorString(e));
+    rescue_hs.end(n);
+    rescue_last = a;
+    rescue_n = n;
+    return VD_OK;
+}
+
+int Ctx::rescue_read_rows(int n, vd_boxes* out) {
+    BoxTargets t{};
+    if (out->where == VD_DEVICE) {
+        t.count = out->count; t.xyxy = out->xyxy; t.label = out->label;
+    } else {
+        int rc = host_box_staging(&stage_box, &stage_box_bytes, out->cap, n, t);
+        if (rc) return rc;
+        if (!out->label) t.label = nullptr;
+    }
+    HoldArgs g{};                                 // the hold's gather: rows, labels (since), counts
+    g.m_xy = rescue_last.e_xy; g.m_age = rescue_last.e_since; g.m_count = rescue_last.e_count;
+    g.m_own = rescue_last.e_own; g.mcap = rescue_last.ecap;
+    hipError_t e = vd_launch_hold_gather(g, n, 0, t.count, t.xyxy, t.label, out->cap, stream);
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "rescue gather: %s", hipGetErrorString(e));
+    if (out->where == VD_DEVICE) return VD_OK;
+    const size_t nbx = (size_t)n * out->cap;
+    VD_CHECK_HIP(hipMemcpyAsync(out->count, t.count, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+    VD_CHECK_HIP(hipMemcpyAsync(out->xyxy, t.xyxy, nbx * 16, hipMemcpyDeviceToHost, stream));
+    if (out->label) VD_CHECK_HIP(hipMemcpyAsync(out->label, t.label, nbx * 4, hipMemcpyDeviceToHost, stream));
+    VD_CHECK_HIP(hipStreamSynchronize(stream));
+    return VD_OK;
+}
+
 // ----------------------------------------------------------------------------
 // C-ABI
 // ----------------------------------------------------------------------------
-#define VD_ENTRY(ctx)                                                         \
+#define VD_ENTRY(ctx)                                                        \
     if (!(ctx)) return vd_set_error(VD_ERR_ARG, "null context");              \
     std::lock_guard<std::mutex> _lk((ctx)->mu);                                \
     if (hipSetDevice((ctx)->device) != hipSuccess)                             \
@@ -1533,6 +1651,7 @@ int vd_create(const vd_cfg* cfg, int device, vd_ctx** out) {
     ctx->f16 = c.precision == VD_PREC_FP16;
     ctx->hold.K = c.hold_frames;
     ctx->hold.P = c.hold_iou_pct;
+    ctx->rescue_hs.K = std::max(1, c.hold_frames);   // the rescue window W
     if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) {
         delete ctx;
         return vd_set_error(VD_ERR_HIP, "hipStreamCreate failed");
@@ -1573,6 +1692,9 @@ int vd_destroy(vd_ctx* h) {
     if (ctx->tiles_buf) hipFree(ctx->tiles_buf);
     if (ctx->tiles_in) hipFree(ctx->tiles_in);
     for (int* p : ctx->hold_hist)
+        if (p) hipFree(p);
+    if (ctx->rescue_rows) hipFree(ctx->rescue_rows);
+    for (int* p : ctx->rescue_hist)
         if (p) hipFree(p);
     if (ctx->jpeg_dev) hipFree(ctx->jpeg_dev);
     if (ctx->jpeg_planes) hipFree(ctx->jpeg_planes);
@@ -2020,8 +2142,21 @@ static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh
     const int* c1 = mosaic_plates ? pp.kcount : nullptr;
     const int* x1 = mosaic_plates ? pp.kxyxy : nullptr;
     int k0 = do_faces ? (tiled ? tm.mcap : fp.kcap) : 0, k1 = mosaic_plates ? pp.kcap : 0;
-    const int* const dc0 = c0; const int* const dx0 = x0; const int* const dc1 = c1; const int* const dx1 = x1;
-    const int dk0 = k0, dk1 = k1;                  // D as detected: what the lead step matches on
+    const int* dc0 = c0; const int* dx0 = x0; const int* dc1 = c1; const int* dx1 = x1;
+    int dk0 = k0, dk1 = k1;                        // D as detected (rescue: E): what the lead step matches on
+    // weak-detection rescue: the lists become E = D ++ R in merged rows (one step, before the hold);
+    // the rescue history is updated whether or not anything is blurred
+    auto rescue = [&]() -> int {
+        if (!ctx->rescue_on() || (!c0 && !c1)) return VD_OK;
+        RescueArgs a{};
+        a.cnt0 = c0; a.xy0 = x0; a.cap0 = k0; a.all0 = c0 && ctx->rescue_low[0] > 0.f ? fp.kall : nullptr;
+        a.cnt1 = c1; a.xy1 = x1; a.cap1 = k1; a.all1 = c1 && ctx->rescue_low[1] > 0.f ? pp.kall : nullptr;
+        int r = ctx->launch_rescue(n, fh, fw, a);
+        if (r) return r;
+        dc0 = c0 = ctx->rescue_last.e_count; dx0 = x0 = ctx->rescue_last.e_xy; dk0 = k0 = ctx->rescue_last.ecap;
+        dc1 = dx1 = c1 = x1 = nullptr; dk1 = k1 = 0;
+        return VD_OK;
+    };
     // box hold: the blur list becomes B = D ++ H in merged rows (one launch, after the lists
     // it reads are complete); the history is updated whether or not anything is blurred
     auto hold = [&]() -> int {
@@ -2058,12 +2193,12 @@ static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh
         if (where == VD_HOST) VD_CHECK_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
         return VD_OK;
     };
-    if (mosaic_first && ((rc = hold()) || (rc = mosaic()))) return rc;
+    if (mosaic_first && ((rc = rescue()) || (rc = hold()) || (rc = mosaic()))) return rc;
     if (fork) {
         VD_CHECK_HIP(hipEventRecord(ctx->ev_join, plate_stream));
         VD_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
     }
-    if (!mosaic_first && ((rc = hold()) || (do_mosaic && (rc = mosaic())))) return rc;
+    if (!mosaic_first && ((rc = rescue()) || (rc = hold()) || (do_mosaic && (rc = mosaic())))) return rc;
     int rc2 = VD_OK;
     if (do_faces) rc2 = ctx->box_finish(faces, n, tf);
     if (do_plates) {
@@ -2292,6 +2427,7 @@ int vd_hold_reset(vd_ctx* h) {
     Ctx* ctx = (Ctx*)h;
     VD_ENTRY(ctx);
     ctx->hold.reset();
+    ctx->rescue_hs.reset();
     ctx->lead.reset();                            // the pending frames are dropped unemitted
     return VD_OK;
 }
@@ -2380,6 +2516,109 @@ int vd_read_held(vd_ctx* h, int n, vd_boxes* out) {
     Ctx* ctx = (Ctx*)h;
     VD_ENTRY(ctx);
     return ctx->hold_read(n, 1, out);
+}
+
+int vd_rescue(vd_ctx* h, float face_low, float plate_low, int span) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    return ctx->rescue_set(face_low, plate_low, span);
+}
+
+int vd_rescue_lists(vd_ctx* h, const vd_boxes* strong, const vd_boxes* weak, int n, int fh, int fw, vd_boxes* out) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    const char* who = "vd_rescue_lists";
+    if (!ctx->rescue_on()) return vd_set_error(VD_ERR_STATE, "%s: rescue is off (vd_rescue)", who);
+    if (ctx->lead.pend)
+        return vd_set_error(VD_ERR_STATE, "%s: %d frames are pending in the look-ahead ring (flush first)", who,
+                            ctx->lead.pend);
+    if (!strong || !strong->count || !strong->xyxy || strong->cap <= 0 || !weak || !weak->count || !weak->xyxy ||
+        weak->cap <= 0)
+        return vd_set_error(VD_ERR_ARG, "%s: null argument", who);
+    if (n <= 0 || fh <= 0 || fw <= 0) return vd_set_error(VD_ERR_ARG, "%s: bad geometry", who);
+    if (out && (!out->count || !out->xyxy || out->cap <= 0))
+        return vd_set_error(VD_ERR_ARG, "vd_boxes needs count, xyxy, cap>0");
+    const vd_boxes* in[2] = {strong, weak};
+    for (const vd_boxes* b : in)
+        if (b->where == VD_HOST)   // a count past cap means boxes the caller does not hold: never skip them silently
+            for (int i = 0; i < n; ++i)
+                if (b->count[i] > b->cap)
+                    return vd_set_error(VD_ERR_CAPACITY, "%s: frame %d has count %d > cap %d", who, i, b->count[i], b->cap);
+    // the kernels read boxes as 16-B vectors: host and unaligned device lists are staged
+    const int* cnt[2];
+    const int* xy[2];
+    bool staged = false;
+    size_t need = 0, off[2] = {0, 0};
+    for (int k = 0; k < 2; ++k) {
+        off[k] = need;
+        need += (size_t)((n + 3) / 4) * 16 + (size_t)n * in[k]->cap * 16;
+    }
+    int rc;
+    for (int k = 0; k < 2; ++k) {
+        cnt[k] = in[k]->count;
+        xy[k] = in[k]->xyxy;
+        const bool host = in[k]->where == VD_HOST;
+        if (!host && !((uintptr_t)in[k]->xyxy & 15)) continue;
+        if (!staged && (rc = ctx->ensure_staging(&ctx->stage_box2, &ctx->stage_box2_bytes, need + 16))) return rc;
+        staged = true;
+        int* dc = (int*)((char*)ctx->stage_box2 + off[k]);
+        int* dx = dc + ((n + 3) / 4) * 4;
+        const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+        VD_CHECK_HIP(hipMemcpyAsync(dc, in[k]->count, (size_t)n * 4, kind, ctx->stream));
+        VD_CHECK_HIP(hipMemcpyAsync(dx, in[k]->xyxy, (size_t)n * in[k]->cap * 16, kind, ctx->stream));
+        cnt[k] = dc;
+        xy[k] = dx;
+    }
+    RescueArgs a{};
+    a.split = 1;
+    a.cnt0 = cnt[0]; a.xy0 = xy[0]; a.cap0 = strong->cap;
+    a.wcnt = cnt[1]; a.wxy = xy[1]; a.wcap = weak->cap;
+    if ((rc = ctx->launch_rescue(n, fh, fw, a))) return rc;
+    if (out && (rc = ctx->rescue_read_rows(n, out))) return rc;
+    if (staged && !(out && out->where == VD_HOST))
+        VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // staging reused by the next call
+    return VD_OK;
+}
+
+int vd_read_rescue(vd_ctx* h, int net, int n, int which, vd_boxes* out) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (!ctx->rescue_on()) return vd_set_error(VD_ERR_STATE, "vd_read_rescue: rescue is off (vd_rescue)");
+    if (net != VD_NET_RETINAFACE && net != VD_NET_YOLOV8N) return vd_set_error(VD_ERR_ARG, "unknown net %d", net);
+    if (which != 0 && which != 1)
+        return vd_set_error(VD_ERR_ARG, "which=%d (expected 0 = rescued boxes, 1 = weak boxes)", which);
+    if (!out || !out->count || !out->xyxy || out->cap <= 0) return vd_set_error(VD_ERR_ARG, "vd_boxes needs count, xyxy, cap>0");
+    const RescueArgs& r = ctx->rescue_last;
+    const bool plate = net == VD_NET_YOLOV8N;
+    const PostScratch& ps = plate ? ctx->plate.post : ctx->face.post;
+    if (!ps.kcount) return vd_set_error(VD_ERR_STATE, "net %d not loaded", net);
+    // W_t is a property of the net's keep list alone; R_t needs the rescue step of vd_process
+    const bool stepped = ctx->rescue_n && !r.split && (plate ? r.cnt1 : r.cnt0) == ps.kcount;
+    if (which == 0 && !stepped)
+        return vd_set_error(VD_ERR_STATE, "vd_read_rescue: net %d took no part in a rescue step of vd_process yet", net);
+    const int frames = which == 0 ? ctx->rescue_n : ps.kn;
+    if (n <= 0 || n > frames) return vd_set_error(VD_ERR_ARG, "n=%d outside [1, %d frames of the last call]", n, frames);
+    BoxTargets t{};
+    int rc;
+    if (out->where == VD_DEVICE) {
+        t.count = out->count; t.xyxy = out->xyxy; t.xyxy_f = out->xyxy_f; t.score = out->score; t.label = out->label;
+    } else {
+        if ((rc = ctx->host_box_staging(&ctx->stage_box, &ctx->stage_box_bytes, out->cap, n, t))) return rc;
+        if (!out->xyxy_f) t.xyxy_f = nullptr;
+        if (!out->score) t.score = nullptr;
+        if (!out->label) t.label = nullptr;
+    }
+    RescueReadArgs a{};
+    a.which = which; a.list = plate ? 1 : 0;
+    a.cnt = ps.kcount; a.all = ctx->rescue_low[plate ? 1 : 0] > 0.f ? ps.kall : ps.kcount; a.kcap = ps.kcap;   // low == 0: no weak boxes
+    a.xy = ps.kxyxy; a.xy_f = ps.kxyxy_f; a.score = ps.kscore; a.label = ps.klabel;
+    if (plate && r.cnt0 && r.all0) { a.cnt_o = r.cnt0; a.all_o = r.all0; a.kcap_o = r.cap0; }
+    a.w_since = which == 0 ? r.w_since : ps.kcount; a.wtot = which == 0 ? r.wtot : 0;   // which 1 never reads it
+    a.cap = out->cap; a.out_count = t.count; a.out_xyxy = t.xyxy; a.out_xyxy_f = t.xyxy_f; a.out_score = t.score;
+    a.out_label = t.label;
+    hipError_t e = vd_launch_rescue_read(a, n, ctx->stream);
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "rescue read: %s", hipGetErrorString(e));
+    return ctx->box_finish(out, n, t);
 }
 
 int vd_tile_rects(int fh, int fw, int rows, int cols, int overlap_pct, int32_t* xywh, int* count) {

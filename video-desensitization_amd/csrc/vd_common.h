@@ -249,6 +249,11 @@ struct PostArgs {
     int B;
     int nc;                  // yolo classes
     float conf;
+    // weak-detection rescue (include/vdmi.h at vd_rescue): with low_on the candidate test runs at `low`
+    // (faces >= low, plates > low), k_all gets the whole keep count and k_count / the caller's arrays the
+    // strong prefix (the boxes that pass `conf`); with low_on == 0 nothing below is read
+    float low; int low_on;
+    int* k_all;              // [B] whole keep list counts (low_on)
     double iou;
     int max_det;             // yolo: 300 (0 = unlimited)
     float max_wh;            // yolo class offset (7680)
@@ -472,6 +477,38 @@ hipError_t vd_launch_hold(const HoldArgs& a, hipStream_t s);
 // scalar stores: no alignment assumed); held_only: H alone (skip each row's own |D| boxes).
 hipError_t vd_launch_hold_gather(const HoldArgs& a, int n, int held_only, int* out_count, int* out_xyxy,
                                  int* out_label, int cap, hipStream_t s);
+
+// Weak-detection rescue (rescue.hip; include/vdmi.h at vd_rescue): E = D ++ R in merged rows with `since`,
+// and the next history. Lists 0 / 1 as the mosaic takes them (list 1 optional); xy pointers 16-B aligned.
+// split == 0: the weak boxes of list i are its row's entries [cnt_i, all_i) (all_i NULL: none);
+// split == 1: list 0 holds the strong boxes and (wcnt, wxy, wcap) the weak ones (vd_rescue_lists).
+#define VD_RESCUE_LDS_BOXES 2048                     // clipped reference boxes a workgroup stages in LDS
+struct RescueArgs {
+    int n, h, w, W, P, S;                            // frames, frame size, window, hold_iou_pct, span
+    int split;
+    const int* cnt0; const int* all0; const int* xy0; int cap0;
+    const int* cnt1; const int* all1; const int* xy1; int cap1;
+    const int* wcnt; const int* wxy; int wcap;
+    const int* hist_cnt; const int* hist_xy; const int* hist_since;   // history read: [W], [W][hcap][4], [W][hcap]
+    int* next_cnt; int* next_xy; int* next_since;    // history written: the other buffer
+    int hcap, hn;                                    // history row capacity (>= ecap), valid slots
+    int* e_xy; int* e_since; int* e_count; int* e_own; int* e_nr0;   // E rows [n][ecap][4], since [n][ecap], |E|, |D|,
+    int ecap;                                        //   rescued boxes of list 0 [n]; ecap >= every |D| + |W|
+    int* w_since; int wtot;                          // per weak box (list 0's, then list 1's): since, 0 = not rescued
+};
+hipError_t vd_launch_rescue(const RescueArgs& a, hipStream_t s);
+// Weak or rescued boxes of one list into caller-shaped arrays [n][cap] (count complete, arrays cut at cap,
+// scalar stores). which 1: the weak tail [cnt, all) of the keep rows as stored; which 0: its rescued boxes
+// (w_since row entries [woff, woff + weak count) > 0) in order, label = since.
+struct RescueReadArgs {
+    int which, list;                                 // list 1: the weak index starts behind list 0's weak boxes
+    const int* cnt; const int* all; int kcap;        // the list's keep rows
+    const int* xy; const float* xy_f; const float* score; const int* label;
+    const int* cnt_o; const int* all_o; int kcap_o;  // the other list (list 1's offset), or NULL
+    const int* w_since; int wtot;
+    int cap; int* out_count; int* out_xyxy; float* out_xyxy_f; float* out_score; int* out_label;
+};
+hipError_t vd_launch_rescue_read(const RescueReadArgs& a, int n, hipStream_t s);
 
 // Look-ahead hold (lead.hip): the emitted frames' blur lists B = D ++ H ++ A in merged rows, and
 // the next pending ring (lead_state.h: window W = ring ++ call). Lists 0 / 1 as the mosaic takes

@@ -24,6 +24,7 @@ VD_BLUR_KSIZE_MAX = 127
 VD_HOLD_MAX = 8
 VD_HOLD_MOTION_OFF, VD_HOLD_MOTION_LINEAR = 0, 1
 VD_LEAD_MAX = 8
+VD_RESCUE_SPAN_MAX = 255
 VD_MASK_RECT, VD_MASK_ELLIPSE = 0, 1
 VD_MASK_GROW_MAX = 200
 VD_TILES_MAX = 4
@@ -101,6 +102,10 @@ SIGNATURES = [
     ("vd_lead_lists", _I, [_P, ctypes.POINTER(vd_boxes), _I, _I, _I, _I, ctypes.POINTER(vd_boxes),
                            ctypes.POINTER(_I)]),
     ("vd_read_lead", _I, [_P, _I, _I, ctypes.POINTER(vd_boxes)]),
+    ("vd_rescue", _I, [_P, _F, _F, _I]),
+    ("vd_rescue_lists", _I, [_P, ctypes.POINTER(vd_boxes), ctypes.POINTER(vd_boxes), _I, _I, _I,
+                             ctypes.POINTER(vd_boxes)]),
+    ("vd_read_rescue", _I, [_P, _I, _I, _I, ctypes.POINTER(vd_boxes)]),
     ("vd_mask", _I, [_P, _I, _I]),
     ("vd_mask_boxes", _I, [_P, ctypes.POINTER(vd_boxes), _I, ctypes.POINTER(vd_boxes)]),
     ("vd_cells", _I, [_P, _I]),
@@ -124,6 +129,7 @@ SIGNATURES = [
                         ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     ("vdt_bottleneck", _I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     ("vdt_plate_raw", _I, [_P, _P, _I, _I, _I, _SZ, _I, _P, ctypes.POINTER(_I)]),
+    ("vdt_plate_postprocess", _I, [_P, _P, _I, _I, _I, ctypes.POINTER(vd_boxes)]),
     ("vdt_jpeg_coefficients", _I, [_P, _SZ, _P, _SZ, ctypes.POINTER(_I)]),
     ("vdt_jdec_stats", _I, [_P, ctypes.POINTER(_I)]),
     ("vdt_set_debug", _I, [_P, ctypes.c_char_p, _I]),
@@ -204,6 +210,18 @@ def check_lead(lead, lead_motion=False):
     if lead_motion and not lead:
         raise ValueError("lead_motion moves led boxes: it needs lead > 0")
     return lead, bool(lead_motion)
+
+
+def check_rescue(rescue, plate_rescue=0.0, rescue_span=60):
+    """(face low, plate low, span) as (float, float, int); ValueError for a negative or NaN low and
+    for a span outside [1, VD_RESCUE_SPAN_MAX]. Both lows 0: off. That a low lies below its net's
+    threshold is the library's check (vd_rescue)."""
+    lo, plo, span = float(rescue), float(plate_rescue), int(rescue_span)
+    if not lo >= 0.0 or not plo >= 0.0:
+        raise ValueError(f"rescue thresholds ({lo}, {plo}): expected 0 (off) or a score below the net's threshold")
+    if not 1 <= span <= VD_RESCUE_SPAN_MAX:
+        raise ValueError(f"rescue_span {span}: expected 1 .. {VD_RESCUE_SPAN_MAX} frames")
+    return lo, plo, span
 
 
 def check_mask(mask, mask_grow):

@@ -128,7 +128,7 @@ class Context:
                  plate_max_det=300, plate_imgsz=640, microbatch=0, microbatch_stage=2, options=None,
                  blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30,
                  hold_motion=False, mask="rect", mask_grow=0, tiles=(1, 1), tile_overlap=20, cells=0,
-                 lead=0, lead_motion=False):
+                 lead=0, lead_motion=False, rescue=0.0, plate_rescue=0.0, rescue_span=60):
         """blur: what process() applies to the kept boxes: "pixelate" (the reference's
         INTER_NEAREST mosaic, the default) or "gaussian" (GaussianBlur(region, (blur_ksize,
         blur_ksize), blur_sigma) per clipped box, in list order; blur_ksize odd in [3, 127],
@@ -170,6 +170,14 @@ class Context:
         process_lead(), whose output lags its input by lead (+ 1 with lead_motion) frames, and
         must be flushed at the end of a stream (lead_flush()); process() with the mosaic flag
         is refused. Kept as self.lead / self.lead_motion (no vd_cfg fields); set_lead() changes
+        them.
+        rescue / plate_rescue / rescue_span: weak-detection rescue (include/vdmi.h at vd_rescue): a
+        face box scored in [rescue, confidence) (a plate box in (plate_rescue, plate_conf]) that
+        matches, under hold_iou_pct, a box blurred in one of the last max(1, hold) frames is blurred
+        too, for at most rescue_span frames (1..255; the default 60 is one second at the
+        reference's output rate) after the track's last strong detection. The detections that
+        process() returns stay the strong ones. 0.0 / 0.0 (the default) is off. Not with tiles.
+        Kept as self.rescue_low / self.plate_rescue_low / self.rescue_span; rescue() changes
         them."""
         if blur not in BLUR_MODES:
             raise ValueError(f"blur {blur!r}: expected 'pixelate' or 'gaussian'")
@@ -178,6 +186,7 @@ class Context:
         tiles, tile_overlap = _lib.check_tiles(tiles, tile_overlap)
         cells = _lib.check_cells(cells)
         lead, lead_motion = _lib.check_lead(lead, lead_motion)
+        rescue, plate_rescue, rescue_span = _lib.check_rescue(rescue, plate_rescue, rescue_span)
         lib = _lib.load()
         cfg = _lib.default_cfg()
         cfg.input_h, cfg.input_w = int(input_shape[0]), int(input_shape[1])
@@ -203,7 +212,7 @@ class Context:
             cfg.blur_ksize, cfg.blur_sigma = int(blur_ksize), float(blur_sigma)
         if hold:                                        # off leaves the fields zero
             cfg.hold_frames, cfg.hold_iou_pct = hold, hold_iou_pct
-        elif lead:                                      # the lead list matches under the same threshold
+        elif lead or rescue or plate_rescue:            # the lead / rescue match uses the same threshold
             cfg.hold_iou_pct = hold_iou_pct
         self.cfg = cfg
         self.device = int(device)
@@ -227,6 +236,9 @@ class Context:
         self.lead, self.lead_motion = 0, False
         if lead:
             self.set_lead(lead, lead_motion)
+        self.rescue_low, self.plate_rescue_low, self.rescue_span = 0.0, 0.0, rescue_span
+        if rescue or plate_rescue:
+            self.rescue(rescue, plate_rescue, rescue_span)
         for k, v in dict(options or {}).items():   # kernel-selection switches (vd_set_option)
             self.set_option(k, v)
 
@@ -534,6 +546,64 @@ class Context:
         boxes = _lib.HostBoxes(n, cap)
         s = boxes.struct()
         check(self._lib.vd_read_held(self._h, n, ctypes.byref(s)))
+        return boxes
+
+    # -- weak-detection rescue ------------------------------------------------------
+    def rescue(self, rescue=0.0, plate_rescue=0.0, rescue_span=60):
+        """vd_rescue: the low thresholds (0.0 / 0.0 = off) and the span. A change forgets the
+        rescue and the hold history; it is refused while lead frames are pending and in a tiling
+        context."""
+        lo, plo, span = _lib.check_rescue(rescue, plate_rescue, rescue_span)
+        check(self._lib.vd_rescue(self._h, lo, plo, span))
+        self.rescue_low, self.plate_rescue_low, self.rescue_span = lo, plo, span
+
+    @staticmethod
+    def _box_lists(boxes):
+        if isinstance(boxes, (_lib.HostBoxes, DeviceBoxes)):
+            return boxes
+        lists = [np.asarray(b, np.int32).reshape(-1, 4) for b in boxes]
+        det = _lib.HostBoxes(len(lists), max(1, max((len(b) for b in lists), default=1)))
+        for i, b in enumerate(lists):
+            det.count[i] = len(b)
+            det.xyxy[i, :len(b)] = b
+        return det
+
+    def rescue_lists(self, strong, weak, h, w, out=None):
+        """vd_rescue_lists: the rescue step alone, for callers with their own detectors. strong /
+        weak: the strong and the weak detections of consecutive h x w frames -- HostBoxes /
+        DeviceBoxes, or lists with one int [k][4] array per frame. Returns `out` (default: a
+        HostBoxes with room for every box) holding E = D ++ R per frame, label = since (0: strong).
+        Only the rescue history advances: hand E to hold()."""
+        ds, dw = self._box_lists(strong), self._box_lists(weak)
+        if ds.n != dw.n:
+            raise ValueError(f"strong has {ds.n} frames, weak {dw.n}")
+        if out is None:
+            out = _lib.HostBoxes(ds.n, max(1, ds.cap + dw.cap))
+        ss, sw, so = ds.struct(), dw.struct(), out.struct()
+        check(self._lib.vd_rescue_lists(self._h, ctypes.byref(ss), ctypes.byref(sw), ds.n, int(h), int(w),
+                                        ctypes.byref(so)))
+        return out
+
+    def read_rescue(self, net, n, which="rescued", cap=None, out=None):
+        """The rescue step's lists of one net for frames [0, n) of the last process() /
+        process_lead() call (vd_read_rescue) as HostBoxes: which="rescued" R (label = since, with
+        the score), "weak" W (label and score as in the keep list). cap defaults to the largest
+        count; out: a HostBoxes / DeviceBoxes to fill instead."""
+        if which not in ("rescued", "weak"):
+            raise ValueError(f"which {which!r}: expected 'rescued' or 'weak'")
+        w = 0 if which == "rescued" else 1
+        if out is not None:
+            s = out.struct()
+            check(self._lib.vd_read_rescue(self._h, net, n, w, ctypes.byref(s)))
+            return out
+        if cap is None:
+            cnt = _lib.HostBoxes(n, 1)
+            s = cnt.struct()
+            check(self._lib.vd_read_rescue(self._h, net, n, w, ctypes.byref(s)))
+            cap = max(1, int(cnt.count.max()))
+        boxes = _lib.HostBoxes(n, cap)
+        s = boxes.struct()
+        check(self._lib.vd_read_rescue(self._h, net, n, w, ctypes.byref(s)))
         return boxes
 
     # -- look-ahead hold -----------------------------------------------------------
@@ -885,6 +955,16 @@ class Context:
         out = np.zeros((n, 64 + self.cfg.plate_nc, A.value), np.float32)
         check(self._lib.vdt_plate_raw(self._h, p, n, h, w, pitch, where, ptr(out), ctypes.byref(A)))
         return out
+
+    def plate_postprocess(self, raw, img_hw, cap=None):
+        """vdt_plate_postprocess: the plate post kernels on raw heads [n][64+nc][A] as plate_raw()
+        returns them, for frames of img_hw whose canvas the last plate forward was run for."""
+        raw = np.ascontiguousarray(raw, np.float32)
+        n = raw.shape[0]
+        boxes = _lib.HostBoxes(n, cap or self.cfg.max_boxes)
+        s = boxes.struct()
+        check(self._lib.vdt_plate_postprocess(self._h, ptr(raw), n, int(img_hw[0]), int(img_hw[1]), ctypes.byref(s)))
+        return self._complete(boxes, _lib.VD_NET_YOLOV8N, cap is None)
 
     def bottleneck(self, x, w1, bn1, w2, bn2, w3, bn3, wd=None, bnd=None, fused=True):
         """One ResNet layer1 bottleneck (bf16 or fp32 context): x f32 NHWC [n,h,w,cin] -> f32

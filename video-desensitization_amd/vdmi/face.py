@@ -112,6 +112,10 @@ class Retinaface(object):
         # look-ahead hold in the fused vd_process_lead: Context(lead=..., lead_motion=...)
         "lead": 0,
         "lead_motion": False,
+        # weak-detection rescue in the fused vd_process: Context(rescue=..., rescue_span=...); the plate
+        # threshold is the plate detector's (YOLO(rescue=...))
+        "rescue": 0.0,
+        "rescue_span": 60,
     }
 
     @classmethod
@@ -128,6 +132,7 @@ class Retinaface(object):
         self.tiles, self.tile_overlap = _lib.check_tiles(self.tiles, self.tile_overlap)
         self.cells = _lib.check_cells(self.cells)
         self.lead, self.lead_motion = _lib.check_lead(self.lead, self.lead_motion)
+        self.rescue, _, self.rescue_span = _lib.check_rescue(self.rescue, 0.0, self.rescue_span)
         if not self.letterbox_image:
             raise ValueError("Batch inference requires letterbox_image=True for shape alignment.")  # face.py:80
         if not self.cuda:
@@ -147,7 +152,7 @@ class Retinaface(object):
                              hold_iou_pct=self.hold_iou_pct, hold_motion=self.hold_motion,
                              mask=self.mask, mask_grow=self.mask_grow, tiles=self.tiles,
                              tile_overlap=self.tile_overlap, cells=self.cells, lead=self.lead,
-                             lead_motion=self.lead_motion)
+                             lead_motion=self.lead_motion, rescue=self.rescue, rescue_span=self.rescue_span)
                      for d in self.device_ids]
         self.ctx = self.ctxs[0]
         self.generate()

@@ -528,7 +528,8 @@ def fused_context(face_detector, plate_detector, batch_size, device=None, slot=0
     # ... and so can its tiling (Context.set_tiles)
     # ... and its cells setting (Context.set_cells)
     key = (id(plate_detector), int(batch_size), dev, int(slot), fd.ctx.mask, fd.ctx.mask_grow, fd.ctx.tiles,
-           fd.ctx.tile_overlap, fd.ctx.cells, fd.ctx.lead, fd.ctx.lead_motion)
+           fd.ctx.tile_overlap, fd.ctx.cells, fd.ctx.lead, fd.ctx.lead_motion, fd.ctx.rescue_low,
+           pd.ctx.plate_rescue_low, fd.ctx.rescue_span)   # ... and the rescue setting (Context.rescue)
     with _FUSED_LOCK:
         cache = fd.__dict__.setdefault("_fused_ctx", {})
         if key in cache:
@@ -552,7 +553,8 @@ def _new_fused_context(fd, pd, batch_size, dev):
                   hold=fd.ctx.cfg.hold_frames, hold_iou_pct=fd.ctx.cfg.hold_iou_pct or 30,
                   hold_motion=fd.ctx.hold_motion, mask=fd.ctx.mask, mask_grow=fd.ctx.mask_grow,
                   tiles=fd.ctx.tiles, tile_overlap=fd.ctx.tile_overlap, cells=fd.ctx.cells,
-                  lead=fd.ctx.lead, lead_motion=fd.ctx.lead_motion)
+                  lead=fd.ctx.lead, lead_motion=fd.ctx.lead_motion, rescue=fd.ctx.rescue_low,
+                  plate_rescue=pd.ctx.plate_rescue_low, rescue_span=fd.ctx.rescue_span)
     ctx.load_weights(_lib.VD_NET_RETINAFACE, fd.state_dict)
     ctx.load_weights(_lib.VD_NET_YOLOV8N, pd.state_dict)
     return ctx
@@ -580,6 +582,18 @@ def _lead_matches(ctx, lead, lead_motion, pct):
     fields: the Context keeps the setting; the match threshold is hold's)."""
     return getattr(ctx, "lead", 0) == lead and (lead == 0 or (bool(ctx.lead_motion) == bool(lead_motion)
                                                              and (ctx.cfg.hold_iou_pct or 30) == pct))
+
+
+def _rescue_matches(fctx, pctx, rescue, plate_rescue, span):
+    """The fused context of these detectors rescues weak boxes exactly so (no cfg fields: the
+    Contexts keep the setting; the face detector carries the face threshold and the span, the
+    plate detector the plate threshold)."""
+    import ctypes
+    f32 = lambda v: ctypes.c_float(v).value
+    lo, plo = getattr(fctx, "rescue_low", 0.0), getattr(pctx, "plate_rescue_low", 0.0)
+    if f32(lo) != f32(rescue) or f32(plo) != f32(plate_rescue):
+        return False
+    return not (rescue or plate_rescue) or getattr(fctx, "rescue_span", 60) == span
 
 
 def _mask_matches(ctx, mask, mask_grow):
@@ -636,7 +650,7 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
                          gpu_codec="auto", jpeg_quality=95, shard="auto", group=None, records=None,
                          blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30,
                          hold_motion=False, mask="rect", mask_grow=0, tiles=(1, 1), tile_overlap=20, cells=0,
-                         lead=0, lead_motion=False):
+                         lead=0, lead_motion=False, rescue=0.0, plate_rescue=0.0, rescue_span=60):
     """combine_detect.py:183-277. Returns (total_processed, total_faces, total_plates).
 
     gpu_codec ("auto" | True | False): with vdmi detectors, no custom loader/saver and
@@ -687,6 +701,15 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     (Retinaface(tiles=..., tile_overlap=...)), else ValueError. Plates are detected on the whole
     frame. (1, 1) (the default) changes nothing.
 
+    rescue / plate_rescue / rescue_span: weak-detection rescue (include/vdmi.h at vd_rescue,
+    Context(rescue=...)): the directory is one video, processed in sorted order as under hold, and a
+    box scored below the detector's threshold but at least `rescue` (plates: above plate_rescue)
+    that continues a blurred track is blurred too, for at most rescue_span frames after the
+    track's last strong detection. It needs the vdmi drop-ins built with the same settings
+    (Retinaface(rescue=..., rescue_span=...), YOLO(rescue=plate_rescue)), else ValueError. The
+    returned totals and `records` are the detections only. A shard that starts at frame b > 0
+    warms up on the rescue_span + hold (+ 1 with hold_motion) frames before it; a dropped batch
+    resets the history. 0.0 / 0.0 (the default) is off.
     hold (0..8) / hold_iou_pct (1..100): box hold (include/vdmi.h, Context(hold=...)): the
     frames are ONE video in the order of their sorted names, and a box stays blurred for up to
     `hold` frames after the last frame in which a detection matched it, so a single missed
@@ -733,6 +756,8 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     tiles, tile_overlap = _lib.check_tiles(tiles, tile_overlap)
     cells = _lib.check_cells(cells)
     lead, lead_motion = _lib.check_lead(lead, lead_motion)
+    rescue, plate_rescue, rescue_span = _lib.check_rescue(rescue, plate_rescue, rescue_span)
+    rescue_on = bool(rescue or plate_rescue)
     if lead and gpu_codec is True:
         raise ValueError("lead > 0: the GPU JPEG codec path is out of scope (use gpu_codec='auto' or False)")
     fctx = getattr(face_detector, "ctx", None)
@@ -740,8 +765,10 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
         raise ValueError("tiles needs the vdmi Retinaface built with the same setting "
                          "(Retinaface(tiles=..., tile_overlap=...))")
     warm_frames = hold + 1 if hold_motion else hold      # the history's depth
+    if rescue_on:
+        warm_frames += rescue_span                       # E_t depends on frames [t - S, t]
     image_paths = [os.path.join(input_dir, f) for f in os.listdir(input_dir) if f.lower().endswith(IMAGE_EXT)]
-    if hold or lead:
+    if hold or lead or rescue_on:
         image_paths.sort()               # the frames of one video, in order
     os.makedirs(output_dir, exist_ok=True)
     if blur not in ("pixelate", "gaussian"):
@@ -751,7 +778,14 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
              and _hold_matches(face_detector.ctx, hold, hold_iou_pct, hold_motion)
              and _mask_matches(face_detector.ctx, mask, mask_grow)
              and _cells_matches(face_detector.ctx, cells)
-             and _lead_matches(face_detector.ctx, lead, lead_motion, hold_iou_pct))
+             and _lead_matches(face_detector.ctx, lead, lead_motion, hold_iou_pct)
+             and _rescue_matches(face_detector.ctx, plate_detector.ctx, rescue, plate_rescue, rescue_span)
+             and (not rescue_on or (face_detector.ctx.cfg.hold_iou_pct or 30) == hold_iou_pct))
+    if rescue_on and not fused:
+        raise ValueError("rescue needs the vdmi Retinaface / YOLO drop-ins built with the same mosaic_level, blur, "
+                         "mask, cells, hold, lead and rescue settings (Retinaface(rescue=..., rescue_span=..., "
+                         "hold_iou_pct=...), YOLO(rescue=plate_rescue)); other detectors call "
+                         "Context.rescue_lists themselves")
     if lead and not fused:
         raise ValueError("lead > 0 needs the vdmi Retinaface / YOLO drop-ins and a face detector built with the "
                          "same mosaic_level, blur, mask, cells, hold and lead settings (Retinaface(lead=..., "
@@ -768,7 +802,8 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
                mosaic_level=mosaic_level, num_workers=num_workers, fused=fused, codec=codec,
                jpeg_quality=jpeg_quality, logger=logger,
                blur=(blur, int(blur_ksize), float(blur_sigma)), hold=hold, hold_warm=warm_frames,
-               mask=(mask, mask_grow), cells=cells, lead=lead, lead_delay=lead + (1 if lead_motion else 0))
+               mask=(mask, mask_grow), cells=cells, lead=lead, lead_delay=lead + (1 if lead_motion else 0),
+               rescue=rescue_on)
     want_rec = records is not None or mode == "ranks"
     if mode == "ranks":
         res, rec = _rank_shard(sorted(image_paths), group, run)
@@ -814,7 +849,7 @@ def _local(paths, first, device, want_rec, run, slot=0, warm=(), tail=(), last=T
     Returns ((processed, faces, plates), records or None)."""
     from .dist import RecordSink
     fd = run["face_detector"]
-    if run.get("hold") or run.get("lead"):
+    if run.get("hold") or run.get("lead") or run.get("rescue"):
         _hold_start(fused_context(fd, run["plate_detector"], run["batch_size"], device, slot), warm,
                     run["loader"], run["mosaic_plates"])
     io = ThreadPoolExecutor(max_workers=run["num_workers"])
@@ -1081,8 +1116,8 @@ def _lead_batches(batches, output_dir, face_detector, plate_detector, batch_size
 
 
 def _hold_dropped(ctx):
-    """A batch was dropped: boxes a batch old must not be held over the gap."""
-    if ctx.cfg.hold_frames:
+    """A batch was dropped: boxes a batch old must not be held (or rescue a weak box) over the gap."""
+    if ctx.cfg.hold_frames or ctx.rescue_low or ctx.plate_rescue_low:
         ctx.hold_reset()
 
 

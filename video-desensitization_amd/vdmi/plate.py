@@ -89,7 +89,7 @@ class YOLO:
     """ultralytics-style plate detector on libvdmi."""
 
     def __init__(self, model="best.pt", nc=1, weights=None, precision="fp32", max_batch=64, device_index=None,
-                 seed=0, imgsz=640, iou=0.7, max_det=300, names=None, device_ids=None):
+                 seed=0, imgsz=640, iou=0.7, max_det=300, names=None, device_ids=None, rescue=0.0):
         from .face import resolve_devices
         self.nc = nc
         self.names = names or {i: f"plate{i}" if nc > 1 else "plate" for i in range(nc)}
@@ -98,8 +98,12 @@ class YOLO:
         self.device_ids = resolve_devices(device_ids, device_index)
         self.device_index = self.device_ids[0]
         self.max_batch = max_batch
+        # rescue: the plate detector's low threshold of the weak-detection rescue (Context(plate_rescue=...));
+        # it acts in a fused face + plate context (vdmi.pipeline), the lists returned here stay the detections
+        _, self.rescue, _ = _lib.check_rescue(0.0, rescue)
         self.ctxs = [Context(device=d, precision=precision, max_batch=max_batch, plate_nc=nc, plate_iou=iou,
-                             plate_max_det=max_det, plate_imgsz=imgsz) for d in self.device_ids]
+                             plate_max_det=max_det, plate_imgsz=imgsz, plate_rescue=self.rescue)
+                     for d in self.device_ids]
         self.ctx = self.ctxs[0]
         if isinstance(weights, str) and weights == "random":   # explicit opt-in (tests, bench)
             weights = yolov8n_state_dict(seed, nc)
