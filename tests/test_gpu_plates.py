@@ -245,7 +245,7 @@ def test_process_detect_early_and_mosaic_early_identical(gpu, mosaic_plates):
 @pytest.mark.parametrize("prec,plates,groups", [("fp32", True, 2), ("fp32", False, 2), ("bf16", True, 2),
                                                ("fp32", True, 3), ("fp16", False, 4)])
 def test_process_face_groups_bit_identical(gpu, prec, plates, groups):
-    """Option face_groups runs the face net as G frame groups on G streams (runtime.cpp
+    """Option face_groups runs the face net as G frame groups on G streams (frames.cpp
     Ctx::face_forward; default 2). Every kernel is batch-invariant, so the float boxes,
     scores and mosaicked frames equal the one-launch schedule's (face_groups=1)
     exactly; an odd batch splits unevenly (5 frames: 2 + 3, 1 + 2 + 2, 1 + 1 + 1 + 2)."""

@@ -1,0 +1,431 @@
+// frames.cpp — frames and box lists in and out of the device; the face path around the net
+// (letterbox, forward, post) and tiled detection.
+
+#include "../../include/vdmi.h"
+#include "vd_common.h"
+#include "vd_math.h"
+#include "nets.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+// cv2.resize mode selection (resize.cpp hal::resize [ext]; oracle/letterbox.py)
+void vd_resize_mode(int ih, int iw, int nh, int nw, int* mode, double* sx, double* sy) {
+    if (nh == ih && nw == iw) { *mode = LB_COPY; *sx = *sy = 1.0; return; }
+    double inv_x = (double)nw / iw, inv_y = (double)nh / ih;
+    double scx = 1.0 / inv_x, scy = 1.0 / inv_y;
+    int isx = (int)std::nearbyint(scx), isy = (int)std::nearbyint(scy);
+    bool area_fast = std::fabs(scx - isx) < 2.220446049250313e-16 && std::fabs(scy - isy) < 2.220446049250313e-16;
+    *mode = (area_fast && isx == 2 && isy == 2) ? LB_AREA2 : LB_LINEAR;
+    *sx = scx;
+    *sy = scy;
+}
+
+const uint8_t* Ctx::frames_to_device(const uint8_t* frames, int n, int h, size_t pitch, int where, int* rc) {
+    *rc = VD_OK;
+    if (where == VD_DEVICE) return frames;
+    size_t bytes = (size_t)n * h * pitch;
+    *rc = ensure_staging(&stage_in, &stage_in_bytes, bytes);
+    if (*rc) return nullptr;
+    hipError_t e = hipMemcpyAsync(stage_in, frames, bytes, hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) {
+        *rc = vd_set_error(VD_ERR_HIP, "H2D frames: %s", hipGetErrorString(e));
+        return nullptr;
+    }
+    return (const uint8_t*)stage_in;
+}
+
+int Ctx::check_frames(int n, int h, int w, size_t pitch) {
+    if (n <= 0 || n > cfg.max_batch) return vd_set_error(VD_ERR_ARG, "n=%d outside [1, max_batch=%d]", n, cfg.max_batch);
+    if (h <= 0 || w <= 0 || pitch < (size_t)w * 3) return vd_set_error(VD_ERR_ARG, "bad frame geometry %dx%d pitch %zu", w, h, pitch);
+    return VD_OK;
+}
+
+// Box outputs: kernels write straight into caller arrays when they are device
+// memory; host outputs go through ctx staging + one D2H at the end. `out` may be
+// NULL (no caller copy; the complete lists stay readable through vd_read_boxes).
+int Ctx::box_targets(vd_boxes* out, int n, BoxTargets& t) {
+    t = BoxTargets{};
+    if (!out) return VD_OK;
+    if (!out->count || !out->xyxy || out->cap <= 0) return vd_set_error(VD_ERR_ARG, "vd_boxes needs count, xyxy, cap>0");
+    t.cap = out->cap;
+    if (out->where == VD_DEVICE) {
+        t.count = out->count; t.xyxy = out->xyxy; t.xyxy_f = out->xyxy_f; t.score = out->score; t.label = out->label;
+        return VD_OK;
+    }
+    return host_box_staging(&stage_box, &stage_box_bytes, out->cap, n, t);
+}
+
+int Ctx::host_box_staging(void** buf, size_t* have, int cap, int n, BoxTargets& t) {
+    size_t nb = (size_t)n * cap;
+    size_t need = n * 4 + nb * (16 + 16 + 4 + 4);
+    int rc = ensure_staging(buf, have, need + 64);
+    if (rc) return rc;
+    char* p = (char*)*buf;
+    t.cap = cap;
+    t.count = (int*)p; p += ((n * 4 + 15) / 16) * 16;
+    t.xyxy = (int*)p; p += nb * 16;
+    t.xyxy_f = (float*)p; p += nb * 16;
+    t.score = (float*)p; p += nb * 4;
+    t.label = (int*)p;
+    return VD_OK;
+}
+
+// Host outputs: one D2H of the staged arrays. count[f] is the complete keep count,
+// which may exceed cap: the arrays then hold the first cap boxes, the rest stay
+// readable through vd_read_boxes, and the mosaic used every box regardless.
+int Ctx::box_finish(vd_boxes* out, int n, const BoxTargets& t) {
+    if (!out || out->where == VD_DEVICE) return VD_OK;
+    size_t nb = (size_t)n * out->cap;
+    VD_CHECK_HIP(hipMemcpyAsync(out->count, t.count, n * 4, hipMemcpyDeviceToHost, stream));
+    VD_CHECK_HIP(hipMemcpyAsync(out->xyxy, t.xyxy, nb * 16, hipMemcpyDeviceToHost, stream));
+    if (out->xyxy_f) VD_CHECK_HIP(hipMemcpyAsync(out->xyxy_f, t.xyxy_f, nb * 16, hipMemcpyDeviceToHost, stream));
+    if (out->score) VD_CHECK_HIP(hipMemcpyAsync(out->score, t.score, nb * 4, hipMemcpyDeviceToHost, stream));
+    if (out->label) VD_CHECK_HIP(hipMemcpyAsync(out->label, t.label, nb * 4, hipMemcpyDeviceToHost, stream));
+    VD_CHECK_HIP(hipStreamSynchronize(stream));
+    return VD_OK;
+}
+
+int vd_count_check(const char* who, const int* count, int rows, int cap) {
+    for (int i = 0; i < rows; ++i)
+        if (count[i] > cap)
+            return vd_set_error(VD_ERR_CAPACITY, "%s: list %d has count %d > cap %d", who, i, count[i], cap);
+    return VD_OK;
+}
+
+int Ctx::box_list_in(const char* who, const vd_boxes* b, int rows, bool vec16, size_t stage_off, BoxListIn* o,
+                     size_t stage_bytes) {
+    if (!b || !b->count || !b->xyxy || b->cap <= 0)
+        return vd_set_error(VD_ERR_ARG, "%s: vd_boxes needs count, xyxy, cap>0", who);
+    const bool host = b->where == VD_HOST;
+    int rc;
+    if (host && (rc = vd_count_check(who, b->count, rows, b->cap))) return rc;
+    o->cnt = b->count;
+    o->xy = b->xyxy;
+    o->staged = host || (vec16 && ((uintptr_t)b->xyxy & 15));
+    if (!o->staged) return VD_OK;
+    const size_t nb = (size_t)rows * b->cap;
+    if ((rc = ensure_staging(&stage_box2, &stage_box2_bytes,
+                             std::max(stage_bytes, stage_off + (size_t)rows * 4 + nb * 16 + 16))))
+        return rc;
+    int* dc = (int*)((char*)stage_box2 + stage_off);
+    int* dx = dc + ((rows + 3) / 4) * 4;          // the boxes start 16-byte aligned
+    const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    VD_CHECK_HIP(hipMemcpyAsync(dc, b->count, (size_t)rows * 4, kind, stream));
+    VD_CHECK_HIP(hipMemcpyAsync(dx, b->xyxy, nb * 16, kind, stream));
+    o->cnt = dc;
+    o->xy = dx;
+    return VD_OK;
+}
+
+int Ctx::rows_out(const HoldArgs& view, int n, int held_only, vd_boxes* out, const char* what) {
+    BoxTargets t{};
+    if (out->where == VD_DEVICE) {
+        t.count = out->count; t.xyxy = out->xyxy; t.label = out->label;
+    } else {
+        int rc = host_box_staging(&stage_box, &stage_box_bytes, out->cap, n, t);
+        if (rc) return rc;
+        if (!out->label) t.label = nullptr;
+    }
+    hipError_t e = vd_launch_hold_gather(view, n, held_only, t.count, t.xyxy, t.label, out->cap, stream);
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "%s gather: %s", what, hipGetErrorString(e));
+    if (out->where == VD_DEVICE) return VD_OK;
+    // arrays past min(count, cap) are not written by the gather: copy whole arrays as box_finish does
+    const size_t nbx = (size_t)n * out->cap;
+    VD_CHECK_HIP(hipMemcpyAsync(out->count, t.count, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+    VD_CHECK_HIP(hipMemcpyAsync(out->xyxy, t.xyxy, nbx * 16, hipMemcpyDeviceToHost, stream));
+    if (out->label) VD_CHECK_HIP(hipMemcpyAsync(out->label, t.label, nbx * 4, hipMemcpyDeviceToHost, stream));
+    VD_CHECK_HIP(hipStreamSynchronize(stream));
+    return VD_OK;
+}
+
+int Ctx::face_letterbox(const uint8_t* dframes, int n, int h, int w, size_t pitch) {
+    LetterboxArgs a;
+    face_letterbox_args(dframes, n, h, w, pitch, &a);
+    t_begin(2, (double)n * (a.nh * (double)w * 3 + (double)a.oh * a.ow * a.cpad * (f32 ? 4 : 2)));
+    hipError_t e = vd_launch_letterbox(a, stream);
+    t_end();
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "letterbox: %s", hipGetErrorString(e));
+    return VD_OK;
+}
+
+void Ctx::face_letterbox_args(const uint8_t* dframes, int n, int h, int w, size_t pitch, LetterboxArgs* out) {
+    LetterboxArgs a{};
+    a.src = dframes; a.n = n; a.ih = h; a.iw = w; a.pitch = pitch;
+    a.oh = face.in_h; a.ow = face.in_w;
+    // utils/utils.py:9-13 (Python doubles)
+    double scale = std::min((double)a.ow / w, (double)a.oh / h);
+    a.nw = (int)(w * scale);
+    a.nh = (int)(h * scale);
+    a.top = (a.oh - a.nh) / 2;
+    a.left = (a.ow - a.nw) / 2;
+    vd_resize_mode(h, w, a.nh, a.nw, &a.mode, &a.scale_x, &a.scale_y);
+    a.pad_value = 128.f;
+    a.mean[0] = 104.f; a.mean[1] = 117.f; a.mean[2] = 123.f;
+    a.div = 1.f;
+    a.flip = 0;
+    // fp32 plan with the fused stem: an fp16 space-to-depth canvas (integer values, exact)
+    a.out = face.input.p; a.cpad = face.input.c; a.out_f32 = face.input.f32 ? 1 : 0;
+    a.out_f16 = (f16 || (f32 && !face.input.f32)) ? 1 : 0;
+    a.s2d = face.s2d ? 1 : 0;
+    *out = a;
+}
+
+int Ctx::face_forward(int n) {
+    const int mb = cfg.microbatch;                        // frames per micro-batch (0 = off)
+    const int stage = cfg.microbatch_stage > 0 ? cfg.microbatch_stage : 2;   // micro-batch through layer<stage>
+    const int split = face.net.stage_end[std::min(std::max(stage, 0), 4)];
+    const int G = std::min(std::min(tune.face_groups, 4), n);
+    if (G >= 2 && mb <= 0 && lane_ev.empty()) {
+        // G frame groups on G streams (group 0 on the context stream): each layer's last
+        // partial round of workgroups leaves CUs that the other groups' launches take.
+        // Every kernel is batch-invariant (a frame's sums do not depend on its batch
+        // position or the launch's frame count), so the results are bit-identical to
+        // one launch over n frames.
+        const Net& net = face.net;
+        while ((int)group_streams.size() < G - 1) {
+            hipStream_t st;
+            hipEvent_t ev;
+            VD_CHECK_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+            VD_CHECK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+            group_streams.push_back(st);
+            group_events.push_back(ev);
+        }
+        if (!ev_half) VD_CHECK_HIP(hipEventCreateWithFlags(&ev_half, hipEventDisableTiming));
+        if (net.amax) VD_CHECK_HIP(hipMemsetAsync(net.amax, 0, net.amax_bytes, stream));
+        VD_CHECK_HIP(hipEventRecord(ev_half, stream));
+        const int ne = (int)net.ops.size();
+        hipStream_t main = stream;
+        for (int g = 0; g < G; ++g) {
+            const int f0 = (int)((long)n * g / G), f1 = (int)((long)n * (g + 1) / G);
+            stream = g ? group_streams[g - 1] : main;
+            if (g) VD_CHECK_HIP(hipStreamWaitEvent(stream, ev_half, 0));
+            int rc = run_ops(net, 0, ne, f0, f1 - f0);
+            if (!rc && g && hipEventRecord(group_events[g - 1], stream) != hipSuccess)
+                rc = vd_set_error(VD_ERR_HIP, "group event");
+            stream = main;
+            if (rc) return rc;
+        }
+        for (int g = 1; g < G; ++g) VD_CHECK_HIP(hipStreamWaitEvent(stream, group_events[g - 1], 0));
+        return VD_OK;
+    }
+    return run_net(face.net, n, mb, split);
+}
+
+int Ctx::face_post(int n, int img_h, int img_w, const BoxTargets& t, const TileGrid* tiles) {
+    face_rows_merged = false;
+    PostArgs p{};
+    p.mode = POST_FACE;
+    for (int l = 0; l < 3; ++l) {
+        p.heads[l] = (const float*)face.heads[l].p;
+        p.lh[l] = face.heads[l].h;
+        p.lw[l] = face.heads[l].w;
+        p.loff[l] = face.loff[l];
+    }
+    p.hstride = face.heads[0].c;
+    p.anchors = face.anchors; p.A = face.A; p.B = n;
+    p.conf = cfg.confidence; p.iou = cfg.nms_iou; p.max_det = 0;
+    p.low = rescue_low[0]; p.low_on = rescue_low[0] > 0.f;       // rescue: the keep list at face_low
+    p.cand_keys = face.post.keys; p.cand_count = face.post.count;
+    p.scratch_box = face.post.box; p.scratch_cls = face.post.cls; p.scratch_nbox = face.post.nbox;
+    p.scratch_area = face.post.area; p.scratch_keys = face.post.sort; p.scratch_supp = face.post.supp;
+    p.sort_cap = face.post.sort_cap;
+    p.img_h = img_h; p.img_w = img_w;
+    // retinaface_correct_boxes factors (utils_bbox.py:118-132), float32 tensor arithmetic
+    const float inh = (float)face.in_h, inw = (float)face.in_w, ih = (float)img_h, iw = (float)img_w;
+    const float rh = inh / ih, rw = inw / iw;
+    const float mn = rh < rw ? rh : rw;
+    const float nh = ih * mn, nw = iw * mn;
+    p.offy = ((inh - nh) / 2.0f) / inh;
+    p.offx = ((inw - nw) / 2.0f) / inw;
+    p.scy = inh / nh;
+    p.scx = inw / nw;
+    if (tiles) {   // the same factors for a tile as a frame of its own
+        const float th = (float)tiles->th, tw = (float)tiles->tw;
+        const float trh = inh / th, trw = inw / tw;
+        const float tmn = trh < trw ? trh : trw;
+        const float tnh = th * tmn, tnw = tw * tmn;
+        p.tile_T = tiles->T; p.tile_h = tiles->th; p.tile_w = tiles->tw;
+        p.tile_offy = ((inh - tnh) / 2.0f) / inh;
+        p.tile_offx = ((inw - tnw) / 2.0f) / inw;
+        p.tile_scy = inh / tnh;
+        p.tile_scx = inw / tnw;
+    }
+    p.cap = t.cap; p.out_count = t.count; p.out_xyxy = t.xyxy; p.out_xyxy_f = t.xyxy_f;
+    p.out_score = t.score; p.out_label = t.label;
+    vd_post_keep_args(face.post, p, n);
+    t_begin(3, (double)n * face.A * 32 * 4);
+    hipError_t e = vd_launch_post(p, stream);
+    t_end();
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "face post: %s", hipGetErrorString(e));
+    return VD_OK;
+}
+
+// ---- tiled face detection (tiles.hip, pre.hip letterbox_tiles_kernel) ----
+int Ctx::tiles_set(int rows, int cols, int overlap_pct) {
+    if (rows < 1 || rows > VD_TILES_MAX || cols < 1 || cols > VD_TILES_MAX || overlap_pct < 0 || overlap_pct > 50)
+        return vd_set_error(VD_ERR_ARG, "vd_tiles: rows, cols in [1, %d] and overlap_pct in [0, 50] required (got %d, "
+                            "%d, %d)", VD_TILES_MAX, rows, cols, overlap_pct);
+    if (rows == tile_rows && cols == tile_cols && overlap_pct == tile_overlap) return VD_OK;
+    if (rescue_on())
+        return vd_set_error(VD_ERR_STATE, "vd_tiles: tiled detection and rescue (vd_rescue) cannot be combined");
+    if (lead.pend)
+        return vd_set_error(VD_ERR_STATE, "vd_tiles: %d frames are pending in the look-ahead ring (flush first)", lead.pend);
+    VD_CHECK_HIP(hipStreamSynchronize(stream));   // a queued launch may still read the merged rows
+    tile_rows = rows; tile_cols = cols; tile_overlap = overlap_pct;
+    tiles_kn = 0;
+    face_rows_merged = false;
+    hold.reset();                                 // the merged rows change capacity: a new stream
+    return VD_OK;
+}
+
+int Ctx::tiles_grid(int h, int w, TileGrid* g) {
+    int32_t r[VD_TILE_INPUTS_MAX][4];
+    int cnt = 0;
+    if (vd_tile_rects_host(h, w, tile_rows, tile_cols, tile_overlap, &r[0][0], &cnt))
+        return vd_set_error(VD_ERR_ARG, "tiles: bad frame geometry %dx%d", w, h);
+    *g = TileGrid{};
+    g->T = cnt; g->tw = r[1][2]; g->th = r[1][3];
+    for (int k = 0; k < cnt; ++k) { g->x0[k] = r[k][0]; g->y0[k] = r[k][1]; }
+    return VD_OK;
+}
+
+int Ctx::face_letterbox_tiles(const uint8_t* dframes, int n, int h, int w, size_t pitch, const TileGrid& g) {
+    LetterboxArgs wa, ta;
+    face_letterbox_args(dframes, n, h, w, pitch, &wa);
+    face_letterbox_args(dframes, n, g.th, g.tw, pitch, &ta);
+    const double canvas = (double)wa.oh * wa.ow * wa.cpad * (f32 ? 4 : 2);
+    t_begin(2, (double)n * (wa.nh * (double)w * 3 + (g.T - 1) * (ta.nh * (double)g.tw * 3) + g.T * canvas));
+    hipError_t e = vd_launch_letterbox_tiles(wa, ta, g, stream);
+    t_end();
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "tile letterbox: %s", hipGetErrorString(e));
+    return VD_OK;
+}
+
+// Merged rows and spill scratch for the floor(max_batch / T) frames a call can carry: T * kcap
+// boxes per frame, so the bytes do not grow with T (the sort keys alone round up to a power of two).
+int Ctx::tiles_merge(int n, const TileGrid& g, const int* cnt, const float* xyxy_f, const float* score, const int* label,
+                     int icap, const BoxTargets& t) {
+    const size_t F = std::max(cfg.max_batch / g.T, 1);
+    const size_t mcap = (size_t)g.T * face.post.kcap;
+    if ((size_t)n > F || icap > face.post.kcap || mcap > 0x3fffffffu)
+        return vd_set_error(VD_ERR_ARG, "tiles merge: n=%d frames of lists of cap %d outside [1, %zu] x [1, %d]", n, icap,
+                            F, face.post.kcap);
+    size_t sort_cap = 1;
+    while (sort_cap < mcap) sort_cap <<= 1;
+    const size_t rows = F * mcap;
+    const size_t need = rows * (16 + 16 + 16 + 4 + 4 + 4 + 1) + F * sort_cap * 8 + F * 4 + 256;
+    int rc = ensure_staging(&tiles_buf, &tiles_buf_bytes, need);
+    if (rc) return rc;
+    TileMergeArgs a{};
+    a.n = n; a.g = g; a.A = face.A; a.iou = cfg.nms_iou;
+    a.cnt = cnt; a.xyxy_f = xyxy_f; a.score = score; a.label = label; a.icap = icap;
+    char* p = (char*)tiles_buf;
+    a.m_xyxy = (int*)p; p += rows * 16;
+    a.m_xyxy_f = (float*)p; p += rows * 16;
+    a.s_box = (float4*)p; p += rows * 16;
+    a.s_keys = (uint64_t*)p; p += F * sort_cap * 8;
+    a.m_score = (float*)p; p += rows * 4;
+    a.m_label = (int*)p; p += rows * 4;
+    a.s_area = (float*)p; p += rows * 4;
+    a.m_count = (int*)p; p += (F * 4 + 15) / 16 * 16;
+    a.s_supp = (uint8_t*)p;
+    a.sort_cap = (int)sort_cap; a.mcap = (int)mcap;
+    a.cap = t.cap; a.out_count = t.count; a.out_xyxy = t.xyxy; a.out_xyxy_f = t.xyxy_f;
+    a.out_score = t.score; a.out_label = t.label;
+    t_begin(3, (double)n * g.T * icap * 24);      // the lists' capacity: the counts are known to the device only
+    hipError_t e = vd_launch_tiles_merge(a, stream);
+    t_end();
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "tiles merge: %s", hipGetErrorString(e));
+    tiles_last = a;
+    tiles_kn = n;
+    face_rows_merged = true;
+    return VD_OK;
+}
+
+int Ctx::tiles_check(int n, int h, int w, TileGrid* g) {
+    int rc = tiles_grid(h, w, g);
+    if (rc) return rc;
+    if ((long long)n * g->T > cfg.max_batch)
+        return vd_set_error(VD_ERR_ARG, "tiles: n=%d frames x %d net inputs exceed max_batch=%d (largest n: %d)", n,
+                            g->T, cfg.max_batch, cfg.max_batch / g->T);
+    return VD_OK;
+}
+
+// after face_forward(n * T): the per-input keep lists (face.post, no caller copy), then their merge
+int Ctx::face_post_tiled(int n, int h, int w, const TileGrid& g, const BoxTargets& t) {
+    int rc = face_post(n * g.T, h, w, BoxTargets{}, &g);
+    if (rc) return rc;
+    const PostScratch& ps = face.post;
+    return tiles_merge(n, g, ps.kcount, ps.kxyxy_f, ps.kscore, ps.klabel, ps.kcap, t);
+}
+
+extern "C" {
+
+int vd_tile_rects(int fh, int fw, int rows, int cols, int overlap_pct, int32_t* xywh, int* count) {
+    if (vd_tile_rects_host(fh, fw, rows, cols, overlap_pct, xywh, count))
+        return vd_set_error(VD_ERR_ARG, "vd_tile_rects: h, w > 0, rows, cols in [1, %d] and overlap_pct in [0, 50] "
+                            "required (got %d x %d, %d, %d, %d)", VD_TILES_MAX, fw, fh, rows, cols, overlap_pct);
+    return VD_OK;
+}
+
+int vd_tiles(vd_ctx* h, int rows, int cols, int overlap_pct) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    return ctx->tiles_set(rows, cols, overlap_pct);
+}
+
+int vd_tiles_merge(vd_ctx* h, const vd_boxes* lists, int n, int fh, int fw, vd_boxes* out) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (!ctx->tiles_on()) return vd_set_error(VD_ERR_STATE, "vd_tiles_merge: tiling is off (vd_tiles)");
+    if (!ctx->face.loaded) return vd_set_error(VD_ERR_STATE, "vd_tiles_merge: RetinaFace weights not loaded");
+    if (!lists || !lists->count || !lists->xyxy_f || !lists->score || lists->cap <= 0)
+        return vd_set_error(VD_ERR_ARG, "vd_tiles_merge: lists need count, xyxy_f, score, cap>0");
+    if (n <= 0 || fh <= 0 || fw <= 0) return vd_set_error(VD_ERR_ARG, "vd_tiles_merge: bad geometry");
+    TileGrid g;
+    int rc = ctx->tiles_check(n, fh, fw, &g);
+    if (rc) return rc;
+    if (lists->cap > ctx->face.post.kcap)
+        return vd_set_error(VD_ERR_ARG, "vd_tiles_merge: lists of cap %d (at most the net's %d anchors)", lists->cap,
+                            ctx->face.post.kcap);
+    const int rows = n * g.T;
+    const bool host = lists->where == VD_HOST;
+    if (host && (rc = vd_count_check("vd_tiles_merge", lists->count, rows, lists->cap))) return rc;
+    BoxTargets t;
+    if ((rc = ctx->box_targets(out, n, t))) return rc;
+    const int* cnt = lists->count;
+    const float* xf = lists->xyxy_f;
+    const float* sc = lists->score;
+    const int* lab = lists->label;
+    if (host) {
+        const size_t nb = (size_t)rows * lists->cap;
+        const size_t c16 = ((size_t)rows * 4 + 15) / 16 * 16;
+        if ((rc = ctx->ensure_staging(&ctx->tiles_in, &ctx->tiles_in_bytes, c16 + nb * 24))) return rc;
+        char* p = (char*)ctx->tiles_in;
+        int* dc = (int*)p; p += c16;
+        float* dx = (float*)p; p += nb * 16;
+        float* ds = (float*)p; p += nb * 4;
+        int* dl = (int*)p;
+        VD_CHECK_HIP(hipMemcpyAsync(dc, lists->count, (size_t)rows * 4, hipMemcpyHostToDevice, ctx->stream));
+        VD_CHECK_HIP(hipMemcpyAsync(dx, lists->xyxy_f, nb * 16, hipMemcpyHostToDevice, ctx->stream));
+        VD_CHECK_HIP(hipMemcpyAsync(ds, lists->score, nb * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (lab) VD_CHECK_HIP(hipMemcpyAsync(dl, lists->label, nb * 4, hipMemcpyHostToDevice, ctx->stream));
+        cnt = dc; xf = dx; sc = ds; lab = lab ? dl : nullptr;
+    }
+    if ((rc = ctx->tiles_merge(n, g, cnt, xf, sc, lab, lists->cap, t))) return rc;
+    if ((rc = ctx->box_finish(out, n, t))) return rc;
+    if (host && !(out && out->where == VD_HOST))
+        VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // staging reused by the next call
+    return VD_OK;
+}
+
+}  // extern "C"

@@ -5,12 +5,58 @@
 #include "hold_state.h"
 #include "lead_state.h"
 
+#include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <unordered_map>
 #include <utility>
 #include <map>
 #include <vector>
+
+// Every context entry of the C-ABI: the context's lock and its device.
+#define VD_ENTRY(ctx)                                                        \
+    if (!(ctx)) return vd_set_error(VD_ERR_ARG, "null context");              \
+    std::lock_guard<std::mutex> _lk((ctx)->mu);                                \
+    if (hipSetDevice((ctx)->device) != hipSuccess)                             \
+        return vd_set_error(VD_ERR_HIP, "hipSetDevice(%d) failed", (ctx)->device)
+
+// [a, a + bytes) and [b, b + bytes) share a byte (device frame batches of one geometry)
+static inline bool vd_ranges_overlap(const void* a, const void* b, size_t bytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return bytes && x < y + bytes && y < x + bytes;
+}
+
+static inline uint16_t f32_to_bf16_rne(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+
+static inline uint16_t f32_to_f16_rne(float f) {   // IEEE binary16, round to nearest even (clang _Float16)
+    const _Float16 h = (_Float16)f;
+    uint16_t u;
+    memcpy(&u, &h, 2);
+    return u;
+}
+
+static inline float f16_bits_to_f32(uint16_t u) {
+    _Float16 h;
+    memcpy(&h, &u, 2);
+    return (float)h;
+}
+
+// host-side 16-bit encoding of the context's half type
+static inline uint16_t to_half(bool f16, float v) { return f16 ? f32_to_f16_rne(v) : f32_to_bf16_rne(v); }
+static inline float from_half(bool f16, uint16_t u) {
+    if (f16) return f16_bits_to_f32(u);
+    uint32_t w = (uint32_t)u << 16;
+    float v;
+    memcpy(&v, &w, 4);
+    return v;
+}
 
 struct HT {   // host tensor from the VDW1 container
     std::vector<int> shape;
@@ -155,6 +201,16 @@ struct BoxTargets {
     float* xyxy_f = nullptr;
     float* score = nullptr;
     int* label = nullptr;
+};
+
+struct BoxListIn {   // a caller's box list as the kernels take it (Ctx::box_list_in)
+    const int* cnt = nullptr;
+    const int* xy = nullptr;
+    bool staged = false;   // copied into the context's staging, which the next call reuses
+};
+
+struct PlaneRows {   // one plane of a ping-pong history: bytes of a slot's row before and after a regrow
+    size_t old_row, new_row;
 };
 
 struct TimedEv {
@@ -323,6 +379,22 @@ struct Ctx {
     int box_targets(vd_boxes* out, int n, BoxTargets& t);
     int box_finish(vd_boxes* out, int n, const BoxTargets& t);
     int host_box_staging(void** buf, size_t* have, int cap, int n, BoxTargets& t);
+    // A caller's list of `rows` rows as device pointers. A host list is refused (VD_ERR_CAPACITY) when a
+    // count exceeds cap, then staged `stage_off` bytes into stage_box2 (sized for stage_bytes if that is
+    // more: a call with two lists). vec16: the consumer reads boxes as 16-byte vectors (hold.hip,
+    // lead.hip, rescue.hip), so a device list whose xyxy is not 16-byte aligned is staged too; the blur
+    // and mask kernels read scalars and take a device list as it is. The next call reuses the staging:
+    // a caller that staged and does not wait for host output synchronises before it returns.
+    int box_list_in(const char* who, const vd_boxes* b, int rows, bool vec16, size_t stage_off, BoxListIn* o,
+                    size_t stage_bytes = 0);
+    // Merged rows (a HoldArgs view: rows, labels, counts, the offset to skip) -> the caller's lists
+    // through the hold's gather; host lists are staged, copied whole, and waited for.
+    int rows_out(const HoldArgs& view, int n, int held_only, vd_boxes* out, const char* what);
+    // A ping-pong pair regrown to `bytes` each: both heads cleared; with cur >= 0 buf[cur]'s head_copy
+    // bytes and its planes (consecutive behind the head, `slots` rows each) carried over from the old
+    // row pitch to the new; then the stream is waited for and the old pair freed.
+    int regrow_pair(int* (&buf)[2], size_t bytes, size_t head, int cur, size_t head_copy, int slots,
+                    std::initializer_list<PlaneRows> planes, const char* what);
     int face_letterbox(const uint8_t* dframes, int n, int h, int w, size_t pitch);
     void face_letterbox_args(const uint8_t* dframes, int n, int h, int w, size_t pitch, LetterboxArgs* a);
     int face_forward(int n);
@@ -346,6 +418,10 @@ struct Ctx {
     int launch_shaped(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
                       const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int pass, int level,
                       int ksize, float sigma, int cells);
+    // launch_shaped with the pass the context is configured for (vd_process, the lead step): pixelation,
+    // or in a Gaussian-mode context the fixed kernel / under vd_cells the scaled smooth blur
+    int launch_cfg_pass(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
+                        const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1);
     // B = D ++ H of n consecutive frames into hold_last's merged rows, and the history update
     int launch_hold(int n, int h, int w, const int* cnt0, const int* xy0, int cap0, const int* cnt1, const int* xy1,
                     int cap1);
@@ -367,6 +443,8 @@ struct Ctx {
     int lead_read(int n, int which, vd_boxes* out);   // merged rows -> caller lists (label 0, +a, -a)
 };
 
+// a host list whose count[i] exceeds cap names boxes the caller does not hold: refused, never skipped silently
+int vd_count_check(const char* who, const int* count, int rows, int cap);
 int vd_alloc_post(Ctx& ctx, PostScratch& ps, int A, int kcap);
 void vd_post_keep_args(PostScratch& ps, PostArgs& p, int n);
 int vd_build_face(Ctx& ctx, const WMap& W);

@@ -1,0 +1,583 @@
+// process.cpp — detection and blurring: the blur passes behind the mask setting, the stand-alone
+// blur entries, vd_detect*, vd_read_boxes and vd_process / vd_process_lead.
+
+#include "../../include/vdmi.h"
+#include "vd_common.h"
+#include "vd_math.h"
+#include "nets.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+int Ctx::launch_mosaic(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
+                       const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int level, int cells) {
+    const int tcap = (cnt0 ? cap0 : 0) + (cnt1 ? cap1 : 0);
+    int rc = ensure_staging(&mosaic_table, &mosaic_table_bytes, vd_mosaic_table_bytes(n, tcap) + 64);
+    if (rc) return rc;
+    const int map_on = tune.mosaic_map | (tune.mosaic_nt << 1) | (tune.mosaic_gather ? 16 : 0) | ((tune.mosaic_rows & 63) << 8);
+    auto launch = [&](int stages) {
+        return vd_launch_mosaic(in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, level, mosaic_table, stages,
+                                map_on, tune.mosaic_cells, stream, cells);
+    };
+    hipError_t e = hipSuccess;
+    if (tune.mosaic_fused) {
+        // one launch: the output pass walks and gathers its bands' cells itself (family 1)
+        t_begin(1, 2.0 * n * (double)h * w * 3);
+        e = launch(8);
+        t_end();
+    } else {
+        t_begin(6, 0);
+        e = launch(1);
+        t_end();
+        if (e == hipSuccess) {
+            t_begin(1, 2.0 * n * (double)h * w * 3);
+            e = launch(2);
+            t_end();
+        }
+    }
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "mosaic: %s", hipGetErrorString(e));
+    return VD_OK;
+}
+
+// The scaled smooth blur (vd_cells in a Gaussian-mode context, vd_smooth): the copy in -> out,
+// then the box pass; no scratch (the cell sums live in LDS). Two family-1 intervals: the copy
+// carries the frames' bytes, the box pass's bytes follow from the boxes.
+int Ctx::launch_smooth(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
+                       const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int level, int cells) {
+    if (h > 32768 || w > 32768 || level < 1 || level > 32768)
+        return vd_set_error(VD_ERR_ARG, "smooth blur: h, w <= 32768 and level in [1, 32768] required (got %d x %d, "
+                            "level %d)", w, h, level);
+    if (cells < VD_CELLS_MIN || cells > VD_CELLS_MAX)
+        return vd_set_error(VD_ERR_ARG, "smooth blur: cells %d outside [%d, %d]", cells, VD_CELLS_MIN, VD_CELLS_MAX);
+    hipError_t e = hipSuccess;
+    for (int stage = 0; stage < 2 && e == hipSuccess; ++stage) {
+        t_begin(1, stage == 0 ? 2.0 * n * (double)h * w * 3 : 0);
+        e = vd_launch_smooth(in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, level, cells, stage, stream);
+        t_end();
+    }
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "smooth: %s", hipGetErrorString(e));
+    return VD_OK;
+}
+
+// Gaussian mode: plan kernel, band pass (copy + independent boxes), dependent-box pass,
+// bracketed as one family-1 interval with the mosaic's algorithmic bytes.
+int Ctx::launch_blur(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
+                     const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int ksize, float sigma) {
+    uint32_t q[VD_BLUR_KSIZE_MAX];
+    if (vd_blur_weights(ksize, sigma, q))
+        return vd_set_error(VD_ERR_ARG, "blur: ksize must be odd in [3, %d] (got %d) and sigma finite",
+                            VD_BLUR_KSIZE_MAX, ksize);
+    const int tcap = (cnt0 ? cap0 : 0) + (cnt1 ? cap1 : 0);
+    int rc = ensure_staging(&blur_table, &blur_table_bytes, vd_blur_table_bytes(n, h, pitch, tcap));
+    if (rc) return rc;
+    t_begin(1, 2.0 * n * (double)h * w * 3);
+    hipError_t e = vd_launch_blur(in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, ksize, q, blur_table,
+                                  stream);
+    t_end();
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "blur: %s", hipGetErrorString(e));
+    return VD_OK;
+}
+
+// ---- mask shaping (mask.hip) ----
+// Merged rows of the lists grown by mask_grow; the row capacity is the lists' capacity, so the
+// scratch and the grid depend on n and the capacities only (the counts stay on the device).
+int Ctx::launch_mask_grow(int n, const int* cnt0, const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1,
+                          int zero_tail) {
+    const size_t mcap = std::max<size_t>((size_t)(cnt0 ? cap0 : 0) + (size_t)(cnt1 ? cap1 : 0), 1);
+    if (mcap > 0x7fffffffu) return vd_set_error(VD_ERR_ARG, "mask: list capacity too large");
+    const size_t nb = (size_t)n * mcap;
+    int rc = ensure_staging(&mask_rows, &mask_rows_bytes, nb * 16 + (size_t)n * 4 + 64);
+    if (rc) return rc;
+    MaskArgs a{};
+    a.n = n;
+    a.cnt0 = cnt0; a.xy0 = xy0; a.cap0 = cap0;
+    a.cnt1 = cnt1; a.xy1 = xy1; a.cap1 = cap1;
+    a.g = mask_grow; a.zero_tail = zero_tail;
+    a.m_xy = (int*)mask_rows; a.m_cnt = a.m_xy + nb * 4; a.mcap = (int)mcap;
+    t_begin(3, (double)nb * 16);                  // the rows' bytes: the counts are known to the device only
+    hipError_t e = vd_launch_mask_grow(a, stream);
+    t_end();
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "mask grow: %s", hipGetErrorString(e));
+    mask_last = a;
+    return VD_OK;
+}
+
+int Ctx::launch_mask_restore(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch) {
+    MaskArgs a = mask_last;
+    a.in = in; a.out = out; a.n = n; a.h = h; a.w = w; a.pitch = pitch;
+    // the bytes moved follow from the boxes (6 B per pixel of a clipped box outside every
+    // ellipse), which the host does not see: time and launches only
+    t_begin(1, 0);
+    hipError_t e = vd_launch_mask_restore(a, stream);
+    t_end();
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "mask restore: %s", hipGetErrorString(e));
+    return VD_OK;
+}
+
+// What the three blurring calls launch. Default mask: the rectangular pass alone, exactly as
+// before. Otherwise the lists are grown into one merged row per frame, the rectangular pass
+// runs on that row (its second list null), and the ellipse composite follows it.
+int Ctx::launch_shaped(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
+                       const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1, int pass, int level,
+                       int ksize, float sigma, int cells) {
+    const bool shaped = mask_on() && (cnt0 || cnt1);
+    if (shaped) {
+        int rc = launch_mask_grow(n, cnt0, xy0, cap0, cnt1, xy1, cap1);
+        if (rc) return rc;
+        cnt0 = mask_last.m_cnt; xy0 = mask_last.m_xy; cap0 = mask_last.mcap;
+        cnt1 = xy1 = nullptr; cap1 = 0;
+    }
+    // the cell levels come from the boxes as this pass receives them: grown, when a mask is set
+    int rc = pass == RECT_GAUSSIAN ? launch_blur(in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, ksize, sigma)
+             : pass == RECT_SMOOTH ? launch_smooth(in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, level, cells)
+                                   : launch_mosaic(in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, level, cells);
+    if (rc) return rc;
+    if (shaped && mask_shape == VD_MASK_ELLIPSE) return launch_mask_restore(in, out, n, h, w, pitch);
+    return VD_OK;
+}
+
+// box-scaled strength (vd_cells): pixelation takes its level per box, the Gaussian mode becomes
+// the scaled smooth blur
+int Ctx::launch_cfg_pass(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,
+                         const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1) {
+    const bool gaussian = cfg.blur_mode == VD_BLUR_GAUSSIAN;
+    const int pass = !gaussian ? RECT_MOSAIC : (cells ? RECT_SMOOTH : RECT_GAUSSIAN);
+    return launch_shaped(in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, pass, cfg.mosaic_level,
+                         cfg.blur_ksize, cfg.blur_sigma, cells);
+}
+
+extern "C" {
+
+int vd_detect(vd_ctx* h, const uint8_t* frames, int n, int fh, int fw, size_t pitch, int where, vd_boxes* faces) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (!ctx->face.loaded) return vd_set_error(VD_ERR_STATE, "RetinaFace weights not loaded");
+    int rc = ctx->check_frames(n, fh, fw, pitch);
+    if (rc) return rc;
+    const bool tiled = ctx->tiles_on();
+    TileGrid g;
+    if (tiled && (rc = ctx->tiles_check(n, fh, fw, &g))) return rc;
+    BoxTargets t;
+    rc = ctx->box_targets(faces, n, t);
+    if (rc) return rc;
+    const uint8_t* d = ctx->frames_to_device(frames, n, fh, pitch, where, &rc);
+    if (rc) return rc;
+    if (tiled) {   // T net inputs per frame, merged into one list (tiles.hip)
+        if ((rc = ctx->face_letterbox_tiles(d, n, fh, fw, pitch, g))) return rc;
+        if ((rc = ctx->face_forward(n * g.T))) return rc;
+        if ((rc = ctx->face_post_tiled(n, fh, fw, g, t))) return rc;
+        return ctx->box_finish(faces, n, t);
+    }
+    if ((rc = ctx->face_letterbox(d, n, fh, fw, pitch))) return rc;
+    if ((rc = ctx->face_forward(n))) return rc;
+    if ((rc = ctx->face_post(n, fh, fw, t))) return rc;
+    return ctx->box_finish(faces, n, t);
+}
+
+int vd_detect_plates(vd_ctx* h, const uint8_t* frames, int n, int fh, int fw, size_t pitch, int where,
+                     vd_boxes* plates) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (!ctx->plate.loaded) return vd_set_error(VD_ERR_STATE, "plate weights not loaded");
+    int rc = ctx->check_frames(n, fh, fw, pitch);
+    if (rc) return rc;
+    BoxTargets t;
+    rc = ctx->box_targets(plates, n, t);
+    if (rc) return rc;
+    const uint8_t* d = ctx->frames_to_device(frames, n, fh, pitch, where, &rc);
+    if (rc) return rc;
+    if ((rc = vd_plate_forward(*ctx, d, n, fh, fw, pitch))) return rc;
+    if ((rc = vd_plate_post(*ctx, n, fh, fw, t))) return rc;
+    return ctx->box_finish(plates, n, t);
+}
+
+// The stand-alone blurring calls: out-of-place pass `pass` over the caller's frames and one box list
+// (host frames and lists are staged; the last five arguments are launch_shaped's).
+static int blur_entry(Ctx* ctx, const char* who, const uint8_t* in, uint8_t* out, int n, int fh, int fw, size_t pitch,
+                      int where, const vd_boxes* boxes, int pass, int level, int ksize, float sigma, int cells) {
+    if (!in || !out || !boxes) return vd_set_error(VD_ERR_ARG, "%s: null argument", who);
+    if (n <= 0 || fh <= 0 || fw <= 0 || pitch < (size_t)fw * 3) return vd_set_error(VD_ERR_ARG, "%s: bad geometry", who);
+    const size_t bytes = (size_t)n * fh * pitch;
+    if ((const void*)in == (const void*)out || (where == VD_DEVICE && vd_ranges_overlap(in, out, bytes)))
+        return vd_set_error(VD_ERR_ARG, "%s: out-of-place only (out must not overlap in)", who);
+    int rc = VD_OK;
+    const uint8_t* din = in;
+    uint8_t* dout = out;
+    if (where == VD_HOST) {
+        if ((rc = ctx->ensure_staging(&ctx->stage_in, &ctx->stage_in_bytes, bytes))) return rc;
+        if ((rc = ctx->ensure_staging(&ctx->stage_out, &ctx->stage_out_bytes, bytes))) return rc;
+        VD_CHECK_HIP(hipMemcpyAsync(ctx->stage_in, in, bytes, hipMemcpyHostToDevice, ctx->stream));
+        din = (const uint8_t*)ctx->stage_in;
+        dout = (uint8_t*)ctx->stage_out;
+    }
+    BoxListIn b;
+    if ((rc = ctx->box_list_in(who, boxes, n, false, 0, &b))) return rc;
+    if ((rc = ctx->launch_shaped(din, dout, n, fh, fw, pitch, b.cnt, b.xy, boxes->cap, nullptr, nullptr, 0, pass, level,
+                                 ksize, sigma, cells)))
+        return rc;
+    if (where == VD_HOST) {
+        VD_CHECK_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    } else if (b.staged) {
+        VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // staging reused by the next call
+    }
+    return VD_OK;
+}
+
+int vd_mosaic(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw, size_t pitch, int where,
+              const vd_boxes* boxes, int level, int mode) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (mode != VD_MOSAIC_OUT_OF_PLACE) return vd_set_error(VD_ERR_ARG, "unsupported mosaic mode %d", mode);
+    if (level <= 0) return vd_set_error(VD_ERR_ARG, "vd_mosaic: bad geometry");
+    return blur_entry(ctx, "vd_mosaic", in, out, n, fh, fw, pitch, where, boxes, Ctx::RECT_MOSAIC, level, 0, 0.f,
+                      ctx->cells);
+}
+
+int vd_blur(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw, size_t pitch, int where,
+            const vd_boxes* boxes, int ksize, float sigma) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    uint32_t q[VD_BLUR_KSIZE_MAX];
+    if (vd_blur_weights(ksize, sigma, q))
+        return vd_set_error(VD_ERR_ARG, "vd_blur: ksize must be odd in [3, %d] (got %d) and sigma finite",
+                            VD_BLUR_KSIZE_MAX, ksize);
+    return blur_entry(ctx, "vd_blur", in, out, n, fh, fw, pitch, where, boxes, Ctx::RECT_GAUSSIAN, 0, ksize, sigma, 0);
+}
+
+int vd_smooth(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw, size_t pitch, int where,
+              const vd_boxes* boxes, int level, int cells) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (cells < VD_CELLS_MIN || cells > VD_CELLS_MAX)
+        return vd_set_error(VD_ERR_ARG, "vd_smooth: cells %d outside [%d, %d]", cells, VD_CELLS_MIN, VD_CELLS_MAX);
+    if (level < 1 || level > 32768) return vd_set_error(VD_ERR_ARG, "vd_smooth: level %d outside [1, 32768]", level);
+    if (fh > 32768 || fw > 32768) return vd_set_error(VD_ERR_ARG, "vd_smooth: bad geometry (h, w in [1, 32768])");
+    return blur_entry(ctx, "vd_smooth", in, out, n, fh, fw, pitch, where, boxes, Ctx::RECT_SMOOTH, level, 0, 0.f, cells);
+}
+
+// A vd_process_lead call's part in the body it shares with vd_process: the blur step becomes
+// the lead step (lists, blur of the m emitted frames, ring update).
+struct LeadCall {
+    int flush, m;
+};
+
+static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh, int fw, size_t pitch, int where,
+                        int flags, vd_boxes* faces, vd_boxes* plates, const LeadCall* lc) {
+    const bool do_faces = flags & VD_PROC_FACES, do_plates = flags & VD_PROC_PLATES;
+    const bool do_mosaic = flags & VD_PROC_MOSAIC, mosaic_plates = flags & VD_PROC_MOSAIC_PLATES;
+    if (do_faces && !ctx->face.loaded) return vd_set_error(VD_ERR_STATE, "RetinaFace weights not loaded");
+    if (do_plates && !ctx->plate.loaded) return vd_set_error(VD_ERR_STATE, "plate weights not loaded");
+    if (mosaic_plates && !do_plates) return vd_set_error(VD_ERR_ARG, "MOSAIC_PLATES needs PLATES");
+    if (!lc && do_mosaic && !out) return vd_set_error(VD_ERR_ARG, "MOSAIC needs an output buffer");
+    if (do_mosaic && ctx->cells && ctx->cfg.blur_mode == VD_BLUR_GAUSSIAN &&
+        (fh > 32768 || fw > 32768 || ctx->cfg.mosaic_level < 1 || ctx->cfg.mosaic_level > 32768))
+        return vd_set_error(VD_ERR_ARG, "vd_process: the smooth blur (vd_cells) needs h, w <= 32768 and mosaic_level "
+                            "in [1, 32768]");
+    int rc = ctx->check_frames(n, fh, fw, pitch);
+    if (rc) return rc;
+    // tiled detection: T net inputs per frame through the face net, merged before anything reads them
+    const bool tiled = do_faces && ctx->tiles_on();
+    TileGrid tg;
+    if (tiled && (rc = ctx->tiles_check(n, fh, fw, &tg))) return rc;
+    // the mosaic is out of place (combine_detect.py:142 blurs a copy; each box reads the
+    // previous box's output, :247-249): its one-launch output pass gathers cell colours
+    // from `in` anywhere in the frame while other workgroups write `out`, so device
+    // frames that overlap would race (host frames are staged in separate buffers)
+    if (!lc && do_mosaic && where == VD_DEVICE && vd_ranges_overlap(in, out, (size_t)n * fh * pitch))
+        return vd_set_error(VD_ERR_ARG, "vd_process: MOSAIC is out-of-place (out must not overlap in)");
+    BoxTargets tf{}, tp{};
+    if (do_faces && (rc = ctx->box_targets(faces, n, tf))) return rc;
+    if (do_plates && plates) {   // plate box staging must not alias the face staging
+        if (!plates->count || !plates->xyxy || plates->cap <= 0)
+            return vd_set_error(VD_ERR_ARG, "vd_boxes needs count, xyxy, cap>0");
+        if (plates->where == VD_DEVICE) {
+            tp.cap = plates->cap; tp.count = plates->count; tp.xyxy = plates->xyxy; tp.xyxy_f = plates->xyxy_f;
+            tp.score = plates->score; tp.label = plates->label;
+        } else if ((rc = ctx->host_box_staging(&ctx->stage_box2, &ctx->stage_box2_bytes, plates->cap, n, tp))) {
+            return rc;
+        }
+    }
+    const uint8_t* d = ctx->frames_to_device(in, n, fh, pitch, where, &rc);
+    if (rc) return rc;
+    // Face and plate branches run concurrently (the reference submits them to two
+    // threads, combine_detect.py:214-217): plates on stream2, forked/joined by events.
+    const bool fork = do_faces && do_plates;
+    hipStream_t plate_stream = ctx->stream2;
+    // Both canvases from one read of the frames where the geometry allows (pre.hip
+    // letterbox_s2d_pair_kernel); the plate branch then forks after it.
+    bool paired = false;
+    if (fork && !tiled) {   // tiling: the tile letterbox fills the face canvases, the plate branch its own
+        LetterboxArgs fa, pa;
+        ctx->face_letterbox_args(d, n, fh, fw, pitch, &fa);
+        if (ctx->tune.lb_pair && vd_plate_letterbox_args(*ctx, d, n, fh, fw, pitch, &pa) == VD_OK &&
+            vd_letterbox_pair_ok(fa, pa)) {
+            ctx->t_begin(2, (double)n * (fa.nh * (double)fw * 3 + (double)(fa.oh / 2 + 1) * (fa.ow / 2 + 1) * (fa.out_f32 ? 64 : 32) +
+                                         (double)(pa.oh / 2 + 1) * (pa.ow / 2 + 1) * (pa.out_f32 ? 64 : 32)));
+            hipError_t e = vd_launch_letterbox_pair(fa, pa, ctx->stream);
+            ctx->t_end();
+            if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "letterbox pair: %s", hipGetErrorString(e));
+            paired = true;
+        }
+    }
+    // The plate branch may be held back until face stage `plate_stage` has been issued
+    // (its HBM-bound convs then overlap the MFMA-bound late face layers).
+    const int ps = ctx->tune.plate_stage;
+    ctx->fork_at = -1;
+    if (fork && ps > 0) {
+        ctx->fork_at = ps >= 5 ? (int)ctx->face.net.ops.size() : ctx->face.net.stage_end[std::min(ps, 4)];
+        if (ctx->fork_at <= 0) ctx->fork_at = -1;
+    }
+    if (fork && ctx->fork_at < 0) {
+        VD_CHECK_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
+        VD_CHECK_HIP(hipStreamWaitEvent(plate_stream, ctx->ev_fork, 0));
+    }
+    if (do_faces) {
+        if (tiled) {
+            if ((rc = ctx->face_letterbox_tiles(d, n, fh, fw, pitch, tg))) return rc;
+        } else if (!paired && (rc = ctx->face_letterbox(d, n, fh, fw, pitch))) {
+            return rc;
+        }
+        if ((rc = ctx->face_forward(tiled ? n * tg.T : n))) return rc;
+        if (ctx->fork_at > 0) {
+            ctx->fork_at = -1;
+            VD_CHECK_HIP(hipStreamWaitEvent(plate_stream, ctx->ev_fork, 0));
+        }
+        if ((rc = tiled ? ctx->face_post_tiled(n, fh, fw, tg, tf) : ctx->face_post(n, fh, fw, tf))) return rc;
+    }
+    if (do_plates) {
+        hipStream_t main = ctx->stream;
+        if (fork) ctx->stream = plate_stream;
+        rc = vd_plate_forward(*ctx, d, n, fh, fw, pitch, paired);
+        if (!rc) rc = vd_plate_post(*ctx, n, fh, fw, tp);
+        ctx->stream = main;
+        if (rc) return rc;
+    }
+    // the mosaic reads plate boxes only with MOSAIC_PLATES (the reference discards them,
+    // combine_detect.py:239): otherwise it runs on the face stream before the plate branch
+    // joins, beside the branch's last launches (option mosaic_early)
+    const bool mosaic_first = do_mosaic && fork && !mosaic_plates && ctx->tune.mosaic_early;
+    // every kept box, from the library's complete keep lists (the caller's arrays
+    // may hold fewer: cap), faces in NMS order then plates (combine_detect.py:241-249)
+    const PostScratch& fp = ctx->face.post;
+    const PostScratch& pp = ctx->plate.post;
+    const TileMergeArgs& tm = ctx->tiles_last;   // tiling: the merged rows are the face list
+    const int* c0 = do_faces ? (tiled ? tm.m_count : fp.kcount) : nullptr;
+    const int* x0 = do_faces ? (tiled ? tm.m_xyxy : fp.kxyxy) : nullptr;
+    const int* c1 = mosaic_plates ? pp.kcount : nullptr;
+    const int* x1 = mosaic_plates ? pp.kxyxy : nullptr;
+    int k0 = do_faces ? (tiled ? tm.mcap : fp.kcap) : 0, k1 = mosaic_plates ? pp.kcap : 0;
+    const int* dc0 = c0; const int* dx0 = x0; const int* dc1 = c1; const int* dx1 = x1;
+    int dk0 = k0, dk1 = k1;                        // D as detected (rescue: E): what the lead step matches on
+    // weak-detection rescue: the lists become E = D ++ R in merged rows (one step, before the hold);
+    // the rescue history is updated whether or not anything is blurred
+    auto rescue = [&]() -> int {
+        if (!ctx->rescue_on() || (!c0 && !c1)) return VD_OK;
+        RescueArgs a{};
+        a.cnt0 = c0; a.xy0 = x0; a.cap0 = k0; a.all0 = c0 && ctx->rescue_low[0] > 0.f ? fp.kall : nullptr;
+        a.cnt1 = c1; a.xy1 = x1; a.cap1 = k1; a.all1 = c1 && ctx->rescue_low[1] > 0.f ? pp.kall : nullptr;
+        int r = ctx->launch_rescue(n, fh, fw, a);
+        if (r) return r;
+        dc0 = c0 = ctx->rescue_last.e_count; dx0 = x0 = ctx->rescue_last.e_xy; dk0 = k0 = ctx->rescue_last.ecap;
+        dc1 = dx1 = c1 = x1 = nullptr; dk1 = k1 = 0;
+        return VD_OK;
+    };
+    // box hold: the blur list becomes B = D ++ H in merged rows (one launch, after the lists
+    // it reads are complete); the history is updated whether or not anything is blurred
+    auto hold = [&]() -> int {
+        if (!ctx->hold.K || (!c0 && !c1)) return VD_OK;
+        int r = ctx->launch_hold(n, fh, fw, c0, x0, k0, c1, x1, k1);
+        if (r) return r;
+        c0 = ctx->hold_last.m_count; x0 = ctx->hold_last.m_xy; k0 = ctx->hold_last.mcap;
+        c1 = x1 = nullptr; k1 = 0;
+        return VD_OK;
+    };
+    auto mosaic = [&]() -> int {
+        uint8_t* dout = out;
+        size_t bytes = (size_t)(lc ? lc->m : n) * fh * pitch;
+        if (where == VD_HOST) {
+            int r = ctx->ensure_staging(&ctx->stage_out, &ctx->stage_out_bytes, std::max(bytes, (size_t)1));
+            if (r) return r;
+            dout = (uint8_t*)ctx->stage_out;
+        }
+        if (lc) {   // look-ahead hold: B = D ++ H ++ A of the frames whose look-ahead is complete
+            int r = ctx->lead_step(VD_LEAD_MODE_PIXELS, d, dout, n, fh, fw, pitch, lc->flush, dc0, dx0, dk0, dc1, dx1, dk1);
+            if (r) return r;
+            if (where == VD_HOST && bytes)
+                VD_CHECK_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
+            return VD_OK;
+        }
+        // mask shaping (vd_mask) acts here, after the hold merge, on the list being blurred only
+        int r = ctx->launch_cfg_pass(d, dout, n, fh, fw, pitch, c0, x0, k0, c1, x1, k1);
+        if (r) return r;
+        if (where == VD_HOST) VD_CHECK_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return VD_OK;
+    };
+    if (mosaic_first && ((rc = rescue()) || (rc = hold()) || (rc = mosaic()))) return rc;
+    if (fork) {
+        VD_CHECK_HIP(hipEventRecord(ctx->ev_join, plate_stream));
+        VD_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+    }
+    if (!mosaic_first && ((rc = rescue()) || (rc = hold()) || (do_mosaic && (rc = mosaic())))) return rc;
+    int rc2 = VD_OK;
+    if (do_faces) rc2 = ctx->box_finish(faces, n, tf);
+    if (do_plates) {
+        int rc3 = ctx->box_finish(plates, n, tp);
+        if (!rc2) rc2 = rc3;
+    }
+    if (where == VD_HOST) VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    return rc2;
+}
+
+int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw, size_t pitch, int where,
+               int flags, vd_boxes* faces, vd_boxes* plates) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (ctx->lead.J && (flags & VD_PROC_MOSAIC))
+        return vd_set_error(VD_ERR_STATE, "vd_process: MOSAIC in a look-ahead context would skip the led boxes "
+                            "(use vd_process_lead)");
+    if (ctx->lead.pend)
+        return vd_set_error(VD_ERR_STATE, "vd_process: %d frames are pending in the look-ahead ring (flush first)",
+                            ctx->lead.pend);
+    return process_impl(ctx, in, out, n, fh, fw, pitch, where, flags, faces, plates, nullptr);
+}
+
+int vd_process_lead(vd_ctx* h, const uint8_t* in, int n, int fh, int fw, size_t pitch, int where, int flags,
+                    vd_boxes* faces, vd_boxes* plates, uint8_t* out, int out_cap, int flush, int* n_out) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    const char* who = "vd_process_lead";
+    if (!ctx->lead.J) return vd_set_error(VD_ERR_STATE, "%s: look-ahead hold is off (vd_lead)", who);
+    if (!(flags & VD_PROC_MOSAIC)) return vd_set_error(VD_ERR_ARG, "%s: flags must include VD_PROC_MOSAIC", who);
+    if (!(flags & VD_PROC_FACES) && !(flags & VD_PROC_MOSAIC_PLATES))
+        return vd_set_error(VD_ERR_ARG, "%s: nothing to blur (FACES or MOSAIC_PLATES needed)", who);
+    if (where != VD_HOST && where != VD_DEVICE) return vd_set_error(VD_ERR_ARG, "%s: bad where", who);
+    if (out_cap < 0 || (n > 0 && !in)) return vd_set_error(VD_ERR_ARG, "%s: null input / negative out_cap", who);
+    if (pitch < (size_t)(fw > 0 ? fw : 0) * 3) return vd_set_error(VD_ERR_ARG, "%s: bad pitch", who);
+    if (n == 0 && flush && !ctx->lead.pend) {      // the end of an empty stream
+        if (n_out) *n_out = 0;
+        return VD_OK;
+    }
+    int rc = ctx->lead_check(who, VD_LEAD_MODE_PIXELS, n, fh, fw, pitch, flush);
+    if (rc) return rc;
+    const int m = ctx->lead.emit(n, flush);
+    if (m > out_cap)
+        return vd_set_error(VD_ERR_CAPACITY, "%s: %d frames to emit, out holds %d", who, m, out_cap);
+    if (m > 0 && !out) return vd_set_error(VD_ERR_ARG, "%s: MOSAIC needs an output buffer", who);
+    const size_t fb = (size_t)fh * pitch;
+    if (where == VD_DEVICE && n > 0 && m > 0) {
+        const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
+        if (a < b + (size_t)m * fb && b < a + (size_t)n * fb)
+            return vd_set_error(VD_ERR_ARG, "%s: out must not overlap in", who);
+    }
+    const LeadCall lc{flush, m};
+    if (n > 0) {
+        rc = process_impl(ctx, in, out, n, fh, fw, pitch, where, flags, faces, plates, &lc);
+    } else {      // flush alone: the pending frames leave, no detection
+        uint8_t* dout = out;
+        const size_t bytes = (size_t)m * fb;
+        if (where == VD_HOST) {
+            if ((rc = ctx->ensure_staging(&ctx->stage_out, &ctx->stage_out_bytes, bytes))) return rc;
+            dout = (uint8_t*)ctx->stage_out;
+        }
+        rc = ctx->lead_step(VD_LEAD_MODE_PIXELS, nullptr, dout, 0, fh, fw, pitch, 1, nullptr, nullptr, 0, nullptr, nullptr, 0);
+        if (!rc && where == VD_HOST) {
+            VD_CHECK_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
+            VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+        }
+    }
+    if (rc) return rc;
+    if (n_out) *n_out = m;
+    return VD_OK;
+}
+
+int vd_read_boxes(vd_ctx* h, int net, int n, vd_boxes* out) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    const PostScratch* ps = net == VD_NET_RETINAFACE ? &ctx->face.post : (net == VD_NET_YOLOV8N ? &ctx->plate.post : nullptr);
+    if (!ps) return vd_set_error(VD_ERR_ARG, "unknown net %d", net);
+    if (!ps->kcount) return vd_set_error(VD_ERR_STATE, "net %d not loaded", net);
+    if (!out || !out->count || !out->xyxy || out->cap <= 0) return vd_set_error(VD_ERR_ARG, "vd_boxes needs count, xyxy, cap>0");
+    // tiled detection: the face lists of the last call are the merged rows (tiles.hip)
+    const bool mg = net == VD_NET_RETINAFACE && ctx->face_rows_merged;
+    const TileMergeArgs& tm = ctx->tiles_last;
+    const int kn = mg ? ctx->tiles_kn : ps->kn, kcap = mg ? tm.mcap : ps->kcap;
+    const int* kcount = mg ? tm.m_count : ps->kcount;
+    const int* kxyxy = mg ? tm.m_xyxy : ps->kxyxy;
+    const float* kxyxy_f = mg ? tm.m_xyxy_f : ps->kxyxy_f;
+    const float* kscore = mg ? tm.m_score : ps->kscore;
+    const int* klabel = mg ? tm.m_label : ps->klabel;
+    if (n <= 0 || n > kn) return vd_set_error(VD_ERR_ARG, "n=%d outside [1, %d frames of the last call]", n, kn);
+    const hipMemcpyKind kind = out->where == VD_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const int w = std::min(out->cap, kcap);   // boxes per frame copied (beyond kcap nothing is ever kept)
+    const size_t dp = (size_t)out->cap, sp = (size_t)kcap;
+    VD_CHECK_HIP(hipMemcpyAsync(out->count, kcount, (size_t)n * 4, kind, ctx->stream));
+    VD_CHECK_HIP(hipMemcpy2DAsync(out->xyxy, dp * 16, kxyxy, sp * 16, (size_t)w * 16, n, kind, ctx->stream));
+    if (out->xyxy_f)
+        VD_CHECK_HIP(hipMemcpy2DAsync(out->xyxy_f, dp * 16, kxyxy_f, sp * 16, (size_t)w * 16, n, kind, ctx->stream));
+    if (out->score)
+        VD_CHECK_HIP(hipMemcpy2DAsync(out->score, dp * 4, kscore, sp * 4, (size_t)w * 4, n, kind, ctx->stream));
+    if (out->label)
+        VD_CHECK_HIP(hipMemcpy2DAsync(out->label, dp * 4, klabel, sp * 4, (size_t)w * 4, n, kind, ctx->stream));
+    if (out->where == VD_HOST) VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    return VD_OK;
+}
+
+int vd_mask(vd_ctx* h, int shape, int grow_pct) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (shape != VD_MASK_RECT && shape != VD_MASK_ELLIPSE)
+        return vd_set_error(VD_ERR_ARG, "vd_mask: shape %d (expected 0 = rect or 1 = ellipse)", shape);
+    if (grow_pct < 0 || grow_pct > VD_MASK_GROW_MAX)
+        return vd_set_error(VD_ERR_ARG, "vd_mask: grow_pct %d outside [0, %d]", grow_pct, VD_MASK_GROW_MAX);
+    ctx->mask_shape = shape;
+    ctx->mask_grow = grow_pct;
+    return VD_OK;
+}
+
+int vd_cells(vd_ctx* h, int cells) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (cells != 0 && (cells < VD_CELLS_MIN || cells > VD_CELLS_MAX))
+        return vd_set_error(VD_ERR_ARG, "vd_cells: %d (expected 0 = off or [%d, %d])", cells, VD_CELLS_MIN,
+                            VD_CELLS_MAX);
+    ctx->cells = cells;
+    return VD_OK;
+}
+
+int vd_cell_level(int W, int H, int level, int cells) {
+    if (level < 1 || (cells != 0 && (cells < VD_CELLS_MIN || cells > VD_CELLS_MAX)))
+        return vd_set_error(VD_ERR_ARG, "vd_cell_level: level >= 1 and cells 0 or in [%d, %d] required (got %d, %d)",
+                            VD_CELLS_MIN, VD_CELLS_MAX, level, cells);
+    return vd_cell_level_hd((long long)W, (long long)H, level, cells);
+}
+
+int vd_mask_boxes(vd_ctx* h, const vd_boxes* in, int n, vd_boxes* out) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (!out || !out->count || !out->xyxy || out->cap <= 0)
+        return vd_set_error(VD_ERR_ARG, "vd_mask_boxes: vd_boxes needs count, xyxy, cap>0");
+    if (n <= 0) return vd_set_error(VD_ERR_ARG, "vd_mask_boxes: n=%d", n);
+    BoxListIn b;
+    int rc = ctx->box_list_in("vd_mask_boxes", in, n, false, 0, &b);
+    if (rc) return rc;
+    // the blur path's kernel; whole rows are copied out, so entries past the count are zeroed
+    if ((rc = ctx->launch_mask_grow(n, b.cnt, b.xy, in->cap, nullptr, nullptr, 0, 1))) return rc;
+    const hipMemcpyKind kind = out->where == VD_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const size_t wb = (size_t)std::min(in->cap, out->cap) * 16;
+    VD_CHECK_HIP(hipMemcpyAsync(out->count, b.cnt, (size_t)n * 4, kind, ctx->stream));   // complete counts, as given
+    VD_CHECK_HIP(hipMemcpy2DAsync(out->xyxy, (size_t)out->cap * 16, ctx->mask_last.m_xy, (size_t)in->cap * 16, wb, n,
+                                  kind, ctx->stream));
+    if (b.staged || out->where == VD_HOST) VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // staging reused, host results
+    return VD_OK;
+}
+
+}  // extern "C"

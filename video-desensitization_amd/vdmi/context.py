@@ -337,39 +337,15 @@ class Context:
         check(self._lib.vd_detect_plates(self._h, p, n, h, w, pitch, where, ctypes.byref(s)))
         return self._complete(boxes, _lib.VD_NET_YOLOV8N, auto)
 
-    def mosaic(self, frames, boxes_xyxy, counts=None, level=None, out=None):
-        """Out-of-place mosaic. boxes_xyxy: int32 [n][cap][4] (host numpy) or a
-        HostBoxes/DeviceBoxes; counts: int32 [n] (host) when boxes_xyxy is an array."""
-        p, n, h, w, pitch, where, keep = _frames_arg(frames)
+    def _blur_args(self, frames, boxes_xyxy, counts, out, pitched):
+        """What mosaic() / blur() / smooth() share -> (the C call's arguments from `in` to `boxes`,
+        out, keepalive). boxes_xyxy: int32 [n][cap][4] (host numpy) with counts int32 [n], or a
+        HostBoxes / DeviceBoxes. pitched: a torch view with padded rows (big[:, :, :w]) is read
+        and written at its own row pitch, and a torch `out` must have the frames' layout."""
+        p, n, h, w, pitch, where, src = _frames_arg(frames, pitched=pitched)
         if isinstance(boxes_xyxy, (_lib.HostBoxes, DeviceBoxes)):
             s = boxes_xyxy.struct()
-        else:
-            xy = np.ascontiguousarray(boxes_xyxy, np.int32).reshape(n, -1, 4)
-            cnt = np.ascontiguousarray(counts if counts is not None else np.full(n, xy.shape[1]), np.int32)
-            cap = max(1, xy.shape[1])
-            if xy.shape[1] == 0:
-                xy = np.zeros((n, 1, 4), np.int32)
-            keep = (keep, xy, cnt)
-            s = _lib.vd_boxes(cap, _lib.VD_HOST, ptr(cnt), ptr(xy), None, None, None)
-        if out is None:
-            if where == _lib.VD_HOST:
-                out = np.empty((n, h, w, 3), np.uint8)
-            else:
-                import torch
-                out = torch.empty_like(frames)
-        optr = out.data_ptr() if _is_torch(out) else ptr(out)
-        check(self._lib.vd_mosaic(self._h, p, optr, n, h, w, pitch, where, ctypes.byref(s),
-                                  int(level or self.cfg.mosaic_level), _lib.VD_MOSAIC_OUT_OF_PLACE))
-        return out
-
-    def blur(self, frames, boxes_xyxy, counts=None, ksize=None, sigma=None, out=None):
-        """Out-of-place Gaussian blur of the boxes (vd_blur), the counterpart of mosaic():
-        the same frames / boxes_xyxy / counts forms. ksize / sigma default to the context's
-        blur_ksize / blur_sigma (31 / 0 in a pixelate context). A torch view with padded
-        rows (big[:, :, :w]) is read and written at its own row pitch."""
-        p, n, h, w, pitch, where, src = _frames_arg(frames, pitched=True)
-        if isinstance(boxes_xyxy, (_lib.HostBoxes, DeviceBoxes)):
-            s = boxes_xyxy.struct()
+            keep = (src, s)
         else:
             xy = np.ascontiguousarray(boxes_xyxy, np.int32).reshape(n, -1, 4)
             cnt = np.ascontiguousarray(counts if counts is not None else np.full(n, xy.shape[1]), np.int32)
@@ -377,6 +353,7 @@ class Context:
             if xy.shape[1] == 0:
                 xy = np.zeros((n, 1, 4), np.int32)
             s = _lib.vd_boxes(cap, _lib.VD_HOST, ptr(cnt), ptr(xy), None, None, None)
+            keep = (src, s, xy, cnt)
         if out is None:
             if pitch != w * 3:
                 raise ValueError("frames with padded rows need out= (a view with the same row pitch)")
@@ -384,20 +361,33 @@ class Context:
                 out = np.empty((n, h, w, 3), np.uint8)
             else:
                 import torch
-                out = torch.empty_like(src)
-        if _is_torch(out):
+                out = torch.empty_like(src if pitched else frames)
+        if pitched and _is_torch(out):
             packed = out.is_contiguous()
             if tuple(out.shape) != (n, h, w, 3) or not (packed or _row_padded(out)) or \
                     (w * 3 if packed else out.stride(1)) != pitch:
                 raise ValueError("out must be uint8 [n,h,w,3] with the frames' row pitch")
-            optr = out.data_ptr()
-        else:
-            optr = ptr(out)
+        optr = out.data_ptr() if _is_torch(out) else ptr(out)
+        return (p, optr, n, h, w, pitch, where, ctypes.byref(s)), out, keep
+
+    def mosaic(self, frames, boxes_xyxy, counts=None, level=None, out=None):
+        """Out-of-place mosaic. boxes_xyxy: int32 [n][cap][4] (host numpy) or a
+        HostBoxes/DeviceBoxes; counts: int32 [n] (host) when boxes_xyxy is an array."""
+        args, out, keep = self._blur_args(frames, boxes_xyxy, counts, out, pitched=False)
+        check(self._lib.vd_mosaic(self._h, *args, int(level or self.cfg.mosaic_level), _lib.VD_MOSAIC_OUT_OF_PLACE))
+        return out
+
+    def blur(self, frames, boxes_xyxy, counts=None, ksize=None, sigma=None, out=None):
+        """Out-of-place Gaussian blur of the boxes (vd_blur), the counterpart of mosaic():
+        the same frames / boxes_xyxy / counts forms. ksize / sigma default to the context's
+        blur_ksize / blur_sigma (31 / 0 in a pixelate context). A torch view with padded
+        rows (big[:, :, :w]) is read and written at its own row pitch."""
+        args, out, keep = self._blur_args(frames, boxes_xyxy, counts, out, pitched=True)
         if ksize is None:
             ksize = self.cfg.blur_ksize or 31
         if sigma is None:
             sigma = self.cfg.blur_sigma
-        check(self._lib.vd_blur(self._h, p, optr, n, h, w, pitch, where, ctypes.byref(s), int(ksize), float(sigma)))
+        check(self._lib.vd_blur(self._h, *args, int(ksize), float(sigma)))
         return out
 
     def smooth(self, frames, boxes_xyxy, counts=None, level=None, cells=None, out=None):
@@ -408,34 +398,8 @@ class Context:
         cells = _lib.check_cells(self.cells if cells is None else cells)
         if cells == 0:
             raise ValueError("smooth() needs cells in 2 .. 64 (the context's setting is 0: off)")
-        p, n, h, w, pitch, where, src = _frames_arg(frames, pitched=True)
-        if isinstance(boxes_xyxy, (_lib.HostBoxes, DeviceBoxes)):
-            s = boxes_xyxy.struct()
-        else:
-            xy = np.ascontiguousarray(boxes_xyxy, np.int32).reshape(n, -1, 4)
-            cnt = np.ascontiguousarray(counts if counts is not None else np.full(n, xy.shape[1]), np.int32)
-            cap = max(1, xy.shape[1])
-            if xy.shape[1] == 0:
-                xy = np.zeros((n, 1, 4), np.int32)
-            s = _lib.vd_boxes(cap, _lib.VD_HOST, ptr(cnt), ptr(xy), None, None, None)
-        if out is None:
-            if pitch != w * 3:
-                raise ValueError("frames with padded rows need out= (a view with the same row pitch)")
-            if where == _lib.VD_HOST:
-                out = np.empty((n, h, w, 3), np.uint8)
-            else:
-                import torch
-                out = torch.empty_like(src)
-        if _is_torch(out):
-            packed = out.is_contiguous()
-            if tuple(out.shape) != (n, h, w, 3) or not (packed or _row_padded(out)) or \
-                    (w * 3 if packed else out.stride(1)) != pitch:
-                raise ValueError("out must be uint8 [n,h,w,3] with the frames' row pitch")
-            optr = out.data_ptr()
-        else:
-            optr = ptr(out)
-        check(self._lib.vd_smooth(self._h, p, optr, n, h, w, pitch, where, ctypes.byref(s),
-                                  int(level or self.cfg.mosaic_level), cells))
+        args, out, keep = self._blur_args(frames, boxes_xyxy, counts, out, pitched=True)
+        check(self._lib.vd_smooth(self._h, *args, int(level or self.cfg.mosaic_level), cells))
         return out
 
     def process(self, frames, out=None, faces=None, plates=None, flags=None):
@@ -488,14 +452,7 @@ class Context:
         largest list) holding every frame's blur list, the frame's own boxes then the held
         ones, label = age (0: own; a: last seen a frames ago). The context's history is
         updated as by process()."""
-        if isinstance(boxes, (_lib.HostBoxes, DeviceBoxes)):
-            det = boxes
-        else:
-            lists = [np.asarray(b, np.int32).reshape(-1, 4) for b in boxes]
-            det = _lib.HostBoxes(len(lists), max(1, max((len(b) for b in lists), default=1)))
-            for i, b in enumerate(lists):
-                det.count[i] = len(b)
-                det.xyxy[i, :len(b)] = b
+        det = self._box_lists(boxes)
         n = det.n
         ds = det.struct()
         if out is not None:
@@ -534,18 +491,23 @@ class Context:
         call (vd_read_held) as HostBoxes; cap defaults to the largest count. out: a
         HostBoxes / DeviceBoxes to fill instead (a device target is queued on the
         context stream, no host wait)."""
+        return self._read_sized(lambda s: self._lib.vd_read_held(self._h, n, s), n, cap, out)
+
+    def _read_sized(self, call, n, cap, out):
+        """A reader's lists of frames [0, n): call(vd_boxes*) fills `out`, or a HostBoxes of
+        `cap` boxes per frame; cap None: the counts are read first and cap is the largest."""
         if out is not None:
             s = out.struct()
-            check(self._lib.vd_read_held(self._h, n, ctypes.byref(s)))
+            check(call(ctypes.byref(s)))
             return out
         if cap is None:
             cnt = _lib.HostBoxes(n, 1)
             s = cnt.struct()
-            check(self._lib.vd_read_held(self._h, n, ctypes.byref(s)))
+            check(call(ctypes.byref(s)))
             cap = max(1, int(cnt.count.max()))
         boxes = _lib.HostBoxes(n, cap)
         s = boxes.struct()
-        check(self._lib.vd_read_held(self._h, n, ctypes.byref(s)))
+        check(call(ctypes.byref(s)))
         return boxes
 
     # -- weak-detection rescue ------------------------------------------------------
@@ -558,10 +520,16 @@ class Context:
         self.rescue_low, self.plate_rescue_low, self.rescue_span = lo, plo, span
 
     @staticmethod
-    def _box_lists(boxes):
+    def _box_lists(boxes, none_if_empty=False):
+        """A HostBoxes / DeviceBoxes as it is; a list with one int [k][4] array per frame as
+        HostBoxes. none_if_empty: None or a list of no frames -> None."""
         if isinstance(boxes, (_lib.HostBoxes, DeviceBoxes)):
             return boxes
+        if boxes is None and none_if_empty:
+            return None
         lists = [np.asarray(b, np.int32).reshape(-1, 4) for b in boxes]
+        if none_if_empty and not lists:
+            return None
         det = _lib.HostBoxes(len(lists), max(1, max((len(b) for b in lists), default=1)))
         for i, b in enumerate(lists):
             det.count[i] = len(b)
@@ -592,19 +560,7 @@ class Context:
         if which not in ("rescued", "weak"):
             raise ValueError(f"which {which!r}: expected 'rescued' or 'weak'")
         w = 0 if which == "rescued" else 1
-        if out is not None:
-            s = out.struct()
-            check(self._lib.vd_read_rescue(self._h, net, n, w, ctypes.byref(s)))
-            return out
-        if cap is None:
-            cnt = _lib.HostBoxes(n, 1)
-            s = cnt.struct()
-            check(self._lib.vd_read_rescue(self._h, net, n, w, ctypes.byref(s)))
-            cap = max(1, int(cnt.count.max()))
-        boxes = _lib.HostBoxes(n, cap)
-        s = boxes.struct()
-        check(self._lib.vd_read_rescue(self._h, net, n, w, ctypes.byref(s)))
-        return boxes
+        return self._read_sized(lambda s: self._lib.vd_read_rescue(self._h, net, n, w, s), n, cap, out)
 
     # -- look-ahead hold -----------------------------------------------------------
     def set_lead(self, lead=0, lead_motion=False):
@@ -635,21 +591,9 @@ class Context:
         if which not in ("lead", "all"):
             raise ValueError(f"which {which!r}: expected 'lead' or 'all'")
         w = 0 if which == "lead" else 1
-        if out is not None:
-            s = out.struct()
-            check(self._lib.vd_read_lead(self._h, n, w, ctypes.byref(s)))
-            return out
-        if n == 0:
+        if out is None and n == 0:
             return _lib.HostBoxes(0, 1)
-        if cap is None:
-            cnt = _lib.HostBoxes(n, 1)
-            s = cnt.struct()
-            check(self._lib.vd_read_lead(self._h, n, w, ctypes.byref(s)))
-            cap = max(1, int(cnt.count.max()))
-        boxes = _lib.HostBoxes(n, cap)
-        s = boxes.struct()
-        check(self._lib.vd_read_lead(self._h, n, w, ctypes.byref(s)))
-        return boxes
+        return self._read_sized(lambda s: self._lib.vd_read_lead(self._h, n, w, s), n, cap, out)
 
     def lead_lists(self, boxes, h, w, flush=False, out=None):
         """vd_lead_lists: the look-ahead step alone, for callers with their own detectors.
@@ -659,17 +603,8 @@ class Context:
         pending + n - delay), everything pending with flush) as HostBoxes of m rows, label 0 /
         +a / -a; with out= (room for pending + n rows) that target is filled and (out, m)
         returned."""
-        if boxes is None:
-            det, n = None, 0
-        elif isinstance(boxes, (_lib.HostBoxes, DeviceBoxes)):
-            det, n = boxes, boxes.n
-        else:
-            lists = [np.asarray(b, np.int32).reshape(-1, 4) for b in boxes]
-            n = len(lists)
-            det = _lib.HostBoxes(n, max(1, max((len(b) for b in lists), default=1))) if n else None
-            for i, b in enumerate(lists):
-                det.count[i] = len(b)
-                det.xyxy[i, :len(b)] = b
+        det = self._box_lists(boxes, none_if_empty=True)
+        n = det.n if det is not None else 0
         ds = det.struct() if det is not None else None
         m = ctypes.c_int(0)
         os_ = out.struct() if out is not None else None
@@ -777,14 +712,7 @@ class Context:
         or a list with one int [k][4] array per frame. Returns `out` (default: host lists for
         host boxes, a DeviceBoxes for device boxes, of the same cap): counts as given, xyxy
         grown, nothing else written."""
-        if isinstance(boxes, (_lib.HostBoxes, DeviceBoxes)):
-            src = boxes
-        else:
-            lists = [np.asarray(b, np.int32).reshape(-1, 4) for b in boxes]
-            src = _lib.HostBoxes(len(lists), max(1, max((len(b) for b in lists), default=1)))
-            for i, b in enumerate(lists):
-                src.count[i] = len(b)
-                src.xyxy[i, :len(b)] = b
+        src = self._box_lists(boxes)
         if out is None:
             out = (DeviceBoxes(src.n, src.cap, src.xyxy.device) if isinstance(src, DeviceBoxes)
                    else _lib.HostBoxes(src.n, src.cap))
