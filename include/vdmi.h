@@ -32,6 +32,9 @@
  *                                   no reference equivalent: the reference blurs the detector's rectangle)
  *   vd_cells / vd_smooth / vd_cell_level: blur strength that follows the box size (at most N cells across a
  *                                   box; no reference equivalent: the reference's cell is level px for every box)
+ *   vd_process_nv12 / vd_mosaic_nv12 / vd_nv12_to_rgb: the same path on NV12 video surfaces (vd_nv12: what a
+ *                                   decoder hands out and an encoder takes back; no reference equivalent: the
+ *                                   reference works on the RGB frames of ffmpeg-split images)
  *   vd_read_boxes                <- the complete per-frame box lists the reference's
  *                                   loop iterates (combine_detect.py:241-249), past any cap
  *   vd_sync / vd_last_error / vd_destroy: runtime plumbing (no reference equivalent;
@@ -40,7 +43,8 @@
  *                                   Python wrapper).
  *
  * Conventions: plain pointers and sizes only. Frames are uint8 RGB, HxWx3,
- * row pitch in bytes, frame i at base + i*h*pitch. `where` says whether a
+ * row pitch in bytes, frame i at base + i*h*pitch (the *_nv12 entries: NV12
+ * surfaces described by a vd_nv12). `where` says whether a
  * pointer is host (VD_HOST) or device (VD_DEVICE) memory of the context's GPU.
  * The caller owns frames and box arrays; the library owns weights, device
  * workspace and its stream. No pointer is retained past a call. Calls are
@@ -611,13 +615,83 @@ int vd_tiles(vd_ctx* ctx, int rows, int cols, int overlap_pct);
  * or before the RetinaFace weights are loaded; n*T > cfg.max_batch: VD_ERR_ARG. */
 int vd_tiles_merge(vd_ctx* ctx, const vd_boxes* lists, int n, int h, int w, vd_boxes* out);
 
+/* ---- NV12 frames: detect and pixelate video surfaces directly ---------------------
+ * A video decoder hands out NV12 surfaces and an encoder takes them back: a pitched luma plane
+ * followed by an interleaved half-resolution chroma plane. These entries take and write that
+ * format; no full-resolution RGB copy of a frame exists in device memory on this path. Integers
+ * only, so every result is defined to the bit.
+ *   layout   h and w are even. A frame is h luma rows of `pitch` bytes (pitch >= w) and, at
+ *            uv_offset >= h*pitch from the frame's first byte, h/2 chroma rows of `pitch` bytes holding
+ *            U, V interleaved: U(y,x) = uv[(y>>1)*pitch + (x & ~1)], V the next byte. Frame i lies at
+ *            base + i*frame_stride, frame_stride >= uv_offset + (h/2)*pitch. Decoders pad the luma
+ *            height (1080 becomes 1088), so uv_offset and frame_stride are explicit. matrix and range
+ *            of an output descriptor are ignored.
+ *   colour   rgb(y,x) = C(Y(y,x), U(y,x), V(y,x)): chroma is nearest (no chroma interpolation);
+ *            int32 arithmetic, >> arithmetic, clip8 clamps to [0, 255]:
+ *              t = cy*(Y - yoff) + 128
+ *              R = clip8((t + crv*(V-128)) >> 8)
+ *              G = clip8((t + cgu*(U-128) + cgv*(V-128)) >> 8)
+ *              B = clip8((t + cbu*(U-128)) >> 8)
+ *              limited: yoff 16, cy 298      full: yoff 0, cy 256
+ *                                 crv   cgu   cgv   cbu
+ *              BT.601 limited     409  -100  -208   516
+ *              BT.709 limited     459   -55  -136   541
+ *              BT.601 full        359   -88  -183   454
+ *              BT.709 full        403   -48  -120   475
+ *            each coefficient round(256 * real coefficient) for Kr/Kb = 0.299/0.114 and 0.2126/0.0722,
+ *            with 255/219 and 255/224 excursions in limited range. One function (csrc/nv12.h) is
+ *            compiled into the letterbox kernels and into vd_nv12_to_rgb.
+ *   detection  vd_process_nv12 returns exactly what vd_process returns on the RGB frames C(frame) in
+ *            the same context with the same flags -- count, xyxy, xyxy_f, score, label of faces and
+ *            plates, vd_read_boxes, vd_read_held, vd_read_rescue, the hold and rescue history --
+ *            because every canvas it builds is bit-identical to the RGB letterbox of C(frame). An NV12
+ *            call is a call of the context's one stream: it advances the same history as an RGB call
+ *            of the same (h, w).
+ *   pixelation  the list being blurred is what vd_process would blur (the complete keep lists, faces
+ *            then plates; E_t ++ H_t under rescue and hold; after mask growth; L(b) from vd_cell_level
+ *            under cells). For box b with luma clip c = clip(b) to [0,w] x [0,h]: an empty c touches
+ *            neither plane; luma is the mosaic above on the Y plane as an h x w one-channel image with
+ *            box c and level L(b); chroma is the same mosaic on the UV plane as an (h/2) x (w/2)
+ *            two-channel image with box cc = (c.x1>>1, c.y1>>1, (c.x2+1)>>1, (c.y2+1)>>1) and level
+ *            Lc = (L(b)+1)>>1. Every chroma sample that colours a hidden luma pixel is hidden, and a
+ *            chroma cell never spans fewer luma pixels than a luma cell. Per plane box j reads the
+ *            output of box j-1. Every output byte of both planes inside [0,w) of each row is written
+ *            exactly once; pad bytes beyond w and rows between the planes are not written.
+ * VD_ERR_ARG, each checked before any state changes: odd or non-positive h or w; pitch < w;
+ * uv_offset < h*pitch; frame_stride too small; unknown matrix or range; device in / out ranges that
+ * overlap (whole n*frame_stride ranges). Limits of this version (VD_ERR_STATE, the message names the
+ * setting): VD_PROC_MOSAIC / vd_mosaic_nv12 in a VD_BLUR_GAUSSIAN or VD_MASK_ELLIPSE context; any
+ * NV12 detection call with tiling on; the look-ahead hold has no NV12 entry point (vd_process_nv12
+ * obeys vd_process's rules in a lead context). One output launch per call for both planes
+ * (nv12.hip, timing family 1, work 2 * 1.5 * h * w per frame); the NV12 letterbox is family 2. */
+#define VD_NV12_BT601 0
+#define VD_NV12_BT709 1
+#define VD_NV12_LIMITED 0
+#define VD_NV12_FULL 1
+typedef struct vd_nv12 {
+    uint8_t* base; size_t pitch, uv_offset, frame_stride;
+    int32_t matrix;   /* VD_NV12_BT601 | VD_NV12_BT709 */
+    int32_t range;    /* VD_NV12_LIMITED | VD_NV12_FULL */
+} vd_nv12;
+/* vd_process on NV12 frames: flags and box contracts are vd_process's; `out` may be NULL without
+ * VD_PROC_MOSAIC. Host frames are staged as NV12 (1.5 B/px). */
+int vd_process_nv12(vd_ctx* ctx, const vd_nv12* in, const vd_nv12* out, int n, int h, int w, int where, int flags,
+                    vd_boxes* faces, vd_boxes* plates);
+/* vd_mosaic on NV12 frames: caller lists, with vd_mosaic's staging and capacity rules; the context's
+ * mask growth (rect) and cells apply as they do to vd_mosaic. */
+int vd_mosaic_nv12(vd_ctx* ctx, const vd_nv12* in, const vd_nv12* out, int n, int h, int w, int where,
+                   const vd_boxes* boxes, int level);
+/* C(frame) of n frames into packed RGB rows of rgb_pitch >= 3*w bytes, frame i at rgb + i*h*rgb_pitch
+ * (host only: no context, no GPU): the routine the kernels' conversion function is compiled from. */
+int vd_nv12_to_rgb(const vd_nv12* in, int n, int h, int w, uint8_t* rgb, size_t rgb_pitch);
+
 /* ---- instrumentation (bench / profiling) ---------------------------------- */
 /* When enabled, every launch of kernel family `fam` is bracketed by HIP events
  * on the context stream; vd_timing_read returns the summed duration (ms), the
  * launch count and the summed algorithmic work (FLOP or bytes) since the last
  * reset. Families: 0 = RetinaFace conv (implicit GEMM / streaming 1x1), 1 = mosaic
  * output pass (or the Gaussian blur's launches, or the smooth blur's copy and box pass; the mask's restore pass, work 0: its bytes follow
- * from the boxes), 2 = letterbox (the tile letterbox too), 3 = post (decode/NMS, box hold,
+ * from the boxes; the NV12 output pass, work 2 * 1.5 * h * w per frame), 2 = letterbox (the tile letterbox too; NV12: 1.5 B/px of source), 3 = post (decode/NMS, box hold,
  * look-ahead lists, mask grow, tile merge), 4 = other (the look-ahead pixel ring's copies), 5 = YOLOv8n plate
  * conv, 6 = mosaic cell table (box prep + walked cell colours). */
 int vd_timing_enable(vd_ctx* ctx, int on);
@@ -632,6 +706,8 @@ int vdt_letterbox(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w, size_
  * the tile letterbox kernel of the detect path: out_nhwc [n*T][H][W][cpad], canvas f*T+t. */
 int vdt_letterbox_tiles(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w, size_t pitch,
                         int where, float* out_nhwc, int cpad);
+/* vdt_letterbox for NV12 frames (vd_nv12), by the NV12 letterbox kernel of the product path. */
+int vdt_letterbox_nv12(vd_ctx* ctx, const vd_nv12* frames, int n, int h, int w, int where, float* out_nhwc, int cpad);
 /* Raw head outputs after the forward, host f32: loc [n][A][4], conf logits [n][A][2],
  * landm [n][A][10], A = number of anchors. */
 int vdt_forward_heads(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w, size_t pitch,

@@ -1,0 +1,223 @@
+"""NV12 against RGB at the bench shape: 64 synthetic 1080p frames already in HBM (fp32, faces |
+plates | mosaic, as bench.py's flagship step), all in one session.
+
+    python tools/nv12bench.py --parent-lib PATH/libvdmi.so [--steps 20] [--warmup 3]
+                              [--repeats 3] [--json profiles/nv12_1080p.json]
+
+Kinds, a child process per measurement (a fresh context, a fresh library), alternating, `--repeats`
+of each:
+    parent   the PARENT commit's build (through VDMI_LIB; the NV12 entry points are not bound),
+             Context.process on the RGB frames C(nv12 frames)
+    rgb      this build, the same call: (a) must equal `parent` within the parent's own repeat spread,
+             in the step time and in family 2 (the refactored letterbox wrappers are on this path)
+    nv12     this build, Context.process_nv12 on the NV12 frames: (b) family 1 (the output pass)
+             moves half the bytes of the RGB pass, family 2 reads 1.5 instead of 3 B/px of source
+    torch    (c, informational, one run) what a caller does without this: a torch NV12 -> RGB and
+             RGB -> NV12 round trip around Context.process
+Per run: ms/step in the steady state (warm-up first, then the steps ended by one synchronise), then
+event-timed steps of their own for the families' times, and for families 1 and 2 the share of the
+8 TB/s HBM peak their algorithmic bytes reach.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "video-desensitization_amd"))
+
+NV12_ENTRIES = ("vd_process_nv12", "vd_mosaic_nv12", "vd_nv12_to_rgb", "vdt_letterbox_nv12")
+KINDS = ("parent", "rgb", "nv12")
+HBM_PEAK = 8.0e12
+# BT.709 limited, real-valued: the frames only have to be plausible NV12, C() of them is the RGB input
+KR, KB = 0.2126, 0.0722
+
+
+def nv12_frames(B, H, W, dev):
+    """Synthetic NV12 frames on the device: synth's RGB scenes through a real-valued forward matrix,
+    chroma averaged over 2 x 2, frame by frame."""
+    import torch
+    from vdmi import synth
+    out = torch.empty((B, H * 3 // 2, W), dtype=torch.uint8, device=dev)
+    for i in range(B):
+        rgb = torch.from_numpy(synth.frames(1, H, W, seed=0, start=i)[0]).to(dev).float()
+        y = KR * rgb[..., 0] + (1 - KR - KB) * rgb[..., 1] + KB * rgb[..., 2]
+        cb = ((rgb[..., 2] - y) / (2 * (1 - KB))).reshape(H // 2, 2, W // 2, 2).mean(dim=(1, 3))
+        cr = ((rgb[..., 0] - y) / (2 * (1 - KR))).reshape(H // 2, 2, W // 2, 2).mean(dim=(1, 3))
+        out[i, :H] = (y * (219 / 255) + 16).round().clamp(0, 255).to(torch.uint8)
+        uv = torch.stack([cb, cr], dim=-1) * (224 / 255) + 128
+        out[i, H:] = uv.round().clamp(0, 255).to(torch.uint8).reshape(H // 2, W)
+    return out
+
+
+def torch_to_rgb(nv, H, W):
+    """What a caller writes today (float, full-frame passes): NV12 -> RGB."""
+    import torch
+    y = (nv[:, :H].float() - 16) * (255 / 219)
+    uv = nv[:, H:].reshape(-1, H // 2, W // 2, 2).float() - 128
+    uv = uv.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2) * (255 / 224)
+    r = y + 2 * (1 - KR) * uv[..., 1]
+    b = y + 2 * (1 - KB) * uv[..., 0]
+    g = (y - KR * r - KB * b) / (1 - KR - KB)
+    return torch.stack([r, g, b], dim=-1).round().clamp(0, 255).to(torch.uint8)
+
+
+def torch_to_nv12(rgb, out, H, W):
+    import torch
+    f = rgb.float()
+    y = KR * f[..., 0] + (1 - KR - KB) * f[..., 1] + KB * f[..., 2]
+    n = rgb.shape[0]
+    cb = ((f[..., 2] - y) / (2 * (1 - KB))).reshape(n, H // 2, 2, W // 2, 2).mean(dim=(2, 4))
+    cr = ((f[..., 0] - y) / (2 * (1 - KR))).reshape(n, H // 2, 2, W // 2, 2).mean(dim=(2, 4))
+    out[:, :H] = (y * (219 / 255) + 16).round().clamp(0, 255).to(torch.uint8)
+    out[:, H:] = (torch.stack([cb, cr], dim=-1) * (224 / 255) + 128).round().clamp(0, 255).to(torch.uint8).reshape(n, H // 2, W)
+
+
+def one(a):
+    """A single measurement in this process: --one parent | rgb | nv12 | torch."""
+    import torch
+    from vdmi import _lib
+    if a.one == "parent":    # the parent's build does not export the NV12 entry points
+        _lib.SIGNATURES = [s for s in _lib.SIGNATURES if s[0] not in NV12_ENTRIES]
+    import vdmi
+    from vdmi import weights
+    B, H, W = a.batch, 1080, 1920
+    dev = torch.device("cuda:0")
+    nv = nv12_frames(B, H, W, dev)
+    flags = _lib.VD_PROC_FACES | _lib.VD_PROC_PLATES | _lib.VD_PROC_MOSAIC
+    ctx = vdmi.Context(device=0, precision="fp32", max_batch=B)
+    ctx.load_weights(_lib.VD_NET_RETINAFACE, weights.retinaface_state_dict(0))
+    ctx.load_weights(_lib.VD_NET_YOLOV8N, weights.yolov8n_state_dict(0))
+    faces, plates = vdmi.DeviceBoxes(B, 256, dev), vdmi.DeviceBoxes(B, 256, dev)
+    if a.one == "nv12":
+        out = torch.empty_like(nv)
+
+        def step():
+            ctx.process_nv12(nv, out, faces=faces, plates=plates, flags=flags)
+    else:
+        # C(nv12 frames) by the header's BT.709 limited table in int32 tensors (arithmetic shifts), frame by
+        # frame: the same pixels for every RGB kind (the parent's build has no vd_nv12_to_rgb)
+        rgb = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+        for i in range(B):
+            uv = nv[i, H:].reshape(H // 2, W // 2, 2).to(torch.int32) - 128
+            uv = uv.repeat_interleave(2, dim=0).repeat_interleave(2, dim=1)
+            u, v = uv[..., 0], uv[..., 1]
+            tt = 298 * (nv[i, :H].to(torch.int32) - 16) + 128
+            px = torch.stack([(tt + 459 * v) >> 8, (tt - 55 * u - 136 * v) >> 8, (tt + 541 * u) >> 8], dim=-1)
+            rgb[i] = px.clamp(0, 255).to(torch.uint8)
+        out = torch.empty_like(rgb)
+        if a.one == "torch":
+            back = torch.empty_like(nv)
+
+            def step():
+                ctx.process(torch_to_rgb(nv, H, W), out, faces=faces, plates=plates, flags=flags)
+                ctx.sync()                         # the torch passes run on torch's stream
+                torch_to_nv12(out, back, H, W)
+                torch.cuda.synchronize()
+        else:
+            def step():
+                ctx.process(rgb, out, faces=faces, plates=plates, flags=flags)
+    torch.cuda.synchronize()
+    for _ in range(max(a.warmup, 1)):
+        step()
+    ctx.sync()
+    t0 = time.perf_counter()
+    for _ in range(a.steps):
+        step()
+    ctx.sync()
+    ms = (time.perf_counter() - t0) * 1e3 / a.steps
+    r = {"ms_per_step": round(ms, 3), "frames_per_s": round(B / ms * 1e3, 1),
+         "faces_per_frame": float(faces.count.float().mean().item()),
+         "plates_per_frame": float(plates.count.float().mean().item())}
+    ctx.timing(True)         # events around every launch slow the step: steps of their own
+    ctx.timing_reset()
+    for _ in range(a.fam_steps):
+        step()
+    fam = [ctx.timing_read(f) for f in range(7)]
+    r["family_ms_per_step"] = [round(t / a.fam_steps, 4) for t, _, _ in fam]
+    for f, name in ((_lib.FAM_MOSAIC, "mosaic"), (_lib.FAM_LETTERBOX, "letterbox")):
+        t, launches, work = fam[f]
+        r[name + "_ms_per_step"] = round(t / a.fam_steps, 4)
+        r[name + "_launches_per_step"] = launches / a.fam_steps
+        r[name + "_bytes_per_step"] = work / a.fam_steps
+        r[name + "_share_of_peak"] = round(work / (t * 1e-3) / HBM_PEAK, 4) if t > 0 else None
+    ctx.timing(False)
+    ctx.close()
+    print("NV12BENCH " + json.dumps(r), flush=True)
+
+
+def child(a, which):
+    env = dict(os.environ)
+    if which == "parent":
+        env["VDMI_LIB"] = os.path.abspath(a.parent_lib)
+    else:
+        env.pop("VDMI_LIB", None)
+    cmd = [sys.executable, os.path.abspath(__file__), "--one", which, "--steps", str(a.steps), "--warmup",
+           str(a.warmup), "--batch", str(a.batch), "--fam-steps", str(a.fam_steps)]
+    p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=a.child_timeout)
+    if p.returncode != 0:
+        raise RuntimeError(f"{which} run failed ({p.returncode}):\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
+    for line in p.stdout.splitlines():
+        if line.startswith("NV12BENCH "):
+            return json.loads(line[len("NV12BENCH "):])
+    raise RuntimeError(f"{which} run printed no result:\n{p.stdout[-2000:]}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent-lib", help="libvdmi.so built from the parent commit")
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--fam-steps", type=int, default=5, help="event-timed steps behind the family figures")
+    ap.add_argument("--child-timeout", type=int, default=240)
+    ap.add_argument("--no-torch", action="store_true", help="skip the informational torch round trip")
+    ap.add_argument("--one", choices=KINDS + ("torch",), help="(internal) one measurement in this process")
+    ap.add_argument("--json", help="also write the result line to this file")
+    a = ap.parse_args()
+    if a.one:
+        return one(a)
+    if not a.parent_lib or not os.path.exists(a.parent_lib):
+        ap.error("--parent-lib: the parent commit's libvdmi.so is needed for the comparison")
+    runs = {k: [] for k in KINDS}
+    for _ in range(a.repeats):                   # parent, rgb, nv12, parent, rgb, nv12, ...
+        for which in KINDS:
+            runs[which].append(child(a, which))  # a failed child raises: nothing more is started
+    torch_run = None if a.no_torch else child(a, "torch")
+    mean = lambda v: round(sum(v) / len(v), 4)
+    col = lambda k, key: [r[key] for r in runs[k]]
+    res = {"what": "NV12 against RGB: process on C(frames) by the parent build and by this build, process_nv12 on "
+                   "the NV12 frames by this build",
+           "machine": "one MI355X, the runs alternating in one session, a process each",
+           "batch": a.batch, "frame": [1080, 1920], "precision": "fp32", "steps": a.steps, "warmup": a.warmup,
+           "hbm_peak_bytes_per_s": HBM_PEAK}
+    for k in KINDS:
+        res[k + "_ms_per_step"] = col(k, "ms_per_step")
+        res[k + "_mean"] = mean(col(k, "ms_per_step"))
+        for fam in ("mosaic", "letterbox"):
+            res[f"{k}_{fam}_ms"] = col(k, fam + "_ms_per_step")
+            res[f"{k}_{fam}_mean"] = mean(col(k, fam + "_ms_per_step"))
+            res[f"{k}_{fam}_share_of_peak"] = col(k, fam + "_share_of_peak")
+    res["parent_spread_ms"] = round(max(res["parent_ms_per_step"]) - min(res["parent_ms_per_step"]), 3)
+    res["rgb_minus_parent_ms"] = round(res["rgb_mean"] - res["parent_mean"], 3)
+    res["parent_letterbox_spread_ms"] = round(max(res["parent_letterbox_ms"]) - min(res["parent_letterbox_ms"]), 4)
+    res["rgb_minus_parent_letterbox_ms"] = round(res["rgb_letterbox_mean"] - res["parent_letterbox_mean"], 4)
+    res["nv12_minus_rgb_ms"] = round(res["nv12_mean"] - res["rgb_mean"], 3)
+    res["nv12_over_rgb_mosaic"] = round(res["nv12_mosaic_mean"] / res["rgb_mosaic_mean"], 4)
+    res["nv12_over_rgb_letterbox"] = round(res["nv12_letterbox_mean"] / res["rgb_letterbox_mean"], 4)
+    res["torch_round_trip"] = torch_run
+    res.update({k + "_runs": runs[k] for k in KINDS})
+    line = json.dumps(res)
+    print(line, flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

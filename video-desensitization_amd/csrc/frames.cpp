@@ -49,6 +49,74 @@ int Ctx::check_frames(int n, int h, int w, size_t pitch) {
     return VD_OK;
 }
 
+// ---- NV12 surfaces (include/vdmi.h at vd_nv12) ----
+int vd_nv12_check(const char* who, const vd_nv12* d, int n, int h, int w, bool colour) {
+    static const char* const rule[] = {"", "null descriptor or base", "n > 0 and even, positive h and w required",
+                                       "pitch < w (or >= 2^31)", "uv_offset < h * pitch (or >= 2^47)",
+                                       "frame_stride < uv_offset + (h/2) * pitch (or >= 2^47)", "unknown matrix",
+                                       "unknown range"};
+    const int r = vd_nv12_layout(d, n, h, w, colour);
+    if (!r) return VD_OK;
+    if (r == 1) return vd_set_error(VD_ERR_ARG, "%s: NV12 frames: %s", who, rule[r]);
+    return vd_set_error(VD_ERR_ARG, "%s: NV12 frames: %s (n=%d, %d x %d, pitch %zu, uv_offset %zu, frame_stride %zu, "
+                        "matrix %d, range %d)", who, rule[r], n, w, h, d->pitch, d->uv_offset, d->frame_stride, d->matrix,
+                        d->range);
+}
+
+// packed device staging of n surfaces: pitch w, chroma right behind the luma
+static Ctx::Nv12Dev nv12_packed(void* p, int h, int w) {
+    return Ctx::Nv12Dev{(uint8_t*)p, (size_t)w, (size_t)h * w, (size_t)h * w / 2 * 3};
+}
+
+int Ctx::nv12_in(const vd_nv12& d, int n, int h, int w, int where, Nv12Dev* o) {
+    if (where == VD_DEVICE) {
+        *o = Nv12Dev{d.base, d.pitch, d.uv_offset, d.frame_stride};
+        return VD_OK;
+    }
+    int rc = ensure_staging(&stage_in, &stage_in_bytes, (size_t)n * h * w / 2 * 3);
+    if (rc) return rc;
+    *o = nv12_packed(stage_in, h, w);
+    for (int f = 0; f < n; ++f) {   // [0, w) of every row of both planes: 1.5 B/px
+        const uint8_t* s = d.base + (size_t)f * d.frame_stride;
+        uint8_t* t = o->base + (size_t)f * o->stride;
+        VD_CHECK_HIP(hipMemcpy2DAsync(t, o->pitch, s, d.pitch, (size_t)w, h, hipMemcpyHostToDevice, stream));
+        VD_CHECK_HIP(hipMemcpy2DAsync(t + o->uv, o->pitch, s + d.uv_offset, d.pitch, (size_t)w, h / 2,
+                                      hipMemcpyHostToDevice, stream));
+    }
+    return VD_OK;
+}
+
+int Ctx::nv12_out_begin(const vd_nv12& d, int n, int h, int w, int where, Nv12Dev* o) {
+    if (where == VD_DEVICE) {
+        *o = Nv12Dev{d.base, d.pitch, d.uv_offset, d.frame_stride};
+        return VD_OK;
+    }
+    int rc = ensure_staging(&stage_out, &stage_out_bytes, (size_t)n * h * w / 2 * 3);
+    if (rc) return rc;
+    *o = nv12_packed(stage_out, h, w);
+    return VD_OK;
+}
+
+int Ctx::nv12_out_finish(const vd_nv12& d, const Nv12Dev& o, int n, int h, int w, int where) {
+    if (where == VD_DEVICE) return VD_OK;
+    for (int f = 0; f < n; ++f) {   // pad bytes and the rows between the planes are not written
+        uint8_t* t = d.base + (size_t)f * d.frame_stride;
+        const uint8_t* s = o.base + (size_t)f * o.stride;
+        VD_CHECK_HIP(hipMemcpy2DAsync(t, d.pitch, s, o.pitch, (size_t)w, h, hipMemcpyDeviceToHost, stream));
+        VD_CHECK_HIP(hipMemcpy2DAsync(t + d.uv_offset, d.pitch, s + o.uv, o.pitch, (size_t)w, h / 2,
+                                      hipMemcpyDeviceToHost, stream));
+    }
+    return VD_OK;
+}
+
+extern "C" int vd_nv12_to_rgb(const vd_nv12* in, int n, int h, int w, uint8_t* rgb, size_t rgb_pitch) {
+    int rc = vd_nv12_check("vd_nv12_to_rgb", in, n, h, w, true);
+    if (rc) return rc;
+    if (!rgb || rgb_pitch < (size_t)w * 3) return vd_set_error(VD_ERR_ARG, "vd_nv12_to_rgb: null rgb or rgb_pitch < 3 * w");
+    vd_nv12_to_rgb_host(in, n, h, w, rgb, rgb_pitch);
+    return VD_OK;
+}
+
 // Box outputs: kernels write straight into caller arrays when they are device
 // memory; host outputs go through ctx staging + one D2H at the end. `out` may be
 // NULL (no caller copy; the complete lists stay readable through vd_read_boxes).
@@ -150,7 +218,7 @@ int Ctx::rows_out(const HoldArgs& view, int n, int held_only, vd_boxes* out, con
 int Ctx::face_letterbox(const uint8_t* dframes, int n, int h, int w, size_t pitch) {
     LetterboxArgs a;
     face_letterbox_args(dframes, n, h, w, pitch, &a);
-    t_begin(2, (double)n * (a.nh * (double)w * 3 + (double)a.oh * a.ow * a.cpad * (f32 ? 4 : 2)));
+    t_begin(2, (double)n * (a.nh * (double)w * vd_src_bpp(a.nv) + (double)a.oh * a.ow * a.cpad * (f32 ? 4 : 2)));
     hipError_t e = vd_launch_letterbox(a, stream);
     t_end();
     if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "letterbox: %s", hipGetErrorString(e));
@@ -160,6 +228,7 @@ int Ctx::face_letterbox(const uint8_t* dframes, int n, int h, int w, size_t pitc
 void Ctx::face_letterbox_args(const uint8_t* dframes, int n, int h, int w, size_t pitch, LetterboxArgs* out) {
     LetterboxArgs a{};
     a.src = dframes; a.n = n; a.ih = h; a.iw = w; a.pitch = pitch;
+    a.nv = nv12_src;       // an NV12 call in flight: dframes / pitch describe the surfaces
     a.oh = face.in_h; a.ow = face.in_w;
     // utils/utils.py:9-13 (Python doubles)
     double scale = std::min((double)a.ow / w, (double)a.oh / h);

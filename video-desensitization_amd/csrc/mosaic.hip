@@ -30,6 +30,7 @@
 // clip_rect); everything else is as above. ncells == 0: `level` for every box, as before.
 #include "vd_kernel.h"
 #include "vd_math.h"
+#include "mosaic_map.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -120,29 +121,8 @@ __device__ __forceinline__ int4 clip_rect(const MosaicArgs& a, int f, int k, int
     return make_int4(x1, y1, x2, y2);
 }
 
-__device__ __forceinline__ bool in_rect(const int4 q, int y, int x) {
-    return x >= q.x && x < q.z && y >= q.y && y < q.w;
-}
-
-__device__ __forceinline__ double up_factor(int len, int s) {      // resizeNN up:   dst = len, src = s
-    return __ddiv_rn(1.0, __ddiv_rn((double)len, (double)s));
-}
-__device__ __forceinline__ double down_factor(int len, int s) {    // resizeNN down: dst = s, src = len
-    return __ddiv_rn(1.0, __ddiv_rn((double)s, (double)len));
-}
-
-// apply() of a box given as (rect, sw | sh << 16): bit-identical to prep_box + apply
-__device__ __forceinline__ void apply_rect(const int4 q, uint32_t sz, int& y, int& x) {
-    const int sw = (int)(sz & 0xFFFFu), sh = (int)(sz >> 16);
-    const int bw = q.z - q.x, bh = q.w - q.y;
-    const int ux = min((int)floor(VD_DMUL((double)(x - q.x), up_factor(bw, sw))), sw - 1);
-    const int dx = min((int)floor(VD_DMUL((double)ux, down_factor(bw, sw))), bw - 1);
-    const int uy = min((int)floor(VD_DMUL((double)(y - q.y), up_factor(bh, sh))), sh - 1);
-    const int dy = min((int)floor(VD_DMUL((double)uy, down_factor(bh, sh))), bh - 1);
-    x = q.x + dx;
-    y = q.y + dy;
-}
-
+// in_rect, up_factor, down_factor, apply_rect (mosaic_map.h): apply() of a box given as
+// (rect, sw | sh << 16), bit-identical to prep_box + apply
 
 // Highest set bit index < lim in a 256-bit mask, or -1.
 __device__ __forceinline__ int top_below(const uint64_t* m, int lim) {

@@ -286,6 +286,20 @@ struct Ctx {
     MaskArgs mask_last{};                         // the last grow launch (row pointers for the restore pass)
     // box-scaled strength (vd_cells): 0 = off, every launch and byte as before
     int cells = 0;
+    // NV12 frames (include/vdmi.h at vd_nv12; pre.hip, nv12.hip). nv12_src.on marks an NV12 call in
+    // flight: the letterbox argument builders hand it to the kernels, and `dframes` / `pitch` of the face
+    // and plate paths are then the first luma byte and the planes' row pitch. Nv12Scope clears it.
+    Nv12Src nv12_src{};
+    struct Nv12Dev { uint8_t* base; size_t pitch, uv, stride; };   // a batch of surfaces in device memory
+    // the caller's input surfaces on the device: as they are, or (host) staged packed in stage_in (1.5 B/px)
+    int nv12_in(const vd_nv12& d, int n, int h, int w, int where, Nv12Dev* o);
+    // where the output pass writes: the caller's surfaces, or (host) packed surfaces in stage_out ...
+    int nv12_out_begin(const vd_nv12& d, int n, int h, int w, int where, Nv12Dev* o);
+    // ... copied back plane by plane, [0, w) of every row only (queued; the caller synchronises)
+    int nv12_out_finish(const vd_nv12& d, const Nv12Dev& o, int n, int h, int w, int where);
+    // the NV12 output pass behind the mask growth and the cells setting (one launch, family 1)
+    int launch_mosaic_nv12(const Nv12Dev& in, const Nv12Dev& out, int n, int h, int w, const int* cnt0, const int* xy0,
+                           int cap0, const int* cnt1, const int* xy1, int cap1, int level, int cells);
     // tiled face detection (tiles.hip, pre.hip letterbox_tiles_kernel; vd_tiles): nothing is allocated
     // or launched while rows * cols == 1
     int tile_rows = 1, tile_cols = 1, tile_overlap = 0;
@@ -442,6 +456,23 @@ struct Ctx {
                   const int* cnt0, const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1);
     int lead_read(int n, int which, vd_boxes* out);   // merged rows -> caller lists (label 0, +a, -a)
 };
+
+// An NV12 call's scope: the context reads NV12 sources from here to the end of the entry point.
+struct Nv12Scope {
+    Ctx* c;
+    Nv12Scope(Ctx* ctx, const Ctx::Nv12Dev& d, int matrix, int range, bool on = true) : c(ctx) {
+        if (!on) return;
+        c->nv12_src.on = 1;
+        c->nv12_src.uv_offset = d.uv;
+        c->nv12_src.frame_stride = d.stride;
+        c->nv12_src.k = vd_nv12_coef(matrix, range);
+    }
+    ~Nv12Scope() { c->nv12_src = Nv12Src{}; }
+};
+// the layout rules of a vd_nv12 descriptor for n frames of h x w (colour: matrix and range too); VD_ERR_ARG
+int vd_nv12_check(const char* who, const vd_nv12* d, int n, int h, int w, bool colour);
+// bytes of source a letterbox reads per pixel of the frame rows it touches (timing work)
+static inline double vd_src_bpp(const Nv12Src& nv) { return nv.on ? 1.5 : 3.0; }
 
 // a host list whose count[i] exceeds cap names boxes the caller does not hold: refused, never skipped silently
 int vd_count_check(const char* who, const int* count, int rows, int cap);

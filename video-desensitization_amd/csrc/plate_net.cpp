@@ -374,6 +374,7 @@ int vd_plate_letterbox_args(Ctx& c, const uint8_t* d, int n, int h, int w, size_
         return vd_set_error(VD_ERR_ARG, "plate canvas %dx%d unsupported", ow, oh);
     LetterboxArgs a{};
     a.src = d; a.n = n; a.ih = h; a.iw = w; a.pitch = pitch;
+    a.nv = c.nv12_src;     // an NV12 call in flight: d / pitch describe the surfaces
     a.oh = oh; a.ow = ow; a.nh = nh; a.nw = nw; a.top = top; a.left = left;
     vd_resize_mode(h, w, nh, nw, &a.mode, &a.scale_x, &a.scale_y);
     a.pad_value = 114.f;
@@ -395,7 +396,7 @@ int vd_plate_forward(Ctx& c, const uint8_t* d, int n, int h, int w, size_t pitch
     if (!letterboxed) {
         const double obytes =
             P.s2d ? (double)(oh / 2 + 1) * (ow / 2 + 1) * (c.f32 ? 64 : 32) : (double)oh * ow * a.cpad * (c.f32 ? 4 : 2);
-        c.t_begin(2, (double)n * (a.nh * (double)w * 3 + obytes));
+        c.t_begin(2, (double)n * (a.nh * (double)w * vd_src_bpp(a.nv) + obytes));
         hipError_t e = vd_launch_letterbox(a, c.stream);
         c.t_end();
         if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "plate letterbox: %s", hipGetErrorString(e));

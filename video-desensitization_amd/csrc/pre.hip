@@ -37,34 +37,92 @@ __device__ __forceinline__ Tap linear_tap(int d, int ssize, double scale) {
     return t;
 }
 
+// ---- pixel sources: where the letterbox arithmetic takes a source pixel's three channels from.
+// A frame in global memory (get(y, x)) and a staged row in LDS (get(x)), each as three packed bytes
+// or as an NV12 surface converted by the library's one conversion (nv12.h) at the tap. Everything
+// below is written once against these and instantiated for both.
+struct FrameRgb {
+    const uint8_t* p; size_t pitch;
+    __device__ __forceinline__ void get(int y, int x, int o[3]) const {
+        const uint8_t* q = p + (size_t)y * pitch + x * 3;
+        o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
+    }
+    __device__ __forceinline__ static int row_bytes(int iw) { return (iw * 3 + 15) / 16 * 16; }   // a staged row
+};
+struct FrameNv12 {
+    const uint8_t* y; const uint8_t* uv; size_t pitch; Nv12Coef k;
+    __device__ __forceinline__ void get(int yy, int x, int o[3]) const {
+        const uint8_t* q = uv + (size_t)(yy >> 1) * pitch + (x & ~1);
+        vd_nv12_rgb(k, y[(size_t)yy * pitch + x], q[0], q[1], o);
+    }
+    // a staged row: the luma row, then (16-B aligned) its chroma row
+    __device__ __forceinline__ static int row_bytes(int iw) { return 2 * ((iw + 15) / 16 * 16); }
+};
+struct RowRgb {
+    const uint8_t* L;
+    __device__ __forceinline__ void get(int x, int o[3]) const { o[0] = L[x * 3]; o[1] = L[x * 3 + 1]; o[2] = L[x * 3 + 2]; }
+};
+struct RowNv12 {
+    const uint8_t* L; int uvo; Nv12Coef k;
+    __device__ __forceinline__ void get(int x, int o[3]) const {
+        const int c = uvo + (x & ~1);
+        vd_nv12_rgb(k, L[x], L[c], L[c + 1], o);
+    }
+};
+
+template <bool NV> struct SrcOf { using Frame = FrameRgb; using Row = RowRgb; };
+template <> struct SrcOf<true> { using Frame = FrameNv12; using Row = RowNv12; };
+
+// frame f of the batch
+template <bool NV>
+__device__ __forceinline__ typename SrcOf<NV>::Frame lb_frame(const LetterboxArgs& a, int f) {
+    if constexpr (NV) {
+        const uint8_t* b = a.src + (size_t)f * a.nv.frame_stride;
+        return FrameNv12{b, b + a.nv.uv_offset, a.pitch, a.nv.k};
+    } else {
+        return FrameRgb{a.src + (size_t)f * a.ih * a.pitch, a.pitch};
+    }
+}
+
+// staged row k of `lrow` (rows of RS bytes)
+template <bool NV>
+__device__ __forceinline__ typename SrcOf<NV>::Row lb_row(const LetterboxArgs& a, const uint8_t* lrow, int k, int RS) {
+    if constexpr (NV) return RowNv12{lrow + k * RS, RS / 2, a.nv.k};
+    else return RowRgb{lrow + k * RS};
+}
+
 // The 3 channels of resized pixel (y, x) (interpolation taps computed once).
-__device__ __forceinline__ void resized_px3(const LetterboxArgs& a, const uint8_t* img, int y, int x, int out[3]) {
+template <typename Frame>
+__device__ __forceinline__ void resized_px3(const LetterboxArgs& a, const Frame& img, int y, int x, int out[3]) {
     if (a.mode == LB_COPY) {
-        const uint8_t* p = img + (size_t)y * a.pitch + x * 3;
-        out[0] = p[0]; out[1] = p[1]; out[2] = p[2];
+        img.get(y, x, out);
         return;
     }
     if (a.mode == LB_AREA2) {
-        const uint8_t* p = img + (size_t)(2 * y) * a.pitch + (2 * x) * 3;
+        int p00[3], p01[3], p10[3], p11[3];
+        img.get(2 * y, 2 * x, p00); img.get(2 * y, 2 * x + 1, p01);
+        img.get(2 * y + 1, 2 * x, p10); img.get(2 * y + 1, 2 * x + 1, p11);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) out[c] = (p[c] + p[c + 3] + p[a.pitch + c] + p[a.pitch + c + 3] + 2) >> 2;
+        for (int c = 0; c < 3; ++c) out[c] = (p00[c] + p01[c] + p10[c] + p11[c] + 2) >> 2;
         return;
     }
     const Tap tx = linear_tap(x, a.iw, a.scale_x);
     const Tap ty = linear_tap(y, a.ih, a.scale_y);
-    const uint8_t* r0 = img + (size_t)ty.s0 * a.pitch;
-    const uint8_t* r1 = img + (size_t)ty.s1 * a.pitch;
+    int p00[3], p01[3], p10[3], p11[3];
+    img.get(ty.s0, tx.s0, p00); img.get(ty.s0, tx.s1, p01);
+    img.get(ty.s1, tx.s0, p10); img.get(ty.s1, tx.s1, p11);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        int d0 = r0[tx.s0 * 3 + c] * tx.a0 + r0[tx.s1 * 3 + c] * tx.a1;
-        int d1 = r1[tx.s0 * 3 + c] * tx.a0 + r1[tx.s1 * 3 + c] * tx.a1;
+        int d0 = p00[c] * tx.a0 + p01[c] * tx.a1;
+        int d1 = p10[c] * tx.a0 + p11[c] * tx.a1;
         int v = ((((d0 >> 4) * ty.a0) >> 16) + (((d1 >> 4) * ty.a1) >> 16) + 2) >> 2;
         out[c] = v < 0 ? 0 : (v > 255 ? 255 : v);
     }
 }
 
 // Normalised canvas pixel (y, x) (resized image or pad value), 3 channels.
-__device__ __forceinline__ void canvas_px(const LetterboxArgs& a, const uint8_t* img, int y, int x, float v[3]) {
+template <typename Frame>
+__device__ __forceinline__ void canvas_px(const LetterboxArgs& a, const Frame& img, int y, int x, float v[3]) {
     const int ry = y - a.top, rx = x - a.left;
     const bool inside = (unsigned)ry < (unsigned)a.nh && (unsigned)rx < (unsigned)a.nw;
     int p3[3] = {0, 0, 0};
@@ -105,7 +163,8 @@ __device__ __forceinline__ void store_s2d(const LetterboxArgs& a, size_t idx, co
 
 // Space-to-depth form (a.s2d): one thread per 2x2 canvas block, 32 B out.
 // (img: the frame's pixels; f: the canvas index in a.out)
-__device__ __forceinline__ void lb_s2d_block(const LetterboxArgs& a, const uint8_t* img, int f, int Y, int X) {
+template <typename Frame>
+__device__ __forceinline__ void lb_s2d_block(const LetterboxArgs& a, const Frame& img, int f, int Y, int X) {
     const int OW = a.ow / 2 + 1, OH = a.oh / 2 + 1;
     if (X >= OW) return;
     float t[16];
@@ -120,9 +179,10 @@ __device__ __forceinline__ void lb_s2d_block(const LetterboxArgs& a, const uint8
     store_s2d(a, ((size_t)f * OH + Y) * OW + X, t);
 }
 
+template <bool NV>
 __global__ __launch_bounds__(256) void letterbox_s2d_kernel(LetterboxArgs a) {
     const int f = blockIdx.z;
-    lb_s2d_block(a, a.src + (size_t)f * a.ih * a.pitch, f, blockIdx.y, blockIdx.x * 256 + threadIdx.x);
+    lb_s2d_block(a, lb_frame<NV>(a, f), f, blockIdx.y, blockIdx.x * 256 + threadIdx.x);
 }
 
 // Space-to-depth form with the source rows staged in LDS: one workgroup per
@@ -145,31 +205,32 @@ __device__ __forceinline__ void lb_src_rows(const LetterboxArgs& a, int y, int* 
     *r1 = ty->a1 ? ty->s1 : -1;
 }
 
-__device__ __forceinline__ void lb_px_lds(const LetterboxArgs& a, const uint8_t* L0, const uint8_t* L1, const Tap& ty,
+template <typename Row>
+__device__ __forceinline__ void lb_px_lds(const LetterboxArgs& a, const Row& L0, const Row& L1, const Tap& ty,
                                           int x, bool row_in, float v[3]) {
     const int rx = x - a.left;
     const bool inside = row_in && (unsigned)rx < (unsigned)a.nw;
     int p3[3] = {0, 0, 0};
     if (inside) {
         if (a.mode == LB_COPY) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) p3[c] = L0[rx * 3 + c];
+            L0.get(rx, p3);
         } else if (a.mode == LB_AREA2) {
+            int p00[3], p01[3], p10[3], p11[3];
+            L0.get(2 * rx, p00); L0.get(2 * rx + 1, p01); L1.get(2 * rx, p10); L1.get(2 * rx + 1, p11);
 #pragma unroll
-            for (int c = 0; c < 3; ++c)
-                p3[c] = (L0[6 * rx + c] + L0[6 * rx + c + 3] + L1[6 * rx + c] + L1[6 * rx + c + 3] + 2) >> 2;
+            for (int c = 0; c < 3; ++c) p3[c] = (p00[c] + p01[c] + p10[c] + p11[c] + 2) >> 2;
         } else if (a.gx_k > 0 && ty.a1 == 0) {
             // exact gather both ways (weights (1, 0): the bilinear sum below reduces to the
             // source byte exactly, ((4 p + 2) >> 2) = p), e.g. 1080p -> 640: column 3 rx + 1
-            const int sx = a.gx_k * rx + a.gx_c;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) p3[c] = L0[sx * 3 + c];
+            L0.get(a.gx_k * rx + a.gx_c, p3);
         } else {
             const Tap tx = linear_tap(rx, a.iw, a.scale_x);
+            int p00[3], p01[3], p10[3], p11[3];
+            L0.get(tx.s0, p00); L0.get(tx.s1, p01); L1.get(tx.s0, p10); L1.get(tx.s1, p11);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const int d0 = L0[tx.s0 * 3 + c] * tx.a0 + L0[tx.s1 * 3 + c] * tx.a1;
-                const int d1 = L1[tx.s0 * 3 + c] * tx.a0 + L1[tx.s1 * 3 + c] * tx.a1;
+                const int d0 = p00[c] * tx.a0 + p01[c] * tx.a1;
+                const int d1 = p10[c] * tx.a0 + p11[c] * tx.a1;
                 const int q = ((((d0 >> 4) * ty.a0) >> 16) + (((d1 >> 4) * ty.a1) >> 16) + 2) >> 2;
                 p3[c] = q < 0 ? 0 : (q > 255 ? 255 : q);
             }
@@ -183,30 +244,43 @@ __device__ __forceinline__ void lb_px_lds(const LetterboxArgs& a, const uint8_t*
     }
 }
 
+// rb bytes of a source row into LDS: 16-B loads where the row start is aligned
+__device__ __forceinline__ void lb_stage(uint8_t* dst, const uint8_t* src, int rb) {
+    const int nch = (rb + 15) / 16;
+    if (((uintptr_t)src & 15) == 0) {
+        for (int i = threadIdx.x; i < nch; i += 256) {
+            if (16 * i + 16 <= rb) *(uint4*)(dst + 16 * i) = *(const uint4*)(src + 16 * i);
+            else for (int b = 16 * i; b < rb; ++b) dst[b] = src[b];
+        }
+    } else {
+        for (int i = threadIdx.x; i < rb; i += 256) dst[i] = src[i];
+    }
+}
+
+// source row `row` of a frame into a staged-row slot: the pixels' bytes, or the luma row and its chroma row
+__device__ __forceinline__ void lb_stage_row(const LetterboxArgs& a, const FrameRgb& img, int row, uint8_t* dst) {
+    lb_stage(dst, img.p + (size_t)row * a.pitch, a.iw * 3);
+}
+__device__ __forceinline__ void lb_stage_row(const LetterboxArgs& a, const FrameNv12& img, int row, uint8_t* dst) {
+    lb_stage(dst, img.y + (size_t)row * a.pitch, a.iw);
+    lb_stage(dst + FrameNv12::row_bytes(a.iw) / 2, img.uv + (size_t)(row >> 1) * a.pitch, a.iw);   // iw is even
+}
+
 // block row Y of canvas f from the frame at img; lrow: 4 staged rows of RS bytes
-__device__ __forceinline__ void lb_s2d_lds_row(const LetterboxArgs& a, const uint8_t* img, int f, int Y, uint8_t* lrow) {
+template <bool NV>
+__device__ __forceinline__ void lb_s2d_lds_row(const LetterboxArgs& a, const typename SrcOf<NV>::Frame& img, int f, int Y,
+                                               uint8_t* lrow) {
     const int OW = a.ow / 2 + 1, OH = a.oh / 2 + 1;
     int rows[4];
     Tap ty[2];
     bool rin[2];
     lb_src_rows(a, 2 * Y - 1, &rows[0], &rows[1], &ty[0], &rin[0]);
     lb_src_rows(a, 2 * Y, &rows[2], &rows[3], &ty[1], &rin[1]);
-    const int rb = a.iw * 3;
-    const int nch = (rb + 15) / 16;
-    const int RS = nch * 16;
+    const int RS = SrcOf<NV>::Frame::row_bytes(a.iw);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         if (rows[k] < 0) continue;
-        const uint8_t* src = img + (size_t)rows[k] * a.pitch;
-        uint8_t* dst = lrow + k * RS;
-        if (((uintptr_t)src & 15) == 0) {
-            for (int i = threadIdx.x; i < nch; i += 256) {
-                if (16 * i + 16 <= rb) *(uint4*)(dst + 16 * i) = *(const uint4*)(src + 16 * i);
-                else for (int b = 16 * i; b < rb; ++b) dst[b] = src[b];
-            }
-        } else {
-            for (int i = threadIdx.x; i < rb; i += 256) dst[i] = src[i];
-        }
+        lb_stage_row(a, img, rows[k], lrow + k * RS);
     }
     __syncthreads();
     for (int X = threadIdx.x; X < OW; X += 256) {
@@ -218,7 +292,8 @@ __device__ __forceinline__ void lb_s2d_lds_row(const LetterboxArgs& a, const uin
             float v[3] = {0.f, 0.f, 0.f};   // conv zero padding outside the canvas
             const int y = 2 * Y + h - 1;
             if ((unsigned)y < (unsigned)a.oh && (unsigned)x < (unsigned)a.ow)
-                lb_px_lds(a, lrow + (2 * h) * RS, lrow + (2 * h + (rows[2 * h + 1] >= 0 ? 1 : 0)) * RS, ty[h], x, rin[h], v);
+                lb_px_lds(a, lb_row<NV>(a, lrow, 2 * h, RS), lb_row<NV>(a, lrow, 2 * h + (rows[2 * h + 1] >= 0 ? 1 : 0), RS),
+                          ty[h], x, rin[h], v);
             t[4 * s + 0] = v[0]; t[4 * s + 1] = v[1]; t[4 * s + 2] = v[2];
             t[4 * s + 3] = 0.f;
         }
@@ -226,10 +301,11 @@ __device__ __forceinline__ void lb_s2d_lds_row(const LetterboxArgs& a, const uin
     }
 }
 
+template <bool NV>
 __global__ __launch_bounds__(256) void letterbox_s2d_lds_kernel(LetterboxArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lrow[];   // 4 staged rows of RS bytes
     const int f = blockIdx.y;
-    lb_s2d_lds_row(a, a.src + (size_t)f * a.ih * a.pitch, f, blockIdx.x, lrow);
+    lb_s2d_lds_row<NV>(a, lb_frame<NV>(a, f), f, blockIdx.x, lrow);
 }
 
 // Two space-to-depth canvases of the same frames in one pass (the face and the
@@ -238,6 +314,7 @@ __global__ __launch_bounds__(256) void letterbox_s2d_lds_kernel(LetterboxArgs a)
 // canvas b; each source row is staged once and both canvases are written from it.
 // Per pixel the arithmetic is exactly letterbox_s2d_lds_kernel's for each canvas.
 // Block rows Y run over the union [y0, y0 + gridDim.x), X over [x0, x0 + nx).
+template <bool NV>
 __global__ __launch_bounds__(256) void letterbox_s2d_pair_kernel(LetterboxArgs a, LetterboxArgs b, int dY, int dX,
                                                                  int y0, int x0, int nx) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lrow[];
@@ -245,7 +322,7 @@ __global__ __launch_bounds__(256) void letterbox_s2d_pair_kernel(LetterboxArgs a
     const int Yb = Y - dY;
     const int OWa = a.ow / 2 + 1, OHa = a.oh / 2 + 1, OWb = b.ow / 2 + 1, OHb = b.oh / 2 + 1;
     const bool ya = (unsigned)Y < (unsigned)OHa, yb = (unsigned)Yb < (unsigned)OHb;
-    const uint8_t* img = a.src + (size_t)f * a.ih * a.pitch;
+    const typename SrcOf<NV>::Frame img = lb_frame<NV>(a, f);
     int ra[4] = {-1, -1, -1, -1}, rb[4] = {-1, -1, -1, -1};
     Tap tya[2], tyb[2];
     bool rina[2] = {false, false}, rinb[2] = {false, false};
@@ -257,24 +334,13 @@ __global__ __launch_bounds__(256) void letterbox_s2d_pair_kernel(LetterboxArgs a
         lb_src_rows(b, 2 * Yb - 1, &rb[0], &rb[1], &tyb[0], &rinb[0]);
         lb_src_rows(b, 2 * Yb, &rb[2], &rb[3], &tyb[1], &rinb[1]);
     }
-    const int rbytes = a.iw * 3;
-    const int nch = (rbytes + 15) / 16;
-    const int RS = nch * 16;
+    const int RS = SrcOf<NV>::Frame::row_bytes(a.iw);
     const bool st1[2] = {ra[1] >= 0 || rb[1] >= 0, ra[3] >= 0 || rb[3] >= 0};   // second rows staged
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int row = ra[k] >= 0 ? ra[k] : rb[k];   // the same source row when both canvases need one
         if (row < 0) continue;
-        const uint8_t* src = img + (size_t)row * a.pitch;
-        uint8_t* dst = lrow + k * RS;
-        if (((uintptr_t)src & 15) == 0) {
-            for (int i = threadIdx.x; i < nch; i += 256) {
-                if (16 * i + 16 <= rbytes) *(uint4*)(dst + 16 * i) = *(const uint4*)(src + 16 * i);
-                else for (int q = 16 * i; q < rbytes; ++q) dst[q] = src[q];
-            }
-        } else {
-            for (int i = threadIdx.x; i < rbytes; i += 256) dst[i] = src[i];
-        }
+        lb_stage_row(a, img, row, lrow + k * RS);
     }
     __syncthreads();
     for (int X = x0 + (int)threadIdx.x; X < x0 + nx; X += 256) {
@@ -293,7 +359,8 @@ __global__ __launch_bounds__(256) void letterbox_s2d_pair_kernel(LetterboxArgs a
                 float v[3] = {0.f, 0.f, 0.f};
                 const int y = 2 * YY + h - 1;
                 if ((unsigned)y < (unsigned)c.oh && (unsigned)x < (unsigned)c.ow)
-                    lb_px_lds(c, lrow + (2 * h) * RS, lrow + (2 * h + (st1[h] ? 1 : 0)) * RS, ty[h], x, rin[h], v);
+                    lb_px_lds(c, lb_row<NV>(c, lrow, 2 * h, RS), lb_row<NV>(c, lrow, 2 * h + (st1[h] ? 1 : 0), RS), ty[h], x,
+                              rin[h], v);
                 t[4 * s + 0] = v[0]; t[4 * s + 1] = v[1]; t[4 * s + 2] = v[2];
                 t[4 * s + 3] = 0.f;
             }
@@ -302,7 +369,8 @@ __global__ __launch_bounds__(256) void letterbox_s2d_pair_kernel(LetterboxArgs a
     }
 }
 
-__device__ __forceinline__ void lb_nhwc_px(const LetterboxArgs& a, const uint8_t* img, int f, int y, int x) {
+template <typename Frame>
+__device__ __forceinline__ void lb_nhwc_px(const LetterboxArgs& a, const Frame& img, int f, int y, int x) {
     if (x >= a.ow) return;
     float v[3];
     canvas_px(a, img, y, x, v);
@@ -329,9 +397,10 @@ __device__ __forceinline__ void lb_nhwc_px(const LetterboxArgs& a, const uint8_t
     }
 }
 
+template <bool NV>
 __global__ __launch_bounds__(256) void letterbox_kernel(LetterboxArgs a) {
     const int f = blockIdx.z;
-    lb_nhwc_px(a, a.src + (size_t)f * a.ih * a.pitch, f, blockIdx.y, blockIdx.x * 256 + threadIdx.x);
+    lb_nhwc_px(a, lb_frame<NV>(a, f), f, blockIdx.y, blockIdx.x * 256 + threadIdx.x);
 }
 
 // Tiled detection (tiles.hip, include/vdmi.h at vd_tiles): the n * T canvases of n frames in one
@@ -346,10 +415,10 @@ __global__ __launch_bounds__(256) void letterbox_tiles_kernel(LetterboxArgs w, L
     extern __shared__ __attribute__((aligned(16))) uint8_t lrow[];
     const int i = blockIdx.y, f = i / g.T, t = i - f * g.T;
     const LetterboxArgs& a = t ? tl : w;
-    const uint8_t* img = w.src + ((size_t)f * w.ih + g.y0[t]) * w.pitch + (size_t)g.x0[t] * 3;
+    const FrameRgb img{w.src + ((size_t)f * w.ih + g.y0[t]) * w.pitch + (size_t)g.x0[t] * 3, w.pitch};
     const int Y = blockIdx.x;
     if (a.s2d && a.iw * 3 <= LB_LDS_MAX) {
-        lb_s2d_lds_row(a, img, i, Y, lrow);
+        lb_s2d_lds_row<false>(a, img, i, Y, lrow);
     } else if (a.s2d) {
         for (int X = threadIdx.x; X < a.ow / 2 + 1; X += 256) lb_s2d_block(a, img, i, Y, X);
     } else {
@@ -414,8 +483,14 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const T* x, int xh, int
 
 // Same frames, both 16-bit (bf16 / fp16) space-to-depth canvases, the same resize
 // (nw, nh, filter) and even relative offsets of the pasted images.
+// bytes of one staged source row (RGB: the pixels; NV12: the luma row and its chroma row, 16-B aligned each);
+// at most LB_LDS_MAX whenever iw * 3 <= LB_LDS_MAX
+static size_t lb_row_bytes(const LetterboxArgs& a) {
+    return a.nv.on ? 2 * (size_t)((a.iw + 15) / 16 * 16) : (size_t)((a.iw * 3 + 15) / 16 * 16);
+}
+
 bool vd_letterbox_pair_ok(const LetterboxArgs& a, const LetterboxArgs& b) {
-    return a.s2d && b.s2d && a.src == b.src && a.n == b.n &&
+    return a.s2d && b.s2d && a.src == b.src && a.n == b.n && a.nv.on == b.nv.on &&
            a.ih == b.ih && a.iw == b.iw && a.pitch == b.pitch && a.iw * 3 <= LB_LDS_MAX && a.nw == b.nw &&
            a.nh == b.nh && a.mode == b.mode && a.scale_x == b.scale_x && a.scale_y == b.scale_y &&
            ((a.top - b.top) & 1) == 0 && ((a.left - b.left) & 1) == 0;
@@ -457,7 +532,9 @@ hipError_t vd_launch_letterbox_pair(const LetterboxArgs& a0, const LetterboxArgs
     lb_set_gather(b);
     if (!vd_letterbox_pair_ok(a, b)) return hipErrorInvalidValue;
     static const bool attr = [] {
-        (void)hipFuncSetAttribute((const void*)letterbox_s2d_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute((const void*)letterbox_s2d_pair_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  4 * LB_LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)letterbox_s2d_pair_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   4 * LB_LDS_MAX);
         return true;
     }();
@@ -465,8 +542,11 @@ hipError_t vd_launch_letterbox_pair(const LetterboxArgs& a0, const LetterboxArgs
     const int dY = (a.top - b.top) / 2, dX = (a.left - b.left) / 2;
     const int y0 = std::min(0, dY), y1 = std::max(a.oh / 2 + 1, b.oh / 2 + 1 + dY);
     const int x0 = std::min(0, dX), x1 = std::max(a.ow / 2 + 1, b.ow / 2 + 1 + dX);
-    const size_t lds = 4 * (size_t)((a.iw * 3 + 15) / 16 * 16);
-    hipLaunchKernelGGL(letterbox_s2d_pair_kernel, dim3(y1 - y0, a.n), dim3(256), lds, s, a, b, dY, dX, y0, x0, x1 - x0);
+    const size_t lds = 4 * lb_row_bytes(a);
+    if (a.nv.on)
+        hipLaunchKernelGGL(letterbox_s2d_pair_kernel<true>, dim3(y1 - y0, a.n), dim3(256), lds, s, a, b, dY, dX, y0, x0, x1 - x0);
+    else
+        hipLaunchKernelGGL(letterbox_s2d_pair_kernel<false>, dim3(y1 - y0, a.n), dim3(256), lds, s, a, b, dY, dX, y0, x0, x1 - x0);
     return hipGetLastError();
 }
 
@@ -475,29 +555,35 @@ hipError_t vd_launch_letterbox(const LetterboxArgs& a0, hipStream_t s) {
     lb_set_gather(a);
     if (a.s2d && a.iw * 3 <= LB_LDS_MAX) {
         static const bool attr = [] {
-            (void)hipFuncSetAttribute((const void*)letterbox_s2d_lds_kernel,
+            (void)hipFuncSetAttribute((const void*)letterbox_s2d_lds_kernel<false>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 4 * LB_LDS_MAX);
+            (void)hipFuncSetAttribute((const void*)letterbox_s2d_lds_kernel<true>,
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 4 * LB_LDS_MAX);
             return true;
         }();
         (void)attr;
-        const size_t lds = 4 * (size_t)((a.iw * 3 + 15) / 16 * 16);
+        const size_t lds = 4 * lb_row_bytes(a);
         dim3 grid(a.oh / 2 + 1, a.n);
-        hipLaunchKernelGGL(letterbox_s2d_lds_kernel, grid, dim3(256), lds, s, a);
+        if (a.nv.on) hipLaunchKernelGGL(letterbox_s2d_lds_kernel<true>, grid, dim3(256), lds, s, a);
+        else hipLaunchKernelGGL(letterbox_s2d_lds_kernel<false>, grid, dim3(256), lds, s, a);
         return hipGetLastError();
     }
     if (a.s2d) {
         dim3 grid((a.ow / 2 + 1 + 255) / 256, a.oh / 2 + 1, a.n);
-        hipLaunchKernelGGL(letterbox_s2d_kernel, grid, dim3(256), 0, s, a);
+        if (a.nv.on) hipLaunchKernelGGL(letterbox_s2d_kernel<true>, grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(letterbox_s2d_kernel<false>, grid, dim3(256), 0, s, a);
         return hipGetLastError();
     }
     dim3 grid((a.ow + 255) / 256, a.oh, a.n);
-    hipLaunchKernelGGL(letterbox_kernel, grid, dim3(256), 0, s, a);
+    if (a.nv.on) hipLaunchKernelGGL(letterbox_kernel<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(letterbox_kernel<false>, grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
 hipError_t vd_launch_letterbox_tiles(const LetterboxArgs& w0, const LetterboxArgs& t0, const TileGrid& g,
                                      hipStream_t s) {
     LetterboxArgs w = w0, t = t0;
+    if (w.nv.on || t.nv.on) return hipErrorInvalidValue;   // the tile letterbox reads packed RGB
     if (g.T < 2 || g.T > VD_TILE_INPUTS_MAX || w.n <= 0 || w.s2d != t.s2d || w.oh != t.oh || w.ow != t.ow ||
         t.ih != g.th || t.iw != g.tw)
         return hipErrorInvalidValue;

@@ -154,6 +154,30 @@ int Ctx::launch_cfg_pass(const uint8_t* in, uint8_t* out, int n, int h, int w, s
                          cfg.blur_ksize, cfg.blur_sigma, cells);
 }
 
+// The NV12 output pass (nv12.hip): what launch_shaped is to the RGB pixelation, without the ellipse
+// composite (refused at the entry points). The cell levels come from the grown boxes.
+int Ctx::launch_mosaic_nv12(const Nv12Dev& in, const Nv12Dev& out, int n, int h, int w, const int* cnt0, const int* xy0,
+                            int cap0, const int* cnt1, const int* xy1, int cap1, int level, int ncells) {
+    if (mask_on() && (cnt0 || cnt1)) {
+        int rc = launch_mask_grow(n, cnt0, xy0, cap0, cnt1, xy1, cap1);
+        if (rc) return rc;
+        cnt0 = mask_last.m_cnt; xy0 = mask_last.m_xy; cap0 = mask_last.mcap;
+        cnt1 = xy1 = nullptr; cap1 = 0;
+    }
+    Nv12MosaicArgs a{};
+    a.in = in.base; a.in_pitch = in.pitch; a.in_uv = in.uv; a.in_stride = in.stride;
+    a.out = out.base; a.out_pitch = out.pitch; a.out_uv = out.uv; a.out_stride = out.stride;
+    a.n = n; a.h = h; a.w = w;
+    a.cnt0 = cnt0; a.xy0 = xy0; a.cap0 = cap0;
+    a.cnt1 = cnt1; a.xy1 = xy1; a.cap1 = cap1;
+    a.level = level; a.cells = ncells;
+    t_begin(1, 2.0 * 1.5 * n * (double)h * w);
+    hipError_t e = vd_launch_mosaic_nv12(a, stream);
+    t_end();
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "nv12 mosaic: %s", hipGetErrorString(e));
+    return VD_OK;
+}
+
 extern "C" {
 
 int vd_detect(vd_ctx* h, const uint8_t* frames, int n, int fh, int fw, size_t pitch, int where, vd_boxes* faces) {
@@ -270,19 +294,26 @@ struct LeadCall {
     int flush, m;
 };
 
+// A vd_process_nv12 call's part in that body: the frames are NV12 surfaces (checked by the entry
+// point), so the letterbox and the output launches differ; `in` / `out` / `pitch` are not used.
+struct Nv12Call {
+    const vd_nv12* in; const vd_nv12* out;
+};
+
 static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh, int fw, size_t pitch, int where,
-                        int flags, vd_boxes* faces, vd_boxes* plates, const LeadCall* lc) {
+                        int flags, vd_boxes* faces, vd_boxes* plates, const LeadCall* lc,
+                        const Nv12Call* nv = nullptr) {
     const bool do_faces = flags & VD_PROC_FACES, do_plates = flags & VD_PROC_PLATES;
     const bool do_mosaic = flags & VD_PROC_MOSAIC, mosaic_plates = flags & VD_PROC_MOSAIC_PLATES;
     if (do_faces && !ctx->face.loaded) return vd_set_error(VD_ERR_STATE, "RetinaFace weights not loaded");
     if (do_plates && !ctx->plate.loaded) return vd_set_error(VD_ERR_STATE, "plate weights not loaded");
     if (mosaic_plates && !do_plates) return vd_set_error(VD_ERR_ARG, "MOSAIC_PLATES needs PLATES");
-    if (!lc && do_mosaic && !out) return vd_set_error(VD_ERR_ARG, "MOSAIC needs an output buffer");
+    if (!lc && !nv && do_mosaic && !out) return vd_set_error(VD_ERR_ARG, "MOSAIC needs an output buffer");
     if (do_mosaic && ctx->cells && ctx->cfg.blur_mode == VD_BLUR_GAUSSIAN &&
         (fh > 32768 || fw > 32768 || ctx->cfg.mosaic_level < 1 || ctx->cfg.mosaic_level > 32768))
         return vd_set_error(VD_ERR_ARG, "vd_process: the smooth blur (vd_cells) needs h, w <= 32768 and mosaic_level "
                             "in [1, 32768]");
-    int rc = ctx->check_frames(n, fh, fw, pitch);
+    int rc = nv ? ctx->check_frames(n, fh, fw, (size_t)fw * 3) : ctx->check_frames(n, fh, fw, pitch);   // NV12: n alone
     if (rc) return rc;
     // tiled detection: T net inputs per frame through the face net, merged before anything reads them
     const bool tiled = do_faces && ctx->tiles_on();
@@ -292,7 +323,7 @@ static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh
     // previous box's output, :247-249): its one-launch output pass gathers cell colours
     // from `in` anywhere in the frame while other workgroups write `out`, so device
     // frames that overlap would race (host frames are staged in separate buffers)
-    if (!lc && do_mosaic && where == VD_DEVICE && vd_ranges_overlap(in, out, (size_t)n * fh * pitch))
+    if (!lc && !nv && do_mosaic && where == VD_DEVICE && vd_ranges_overlap(in, out, (size_t)n * fh * pitch))
         return vd_set_error(VD_ERR_ARG, "vd_process: MOSAIC is out-of-place (out must not overlap in)");
     BoxTargets tf{}, tp{};
     if (do_faces && (rc = ctx->box_targets(faces, n, tf))) return rc;
@@ -306,8 +337,16 @@ static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh
             return rc;
         }
     }
-    const uint8_t* d = ctx->frames_to_device(in, n, fh, pitch, where, &rc);
-    if (rc) return rc;
+    const uint8_t* d = nullptr;
+    Ctx::Nv12Dev nin{}, nout{};
+    if (nv) {   // host surfaces are staged packed; from here d / pitch are the first luma byte and the planes' pitch
+        if ((rc = ctx->nv12_in(*nv->in, n, fh, fw, where, &nin))) return rc;
+        d = nin.base; pitch = nin.pitch;
+    } else {
+        d = ctx->frames_to_device(in, n, fh, pitch, where, &rc);
+        if (rc) return rc;
+    }
+    const Nv12Scope nv_scope(ctx, nin, nv ? nv->in->matrix : 0, nv ? nv->in->range : 0, nv != nullptr);
     // Face and plate branches run concurrently (the reference submits them to two
     // threads, combine_detect.py:214-217): plates on stream2, forked/joined by events.
     const bool fork = do_faces && do_plates;
@@ -320,7 +359,7 @@ static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh
         ctx->face_letterbox_args(d, n, fh, fw, pitch, &fa);
         if (ctx->tune.lb_pair && vd_plate_letterbox_args(*ctx, d, n, fh, fw, pitch, &pa) == VD_OK &&
             vd_letterbox_pair_ok(fa, pa)) {
-            ctx->t_begin(2, (double)n * (fa.nh * (double)fw * 3 + (double)(fa.oh / 2 + 1) * (fa.ow / 2 + 1) * (fa.out_f32 ? 64 : 32) +
+            ctx->t_begin(2, (double)n * (fa.nh * (double)fw * vd_src_bpp(fa.nv) + (double)(fa.oh / 2 + 1) * (fa.ow / 2 + 1) * (fa.out_f32 ? 64 : 32) +
                                          (double)(pa.oh / 2 + 1) * (pa.ow / 2 + 1) * (pa.out_f32 ? 64 : 32)));
             hipError_t e = vd_launch_letterbox_pair(fa, pa, ctx->stream);
             ctx->t_end();
@@ -401,6 +440,13 @@ static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh
         return VD_OK;
     };
     auto mosaic = [&]() -> int {
+        if (nv) {   // both planes in one launch (nv12.hip); host surfaces come back plane by plane
+            int r = ctx->nv12_out_begin(*nv->out, n, fh, fw, where, &nout);
+            if (r) return r;
+            if ((r = ctx->launch_mosaic_nv12(nin, nout, n, fh, fw, c0, x0, k0, c1, x1, k1, ctx->cfg.mosaic_level, ctx->cells)))
+                return r;
+            return ctx->nv12_out_finish(*nv->out, nout, n, fh, fw, where);
+        }
         uint8_t* dout = out;
         size_t bytes = (size_t)(lc ? lc->m : n) * fh * pitch;
         if (where == VD_HOST) {
@@ -448,6 +494,74 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
         return vd_set_error(VD_ERR_STATE, "vd_process: %d frames are pending in the look-ahead ring (flush first)",
                             ctx->lead.pend);
     return process_impl(ctx, in, out, n, fh, fw, pitch, where, flags, faces, plates, nullptr);
+}
+
+// ---- NV12 frames (include/vdmi.h at vd_nv12) ----
+// what every NV12 blurring call checks before anything changes: the descriptors, the limits of this
+// version, and (device) that the whole n * frame_stride ranges do not overlap
+static int nv12_blur_check(Ctx* ctx, const char* who, const vd_nv12* in, const vd_nv12* out, int n, int fh, int fw,
+                           int where, bool host_in_place) {
+    int rc = vd_nv12_check(who, out, n, fh, fw, false);
+    if (rc) return rc;
+    if (ctx->cfg.blur_mode == VD_BLUR_GAUSSIAN)
+        return vd_set_error(VD_ERR_STATE, "%s: blur_mode VD_BLUR_GAUSSIAN has no NV12 pass yet (pixelation only)", who);
+    if (ctx->mask_shape == VD_MASK_ELLIPSE)
+        return vd_set_error(VD_ERR_STATE, "%s: mask shape VD_MASK_ELLIPSE has no NV12 pass yet (vd_mask rect only)", who);
+    if (in->base == out->base && !(host_in_place && where == VD_HOST))   // host frames are staged in separate buffers
+        return vd_set_error(VD_ERR_ARG, "%s: out-of-place only (out must not overlap in)", who);
+    if (where == VD_DEVICE) {
+        const uintptr_t a = (uintptr_t)in->base, b = (uintptr_t)out->base;
+        if (a < b + (size_t)n * out->frame_stride && b < a + (size_t)n * in->frame_stride)
+            return vd_set_error(VD_ERR_ARG, "%s: out-of-place only (out must not overlap in)", who);
+    }
+    return VD_OK;
+}
+
+int vd_process_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n, int fh, int fw, int where, int flags,
+                    vd_boxes* faces, vd_boxes* plates) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    const char* who = "vd_process_nv12";
+    if (where != VD_HOST && where != VD_DEVICE) return vd_set_error(VD_ERR_ARG, "%s: bad where", who);
+    int rc = vd_nv12_check(who, in, n, fh, fw, true);
+    if (rc) return rc;
+    if (flags & VD_PROC_MOSAIC) {
+        if (!out) return vd_set_error(VD_ERR_ARG, "%s: MOSAIC needs an output descriptor", who);
+        if ((rc = nv12_blur_check(ctx, who, in, out, n, fh, fw, where, true))) return rc;
+    }
+    if ((flags & VD_PROC_FACES) && ctx->tiles_on())
+        return vd_set_error(VD_ERR_STATE, "%s: tiled detection (vd_tiles) reads RGB frames only", who);
+    if (ctx->lead.J && (flags & VD_PROC_MOSAIC))
+        return vd_set_error(VD_ERR_STATE, "%s: MOSAIC in a look-ahead context would skip the led boxes (vd_lead has no "
+                            "NV12 entry point)", who);
+    if (ctx->lead.pend)
+        return vd_set_error(VD_ERR_STATE, "%s: %d frames are pending in the look-ahead ring (flush first)", who,
+                            ctx->lead.pend);
+    const Nv12Call nv{in, out};
+    return process_impl(ctx, nullptr, nullptr, n, fh, fw, 0, where, flags, faces, plates, nullptr, &nv);
+}
+
+int vd_mosaic_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n, int fh, int fw, int where,
+                   const vd_boxes* boxes, int level) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    const char* who = "vd_mosaic_nv12";
+    if (where != VD_HOST && where != VD_DEVICE) return vd_set_error(VD_ERR_ARG, "%s: bad where", who);
+    if (!boxes) return vd_set_error(VD_ERR_ARG, "%s: null argument", who);
+    if (level <= 0) return vd_set_error(VD_ERR_ARG, "%s: bad geometry", who);
+    int rc = vd_nv12_check(who, in, n, fh, fw, false);
+    if (rc) return rc;
+    if ((rc = nv12_blur_check(ctx, who, in, out, n, fh, fw, where, false))) return rc;
+    BoxListIn b;
+    if ((rc = ctx->box_list_in(who, boxes, n, false, 0, &b))) return rc;
+    Ctx::Nv12Dev nin{}, nout{};
+    if ((rc = ctx->nv12_in(*in, n, fh, fw, where, &nin))) return rc;
+    if ((rc = ctx->nv12_out_begin(*out, n, fh, fw, where, &nout))) return rc;
+    if ((rc = ctx->launch_mosaic_nv12(nin, nout, n, fh, fw, b.cnt, b.xy, boxes->cap, nullptr, nullptr, 0, level, ctx->cells)))
+        return rc;
+    if ((rc = ctx->nv12_out_finish(*out, nout, n, fh, fw, where))) return rc;
+    if (where == VD_HOST || b.staged) VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // host results; staging reused
+    return VD_OK;
 }
 
 int vd_process_lead(vd_ctx* h, const uint8_t* in, int n, int fh, int fw, size_t pitch, int where, int flags,

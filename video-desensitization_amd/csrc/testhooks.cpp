@@ -68,6 +68,21 @@ int vdt_letterbox(vd_ctx* h, const uint8_t* frames, int n, int fh, int fw, size_
     return letterbox_readback(ctx, n, out, cpad);
 }
 
+int vdt_letterbox_nv12(vd_ctx* h, const vd_nv12* frames, int n, int fh, int fw, int where, float* out, int cpad) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (!ctx->face.loaded) return vd_set_error(VD_ERR_STATE, "RetinaFace weights not loaded");
+    if (where != VD_HOST && where != VD_DEVICE) return vd_set_error(VD_ERR_ARG, "vdt_letterbox_nv12: bad where");
+    int rc = vd_nv12_check("vdt_letterbox_nv12", frames, n, fh, fw, true);
+    if (rc) return rc;
+    if ((rc = ctx->check_frames(n, fh, fw, (size_t)fw * 3))) return rc;   // n within max_batch
+    Ctx::Nv12Dev d{};
+    if ((rc = ctx->nv12_in(*frames, n, fh, fw, where, &d))) return rc;
+    const Nv12Scope scope(ctx, d, frames->matrix, frames->range);
+    if ((rc = ctx->face_letterbox(d.base, n, fh, fw, d.pitch))) return rc;
+    return letterbox_readback(ctx, n, out, cpad);
+}
+
 // the first n face canvases as host f32 [n][H][W][cpad], whatever form the plan keeps them in
 static int letterbox_readback(Ctx* ctx, int n, float* out, int cpad) {
     const Act& in = ctx->face.input;

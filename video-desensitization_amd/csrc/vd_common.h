@@ -5,6 +5,7 @@
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "nv12.h"
 
 enum VdAct { VD_ACT_NONE = 0, VD_ACT_RELU = 1, VD_ACT_LEAKY = 2, VD_ACT_SILU = 3 };
 enum VdResMode { VD_RES_NONE = 0, VD_RES_PRE_ACT = 1, VD_RES_POST_ACT = 2 };
@@ -307,6 +308,7 @@ struct LetterboxArgs {
                            //    Y in [0, oh/2], X in [0, ow/2]
     int gx_k, gx_c;        // set by the launcher (pre.hip): gx_k > 0 when the LB_LINEAR column taps are
                            //    an exact gather, source column gx_k * rx + gx_c with weights (1, 0)
+    Nv12Src nv;            // nv.on: the frames are NV12 surfaces (nv12.h), converted at the taps
 };
 
 // One batch of JPEG frames (jpeg_host.cpp -> jpeg.hip): sparse coefficients per
@@ -432,6 +434,16 @@ hipError_t vd_launch_mosaic(const uint8_t* in, uint8_t* out, int n, int h, int w
                             const int* cnt1, const int* xy1, int cap1, int level, void* table,
                             int stages, int map_on, int cell_blocks, hipStream_t s, int cells = 0);   // stages: 1 = cell table, 2 = output pass, 4 = copy; cells: vd_cells (0 = off)
 size_t vd_mosaic_table_bytes(int n, int tcap);
+// Pixelation of NV12 frames (nv12.hip; include/vdmi.h at vd_nv12): one launch, both planes. Luma at
+// in / out, chroma at + *_uv bytes, frame f at + f * *_stride; lists as vd_launch_mosaic takes them.
+struct Nv12MosaicArgs {
+    const uint8_t* in; uint8_t* out; int n, h, w;
+    size_t in_pitch, in_uv, in_stride, out_pitch, out_uv, out_stride;
+    const int* cnt0; const int* xy0; int cap0;
+    const int* cnt1; const int* xy1; int cap1;
+    int level, cells;
+};
+hipError_t vd_launch_mosaic_nv12(const Nv12MosaicArgs& a, hipStream_t s);
 // Box-scaled strength (include/vdmi.h at vd_cells): the cell level L of a box of unclipped size
 // W x H under the base level and the cells setting. cells == 0 or an empty box: the base level;
 // otherwise max(level, min(32768, ceil(max(W, H) / cells))). The one routine of the kernels

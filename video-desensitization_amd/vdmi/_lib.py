@@ -30,6 +30,10 @@ VD_MASK_GROW_MAX = 200
 VD_TILES_MAX = 4
 VD_CELLS_MIN, VD_CELLS_MAX = 2, 64
 MASK_SHAPES = {"rect": VD_MASK_RECT, "ellipse": VD_MASK_ELLIPSE}
+VD_NV12_BT601, VD_NV12_BT709 = 0, 1
+VD_NV12_LIMITED, VD_NV12_FULL = 0, 1
+NV12_MATRICES = {"bt601": VD_NV12_BT601, "bt709": VD_NV12_BT709}
+NV12_RANGES = {"limited": VD_NV12_LIMITED, "full": VD_NV12_FULL}
 VD_PROC_FACES, VD_PROC_PLATES, VD_PROC_MOSAIC, VD_PROC_MOSAIC_PLATES = 1, 2, 4, 8
 FAM_CONV, FAM_MOSAIC, FAM_LETTERBOX, FAM_POST, FAM_OTHER, FAM_PLATE_CONV, FAM_MOSAIC_CELLS = 0, 1, 2, 3, 4, 5, 6
 
@@ -69,6 +73,11 @@ class vd_boxes(ctypes.Structure):
                 ("count", ctypes.c_void_p), ("xyxy", ctypes.c_void_p),
                 ("xyxy_f", ctypes.c_void_p), ("score", ctypes.c_void_p),
                 ("label", ctypes.c_void_p)]
+
+
+class vd_nv12(ctypes.Structure):
+    _fields_ = [("base", ctypes.c_void_p), ("pitch", ctypes.c_size_t), ("uv_offset", ctypes.c_size_t),
+                ("frame_stride", ctypes.c_size_t), ("matrix", ctypes.c_int32), ("range", ctypes.c_int32)]
 
 
 # (name, restype, argtypes) for every symbol of include/vdmi.h
@@ -117,6 +126,12 @@ SIGNATURES = [
     ("vd_jpeg_decode", _I, [_P, ctypes.POINTER(_P), ctypes.POINTER(_SZ), _I, _P, _I, _I, _SZ, _I]),
     ("vd_jpeg_info", _I, [_P, _SZ, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     ("vd_jpeg_encode", _I, [_P, _P, _I, _I, _I, _SZ, _I, _I, _I, _P, _SZ, ctypes.POINTER(_SZ)]),
+    ("vd_process_nv12", _I, [_P, ctypes.POINTER(vd_nv12), ctypes.POINTER(vd_nv12), _I, _I, _I, _I, _I,
+                             ctypes.POINTER(vd_boxes), ctypes.POINTER(vd_boxes)]),
+    ("vd_mosaic_nv12", _I, [_P, ctypes.POINTER(vd_nv12), ctypes.POINTER(vd_nv12), _I, _I, _I, _I,
+                            ctypes.POINTER(vd_boxes), _I]),
+    ("vd_nv12_to_rgb", _I, [ctypes.POINTER(vd_nv12), _I, _I, _I, _P, _SZ]),
+    ("vdt_letterbox_nv12", _I, [_P, ctypes.POINTER(vd_nv12), _I, _I, _I, _I, _P, _I]),
     ("vd_timing_enable", _I, [_P, _I]),
     ("vd_timing_reset", _I, [_P]),
     ("vd_timing_read", _I, [_P, _I, ctypes.POINTER(_D), ctypes.POINTER(ctypes.c_int64),

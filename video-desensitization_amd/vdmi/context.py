@@ -48,6 +48,63 @@ def _frames_arg(frames, pitched=False):
     return a.ctypes.data, n, h, w, w * 3, _lib.VD_HOST, a
 
 
+def _nv12_arg(frames, height=None, matrix="bt709", range="limited", writable=False):
+    """NV12 frames -> (vd_nv12, n, h, w, where, keepalive). frames: uint8 [n, rows, w] (or [rows, w]),
+    numpy or torch, host or device: `rows` luma rows followed by rows / 2 chroma rows of interleaved
+    U, V. rows = 3h/2 is the packed layout; with height=h a taller rows = 3H/2 describes a luma
+    plane padded to H >= h rows (a decoder's aligned height: the chroma plane starts at row H). A
+    torch view with padded rows or frames (big[:, :, :w], big[:, :rows]) is passed by its strides.
+    writable: the call writes the frames, so a layout that would need a packed copy is a ValueError."""
+    if matrix not in _lib.NV12_MATRICES:
+        raise ValueError(f"matrix {matrix!r}: expected 'bt601' or 'bt709'")
+    if range not in _lib.NV12_RANGES:
+        raise ValueError(f"range {range!r}: expected 'limited' or 'full'")
+    if _is_torch(frames):
+        t = frames if frames.dim() == 3 else frames[None]
+        if t.dtype.__str__() != "torch.uint8" or t.dim() != 3:
+            raise ValueError("NV12 frames must be uint8 [n, rows, w]")
+        n, rows, w = t.shape
+        st = t.stride()
+        if not (st[2] == 1 and st[1] >= w and (n == 1 or st[0] >= rows * st[1])):
+            if writable:
+                raise ValueError("NV12 out: a torch tensor with unit column stride and row-major frames is needed")
+            t = t.contiguous()
+            st = t.stride()
+        base, pitch, fstride = t.data_ptr(), st[1], (st[0] if n > 1 else rows * st[1])
+        where = _lib.VD_DEVICE if t.is_cuda else _lib.VD_HOST
+        keep = t
+    else:
+        a = np.ascontiguousarray(frames, dtype=np.uint8)
+        if writable and a is not frames:
+            raise ValueError("NV12 out: a C-contiguous uint8 numpy array is needed")
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("NV12 frames must be uint8 [n, rows, w]")
+        n, rows, w = a.shape
+        base, pitch, fstride, where, keep = a.ctypes.data, w, rows * w, _lib.VD_HOST, a
+    if rows % 3:
+        raise ValueError(f"NV12 frames of {rows} rows: expected 3/2 of an even (padded) height")
+    hpad = rows // 3 * 2
+    h = hpad if height is None else int(height)
+    if h > hpad:
+        raise ValueError(f"height {h} exceeds the {hpad} luma rows that {rows} rows hold")
+    d = _lib.vd_nv12(base, pitch, hpad * pitch, fstride, _lib.NV12_MATRICES[matrix], _lib.NV12_RANGES[range])
+    return d, n, h, w, where, keep
+
+
+def nv12_to_rgb(frames, matrix="bt709", range="limited", height=None):
+    """vd_nv12_to_rgb (host only, no GPU: the routine the kernels' conversion is compiled from): host
+    NV12 frames (the forms of Context.process_nv12) -> uint8 [n, h, w, 3]."""
+    if _is_torch(frames):
+        frames = frames.cpu()
+    d, n, h, w, _, keep = _nv12_arg(frames, height, matrix, range)
+    out = np.empty((n, max(h, 0), max(w, 0), 3), np.uint8)
+    check(_lib.load().vd_nv12_to_rgb(ctypes.byref(d), n, h, w, ptr(out), w * 3))
+    del keep
+    return out
+
+
 def jpeg_info(data):
     """(h, w, components) of a baseline JPEG (host-only parse, no GPU). A bytes object is
     parsed in place (its own buffer: no copy -- a 2.4-MB frame copied under the GIL for every
@@ -443,6 +500,81 @@ class Context:
         if flags & _lib.VD_PROC_PLATES:
             plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
         return out, faces, plates
+
+    # -- NV12 frames ---------------------------------------------------------------
+    @staticmethod
+    def _nv12_out(frames, out, height):
+        """The output surfaces of an NV12 blurring call: `out` in any layout of _nv12_arg, or new
+        ones like the input -> (out, vd_nv12, keepalive)."""
+        if out is None:
+            if _is_torch(frames):
+                import torch
+                out = torch.empty_like(frames, memory_format=torch.contiguous_format)
+            else:
+                out = np.empty(np.shape(frames), np.uint8)
+        d, n, h, w, where, keep = _nv12_arg(out, height, writable=True)
+        return out, d, (n, h, w, where), keep
+
+    def process_nv12(self, frames, out=None, faces=None, plates=None, flags=None, matrix="bt709", range="limited",
+                     height=None):
+        """vd_process_nv12: process() on NV12 frames (uint8 [n, rows, w]; _nv12_arg gives the
+        layouts). Detections are exactly process()'s on nv12_to_rgb(frames); with VD_PROC_MOSAIC
+        both planes of `out` (default: new surfaces like the input) are pixelated. -> (out, faces, plates)."""
+        d, n, h, w, where, keep = _nv12_arg(frames, height, matrix, range)
+        if flags is None:
+            flags = _lib.VD_PROC_FACES | _lib.VD_PROC_MOSAIC
+        od = None
+        if flags & _lib.VD_PROC_MOSAIC:
+            out, od, geo, okeep = self._nv12_out(frames, out, height)
+            if geo != (n, h, w, where):
+                raise ValueError("out must hold NV12 frames of the input's n, h, w in the same memory (host / device)")
+        fs = ps = None
+        auto_f, auto_p = faces is None, plates is None
+        if flags & _lib.VD_PROC_FACES:
+            faces = self._boxes(faces, n)
+            fs = faces.struct()
+        if flags & _lib.VD_PROC_PLATES:
+            plates = self._boxes(plates, n)
+            ps = plates.struct()
+        check(self._lib.vd_process_nv12(self._h, ctypes.byref(d), ctypes.byref(od) if od is not None else None, n, h, w,
+                                        where, flags, ctypes.byref(fs) if fs is not None else None,
+                                        ctypes.byref(ps) if ps is not None else None))
+        if flags & _lib.VD_PROC_FACES:
+            faces = self._complete(faces, _lib.VD_NET_RETINAFACE, auto_f)
+        if flags & _lib.VD_PROC_PLATES:
+            plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
+        return out, faces, plates
+
+    def mosaic_nv12(self, frames, boxes_xyxy, counts=None, level=None, out=None, height=None):
+        """vd_mosaic_nv12: out-of-place pixelation of both planes of NV12 frames with caller lists
+        (the boxes_xyxy / counts forms of mosaic()); the context's mask growth and cells apply."""
+        d, n, h, w, where, keep = _nv12_arg(frames, height)
+        if isinstance(boxes_xyxy, (_lib.HostBoxes, DeviceBoxes)):
+            s = boxes_xyxy.struct()
+            bkeep = None
+        else:
+            xy = np.ascontiguousarray(boxes_xyxy, np.int32).reshape(n, -1, 4)
+            cnt = np.ascontiguousarray(counts if counts is not None else np.full(n, xy.shape[1]), np.int32)
+            cap = max(1, xy.shape[1])
+            if xy.shape[1] == 0:
+                xy = np.zeros((n, 1, 4), np.int32)
+            s = _lib.vd_boxes(cap, _lib.VD_HOST, ptr(cnt), ptr(xy), None, None, None)
+            bkeep = (xy, cnt)
+        out, od, geo, okeep = self._nv12_out(frames, out, height)
+        if geo != (n, h, w, where):
+            raise ValueError("out must hold NV12 frames of the input's n, h, w in the same memory (host / device)")
+        check(self._lib.vd_mosaic_nv12(self._h, ctypes.byref(d), ctypes.byref(od), n, h, w, where, ctypes.byref(s),
+                                       int(level or self.cfg.mosaic_level)))
+        del keep, bkeep, okeep
+        return out
+
+    def letterbox_nv12(self, frames, cpad=4, matrix="bt709", range="limited", height=None):
+        """vdt_letterbox_nv12: the face canvas of NV12 frames by the product path's NV12 kernel."""
+        d, n, h, w, where, keep = _nv12_arg(frames, height, matrix, range)
+        out = np.zeros((n, self.cfg.input_h, self.cfg.input_w, cpad), np.float32)
+        check(self._lib.vdt_letterbox_nv12(self._h, ctypes.byref(d), n, h, w, where, ptr(out), cpad))
+        del keep
+        return out
 
     # -- box hold ----------------------------------------------------------------
     def hold(self, boxes, h, w, out=None):
