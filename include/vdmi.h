@@ -615,7 +615,7 @@ int vd_tiles(vd_ctx* ctx, int rows, int cols, int overlap_pct);
  * or before the RetinaFace weights are loaded; n*T > cfg.max_batch: VD_ERR_ARG. */
 int vd_tiles_merge(vd_ctx* ctx, const vd_boxes* lists, int n, int h, int w, vd_boxes* out);
 
-/* ---- NV12 frames: detect and pixelate video surfaces directly ---------------------
+/* ---- NV12 frames: detect and blur video surfaces directly -------------------------
  * A video decoder hands out NV12 surfaces and an encoder takes them back: a pitched luma plane
  * followed by an interleaved half-resolution chroma plane. These entries take and write that
  * format; no full-resolution RGB copy of a frame exists in device memory on this path. Integers
@@ -657,13 +657,45 @@ int vd_tiles_merge(vd_ctx* ctx, const vd_boxes* lists, int n, int h, int w, vd_b
  *            chroma cell never spans fewer luma pixels than a luma cell. Per plane box j reads the
  *            output of box j-1. Every output byte of both planes inside [0,w) of each row is written
  *            exactly once; pad bytes beyond w and rows between the planes are not written.
+ *   smooth   (VD_PROC_MOSAIC / vd_mosaic_nv12 in a VD_BLUR_GAUSSIAN context with vd_cells on, and
+ *            vd_smooth_nv12) the scaled smooth blur of vd_cells, plane by plane, on the same list with
+ *            the same c, cc and L(b). Luma: the blur on the Y plane as an h x w one-channel image with
+ *            rectangle c and f = L(b). Chroma: the blur on the UV plane as an (h/2) x (w/2)
+ *            two-channel image with rectangle cc and fc = (L(b)+1)>>1, U and V each treated as the RGB
+ *            path treats a channel. Cells, Q8.4 means, across, down and the rounding terms are exactly
+ *            vd_cells' formulas; every box reads `in`. Owner: per plane, the owner of a sample is the
+ *            box with the largest L(b) -- the luma level in both planes, so ownership is the same in
+ *            both (L = 7 and L = 8 share fc = 4) -- among the boxes whose rectangle of that plane (c
+ *            or cc) holds the sample, ties to the lowest list index; a sample in no rectangle is
+ *            out = in. Every byte inside [0,w) of both planes' rows is written exactly once; pad
+ *            bytes and the rows between the planes are never written. Chroma grid bound: a luma grid
+ *            has at most N = cells cells per side, a chroma grid at most N + 1, since cw <= bw/2 + 1
+ *            <= N*L/2 + 1 <= N*fc + 1; the bound is reached (N = 2, level 1, box (1, 0, 5, 4): L = 2,
+ *            fc = 1, cc = (0, 0, 3, 2), 3 cells across). Needs h, w <= 32768 and 1 <= level <= 32768
+ *            (VD_ERR_ARG otherwise). Launches (smooth.hip): one copy of both planes and one box pass
+ *            of both planes, family 1, no scratch memory.
+ *   ellipse  (a VD_MASK_ELLIPSE context, over pixelation and the smooth blur alike) R is the
+ *            rectangular NV12 pass above on the grown list, E_k the luma pixels of box k's clipped
+ *            rectangle inside its ellipse by the unchanged predicate of vd_mask. Luma: out_Y(p) =
+ *            R_Y(p) if p lies in some E_k, else in_Y(p). Chroma: sample (cy, cx) is hidden iff at
+ *            least one of its four luma pixels (2cy + {0,1}, 2cx + {0,1}) lies in some E_k; out_UV =
+ *            R_UV where hidden, else in_UV. So a hidden luma pixel has both its Y and its UV from R,
+ *            for a pixel that is not hidden and whose chroma sample is not hidden C(out) = C(in)
+ *            exactly, and the g >= 42 coverage guarantee carries over unchanged. In span form the
+ *            hidden samples of chroma row cy for box k are the union of [xl >> 1, (xr + 1) >> 1) over
+ *            the non-empty spans [xl, xr) of E_k in luma rows 2cy and 2cy + 1. One restore launch
+ *            after the rectangular pass (mask.hip, family 1, work 0).
+ * Order, as for RGB frames: hold merge, rescue, mask growth, L from the grown boxes, the rectangular
+ * pass, the restore.
  * VD_ERR_ARG, each checked before any state changes: odd or non-positive h or w; pitch < w;
  * uv_offset < h*pitch; frame_stride too small; unknown matrix or range; device in / out ranges that
- * overlap (whole n*frame_stride ranges). Limits of this version (VD_ERR_STATE, the message names the
- * setting): VD_PROC_MOSAIC / vd_mosaic_nv12 in a VD_BLUR_GAUSSIAN or VD_MASK_ELLIPSE context; any
- * NV12 detection call with tiling on; the look-ahead hold has no NV12 entry point (vd_process_nv12
- * obeys vd_process's rules in a lead context). One output launch per call for both planes
- * (nv12.hip, timing family 1, work 2 * 1.5 * h * w per frame); the NV12 letterbox is family 2. */
+ * overlap (whole n*frame_stride ranges); the smooth blur's limits above. Limits of this version
+ * (VD_ERR_STATE, the message names the setting): VD_PROC_MOSAIC / vd_mosaic_nv12 in a
+ * VD_BLUR_GAUSSIAN context with cells off (the fixed 31-tap Gaussian has no NV12 pass: set cells);
+ * any NV12 detection call with tiling on; the look-ahead hold has no NV12 entry point
+ * (vd_process_nv12 obeys vd_process's rules in a lead context). Pixelation is one output launch per
+ * call for both planes (nv12.hip, timing family 1, work 2 * 1.5 * h * w per frame); the NV12
+ * letterbox is family 2. */
 #define VD_NV12_BT601 0
 #define VD_NV12_BT709 1
 #define VD_NV12_LIMITED 0
@@ -678,9 +710,16 @@ typedef struct vd_nv12 {
 int vd_process_nv12(vd_ctx* ctx, const vd_nv12* in, const vd_nv12* out, int n, int h, int w, int where, int flags,
                     vd_boxes* faces, vd_boxes* plates);
 /* vd_mosaic on NV12 frames: caller lists, with vd_mosaic's staging and capacity rules; the context's
- * mask growth (rect) and cells apply as they do to vd_mosaic. */
+ * mask setting and cells apply as they do to vd_mosaic. The context's blur mode chooses the pass as
+ * it does for vd_process_nv12: pixelation, or in a VD_BLUR_GAUSSIAN context with cells on the
+ * scaled smooth blur at `level` (cells off: VD_ERR_STATE). */
 int vd_mosaic_nv12(vd_ctx* ctx, const vd_nv12* in, const vd_nv12* out, int n, int h, int w, int where,
                    const vd_boxes* boxes, int level);
+/* vd_smooth on NV12 frames: the scaled smooth blur of both planes with caller lists in any context,
+ * with vd_mosaic_nv12's staging, capacity and overlap rules; cells in [VD_CELLS_MIN, VD_CELLS_MAX],
+ * h, w <= 32768 and 1 <= level <= 32768 (VD_ERR_ARG otherwise); the context's mask setting applies. */
+int vd_smooth_nv12(vd_ctx* ctx, const vd_nv12* in, const vd_nv12* out, int n, int h, int w, int where,
+                   const vd_boxes* boxes, int level, int cells);
 /* C(frame) of n frames into packed RGB rows of rgb_pitch >= 3*w bytes, frame i at rgb + i*h*rgb_pitch
  * (host only: no context, no GPU): the routine the kernels' conversion function is compiled from. */
 int vd_nv12_to_rgb(const vd_nv12* in, int n, int h, int w, uint8_t* rgb, size_t rgb_pitch);
@@ -691,7 +730,7 @@ int vd_nv12_to_rgb(const vd_nv12* in, int n, int h, int w, uint8_t* rgb, size_t 
  * launch count and the summed algorithmic work (FLOP or bytes) since the last
  * reset. Families: 0 = RetinaFace conv (implicit GEMM / streaming 1x1), 1 = mosaic
  * output pass (or the Gaussian blur's launches, or the smooth blur's copy and box pass; the mask's restore pass, work 0: its bytes follow
- * from the boxes; the NV12 output pass, work 2 * 1.5 * h * w per frame), 2 = letterbox (the tile letterbox too; NV12: 1.5 B/px of source), 3 = post (decode/NMS, box hold,
+ * from the boxes; the NV12 output pass or the NV12 smooth blur's copy, work 2 * 1.5 * h * w per frame, its box pass and the NV12 restore, work 0), 2 = letterbox (the tile letterbox too; NV12: 1.5 B/px of source), 3 = post (decode/NMS, box hold,
  * look-ahead lists, mask grow, tile merge), 4 = other (the look-ahead pixel ring's copies), 5 = YOLOv8n plate
  * conv, 6 = mosaic cell table (box prep + walked cell colours). */
 int vd_timing_enable(vd_ctx* ctx, int on);

@@ -17,6 +17,16 @@ of each:
 Per run: ms/step in the steady state (warm-up first, then the steps ended by one synchronise), then
 event-timed steps of their own for the families' times, and for families 1 and 2 the share of the
 8 TB/s HBM peak their algorithmic bytes reach.
+
+    python tools/nv12bench.py --modes --parent-lib PATH/libvdmi.so [--repeats 5] [--fam-steps 5]
+                              [--level 8] [--cells 16] [--json profiles/nv12_modes_1080p.json]
+
+--modes: the scaled smooth blur and the ellipse mask on NV12 frames. Family 1 of one stand-alone call
+(smooth_nv12, mosaic_nv12 under masks ("rect", 0), ("rect", 42), ("ellipse", 42)) over the face lists
+detected on the frames -- the boxes tools/cellsbench.py blurs -- beside smooth / mosaic on
+nv12_to_rgb of the same frames, by this build and, for the calls it has, by the parent's build: the
+median of --repeats groups with their spread. The restore pass alone is the ellipse row minus the
+("rect", 42) row of the same call.
 """
 import argparse
 import json
@@ -149,14 +159,113 @@ def one(a):
     print("NV12BENCH " + json.dumps(r), flush=True)
 
 
+# ---- --modes: the stand-alone blurring passes, smooth and ellipse, NV12 beside RGB -------------------
+# (row, call, mask): family 1 of one call over the face lists detected on the frames. The restore pass
+# alone is the ("ellipse", 42) row minus the ("rect", 42) row of the same call: the same grown lists,
+# the same rectangular pass.
+MODE_ROWS = [("rgb_smooth", "smooth", ("rect", 0)), ("rgb_smooth_grow42", "smooth", ("rect", 42)),
+             ("rgb_smooth_ellipse42", "smooth", ("ellipse", 42)),
+             ("rgb_mosaic_grow42", "mosaic", ("rect", 42)), ("rgb_mosaic_ellipse42", "mosaic", ("ellipse", 42)),
+             ("nv12_mosaic", "mosaic_nv12", ("rect", 0)), ("nv12_mosaic_grow42", "mosaic_nv12", ("rect", 42)),
+             ("nv12_mosaic_ellipse42", "mosaic_nv12", ("ellipse", 42)),
+             ("nv12_smooth", "smooth_nv12", ("rect", 0)), ("nv12_smooth_grow42", "smooth_nv12", ("rect", 42)),
+             ("nv12_smooth_ellipse42", "smooth_nv12", ("ellipse", 42))]
+PARENT_LACKS = ("nv12_mosaic_ellipse42", "nv12_smooth", "nv12_smooth_grow42", "nv12_smooth_ellipse42")
+RESTORE = {"rgb_smooth": ("rgb_smooth_ellipse42", "rgb_smooth_grow42"),
+           "rgb_mosaic": ("rgb_mosaic_ellipse42", "rgb_mosaic_grow42"),
+           "nv12_mosaic": ("nv12_mosaic_ellipse42", "nv12_mosaic_grow42"),
+           "nv12_smooth": ("nv12_smooth_ellipse42", "nv12_smooth_grow42")}
+
+
+def median(v):
+    s = sorted(v)
+    return s[len(s) // 2] if len(s) % 2 else (s[len(s) // 2 - 1] + s[len(s) // 2]) / 2
+
+
+def one_modes(a):
+    """--one modes-parent | modes-this: every row this library has, one context, the same boxes."""
+    import torch
+    from vdmi import _lib
+    parent = a.one == "modes-parent"
+    if parent:               # the parent's build has no vd_smooth_nv12
+        _lib.SIGNATURES = [s for s in _lib.SIGNATURES if s[0] != "vd_smooth_nv12"]
+    import vdmi
+    from vdmi import synth, weights
+    B, H, W = a.batch, 1080, 1920
+    dev = torch.device("cuda:0")
+    nv = nv12_frames(B, H, W, dev)
+    rgb = torch.from_numpy(vdmi.nv12_to_rgb(nv.cpu())).to(dev)
+    ctx = vdmi.Context(device=0, precision="fp32", max_batch=B)
+    ctx.load_weights(_lib.VD_NET_RETINAFACE, weights.retinaface_state_dict(0))
+    boxes = vdmi.DeviceBoxes(B, 256, dev)
+    # the box set of tools/cellsbench.py: the face lists of its RGB frames (a pass's time follows the boxes, not the pixels)
+    ctx.process(torch.from_numpy(synth.frames(B, H, W, seed=0)).to(dev), flags=_lib.VD_PROC_FACES, faces=boxes)
+    ctx.sync()
+    cnt = boxes.count.cpu().numpy().clip(0, 256)
+    xy = boxes.xyxy.cpu().numpy()
+    area = sum(max(0, min(W, int(b[2])) - max(0, int(b[0]))) * max(0, min(H, int(b[3])) - max(0, int(b[1])))
+               for f in range(B) for b in xy[f, :cnt[f]])
+    out_rgb, out_nv = torch.empty_like(rgb), torch.empty_like(nv)
+    calls = {"smooth": lambda: ctx.smooth(rgb, boxes, level=a.level, cells=a.cells, out=out_rgb),
+             "mosaic": lambda: ctx.mosaic(rgb, boxes, level=a.level, out=out_rgb),
+             "mosaic_nv12": lambda: ctx.mosaic_nv12(nv, boxes, level=a.level, out=out_nv),
+             "smooth_nv12": lambda: ctx.smooth_nv12(nv, boxes, level=a.level, cells=a.cells, out=out_nv)}
+    r = {"boxes_per_frame": float(cnt.sum()) / B, "box_pixels_per_frame": area / B, "rows": {}}
+    ctx.timing(True)
+    for name, call, mask in MODE_ROWS:
+        if parent and name in PARENT_LACKS:
+            continue
+        ctx.set_mask(*mask)
+        step = calls[call]
+        for _ in range(max(a.warmup, 1)):
+            step()
+        ctx.sync()
+        ms, launches = [], 0
+        for _ in range(a.repeats):
+            ctx.timing_reset()
+            for _ in range(a.fam_steps):
+                step()
+            ctx.sync()
+            t, k, _ = ctx.timing_read(_lib.FAM_MOSAIC)
+            ms.append(round(t / a.fam_steps, 4))
+            launches = k / a.fam_steps
+        r["rows"][name] = {"fam1_ms_per_call": ms, "median_ms": round(median(ms), 4),
+                           "spread_ms": round(max(ms) - min(ms), 4), "launches_per_call": launches}
+    ctx.timing(False)
+    ctx.close()
+    print("NV12BENCH " + json.dumps(r), flush=True)
+
+
+def modes(a):
+    """The smooth and ellipse passes on NV12 frames beside their RGB counterparts and the parent build."""
+    res = {"what": "family 1 (the blurring pass) of one stand-alone call on 64 x 1080p frames in HBM over the face "
+                   "lists detected on them: smooth / mosaic on nv12_to_rgb(frames), smooth_nv12 / mosaic_nv12 on the "
+                   "NV12 frames; *_grow42 is mask ('rect', 42), *_ellipse42 mask ('ellipse', 42), restore_ms their "
+                   "difference of medians (the restore pass alone)",
+           "machine": "one MI355X, parent and this build in one session, a process each",
+           "batch": a.batch, "frame": [1080, 1920], "level": a.level, "cells": a.cells, "repeats": a.repeats,
+           "fam_steps": a.fam_steps}
+    for which in ("modes-parent", "modes-this"):
+        r = child(a, which)
+        for k, (e, g) in RESTORE.items():
+            if e in r["rows"] and g in r["rows"]:
+                r.setdefault("restore_ms", {})[k] = round(r["rows"][e]["median_ms"] - r["rows"][g]["median_ms"], 4)
+        res[which.split("-")[1]] = r
+    t = res["this"]["rows"]
+    res["nv12_over_rgb"] = {k: round(t["nv12_" + k]["median_ms"] / t["rgb_" + k]["median_ms"], 4)
+                            for k in ("smooth", "smooth_grow42", "smooth_ellipse42", "mosaic_grow42", "mosaic_ellipse42")}
+    return res
+
+
 def child(a, which):
     env = dict(os.environ)
-    if which == "parent":
+    if which in ("parent", "modes-parent"):
         env["VDMI_LIB"] = os.path.abspath(a.parent_lib)
     else:
         env.pop("VDMI_LIB", None)
     cmd = [sys.executable, os.path.abspath(__file__), "--one", which, "--steps", str(a.steps), "--warmup",
-           str(a.warmup), "--batch", str(a.batch), "--fam-steps", str(a.fam_steps)]
+           str(a.warmup), "--batch", str(a.batch), "--fam-steps", str(a.fam_steps), "--repeats", str(a.repeats),
+           "--level", str(a.level), "--cells", str(a.cells)]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=a.child_timeout)
     if p.returncode != 0:
         raise RuntimeError(f"{which} run failed ({p.returncode}):\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
@@ -176,13 +285,25 @@ def main():
     ap.add_argument("--fam-steps", type=int, default=5, help="event-timed steps behind the family figures")
     ap.add_argument("--child-timeout", type=int, default=240)
     ap.add_argument("--no-torch", action="store_true", help="skip the informational torch round trip")
-    ap.add_argument("--one", choices=KINDS + ("torch",), help="(internal) one measurement in this process")
+    ap.add_argument("--one", choices=KINDS + ("torch", "modes-parent", "modes-this"),
+                    help="(internal) one measurement in this process")
+    ap.add_argument("--modes", action="store_true", help="the smooth and ellipse passes instead of the full step")
+    ap.add_argument("--level", type=int, default=8, help="--modes: the base level")
+    ap.add_argument("--cells", type=int, default=16, help="--modes: cells of the smooth blur")
     ap.add_argument("--json", help="also write the result line to this file")
     a = ap.parse_args()
     if a.one:
-        return one(a)
+        return one_modes(a) if a.one.startswith("modes-") else one(a)
     if not a.parent_lib or not os.path.exists(a.parent_lib):
         ap.error("--parent-lib: the parent commit's libvdmi.so is needed for the comparison")
+    if a.modes:
+        line = json.dumps(modes(a))
+        print(line, flush=True)
+        if a.json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, "w") as f:
+                f.write(line + "\n")
+        return
     runs = {k: [] for k in KINDS}
     for _ in range(a.repeats):                   # parent, rgb, nv12, parent, rgb, nv12, ...
         for which in KINDS:

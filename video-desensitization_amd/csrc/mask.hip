@@ -214,6 +214,156 @@ __global__ __launch_bounds__(THREADS) void mask_restore_kernel(MaskArgs a) {
     }
 }
 
+// ---- NV12 frames (include/vdmi.h at vd_nv12, "ellipse") ----
+// The composite on both planes after the rectangular NV12 pass (nv12.hip / smooth.hip) gave R:
+//   luma    out_Y(p) = R_Y(p) where p lies in some E_k, in_Y(p) elsewhere: mask_restore_kernel's
+//           pass with one byte per pixel;
+//   chroma  sample (cy, cx) is hidden iff one of its four luma pixels (2cy + {0, 1}, 2cx + {0, 1})
+//           lies in some E_k; out_UV = R_UV where hidden, in_UV elsewhere. In span form: a
+//           non-empty span [xl, xr) of luma row 2cy or 2cy + 1 hides chroma samples
+//           [xl >> 1, (xr + 1) >> 1) of row cy. Only samples of some box's chroma rectangle cc_k
+//           can differ from `in`, so those are the ones tested.
+// The same band per workgroup (BR luma rows, BR / 2 chroma rows; BR and h are even, so a chroma
+// row's two luma rows lie in one band), the same LDS list and spans; a wave takes a (box, luma
+// row) and then a (box, chroma row) at a time. Past BCAP the global row is walked with the
+// predicate as written, the four-pixel rule included.
+__device__ __forceinline__ void restore_y(const uint8_t* in_y, uint8_t* out_y, const MaskNv12Args& a, int x, int y) {
+    out_y[(size_t)y * a.out_pitch + x] = in_y[(size_t)y * a.in_pitch + x];
+}
+
+__device__ __forceinline__ void restore_uv(const uint8_t* in_uv, uint8_t* out_uv, const MaskNv12Args& a, int cx, int cy) {
+    const size_t i = (size_t)cy * a.in_pitch + 2 * (size_t)cx, o = (size_t)cy * a.out_pitch + 2 * (size_t)cx;
+    out_uv[o] = in_uv[i];
+    out_uv[o + 1] = in_uv[i + 1];
+}
+
+__global__ __launch_bounds__(THREADS) void mask_restore_nv12_kernel(MaskNv12Args a) {
+    __shared__ int4 s_box[BCAP];
+    __shared__ __attribute__((aligned(16))) int s_xl[BR][BCAP], s_xr[BR][BCAP];
+    __shared__ int s_n;
+    const int bands = (a.h + BR - 1) / BR;
+    const int f = blockIdx.x / bands, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int by0 = (blockIdx.x % bands) * BR, by1 = min(by0 + BR, a.h);   // both even
+    const uint8_t* in_y = a.in + (size_t)f * a.in_stride;
+    const uint8_t* in_uv = in_y + a.in_uv;
+    uint8_t* out_y = a.out + (size_t)f * a.out_stride;
+    uint8_t* out_uv = out_y + a.out_uv;
+    const int nb = min(max(a.m_cnt[f], 0), a.mcap);
+    const int4* row = (const int4*)a.m_xy + (size_t)f * a.mcap;
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    for (int k = tid; k < nb; k += THREADS) {
+        const int4 b = row[k];
+        int4 c;
+        if (clip_box(b, a.w, a.h, c) && c.y < by1 && c.w > by0) {
+            const int i = atomicAdd(&s_n, 1);
+            if (i < BCAP) s_box[i] = b;
+        }
+    }
+    __syncthreads();
+    const int nt = s_n;                                // uniform over the workgroup
+    if (nt == 0) return;
+
+    if (nt <= BCAP) {
+        const int nt4 = (nt + 3) & ~3;
+        for (int p = tid; p < nt4 * BR; p += THREADS) {
+            const int k = p % nt4, r = p / nt4;
+            int xl = ROW_NONE, xr = ROW_NONE;
+            if (k < nt) {
+                const int4 b = s_box[k];
+                int4 c;
+                clip_box(b, a.w, a.h, c);
+                row_span(b, c, by0 + r, xl, xr);
+            }
+            s_xl[r][k] = xl;
+            s_xr[r][k] = xr;
+        }
+        __syncthreads();
+        // luma: the pixels of a box's row outside its own span that no other span of the row holds
+        for (int p = wid; p < nt * BR; p += WAVES) {
+            const int k = p / BR, r = p % BR;
+            const int xl = s_xl[r][k], xr = s_xr[r][k];
+            if (xl == ROW_NONE) continue;
+            const int4 b = s_box[k];
+            const int cx1 = max(0, b.x), cx2 = min(a.w, b.z);
+            const int nl = xl - cx1, no = nl + (cx2 - xr);
+            for (int i = lane; i < no; i += 64) {
+                const int x = i < nl ? cx1 + i : xr + (i - nl);
+                const int4* vl = (const int4*)s_xl[r];
+                const int4* vr = (const int4*)s_xr[r];
+                bool hidden = false;
+                for (int j = 0; j < nt4 / 4; ++j) {
+                    const int4 l = vl[j], h = vr[j];
+                    hidden |= (x >= l.x && x < h.x) | (x >= l.y && x < h.y) | (x >= l.z && x < h.z) |
+                              (x >= l.w && x < h.w);
+                }
+                if (!hidden) restore_y(in_y, out_y, a, x, by0 + r);
+            }
+        }
+        // chroma: the samples of a box's chroma rectangle that no span of the two luma rows hides
+        // (an empty span, xl == xr or ROW_NONE, hides nothing: the l < h terms)
+        for (int p = wid; p < nt * (BR / 2); p += WAVES) {
+            const int k = p / (BR / 2), rc = p % (BR / 2);
+            const int cy = by0 / 2 + rc;
+            const int4 b = s_box[k];
+            int4 c;
+            clip_box(b, a.w, a.h, c);
+            if (cy < (c.y >> 1) || cy >= ((c.w + 1) >> 1)) continue;   // not a row of cc_k (or past the frame)
+            const int ccx2 = (c.z + 1) >> 1;
+            for (int x = (c.x >> 1) + lane; x < ccx2; x += 64) {
+                bool hidden = false;
+                for (int r = 2 * rc; r < 2 * rc + 2; ++r) {
+                    const int4* vl = (const int4*)s_xl[r];
+                    const int4* vr = (const int4*)s_xr[r];
+                    for (int j = 0; j < nt4 / 4; ++j) {
+                        const int4 l = vl[j], h = vr[j];
+                        hidden |= (l.x < h.x && x >= (l.x >> 1) && x < ((h.x + 1) >> 1)) |
+                                  (l.y < h.y && x >= (l.y >> 1) && x < ((h.y + 1) >> 1)) |
+                                  (l.z < h.z && x >= (l.z >> 1) && x < ((h.z + 1) >> 1)) |
+                                  (l.w < h.w && x >= (l.w >> 1) && x < ((h.w + 1) >> 1));
+                    }
+                }
+                if (!hidden) restore_uv(in_uv, out_uv, a, x, cy);
+            }
+        }
+        return;
+    }
+
+    // more boxes than the LDS list holds: the same composite from the global row
+    auto in_some_ellipse = [&](int x, int y, int skip) {
+        for (int j = 0; j < nb; ++j) {
+            if (j == skip) continue;
+            const int4 o = row[j];
+            int4 oc;
+            if (!clip_box(o, a.w, a.h, oc) || x < oc.x || x >= oc.z || y < oc.y || y >= oc.w) continue;
+            if (in_ellipse(o, x, y)) return true;
+        }
+        return false;
+    };
+    for (int k = 0; k < nb; ++k) {
+        const int4 b = row[k];
+        int4 c;
+        if (!clip_box(b, a.w, a.h, c) || c.y >= by1 || c.w <= by0) continue;
+        const int y0 = max(c.y, by0), y1 = min(c.w, by1), bw = c.z - c.x;
+        const long long npx = (long long)(y1 - y0) * bw;
+        for (long long p = tid; p < npx; p += THREADS) {
+            const int y = y0 + (int)(p / bw), x = c.x + (int)(p % bw);
+            if (in_ellipse(b, x, y)) continue;
+            if (!in_some_ellipse(x, y, k)) restore_y(in_y, out_y, a, x, y);
+        }
+        // the band's chroma rows of cc_k: by the four luma pixels of each sample
+        const int ccx1 = c.x >> 1, cbw = ((c.z + 1) >> 1) - ccx1;
+        const int cy0 = max(c.y >> 1, by0 / 2), cy1 = min((c.w + 1) >> 1, by1 / 2);
+        const long long ncs = (long long)(cy1 - cy0) * cbw;
+        for (long long p = tid; p < ncs; p += THREADS) {
+            const int cy = cy0 + (int)(p / cbw), cx = ccx1 + (int)(p % cbw);
+            bool hidden = false;
+            for (int q = 0; q < 4 && !hidden; ++q) hidden = in_some_ellipse(2 * cx + (q & 1), 2 * cy + (q >> 1), -1);
+            if (!hidden) restore_uv(in_uv, out_uv, a, cx, cy);
+        }
+    }
+}
+
 }  // namespace
 
 hipError_t vd_launch_mask_grow(const MaskArgs& a, hipStream_t s) {
@@ -234,5 +384,15 @@ hipError_t vd_launch_mask_restore(const MaskArgs& a, hipStream_t s) {
     const long long blocks = (long long)((a.h + BR - 1) / BR) * a.n;
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(mask_restore_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t vd_launch_mask_restore_nv12(const MaskNv12Args& a, hipStream_t s) {
+    if (a.n <= 0 || a.h <= 0 || a.w <= 0 || (a.h & 1) || (a.w & 1) || a.in_pitch < (size_t)a.w ||
+        a.out_pitch < (size_t)a.w || !a.in || !a.out || !a.m_cnt || !a.m_xy || a.mcap <= 0)
+        return hipErrorInvalidValue;
+    const long long blocks = (long long)((a.h + BR - 1) / BR) * a.n;
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mask_restore_nv12_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, s, a);
     return hipGetLastError();
 }

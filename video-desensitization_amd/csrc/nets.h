@@ -297,9 +297,16 @@ struct Ctx {
     int nv12_out_begin(const vd_nv12& d, int n, int h, int w, int where, Nv12Dev* o);
     // ... copied back plane by plane, [0, w) of every row only (queued; the caller synchronises)
     int nv12_out_finish(const vd_nv12& d, const Nv12Dev& o, int n, int h, int w, int where);
-    // the NV12 output pass behind the mask growth and the cells setting (one launch, family 1)
-    int launch_mosaic_nv12(const Nv12Dev& in, const Nv12Dev& out, int n, int h, int w, const int* cnt0, const int* xy0,
-                           int cap0, const int* cnt1, const int* xy1, int cap1, int level, int cells);
+    // the NV12 output pass behind the mask setting, what launch_shaped is to RGB frames: grow, the
+    // rectangular pass (RECT_MOSAIC: nv12.hip, one launch; RECT_SMOOTH: smooth.hip, copy + box pass),
+    // then under VD_MASK_ELLIPSE the restore of both planes; all family 1
+    int launch_nv12_pass(const Nv12Dev& in, const Nv12Dev& out, int n, int h, int w, const int* cnt0, const int* xy0,
+                         int cap0, const int* cnt1, const int* xy1, int cap1, int pass, int level, int cells);
+    // the rectangular pass an NV12 blurring call of this context runs, or -1: the fixed-kernel Gaussian
+    // (VD_BLUR_GAUSSIAN with cells off) has no NV12 pass
+    int nv12_cfg_pass() const {
+        return cfg.blur_mode != VD_BLUR_GAUSSIAN ? (int)RECT_MOSAIC : (cells ? (int)RECT_SMOOTH : -1);
+    }
     // tiled face detection (tiles.hip, pre.hip letterbox_tiles_kernel; vd_tiles): nothing is allocated
     // or launched while rows * cols == 1
     int tile_rows = 1, tile_cols = 1, tile_overlap = 0;

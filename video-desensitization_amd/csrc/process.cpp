@@ -154,11 +154,20 @@ int Ctx::launch_cfg_pass(const uint8_t* in, uint8_t* out, int n, int h, int w, s
                          cfg.blur_ksize, cfg.blur_sigma, cells);
 }
 
-// The NV12 output pass (nv12.hip): what launch_shaped is to the RGB pixelation, without the ellipse
-// composite (refused at the entry points). The cell levels come from the grown boxes.
-int Ctx::launch_mosaic_nv12(const Nv12Dev& in, const Nv12Dev& out, int n, int h, int w, const int* cnt0, const int* xy0,
-                            int cap0, const int* cnt1, const int* xy1, int cap1, int level, int ncells) {
-    if (mask_on() && (cnt0 || cnt1)) {
+// The NV12 output pass: what launch_shaped is to RGB frames. Pixelation (nv12.hip) or the scaled
+// smooth blur (smooth.hip) of both planes on the grown lists, then the ellipse composite of both
+// planes (mask.hip). The cell levels come from the grown boxes.
+int Ctx::launch_nv12_pass(const Nv12Dev& in, const Nv12Dev& out, int n, int h, int w, const int* cnt0, const int* xy0,
+                          int cap0, const int* cnt1, const int* xy1, int cap1, int pass, int level, int ncells) {
+    if (pass == RECT_SMOOTH) {
+        if (h > 32768 || w > 32768 || level < 1 || level > 32768)
+            return vd_set_error(VD_ERR_ARG, "smooth blur: h, w <= 32768 and level in [1, 32768] required (got %d x %d, "
+                                "level %d)", w, h, level);
+        if (ncells < VD_CELLS_MIN || ncells > VD_CELLS_MAX)
+            return vd_set_error(VD_ERR_ARG, "smooth blur: cells %d outside [%d, %d]", ncells, VD_CELLS_MIN, VD_CELLS_MAX);
+    }
+    const bool shaped = mask_on() && (cnt0 || cnt1);
+    if (shaped) {
         int rc = launch_mask_grow(n, cnt0, xy0, cap0, cnt1, xy1, cap1);
         if (rc) return rc;
         cnt0 = mask_last.m_cnt; xy0 = mask_last.m_xy; cap0 = mask_last.mcap;
@@ -171,10 +180,30 @@ int Ctx::launch_mosaic_nv12(const Nv12Dev& in, const Nv12Dev& out, int n, int h,
     a.cnt0 = cnt0; a.xy0 = xy0; a.cap0 = cap0;
     a.cnt1 = cnt1; a.xy1 = xy1; a.cap1 = cap1;
     a.level = level; a.cells = ncells;
-    t_begin(1, 2.0 * 1.5 * n * (double)h * w);
-    hipError_t e = vd_launch_mosaic_nv12(a, stream);
+    hipError_t e = hipSuccess;
+    if (pass == RECT_SMOOTH) {   // the copy carries the frames' bytes, the box pass's follow from the boxes
+        for (int stage = 0; stage < 2 && e == hipSuccess; ++stage) {
+            t_begin(1, stage == 0 ? 2.0 * 1.5 * n * (double)h * w : 0);
+            e = vd_launch_smooth_nv12(a, stage, stream);
+            t_end();
+        }
+        if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "nv12 smooth: %s", hipGetErrorString(e));
+    } else {
+        t_begin(1, 2.0 * 1.5 * n * (double)h * w);
+        e = vd_launch_mosaic_nv12(a, stream);
+        t_end();
+        if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "nv12 mosaic: %s", hipGetErrorString(e));
+    }
+    if (!(shaped && mask_shape == VD_MASK_ELLIPSE)) return VD_OK;
+    MaskNv12Args m{};
+    m.in = in.base; m.in_pitch = in.pitch; m.in_uv = in.uv; m.in_stride = in.stride;
+    m.out = out.base; m.out_pitch = out.pitch; m.out_uv = out.uv; m.out_stride = out.stride;
+    m.n = n; m.h = h; m.w = w;
+    m.m_cnt = mask_last.m_cnt; m.m_xy = mask_last.m_xy; m.mcap = mask_last.mcap;
+    t_begin(1, 0);               // as the RGB restore: its bytes follow from the boxes
+    e = vd_launch_mask_restore_nv12(m, stream);
     t_end();
-    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "nv12 mosaic: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "nv12 mask restore: %s", hipGetErrorString(e));
     return VD_OK;
 }
 
@@ -440,10 +469,11 @@ static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh
         return VD_OK;
     };
     auto mosaic = [&]() -> int {
-        if (nv) {   // both planes in one launch (nv12.hip); host surfaces come back plane by plane
+        if (nv) {   // both planes, by the pass the context's blur mode asks for; host surfaces come back plane by plane
             int r = ctx->nv12_out_begin(*nv->out, n, fh, fw, where, &nout);
             if (r) return r;
-            if ((r = ctx->launch_mosaic_nv12(nin, nout, n, fh, fw, c0, x0, k0, c1, x1, k1, ctx->cfg.mosaic_level, ctx->cells)))
+            if ((r = ctx->launch_nv12_pass(nin, nout, n, fh, fw, c0, x0, k0, c1, x1, k1, ctx->nv12_cfg_pass(),
+                                           ctx->cfg.mosaic_level, ctx->cells)))
                 return r;
             return ctx->nv12_out_finish(*nv->out, nout, n, fh, fw, where);
         }
@@ -497,16 +527,16 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
 }
 
 // ---- NV12 frames (include/vdmi.h at vd_nv12) ----
-// what every NV12 blurring call checks before anything changes: the descriptors, the limits of this
-// version, and (device) that the whole n * frame_stride ranges do not overlap
+// what every NV12 blurring call checks before anything changes: the descriptors, the one blur mode
+// without an NV12 pass (`pass` < 0: Ctx::nv12_cfg_pass), and (device) that the whole n * frame_stride
+// ranges do not overlap
 static int nv12_blur_check(Ctx* ctx, const char* who, const vd_nv12* in, const vd_nv12* out, int n, int fh, int fw,
-                           int where, bool host_in_place) {
+                           int where, bool host_in_place, int pass) {
     int rc = vd_nv12_check(who, out, n, fh, fw, false);
     if (rc) return rc;
-    if (ctx->cfg.blur_mode == VD_BLUR_GAUSSIAN)
-        return vd_set_error(VD_ERR_STATE, "%s: blur_mode VD_BLUR_GAUSSIAN has no NV12 pass yet (pixelation only)", who);
-    if (ctx->mask_shape == VD_MASK_ELLIPSE)
-        return vd_set_error(VD_ERR_STATE, "%s: mask shape VD_MASK_ELLIPSE has no NV12 pass yet (vd_mask rect only)", who);
+    if (pass < 0)
+        return vd_set_error(VD_ERR_STATE, "%s: the fixed-kernel Gaussian (blur_mode VD_BLUR_GAUSSIAN with cells off) has "
+                            "no NV12 pass: set cells (vd_cells) for the scaled smooth blur", who);
     if (in->base == out->base && !(host_in_place && where == VD_HOST))   // host frames are staged in separate buffers
         return vd_set_error(VD_ERR_ARG, "%s: out-of-place only (out must not overlap in)", who);
     if (where == VD_DEVICE) {
@@ -527,7 +557,7 @@ int vd_process_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n, int
     if (rc) return rc;
     if (flags & VD_PROC_MOSAIC) {
         if (!out) return vd_set_error(VD_ERR_ARG, "%s: MOSAIC needs an output descriptor", who);
-        if ((rc = nv12_blur_check(ctx, who, in, out, n, fh, fw, where, true))) return rc;
+        if ((rc = nv12_blur_check(ctx, who, in, out, n, fh, fw, where, true, ctx->nv12_cfg_pass()))) return rc;
     }
     if ((flags & VD_PROC_FACES) && ctx->tiles_on())
         return vd_set_error(VD_ERR_STATE, "%s: tiled detection (vd_tiles) reads RGB frames only", who);
@@ -541,27 +571,47 @@ int vd_process_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n, int
     return process_impl(ctx, nullptr, nullptr, n, fh, fw, 0, where, flags, faces, plates, nullptr, &nv);
 }
 
-int vd_mosaic_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n, int fh, int fw, int where,
-                   const vd_boxes* boxes, int level) {
-    Ctx* ctx = (Ctx*)h;
-    VD_ENTRY(ctx);
-    const char* who = "vd_mosaic_nv12";
+// The stand-alone NV12 blurring calls: pass `pass` over the caller's surfaces and one box list, with
+// blur_entry's staging, capacity and overlap rules.
+static int nv12_blur_entry(Ctx* ctx, const char* who, const vd_nv12* in, const vd_nv12* out, int n, int fh, int fw,
+                           int where, const vd_boxes* boxes, int pass, int level, int cells) {
     if (where != VD_HOST && where != VD_DEVICE) return vd_set_error(VD_ERR_ARG, "%s: bad where", who);
     if (!boxes) return vd_set_error(VD_ERR_ARG, "%s: null argument", who);
     if (level <= 0) return vd_set_error(VD_ERR_ARG, "%s: bad geometry", who);
     int rc = vd_nv12_check(who, in, n, fh, fw, false);
     if (rc) return rc;
-    if ((rc = nv12_blur_check(ctx, who, in, out, n, fh, fw, where, false))) return rc;
+    if ((rc = nv12_blur_check(ctx, who, in, out, n, fh, fw, where, false, pass))) return rc;
+    if (pass == Ctx::RECT_SMOOTH && (fh > 32768 || fw > 32768 || level > 32768))
+        return vd_set_error(VD_ERR_ARG, "%s: the smooth blur needs h, w <= 32768 and level in [1, 32768] (got %d x %d, "
+                            "level %d)", who, fw, fh, level);
     BoxListIn b;
     if ((rc = ctx->box_list_in(who, boxes, n, false, 0, &b))) return rc;
     Ctx::Nv12Dev nin{}, nout{};
     if ((rc = ctx->nv12_in(*in, n, fh, fw, where, &nin))) return rc;
     if ((rc = ctx->nv12_out_begin(*out, n, fh, fw, where, &nout))) return rc;
-    if ((rc = ctx->launch_mosaic_nv12(nin, nout, n, fh, fw, b.cnt, b.xy, boxes->cap, nullptr, nullptr, 0, level, ctx->cells)))
+    if ((rc = ctx->launch_nv12_pass(nin, nout, n, fh, fw, b.cnt, b.xy, boxes->cap, nullptr, nullptr, 0, pass, level, cells)))
         return rc;
     if ((rc = ctx->nv12_out_finish(*out, nout, n, fh, fw, where))) return rc;
     if (where == VD_HOST || b.staged) VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // host results; staging reused
     return VD_OK;
+}
+
+int vd_mosaic_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n, int fh, int fw, int where,
+                   const vd_boxes* boxes, int level) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    // the context's blur mode chooses the pass, as it does for vd_process_nv12
+    return nv12_blur_entry(ctx, "vd_mosaic_nv12", in, out, n, fh, fw, where, boxes, ctx->nv12_cfg_pass(), level, ctx->cells);
+}
+
+int vd_smooth_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n, int fh, int fw, int where,
+                   const vd_boxes* boxes, int level, int cells) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (cells < VD_CELLS_MIN || cells > VD_CELLS_MAX)
+        return vd_set_error(VD_ERR_ARG, "vd_smooth_nv12: cells %d outside [%d, %d]", cells, VD_CELLS_MIN, VD_CELLS_MAX);
+    if (level < 1 || level > 32768) return vd_set_error(VD_ERR_ARG, "vd_smooth_nv12: level %d outside [1, 32768]", level);
+    return nv12_blur_entry(ctx, "vd_smooth_nv12", in, out, n, fh, fw, where, boxes, Ctx::RECT_SMOOTH, level, cells);
 }
 
 int vd_process_lead(vd_ctx* h, const uint8_t* in, int n, int fh, int fw, size_t pitch, int where, int flags,

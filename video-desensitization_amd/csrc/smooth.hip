@@ -48,6 +48,25 @@
 // same sums, so two runs give the same bytes.
 // HBM traffic = read + write of every frame (2*W*H*3 bytes) + one read and one write of every
 // clipped box.
+//
+// NV12 frames (vd_smooth_nv12, vd_process_nv12 / vd_mosaic_nv12 in a Gaussian-mode context with
+// vd_cells on; include/vdmi.h at vd_nv12). The box pass is one body over the bytes per sample C:
+// 3 for RGB, 1 for the luma plane (an h x w image, rectangle c = clip(b), f = L(b)), 2 for the
+// chroma plane (an (h/2) x (w/2) image of U, V pairs, rectangle cc = (c.x1 >> 1, c.y1 >> 1,
+// (c.x2 + 1) >> 1, (c.y2 + 1) >> 1), fc = (L(b) + 1) >> 1). Only x = bc / C and the owner's
+// comparison differ: in both planes the owner of a sample is the box with the largest LUMA level
+// L(b) among the boxes whose rectangle of that plane holds it (ties to the lowest index), so both
+// planes hide the same box where boxes overlap (L = 7 and L = 8 share fc = 4).
+// Chroma grid bound: cw <= bw / 2 + 1 <= N * L / 2 + 1 <= N * fc + 1, so a chroma grid has at
+// most N + 1 cells per side, and reaches it (N = 2, level 1, box (1, 0, 5, 4): L = 2, fc = 1,
+// cc = (0, 0, 3, 2)); the LDS holds max(N^2 * 3, (N + 1)^2 * 2) sums.
+//   smooth_copy_nv12_kernel  [0, w) of every row of both planes in -> out, one workgroup per
+//                            (frame, band of CR rows of one plane); 16-B vectors where the two
+//                            rows are congruent mod 16, bytes otherwise; pad bytes and the rows
+//                            between the planes are never touched.
+//   smooth_box_nv12_kernel   grid (SLOTS, frames, 2 * PARTS): the plane is the upper half of z.
+// HBM traffic = read + write of every frame at 1.5 B/px + one read and one write of every clipped
+// box per plane. No scratch memory.
 #include "vd_kernel.h"
 #include "vdmi.h"
 
@@ -63,8 +82,15 @@ constexpr int PART_PX = 16384;   // ... one per this many pixels of the clipped 
 constexpr int BEAT_CAP = 128;    // beating boxes listed in LDS; more: the global list is walked per pixel
 constexpr int F32_MAX = 4096;    // largest f whose cell sums fit uint32
 
+// a plane of the batch: frame f at + f * stride, rows of `pitch` bytes
+struct SmoothPlane {
+    const uint8_t* in; uint8_t* out;
+    size_t in_pitch, in_stride, out_pitch, out_stride;
+};
+
 struct SmoothArgs {
-    const uint8_t* in; uint8_t* out; int n, h, w; size_t pitch;
+    SmoothPlane pl[2];                               // RGB: pl[0] alone; NV12: luma, chroma
+    int n, h, w;                                     // frames; the frame's (luma) size, which boxes are clipped to
     const int* cnt0; const int* xy0; int cap0;      // list 0 (faces)
     const int* cnt1; const int* xy1; int cap1;      // list 1 (plates, optional)
     int level, cells;
@@ -117,49 +143,82 @@ __global__ __launch_bounds__(THREADS) void smooth_copy_kernel(SmoothArgs a, int 
     const int f = blockIdx.y, y0 = blockIdx.x * CR, tid = threadIdx.x;
     const int rows = min(CR, a.h - y0);
     const size_t row_bytes = (size_t)a.w * 3;
-    const uint8_t* src = a.in + ((size_t)f * a.h + y0) * a.pitch;
-    uint8_t* dst = a.out + ((size_t)f * a.h + y0) * a.pitch;
+    const size_t pitch = a.pl[0].in_pitch;                 // RGB: one pitch, frames h * pitch apart
+    const uint8_t* src = a.pl[0].in + ((size_t)f * a.h + y0) * pitch;
+    uint8_t* dst = a.pl[0].out + ((size_t)f * a.h + y0) * pitch;
     if (!vec_ok) {                                         // in and out differ mod 16: bytes
         for (int r = 0; r < rows; ++r)
-            for (size_t i = tid; i < row_bytes; i += THREADS) dst[r * a.pitch + i] = src[r * a.pitch + i];
+            for (size_t i = tid; i < row_bytes; i += THREADS) dst[r * pitch + i] = src[r * pitch + i];
         return;
     }
     // the band itself: one span when the rows are packed, else row by row (padding untouched)
-    if (a.pitch == row_bytes) {
+    if (pitch == row_bytes) {
         copy_span(dst, src, (size_t)rows * row_bytes, tid);
     } else {
-        for (int r = 0; r < rows; ++r) copy_span(dst + r * a.pitch, src + r * a.pitch, row_bytes, tid);
+        for (int r = 0; r < rows; ++r) copy_span(dst + r * pitch, src + r * pitch, row_bytes, tid);
+    }
+}
+
+// NV12: bands [0, by) are luma rows, the rest chroma rows; a row of either plane has w bytes
+__global__ __launch_bounds__(THREADS) void smooth_copy_nv12_kernel(SmoothArgs a, int by) {
+    const int f = blockIdx.y, tid = threadIdx.x;
+    const int P = (int)blockIdx.x >= by ? 1 : 0;
+    const int y0 = ((int)blockIdx.x - (P ? by : 0)) * CR;
+    const int rows = min(CR, (P ? a.h / 2 : a.h) - y0);
+    const SmoothPlane& pl = a.pl[P];
+    const size_t row_bytes = (size_t)a.w;
+    const uint8_t* src = pl.in + (size_t)f * pl.in_stride + (size_t)y0 * pl.in_pitch;
+    uint8_t* dst = pl.out + (size_t)f * pl.out_stride + (size_t)y0 * pl.out_pitch;
+    if (pl.in_pitch == row_bytes && pl.out_pitch == row_bytes) {   // packed rows: the band is one span
+        const size_t nb = (size_t)rows * row_bytes;
+        if ((((uintptr_t)src ^ (uintptr_t)dst) & 15) == 0) copy_span(dst, src, nb, tid);
+        else for (size_t i = tid; i < nb; i += THREADS) dst[i] = src[i];
+        return;
+    }
+    for (int r = 0; r < rows; ++r) {                       // uniform over the workgroup
+        const uint8_t* sr = src + (size_t)r * pl.in_pitch;
+        uint8_t* dr = dst + (size_t)r * pl.out_pitch;
+        if ((((uintptr_t)sr ^ (uintptr_t)dr) & 15) == 0) copy_span(dr, sr, row_bytes, tid);
+        else for (size_t i = tid; i < row_bytes; i += THREADS) dr[i] = sr[i];
     }
 }
 
 // t(x, j) of the definition for one channel: the row of means j, the two clamped cell columns
 // and the weight r of the second
+template <int C>
 __device__ __forceinline__ uint32_t across(const uint32_t* mean, int j, int sw, int ia, int ib, uint32_t r,
                                            uint32_t f, int ch) {
-    const uint32_t va = mean[(j * sw + ia) * 3 + ch], vb = mean[(j * sw + ib) * 3 + ch];
+    const uint32_t va = mean[(j * sw + ia) * C + ch], vb = mean[(j * sw + ib) * C + ch];
     return ((2u * f - r) * va + r * vb + f) / (2u * f);
 }
 
-__global__ __launch_bounds__(THREADS) void smooth_box_kernel(SmoothArgs a) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t s_cell[];   // [sh][sw][3] sums, then Q8.4 means
-    __shared__ int4 s_beat[BEAT_CAP];                   // clipped rectangles of the boxes beating this one
-    __shared__ int s_nbeat;
-    const int fr = blockIdx.y, tid = threadIdx.x, part = blockIdx.z;
+// The box pass of one plane with C bytes per sample (3: RGB, 1: luma, 2 and CHROMA: the U, V pairs).
+// s_cell: [sh][sw][C] sums, then Q8.4 means; s_beat: this plane's rectangles of the boxes beating
+// the box in hand.
+template <int C, bool CHROMA>
+__device__ __forceinline__ void smooth_box_body(const SmoothArgs& a, const SmoothPlane& pl, int part, uint32_t* s_cell,
+                                                int4* s_beat, int& s_nbeat) {
+    const int fr = blockIdx.y, tid = threadIdx.x;
     int n0;
     const int nb = frame_boxes(a, fr, n0);
-    const uint8_t* src = a.in + (size_t)fr * a.h * a.pitch;
-    uint8_t* dst = a.out + (size_t)fr * a.h * a.pitch;
+    const uint8_t* src = pl.in + (size_t)fr * pl.in_stride;
+    uint8_t* dst = pl.out + (size_t)fr * pl.out_stride;
+    // the rectangle of this plane of a clipped (luma) box
+    auto plane_rect = [](int4 q) { return CHROMA ? make_int4(q.x >> 1, q.y >> 1, (q.z + 1) >> 1, (q.w + 1) >> 1) : q; };
 
     for (int k = blockIdx.x; k < nb; k += gridDim.x) {     // uniform over the workgroup
         const int4 b = raw_box(a, fr, k, n0);
         int4 c;
         if (!clip_box(b, a.w, a.h, c)) continue;
-        const int f = box_level(a, b);
+        c = plane_rect(c);
+        const int L = box_level(a, b);                     // what the owner is chosen by, in every plane
+        const int f = CHROMA ? (L + 1) >> 1 : L;
         const int bw = c.z - c.x, bh = c.w - c.y;
         const int sw = (bw + f - 1) / f, sh = (bh + f - 1) / f;
-        const int ncell = sw * sh * 3;
+        const int ncell = sw * sh * C;
         const bool wide = f > F32_MAX;                     // 64-bit sums, at most 8 x 8 cells
-        if (sw > a.cells || sh > a.cells || (wide && ncell > THREADS)) continue;   // the LDS holds cells^2: cannot happen for h, w <= 32768
+        const int gmax = a.cells + (CHROMA ? 1 : 0);       // the chroma grid bound (header)
+        if (sw > gmax || sh > gmax || (wide && ncell > THREADS)) continue;   // the LDS holds that many: cannot happen for h, w <= 32768
         // a large box is cut into bands of whole cell rows, one per part (blockIdx.z)
         const int nparts = min(min(PARTS, sh), max(1, (int)(((long long)bw * bh) / PART_PX)));
         if (part >= nparts) continue;
@@ -176,9 +235,10 @@ __global__ __launch_bounds__(THREADS) void smooth_box_kernel(SmoothArgs a) {
             const int4 bm = raw_box(a, fr, m, n0);
             int4 cm;
             if (!clip_box(bm, a.w, a.h, cm)) continue;
+            cm = plane_rect(cm);
             if (cm.x >= c.z || cm.z <= c.x || cm.y >= c.w || cm.w <= c.y) continue;
             const int fm = box_level(a, bm);
-            if (fm > f || (fm == f && m < k)) {
+            if (fm > L || (fm == L && m < k)) {
                 const int i = atomicAdd(&s_nbeat, 1);
                 if (i < BEAT_CAP) s_beat[i] = cm;
             }
@@ -186,7 +246,7 @@ __global__ __launch_bounds__(THREADS) void smooth_box_kernel(SmoothArgs a) {
 
         // thread layout of both walks: a row has nbx bytes; a narrow box is cut into RG groups of
         // consecutive rows walked side by side, a wide one is walked CP byte columns at a time
-        const int nbx = bw * 3;
+        const int nbx = bw * C;
         const int CP = nbx < THREADS ? nbx : THREADS;
         const int RG = nbx < THREADS ? THREADS / nbx : 1;
         const int rg = tid / CP, col0 = tid - rg * CP;
@@ -200,20 +260,20 @@ __global__ __launch_bounds__(THREADS) void smooth_box_kernel(SmoothArgs a) {
         const int jA = part * sh / nparts, jB = (part + 1) * sh / nparts;
         int ya, yb;
         my_rows(max(jA - 1, 0) * f, min((jB + 1) * f, bh), ya, yb);
-        const uint8_t* sbox = src + (size_t)c.y * a.pitch + (size_t)c.x * 3;
-        uint8_t* dbox = dst + (size_t)c.y * a.pitch + (size_t)c.x * 3;
+        const uint8_t* sbox = src + (size_t)c.y * pl.in_pitch + (size_t)c.x * C;
+        uint8_t* dbox = dst + (size_t)c.y * pl.out_pitch + (size_t)c.x * C;
 
         // (2) cell sums
         if (ya < yb)
             for (int bc = col0; bc < nbx; bc += CP) {
-                const int x = bc / 3, ch = bc - 3 * x, i = x / f;
+                const int x = bc / C, ch = bc - C * x, i = x / f;
                 for (int j = ya / f; j * f < yb; ++j) {
                     const int y0 = max(ya, j * f), y1 = min(yb, j * f + f);
                     uint32_t acc = 0;                      // at most 255 * 32768
-                    const uint8_t* p = sbox + (size_t)y0 * a.pitch + bc;
+                    const uint8_t* p = sbox + (size_t)y0 * pl.in_pitch + bc;
 #pragma unroll 8
-                    for (int y = y0; y < y1; ++y, p += a.pitch) acc += *p;
-                    const int e = (j * sw + i) * 3 + ch;
+                    for (int y = y0; y < y1; ++y, p += pl.in_pitch) acc += *p;
+                    const int e = (j * sw + i) * C + ch;
                     if (wide) atomicAdd(&s_cell64[e], (unsigned long long)acc);
                     else atomicAdd(&s_cell[e], acc);
                 }
@@ -222,7 +282,7 @@ __global__ __launch_bounds__(THREADS) void smooth_box_kernel(SmoothArgs a) {
 
         // (3) sums -> Q8.4 means, in place
         auto mean_of = [&](int e, unsigned long long S) -> uint32_t {
-            const int cell = e / 3, j = cell / sw, i = cell - j * sw;
+            const int cell = e / C, j = cell / sw, i = cell - j * sw;
             const uint32_t n = (uint32_t)(min(i * f + f, bw) - i * f) * (uint32_t)(min(j * f + f, bh) - j * f);
             if ((S >> 27) == 0) return (16u * (uint32_t)S + n / 2) / n;
             return (uint32_t)((16ULL * S + n / 2) / n);
@@ -242,7 +302,7 @@ __global__ __launch_bounds__(THREADS) void smooth_box_kernel(SmoothArgs a) {
         if (ya < yb) {
             const uint32_t uf = (uint32_t)f, f2 = 2u * uf, d = 32u * uf;
             for (int bc = col0; bc < nbx; bc += CP) {
-                const int x = bc / 3, ch = bc - 3 * x;
+                const int x = bc / C, ch = bc - C * x;
                 const int u = 2 * x + 1 - f;               // > -2f
                 const int i0 = u < 0 ? -1 : (int)((uint32_t)u / f2);
                 const uint32_t r = (uint32_t)(u - (int)f2 * i0);
@@ -257,8 +317,8 @@ __global__ __launch_bounds__(THREADS) void smooth_box_kernel(SmoothArgs a) {
                 int dq = 0;
                 auto cell_rows = [&]() {
                     const int ja = min(max(j0, 0), sh - 1), jb = min(max(j0 + 1, 0), sh - 1);
-                    const uint32_t t0 = across(s_cell, ja, sw, ia, ib, r, uf, ch);
-                    const uint32_t t1 = jb == ja ? t0 : across(s_cell, jb, sw, ia, ib, r, uf, ch);
+                    const uint32_t t0 = across<C>(s_cell, ja, sw, ia, ib, r, uf, ch);
+                    const uint32_t t1 = jb == ja ? t0 : across<C>(s_cell, jb, sw, ia, ib, r, uf, ch);
                     const uint32_t T = (f2 - s) * t0 + s * t1 + 16u * uf;
                     o = T / d;
                     rem = T - o * d;
@@ -268,8 +328,8 @@ __global__ __launch_bounds__(THREADS) void smooth_box_kernel(SmoothArgs a) {
                 };
                 cell_rows();
                 const int gx = c.x + x;
-                uint8_t* p = dbox + (size_t)ya * a.pitch + bc;
-                for (int y = ya; y < yb; ++y, p += a.pitch) {
+                uint8_t* p = dbox + (size_t)ya * pl.out_pitch + bc;
+                for (int y = ya; y < yb; ++y, p += pl.out_pitch) {
                     bool mine = true;
                     if (nbeat) {
                         const int gy = c.y + y;
@@ -284,9 +344,10 @@ __global__ __launch_bounds__(THREADS) void smooth_box_kernel(SmoothArgs a) {
                                 const int4 bm = raw_box(a, fr, m, n0);
                                 int4 cm;
                                 if (!clip_box(bm, a.w, a.h, cm)) continue;
+                                cm = plane_rect(cm);
                                 if (gx < cm.x || gx >= cm.z || gy < cm.y || gy >= cm.w) continue;
                                 const int fm = box_level(a, bm);
-                                if (fm > f || (fm == f && m < k)) mine = false;
+                                if (fm > L || (fm == L && m < k)) mine = false;
                             }
                         }
                     }
@@ -307,11 +368,32 @@ __global__ __launch_bounds__(THREADS) void smooth_box_kernel(SmoothArgs a) {
     }
 }
 
+__global__ __launch_bounds__(THREADS) void smooth_box_kernel(SmoothArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_cell[];
+    __shared__ int4 s_beat[BEAT_CAP];
+    __shared__ int s_nbeat;
+    smooth_box_body<3, false>(a, a.pl[0], blockIdx.z, s_cell, s_beat, s_nbeat);
+}
+
+// both planes of NV12 frames: grid z = plane * PARTS + part (uniform over the workgroup)
+__global__ __launch_bounds__(THREADS) void smooth_box_nv12_kernel(SmoothArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_cell[];
+    __shared__ int4 s_beat[BEAT_CAP];
+    __shared__ int s_nbeat;
+    if (blockIdx.z < PARTS) smooth_box_body<1, false>(a, a.pl[0], blockIdx.z, s_cell, s_beat, s_nbeat);
+    else smooth_box_body<2, true>(a, a.pl[1], blockIdx.z - PARTS, s_cell, s_beat, s_nbeat);
+}
+
 }  // namespace
 
+// The cell sums of one box: cells^2 * 3 (RGB) or (cells + 1)^2 * 2 (a chroma grid, header) uint32,
+// or 64-bit sums of the few cells a level above F32_MAX leaves (RGB and luma: 8 x 8; chroma pairs:
+// min(cells + 1, 4) squared, since cw <= 16384 and fc > 4096).
 size_t vd_smooth_lds_bytes(int cells) {
-    const int c8 = std::min(cells, 8);
-    return std::max((size_t)cells * cells * 3 * 4, (size_t)c8 * c8 * 3 * 8);
+    const int c8 = std::min(cells, 8), c4 = std::min(cells + 1, 4);
+    const size_t narrow = std::max((size_t)cells * cells * 3 * 4, (size_t)(cells + 1) * (cells + 1) * 2 * 4);
+    const size_t wide = std::max((size_t)c8 * c8 * 3 * 8, (size_t)c4 * c4 * 2 * 8);
+    return std::max(narrow, wide);
 }
 
 hipError_t vd_launch_smooth(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch,
@@ -322,13 +404,40 @@ hipError_t vd_launch_smooth(const uint8_t* in, uint8_t* out, int n, int h, int w
     if (h > 32768 || w > 32768 || level < 1 || level > 32768 || cells < VD_CELLS_MIN || cells > VD_CELLS_MAX ||
         n > 65535 || pitch < (size_t)w * 3)
         return hipErrorInvalidValue;
-    SmoothArgs a{in, out, n, h, w, pitch, cnt0, xy0, cap0, cnt1, xy1, cap1, level, cells};
+    SmoothArgs a{};
+    a.pl[0] = SmoothPlane{in, out, pitch, (size_t)h * pitch, pitch, (size_t)h * pitch};
+    a.n = n; a.h = h; a.w = w;
+    a.cnt0 = cnt0; a.xy0 = xy0; a.cap0 = cap0;
+    a.cnt1 = cnt1; a.xy1 = xy1; a.cap1 = cap1;
+    a.level = level; a.cells = cells;
     if (stage == 0) {
         // vectors need in and out congruent mod 16 (then every row's spans are, at one pitch)
         const int vec_ok = (((uintptr_t)in ^ (uintptr_t)out) & 15) == 0;
         hipLaunchKernelGGL(smooth_copy_kernel, dim3((h + CR - 1) / CR, n), dim3(THREADS), 0, s, a, vec_ok);
     } else if (cnt0 || cnt1) {
         hipLaunchKernelGGL(smooth_box_kernel, dim3(SLOTS, n, PARTS), dim3(THREADS), vd_smooth_lds_bytes(cells), s, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t vd_launch_smooth_nv12(const Nv12MosaicArgs& v, int stage, hipStream_t s) {
+    if (v.n <= 0 || v.h <= 0 || v.w <= 0 || (v.h & 1) || (v.w & 1) || v.h > 32768 || v.w > 32768 || v.level < 1 ||
+        v.level > 32768 || v.cells < VD_CELLS_MIN || v.cells > VD_CELLS_MAX || v.n > 65535 ||
+        v.in_pitch < (size_t)v.w || v.out_pitch < (size_t)v.w || !v.in || !v.out)
+        return hipErrorInvalidValue;
+    SmoothArgs a{};
+    a.pl[0] = SmoothPlane{v.in, v.out, v.in_pitch, v.in_stride, v.out_pitch, v.out_stride};
+    a.pl[1] = SmoothPlane{v.in + v.in_uv, v.out + v.out_uv, v.in_pitch, v.in_stride, v.out_pitch, v.out_stride};
+    a.n = v.n; a.h = v.h; a.w = v.w;
+    a.cnt0 = v.cnt0; a.xy0 = v.xy0; a.cap0 = v.cap0;
+    a.cnt1 = v.cnt1; a.xy1 = v.xy1; a.cap1 = v.cap1;
+    a.level = v.level; a.cells = v.cells;
+    if (stage == 0) {
+        const int by = (v.h + CR - 1) / CR, bc = (v.h / 2 + CR - 1) / CR;
+        hipLaunchKernelGGL(smooth_copy_nv12_kernel, dim3(by + bc, v.n), dim3(THREADS), 0, s, a, by);
+    } else if (v.cnt0 || v.cnt1) {
+        hipLaunchKernelGGL(smooth_box_nv12_kernel, dim3(SLOTS, v.n, 2 * PARTS), dim3(THREADS),
+                           vd_smooth_lds_bytes(v.cells), s, a);
     }
     return hipGetLastError();
 }

@@ -462,6 +462,10 @@ hipError_t vd_launch_smooth(const uint8_t* in, uint8_t* out, int n, int h, int w
                             const int* cnt0, const int* xy0, int cap0,
                             const int* cnt1, const int* xy1, int cap1, int level, int cells, int stage,
                             hipStream_t s);
+// ... of NV12 frames, both planes (smooth.hip; include/vdmi.h at vd_nv12): stage 0 copies [0, w) of
+// every row of both planes, stage 1 is the box pass of both planes in one launch. Even h, w <= 32768.
+hipError_t vd_launch_smooth_nv12(const Nv12MosaicArgs& a, int stage, hipStream_t s);
+size_t vd_smooth_lds_bytes(int cells);   // dynamic LDS of either box pass (RGB cells^2 * 3, chroma (cells + 1)^2 * 2 sums)
 // Gaussian blur of box lists (blur.hip): plan + band pass + dependent-box pass on `s`.
 // q: the ksize Q20 weights of vd_blur_weights; table: vd_blur_table_bytes(n, h, pitch, tcap) bytes.
 hipError_t vd_launch_blur(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch,
@@ -559,6 +563,15 @@ struct MaskArgs {
 };
 hipError_t vd_launch_mask_grow(const MaskArgs& a, hipStream_t s);
 hipError_t vd_launch_mask_restore(const MaskArgs& a, hipStream_t s);
+// Restore on NV12 frames (include/vdmi.h at vd_nv12, "ellipse"), after the rectangular NV12 pass on the
+// same stream: luma bytes of the rows' clipped boxes outside every ellipse, and chroma pairs of
+// their chroma rectangles none of whose four luma pixels lies in an ellipse, are copied in -> out.
+struct MaskNv12Args {
+    const uint8_t* in; uint8_t* out; int n, h, w;
+    size_t in_pitch, in_uv, in_stride, out_pitch, out_uv, out_stride;
+    const int* m_cnt; const int* m_xy; int mcap;     // the grown merged rows (MaskArgs)
+};
+hipError_t vd_launch_mask_restore_nv12(const MaskNv12Args& a, hipStream_t s);
 
 // Tiled face detection (include/vdmi.h at vd_tiles). T = 1 + rows * cols net inputs per frame:
 // input 0 the whole frame, input 1 + r * cols + c tile (r, c); every tile is tw x th pixels.

@@ -130,6 +130,8 @@ SIGNATURES = [
                              ctypes.POINTER(vd_boxes), ctypes.POINTER(vd_boxes)]),
     ("vd_mosaic_nv12", _I, [_P, ctypes.POINTER(vd_nv12), ctypes.POINTER(vd_nv12), _I, _I, _I, _I,
                             ctypes.POINTER(vd_boxes), _I]),
+    ("vd_smooth_nv12", _I, [_P, ctypes.POINTER(vd_nv12), ctypes.POINTER(vd_nv12), _I, _I, _I, _I,
+                            ctypes.POINTER(vd_boxes), _I, _I]),
     ("vd_nv12_to_rgb", _I, [ctypes.POINTER(vd_nv12), _I, _I, _I, _P, _SZ]),
     ("vdt_letterbox_nv12", _I, [_P, ctypes.POINTER(vd_nv12), _I, _I, _I, _I, _P, _I]),
     ("vd_timing_enable", _I, [_P, _I]),

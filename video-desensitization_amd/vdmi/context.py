@@ -519,7 +519,9 @@ class Context:
                      height=None):
         """vd_process_nv12: process() on NV12 frames (uint8 [n, rows, w]; _nv12_arg gives the
         layouts). Detections are exactly process()'s on nv12_to_rgb(frames); with VD_PROC_MOSAIC
-        both planes of `out` (default: new surfaces like the input) are pixelated. -> (out, faces, plates)."""
+        both planes of `out` (default: new surfaces like the input) are blurred as the context's
+        settings ask: pixelation, or with blur="gaussian" and cells on the scaled smooth blur, under
+        the mask setting (blur="gaussian" with cells=0 has no NV12 pass). -> (out, faces, plates)."""
         d, n, h, w, where, keep = _nv12_arg(frames, height, matrix, range)
         if flags is None:
             flags = _lib.VD_PROC_FACES | _lib.VD_PROC_MOSAIC
@@ -545,9 +547,8 @@ class Context:
             plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
         return out, faces, plates
 
-    def mosaic_nv12(self, frames, boxes_xyxy, counts=None, level=None, out=None, height=None):
-        """vd_mosaic_nv12: out-of-place pixelation of both planes of NV12 frames with caller lists
-        (the boxes_xyxy / counts forms of mosaic()); the context's mask growth and cells apply."""
+    def _nv12_blur(self, fn, frames, boxes_xyxy, counts, out, height, *tail):
+        """What mosaic_nv12() / smooth_nv12() share: fn(ctx, in, out, n, h, w, where, boxes, *tail)."""
         d, n, h, w, where, keep = _nv12_arg(frames, height)
         if isinstance(boxes_xyxy, (_lib.HostBoxes, DeviceBoxes)):
             s = boxes_xyxy.struct()
@@ -563,10 +564,27 @@ class Context:
         out, od, geo, okeep = self._nv12_out(frames, out, height)
         if geo != (n, h, w, where):
             raise ValueError("out must hold NV12 frames of the input's n, h, w in the same memory (host / device)")
-        check(self._lib.vd_mosaic_nv12(self._h, ctypes.byref(d), ctypes.byref(od), n, h, w, where, ctypes.byref(s),
-                                       int(level or self.cfg.mosaic_level)))
+        check(fn(self._h, ctypes.byref(d), ctypes.byref(od), n, h, w, where, ctypes.byref(s), *tail))
         del keep, bkeep, okeep
         return out
+
+    def mosaic_nv12(self, frames, boxes_xyxy, counts=None, level=None, out=None, height=None):
+        """vd_mosaic_nv12: the out-of-place blur of both planes of NV12 frames with caller lists (the
+        boxes_xyxy / counts forms of mosaic()) that the context's blur mode asks for: pixelation, or
+        in a blur="gaussian" context with cells on the scaled smooth blur. The context's mask
+        setting and cells apply."""
+        return self._nv12_blur(self._lib.vd_mosaic_nv12, frames, boxes_xyxy, counts, out, height,
+                               int(level or self.cfg.mosaic_level))
+
+    def smooth_nv12(self, frames, boxes_xyxy, counts=None, level=None, cells=None, out=None, height=None):
+        """vd_smooth_nv12: the out-of-place scaled smooth blur of both planes of NV12 frames with
+        caller lists, the counterpart of smooth(). level defaults to the context's mosaic_level,
+        cells to the context's setting (ValueError if that is 0: off); the mask setting applies."""
+        cells = _lib.check_cells(self.cells if cells is None else cells)
+        if cells == 0:
+            raise ValueError("smooth_nv12() needs cells in 2 .. 64 (the context's setting is 0: off)")
+        return self._nv12_blur(self._lib.vd_smooth_nv12, frames, boxes_xyxy, counts, out, height,
+                               int(level or self.cfg.mosaic_level), cells)
 
     def letterbox_nv12(self, frames, cpad=4, matrix="bt709", range="limited", height=None):
         """vdt_letterbox_nv12: the face canvas of NV12 frames by the product path's NV12 kernel."""
