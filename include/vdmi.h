@@ -596,8 +596,9 @@ int vd_cell_level(int W, int H, int level, int cells);
  * which the merge suppresses or keeps beside the full one -- for an anonymiser covering more is
  * harmless. The merged lists ARE the face detections of the call: the caller's `faces` (vd_boxes
  * contract), vd_read_boxes(VD_NET_RETINAFACE), D_t of the box hold, and what the blur hides.
- * Plates are detected on the whole frame as before (tiling the plate branch is out of scope), and
- * the paired face+plate letterbox is not used while tiling is on. */
+ * Which nets the tiling applies to is a second setting (vd_tiles_nets below): faces alone by
+ * default, and plates are then detected on the whole frame exactly as in an untiled context. The
+ * paired face+plate letterbox is not used while the face net is tiled. */
 #define VD_TILES_MAX 4
 /* The rectangles (x, y, w, h) of an h x w frame: xywh[0] the frame, xywh[1 + r*cols + c] tile
  * (r, c); *count = 1 + rows*cols (either pointer may be NULL). Host only, no context, no GPU: the
@@ -614,6 +615,58 @@ int vd_tiles(vd_ctx* ctx, int rows, int cols, int overlap_pct);
  * vd_boxes contract (may be NULL: vd_read_boxes hands the rows out). VD_ERR_STATE with tiling off
  * or before the RetinaFace weights are loaded; n*T > cfg.max_batch: VD_ERR_ARG. */
 int vd_tiles_merge(vd_ctx* ctx, const vd_boxes* lists, int n, int h, int w, vd_boxes* out);
+
+/* ---- tiled plate detection: small plates in high-resolution frames -----------------
+ * The plate net sees a frame shrunk onto its plate_imgsz canvas too: a 3840x2160 frame is scaled by
+ * 1/6, and a 440 x 140 mm plate 25 m ahead of a 3840-px-wide, 60-degree camera (about 58 x 19 px in
+ * the source) reaches the net about 10 x 3 px, under one cell of the stride-8 head; on a (2, 2, 20)
+ * tile it is 16 x 5 px. With a tiling (R, C, O) set by vd_tiles, vd_tiles_nets says which nets are
+ * tiled: VD_TILE_FACES (the default: nothing changes by a byte, no launch is added, no memory is
+ * allocated), VD_TILE_PLATES or both. A face net that is not tiled runs exactly as in an untiled
+ * context. When plates are tiled, every call that runs the plate net (vd_detect_plates, vd_process /
+ * vd_process_lead with VD_PROC_PLATES) runs it on the whole frame and on the R x C rectangles of
+ * vd_tile_rects (the face tiling's rectangles), moves the tile boxes back to frame coordinates and
+ * merges the T = 1 + R*C lists per frame into one. To the bit:
+ *   per input  the keep list of input t of frame f is exactly what vd_detect_plates returns for a
+ *              standalone frame holding rectangle t of frame f: the ultralytics letterbox of that
+ *              rectangle (scale-up included, pad 114, stride-32 auto padding; each tile canvas is
+ *              bit-identical to the plate letterbox of a frame holding those pixels), the forward,
+ *              the candidate test, the class-offset NMS at cfg.plate_iou, plate_max_det, and
+ *              scale_boxes with the rectangle's own gain and pad, clipped to the rectangle. The whole
+ *              frame and the tiles can need canvases of different sizes (360x640 with (1, 3, 0):
+ *              384x640 against 640x384), so the tile inputs go through a forward of their own
+ *              (inputs f*R*C + (t-1)); the result does not depend on how the inputs are batched.
+ *   map        box i of input t > 0 becomes X = x + (float)x0_t, Y = y + (float)y0_t on both corners
+ *              (one float32 add each, no FMA); input 0 is left as it is;
+ *   order      descending score compared as bit patterns, ties to the lower t, then to the lower list
+ *              position (the key of the face merge);
+ *   NMS        greedy over that order on the mapped boxes: a kept box a suppresses a later box b iff
+ *              label(a) == label(b) and IoU(a, b) > cfg.plate_iou, with area = (x2 - x1) * (y2 - y1)
+ *              in float32 and the float32 quotient compared against the double. No class offset is
+ *              added (7680 is smaller than the frames accepted here, and an offset would cost the
+ *              higher classes mantissa bits); for class 0 the arithmetic equals the per-input rule's;
+ *   no cap     the merged list has no max_det: the merged rows hold T x the per-input keep capacity,
+ *              so nothing is ever dropped, and no border rule drops tile boxes;
+ *   emit       xyxy_f = the mapped box, xyxy = int() of it, score, label = the class id.
+ * One launch (timing family 3) on the plate stream, before the plate branch joins. The merged list IS
+ * the plate detections of the call: the caller's `plates` (vd_boxes contract, unchanged),
+ * vd_read_boxes(VD_NET_YOLOV8N), the plate part of D_t for hold, lead and the blur list under
+ * VD_PROC_MOSAIC_PLATES. Capacity: a call that runs a tiled net needs n*T <= cfg.max_batch
+ * (VD_ERR_ARG, the message names the largest n), whichever net is tiled. Rescue with tiling on stays
+ * refused for any nets value, and an NV12 call that would run a tiled net is VD_ERR_STATE. */
+#define VD_TILE_FACES 1
+#define VD_TILE_PLATES 2
+/* Which nets the tiling applies to: nets in {VD_TILE_FACES, VD_TILE_PLATES, VD_TILE_FACES |
+ * VD_TILE_PLATES}; anything else is VD_ERR_ARG and the setting stays unchanged. Stored, with no
+ * effect, while R*C == 1. VD_ERR_STATE while lead frames are pending. A change while tiling is on
+ * forgets the hold history, as vd_tiles does (the merged rows change capacity); setting the value
+ * the context already has changes nothing. */
+int vd_tiles_nets(vd_ctx* ctx, int nets);
+/* The plate merge step alone on caller lists, by the kernel of the detect path: vd_tiles_merge's
+ * layout (row f*T+t), staging, capacity and state rules, with cap at most the plate net's per-input
+ * keep capacity; `label` is read as the class (NULL: 0). VD_ERR_STATE with tiling off or before the
+ * plate weights are loaded. */
+int vd_tiles_merge_plates(vd_ctx* ctx, const vd_boxes* lists, int n, int h, int w, vd_boxes* out);
 
 /* ---- NV12 frames: detect and blur video surfaces directly -------------------------
  * A video decoder hands out NV12 surfaces and an encoder takes them back: a pitched luma plane
@@ -781,6 +834,11 @@ int vdt_bottleneck(vd_ctx* ctx, const float* x, int n, int h, int w, int cin,
 int vdt_jpeg_coefficients(const uint8_t* data, size_t size, int16_t* out, size_t cap_blocks, int* nblocks);
 int vdt_plate_raw(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w, size_t pitch,
                   int where, float* out, int* anchors);
+/* vdt_plate_raw for the n*R*C tile inputs of a tiling context (vd_tiles; VD_ERR_STATE when off), by
+ * the tile letterbox kernel and the forward of the product path: input f*R*C + (t-1) in
+ * vdt_plate_raw's layout; out NULL queries A. n*T <= cfg.max_batch as for the detect calls. */
+int vdt_plate_raw_tiles(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w, size_t pitch,
+                        int where, float* out, int* anchors);
 /* Plate post-processing only (score, threshold, DFL decode, NMS, scale_boxes) on caller-provided raw
  * heads in vdt_plate_raw's layout, host f32 [n][64 + nc][A], for n frames of h x w whose canvas the
  * context's last plate forward (vdt_plate_raw, vd_detect_plates, vd_process) was run for; honours the

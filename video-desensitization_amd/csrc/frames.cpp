@@ -350,8 +350,8 @@ int Ctx::tiles_set(int rows, int cols, int overlap_pct) {
         return vd_set_error(VD_ERR_STATE, "vd_tiles: %d frames are pending in the look-ahead ring (flush first)", lead.pend);
     VD_CHECK_HIP(hipStreamSynchronize(stream));   // a queued launch may still read the merged rows
     tile_rows = rows; tile_cols = cols; tile_overlap = overlap_pct;
-    tiles_kn = 0;
-    face_rows_merged = false;
+    tiles_kn = ptiles_kn = 0;
+    face_rows_merged = plate_rows_merged = false;
     hold.reset();                                 // the merged rows change capacity: a new stream
     return VD_OK;
 }
@@ -381,23 +381,27 @@ int Ctx::face_letterbox_tiles(const uint8_t* dframes, int n, int h, int w, size_
 
 // Merged rows and spill scratch for the floor(max_batch / T) frames a call can carry: T * kcap
 // boxes per frame, so the bytes do not grow with T (the sort keys alone round up to a power of two).
+// plates: the plate lists, class-aware at cfg.plate_iou, in a buffer of their own (both nets' rows
+// are live after a vd_process call).
 int Ctx::tiles_merge(int n, const TileGrid& g, const int* cnt, const float* xyxy_f, const float* score, const int* label,
-                     int icap, const BoxTargets& t) {
+                     int icap, const BoxTargets& t, bool plates, bool split) {
+    const int kcap = plates ? plate.post.kcap : face.post.kcap;
     const size_t F = std::max(cfg.max_batch / g.T, 1);
-    const size_t mcap = (size_t)g.T * face.post.kcap;
-    if ((size_t)n > F || icap > face.post.kcap || mcap > 0x3fffffffu)
+    const size_t mcap = (size_t)g.T * kcap;
+    if ((size_t)n > F || icap > kcap || mcap > 0x3fffffffu)
         return vd_set_error(VD_ERR_ARG, "tiles merge: n=%d frames of lists of cap %d outside [1, %zu] x [1, %d]", n, icap,
-                            F, face.post.kcap);
+                            F, kcap);
     size_t sort_cap = 1;
     while (sort_cap < mcap) sort_cap <<= 1;
     const size_t rows = F * mcap;
-    const size_t need = rows * (16 + 16 + 16 + 4 + 4 + 4 + 1) + F * sort_cap * 8 + F * 4 + 256;
-    int rc = ensure_staging(&tiles_buf, &tiles_buf_bytes, need);
+    const size_t need = rows * (16 + 16 + 16 + 4 + 4 + 4 + 1 + (plates ? 4 : 0)) + F * sort_cap * 8 + F * 4 + 256;
+    int rc = plates ? ensure_staging(&ptiles_buf, &ptiles_buf_bytes, need) : ensure_staging(&tiles_buf, &tiles_buf_bytes, need);
     if (rc) return rc;
     TileMergeArgs a{};
-    a.n = n; a.g = g; a.A = face.A; a.iou = cfg.nms_iou;
+    a.n = n; a.g = g; a.A = face.A; a.iou = plates ? cfg.plate_iou : cfg.nms_iou;
     a.cnt = cnt; a.xyxy_f = xyxy_f; a.score = score; a.label = label; a.icap = icap;
-    char* p = (char*)tiles_buf;
+    a.plate = plates ? 1 : 0; a.split = split ? 1 : 0;
+    char* p = (char*)(plates ? ptiles_buf : tiles_buf);
     a.m_xyxy = (int*)p; p += rows * 16;
     a.m_xyxy_f = (float*)p; p += rows * 16;
     a.s_box = (float4*)p; p += rows * 16;
@@ -405,6 +409,7 @@ int Ctx::tiles_merge(int n, const TileGrid& g, const int* cnt, const float* xyxy
     a.m_score = (float*)p; p += rows * 4;
     a.m_label = (int*)p; p += rows * 4;
     a.s_area = (float*)p; p += rows * 4;
+    if (plates) { a.s_cls = (int*)p; p += rows * 4; }
     a.m_count = (int*)p; p += (F * 4 + 15) / 16 * 16;
     a.s_supp = (uint8_t*)p;
     a.sort_cap = (int)sort_cap; a.mcap = (int)mcap;
@@ -414,9 +419,33 @@ int Ctx::tiles_merge(int n, const TileGrid& g, const int* cnt, const float* xyxy
     hipError_t e = vd_launch_tiles_merge(a, stream);
     t_end();
     if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "tiles merge: %s", hipGetErrorString(e));
-    tiles_last = a;
-    tiles_kn = n;
-    face_rows_merged = true;
+    if (plates) {
+        ptiles_last = a;
+        ptiles_kn = n;
+        plate_rows_merged = true;
+    } else {
+        tiles_last = a;
+        tiles_kn = n;
+        face_rows_merged = true;
+    }
+    return VD_OK;
+}
+
+int Ctx::tiles_nets_set(int nets) {
+    if (nets != VD_TILE_FACES && nets != VD_TILE_PLATES && nets != (VD_TILE_FACES | VD_TILE_PLATES))
+        return vd_set_error(VD_ERR_ARG, "vd_tiles_nets: nets %d (expected VD_TILE_FACES = 1, VD_TILE_PLATES = 2 or both = 3)",
+                            nets);
+    if (nets == tile_nets) return VD_OK;
+    if (lead.pend)
+        return vd_set_error(VD_ERR_STATE, "vd_tiles_nets: %d frames are pending in the look-ahead ring (flush first)",
+                            lead.pend);
+    if (tiles_on()) {
+        VD_CHECK_HIP(hipStreamSynchronize(stream));   // a queued launch may still read the merged rows
+        tiles_kn = ptiles_kn = 0;
+        face_rows_merged = plate_rows_merged = false;
+        hold.reset();                                 // the merged rows change capacity: a new stream
+    }
+    tile_nets = nets;
     return VD_OK;
 }
 
@@ -437,38 +466,25 @@ int Ctx::face_post_tiled(int n, int h, int w, const TileGrid& g, const BoxTarget
     return tiles_merge(n, g, ps.kcount, ps.kxyxy_f, ps.kscore, ps.klabel, ps.kcap, t);
 }
 
-extern "C" {
-
-int vd_tile_rects(int fh, int fw, int rows, int cols, int overlap_pct, int32_t* xywh, int* count) {
-    if (vd_tile_rects_host(fh, fw, rows, cols, overlap_pct, xywh, count))
-        return vd_set_error(VD_ERR_ARG, "vd_tile_rects: h, w > 0, rows, cols in [1, %d] and overlap_pct in [0, 50] "
-                            "required (got %d x %d, %d, %d, %d)", VD_TILES_MAX, fw, fh, rows, cols, overlap_pct);
-    return VD_OK;
-}
-
-int vd_tiles(vd_ctx* h, int rows, int cols, int overlap_pct) {
-    Ctx* ctx = (Ctx*)h;
-    VD_ENTRY(ctx);
-    return ctx->tiles_set(rows, cols, overlap_pct);
-}
-
-int vd_tiles_merge(vd_ctx* h, const vd_boxes* lists, int n, int fh, int fw, vd_boxes* out) {
-    Ctx* ctx = (Ctx*)h;
-    VD_ENTRY(ctx);
-    if (!ctx->tiles_on()) return vd_set_error(VD_ERR_STATE, "vd_tiles_merge: tiling is off (vd_tiles)");
-    if (!ctx->face.loaded) return vd_set_error(VD_ERR_STATE, "vd_tiles_merge: RetinaFace weights not loaded");
+// vd_tiles_merge / vd_tiles_merge_plates: the merge step alone on caller lists
+static int tiles_merge_entry(Ctx* ctx, const char* who, bool plates, const vd_boxes* lists, int n, int fh, int fw,
+                             vd_boxes* out) {
+    if (!ctx->tiles_on()) return vd_set_error(VD_ERR_STATE, "%s: tiling is off (vd_tiles)", who);
+    if (!(plates ? ctx->plate.loaded : ctx->face.loaded))
+        return vd_set_error(VD_ERR_STATE, "%s: %s weights not loaded", who, plates ? "plate" : "RetinaFace");
     if (!lists || !lists->count || !lists->xyxy_f || !lists->score || lists->cap <= 0)
-        return vd_set_error(VD_ERR_ARG, "vd_tiles_merge: lists need count, xyxy_f, score, cap>0");
-    if (n <= 0 || fh <= 0 || fw <= 0) return vd_set_error(VD_ERR_ARG, "vd_tiles_merge: bad geometry");
+        return vd_set_error(VD_ERR_ARG, "%s: lists need count, xyxy_f, score, cap>0", who);
+    if (n <= 0 || fh <= 0 || fw <= 0) return vd_set_error(VD_ERR_ARG, "%s: bad geometry", who);
     TileGrid g;
     int rc = ctx->tiles_check(n, fh, fw, &g);
     if (rc) return rc;
-    if (lists->cap > ctx->face.post.kcap)
-        return vd_set_error(VD_ERR_ARG, "vd_tiles_merge: lists of cap %d (at most the net's %d anchors)", lists->cap,
-                            ctx->face.post.kcap);
+    const int kcap = plates ? ctx->plate.post.kcap : ctx->face.post.kcap;
+    if (lists->cap > kcap)
+        return vd_set_error(VD_ERR_ARG, "%s: lists of cap %d (at most the net's %d %s)", who, lists->cap, kcap,
+                            plates ? "kept boxes per input" : "anchors");
     const int rows = n * g.T;
     const bool host = lists->where == VD_HOST;
-    if (host && (rc = vd_count_check("vd_tiles_merge", lists->count, rows, lists->cap))) return rc;
+    if (host && (rc = vd_count_check(who, lists->count, rows, lists->cap))) return rc;
     BoxTargets t;
     if ((rc = ctx->box_targets(out, n, t))) return rc;
     const int* cnt = lists->count;
@@ -490,11 +506,45 @@ int vd_tiles_merge(vd_ctx* h, const vd_boxes* lists, int n, int fh, int fw, vd_b
         if (lab) VD_CHECK_HIP(hipMemcpyAsync(dl, lists->label, nb * 4, hipMemcpyHostToDevice, ctx->stream));
         cnt = dc; xf = dx; sc = ds; lab = lab ? dl : nullptr;
     }
-    if ((rc = ctx->tiles_merge(n, g, cnt, xf, sc, lab, lists->cap, t))) return rc;
+    if ((rc = ctx->tiles_merge(n, g, cnt, xf, sc, lab, lists->cap, t, plates))) return rc;
     if ((rc = ctx->box_finish(out, n, t))) return rc;
     if (host && !(out && out->where == VD_HOST))
         VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // staging reused by the next call
     return VD_OK;
+}
+
+
+extern "C" {
+
+int vd_tile_rects(int fh, int fw, int rows, int cols, int overlap_pct, int32_t* xywh, int* count) {
+    if (vd_tile_rects_host(fh, fw, rows, cols, overlap_pct, xywh, count))
+        return vd_set_error(VD_ERR_ARG, "vd_tile_rects: h, w > 0, rows, cols in [1, %d] and overlap_pct in [0, 50] "
+                            "required (got %d x %d, %d, %d, %d)", VD_TILES_MAX, fw, fh, rows, cols, overlap_pct);
+    return VD_OK;
+}
+
+int vd_tiles(vd_ctx* h, int rows, int cols, int overlap_pct) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    return ctx->tiles_set(rows, cols, overlap_pct);
+}
+
+int vd_tiles_merge(vd_ctx* h, const vd_boxes* lists, int n, int fh, int fw, vd_boxes* out) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    return tiles_merge_entry(ctx, "vd_tiles_merge", false, lists, n, fh, fw, out);
+}
+
+int vd_tiles_merge_plates(vd_ctx* h, const vd_boxes* lists, int n, int fh, int fw, vd_boxes* out) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    return tiles_merge_entry(ctx, "vd_tiles_merge_plates", true, lists, n, fh, fw, out);
+}
+
+int vd_tiles_nets(vd_ctx* h, int nets) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    return ctx->tiles_nets_set(nets);
 }
 
 }  // extern "C"

@@ -316,18 +316,31 @@ struct Ctx {
     int tiles_kn = 0;                             // frames of the last merge
     bool face_rows_merged = false;                // the last face call's lists are tiles_last's rows, not face.post's
     bool tiles_on() const { return tile_rows * tile_cols > 1; }
+    // which nets the tiling applies to (vd_tiles_nets; VD_TILE_FACES | VD_TILE_PLATES): faces alone by
+    // default, so a tiling context runs the plate net exactly as an untiled one
+    int tile_nets = VD_TILE_FACES;
+    bool faces_tiled() const { return tiles_on() && (tile_nets & VD_TILE_FACES); }
+    bool plates_tiled() const { return tiles_on() && (tile_nets & VD_TILE_PLATES); }
+    int tiles_nets_set(int nets);
+    // tiled plate detection: the plate lists' merged rows + spill scratch (allocated by the first merge)
+    void* ptiles_buf = nullptr; size_t ptiles_buf_bytes = 0;
+    TileMergeArgs ptiles_last{};                  // the last plate merge (merged-row pointers for the readers)
+    int ptiles_kn = 0;                            // frames of the last plate merge
+    bool plate_rows_merged = false;               // the last plate call's lists are ptiles_last's rows, not plate.post's
     int tiles_T() const { return 1 + tile_rows * tile_cols; }
     int tiles_set(int rows, int cols, int overlap_pct);
     int tiles_grid(int h, int w, TileGrid* g);    // the setting's rectangles of an h x w frame
     int face_letterbox_tiles(const uint8_t* dframes, int n, int h, int w, size_t pitch, const TileGrid& g);
     // the T lists of each of n frames (rows of icap, device) -> tiles_last's merged rows and the caller's targets
+    // plates: the class-aware merge at cfg.plate_iou into ptiles_last's rows (split: TileMergeArgs)
     int tiles_merge(int n, const TileGrid& g, const int* cnt, const float* xyxy_f, const float* score, const int* label,
-                    int icap, const BoxTargets& t);
+                    int icap, const BoxTargets& t, bool plates = false, bool split = false);
     int tiles_check(int n, int h, int w, TileGrid* g);   // the grid, and n * T <= max_batch
     // after face_forward(n * T): per-input post (sizes per input) + merge into the caller's targets
     int face_post_tiled(int n, int h, int w, const TileGrid& g, const BoxTargets& t);
     // the face lists a call leaves for the blur / the hold / vd_read_boxes: per-net keep lists or merged rows
-    int face_rows_cap() const { return tiles_on() ? tiles_T() * face.post.kcap : face.post.kcap; }
+    int face_rows_cap() const { return faces_tiled() ? tiles_T() * face.post.kcap : face.post.kcap; }
+    int plate_rows_cap() const { return plates_tiled() ? tiles_T() * plate.post.kcap : plate.post.kcap; }
     // JPEG frame decode (jpeg_host.cpp): pinned host staging, device copy, planes
     void* jpeg_host = nullptr; size_t jpeg_host_bytes = 0;
     void* jpeg_dev = nullptr; size_t jpeg_dev_bytes = 0;
@@ -487,7 +500,14 @@ int vd_alloc_post(Ctx& ctx, PostScratch& ps, int A, int kcap);
 void vd_post_keep_args(PostScratch& ps, PostArgs& p, int n);
 int vd_build_face(Ctx& ctx, const WMap& W);
 int vd_build_plate(Ctx& ctx, const WMap& W);
-// letterboxed: the canvas was already written (vd_launch_letterbox_pair in vd_process)
-int vd_plate_forward(Ctx& ctx, const uint8_t* dframes, int n, int h, int w, size_t pitch, bool letterboxed = false);
+// letterboxed: the canvas was already written (vd_launch_letterbox_pair in vd_process).
+// tiles: the n * (T - 1) tile inputs of the n frames instead (input f * (T - 1) + (t - 1)).
+int vd_plate_forward(Ctx& ctx, const uint8_t* dframes, int n, int h, int w, size_t pitch, bool letterboxed = false,
+                     const TileGrid* tiles = nullptr);
 int vd_plate_letterbox_args(Ctx& ctx, const uint8_t* dframes, int n, int h, int w, size_t pitch, LetterboxArgs* a);
-int vd_plate_post(Ctx& ctx, int n, int img_h, int img_w, const BoxTargets& t);
+// row0: the keep rows of the n inputs start at row row0 of plate.post (the tile inputs behind the whole frames)
+int vd_plate_post(Ctx& ctx, int n, int img_h, int img_w, const BoxTargets& t, int row0 = 0);
+// What a call that runs the plate net does: forward + post of the n frames, and with `tiles` (the
+// plate net is tiled) the tile inputs' forward + post and the merge into ptiles_last's rows.
+int vd_plate_detect(Ctx& ctx, const uint8_t* dframes, int n, int h, int w, size_t pitch, bool letterboxed,
+                    const TileGrid* tiles, const BoxTargets& t);

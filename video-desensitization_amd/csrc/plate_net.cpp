@@ -387,17 +387,22 @@ int vd_plate_letterbox_args(Ctx& c, const uint8_t* d, int n, int h, int w, size_
     return VD_OK;
 }
 
-int vd_plate_forward(Ctx& c, const uint8_t* d, int n, int h, int w, size_t pitch, bool letterboxed) {
+int vd_plate_forward(Ctx& c, const uint8_t* d, int n, int h, int w, size_t pitch, bool letterboxed,
+                     const TileGrid* tiles) {
     PlateNet& P = c.plate;
     LetterboxArgs a;
-    int rc0 = vd_plate_letterbox_args(c, d, n, h, w, pitch, &a);
+    // tiles: each of the n * (T - 1) tiles is letterboxed as a frame of its own, read in place
+    const int frames = n, ih = tiles ? tiles->th : h, iw = tiles ? tiles->tw : w;
+    if (tiles) n *= tiles->T - 1;
+    int rc0 = vd_plate_letterbox_args(c, d, n, ih, iw, pitch, &a);
     if (rc0) return rc0;
     const int oh = a.oh, ow = a.ow;
     if (!letterboxed) {
         const double obytes =
             P.s2d ? (double)(oh / 2 + 1) * (ow / 2 + 1) * (c.f32 ? 64 : 32) : (double)oh * ow * a.cpad * (c.f32 ? 4 : 2);
-        c.t_begin(2, (double)n * (a.nh * (double)w * vd_src_bpp(a.nv) + obytes));
-        hipError_t e = vd_launch_letterbox(a, c.stream);
+        c.t_begin(2, (double)n * (a.nh * (double)iw * vd_src_bpp(a.nv) + obytes));
+        hipError_t e = tiles ? vd_launch_letterbox_tile_inputs(a, *tiles, frames, h, w, c.stream)
+                             : vd_launch_letterbox(a, c.stream);
         c.t_end();
         if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "plate letterbox: %s", hipGetErrorString(e));
     }
@@ -423,8 +428,9 @@ int vd_plate_forward(Ctx& c, const uint8_t* d, int n, int h, int w, size_t pitch
     return c.run_net(*net, n);
 }
 
-int vd_plate_post(Ctx& c, int n, int img_h, int img_w, const BoxTargets& t) {
+int vd_plate_post(Ctx& c, int n, int img_h, int img_w, const BoxTargets& t, int row0) {
     PlateNet& P = c.plate;
+    c.plate_rows_merged = false;
     PostArgs p{};
     p.mode = POST_YOLO;
     for (int l = 0; l < 3; ++l) {
@@ -449,10 +455,51 @@ int vd_plate_post(Ctx& c, int n, int img_h, int img_w, const BoxTargets& t) {
     p.cap = t.cap; p.out_count = t.count; p.out_xyxy = t.xyxy; p.out_xyxy_f = t.xyxy_f;
     p.out_score = t.score; p.out_label = t.label;
     vd_post_keep_args(P.post, p, n);
+    if (row0) {   // the tile inputs' keep rows behind the whole frames' (row0 + n <= max_batch)
+        const size_t r = (size_t)row0 * p.kcap;
+        p.k_count += row0; p.k_all += row0;
+        p.k_xyxy += r * 4; p.k_xyxy_f += r * 4; p.k_score += r; p.k_label += r;
+    }
     c.t_begin(3, (double)n * P.A * P.hstride * 4);
     hipError_t e = vd_launch_post(p, c.stream);
     c.t_end();
     if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "plate post: %s", hipGetErrorString(e));
+    return VD_OK;
+}
+
+// The whole-frame lists stay in plate.post's rows [0, n) while the tile inputs' forward and post
+// run (their rows follow at n), then one merge launch reads both; everything on c.stream, so in
+// vd_process the plate branch ends with the merge before it joins.
+int vd_plate_detect(Ctx& c, const uint8_t* d, int n, int h, int w, size_t pitch, bool letterboxed,
+                    const TileGrid* tiles, const BoxTargets& t) {
+    int rc = vd_plate_forward(c, d, n, h, w, pitch, letterboxed);
+    if (rc) return rc;
+    if (!tiles) return vd_plate_post(c, n, h, w, t);
+    if ((rc = vd_plate_post(c, n, h, w, BoxTargets{}))) return rc;
+    if ((rc = vd_plate_forward(c, d, n, h, w, pitch, false, tiles))) return rc;
+    if ((rc = vd_plate_post(c, n * (tiles->T - 1), tiles->th, tiles->tw, BoxTargets{}, n))) return rc;
+    const PostScratch& ps = c.plate.post;
+    return c.tiles_merge(n, *tiles, ps.kcount, ps.kxyxy_f, ps.kscore, ps.klabel, ps.kcap, t, true, true);
+}
+
+// the raw head tensors of the last forward's n inputs -> [n][64 + nc][A] (box DFL logits, class
+// logits), anchor order level/y/x
+static int plate_heads_out(Ctx* ctx, int n, float* out, int* anchors) {
+    VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    PlateNet& P = ctx->plate;
+    if (anchors) *anchors = P.A;
+    if (!out) return VD_OK;
+    const int C = 64 + P.nc;
+    for (int l = 0; l < 3; ++l) {
+        const Act& hd = P.head[l];
+        const size_t px = (size_t)P.lh[l] * P.lw[l];
+        std::vector<float> buf((size_t)n * px * P.hstride);
+        VD_CHECK_HIP(hipMemcpy(buf.data(), hd.p, buf.size() * 4, hipMemcpyDeviceToHost));
+        for (int b = 0; b < n; ++b)
+            for (size_t q = 0; q < px; ++q)
+                for (int ch = 0; ch < C; ++ch)
+                    out[((size_t)b * C + ch) * P.A + P.loff[l] + q] = buf[((size_t)b * px + q) * P.hstride + ch];
+    }
     return VD_OK;
 }
 
@@ -468,23 +515,25 @@ extern "C" int vdt_plate_raw(vd_ctx* h, const uint8_t* frames, int n, int fh, in
     const uint8_t* d = ctx->frames_to_device(frames, n, fh, pitch, where, &rc);
     if (rc) return rc;
     if ((rc = vd_plate_forward(*ctx, d, n, fh, fw, pitch))) return rc;
-    VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    PlateNet& P = ctx->plate;
-    if (anchors) *anchors = P.A;
-    if (!out) return VD_OK;
-    // raw head tensors -> [n][64 + nc][A] (box DFL logits, class logits), anchor order level/y/x
-    const int C = 64 + P.nc;
-    for (int l = 0; l < 3; ++l) {
-        const Act& hd = P.head[l];
-        const size_t px = (size_t)P.lh[l] * P.lw[l];
-        std::vector<float> buf((size_t)n * px * P.hstride);
-        VD_CHECK_HIP(hipMemcpy(buf.data(), hd.p, buf.size() * 4, hipMemcpyDeviceToHost));
-        for (int b = 0; b < n; ++b)
-            for (size_t q = 0; q < px; ++q)
-                for (int ch = 0; ch < C; ++ch)
-                    out[((size_t)b * C + ch) * P.A + P.loff[l] + q] = buf[((size_t)b * px + q) * P.hstride + ch];
-    }
-    return VD_OK;
+    return plate_heads_out(ctx, n, out, anchors);
+}
+
+extern "C" int vdt_plate_raw_tiles(vd_ctx* h, const uint8_t* frames, int n, int fh, int fw, size_t pitch, int where,
+                                   float* out, int* anchors) {
+    Ctx* ctx = (Ctx*)h;
+    if (!ctx) return vd_set_error(VD_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return vd_set_error(VD_ERR_HIP, "hipSetDevice");
+    if (!ctx->tiles_on()) return vd_set_error(VD_ERR_STATE, "vdt_plate_raw_tiles: tiling is off (vd_tiles)");
+    if (!ctx->plate.loaded) return vd_set_error(VD_ERR_STATE, "plate weights not loaded");
+    int rc = ctx->check_frames(n, fh, fw, pitch);
+    if (rc) return rc;
+    TileGrid g;
+    if ((rc = ctx->tiles_check(n, fh, fw, &g))) return rc;
+    const uint8_t* d = ctx->frames_to_device(frames, n, fh, pitch, where, &rc);
+    if (rc) return rc;
+    if ((rc = vd_plate_forward(*ctx, d, n, fh, fw, pitch, false, &g))) return rc;
+    return plate_heads_out(ctx, n * (g.T - 1), out, anchors);
 }
 
 extern "C" int vdt_plate_postprocess(vd_ctx* h, const float* raw, int n, int fh, int fw, vd_boxes* plates) {

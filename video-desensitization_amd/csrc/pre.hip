@@ -411,12 +411,8 @@ __global__ __launch_bounds__(256) void letterbox_kernel(LetterboxArgs a) {
 // they write for a standalone frame holding those pixels. Grid axis x: the canvas's block rows
 // (space-to-depth) or rows; a workgroup walks its row 256 pixels at a time, so the source rows
 // are read along the row (staged in LDS with 16-B loads where the row start is aligned).
-__global__ __launch_bounds__(256) void letterbox_tiles_kernel(LetterboxArgs w, LetterboxArgs tl, TileGrid g) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t lrow[];
-    const int i = blockIdx.y, f = i / g.T, t = i - f * g.T;
-    const LetterboxArgs& a = t ? tl : w;
-    const FrameRgb img{w.src + ((size_t)f * w.ih + g.y0[t]) * w.pitch + (size_t)g.x0[t] * 3, w.pitch};
-    const int Y = blockIdx.x;
+// (block) row Y of canvas i from the rectangle at img, in the canvas form a asks for
+__device__ __forceinline__ void lb_rect_row(const LetterboxArgs& a, const FrameRgb& img, int i, int Y, uint8_t* lrow) {
     if (a.s2d && a.iw * 3 <= LB_LDS_MAX) {
         lb_s2d_lds_row<false>(a, img, i, Y, lrow);
     } else if (a.s2d) {
@@ -424,6 +420,25 @@ __global__ __launch_bounds__(256) void letterbox_tiles_kernel(LetterboxArgs w, L
     } else {
         for (int x = threadIdx.x; x < a.ow; x += 256) lb_nhwc_px(a, img, i, Y, x);
     }
+}
+
+__global__ __launch_bounds__(256) void letterbox_tiles_kernel(LetterboxArgs w, LetterboxArgs tl, TileGrid g) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lrow[];
+    const int i = blockIdx.y, f = i / g.T, t = i - f * g.T;
+    const LetterboxArgs& a = t ? tl : w;
+    const FrameRgb img{w.src + ((size_t)f * w.ih + g.y0[t]) * w.pitch + (size_t)g.x0[t] * 3, w.pitch};
+    lb_rect_row(a, img, i, blockIdx.x, lrow);
+}
+
+// The tile-only form (tiled plate detection: the plate letterbox's canvas size follows the
+// rectangle's aspect, so the whole frame's canvas can differ from the tiles' and is written by
+// the plain kernels): canvas i = f * (T - 1) + (t - 1) is tile t >= 1 of frame f (fh rows).
+__global__ __launch_bounds__(256) void letterbox_tile_inputs_kernel(LetterboxArgs tl, TileGrid g, int fh) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lrow[];
+    const int RC = g.T - 1;
+    const int i = blockIdx.y, f = i / RC, t = 1 + i - f * RC;
+    const FrameRgb img{tl.src + ((size_t)f * fh + g.y0[t]) * tl.pitch + (size_t)g.x0[t] * 3, tl.pitch};
+    lb_rect_row(tl, img, i, blockIdx.x, lrow);
 }
 
 // NHWC max-pool (torch semantics: padded taps ignored), vectorised 16 B per thread.
@@ -604,6 +619,27 @@ hipError_t vd_launch_letterbox_tiles(const LetterboxArgs& w0, const LetterboxArg
             if (a->iw * 3 <= LB_LDS_MAX) lds = std::max(lds, 4 * (size_t)((a->iw * 3 + 15) / 16 * 16));
     const dim3 grid(w.s2d ? w.oh / 2 + 1 : w.oh, w.n * g.T);
     hipLaunchKernelGGL(letterbox_tiles_kernel, grid, dim3(256), lds, s, w, t, g);
+    return hipGetLastError();
+}
+
+hipError_t vd_launch_letterbox_tile_inputs(const LetterboxArgs& t0, const TileGrid& g, int n, int fh, int fw,
+                                           hipStream_t s) {
+    LetterboxArgs t = t0;
+    if (t.nv.on) return hipErrorInvalidValue;   // the tile letterbox reads packed RGB
+    if (g.T < 2 || g.T > VD_TILE_INPUTS_MAX || n <= 0 || t.ih != g.th || t.iw != g.tw || t.pitch < (size_t)fw * 3)
+        return hipErrorInvalidValue;
+    for (int k = 1; k < g.T; ++k)   // every tile inside the frame
+        if (g.x0[k] < 0 || g.y0[k] < 0 || g.x0[k] + g.tw > fw || g.y0[k] + g.th > fh) return hipErrorInvalidValue;
+    lb_set_gather(t);
+    static const bool attr = [] {
+        (void)hipFuncSetAttribute((const void*)letterbox_tile_inputs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  4 * LB_LDS_MAX);
+        return true;
+    }();
+    (void)attr;
+    const size_t lds = t.s2d && t.iw * 3 <= LB_LDS_MAX ? 4 * (size_t)((t.iw * 3 + 15) / 16 * 16) : 0;
+    const dim3 grid(t.s2d ? t.oh / 2 + 1 : t.oh, n * (g.T - 1));
+    hipLaunchKernelGGL(letterbox_tile_inputs_kernel, grid, dim3(256), lds, s, t, g, fh);
     return hipGetLastError();
 }
 

@@ -215,7 +215,7 @@ int vd_detect(vd_ctx* h, const uint8_t* frames, int n, int fh, int fw, size_t pi
     if (!ctx->face.loaded) return vd_set_error(VD_ERR_STATE, "RetinaFace weights not loaded");
     int rc = ctx->check_frames(n, fh, fw, pitch);
     if (rc) return rc;
-    const bool tiled = ctx->tiles_on();
+    const bool tiled = ctx->faces_tiled();
     TileGrid g;
     if (tiled && (rc = ctx->tiles_check(n, fh, fw, &g))) return rc;
     BoxTargets t;
@@ -242,13 +242,15 @@ int vd_detect_plates(vd_ctx* h, const uint8_t* frames, int n, int fh, int fw, si
     if (!ctx->plate.loaded) return vd_set_error(VD_ERR_STATE, "plate weights not loaded");
     int rc = ctx->check_frames(n, fh, fw, pitch);
     if (rc) return rc;
+    const bool tiled = ctx->plates_tiled();   // T net inputs per frame, merged into one list (tiles.hip)
+    TileGrid g;
+    if (tiled && (rc = ctx->tiles_check(n, fh, fw, &g))) return rc;
     BoxTargets t;
     rc = ctx->box_targets(plates, n, t);
     if (rc) return rc;
     const uint8_t* d = ctx->frames_to_device(frames, n, fh, pitch, where, &rc);
     if (rc) return rc;
-    if ((rc = vd_plate_forward(*ctx, d, n, fh, fw, pitch))) return rc;
-    if ((rc = vd_plate_post(*ctx, n, fh, fw, t))) return rc;
+    if ((rc = vd_plate_detect(*ctx, d, n, fh, fw, pitch, false, tiled ? &g : nullptr, t))) return rc;
     return ctx->box_finish(plates, n, t);
 }
 
@@ -344,10 +346,12 @@ static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh
                             "in [1, 32768]");
     int rc = nv ? ctx->check_frames(n, fh, fw, (size_t)fw * 3) : ctx->check_frames(n, fh, fw, pitch);   // NV12: n alone
     if (rc) return rc;
-    // tiled detection: T net inputs per frame through the face net, merged before anything reads them
-    const bool tiled = do_faces && ctx->tiles_on();
+    // tiled detection: T net inputs per frame through the tiled nets (vd_tiles_nets), merged before
+    // anything reads them
+    const bool tiled = do_faces && ctx->faces_tiled();
+    const bool ptiled = do_plates && ctx->plates_tiled();
     TileGrid tg;
-    if (tiled && (rc = ctx->tiles_check(n, fh, fw, &tg))) return rc;
+    if ((tiled || ptiled) && (rc = ctx->tiles_check(n, fh, fw, &tg))) return rc;
     // the mosaic is out of place (combine_detect.py:142 blurs a copy; each box reads the
     // previous box's output, :247-249): its one-launch output pass gathers cell colours
     // from `in` anywhere in the frame while other workgroups write `out`, so device
@@ -424,8 +428,7 @@ static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh
     if (do_plates) {
         hipStream_t main = ctx->stream;
         if (fork) ctx->stream = plate_stream;
-        rc = vd_plate_forward(*ctx, d, n, fh, fw, pitch, paired);
-        if (!rc) rc = vd_plate_post(*ctx, n, fh, fw, tp);
+        rc = vd_plate_detect(*ctx, d, n, fh, fw, pitch, paired, ptiled ? &tg : nullptr, tp);
         ctx->stream = main;
         if (rc) return rc;
     }
@@ -440,9 +443,10 @@ static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh
     const TileMergeArgs& tm = ctx->tiles_last;   // tiling: the merged rows are the face list
     const int* c0 = do_faces ? (tiled ? tm.m_count : fp.kcount) : nullptr;
     const int* x0 = do_faces ? (tiled ? tm.m_xyxy : fp.kxyxy) : nullptr;
-    const int* c1 = mosaic_plates ? pp.kcount : nullptr;
-    const int* x1 = mosaic_plates ? pp.kxyxy : nullptr;
-    int k0 = do_faces ? (tiled ? tm.mcap : fp.kcap) : 0, k1 = mosaic_plates ? pp.kcap : 0;
+    const TileMergeArgs& pm = ctx->ptiles_last;  //   ... and the plate list, where the plate net is tiled
+    const int* c1 = mosaic_plates ? (ptiled ? pm.m_count : pp.kcount) : nullptr;
+    const int* x1 = mosaic_plates ? (ptiled ? pm.m_xyxy : pp.kxyxy) : nullptr;
+    int k0 = do_faces ? (tiled ? tm.mcap : fp.kcap) : 0, k1 = mosaic_plates ? (ptiled ? pm.mcap : pp.kcap) : 0;
     const int* dc0 = c0; const int* dx0 = x0; const int* dc1 = c1; const int* dx1 = x1;
     int dk0 = k0, dk1 = k1;                        // D as detected (rescue: E): what the lead step matches on
     // weak-detection rescue: the lists become E = D ++ R in merged rows (one step, before the hold);
@@ -559,7 +563,7 @@ int vd_process_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n, int
         if (!out) return vd_set_error(VD_ERR_ARG, "%s: MOSAIC needs an output descriptor", who);
         if ((rc = nv12_blur_check(ctx, who, in, out, n, fh, fw, where, true, ctx->nv12_cfg_pass()))) return rc;
     }
-    if ((flags & VD_PROC_FACES) && ctx->tiles_on())
+    if (((flags & VD_PROC_FACES) && ctx->faces_tiled()) || ((flags & VD_PROC_PLATES) && ctx->plates_tiled()))
         return vd_set_error(VD_ERR_STATE, "%s: tiled detection (vd_tiles) reads RGB frames only", who);
     if (ctx->lead.J && (flags & VD_PROC_MOSAIC))
         return vd_set_error(VD_ERR_STATE, "%s: MOSAIC in a look-ahead context would skip the led boxes (vd_lead has no "
@@ -670,10 +674,11 @@ int vd_read_boxes(vd_ctx* h, int net, int n, vd_boxes* out) {
     if (!ps) return vd_set_error(VD_ERR_ARG, "unknown net %d", net);
     if (!ps->kcount) return vd_set_error(VD_ERR_STATE, "net %d not loaded", net);
     if (!out || !out->count || !out->xyxy || out->cap <= 0) return vd_set_error(VD_ERR_ARG, "vd_boxes needs count, xyxy, cap>0");
-    // tiled detection: the face lists of the last call are the merged rows (tiles.hip)
-    const bool mg = net == VD_NET_RETINAFACE && ctx->face_rows_merged;
-    const TileMergeArgs& tm = ctx->tiles_last;
-    const int kn = mg ? ctx->tiles_kn : ps->kn, kcap = mg ? tm.mcap : ps->kcap;
+    // tiled detection: the lists of a tiled net's last call are the merged rows (tiles.hip)
+    const bool face = net == VD_NET_RETINAFACE;
+    const bool mg = face ? ctx->face_rows_merged : ctx->plate_rows_merged;
+    const TileMergeArgs& tm = face ? ctx->tiles_last : ctx->ptiles_last;
+    const int kn = mg ? (face ? ctx->tiles_kn : ctx->ptiles_kn) : ps->kn, kcap = mg ? tm.mcap : ps->kcap;
     const int* kcount = mg ? tm.m_count : ps->kcount;
     const int* kxyxy = mg ? tm.m_xyxy : ps->kxyxy;
     const float* kxyxy_f = mg ? tm.m_xyxy_f : ps->kxyxy_f;

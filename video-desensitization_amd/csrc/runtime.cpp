@@ -822,6 +822,7 @@ int vd_destroy(vd_ctx* h) {
     ctx->lead_free();
     if (ctx->mask_rows) hipFree(ctx->mask_rows);
     if (ctx->tiles_buf) hipFree(ctx->tiles_buf);
+    if (ctx->ptiles_buf) hipFree(ctx->ptiles_buf);
     if (ctx->tiles_in) hipFree(ctx->tiles_in);
     for (int* p : ctx->hold_hist)
         if (p) hipFree(p);

@@ -18,6 +18,12 @@
 // sorted and swept in LDS, more in the per-frame global scratch (as nms_kernel does). The
 // merged rows hold T * icap boxes, so nothing is ever dropped. Caller lists are read and
 // written with scalar accesses (no alignment assumed).
+//
+// Tiled plate detection (include/vdmi.h at vd_tiles_nets) merges with the same kernel in its
+// PLATE form: the input's label is the box's class, a kept box suppresses boxes of its own class
+// only (no class offset: vd_nms.h CLS sweep on the mapped boxes, cfg.plate_iou), and the emitted
+// label is the class. With p.split the lists come from two forwards: frame f's whole-frame list
+// at row f, its tile t at row n + f * (T - 1) + (t - 1).
 #include "vd_common.h"
 #include "vd_math.h"
 #include "vd_nms.h"
@@ -50,21 +56,28 @@ int vd_tile_rects_host(int h, int w, int rows, int cols, int overlap_pct, int32_
 
 namespace {
 
+template <bool PLATE>
 __global__ __launch_bounds__(VD_NMS_THREADS) void tiles_merge_kernel(TileMergeArgs p) {
     __shared__ __attribute__((aligned(16))) float4 l_box[VD_NMS_LDS_CAND];
     __shared__ __attribute__((aligned(16))) uint64_t l_keys[VD_NMS_LDS_CAND];
     __shared__ float l_area[VD_NMS_LDS_CAND];
+    __shared__ int l_cls[PLATE ? VD_NMS_LDS_CAND : 1];
     __shared__ uint8_t l_supp[VD_NMS_LDS_CAND];
     __shared__ uint64_t s_chunk_keep;
     __shared__ int s_nkept;
     __shared__ int s_off[VD_TILE_INPUTS_MAX + 1];
     const int tid = threadIdx.x;
     const int f = blockIdx.x, T = p.g.T;
+    // the row of frame f's input t in the input lists
+    auto row = [&](int t) -> size_t {
+        if (PLATE && p.split) return t ? (size_t)p.n + (size_t)f * (T - 1) + (t - 1) : (size_t)f;
+        return (size_t)f * T + t;
+    };
     if (tid == 0) {
         int o = 0;
         for (int t = 0; t < T; ++t) {
             s_off[t] = o;
-            o += min(max(p.cnt[(size_t)f * T + t], 0), p.icap);
+            o += min(max(p.cnt[row(t)], 0), p.icap);
         }
         s_off[T] = o;
     }
@@ -82,11 +95,12 @@ __global__ __launch_bounds__(VD_NMS_THREADS) void tiles_merge_kernel(TileMergeAr
     float4* box = lds ? l_box : p.s_box + (size_t)f * p.mcap;
     float* area = lds ? l_area : p.s_area + (size_t)f * p.mcap;
     uint8_t* supp = lds ? l_supp : p.s_supp + (size_t)f * p.mcap;
+    int* cls = PLATE ? (lds ? l_cls : p.s_cls + (size_t)f * p.mcap) : nullptr;
     int P = 1;
     while (P < M) P <<= 1;
     for (int t = 0; t < T; ++t) {
         const int o = s_off[t], c = s_off[t + 1] - o;
-        const float* sc = p.score + ((size_t)f * T + t) * p.icap;
+        const float* sc = p.score + row(t) * p.icap;
         for (int i = tid; i < c; i += VD_NMS_THREADS)
             keys[o + i] = ((uint64_t)(0xFFFFFFFFu - __float_as_uint(sc[i])) << 32) | (uint32_t)(t * p.icap + i);
     }
@@ -96,7 +110,7 @@ __global__ __launch_bounds__(VD_NMS_THREADS) void tiles_merge_kernel(TileMergeAr
     for (int i = tid; i < M; i += VD_NMS_THREADS) {
         const int idx = (int)(keys[i] & 0xFFFFFFFFu);
         const int t = idx / p.icap, pos = idx - t * p.icap;
-        const float* q = p.xyxy_f + (((size_t)f * T + t) * p.icap + pos) * 4;
+        const float* q = p.xyxy_f + (row(t) * p.icap + pos) * 4;
         float4 bx = make_float4(q[0], q[1], q[2], q[3]);
         if (t) {                                           // one float32 add per coordinate, no FMA
             const float ox = (float)p.g.x0[t], oy = (float)p.g.y0[t];
@@ -105,16 +119,17 @@ __global__ __launch_bounds__(VD_NMS_THREADS) void tiles_merge_kernel(TileMergeAr
         box[i] = bx;
         area[i] = VD_FMUL(VD_FSUB(bx.z, bx.x), VD_FSUB(bx.w, bx.y));
         supp[i] = 0;
+        if constexpr (PLATE) cls[i] = p.label ? p.label[row(t) * p.icap + pos] : 0;
     }
     if (tid == 0) s_nkept = 0;
     __syncthreads();
 
-    vd_nms_greedy(M, box, area, supp, &s_chunk_keep, &s_nkept, p.iou, p.mcap, [&](int pos, int j, const float4& b) {
+    vd_nms_greedy_cls<PLATE>(M, box, area, supp, &s_chunk_keep, &s_nkept, p.iou, p.mcap, [&](int pos, int j, const float4& b) {
         const uint64_t key = keys[j];
         const int idx = (int)(key & 0xFFFFFFFFu);
         const int t = idx / p.icap, ipos = idx - t * p.icap;
         const float sc = __uint_as_float(0xFFFFFFFFu - (uint32_t)(key >> 32));
-        const int lab = t * p.A + (p.label ? p.label[((size_t)f * T + t) * p.icap + ipos] : 0);
+        const int lab = PLATE ? cls[j] : t * p.A + (p.label ? p.label[row(t) * p.icap + ipos] : 0);
         const int4 ib = make_int4(vd_trunc_i32(b.x), vd_trunc_i32(b.y), vd_trunc_i32(b.z), vd_trunc_i32(b.w));
         const size_t k = (size_t)f * p.mcap + pos;
         ((int4*)p.m_xyxy)[k] = ib;
@@ -131,7 +146,7 @@ __global__ __launch_bounds__(VD_NMS_THREADS) void tiles_merge_kernel(TileMergeAr
         }
         if (p.out_score) p.out_score[o] = sc;
         if (p.out_label) p.out_label[o] = lab;
-    });
+    }, cls);
     if (tid == 0) {
         p.m_count[f] = s_nkept;
         if (p.out_count) p.out_count[f] = s_nkept;
@@ -144,6 +159,8 @@ hipError_t vd_launch_tiles_merge(const TileMergeArgs& a, hipStream_t s) {
     if (a.n <= 0 || a.g.T < 2 || a.g.T > VD_TILE_INPUTS_MAX || a.icap <= 0 || (long long)a.g.T * a.icap > a.mcap ||
         a.sort_cap < a.mcap || (a.sort_cap & (a.sort_cap - 1)) || (long long)a.g.T * a.icap > 0x7fffffffLL)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(tiles_merge_kernel, dim3(a.n), dim3(VD_NMS_THREADS), 0, s, a);
+    if (a.plate && !a.s_cls) return hipErrorInvalidValue;
+    if (a.plate) hipLaunchKernelGGL(tiles_merge_kernel<true>, dim3(a.n), dim3(VD_NMS_THREADS), 0, s, a);
+    else hipLaunchKernelGGL(tiles_merge_kernel<false>, dim3(a.n), dim3(VD_NMS_THREADS), 0, s, a);
     return hipGetLastError();
 }

@@ -80,7 +80,7 @@ int Ctx::launch_hold(int n, int h, int w, const int* cnt0, const int* xy0, int c
         return vd_set_error(VD_ERR_ARG, "hold motion: frames of at most 32768 x 32768 (got %d x %d)", h, w);
     // rows sized for the loaded detectors' complete keep lists (vd_process never regrows them)
     // and for this call's lists; (K + 1) rows of that size hold D and K complete older lists
-    const int nets = (face.loaded ? face_rows_cap() : 0) + (plate.loaded ? plate.post.kcap : 0);
+    const int nets = (face.loaded ? face_rows_cap() : 0) + (plate.loaded ? plate_rows_cap() : 0);
     const int need = std::max(std::max((cnt0 ? cap0 : 0) + (cnt1 ? cap1 : 0), nets), 1);
     int rc = hold_history(need);
     if (rc) return rc;
@@ -120,7 +120,7 @@ int Ctx::hold_read(int n, int held_only, vd_boxes* out) {
 // The D-list capacity of a ring slot: the loaded detectors' complete keep lists, this call's
 // lists, and whatever the hold history already carries (its rows are copied into the ring).
 int Ctx::lead_need(int cap0, int cap1) const {
-    const int nets = (face.loaded ? face_rows_cap() : 0) + (plate.loaded ? plate.post.kcap : 0);
+    const int nets = (face.loaded ? face_rows_cap() : 0) + (plate.loaded ? plate_rows_cap() : 0);
     return std::max(std::max(std::max(cap0 + cap1, nets), hold.K ? hold_hcap : 0), 1);
 }
 

@@ -591,6 +591,11 @@ int vd_tile_rects_host(int h, int w, int rows, int cols, int overlap_pct, int32_
 // `whole`; both of one canvas form).
 hipError_t vd_launch_letterbox_tiles(const LetterboxArgs& whole, const LetterboxArgs& tile, const TileGrid& g,
                                      hipStream_t s);
+// The tile canvases alone (tiled plate detection: the whole-frame canvas can differ in size, so it
+// is written by vd_launch_letterbox): canvas f * (T - 1) + (t - 1) is frame f's tile t, n frames of
+// fh x fw pixels at tile.src / tile.pitch; `tile`: the geometry of a tile as a frame of its own.
+hipError_t vd_launch_letterbox_tile_inputs(const LetterboxArgs& tile, const TileGrid& g, int n, int fh, int fw,
+                                           hipStream_t s);
 // Cross-tile merge (tiles.hip): per frame, the T keep lists -> one list in merged rows.
 struct TileMergeArgs {
     int n; TileGrid g;
@@ -604,6 +609,12 @@ struct TileMergeArgs {
     int* m_count; int* m_xyxy; float* m_xyxy_f; float* m_score; int* m_label;   // merged rows [n][mcap]
     int cap;                                         // caller's capacity per frame (out_* may all be NULL)
     int* out_count; int* out_xyxy; float* out_xyxy_f; float* out_score; int* out_label;
+    // tiled plate detection (include/vdmi.h at vd_tiles_nets): the class-aware form. label_in is the
+    // box's class, a kept box suppresses boxes of its own class only, label = the class (A unused)
+    int plate;
+    int split;                                       // plate: frame f's input 0 at row f, input t > 0 at row
+                                                     //   n + f * (T - 1) + (t - 1) (two forwards); 0: row f * T + t
+    int* s_cls;                                      // plate: spill scratch [n][mcap]
 };
 hipError_t vd_launch_tiles_merge(const TileMergeArgs& a, hipStream_t s);
 

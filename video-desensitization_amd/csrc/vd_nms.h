@@ -32,10 +32,12 @@ __device__ __forceinline__ void vd_nms_sort(uint64_t* keys, int P) {
 // readlane sweep, then all 16 waves suppress later candidates against the chunk's kept boxes --
 // exactly the sequential greedy keep list. Kept candidate j gets emit_fn(pos, j, box[j]) from
 // its lane of wave 0 while pos < limit; *nkept_s ends as the complete keep count.
-template <typename Emit>
-__device__ __forceinline__ void vd_nms_greedy(int M, const float4* box, const float* area, uint8_t* supp,
-                                              uint64_t* chunk_keep, int* nkept_s, double iou, int limit,
-                                              Emit emit_fn) {
+// CLS (the plate tile merge): cls[0, M) holds each box's class, and a kept box suppresses boxes
+// of its own class only; without it cls is never read and the sweep is the one above.
+template <bool CLS, typename Emit>
+__device__ __forceinline__ void vd_nms_greedy_cls(int M, const float4* box, const float* area, uint8_t* supp,
+                                                  uint64_t* chunk_keep, int* nkept_s, double iou, int limit,
+                                                  Emit emit_fn, const int* cls) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     for (int c0 = 0; c0 < M; c0 += 64) {
         if (wid == 0) {
@@ -44,9 +46,14 @@ __device__ __forceinline__ void vd_nms_greedy(int M, const float4* box, const fl
             const float4 bj = valid ? box[j] : make_float4(0, 0, 0, 0);
             const float aj = valid ? area[j] : 0.f;
             const bool alive = valid && !supp[j];
+            int cj = 0;
+            if constexpr (CLS) cj = valid ? cls[j] : 0;
             uint64_t mask = 0;
             const int lim = min(64, M - c0);
             for (int k = lane + 1; k < lim; ++k) {
+                if constexpr (CLS) {
+                    if (cls[c0 + k] != cj) continue;
+                }
                 const float4 bk = box[c0 + k];
                 if (vd_iou_gt(bj.x, bj.y, bj.z, bj.w, aj, bk.x, bk.y, bk.z, bk.w, area[c0 + k], iou))
                     mask |= 1ULL << k;
@@ -77,10 +84,15 @@ __device__ __forceinline__ void vd_nms_greedy(int M, const float4* box, const fl
                 if (supp[j]) continue;
                 const float4 bj = box[j];
                 const float aj = area[j];
+                int cj = 0;
+                if constexpr (CLS) cj = cls[j];
                 uint64_t bits = kb;
                 while (bits) {
                     const int i = __ffsll((long long)bits) - 1;
                     bits &= bits - 1;
+                    if constexpr (CLS) {
+                        if (cls[c0 + i] != cj) continue;
+                    }
                     const float4 bi = box[c0 + i];
                     if (vd_iou_gt(bi.x, bi.y, bi.z, bi.w, area[c0 + i], bj.x, bj.y, bj.z, bj.w, aj, iou)) {
                         supp[j] = 1;
@@ -91,6 +103,13 @@ __device__ __forceinline__ void vd_nms_greedy(int M, const float4* box, const fl
         }
         __syncthreads();
     }
+}
+
+template <typename Emit>
+__device__ __forceinline__ void vd_nms_greedy(int M, const float4* box, const float* area, uint8_t* supp,
+                                              uint64_t* chunk_keep, int* nkept_s, double iou, int limit,
+                                              Emit emit_fn) {
+    vd_nms_greedy_cls<false>(M, box, area, supp, chunk_keep, nkept_s, iou, limit, emit_fn, nullptr);
 }
 
 // int(x) of a Python float; values beyond int32 are clamped (the mosaic clips to the frame

@@ -28,6 +28,8 @@ VD_RESCUE_SPAN_MAX = 255
 VD_MASK_RECT, VD_MASK_ELLIPSE = 0, 1
 VD_MASK_GROW_MAX = 200
 VD_TILES_MAX = 4
+VD_TILE_FACES, VD_TILE_PLATES = 1, 2
+TILE_NETS = {"faces": VD_TILE_FACES, "plates": VD_TILE_PLATES, "both": VD_TILE_FACES | VD_TILE_PLATES}
 VD_CELLS_MIN, VD_CELLS_MAX = 2, 64
 MASK_SHAPES = {"rect": VD_MASK_RECT, "ellipse": VD_MASK_ELLIPSE}
 VD_NV12_BT601, VD_NV12_BT709 = 0, 1
@@ -123,6 +125,8 @@ SIGNATURES = [
     ("vd_tile_rects", _I, [_I, _I, _I, _I, _I, _P, ctypes.POINTER(_I)]),
     ("vd_tiles", _I, [_P, _I, _I, _I]),
     ("vd_tiles_merge", _I, [_P, ctypes.POINTER(vd_boxes), _I, _I, _I, ctypes.POINTER(vd_boxes)]),
+    ("vd_tiles_nets", _I, [_P, _I]),
+    ("vd_tiles_merge_plates", _I, [_P, ctypes.POINTER(vd_boxes), _I, _I, _I, ctypes.POINTER(vd_boxes)]),
     ("vd_jpeg_decode", _I, [_P, ctypes.POINTER(_P), ctypes.POINTER(_SZ), _I, _P, _I, _I, _SZ, _I]),
     ("vd_jpeg_info", _I, [_P, _SZ, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     ("vd_jpeg_encode", _I, [_P, _P, _I, _I, _I, _SZ, _I, _I, _I, _P, _SZ, ctypes.POINTER(_SZ)]),
@@ -146,6 +150,7 @@ SIGNATURES = [
                         ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     ("vdt_bottleneck", _I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     ("vdt_plate_raw", _I, [_P, _P, _I, _I, _I, _SZ, _I, _P, ctypes.POINTER(_I)]),
+    ("vdt_plate_raw_tiles", _I, [_P, _P, _I, _I, _I, _SZ, _I, _P, ctypes.POINTER(_I)]),
     ("vdt_plate_postprocess", _I, [_P, _P, _I, _I, _I, ctypes.POINTER(vd_boxes)]),
     ("vdt_jpeg_coefficients", _I, [_P, _SZ, _P, _SZ, ctypes.POINTER(_I)]),
     ("vdt_jdec_stats", _I, [_P, ctypes.POINTER(_I)]),
@@ -282,6 +287,14 @@ def check_tiles(tiles, tile_overlap):
     if not 0 <= ov <= 50:
         raise ValueError(f"tile_overlap {ov}: expected 0 .. 50 percent")
     return (rows, cols), ov
+
+
+def check_tile_nets(tile_nets):
+    """tile_nets as its name ("faces" | "plates" | "both": which nets a tiling applies to,
+    vd_tiles_nets); ValueError for anything else."""
+    if not isinstance(tile_nets, str) or tile_nets not in TILE_NETS:
+        raise ValueError(f"tile_nets {tile_nets!r}: expected 'faces', 'plates' or 'both'")
+    return tile_nets
 
 
 def tile_rects(h, w, tiles, tile_overlap=20):

@@ -185,7 +185,7 @@ class Context:
                  plate_max_det=300, plate_imgsz=640, microbatch=0, microbatch_stage=2, options=None,
                  blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30,
                  hold_motion=False, mask="rect", mask_grow=0, tiles=(1, 1), tile_overlap=20, cells=0,
-                 lead=0, lead_motion=False, rescue=0.0, plate_rescue=0.0, rescue_span=60):
+                 lead=0, lead_motion=False, rescue=0.0, plate_rescue=0.0, rescue_span=60, tile_nets="faces"):
         """blur: what process() applies to the kept boxes: "pixelate" (the reference's
         INTER_NEAREST mosaic, the default) or "gaussian" (GaussianBlur(region, (blur_ksize,
         blur_ksize), blur_sigma) per clipped box, in list order; blur_ksize odd in [3, 127],
@@ -213,6 +213,12 @@ class Context:
         inputs per frame: a call carries max_batch // T frames, and detect() / process() split a
         longer batch. (1, 1) (the default) is off. Kept as self.tiles / self.tile_overlap;
         set_tiles() changes them.
+        tile_nets: which nets the tiling applies to (include/vdmi.h at vd_tiles_nets): "faces" (the
+        default: the plate net sees the whole frame only, as in an untiled context), "plates" (the
+        plate net alone: small plates in high-resolution frames, at a fraction of the face net's
+        cost) or "both". A tiled plate net gives T lists per frame, merged per class at plate_iou;
+        the calls that run it carry max_batch // T frames and split a longer batch. No effect
+        while tiles == (1, 1). Kept as self.tile_nets; set_tile_nets() changes it.
         cells: box-scaled strength (include/vdmi.h at vd_cells): with cells = N in 2..64 every box
         is hidden with at most N cells along its longer side instead of a constant number of
         pixels -- pixelation picks its level per box (never below mosaic_level), and a
@@ -241,6 +247,7 @@ class Context:
         hold, hold_iou_pct = _lib.check_hold(hold, hold_iou_pct, hold_motion)   # before the library is touched
         mask, mask_grow = _lib.check_mask(mask, mask_grow)
         tiles, tile_overlap = _lib.check_tiles(tiles, tile_overlap)
+        tile_nets = _lib.check_tile_nets(tile_nets)
         cells = _lib.check_cells(cells)
         lead, lead_motion = _lib.check_lead(lead, lead_motion)
         rescue, plate_rescue, rescue_span = _lib.check_rescue(rescue, plate_rescue, rescue_span)
@@ -287,6 +294,9 @@ class Context:
         self.tiles, self.tile_overlap = (1, 1), tile_overlap
         if tiles != (1, 1):
             self.set_tiles(tiles, tile_overlap)
+        self.tile_nets = "faces"
+        if tile_nets != "faces":
+            self.set_tile_nets(tile_nets)
         self.cells = 0
         if cells:
             self.set_cells(cells)
@@ -370,8 +380,8 @@ class Context:
 
     def detect(self, frames, boxes=None):
         p, n, h, w, pitch, where, keep = _frames_arg(frames)
-        step = self.frames_per_call()
-        if n > step and self.tiles != (1, 1):          # tiling: max_batch // T frames per call
+        step = self.frames_per_call(faces=True, plates=False)
+        if n > step and step < self.cfg.max_batch:     # tiling: max_batch // T frames per call
             parts = [self.detect(keep[s0:s0 + step], _rows(boxes, s0, min(step, n - s0)))
                      for s0 in range(0, n, step)]
             return boxes if boxes is not None else _host_concat(parts)
@@ -381,13 +391,25 @@ class Context:
         check(self._lib.vd_detect(self._h, p, n, h, w, pitch, where, ctypes.byref(s)))
         return self._complete(boxes, _lib.VD_NET_RETINAFACE, auto)
 
-    def frames_per_call(self):
-        """Frames one detect() / process() call carries: max_batch, or max_batch // T under tiling."""
+    def frames_per_call(self, faces=True, plates=True):
+        """Frames one call carries: max_batch, or max_batch // T when it runs a tiled net. faces /
+        plates: the nets the call runs (by default both: the bound that holds for every call)."""
         r, c = self.tiles
-        return self.cfg.max_batch if r * c == 1 else max(1, self.cfg.max_batch // (1 + r * c))
+        nets = _lib.TILE_NETS[self.tile_nets]
+        tiled = r * c > 1 and ((faces and nets & _lib.VD_TILE_FACES) or (plates and nets & _lib.VD_TILE_PLATES))
+        return max(1, self.cfg.max_batch // (1 + r * c)) if tiled else self.cfg.max_batch
+
+    def _step(self, flags):
+        """frames_per_call() of a process() / process_lead() call with these flags."""
+        return self.frames_per_call(bool(flags & _lib.VD_PROC_FACES), bool(flags & _lib.VD_PROC_PLATES))
 
     def detect_plates(self, frames, boxes=None):
         p, n, h, w, pitch, where, keep = _frames_arg(frames)
+        step = self.frames_per_call(faces=False, plates=True)
+        if n > step and step < self.cfg.max_batch:     # plates tiled: max_batch // T frames per call
+            parts = [self.detect_plates(keep[s0:s0 + step], _rows(boxes, s0, min(step, n - s0)))
+                     for s0 in range(0, n, step)]
+            return boxes if boxes is not None else _host_concat(parts)
         auto = boxes is None
         boxes = self._boxes(boxes, n)
         s = boxes.struct()
@@ -469,8 +491,8 @@ class Context:
             else:
                 import torch
                 out = torch.empty_like(frames)
-        step = self.frames_per_call()
-        if n > step and self.tiles != (1, 1) and flags & _lib.VD_PROC_FACES:   # tiling: consecutive calls (exact under hold:
+        step = self._step(flags)
+        if n > step and step < self.cfg.max_batch:     # a tiled net: consecutive calls (exact under hold:
             pf, pp = [], []                            # the history carries across calls)
             for s0 in range(0, n, step):
                 k = min(step, n - s0)
@@ -787,8 +809,8 @@ class Context:
                 out = torch.empty((room, h, w, 3), dtype=torch.uint8, device=frames.device)
         if len(out) and tuple(out.shape[1:]) != (h, w, 3):
             raise ValueError(f"out must be uint8 [m,{h},{w},3]")
-        step = self.frames_per_call()
-        if n > step and self.tiles != (1, 1) and flags & _lib.VD_PROC_FACES:
+        step = self._step(flags)
+        if n > step and step < self.cfg.max_batch:
             pf, pp, m = [], [], 0
             for s0 in range(0, n, step):
                 k = min(step, n - s0)
@@ -886,6 +908,13 @@ class Context:
         check(self._lib.vd_tiles(self._h, tiles[0], tiles[1], tile_overlap))
         self.tiles, self.tile_overlap = tiles, tile_overlap
 
+    def set_tile_nets(self, tile_nets="faces"):
+        """vd_tiles_nets: which nets the tiling applies to from the next call on: "faces" (the
+        default), "plates" or "both". A change while tiling is on forgets the hold history."""
+        tile_nets = _lib.check_tile_nets(tile_nets)
+        check(self._lib.vd_tiles_nets(self._h, _lib.TILE_NETS[tile_nets]))
+        self.tile_nets = tile_nets
+
     def tile_rects(self, h, w):
         """The net inputs' rectangles (x, y, w, h) of an h x w frame under the context's tiling
         (vd_tile_rects): int32 [T][4], row 0 the whole frame."""
@@ -905,6 +934,20 @@ class Context:
             return out
         check(self._lib.vd_tiles_merge(self._h, ctypes.byref(ls), n, int(h), int(w), None))
         return self.read_boxes(_lib.VD_NET_RETINAFACE, n)
+
+    def tiles_merge_plates(self, lists, h, w, out=None):
+        """vd_tiles_merge_plates: the plate merge alone, the counterpart of tiles_merge(): the same
+        layout of `lists`, label read as the class. Returns `out` (default: HostBoxes with the
+        complete merged lists): the mapped boxes in merged order, label = the class."""
+        T = 1 + self.tiles[0] * self.tiles[1]
+        n = lists.n // T
+        ls = lists.struct()
+        if out is not None:
+            s = out.struct()
+            check(self._lib.vd_tiles_merge_plates(self._h, ctypes.byref(ls), n, int(h), int(w), ctypes.byref(s)))
+            return out
+        check(self._lib.vd_tiles_merge_plates(self._h, ctypes.byref(ls), n, int(h), int(w), None))
+        return self.read_boxes(_lib.VD_NET_YOLOV8N, n)
 
     def letterbox_tiles(self, frames, cpad=4):
         """vdt_letterbox_tiles: letterbox() for the n * T canvases of a tiling context, canvas
@@ -1032,6 +1075,17 @@ class Context:
         check(self._lib.vdt_plate_raw(self._h, p, n, h, w, pitch, where, None, ctypes.byref(A)))
         out = np.zeros((n, 64 + self.cfg.plate_nc, A.value), np.float32)
         check(self._lib.vdt_plate_raw(self._h, p, n, h, w, pitch, where, ptr(out), ctypes.byref(A)))
+        return out
+
+    def plate_raw_tiles(self, frames):
+        """vdt_plate_raw_tiles: plate_raw() of the n * R * C tile inputs of a tiling context, input
+        f * R * C + (t - 1); a torch view with padded rows is read at its own row pitch."""
+        p, n, h, w, pitch, where, keep = _frames_arg(frames, pitched=True)
+        ni = n * self.tiles[0] * self.tiles[1]
+        A = ctypes.c_int()
+        check(self._lib.vdt_plate_raw_tiles(self._h, p, n, h, w, pitch, where, None, ctypes.byref(A)))
+        out = np.zeros((ni, 64 + self.cfg.plate_nc, A.value), np.float32)
+        check(self._lib.vdt_plate_raw_tiles(self._h, p, n, h, w, pitch, where, ptr(out), ctypes.byref(A)))
         return out
 
     def plate_postprocess(self, raw, img_hw, cap=None):

@@ -25,7 +25,8 @@ Differences, all deliberate:
   ``blur`` / ``blur_ksize`` / ``blur_sigma`` (Context's: "gaussian" makes the fused
   ``batch_process_images`` path blur the boxes instead of pixelating them), ``tiles`` /
   ``tile_overlap`` (Context's tiled detection: the frame plus R x C overlapping crops at
-  their native scale, merged by one more NMS, for faces too small for the letterboxed frame).
+  their native scale, merged by one more NMS, for faces too small for the letterboxed frame),
+  ``tile_nets`` ("faces" | "plates" | "both": which nets of a fused context the tiling applies to).
 * Devices (face.py:55-56 wraps the net in ``nn.DataParallel``: every forward is
   split over ALL visible GPUs, the weights re-broadcast each time): one context per
   device, weights uploaded once each; ``detect_images`` cuts the image list into
@@ -107,6 +108,8 @@ class Retinaface(object):
         # tiled face detection for small faces in large frames: Context(tiles=(R, C), tile_overlap=...)
         "tiles": (1, 1),
         "tile_overlap": 20,
+        # which nets the tiling applies to in the fused vd_process: Context(tile_nets=...)
+        "tile_nets": "faces",
         # box-scaled strength of what the fused vd_process blurs: Context(cells=...)
         "cells": 0,
         # look-ahead hold in the fused vd_process_lead: Context(lead=..., lead_motion=...)
@@ -130,6 +133,7 @@ class Retinaface(object):
             raise ValueError(f"backbone must be 'resnet50' or 'mobilenet', got {self.backbone!r}")
         _lib.check_mask(self.mask, self.mask_grow)          # before a device or the library is touched
         self.tiles, self.tile_overlap = _lib.check_tiles(self.tiles, self.tile_overlap)
+        self.tile_nets = _lib.check_tile_nets(self.tile_nets)
         self.cells = _lib.check_cells(self.cells)
         self.lead, self.lead_motion = _lib.check_lead(self.lead, self.lead_motion)
         self.rescue, _, self.rescue_span = _lib.check_rescue(self.rescue, 0.0, self.rescue_span)
@@ -152,7 +156,8 @@ class Retinaface(object):
                              hold_iou_pct=self.hold_iou_pct, hold_motion=self.hold_motion,
                              mask=self.mask, mask_grow=self.mask_grow, tiles=self.tiles,
                              tile_overlap=self.tile_overlap, cells=self.cells, lead=self.lead,
-                             lead_motion=self.lead_motion, rescue=self.rescue, rescue_span=self.rescue_span)
+                             lead_motion=self.lead_motion, rescue=self.rescue, rescue_span=self.rescue_span,
+                             tile_nets=self.tile_nets)
                      for d in self.device_ids]
         self.ctx = self.ctxs[0]
         self.generate()

@@ -525,11 +525,12 @@ def fused_context(face_detector, plate_detector, batch_size, device=None, slot=0
     dev = fd.device_ids[0] if device is None else int(device)
     # the face detector's mask setting can change after it was built (Context.set_mask): a
     # cached context with another mask is never reused
-    # ... and so can its tiling (Context.set_tiles)
+    # ... and so can its tiling (Context.set_tiles, Context.set_tile_nets)
     # ... and its cells setting (Context.set_cells)
     key = (id(plate_detector), int(batch_size), dev, int(slot), fd.ctx.mask, fd.ctx.mask_grow, fd.ctx.tiles,
            fd.ctx.tile_overlap, fd.ctx.cells, fd.ctx.lead, fd.ctx.lead_motion, fd.ctx.rescue_low,
-           pd.ctx.plate_rescue_low, fd.ctx.rescue_span)   # ... and the rescue setting (Context.rescue)
+           pd.ctx.plate_rescue_low, fd.ctx.rescue_span,   # ... and the rescue setting (Context.rescue)
+           fd.ctx.tile_nets)
     with _FUSED_LOCK:
         cache = fd.__dict__.setdefault("_fused_ctx", {})
         if key in cache:
@@ -554,7 +555,7 @@ def _new_fused_context(fd, pd, batch_size, dev):
                   hold_motion=fd.ctx.hold_motion, mask=fd.ctx.mask, mask_grow=fd.ctx.mask_grow,
                   tiles=fd.ctx.tiles, tile_overlap=fd.ctx.tile_overlap, cells=fd.ctx.cells,
                   lead=fd.ctx.lead, lead_motion=fd.ctx.lead_motion, rescue=fd.ctx.rescue_low,
-                  plate_rescue=pd.ctx.plate_rescue_low, rescue_span=fd.ctx.rescue_span)
+                  plate_rescue=pd.ctx.plate_rescue_low, rescue_span=fd.ctx.rescue_span, tile_nets=fd.ctx.tile_nets)
     ctx.load_weights(_lib.VD_NET_RETINAFACE, fd.state_dict)
     ctx.load_weights(_lib.VD_NET_YOLOV8N, pd.state_dict)
     return ctx
@@ -608,9 +609,10 @@ def _cells_matches(ctx, cells):
     return ctx.cells == cells
 
 
-def _tiles_matches(ctx, tiles, tile_overlap):
-    """The context detects faces with exactly this tiling (off: any overlap)."""
-    return ctx.tiles == tiles and (tiles == (1, 1) or ctx.tile_overlap == tile_overlap)
+def _tiles_matches(ctx, tiles, tile_overlap, tile_nets="faces"):
+    """The context detects with exactly this tiling (off: any overlap, any nets)."""
+    return ctx.tiles == tiles and (tiles == (1, 1) or (ctx.tile_overlap == tile_overlap
+                                                       and getattr(ctx, "tile_nets", "faces") == tile_nets))
 
 
 def _is_vdmi_pair(face_detector, plate_detector):
@@ -650,7 +652,7 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
                          gpu_codec="auto", jpeg_quality=95, shard="auto", group=None, records=None,
                          blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30,
                          hold_motion=False, mask="rect", mask_grow=0, tiles=(1, 1), tile_overlap=20, cells=0,
-                         lead=0, lead_motion=False, rescue=0.0, plate_rescue=0.0, rescue_span=60):
+                         lead=0, lead_motion=False, rescue=0.0, plate_rescue=0.0, rescue_span=60, tile_nets="faces"):
     """combine_detect.py:183-277. Returns (total_processed, total_faces, total_plates).
 
     gpu_codec ("auto" | True | False): with vdmi detectors, no custom loader/saver and
@@ -698,8 +700,14 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     the face net whole and as rows x cols overlapping crops at their native scale, merged by one
     more NMS, so faces too small for the letterboxed frame are found. It is a property of the
     detector: the face detector must be the vdmi Retinaface built with the same setting
-    (Retinaface(tiles=..., tile_overlap=...)), else ValueError. Plates are detected on the whole
-    frame. (1, 1) (the default) changes nothing.
+    (Retinaface(tiles=..., tile_overlap=...)), else ValueError. (1, 1) (the default) changes
+    nothing.
+    tile_nets ("faces" | "plates" | "both"): which nets the tiling applies to (include/vdmi.h at
+    vd_tiles_nets, Context(tile_nets=...)). "faces" (the default): plates are detected on the whole
+    frame. "plates" / "both": the plate net also sees the rows x cols crops and its lists are merged
+    per class, so plates too small for the letterboxed frame are found; "plates" leaves the face
+    net untiled, at a fraction of the cost. Like tiles it must match the face detector's setting
+    (Retinaface(tile_nets=...)), else ValueError; it has no effect while tiles == (1, 1).
 
     rescue / plate_rescue / rescue_span: weak-detection rescue (include/vdmi.h at vd_rescue,
     Context(rescue=...)): the directory is one video, processed in sorted order as under hold, and a
@@ -754,6 +762,7 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     hold, hold_iou_pct = _lib.check_hold(hold, hold_iou_pct, hold_motion)
     mask, mask_grow = _lib.check_mask(mask, mask_grow)
     tiles, tile_overlap = _lib.check_tiles(tiles, tile_overlap)
+    tile_nets = _lib.check_tile_nets(tile_nets)
     cells = _lib.check_cells(cells)
     lead, lead_motion = _lib.check_lead(lead, lead_motion)
     rescue, plate_rescue, rescue_span = _lib.check_rescue(rescue, plate_rescue, rescue_span)
@@ -761,9 +770,9 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     if lead and gpu_codec is True:
         raise ValueError("lead > 0: the GPU JPEG codec path is out of scope (use gpu_codec='auto' or False)")
     fctx = getattr(face_detector, "ctx", None)
-    if not (_tiles_matches(fctx, tiles, tile_overlap) if hasattr(fctx, "tiles") else tiles == (1, 1)):
+    if not (_tiles_matches(fctx, tiles, tile_overlap, tile_nets) if hasattr(fctx, "tiles") else tiles == (1, 1)):
         raise ValueError("tiles needs the vdmi Retinaface built with the same setting "
-                         "(Retinaface(tiles=..., tile_overlap=...))")
+                         "(Retinaface(tiles=..., tile_overlap=..., tile_nets=...))")
     warm_frames = hold + 1 if hold_motion else hold      # the history's depth
     if rescue_on:
         warm_frames += rescue_span                       # E_t depends on frames [t - S, t]

@@ -89,7 +89,8 @@ class YOLO:
     """ultralytics-style plate detector on libvdmi."""
 
     def __init__(self, model="best.pt", nc=1, weights=None, precision="fp32", max_batch=64, device_index=None,
-                 seed=0, imgsz=640, iou=0.7, max_det=300, names=None, device_ids=None, rescue=0.0):
+                 seed=0, imgsz=640, iou=0.7, max_det=300, names=None, device_ids=None, rescue=0.0, tiles=(1, 1),
+                 tile_overlap=20):
         from .face import resolve_devices
         self.nc = nc
         self.names = names or {i: f"plate{i}" if nc > 1 else "plate" for i in range(nc)}
@@ -101,8 +102,13 @@ class YOLO:
         # rescue: the plate detector's low threshold of the weak-detection rescue (Context(plate_rescue=...));
         # it acts in a fused face + plate context (vdmi.pipeline), the lists returned here stay the detections
         _, self.rescue, _ = _lib.check_rescue(0.0, rescue)
+        # tiles / tile_overlap: tiled plate detection of the detector's own contexts (Context(tiles=...,
+        # tile_nets="plates")): every image also goes through the net as R x C overlapping crops, merged per
+        # class, so plates too small for the letterboxed image are found; a call carries max_batch // T images
+        self.tiles, self.tile_overlap = _lib.check_tiles(tiles, tile_overlap)
         self.ctxs = [Context(device=d, precision=precision, max_batch=max_batch, plate_nc=nc, plate_iou=iou,
-                             plate_max_det=max_det, plate_imgsz=imgsz, plate_rescue=self.rescue)
+                             plate_max_det=max_det, plate_imgsz=imgsz, plate_rescue=self.rescue, tiles=self.tiles,
+                             tile_overlap=self.tile_overlap, tile_nets="plates")
                      for d in self.device_ids]
         self.ctx = self.ctxs[0]
         if isinstance(weights, str) and weights == "random":   # explicit opt-in (tests, bench)
@@ -134,8 +140,9 @@ class YOLO:
         for i, im in enumerate(imgs):
             groups.setdefault(im.shape[:2], []).append(i)
         for (h, w), idx in groups.items():
-            for s in range(0, len(idx), self.max_batch):
-                chunk = idx[s:s + self.max_batch]
+            step = ctx.frames_per_call(faces=False, plates=True)   # a long batch is split
+            for s in range(0, len(idx), step):
+                chunk = idx[s:s + step]
                 batch = np.stack([imgs[i] for i in chunk]) if len(chunk) > 1 else imgs[chunk[0]][None]
                 bx = ctx.detect_plates(np.ascontiguousarray(batch, np.uint8))
                 for j, i in enumerate(chunk):
