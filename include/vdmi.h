@@ -32,7 +32,7 @@
  *                                   no reference equivalent: the reference blurs the detector's rectangle)
  *   vd_cells / vd_smooth / vd_cell_level: blur strength that follows the box size (at most N cells across a
  *                                   box; no reference equivalent: the reference's cell is level px for every box)
- *   vd_process_nv12 / vd_mosaic_nv12 / vd_nv12_to_rgb: the same path on NV12 video surfaces (vd_nv12: what a
+ *   vd_process_nv12 / vd_process_lead_nv12 / vd_mosaic_nv12 / vd_nv12_to_rgb: the same path on NV12 video surfaces (vd_nv12: what a
  *                                   decoder hands out and an encoder takes back; no reference equivalent: the
  *                                   reference works on the RGB frames of ffmpeg-split images)
  *   vd_read_boxes                <- the complete per-frame box lists the reference's
@@ -374,7 +374,7 @@ int vd_read_held(vd_ctx* ctx, int n, vd_boxes* out);
  * of the pending frames. flags must include VD_PROC_MOSAIC (VD_ERR_ARG). Refusals, each checked
  * before any state changes: m > out_cap VD_ERR_CAPACITY; J == 0 VD_ERR_STATE; (h, w, pitch)
  * differing from the pending frames' VD_ERR_STATE (flush first); frames pending from
- * vd_lead_lists VD_ERR_STATE; motion with h or w > 32768 VD_ERR_ARG.
+ * vd_lead_lists or vd_process_lead_nv12 VD_ERR_STATE; motion with h or w > 32768 VD_ERR_ARG.
  *
  * vd_lead_lists: the same step for callers with their own detectors, lists only, by the same
  * kernel. det: the D lists of n consecutive h x w frames as for vd_hold (a host list with
@@ -382,7 +382,7 @@ int vd_read_held(vd_ctx* ctx, int n, vd_boxes* out);
  * room for pending + n frames): B_t of the m emitted frames under the vd_boxes contract, label
  * 0 for an own box, +a for a box held from frame t - a, -a for a box led from frame t + a;
  * score and xyxy_f are not written. The hold history advances as by vd_hold. Frames pending
- * from vd_process_lead: VD_ERR_STATE.
+ * from vd_process_lead or vd_process_lead_nv12: VD_ERR_STATE.
  *
  * vd_read_lead: the lists of emitted frames [0, n) of the last lead call under the vd_boxes
  * contract, which 0: A_t alone (labels -a), 1: B_t; ordered on the context stream like
@@ -745,8 +745,8 @@ int vd_tiles_merge_plates(vd_ctx* ctx, const vd_boxes* lists, int n, int h, int 
  * overlap (whole n*frame_stride ranges); the smooth blur's limits above. Limits of this version
  * (VD_ERR_STATE, the message names the setting): VD_PROC_MOSAIC / vd_mosaic_nv12 in a
  * VD_BLUR_GAUSSIAN context with cells off (the fixed 31-tap Gaussian has no NV12 pass: set cells);
- * any NV12 detection call with tiling on; the look-ahead hold has no NV12 entry point
- * (vd_process_nv12 obeys vd_process's rules in a lead context). Pixelation is one output launch per
+ * any NV12 detection call with tiling on. The look-ahead hold has its own NV12 entry point,
+ * vd_process_lead_nv12 below (vd_process_nv12 obeys vd_process's rules in a lead context). Pixelation is one output launch per
  * call for both planes (nv12.hip, timing family 1, work 2 * 1.5 * h * w per frame); the NV12
  * letterbox is family 2. */
 #define VD_NV12_BT601 0
@@ -773,6 +773,38 @@ int vd_mosaic_nv12(vd_ctx* ctx, const vd_nv12* in, const vd_nv12* out, int n, in
  * h, w <= 32768 and 1 <= level <= 32768 (VD_ERR_ARG otherwise); the context's mask setting applies. */
 int vd_smooth_nv12(vd_ctx* ctx, const vd_nv12* in, const vd_nv12* out, int n, int h, int w, int where,
                    const vd_boxes* boxes, int level, int cells);
+/* vd_process_lead on NV12 frames: the look-ahead hold (vd_lead with J > 0) on video surfaces. The n
+ * surfaces of `in` are pushed and the m oldest unemitted ones are written, blurred, to the first m of
+ * the out_cap surfaces `out` describes (emitted frame i at out->base + i * out->frame_stride; `out` may
+ * be NULL when nothing is emitted). Nothing new is defined: with C the conversion above,
+ *   lists   faces / plates of the pushed frames, the hold history, m, *n_out and vd_read_lead of the
+ *           emitted frames are exactly vd_process_lead's on the RGB stream C(frame) in a context
+ *           with the same settings;
+ *   pixels  emitted surface t is exactly what vd_mosaic_nv12 writes for input surface t and the list
+ *           B_t = D_t ++ H_t ++ A_t under the context's settings (pixelation, or in a VD_BLUR_GAUSSIAN
+ *           context with cells on the scaled smooth blur; mask growth, the ellipse restore and cells
+ *           act on B_t as in vd_process_nv12). Bytes of `out` outside [0, w) of the two planes' rows
+ *           are not written.
+ * Neither depends on how the stream is cut into calls (calls of one frame and of fewer than `delay`
+ * frames included), on `where`, or on the surface layout of any call: the pending surfaces live in a
+ * ring of the library's own, packed (pitch w, chroma at h * w, 1.5 * h * w bytes per frame, `delay`
+ * slots: half the RGB ring), so pitch, uv_offset and frame_stride may differ from call to call, as
+ * decoders hand out surfaces from pools; matrix and range may differ too (they enter the detection
+ * of the pushed frames only). h and w must equal the pending frames'. Delay, flush and n == 0 follow
+ * vd_process_lead: with n == 0 `in` may be NULL and flush is required; the end of an empty stream is
+ * VD_OK with *n_out = 0. Per call one launch packs the kept surfaces into the ring (nv12.hip, timing
+ * family 4, work = bytes read + written); the slots that stay move down by device-to-device copies.
+ * Refusals, each checked before any state changes (a VD_ERR_STATE message names the setting): a bad
+ * descriptor or odd h or w VD_ERR_ARG; J == 0 VD_ERR_STATE; flags without VD_PROC_MOSAIC, or with
+ * neither VD_PROC_FACES nor VD_PROC_MOSAIC_PLATES, VD_ERR_ARG; m > out_cap VD_ERR_CAPACITY; m > 0 with
+ * `out` NULL VD_ERR_ARG; device in / out ranges (n * frame_stride, m * frame_stride) that overlap
+ * VD_ERR_ARG; a VD_BLUR_GAUSSIAN context with cells off VD_ERR_STATE; a call that would run a tiled net
+ * VD_ERR_STATE; h or w differing from the pending frames' VD_ERR_STATE (flush first); frames pending
+ * from vd_process_lead or vd_lead_lists VD_ERR_STATE, as are those two calls while NV12 frames are
+ * pending; motion with h or w > 32768 VD_ERR_ARG. Everything vd_lead lists as refused while frames are
+ * pending is refused for pending NV12 frames too, and vd_hold_reset abandons them. */
+int vd_process_lead_nv12(vd_ctx* ctx, const vd_nv12* in, const vd_nv12* out, int n, int h, int w, int where, int flags,
+                         vd_boxes* faces, vd_boxes* plates, int out_cap, int flush, int* n_out);
 /* C(frame) of n frames into packed RGB rows of rgb_pitch >= 3*w bytes, frame i at rgb + i*h*rgb_pitch
  * (host only: no context, no GPU): the routine the kernels' conversion function is compiled from. */
 int vd_nv12_to_rgb(const vd_nv12* in, int n, int h, int w, uint8_t* rgb, size_t rgb_pitch);
@@ -784,7 +816,7 @@ int vd_nv12_to_rgb(const vd_nv12* in, int n, int h, int w, uint8_t* rgb, size_t 
  * reset. Families: 0 = RetinaFace conv (implicit GEMM / streaming 1x1), 1 = mosaic
  * output pass (or the Gaussian blur's launches, or the smooth blur's copy and box pass; the mask's restore pass, work 0: its bytes follow
  * from the boxes; the NV12 output pass or the NV12 smooth blur's copy, work 2 * 1.5 * h * w per frame, its box pass and the NV12 restore, work 0), 2 = letterbox (the tile letterbox too; NV12: 1.5 B/px of source), 3 = post (decode/NMS, box hold,
- * look-ahead lists, mask grow, tile merge), 4 = other (the look-ahead pixel ring's copies), 5 = YOLOv8n plate
+ * look-ahead lists, mask grow, tile merge), 4 = other (the look-ahead pixel ring's copies and the NV12 ring push), 5 = YOLOv8n plate
  * conv, 6 = mosaic cell table (box prep + walked cell colours). */
 int vd_timing_enable(vd_ctx* ctx, int on);
 int vd_timing_reset(vd_ctx* ctx);

@@ -1,7 +1,8 @@
 // lead_state_check.cpp — host check of the look-ahead hold's pending-ring bookkeeping
 // (csrc/lead_state.h): the emission arithmetic and the window-to-slot mapping the kernel and
 // the runtime share, run over host arrays that stand for the two device buffers, against a
-// plain deque of the frames pushed and not yet emitted. Stand-alone, no HIP:
+// plain deque of the frames pushed and not yet emitted; and the rule that one stream is pushed
+// by one entry point (RGB frames, lists or NV12 surfaces). Stand-alone, no HIP:
 //
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       tools/lead_state_check.cpp -o lead_state_check && ./lead_state_check
@@ -12,6 +13,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <deque>
 #include <vector>
 
@@ -37,6 +39,8 @@ static int run(int J, int motion, long* checks) {
     std::vector<int> buf[2] = {std::vector<int>(D, -1), std::vector<int>(D, -1)};   // slot -> frame id
     std::deque<int> model;                                                         // oldest first
     int next_id = 0, emitted = 0;                                                  // frames leave in order
+    static const int MODES[3] = {VD_LEAD_MODE_PIXELS, VD_LEAD_MODE_LISTS, VD_LEAD_MODE_NV12};
+    int mode = MODES[0];                                                           // the entry point pushing this stream
     for (int step = 0; step < 600; ++step) {
         int n = step < 13 ? step : (int)rnd(13);
         int flush = rnd(8) == 0;
@@ -48,6 +52,13 @@ static int run(int J, int motion, long* checks) {
         }
         if (st.pend != (int)model.size()) return fail("pending count", D, step);
         if (st.pend > D) return fail("pending above delay", D, step);
+        // a new stream may come through any entry point; a pending one takes its own alone
+        if (st.pend == 0) mode = MODES[rnd(3)];
+        for (int cm : MODES) {
+            const int want_ok = st.pend == 0 || cm == mode;
+            if (vd_lead_mode_ok(st.pend, st.mode, cm) != want_ok) return fail("mode mismatch rule", D, step);
+            ++*checks;
+        }
         std::vector<int> call(n);
         for (int f = 0; f < n; ++f) call[f] = next_id++;
         const int m = st.emit(n, flush);
@@ -86,9 +97,12 @@ static int run(int J, int motion, long* checks) {
         }
         emitted += m;
         model.assign(win.begin() + m, win.end());
-        st.end(n, flush, VD_LEAD_MODE_LISTS, 100, 100, 300);
+        // the ring of NV12 surfaces is the library's own, packed: no pitch to remember
+        const unsigned long long pitch = mode == VD_LEAD_MODE_PIXELS ? 300 : 0;
+        st.end(n, flush, mode, 100, 100, pitch);
         if (st.pend != (int)model.size()) return fail("pending after the call", D, step);
-        if ((st.pend == 0) != (st.mode == VD_LEAD_MODE_NONE)) return fail("mode", D, step);
+        if (st.mode != (st.pend ? mode : VD_LEAD_MODE_NONE)) return fail("mode", D, step);
+        if (st.pitch != (st.pend ? pitch : 0) || st.h != (st.pend ? 100 : 0)) return fail("pending geometry", D, step);
         for (int j = 0; j < st.pend; ++j)
             if (buf[st.cur].at(j) != model[j]) return fail("shifted ring", D, step);
     }
@@ -97,6 +111,10 @@ static int run(int J, int motion, long* checks) {
 
 int main() {
     long checks = 0;
+    if (std::strcmp(vd_lead_mode_caller(VD_LEAD_MODE_PIXELS), "vd_process_lead") ||
+        std::strcmp(vd_lead_mode_caller(VD_LEAD_MODE_LISTS), "vd_lead_lists") ||
+        std::strcmp(vd_lead_mode_caller(VD_LEAD_MODE_NV12), "vd_process_lead_nv12"))
+        return fail("mode caller names", 0, 0);
     for (int motion = 0; motion <= 1; ++motion)
         for (int J = 1; J <= VD_LEAD_MAX; ++J)                // delays 1 .. 9
             if (run(J, motion, &checks)) return 1;

@@ -43,6 +43,20 @@ VD_LHD inline int vd_lead_source(int i, int pend, int n, int* idx) {
 #define VD_LEAD_MODE_NONE 0     // nothing pending
 #define VD_LEAD_MODE_PIXELS 1   // pending frames were pushed by vd_process_lead
 #define VD_LEAD_MODE_LISTS 2    // pending lists were pushed by vd_lead_lists
+#define VD_LEAD_MODE_NV12 3     // pending NV12 surfaces were pushed by vd_process_lead_nv12
+
+// One stream is pushed by one entry point: a call of mode `call_mode` joins the pending frames
+// only when nothing is pending or they were pushed in the same mode (otherwise: flush first).
+VD_LHD inline int vd_lead_mode_ok(int pend, int pending_mode, int call_mode) {
+    return pend == 0 || pending_mode == call_mode;
+}
+
+// The entry point that pushes frames of `mode` (for the refusal's message).
+inline const char* vd_lead_mode_caller(int mode) {
+    return mode == VD_LEAD_MODE_PIXELS ? "vd_process_lead"
+           : mode == VD_LEAD_MODE_LISTS ? "vd_lead_lists"
+           : mode == VD_LEAD_MODE_NV12 ? "vd_process_lead_nv12" : "nothing";
+}
 
 struct LeadState {
     int J = 0;          // vd_lead frames (0: off)

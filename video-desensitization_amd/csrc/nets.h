@@ -261,7 +261,7 @@ struct Ctx {
     int* lead_ring[2] = {nullptr, nullptr};       // ping-pong pending lists (vd_common.h LeadArgs gives the layout)
     int lead_hcap = 0;                            // D-list capacity of a ring slot (boxes); rows: (K + 1) * lead_hcap
     int lead_slots = 0;                           // slots the ring buffers were sized for (= delay)
-    void* lead_pix = nullptr; size_t lead_pix_bytes = 0;     // pixel ring: delay frames, oldest first
+    void* lead_pix = nullptr; size_t lead_pix_bytes = 0;     // pixel ring: delay frames (RGB, or packed NV12), oldest first
     void* lead_rows = nullptr; size_t lead_rows_bytes = 0;   // the last call's merged rows, labels, |B|, |D|, |D ++ H|
     LeadArgs lead_last{};                         // the last launch (merged-row pointers for the readers)
     int lead_m = 0;                               // frames the last lead call emitted
@@ -471,9 +471,12 @@ struct Ctx {
     // One lead step: the n pushed frames' D lists (and, under hold, hold_last's rows) join the window, the m
     // oldest frames get B = D ++ H ++ A in lead_last's merged rows, the rest becomes the next ring. With
     // pixels (din / dout device pointers, dout for m frames) the emitted frames are blurred and the pixel
-    // ring is updated. The state advances only when everything was queued.
+    // ring is updated. The state advances only when everything was queued. VD_LEAD_MODE_NV12: the frames
+    // are the surfaces *nvin (n of them), the emitted ones go to *nvout (m of them), and the ring holds
+    // packed surfaces (pitch w, chroma at h * w, 1.5 * h * w bytes a slot); din / dout / pitch are not used.
     int lead_step(int mode, const uint8_t* din, uint8_t* dout, int n, int h, int w, size_t pitch, int flush,
-                  const int* cnt0, const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1);
+                  const int* cnt0, const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1,
+                  const Nv12Dev* nvin = nullptr, const Nv12Dev* nvout = nullptr);
     int lead_read(int n, int which, vd_boxes* out);   // merged rows -> caller lists (label 0, +a, -a)
 };
 

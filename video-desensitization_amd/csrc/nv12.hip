@@ -1,4 +1,5 @@
-// nv12.hip — out-of-place pixelation of NV12 frames, both planes in one launch.
+// nv12.hip — out-of-place pixelation of NV12 frames, both planes in one launch; and, at the end, the
+// copy that packs surfaces into the look-ahead ring (vd_launch_nv12_pack).
 //
 // Definition (include/vdmi.h at vd_nv12): for box b of the list being blurred, c = b clipped to
 // the frame and L = L(b) (vd_cell_level_hd of the box as stored): the luma plane takes the mosaic
@@ -259,7 +260,53 @@ __global__ __launch_bounds__(256) void nv12_mosaic_kernel(Nv12MosaicArgs a) {
     }
 }
 
+// ---- the look-ahead ring push: surfaces from one layout into another, [0, w) of every plane row ----
+// Grid-y runs over groups of PACK_ROWS (frame, plane row) pairs, one wave per row (a surface's h luma
+// rows, then its h / 2 chroma rows); grid-x over the row in steps of 64 lanes x 16 B. A row whose
+// source and target starts are congruent mod 16 goes as a byte head up to the first 16-B boundary,
+// 16-B loads and stores, and a byte tail; any other row goes byte by byte. Nothing is assumed of w,
+// the pitches, the plane offsets or the strides: a packed slot of w = 130 starts its rows at every
+// residue. Bytes outside [0, w) of a row are neither read nor written.
+constexpr int PACK_ROWS = 4;
+constexpr int PACK_STEP = 64 * 16;    // bytes of a row per grid-x step
+
+__device__ __forceinline__ size_t pack_row(int y, int h, size_t pitch, size_t uv) {
+    return y < h ? (size_t)y * pitch : uv + (size_t)(y - h) * pitch;
+}
+
+__global__ __launch_bounds__(64 * PACK_ROWS) void nv12_pack_kernel(Nv12PackArgs a) {
+    const int lane = threadIdx.x, rows = a.h + a.h / 2;
+    const long long total = (long long)a.n * rows;
+    for (long long r = (long long)blockIdx.y * PACK_ROWS + threadIdx.y; r < total; r += (long long)gridDim.y * PACK_ROWS) {
+        const int f = (int)(r / rows), y = (int)(r - (long long)f * rows);
+        const uint8_t* s = a.src + (size_t)f * a.src_stride + pack_row(y, a.h, a.src_pitch, a.src_uv);
+        uint8_t* d = a.dst + (size_t)f * a.dst_stride + pack_row(y, a.h, a.dst_pitch, a.dst_uv);
+        const bool vec = (((uintptr_t)s ^ (uintptr_t)d) & 15) == 0;
+        const int head = vec ? min(a.w, (int)((16 - ((uintptr_t)s & 15)) & 15)) : a.w;
+        const int nvec = (a.w - head) >> 4, tail0 = head + (nvec << 4);
+        const int v = blockIdx.x * 64 + lane;
+        if (v < nvec) *(uint4*)(d + head + ((size_t)v << 4)) = *(const uint4*)(s + head + ((size_t)v << 4));
+        // the head and the tail (fewer than 16 bytes each), or the whole row
+        const int nbytes = head + (a.w - tail0);
+        const int b1 = min(nbytes, (int)(blockIdx.x + 1) * PACK_STEP);
+        for (int i = blockIdx.x * PACK_STEP + lane; i < b1; i += 64) {
+            const int x = i < head ? i : tail0 + (i - head);
+            d[x] = s[x];
+        }
+    }
+}
+
 }  // namespace
+
+hipError_t vd_launch_nv12_pack(const Nv12PackArgs& a, hipStream_t s) {
+    if (a.n <= 0 || a.h <= 0 || a.w <= 0 || (a.h & 1) || (a.w & 1) || a.src_pitch < (size_t)a.w ||
+        a.dst_pitch < (size_t)a.w || !a.src || !a.dst)
+        return hipErrorInvalidValue;
+    const long long groups = ((long long)a.n * (a.h + a.h / 2) + PACK_ROWS - 1) / PACK_ROWS;
+    const dim3 grid((a.w + PACK_STEP - 1) / PACK_STEP, (unsigned)(groups < 65535 ? groups : 65535));
+    hipLaunchKernelGGL(nv12_pack_kernel, grid, dim3(64, PACK_ROWS), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t vd_launch_mosaic_nv12(const Nv12MosaicArgs& a, hipStream_t s) {
     // sw | sh << 16 holds 16 bits per axis; even sizes only (the chroma plane is (h/2) x (w/2) pairs)

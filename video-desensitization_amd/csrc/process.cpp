@@ -1,5 +1,5 @@
 // process.cpp — detection and blurring: the blur passes behind the mask setting, the stand-alone
-// blur entries, vd_detect*, vd_read_boxes and vd_process / vd_process_lead.
+// blur entries, vd_detect*, vd_read_boxes and vd_process / vd_process_lead and their NV12 forms.
 
 #include "../../include/vdmi.h"
 #include "vd_common.h"
@@ -326,7 +326,8 @@ struct LeadCall {
 };
 
 // A vd_process_nv12 call's part in that body: the frames are NV12 surfaces (checked by the entry
-// point), so the letterbox and the output launches differ; `in` / `out` / `pitch` are not used.
+// point), so the letterbox and the output launches differ; `in` / `out` / `pitch` are not used. Together
+// with a LeadCall (vd_process_lead_nv12) `out` describes the m emitted surfaces, NULL when m == 0.
 struct Nv12Call {
     const vd_nv12* in; const vd_nv12* out;
 };
@@ -473,6 +474,14 @@ static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh
         return VD_OK;
     };
     auto mosaic = [&]() -> int {
+        if (nv && lc) {   // look-ahead hold on surfaces: the m emitted ones leave through the output side
+            int r = lc->m ? ctx->nv12_out_begin(*nv->out, lc->m, fh, fw, where, &nout) : VD_OK;
+            if (r) return r;
+            if ((r = ctx->lead_step(VD_LEAD_MODE_NV12, nullptr, nullptr, n, fh, fw, 0, lc->flush, dc0, dx0, dk0, dc1, dx1, dk1,
+                                    &nin, &nout)))
+                return r;
+            return lc->m ? ctx->nv12_out_finish(*nv->out, nout, lc->m, fh, fw, where) : VD_OK;
+        }
         if (nv) {   // both planes, by the pass the context's blur mode asks for; host surfaces come back plane by plane
             int r = ctx->nv12_out_begin(*nv->out, n, fh, fw, where, &nout);
             if (r) return r;
@@ -566,8 +575,8 @@ int vd_process_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n, int
     if (((flags & VD_PROC_FACES) && ctx->faces_tiled()) || ((flags & VD_PROC_PLATES) && ctx->plates_tiled()))
         return vd_set_error(VD_ERR_STATE, "%s: tiled detection (vd_tiles) reads RGB frames only", who);
     if (ctx->lead.J && (flags & VD_PROC_MOSAIC))
-        return vd_set_error(VD_ERR_STATE, "%s: MOSAIC in a look-ahead context would skip the led boxes (vd_lead has no "
-                            "NV12 entry point)", who);
+        return vd_set_error(VD_ERR_STATE, "%s: MOSAIC in a look-ahead context would skip the led boxes (use "
+                            "vd_process_lead_nv12)", who);
     if (ctx->lead.pend)
         return vd_set_error(VD_ERR_STATE, "%s: %d frames are pending in the look-ahead ring (flush first)", who,
                             ctx->lead.pend);
@@ -661,6 +670,64 @@ int vd_process_lead(vd_ctx* h, const uint8_t* in, int n, int fh, int fw, size_t 
             VD_CHECK_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
             VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
         }
+    }
+    if (rc) return rc;
+    if (n_out) *n_out = m;
+    return VD_OK;
+}
+
+// vd_process_lead on NV12 surfaces: vd_process_lead's rules with vd_process_nv12's descriptors. Every
+// refusal comes before anything changes; `out` describes out_cap surfaces, of which m are written.
+int vd_process_lead_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n, int fh, int fw, int where, int flags,
+                         vd_boxes* faces, vd_boxes* plates, int out_cap, int flush, int* n_out) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    const char* who = "vd_process_lead_nv12";
+    if (where != VD_HOST && where != VD_DEVICE) return vd_set_error(VD_ERR_ARG, "%s: bad where", who);
+    if (n < 0 || out_cap < 0) return vd_set_error(VD_ERR_ARG, "%s: negative n / out_cap", who);
+    int rc;
+    if (n > 0) {
+        if ((rc = vd_nv12_check(who, in, n, fh, fw, true))) return rc;
+    } else if (fh <= 0 || fw <= 0 || (fh & 1) || (fw & 1)) {
+        return vd_set_error(VD_ERR_ARG, "%s: NV12 frames: even, positive h and w required (got %d x %d)", who, fw, fh);
+    }
+    if (!ctx->lead.J) return vd_set_error(VD_ERR_STATE, "%s: look-ahead hold is off (vd_lead)", who);
+    if (!(flags & VD_PROC_MOSAIC)) return vd_set_error(VD_ERR_ARG, "%s: flags must include VD_PROC_MOSAIC", who);
+    if (!(flags & VD_PROC_FACES) && !(flags & VD_PROC_MOSAIC_PLATES))
+        return vd_set_error(VD_ERR_ARG, "%s: nothing to blur (FACES or MOSAIC_PLATES needed)", who);
+    if (n == 0 && flush && !ctx->lead.pend) {      // the end of an empty stream
+        if (n_out) *n_out = 0;
+        return VD_OK;
+    }
+    if (ctx->nv12_cfg_pass() < 0)
+        return vd_set_error(VD_ERR_STATE, "%s: the fixed-kernel Gaussian (blur_mode VD_BLUR_GAUSSIAN with cells off) has "
+                            "no NV12 pass: set cells (vd_cells) for the scaled smooth blur", who);
+    if (n > 0 && (((flags & VD_PROC_FACES) && ctx->faces_tiled()) || ((flags & VD_PROC_PLATES) && ctx->plates_tiled())))
+        return vd_set_error(VD_ERR_STATE, "%s: tiled detection (vd_tiles) reads RGB frames only", who);
+    if ((rc = ctx->lead_check(who, VD_LEAD_MODE_NV12, n, fh, fw, 0, flush))) return rc;
+    const int m = ctx->lead.emit(n, flush);
+    if (m > out_cap) return vd_set_error(VD_ERR_CAPACITY, "%s: %d frames to emit, out holds %d", who, m, out_cap);
+    if (m > 0) {
+        if (!out) return vd_set_error(VD_ERR_ARG, "%s: MOSAIC needs an output descriptor", who);
+        if ((rc = vd_nv12_check(who, out, m, fh, fw, false))) return rc;
+        if (where == VD_DEVICE && n > 0) {
+            const uintptr_t a = (uintptr_t)in->base, b = (uintptr_t)out->base;
+            if (a < b + (size_t)m * out->frame_stride && b < a + (size_t)n * in->frame_stride)
+                return vd_set_error(VD_ERR_ARG, "%s: out must not overlap in", who);
+        }
+    }
+    const LeadCall lc{flush, m};
+    if (n > 0) {
+        const Nv12Call nv{in, out};
+        rc = process_impl(ctx, nullptr, nullptr, n, fh, fw, 0, where, flags, faces, plates, &lc, &nv);
+    } else {      // flush alone: the pending surfaces leave, no detection
+        Ctx::Nv12Dev nin{}, nout{};
+        if ((rc = ctx->nv12_out_begin(*out, m, fh, fw, where, &nout))) return rc;
+        if ((rc = ctx->lead_step(VD_LEAD_MODE_NV12, nullptr, nullptr, 0, fh, fw, 0, 1, nullptr, nullptr, 0, nullptr, nullptr,
+                                 0, &nin, &nout)))
+            return rc;
+        if ((rc = ctx->nv12_out_finish(*out, nout, m, fh, fw, where))) return rc;
+        if (where == VD_HOST) VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     }
     if (rc) return rc;
     if (n_out) *n_out = m;

@@ -132,9 +132,9 @@ int Ctx::lead_check(const char* who, int mode, int n, int h, int w, size_t pitch
     if ((lead.motion || (hold.K && hold.motion)) && (h > 32768 || w > 32768))
         return vd_set_error(VD_ERR_ARG, "%s: motion needs frames of at most 32768 x 32768 (got %d x %d)", who, w, h);
     if (lead.pend) {
-        if (lead.mode != mode)
+        if (!vd_lead_mode_ok(lead.pend, lead.mode, mode))
             return vd_set_error(VD_ERR_STATE, "%s: %d frames are pending from %s (flush first)", who, lead.pend,
-                                lead.mode == VD_LEAD_MODE_PIXELS ? "vd_process_lead" : "vd_lead_lists");
+                                vd_lead_mode_caller(lead.mode));
         if (lead.h != h || lead.w != w || (mode == VD_LEAD_MODE_PIXELS && lead.pitch != (unsigned long long)pitch))
             return vd_set_error(VD_ERR_STATE, "%s: %d frames of %dx%d (pitch %llu) are pending; got %dx%d (pitch %zu): "
                                 "flush first", who, lead.pend, lead.w, lead.h, lead.pitch, w, h, pitch);
@@ -180,9 +180,11 @@ int Ctx::lead_buffers(int need, size_t frame_bytes) {
 }
 
 int Ctx::lead_step(int mode, const uint8_t* din, uint8_t* dout, int n, int h, int w, size_t pitch, int flush,
-                   const int* cnt0, const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1) {
-    const bool pixels = mode == VD_LEAD_MODE_PIXELS;
-    const size_t fb = pixels ? (size_t)h * pitch : 0;
+                   const int* cnt0, const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1,
+                   const Nv12Dev* nvin, const Nv12Dev* nvout) {
+    const bool pixels = mode == VD_LEAD_MODE_PIXELS, nv12 = mode == VD_LEAD_MODE_NV12;
+    // a ring slot: an RGB frame as pushed, or a packed NV12 surface (pitch w, chroma at h * w): half the bytes
+    const size_t fb = pixels ? (size_t)h * pitch : nv12 ? (size_t)h * w / 2 * 3 : 0;
     int rc = lead_buffers(std::max(lead_hcap, lead_need(cnt0 ? cap0 : 0, cnt1 ? cap1 : 0)), fb);
     if (rc) return rc;
     const int delay = lead.delay(), pend = lead.pend, m = lead.emit(n, flush), keep = pend + n - m;
@@ -236,7 +238,45 @@ int Ctx::lead_step(int mode, const uint8_t* din, uint8_t* dout, int n, int h, in
                                         hipMemcpyDeviceToDevice, stream));
         t_end();
     }
-    lead.end(n, flush, mode, h, w, pitch);
+    if (nv12) {
+        // the same on surfaces: a ring slot is itself a valid surface for the NV12 passes
+        const Nv12Dev ring{(uint8_t*)lead_pix, (size_t)w, (size_t)h * w, fb};
+        const int mr = std::min(m, pend), mi = m - mr;
+        const int pass = nv12_cfg_pass();
+        if (mr && (rc = launch_nv12_pass(ring, *nvout, mr, h, w, a.m_count, a.m_xy, a.mcap, nullptr, nullptr, 0, pass,
+                                         cfg.mosaic_level, cells)))
+            return rc;
+        if (mi) {
+            Nv12Dev o = *nvout;
+            o.base += (size_t)mr * o.stride;
+            if ((rc = launch_nv12_pass(*nvin, o, mi, h, w, a.m_count + mr, a.m_xy + (size_t)mr * mcap * 4, a.mcap, nullptr,
+                                       nullptr, 0, pass, cfg.mosaic_level, cells)))
+                return rc;
+        }
+        // the staying slots move down slot by slot (ascending: one copy's source and target never
+        // overlap); then one launch packs this call's kept surfaces behind them (nv12.hip)
+        const int stay = pend - mr, push = keep - stay;
+        if (mr && stay) {
+            t_begin(4, (double)stay * fb * 2);
+            for (int j = 0; j < stay; ++j)
+                VD_CHECK_HIP(hipMemcpyAsync(ring.base + (size_t)j * fb, ring.base + (size_t)(j + mr) * fb, fb,
+                                            hipMemcpyDeviceToDevice, stream));
+            t_end();
+        }
+        if (push > 0) {
+            Nv12PackArgs p{};
+            p.src = nvin->base + (size_t)mi * nvin->stride;
+            p.src_pitch = nvin->pitch; p.src_uv = nvin->uv; p.src_stride = nvin->stride;
+            p.dst = ring.base + (size_t)stay * fb;
+            p.dst_pitch = ring.pitch; p.dst_uv = ring.uv; p.dst_stride = ring.stride;
+            p.n = push; p.h = h; p.w = w;
+            t_begin(4, (double)push * fb * 2);
+            hipError_t e = vd_launch_nv12_pack(p, stream);
+            t_end();
+            if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "nv12 ring push: %s", hipGetErrorString(e));
+        }
+    }
+    lead.end(n, flush, mode, h, w, nv12 ? 0 : pitch);
     lead_last = a;
     lead_m = m;
     return VD_OK;

@@ -444,6 +444,13 @@ struct Nv12MosaicArgs {
     int level, cells;
 };
 hipError_t vd_launch_mosaic_nv12(const Nv12MosaicArgs& a, hipStream_t s);
+// The look-ahead ring push of NV12 surfaces (nv12.hip): [0, w) of every row of both planes of n
+// surfaces, src layout -> dst layout, one launch. No alignment is assumed of either layout.
+struct Nv12PackArgs {
+    const uint8_t* src; uint8_t* dst; int n, h, w;
+    size_t src_pitch, src_uv, src_stride, dst_pitch, dst_uv, dst_stride;
+};
+hipError_t vd_launch_nv12_pack(const Nv12PackArgs& a, hipStream_t s);
 // Box-scaled strength (include/vdmi.h at vd_cells): the cell level L of a box of unclipped size
 // W x H under the base level and the cells setting. cells == 0 or an empty box: the base level;
 // otherwise max(level, min(32768, ceil(max(W, H) / cells))). The one routine of the kernels

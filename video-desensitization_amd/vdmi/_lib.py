@@ -132,6 +132,8 @@ SIGNATURES = [
     ("vd_jpeg_encode", _I, [_P, _P, _I, _I, _I, _SZ, _I, _I, _I, _P, _SZ, ctypes.POINTER(_SZ)]),
     ("vd_process_nv12", _I, [_P, ctypes.POINTER(vd_nv12), ctypes.POINTER(vd_nv12), _I, _I, _I, _I, _I,
                              ctypes.POINTER(vd_boxes), ctypes.POINTER(vd_boxes)]),
+    ("vd_process_lead_nv12", _I, [_P, ctypes.POINTER(vd_nv12), ctypes.POINTER(vd_nv12), _I, _I, _I, _I, _I,
+                                  ctypes.POINTER(vd_boxes), ctypes.POINTER(vd_boxes), _I, _I, ctypes.POINTER(_I)]),
     ("vd_mosaic_nv12", _I, [_P, ctypes.POINTER(vd_nv12), ctypes.POINTER(vd_nv12), _I, _I, _I, _I,
                             ctypes.POINTER(vd_boxes), _I]),
     ("vd_smooth_nv12", _I, [_P, ctypes.POINTER(vd_nv12), ctypes.POINTER(vd_nv12), _I, _I, _I, _I,

@@ -843,13 +843,85 @@ class Context:
         if flags & _lib.VD_PROC_PLATES:
             plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
         self._lead_geom = (h, w, pitch, where, getattr(frames, "device", None))
+        self._lead_nv12 = None
         return out[:m.value], faces, plates
+
+    def process_lead_nv12(self, frames, out=None, faces=None, plates=None, flags=None, flush=False, matrix="bt709",
+                          range="limited", height=None):
+        """vd_process_lead_nv12: process_lead() on NV12 frames (the layouts of process_nv12()). The
+        surfaces are pushed -- faces / plates are THEIR detections, exactly process_lead()'s on
+        nv12_to_rgb(frames) -- and the m surfaces whose look-ahead is complete come back with both
+        planes blurred over B = D ++ H ++ A as mosaic_nv12() blurs them under the context's settings.
+        The layout, matrix and range may change from call to call of one stream; h and w may not.
+        frames may be None with flush=True. -> (out[:m], faces, plates); out defaults to new surfaces
+        like the input, for pending + n frames."""
+        if flags is None:
+            flags = _lib.VD_PROC_FACES | _lib.VD_PROC_MOSAIC
+        if frames is None:
+            return self.lead_flush(out), faces, plates
+        d, n, h, w, where, keep = _nv12_arg(frames, height, matrix, range)
+        rows = int((frames.shape if _is_torch(frames) else np.shape(frames))[-2])
+        dev = getattr(frames, "device", None) if _is_torch(frames) else None
+        if out is None:
+            out = self._nv12_new(self.lead_pending() + n, rows, w, where, dev)
+        od = None
+        if len(out):
+            od, cap, oh, ow, owhere, okeep = _nv12_arg(out, height, writable=True)
+            if (oh, ow, owhere) != (h, w, where):
+                raise ValueError("out must hold NV12 frames of the input's h, w in the same memory (host / device)")
+        fs = ps = None
+        auto_f, auto_p = faces is None, plates is None
+        if flags & _lib.VD_PROC_FACES:
+            faces = self._boxes(faces, n)
+            fs = faces.struct()
+        if flags & _lib.VD_PROC_PLATES:
+            plates = self._boxes(plates, n)
+            ps = plates.struct()
+        m = ctypes.c_int(0)
+        check(self._lib.vd_process_lead_nv12(self._h, ctypes.byref(d), ctypes.byref(od) if od is not None else None, n,
+                                             h, w, where, flags, ctypes.byref(fs) if fs is not None else None,
+                                             ctypes.byref(ps) if ps is not None else None, len(out), 1 if flush else 0,
+                                             ctypes.byref(m)))
+        if flags & _lib.VD_PROC_FACES:
+            faces = self._complete(faces, _lib.VD_NET_RETINAFACE, auto_f)
+        if flags & _lib.VD_PROC_PLATES:
+            plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
+        self._lead_nv12 = (h, w, rows, where, dev)
+        del keep
+        return out[:m.value], faces, plates
+
+    @staticmethod
+    def _nv12_new(n, rows, w, where, dev):
+        """n new packed surfaces of `rows` rows (3/2 of the, possibly padded, luma height) by w."""
+        if where == _lib.VD_HOST and dev is None:
+            return np.empty((n, rows, w), np.uint8)
+        import torch
+        return torch.empty((n, rows, w), dtype=torch.uint8, device=dev)
+
+    def _lead_flush_nv12(self, out, pend):
+        h, w, rows, where, dev = self._lead_nv12
+        if out is None:
+            out = self._nv12_new(pend, rows, w, where, dev)
+        if pend == 0 or len(out) == 0:
+            if pend:
+                raise _lib.VdCapacityError(_lib.VD_ERR_CAPACITY, f"{pend} frames to emit, out holds 0")
+            return out[:0]
+        od, cap, oh, ow, owhere, okeep = _nv12_arg(out, h, writable=True)
+        m = ctypes.c_int(0)
+        check(self._lib.vd_process_lead_nv12(self._h, None, ctypes.byref(od), 0, h, w, owhere,
+                                             _lib.VD_PROC_FACES | _lib.VD_PROC_MOSAIC, None, None, cap, 1,
+                                             ctypes.byref(m)))
+        del okeep
+        return out[:m.value]
 
     def lead_flush(self, out=None):
         """End the stream: the pending frames of process_lead() leave, blurred with what is
         known (vd_process_lead with n == 0 and flush). -> out[:m]; out defaults to a new array
-        / tensor like the frames pushed last."""
+        / tensor like the frames pushed last. Pending frames of process_lead_nv12() leave as NV12
+        surfaces (vd_process_lead_nv12), host or device as they were pushed, with their luma height."""
         pend = self.lead_pending()
+        if getattr(self, "_lead_nv12", None) is not None:
+            return self._lead_flush_nv12(out, pend)
         geom = getattr(self, "_lead_geom", None)
         if pend == 0 or geom is None:
             if out is not None:
