@@ -848,6 +848,52 @@ int vdt_conv2d(vd_ctx* ctx, const float* x, int n, int h, int w, int cin,
                const float* wgt, int cout, int kh, int kw, int stride, int pad,
                const float* scale, const float* shift, int act, float slope,
                const float* res, int res_mode, float* y, int* oh, int* ow);
+/* One plan op through the production executor (Ctx::run_ops on a one-op plan), on whole NHWC
+ * buffers with the channel strides, channel offsets and frame offset a network plan would use.
+ * Buffers are host f32 images converted to the context's element type on the way in and back
+ * on the way out (use values exact in that type):
+ *   x   [frames][xh][xw][ldx]   the op reads channels [xcoff, ...) of it
+ *   y   [frames][yh][yw][ldy]   in: the prior contents, out: the contents after the op
+ *   res [frames][rh][rw][res_ld] optional (conv): residual slice at res_coff, res_mode 1 = before
+ *       the activation, 2 = after it; res_up: the residual is the nearest-2x source (rh, rw =
+ *       the half-size map); r_is_y: the residual is another slice of the y buffer (res unused)
+ *   x2  [frames][xh2][xw2][ldx2] optional (conv): a second 1x1 conv (w2, cin2, stride2, BN
+ *       scale2 / shift2, no activation) summed before the activation
+ * Only frames [f0, f0 + n) are run; frames <= cfg.max_batch.
+ * y_is_x: the output slice lies in the x buffer (one allocation, one set of range slots); y is
+ *   then only written (the x buffer after the op) and has x's shape.
+ * out16: in bf16 / fp16 contexts the y buffer is kept in the context's 16-bit type as the
+ *   networks keep it (0: f32, as vdt_conv2d has it); ignored in fp32 contexts. out16 = 0 with
+ *   y_is_x or r_is_y in a 16-bit context is VD_ERR_ARG.
+ * VDT_OP_CONV: weights w [cout][cin][kh][kw] f32, BN scale / shift [cout], act as vdt_conv2d.
+ *   grp_co > 0 (fp32 contexts): output channel n reads input channels
+ *   xcoff + (n / grp_co) * grp_ci + [0, cin).
+ * VDT_OP_MAXPOOL: ch channels, window k, stride s, padding p (padded taps ignored).
+ * VDT_OP_UPSAMPLE: ch channels, nearest 2x (yh = 2 xh, yw = 2 xw).
+ * VDT_OP_DWCONV: depthwise 3x3, pad 1, w [cout][3][3] (cout = cin channels, stride 1 / 2), BN,
+ *   act; the plan form: xcoff = ycoff = 0.
+ * fp16-pair plan (fp32 context, option f32_split = 2) only, else untouched: xslots [frames]
+ *   out: the x buffer's per-frame range slots after the op (initialised to the host max |x| of
+ *   the whole x buffer of each frame); yslots [frames] in / out: the y buffer's slots (with
+ *   y_is_x: the x slots). ranged = 1 when the slots exist.
+ * family (out): the kernel family that took the conv (the dispatch record), "" for the others. */
+enum { VDT_OP_CONV = 0, VDT_OP_MAXPOOL = 1, VDT_OP_UPSAMPLE = 2, VDT_OP_DWCONV = 3 };
+typedef struct vdt_op {
+    int32_t kind, frames, f0, n;
+    const float* x; int32_t xh, xw, ldx, xcoff;
+    float* y; int32_t yh, yw, ldy, ycoff;
+    int32_t y_is_x, r_is_y, out16;
+    const float* res; int32_t rh, rw, res_ld, res_coff, res_mode, res_up;
+    const float* x2; int32_t xh2, xw2, ldx2;
+    int32_t cin, cout, kh, kw, stride, pad, act; float slope;
+    const float* w; const float* scale; const float* shift;
+    int32_t grp_co, grp_ci;
+    int32_t cin2, stride2; const float* w2; const float* scale2; const float* shift2;
+    int32_t ch, k, s, p;
+    float* xslots; float* yslots; int32_t ranged;
+    char family[32];
+} vdt_op;
+int vdt_run_op(vd_ctx* ctx, vdt_op* op);
 /* One ResNet layer1 bottleneck on host f32 NHWC x [n][h][w][cin] -> y [n][h][w][256]
  * (bf16 context): conv1 1x1 cin->64, conv2 3x3 64->64 pad 1, conv3 1x1 64->256, each
  * OIHW weights + BN as bn = [scale[cout] | shift[cout]]; ReLU after each, the residual

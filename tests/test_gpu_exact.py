@@ -26,7 +26,11 @@ The phased 256 x 256 kernel (conv_big.hip) is NOT reached by any case here or in
 test_conv_big_matches_torch: vdt_conv2d asks for the f32 accumulator (out_f32 = 1) and
 vd_conv_big_ok refuses out_f32, so the BIG_CASES options (conv_big = 1, conv_big_kmin = 0,
 conv_stream = 0) leave those shapes on the bf16 implicit GEMM of conv.hip. The legs are
-kept (they are GEMM coverage at K up to 4608) under that name."""
+kept (they are GEMM coverage at K up to 4608) under that name. Their sibling
+test_gpu_layouts.py runs the same shapes and options through vdt_run_op with the 16-bit
+output of the plans, reaches conv_big.hip and asserts so (the dispatch record); it also
+takes this file's method to channel slices, res_up, the fused second conv, grouped rows,
+in-place concats and frame offsets."""
 import numpy as np
 import pytest
 import torch
@@ -175,7 +179,8 @@ def test_conv_integer_exact(gpu, face_ctx_factory, prec, case):
 @pytest.mark.parametrize("case", BIG_CASES)
 def test_conv_big_options_integer_exact(gpu, face_ctx_factory, case):
     """BIG_CASES under the options of test_conv_big_matches_torch, bf16. Through the hook
-    these run conv.hip's implicit GEMM, not conv_big.hip (module docstring)."""
+    these run conv.hip's implicit GEMM, not conv_big.hip (module docstring);
+    test_gpu_layouts.py::test_conv_layout_16bit[L1.*] is the leg that does."""
     _check_integer_exact(face_ctx_factory, "bf16", case, BIG_OPTIONS)
 
 

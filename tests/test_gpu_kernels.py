@@ -326,8 +326,9 @@ def test_conv_fp32_split_error_matches_exact_f32(gpu, face_ctx_factory, case):
 
 
 BIG_CASES = [
-    # 256 x 256-tile phased kernel (conv_big.hip): Cout % 256 == 0, Cin % 64 == 0
-    (2, 20, 24, 128, 256, 3, 1, 1, 1, 1),     # 3x3 + residual before ReLU, M tail (960 rows)
+    # shapes of the 256 x 256-tile phased kernel (conv_big.hip): Cout % 256 == 0, Cin % 64 == 0; through
+    # vdt_conv2d (f32 output) they run the implicit GEMM, through vdt_run_op (test_gpu_layouts.py) conv_big.hip
+    (2, 20, 24, 128, 256, 3, 1, 1, 1, 1),    # 3x3 + residual before ReLU, M tail (960 rows)
     (1, 26, 30, 64, 256, 3, 2, 1, 1, 0),      # stride 2, two K tiles per tap row
     (1, 33, 31, 256, 512, 1, 1, 0, 0, 2),     # 1x1, two N tiles, residual after activation
     (2, 9, 11, 512, 256, 3, 1, 1, 2, 0),      # K = 4608 (72 K tiles), leaky
@@ -339,7 +340,9 @@ def test_conv_big_matches_torch(gpu, face_ctx_factory, case):
     """The phased 256x256 kernel's options on small shapes (option conv_big = min tiles).
     Through this hook the shapes stay on the implicit GEMM: vdt_conv2d asks for the f32
     accumulator (out_f32 = 1), which vd_conv_big_ok refuses (conv_big.hip stores 16-bit
-    outputs only). Only whole-network runs of the 16-bit plans can reach the phased kernel."""
+    outputs only), so this is GEMM coverage at K up to 4608. The phased kernel itself is
+    reached by the same shapes and options with the plans' 16-bit output in
+    test_gpu_layouts.py (rows L1 / L2, which assert the dispatch record "conv_big")."""
     test_conv_matches_torch(gpu, face_ctx_factory, "bf16", case,
                             options=dict(conv_big=1, conv_big_kmin=0, conv_stream=0))
 

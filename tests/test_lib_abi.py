@@ -29,14 +29,15 @@ def test_library_exports_every_header_symbol():
 
 
 def test_struct_layout_matches_header(tmp_path):
-    """ctypes mirrors of vd_cfg / vd_boxes have the C compiler's size and field offsets."""
+    """ctypes mirrors of vd_cfg / vd_boxes / vdt_op have the C compiler's size and field offsets."""
     import shutil
     import subprocess
     from vdmi import _lib
     cc = shutil.which("gcc") or shutil.which("cc")
     if cc is None:
         pytest.skip("no C compiler")
-    fields = {"vd_cfg": [f[0] for f in _lib.vd_cfg._fields_], "vd_boxes": [f[0] for f in _lib.vd_boxes._fields_]}
+    fields = {"vd_cfg": [f[0] for f in _lib.vd_cfg._fields_], "vd_boxes": [f[0] for f in _lib.vd_boxes._fields_],
+              "vdt_op": [f[0] for f in _lib.vdt_op._fields_]}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "vdmi.h"', "int main(void){"]
     for st, fl in fields.items():
         lines.append(f'printf("{st} %zu\\n", sizeof({st}));')
@@ -48,7 +49,7 @@ def test_struct_layout_matches_header(tmp_path):
     exe = tmp_path / "layout"
     subprocess.run([cc, "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
     out = dict(l.split() for l in subprocess.run([str(exe)], capture_output=True, text=True).stdout.splitlines())
-    for st, cls in (("vd_cfg", _lib.vd_cfg), ("vd_boxes", _lib.vd_boxes)):
+    for st, cls in (("vd_cfg", _lib.vd_cfg), ("vd_boxes", _lib.vd_boxes), ("vdt_op", _lib.vdt_op)):
         assert int(out[st]) == ctypes.sizeof(cls)
         for f in fields[st]:
             assert int(out[f"{st}.{f}"]) == getattr(cls, f).offset, f

@@ -353,6 +353,7 @@ hipError_t launch_bn(const ConvArgs& a0, bool dense, hipStream_t s) {
     constexpr size_t BUF = (size_t)(BM + BN) * 128, EPI = (size_t)(BM / EP) * (BN + 4) * 4;
     const int nk = a.kpad / (8 * VEC);
     const size_t lds = std::max((nk > 1 ? STAGES : 1) * BUF, EPI);
+    vd_conv_fam_set(VD_FAM_GEMM);
     if (dense) hipLaunchKernelGGL((conv_igemm_kernel<T, BM, BN, NT, 2, true>), grid, block, lds, s, a);
     else hipLaunchKernelGGL((conv_igemm_kernel<T, BM, BN, NT, 2, false>), grid, block, lds, s, a);
     return hipGetLastError();

@@ -301,6 +301,7 @@ hipError_t launch_stream_t(const ConvArgs& a, hipStream_t s) {
     int k = std::max(1, resident / (8 * nchunks));
     k = std::min(k, std::max(1, (groups + 63) / 64));
     dim3 grid(8 * nchunks * k), block(512);
+    vd_conv_fam_set(KS2 ? VD_FAM_DUAL : (TAPS ? VD_FAM_TAPS : VD_FAM_STREAM));
     hipLaunchKernelGGL((conv1x1_stream_kernel<KS, NTT, ACT, RES, TAPS, KS2, F16>), grid, block, lds, s, a, nchunks, groups);
     return hipGetLastError();
 }

@@ -337,6 +337,7 @@ hipError_t vd_launch_conv_big(const ConvArgs& a0, hipStream_t s) {
     ConvArgs a = a0;
     a.ntiles_n = a.cout / 256;
     dim3 grid(((a.M + 255) / 256) * a.ntiles_n), block(512);
+    vd_conv_fam_set(VD_FAM_BIG);
     if (a.f16) hipLaunchKernelGGL(conv_big_kernel<true>, grid, block, LDS_BYTES, s, a);
     else hipLaunchKernelGGL(conv_big_kernel<false>, grid, block, LDS_BYTES, s, a);
     return hipGetLastError();

@@ -500,6 +500,7 @@ static hipError_t launch_x6(const ConvArgs& a0, hipStream_t s) {
     a.ntiles_n = (a.cout + BN - 1) / BN;
     const int mt = (a.M + BM - 1) / BM;
     const int lds = S::LDS + (a.ymax ? 4 * a.B : 0);
+    vd_conv_fam_set(TR ? VD_FAM_X6_TR : VD_FAM_X6_TILE);
     hipLaunchKernelGGL((conv_x6_kernel<BM, BN, NT, NST, TERMS, MF, TR, PF>), dim3(mt * a.ntiles_n), dim3(NT), lds, s, a);
     return hipGetLastError();
 }

@@ -425,6 +425,7 @@ static hipError_t launch_x6_halo_pf(const ConvArgs& a0, hipStream_t s) {
     const int lds = x6_halo_lds<BN, NSB>(a);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const int mt = (a.M + 255) / 256;
+    vd_conv_fam_set(S2 ? VD_FAM_X6_HALO_S2 : VD_FAM_X6_HALO);
     hipLaunchKernelGGL((conv_x6_halo_kernel<BN, NSB, TR, S2, PF>), dim3(mt * a.ntiles_n), dim3(512), lds, s, a);
     return hipGetLastError();
 }

@@ -499,6 +499,7 @@ hipError_t launch_dual_x6(const ConvArgs& a0, hipStream_t s) {
     const int groups = (a.M + 15) / 16;
     int k = std::max(1, resident / (8 * nchunks));
     k = std::min(k, std::max(1, (groups + 63) / 64));
+    vd_conv_fam_set(VD_FAM_X6_DUAL);
     hipLaunchKernelGGL((conv1x1_x6_dual_kernel<KS, KS2, NTT>), dim3(8 * nchunks * k), dim3(512),
                        lds + (a.ymax ? 4 * a.B : 0), s, a, nchunks, groups);
     return hipGetLastError();
@@ -528,6 +529,7 @@ hipError_t launch_stream_x6(const ConvArgs& a, hipStream_t s) {
     const int groups = (a.M + 15) / 16;
     int k = std::max(1, resident / (8 * nchunks));
     k = std::min(k, std::max(1, (groups + 63) / 64));
+    vd_conv_fam_set(TAPS ? VD_FAM_X6_TAPS : VD_FAM_X6_STREAM);
     hipLaunchKernelGGL((conv1x1_x6_kernel<KS, NTT, ACT, RES, TERMS, TAPS, RL>), dim3(8 * nchunks * k), dim3(512),
                        lds + (a.ymax ? 4 * a.B : 0), s, a, nchunks, groups);
     return hipGetLastError();

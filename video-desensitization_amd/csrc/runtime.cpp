@@ -34,6 +34,11 @@ int vd_set_error(int code, const char* fmt, ...) {
     return code;
 }
 
+// the dispatch record (vd_common.h VdConvFam)
+static thread_local int g_conv_fam = VD_FAM_NONE;
+void vd_conv_fam_set(int fam) { g_conv_fam = fam; }
+int vd_conv_fam_get() { return g_conv_fam; }
+
 // ----------------------------------------------------------------------------
 // weights container
 // ----------------------------------------------------------------------------

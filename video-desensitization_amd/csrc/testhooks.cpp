@@ -289,4 +289,215 @@ int vdt_conv2d(vd_ctx* h, const float* x, int n, int xh, int xw, int cin, const 
     return VD_OK;
 }
 
+// ---- vdt_run_op: one op of a plan on whole buffers, through Ctx::run_ops ----
+// a host f32 image [frames][a.h][a.w][a.c] as a device buffer of the Act's element type
+static int op_upload(Ctx* ctx, Act& a, const float* host, int frames, bool f32) {
+    const size_t elems = (size_t)frames * a.h * a.w * a.c;
+    a.f32 = f32;
+    int rc = ctx->dalloc(&a.p, elems * (f32 ? 4 : 2));
+    if (rc) return rc;
+    if (f32) {
+        VD_CHECK_HIP(hipMemcpy(a.p, host, elems * 4, hipMemcpyHostToDevice));
+    } else {
+        std::vector<uint16_t> hb(elems);
+        for (size_t i = 0; i < elems; ++i) hb[i] = to_half(ctx->f16, host[i]);
+        VD_CHECK_HIP(hipMemcpy(a.p, hb.data(), elems * 2, hipMemcpyHostToDevice));
+    }
+    return VD_OK;
+}
+
+static int op_download(Ctx* ctx, const Act& a, float* host, int frames) {
+    const size_t elems = (size_t)frames * a.h * a.w * a.c;
+    if (a.f32) {
+        VD_CHECK_HIP(hipMemcpy(host, a.p, elems * 4, hipMemcpyDeviceToHost));
+    } else {
+        std::vector<uint16_t> hb(elems);
+        VD_CHECK_HIP(hipMemcpy(hb.data(), a.p, elems * 2, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < elems; ++i) host[i] = from_half(ctx->f16, hb[i]);
+    }
+    return VD_OK;
+}
+
+// per-frame range slots [frames] holding `init` (f32 bit patterns; NULL: zeros)
+static int op_slots(Ctx* ctx, Act& a, const float* init, int frames) {
+    std::vector<float> z(frames, 0.f);
+    int rc = ctx->dalloc((void**)&a.amax, (size_t)frames * 4);
+    if (rc) return rc;
+    VD_CHECK_HIP(hipMemcpy(a.amax, init ? init : z.data(), (size_t)frames * 4, hipMemcpyHostToDevice));
+    return VD_OK;
+}
+
+static int op_conv(Ctx* ctx, const float* w, const float* scale, const float* shift, int cin, int cout, int kh, int kw,
+                   int stride, int pad, int act, float slope, int* idx) {
+    Conv cv{};
+    cv.cin = cin; cv.cout = cout; cv.kh = kh; cv.kw = kw; cv.stride = stride; cv.pad = pad; cv.act = act;
+    cv.slope = slope;
+    std::vector<float> wv(w, w + (size_t)cout * cin * kh * kw), sc(scale, scale + cout), sh(shift, shift + cout);
+    int rc = ctx->upload_conv(cv, wv, sc, sh);
+    if (rc) return rc;
+    ctx->convs.push_back(cv);
+    *idx = (int)ctx->convs.size() - 1;
+    return VD_OK;
+}
+
+static int run_op_impl(Ctx* ctx, vdt_op* o) {
+    const bool f32 = ctx->f32;
+    const bool ranged = f32 && ctx->tune.f32_split == 2;
+    const int vec = f32 ? 4 : 8;
+    o->ranged = ranged ? 1 : 0;
+    o->family[0] = 0;
+    if (!o->x || !o->y || o->frames <= 0 || o->frames > ctx->cfg.max_batch || o->f0 < 0 || o->n <= 0 ||
+        o->f0 + o->n > o->frames)
+        return vd_set_error(VD_ERR_ARG, "vdt_run_op: buffers / frames [f0, f0 + n) within frames <= max_batch");
+    if (o->xh <= 0 || o->xw <= 0 || o->ldx <= 0 || o->yh <= 0 || o->yw <= 0 || o->ldy <= 0 || o->xcoff < 0 || o->ycoff < 0)
+        return vd_set_error(VD_ERR_ARG, "vdt_run_op: bad buffer shape");
+    if (o->y_is_x && (o->xh != o->yh || o->xw != o->yw || o->ldx != o->ldy))
+        return vd_set_error(VD_ERR_ARG, "vdt_run_op: y_is_x needs one buffer shape");
+    if (!f32 && !o->out16 && (o->y_is_x || o->r_is_y))
+        return vd_set_error(VD_ERR_ARG, "vdt_run_op: an f32 output cannot share a 16-bit buffer (out16 = 0)");
+    const bool conv = o->kind == VDT_OP_CONV;
+    if (!f32 && !o->out16 && !conv)
+        return vd_set_error(VD_ERR_ARG, "vdt_run_op: only convs write f32 outputs in a 16-bit context (out16 = 0)");
+    const bool has_res = conv && o->res_mode != VD_RES_NONE && (o->r_is_y || o->res);
+    if (!conv && (o->res || o->r_is_y || o->x2)) return vd_set_error(VD_ERR_ARG, "vdt_run_op: residual / x2 on a conv only");
+    if (ranged && (!o->xslots || !o->yslots)) return vd_set_error(VD_ERR_ARG, "vdt_run_op: range slot arrays");
+
+    Act ax{}, ay{}, ar{}, ax2{};
+    int rc;
+    ax.h = o->xh; ax.w = o->xw; ax.c = o->ldx;
+    if ((rc = op_upload(ctx, ax, o->x, o->frames, f32))) return rc;
+    if (ranged) {   // what the producers of the whole buffer would have left: max |x| of each frame
+        const size_t fe = (size_t)o->xh * o->xw * o->ldx;
+        std::vector<float> mx(o->frames, 0.f);
+        for (int b = 0; b < o->frames; ++b)
+            for (size_t i = 0; i < fe; ++i) mx[b] = std::max(mx[b], std::fabs(o->x[b * fe + i]));
+        if ((rc = op_slots(ctx, ax, mx.data(), o->frames))) return rc;
+    }
+    if (o->y_is_x) {
+        ay = ax;
+    } else {
+        ay.h = o->yh; ay.w = o->yw; ay.c = o->ldy;
+        if ((rc = op_upload(ctx, ay, o->y, o->frames, f32 || !o->out16))) return rc;
+        if (ranged && (rc = op_slots(ctx, ay, o->yslots, o->frames))) return rc;
+    }
+    if (has_res) {
+        if (o->r_is_y) {
+            if (o->res_up) return vd_set_error(VD_ERR_ARG, "vdt_run_op: r_is_y with res_up");
+            ar = ay;
+        } else {
+            ar.h = o->rh; ar.w = o->rw; ar.c = o->res_ld;
+            if (ar.h <= 0 || ar.w <= 0 || ar.c <= 0) return vd_set_error(VD_ERR_ARG, "vdt_run_op: bad residual shape");
+            if ((rc = op_upload(ctx, ar, o->res, o->frames, f32))) return rc;
+        }
+        const bool fits = o->res_up ? (ar.h >= (o->yh + 1) / 2 && ar.w >= (o->yw + 1) / 2) : (ar.h == o->yh && ar.w == o->yw);
+        if (!fits || o->res_coff < 0 || o->res_coff + o->cout > ar.c)
+            return vd_set_error(VD_ERR_ARG, "vdt_run_op: residual slice outside its buffer");
+    }
+
+    Net net;
+    if (conv) {
+        if (!o->w || !o->scale || !o->shift || o->cin <= 0 || o->cout <= 0 || o->kh <= 0 || o->kw <= 0 || o->stride <= 0 ||
+            o->pad < 0)
+            return vd_set_error(VD_ERR_ARG, "vdt_run_op: bad conv");
+        if (o->grp_co && (!f32 || o->grp_co < 0 || o->grp_ci <= 0 || o->cout % o->grp_co))
+            return vd_set_error(VD_ERR_ARG, "vdt_run_op: grouped convs are an fp32-plan form");
+        int ci = -1, c2 = -1;
+        if ((rc = op_conv(ctx, o->w, o->scale, o->shift, o->cin, o->cout, o->kh, o->kw, o->stride, o->pad, o->act,
+                          o->slope, &ci)))
+            return rc;
+        ctx->convs[ci].grp_co = o->grp_co;   // after the upload, as the plate net's yconv_group sets them
+        ctx->convs[ci].grp_ci = o->grp_co ? o->grp_ci : 0;
+        if (o->x2) {
+            if (!o->w2 || !o->scale2 || !o->shift2 || o->cin2 <= 0 || o->stride2 <= 0 || o->xh2 <= 0 || o->xw2 <= 0 ||
+                o->ldx2 <= 0 || o->xcoff || o->ycoff || has_res || o->grp_co)
+                return vd_set_error(VD_ERR_ARG, "vdt_run_op: bad second conv (plan form: no offsets, no residual)");
+            if ((rc = op_conv(ctx, o->w2, o->scale2, o->shift2, o->cin2, o->cout, 1, 1, o->stride2, 0, VD_ACT_NONE, 0.f, &c2)))
+                return rc;
+            ax2.h = o->xh2; ax2.w = o->xw2; ax2.c = o->ldx2;
+            if ((rc = op_upload(ctx, ax2, o->x2, o->frames, f32))) return rc;
+            if (ranged) {
+                const size_t fe = (size_t)o->xh2 * o->xw2 * o->ldx2;
+                std::vector<float> mx(o->frames, 0.f);
+                for (int b = 0; b < o->frames; ++b)
+                    for (size_t i = 0; i < fe; ++i) mx[b] = std::max(mx[b], std::fabs(o->x2[b * fe + i]));
+                if ((rc = op_slots(ctx, ax2, mx.data(), o->frames))) return rc;
+            }
+            rc = ctx->add_conv_dual(net, ci, ax, c2, ax2, ay);
+        } else {
+            rc = ctx->add_conv(net, ci, ax, o->xcoff, ay, o->ycoff, has_res ? &ar : nullptr, o->res_coff, o->res_mode,
+                               o->res_up);
+        }
+        if (rc) return rc;
+    } else if (o->kind == VDT_OP_MAXPOOL || o->kind == VDT_OP_UPSAMPLE) {
+        const bool pool = o->kind == VDT_OP_MAXPOOL;
+        if (o->ch <= 0 || (o->ch | o->ldx | o->xcoff | o->ldy | o->ycoff) % vec || o->xcoff + o->ch > o->ldx ||
+            o->ycoff + o->ch > o->ldy)
+            return vd_set_error(VD_ERR_ARG, "vdt_run_op: channel slices of whole %d-element vectors inside the buffers", vec);
+        if (pool ? (o->k <= 0 || o->s <= 0 || o->p < 0 || o->p >= o->k || o->xh + 2 * o->p < o->k ||
+                    o->xw + 2 * o->p < o->k || o->yh != (o->xh + 2 * o->p - o->k) / o->s + 1 ||
+                    o->yw != (o->xw + 2 * o->p - o->k) / o->s + 1)
+                 : (o->yh != 2 * o->xh || o->yw != 2 * o->xw))
+            return vd_set_error(VD_ERR_ARG, "vdt_run_op: pool / upsample output shape");
+        Op op{};
+        op.kind = pool ? OP_MAXPOOL : OP_UPSAMPLE;
+        op.x = ax; op.xcoff = o->xcoff;
+        op.y = ay; op.ycoff = o->ycoff;
+        op.ch = o->ch; op.k = o->k; op.s = o->s; op.p = o->p;
+        net.ops.push_back(op);
+    } else if (o->kind == VDT_OP_DWCONV) {
+        if (!o->w || !o->scale || !o->shift || o->cout <= 0 || o->cout % vec || o->ldx % vec || o->ldy % vec ||
+            (o->stride != 1 && o->stride != 2) || o->xcoff || o->ycoff || o->y_is_x)
+            return vd_set_error(VD_ERR_ARG, "vdt_run_op: bad depthwise conv (plan form: offsets 0, whole vectors)");
+        DwConv d;
+        d.c = o->cout; d.stride = o->stride; d.act = o->act; d.slope = o->slope;
+        std::vector<float> wt((size_t)9 * d.c);
+        for (int c = 0; c < d.c; ++c)
+            for (int t = 0; t < 9; ++t) wt[(size_t)t * d.c + c] = o->w[(size_t)c * 9 + t];
+        if (f32) {
+            if ((rc = ctx->dalloc(&d.w, wt.size() * 4))) return rc;
+            VD_CHECK_HIP(hipMemcpy(d.w, wt.data(), wt.size() * 4, hipMemcpyHostToDevice));
+        } else {
+            std::vector<uint16_t> hw(wt.size());
+            for (size_t i = 0; i < wt.size(); ++i) hw[i] = to_half(ctx->f16, wt[i]);
+            if ((rc = ctx->dalloc(&d.w, hw.size() * 2))) return rc;
+            VD_CHECK_HIP(hipMemcpy(d.w, hw.data(), hw.size() * 2, hipMemcpyHostToDevice));
+        }
+        if ((rc = ctx->dalloc((void**)&d.scale, d.c * 4)) || (rc = ctx->dalloc((void**)&d.shift, d.c * 4))) return rc;
+        VD_CHECK_HIP(hipMemcpy(d.scale, o->scale, d.c * 4, hipMemcpyHostToDevice));
+        VD_CHECK_HIP(hipMemcpy(d.shift, o->shift, d.c * 4, hipMemcpyHostToDevice));
+        ctx->dwconvs.push_back(d);
+        if ((rc = ctx->add_dwconv(net, (int)ctx->dwconvs.size() - 1, ax, ay))) return rc;
+    } else {
+        return vd_set_error(VD_ERR_ARG, "vdt_run_op: unknown op kind %d", o->kind);
+    }
+
+    vd_conv_fam_set(VD_FAM_NONE);
+    if ((rc = ctx->run_ops(net, 0, 1, o->f0, o->n))) return rc;
+    VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    if (conv) snprintf(o->family, sizeof o->family, "%s", vd_conv_fam_name(vd_conv_fam_get()));
+    if ((rc = op_download(ctx, ay, o->y, o->frames))) return rc;
+    if (ranged) {
+        VD_CHECK_HIP(hipMemcpy(o->xslots, ax.amax, (size_t)o->frames * 4, hipMemcpyDeviceToHost));
+        VD_CHECK_HIP(hipMemcpy(o->yslots, ay.amax, (size_t)o->frames * 4, hipMemcpyDeviceToHost));
+    }
+    return VD_OK;
+}
+
+int vdt_run_op(vd_ctx* h, vdt_op* o) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (!o) return vd_set_error(VD_ERR_ARG, "vdt_run_op: null op");
+    const size_t nalloc = ctx->allocs.size(), nconv = ctx->convs.size(), ndw = ctx->dwconvs.size();
+    const int rc = run_op_impl(ctx, o);
+    // release this call's temporaries; amax_snaps is keyed by conv index and its arrays are among the
+    // allocations freed here, so the temporary convs' entries go first
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->amax_snaps.erase(ctx->amax_snaps.lower_bound((int)nconv), ctx->amax_snaps.end());
+    for (size_t i = nalloc; i < ctx->allocs.size(); ++i) hipFree(ctx->allocs[i]);
+    ctx->allocs.resize(nalloc);
+    ctx->convs.resize(nconv);
+    ctx->dwconvs.resize(ndw);
+    return rc;
+}
+
 }  // extern "C"

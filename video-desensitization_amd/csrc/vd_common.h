@@ -388,6 +388,34 @@ struct JpegHuffArgs {
     unsigned long long* segbase;                // [n + 1] frame offsets in seg (exclusive scan; [n] = total)
 };
 
+// Dispatch record: the kernel family that took the calling thread's last conv, written by
+// each launcher where its choice is final and read back by the test hook vdt_run_op. Host
+// side only (runtime.cpp holds the thread_local): it changes no decision and no kernel
+// argument and is never read on the device.
+enum VdConvFam {
+    VD_FAM_NONE = 0,
+    VD_FAM_GEMM,          // conv.hip conv_igemm_kernel: the 16-bit plans' implicit GEMM, the exact-f32 MFMA form
+    VD_FAM_STREAM,        // conv1x1.hip streaming 1x1
+    VD_FAM_DUAL,          //   ... with the fused second 1x1 conv
+    VD_FAM_TAPS,          //   ... streaming taps
+    VD_FAM_BIG,           // conv_big.hip phased 256 x 256 tiles
+    VD_FAM_X6_TILE,       // conv_x6.hip GEMM tiles (LDS epilogue)
+    VD_FAM_X6_TR,         //   ... TR tiles (D^T accumulators, register epilogue)
+    VD_FAM_X6_HALO,       // conv_x6_halo.hip 3x3 stride 1 (dense or grouped)
+    VD_FAM_X6_HALO_S2,    //   ... stride 2 (phase halos)
+    VD_FAM_X6_STREAM,     // conv_x6_stream.hip streaming 1x1 slices
+    VD_FAM_X6_TAPS,       //   ... streaming taps
+    VD_FAM_X6_DUAL,       //   ... with the fused second 1x1 conv
+    VD_FAM_COUNT
+};
+static inline const char* vd_conv_fam_name(int f) {
+    static const char* const names[VD_FAM_COUNT] = {"", "gemm", "stream", "dual", "taps", "conv_big", "x6_tile", "x6_tr",
+                                                    "x6_halo", "x6_halo_s2", "x6_stream", "x6_taps", "x6_dual"};
+    return f >= 0 && f < VD_FAM_COUNT ? names[f] : "";
+}
+void vd_conv_fam_set(int fam);
+int vd_conv_fam_get();
+
 // ---- kernel launchers (one translation unit each) ----
 hipError_t vd_launch_jpeg_fdct(const JpegEncArgs& a, hipStream_t s);
 hipError_t vd_launch_jpeg_huff(const JpegHuffArgs& a, hipStream_t s);          // codes -> words, bit totals

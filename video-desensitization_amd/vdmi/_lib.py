@@ -82,8 +82,27 @@ class vd_nv12(ctypes.Structure):
                 ("frame_stride", ctypes.c_size_t), ("matrix", ctypes.c_int32), ("range", ctypes.c_int32)]
 
 
-# (name, restype, argtypes) for every symbol of include/vdmi.h
 _P, _I, _SZ, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float, ctypes.c_double
+VDT_OP_CONV, VDT_OP_MAXPOOL, VDT_OP_UPSAMPLE, VDT_OP_DWCONV = 0, 1, 2, 3
+_I32 = ctypes.c_int32
+
+
+class vdt_op(ctypes.Structure):
+    _fields_ = ([(k, _I32) for k in ("kind", "frames", "f0", "n")]
+                + [("x", _P)] + [(k, _I32) for k in ("xh", "xw", "ldx", "xcoff")]
+                + [("y", _P)] + [(k, _I32) for k in ("yh", "yw", "ldy", "ycoff")]
+                + [(k, _I32) for k in ("y_is_x", "r_is_y", "out16")]
+                + [("res", _P)] + [(k, _I32) for k in ("rh", "rw", "res_ld", "res_coff", "res_mode", "res_up")]
+                + [("x2", _P)] + [(k, _I32) for k in ("xh2", "xw2", "ldx2")]
+                + [(k, _I32) for k in ("cin", "cout", "kh", "kw", "stride", "pad", "act")] + [("slope", _F)]
+                + [("w", _P), ("scale", _P), ("shift", _P)]
+                + [("grp_co", _I32), ("grp_ci", _I32), ("cin2", _I32), ("stride2", _I32)]
+                + [("w2", _P), ("scale2", _P), ("shift2", _P)]
+                + [(k, _I32) for k in ("ch", "k", "s", "p")]
+                + [("xslots", _P), ("yslots", _P), ("ranged", _I32), ("family", ctypes.c_char * 32)])
+
+
+# (name, restype, argtypes) for every symbol of include/vdmi.h
 SIGNATURES = [
     ("vd_default_cfg", _I, [ctypes.POINTER(vd_cfg)]),
     ("vd_abi_version", _I, []),
@@ -150,6 +169,7 @@ SIGNATURES = [
     ("vdt_postprocess", _I, [_P, _P, _P, _I, _P, ctypes.POINTER(vd_boxes)]),
     ("vdt_conv2d", _I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _F, _P, _I, _P,
                         ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    ("vdt_run_op", _I, [_P, ctypes.POINTER(vdt_op)]),
     ("vdt_bottleneck", _I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     ("vdt_plate_raw", _I, [_P, _P, _I, _I, _I, _SZ, _I, _P, ctypes.POINTER(_I)]),
     ("vdt_plate_raw_tiles", _I, [_P, _P, _I, _I, _I, _SZ, _I, _P, ctypes.POINTER(_I)]),

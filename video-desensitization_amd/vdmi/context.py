@@ -1199,3 +1199,70 @@ class Context:
                                    ptr(shift), act, float(slope), ptr(r), res_mode, ptr(y), ctypes.byref(o1),
                                    ctypes.byref(o2)))
         return y
+
+    def run_op(self, kind, x, y, *, xcoff=0, ycoff=0, y_is_x=False, out16=True, f0=0, n=None,
+               w=None, scale=None, shift=None, stride=1, pad=0, act=0, slope=0.0, grp_co=0, grp_ci=0,
+               res=None, res_coff=0, res_mode=0, res_up=False, r_is_y=False,
+               x2=None, w2=None, scale2=None, shift2=None, stride2=1,
+               ch=0, k=0, s=0, p=0, yslots=None):
+        """vdt_run_op: one plan op ("conv" | "maxpool" | "upsample" | "dwconv") through the production
+        executor on whole NHWC buffers. x [frames,xh,xw,ldx] and y [frames,yh,yw,ldy] are f32 images of
+        the buffers (y: the prior contents; with y_is_x pass y=None, the output lies in x's buffer);
+        res [frames,rh,rw,res_ld] / x2 [frames,xh2,xw2,ldx2] likewise. Conv weights w [cout,cin,kh,kw]
+        (dwconv: [c,3,3] or [c,1,3,3]). Returns a dict: y (the y buffer after the op), family (the
+        dispatch record), and in the fp16-pair plan xslots / yslots [frames] (else None)."""
+        f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        x = f(x)
+        o = _lib.vdt_op()
+        o.kind = {"conv": _lib.VDT_OP_CONV, "maxpool": _lib.VDT_OP_MAXPOOL, "upsample": _lib.VDT_OP_UPSAMPLE,
+                  "dwconv": _lib.VDT_OP_DWCONV}[kind]
+        frames = x.shape[0]
+        o.frames, o.f0, o.n = frames, int(f0), int(frames - f0 if n is None else n)
+        o.x, (o.xh, o.xw, o.ldx), o.xcoff = ptr(x), x.shape[1:], int(xcoff)
+        yb = np.zeros_like(x) if y_is_x else f(y).copy()
+        assert yb.shape[0] == frames
+        o.y, (o.yh, o.yw, o.ldy), o.ycoff = ptr(yb), yb.shape[1:], int(ycoff)
+        o.y_is_x, o.r_is_y, o.out16 = int(bool(y_is_x)), int(bool(r_is_y)), int(bool(out16))
+        keep = [x, yb]
+        if res is not None:
+            res = f(res)
+            assert res.shape[0] == frames
+            o.res, (o.rh, o.rw, o.res_ld) = ptr(res), res.shape[1:]
+            keep.append(res)
+        o.res_coff, o.res_mode, o.res_up = int(res_coff), int(res_mode), int(bool(res_up))
+        if kind in ("conv", "dwconv"):
+            w = f(w)
+            if kind == "dwconv":
+                w = np.ascontiguousarray(w.reshape(w.shape[0], 3, 3))
+                o.cin = o.cout = w.shape[0]
+                o.kh = o.kw = 3
+                o.pad = 1
+            else:
+                o.cout, o.cin, o.kh, o.kw = w.shape
+                o.pad = int(pad)
+            cout = w.shape[0]
+            scale = f(np.ones(cout) if scale is None else scale)
+            shift = f(np.zeros(cout) if shift is None else shift)
+            assert scale.shape == (cout,) and shift.shape == (cout,)
+            o.w, o.scale, o.shift = ptr(w), ptr(scale), ptr(shift)
+            o.stride, o.act, o.slope = int(stride), int(act), float(slope)
+            o.grp_co, o.grp_ci = int(grp_co), int(grp_ci)
+            keep += [w, scale, shift]
+            if x2 is not None:
+                x2, w2 = f(x2), f(w2)
+                assert x2.shape[0] == frames and w2.shape[0] == cout and w2.shape[2:] == (1, 1)
+                scale2 = f(np.ones(cout) if scale2 is None else scale2)
+                shift2 = f(np.zeros(cout) if shift2 is None else shift2)
+                o.x2, (o.xh2, o.xw2, o.ldx2) = ptr(x2), x2.shape[1:]
+                o.cin2, o.stride2 = w2.shape[1], int(stride2)
+                o.w2, o.scale2, o.shift2 = ptr(w2), ptr(scale2), ptr(shift2)
+                keep += [x2, w2, scale2, shift2]
+        o.ch, o.k, o.s, o.p = int(ch), int(k), int(s), int(p)
+        xs = np.zeros(frames, np.float32)
+        ys = np.zeros(frames, np.float32) if yslots is None else f(yslots).copy()
+        assert ys.shape == (frames,)
+        o.xslots, o.yslots = ptr(xs), ptr(ys)
+        check(self._lib.vdt_run_op(self._h, ctypes.byref(o)))
+        del keep
+        ranged = bool(o.ranged)
+        return dict(y=yb, family=o.family.decode(), xslots=xs if ranged else None, yslots=ys if ranged else None)
