@@ -35,6 +35,8 @@
  *   vd_process_nv12 / vd_process_lead_nv12 / vd_mosaic_nv12 / vd_nv12_to_rgb: the same path on NV12 video surfaces (vd_nv12: what a
  *                                   decoder hands out and an encoder takes back; no reference equivalent: the
  *                                   reference works on the RGB frames of ffmpeg-split images)
+ *   vd_process_yuv420 / vd_mosaic_yuv420 / vd_smooth_yuv420 / vd_yuv420_to_rgb: the same path on 8-bit 4:2:0 frames in
+ *                                   any layout (vd_yuv420: I420 / YV12 from a software decoder, NV12, NV21)
  *   vd_read_boxes                <- the complete per-frame box lists the reference's
  *                                   loop iterates (combine_detect.py:241-249), past any cap
  *   vd_sync / vd_last_error / vd_destroy: runtime plumbing (no reference equivalent;
@@ -44,7 +46,7 @@
  *
  * Conventions: plain pointers and sizes only. Frames are uint8 RGB, HxWx3,
  * row pitch in bytes, frame i at base + i*h*pitch (the *_nv12 entries: NV12
- * surfaces described by a vd_nv12). `where` says whether a
+ * surfaces described by a vd_nv12; the *_yuv420 entries: a vd_yuv420). `where` says whether a
  * pointer is host (VD_HOST) or device (VD_DEVICE) memory of the context's GPU.
  * The caller owns frames and box arrays; the library owns weights, device
  * workspace and its stream. No pointer is retained past a call. Calls are
@@ -809,6 +811,68 @@ int vd_process_lead_nv12(vd_ctx* ctx, const vd_nv12* in, const vd_nv12* out, int
  * (host only: no context, no GPU): the routine the kernels' conversion function is compiled from. */
 int vd_nv12_to_rgb(const vd_nv12* in, int n, int h, int w, uint8_t* rgb, size_t rgb_pitch);
 
+/* ---- 8-bit 4:2:0 frames in any layout: I420, YV12, NV12, NV21 ----------------------
+ * A software decoder hands out planar 4:2:0 (yuv420p: a luma plane, a U plane and a V plane of
+ * (h/2) x (w/2) bytes each), a hardware decoder NV12. All that differs between the 8-bit 4:2:0
+ * layouts is where chroma sample (cy, cx) of U and of V lives, so one descriptor covers them:
+ *   layout   h and w are even. A frame is h luma rows of `pitch` bytes (pitch >= w) at the frame's
+ *            first byte, and
+ *              U(cy, cx) = frame[u_offset + cy*chroma_pitch + cx*chroma_step]
+ *              V(cy, cx) = frame[v_offset + cy*chroma_pitch + cx*chroma_step]
+ *            for cy in [0, h/2), cx in [0, w/2). chroma_step 1: two planes of h/2 rows of w/2 bytes
+ *            (I420: U first; YV12: V first). chroma_step 2: one plane of h/2 rows of w bytes of
+ *            interleaved pairs, |u_offset - v_offset| = 1 (NV12: v_offset = u_offset + 1; NV21:
+ *            u_offset = v_offset + 1). chroma_pitch >= (w/2)*chroma_step. Frame i lies at base +
+ *            i*frame_stride. The luma plane is bytes [0, (h-1)*pitch + w) of a frame, a chroma plane
+ *            [offset, offset + (h/2-1)*chroma_pitch + (w/2)*chroma_step) (interleaved: one plane from
+ *            min(u_offset, v_offset), w bytes a row); the planes of a frame must not overlap and,
+ *            when n > 1, must end within frame_stride. matrix and range of an output descriptor
+ *            are ignored.
+ *   N(S)     for a surface S, N(S) is the NV12 surface with the same Y, U and V samples.
+ *   results  nothing new is defined. Every list a *_yuv420 call returns or stores (detections,
+ *            vd_read_boxes, vd_read_held, vd_read_rescue, grown lists, the hold and rescue history)
+ *            is exactly what the *_nv12 call returns on N(in); for the output O, N(O) equals the
+ *            *_nv12 call's output on every sample of the picture. `in` and `out` are independent
+ *            descriptors and their layouts may differ (I420 in, NV12 out; NV12 in, YV12 out): a
+ *            blurring call thereby also converts between a decoder's and an encoder's layout.
+ *            Bytes outside [0, w) of luma rows and outside [0, (w/2)*chroma_step) of chroma rows,
+ *            and everything between planes and surfaces, are never written, and nothing outside
+ *            those ranges is read for a result. A descriptor with chroma_step 2 and v_offset =
+ *            u_offset + 1 and chroma_pitch = pitch gives byte for byte what the *_nv12 entry gives
+ *            (it runs the same kernels). A *_yuv420 call is a call of the context's one stream, as
+ *            an NV12 or RGB call of the same (h, w) is.
+ * Flags, box contracts, staging and capacity rules of vd_process_yuv420 / vd_mosaic_yuv420 /
+ * vd_smooth_yuv420 are those of vd_process_nv12 / vd_mosaic_nv12 / vd_smooth_nv12. Host frames are
+ * staged in their own layout, packed, at 1.5 B/px.
+ * VD_ERR_ARG, each checked before any state changes, the message naming the field: a NULL
+ * descriptor or base; odd or non-positive h or w; pitch < w; chroma_step outside {1, 2};
+ * chroma_pitch < (w/2)*chroma_step; chroma_step 2 with |u_offset - v_offset| != 1; planes that
+ * overlap each other or the luma plane (u_offset / v_offset); a plane that reaches past
+ * frame_stride when n > 1; unknown matrix or range (detection and conversion); device `out`
+ * overlapping device `in` (the whole extents of the n frames). VD_ERR_STATE, with the messages of
+ * vd_process_nv12: a VD_BLUR_GAUSSIAN context with cells off; a call that would run a tiled net;
+ * VD_PROC_MOSAIC in a look-ahead context. Not in this version, and without an entry point: a
+ * planar form of vd_process_lead_nv12 (the look-ahead ring stays NV12), 10-bit surfaces (P010,
+ * yuv420p10), 4:2:2 and 4:4:4. */
+typedef struct vd_yuv420 {
+    uint8_t* base;        /* first luma byte of frame 0 */
+    size_t   pitch;       /* luma row pitch, bytes */
+    size_t   u_offset;    /* from a frame's first luma byte to its first U sample */
+    size_t   v_offset;    /* ... to its first V sample */
+    size_t   chroma_pitch;/* pitch of a chroma row, bytes (planar: often pitch/2; interleaved: pitch) */
+    size_t   frame_stride;
+    int32_t  chroma_step; /* 1: planar (U and V planes of h/2 x w/2 bytes); 2: interleaved pairs */
+    int32_t  matrix, range;   /* VD_NV12_BT601|BT709, VD_NV12_LIMITED|FULL */
+} vd_yuv420;
+int vd_process_yuv420(vd_ctx* ctx, const vd_yuv420* in, const vd_yuv420* out, int n, int h, int w, int where, int flags,
+                      vd_boxes* faces, vd_boxes* plates);
+int vd_mosaic_yuv420(vd_ctx* ctx, const vd_yuv420* in, const vd_yuv420* out, int n, int h, int w, int where,
+                     const vd_boxes* boxes, int level);
+int vd_smooth_yuv420(vd_ctx* ctx, const vd_yuv420* in, const vd_yuv420* out, int n, int h, int w, int where,
+                     const vd_boxes* boxes, int level, int cells);
+/* vd_nv12_to_rgb for any layout: C(frame) of n frames (host only: no context, no GPU), by the same function. */
+int vd_yuv420_to_rgb(const vd_yuv420* in, int n, int h, int w, uint8_t* rgb, size_t rgb_pitch);
+
 /* ---- instrumentation (bench / profiling) ---------------------------------- */
 /* When enabled, every launch of kernel family `fam` is bracketed by HIP events
  * on the context stream; vd_timing_read returns the summed duration (ms), the
@@ -832,6 +896,8 @@ int vdt_letterbox_tiles(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w,
                         int where, float* out_nhwc, int cpad);
 /* vdt_letterbox for NV12 frames (vd_nv12), by the NV12 letterbox kernel of the product path. */
 int vdt_letterbox_nv12(vd_ctx* ctx, const vd_nv12* frames, int n, int h, int w, int where, float* out_nhwc, int cpad);
+/* ... for 4:2:0 frames in any layout (vd_yuv420), by the letterbox kernel the product path runs for that layout. */
+int vdt_letterbox_yuv420(vd_ctx* ctx, const vd_yuv420* frames, int n, int h, int w, int where, float* out_nhwc, int cpad);
 /* Raw head outputs after the forward, host f32: loc [n][A][4], conf logits [n][A][2],
  * landm [n][A][10], A = number of anchors. */
 int vdt_forward_heads(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w, size_t pitch,

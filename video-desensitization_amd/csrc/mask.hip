@@ -231,10 +231,12 @@ __device__ __forceinline__ void restore_y(const uint8_t* in_y, uint8_t* out_y, c
     out_y[(size_t)y * a.out_pitch + x] = in_y[(size_t)y * a.in_pitch + x];
 }
 
-__device__ __forceinline__ void restore_uv(const uint8_t* in_uv, uint8_t* out_uv, const MaskNv12Args& a, int cx, int cy) {
-    const size_t i = (size_t)cy * a.in_pitch + 2 * (size_t)cx, o = (size_t)cy * a.out_pitch + 2 * (size_t)cx;
-    out_uv[o] = in_uv[i];
-    out_uv[o + 1] = in_uv[i + 1];
+// U and V by their offsets and steps (include/vdmi.h at vd_yuv420; NV12: V the byte after U, step 2)
+struct ChromaPtrs { const uint8_t* in_u; const uint8_t* in_v; uint8_t* out_u; uint8_t* out_v; };
+__device__ __forceinline__ void restore_uv(const ChromaPtrs& c, const MaskNv12Args& a, int cx, int cy) {
+    const size_t i = (size_t)cy * a.in_cp + (size_t)cx * a.in_step, o = (size_t)cy * a.out_cp + (size_t)cx * a.out_step;
+    c.out_u[o] = c.in_u[i];
+    c.out_v[o] = c.in_v[i];
 }
 
 __global__ __launch_bounds__(THREADS) void mask_restore_nv12_kernel(MaskNv12Args a) {
@@ -245,9 +247,8 @@ __global__ __launch_bounds__(THREADS) void mask_restore_nv12_kernel(MaskNv12Args
     const int f = blockIdx.x / bands, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int by0 = (blockIdx.x % bands) * BR, by1 = min(by0 + BR, a.h);   // both even
     const uint8_t* in_y = a.in + (size_t)f * a.in_stride;
-    const uint8_t* in_uv = in_y + a.in_uv;
     uint8_t* out_y = a.out + (size_t)f * a.out_stride;
-    uint8_t* out_uv = out_y + a.out_uv;
+    const ChromaPtrs chroma{in_y + a.in_uv, in_y + a.in_v, out_y + a.out_uv, out_y + a.out_v};
     const int nb = min(max(a.m_cnt[f], 0), a.mcap);
     const int4* row = (const int4*)a.m_xy + (size_t)f * a.mcap;
     if (tid == 0) s_n = 0;
@@ -323,7 +324,7 @@ __global__ __launch_bounds__(THREADS) void mask_restore_nv12_kernel(MaskNv12Args
                                   (l.w < h.w && x >= (l.w >> 1) && x < ((h.w + 1) >> 1));
                     }
                 }
-                if (!hidden) restore_uv(in_uv, out_uv, a, x, cy);
+                if (!hidden) restore_uv(chroma, a, x, cy);
             }
         }
         return;
@@ -359,7 +360,7 @@ __global__ __launch_bounds__(THREADS) void mask_restore_nv12_kernel(MaskNv12Args
             const int cy = cy0 + (int)(p / cbw), cx = ccx1 + (int)(p % cbw);
             bool hidden = false;
             for (int q = 0; q < 4 && !hidden; ++q) hidden = in_some_ellipse(2 * cx + (q & 1), 2 * cy + (q >> 1), -1);
-            if (!hidden) restore_uv(in_uv, out_uv, a, cx, cy);
+            if (!hidden) restore_uv(chroma, a, cx, cy);
         }
     }
 }
@@ -389,7 +390,9 @@ hipError_t vd_launch_mask_restore(const MaskArgs& a, hipStream_t s) {
 
 hipError_t vd_launch_mask_restore_nv12(const MaskNv12Args& a, hipStream_t s) {
     if (a.n <= 0 || a.h <= 0 || a.w <= 0 || (a.h & 1) || (a.w & 1) || a.in_pitch < (size_t)a.w ||
-        a.out_pitch < (size_t)a.w || !a.in || !a.out || !a.m_cnt || !a.m_xy || a.mcap <= 0)
+        a.out_pitch < (size_t)a.w || !a.in || !a.out || !a.m_cnt || !a.m_xy || a.mcap <= 0 ||
+        (a.in_step != 1 && a.in_step != 2) || (a.out_step != 1 && a.out_step != 2) ||
+        a.in_cp < (size_t)(a.w / 2) * a.in_step || a.out_cp < (size_t)(a.w / 2) * a.out_step)
         return hipErrorInvalidValue;
     const long long blocks = (long long)((a.h + BR - 1) / BR) * a.n;
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;

@@ -290,13 +290,16 @@ struct Ctx {
     // flight: the letterbox argument builders hand it to the kernels, and `dframes` / `pitch` of the face
     // and plate paths are then the first luma byte and the planes' row pitch. Nv12Scope clears it.
     Nv12Src nv12_src{};
-    struct Nv12Dev { uint8_t* base; size_t pitch, uv, stride; };   // a batch of surfaces in device memory
-    // the caller's input surfaces on the device: as they are, or (host) staged packed in stage_in (1.5 B/px)
-    int nv12_in(const vd_nv12& d, int n, int h, int w, int where, Nv12Dev* o);
+    // a batch of 4:2:0 surfaces in device memory, in any layout of vd_yuv420 (nv12.h); the *_nv12 entries
+    // pass the NV12 descriptor through the same path
+    using Nv12Dev = Yuv420Dev;
+    // the caller's input surfaces on the device: as they are, or (host) staged packed in their own
+    // layout in stage_in (1.5 B/px)
+    int nv12_in(const vd_yuv420& d, int n, int h, int w, int where, Nv12Dev* o);
     // where the output pass writes: the caller's surfaces, or (host) packed surfaces in stage_out ...
-    int nv12_out_begin(const vd_nv12& d, int n, int h, int w, int where, Nv12Dev* o);
-    // ... copied back plane by plane, [0, w) of every row only (queued; the caller synchronises)
-    int nv12_out_finish(const vd_nv12& d, const Nv12Dev& o, int n, int h, int w, int where);
+    int nv12_out_begin(const vd_yuv420& d, int n, int h, int w, int where, Nv12Dev* o);
+    // ... copied back plane by plane, the picture's bytes of every row only (queued; the caller synchronises)
+    int nv12_out_finish(const vd_yuv420& d, const Nv12Dev& o, int n, int h, int w, int where);
     // the NV12 output pass behind the mask setting, what launch_shaped is to RGB frames: grow, the
     // rectangular pass (RECT_MOSAIC: nv12.hip, one launch; RECT_SMOOTH: smooth.hip, copy + box pass),
     // then under VD_MASK_ELLIPSE the restore of both planes; all family 1
@@ -485,8 +488,11 @@ struct Nv12Scope {
     Ctx* c;
     Nv12Scope(Ctx* ctx, const Ctx::Nv12Dev& d, int matrix, int range, bool on = true) : c(ctx) {
         if (!on) return;
-        c->nv12_src.on = 1;
-        c->nv12_src.uv_offset = d.uv;
+        c->nv12_src.on = d.nv12() ? 1 : 2;      // the NV12 letterbox kernels, or the ones for any layout
+        c->nv12_src.uv_offset = d.u;
+        c->nv12_src.v_offset = d.v;
+        c->nv12_src.cpitch = d.cpitch;
+        c->nv12_src.step = d.step;
         c->nv12_src.frame_stride = d.stride;
         c->nv12_src.k = vd_nv12_coef(matrix, range);
     }
@@ -494,6 +500,8 @@ struct Nv12Scope {
 };
 // the layout rules of a vd_nv12 descriptor for n frames of h x w (colour: matrix and range too); VD_ERR_ARG
 int vd_nv12_check(const char* who, const vd_nv12* d, int n, int h, int w, bool colour);
+// ... of a vd_yuv420 descriptor (the message names the field); extent: the bytes the n frames span
+int vd_yuv420_check(const char* who, const vd_yuv420* d, int n, int h, int w, bool colour, size_t* extent = nullptr);
 // bytes of source a letterbox reads per pixel of the frame rows it touches (timing work)
 static inline double vd_src_bpp(const Nv12Src& nv) { return nv.on ? 1.5 : 3.0; }
 

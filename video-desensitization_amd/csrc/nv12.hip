@@ -1,5 +1,6 @@
-// nv12.hip — out-of-place pixelation of NV12 frames, both planes in one launch; and, at the end, the
-// copy that packs surfaces into the look-ahead ring (vd_launch_nv12_pack).
+// nv12.hip — out-of-place pixelation of 8-bit 4:2:0 frames (NV12, and every layout of vd_yuv420), all
+// planes in one launch; and, at the end, the copy that packs NV12 surfaces into the look-ahead ring
+// (vd_launch_nv12_pack).
 //
 // Definition (include/vdmi.h at vd_nv12): for box b of the list being blurred, c = b clipped to
 // the frame and L = L(b) (vd_cell_level_hd of the box as stored): the luma plane takes the mosaic
@@ -24,6 +25,15 @@
 // Rows are moved with 16-B loads and stores when both surfaces are 16-B aligned throughout (base,
 // pitch, uv_offset, frame_stride), otherwise byte by byte; a row's tail past the last whole chunk
 // always goes byte by byte.
+// Other layouts (include/vdmi.h at vd_yuv420): the chroma plane stays one two-channel (h/2) x (w/2)
+// image whose sample is the pair u | v << 8 -- every box, cell and owner decision above is shared by
+// U and V -- and only the addresses differ: the gathers read U and V at their own offsets, chroma_step
+// apart, and in the band stream a lane moves 8 pairs between two interleaved surfaces and otherwise
+// 16 samples, as 16 B of the U plane and 16 B of the V plane on a planar side and 32 B of pairs on
+// an interleaved one, split and joined in registers. The steps of input and output are template
+// parameters, so no streaming loop branches on the layout; the NV12 -> NV12 instantiation is the
+// kernel as it was. 16-B accesses need base, both pitches, the plane offsets and the stride of
+// a surface aligned; otherwise, and in row tails, samples go byte by byte.
 // Past the capacities below -- a frame of more than NV12_LDS_BOXES boxes, a band that more than
 // NV12_BAND_BOXES boxes meet, slices of more than NV12_CELLS cells in a plane -- the band's samples
 // walk the whole list themselves (the generic path; same result).
@@ -75,9 +85,31 @@ __device__ __forceinline__ unsigned nv_src(const uint8_t* plane, size_t pitch, i
     return P ? (unsigned)p[0] | ((unsigned)p[1] << 8) : (unsigned)p[0];
 }
 
+// Layouts (include/vdmi.h at vd_yuv420). The kernel below is instantiated per chroma step of the
+// input (IS) and of the output (OS): 1 planar, 2 interleaved; SW: an interleaved side may hold V
+// first (NV21), told by its offsets. <2, 2, false> is the NV12 kernel. In every form a chroma
+// sample is the pair u | v << 8, so boxes, cells and owners are decided once for both channels;
+// only the addresses differ.
+// chroma sample (y, x) of a surface with U at pu, V at pv, rows of cp bytes, samples ST apart
+template <int ST>
+__device__ __forceinline__ unsigned yuv_src(const uint8_t* pu, const uint8_t* pv, size_t cp, int y, int x) {
+    const size_t o = (size_t)y * cp + (size_t)x * ST;
+    return (unsigned)pu[o] | ((unsigned)pv[o] << 8);
+}
+// two words of interleaved pairs (a0 b0 a1 b1 | a2 b2 a3 b3) <-> a word of a's and a word of b's
+__device__ __forceinline__ void yuv_split(uint32_t w0, uint32_t w1, uint32_t& a, uint32_t& b) {
+    a = (w0 & 0xFFu) | ((w0 >> 8) & 0xFF00u) | ((w1 & 0xFFu) << 16) | ((w1 & 0xFF0000u) << 8);
+    b = ((w0 >> 8) & 0xFFu) | ((w0 >> 16) & 0xFF00u) | ((w1 << 8) & 0xFF0000u) | (w1 & 0xFF000000u);
+}
+__device__ __forceinline__ void yuv_join(uint32_t a, uint32_t b, uint32_t& w0, uint32_t& w1) {
+    w0 = (a & 0xFFu) | ((b & 0xFFu) << 8) | ((a & 0xFF00u) << 8) | ((b & 0xFF00u) << 16);
+    w1 = ((a >> 16) & 0xFFu) | (((b >> 16) & 0xFFu) << 8) | ((a >> 24) << 16) | ((b >> 24) << 24);
+}
+__device__ __forceinline__ uint32_t yuv_swap16(uint32_t w) { return ((w & 0x00FF00FFu) << 8) | ((w >> 8) & 0x00FF00FFu); }
+
 __device__ __forceinline__ int up_index(int d, double f, int s) { return min((int)floor(VD_DMUL((double)d, f)), s - 1); }
 
-template <bool VEC>
+template <bool VEC, int IS, int OS, bool SW>
 __global__ __launch_bounds__(256) void nv12_mosaic_kernel(Nv12MosaicArgs a) {
     __shared__ int4 s_q[2][NV12_LDS_BOXES];
     __shared__ uint32_t s_sz[2][NV12_LDS_BOXES];
@@ -88,9 +120,15 @@ __global__ __launch_bounds__(256) void nv12_mosaic_kernel(Nv12MosaicArgs a) {
 
     const int f = blockIdx.y, band = blockIdx.x, tid = threadIdx.x;
     const uint8_t* in_y = a.in + (size_t)f * a.in_stride;
-    const uint8_t* in_uv = in_y + a.in_uv;
+    const uint8_t* in_u = in_y + a.in_uv;
+    const uint8_t* in_v = in_y + a.in_v;
     uint8_t* out_y = a.out + (size_t)f * a.out_stride;
-    uint8_t* out_uv = out_y + a.out_uv;
+    uint8_t* out_u = out_y + a.out_uv;
+    uint8_t* out_v = out_y + a.out_v;
+    // an interleaved side: its pairs start at the lower offset; V first there means swapped pairs
+    const bool isw = SW && IS == 2 && a.in_v < a.in_uv, osw = SW && OS == 2 && a.out_v < a.out_uv;
+    const uint8_t* in_c = isw ? in_v : in_u;
+    uint8_t* out_c = osw ? out_v : out_u;
     // the band's rows per plane: luma [r0[0], r1[0]), chroma [r0[1], r1[1]) (h is even)
     const int r0[2] = {band * NV12_ROWS, band * (NV12_ROWS / 2)};
     const int r1[2] = {min(r0[0] + NV12_ROWS, a.h), min(r0[1] + NV12_ROWS / 2, a.h / 2)};
@@ -172,7 +210,7 @@ __global__ __launch_bounds__(256) void nv12_mosaic_kernel(Nv12MosaicArgs a) {
             int x = q.x + min((int)floor(VD_DMUL((double)ux, down_factor(bw, sw))), bw - 1);
             int y = q.y + min((int)floor(VD_DMUL((double)uy, down_factor(bh, sh))), bh - 1);
             walk(P, b.idx, y, x);
-            if (P) s_cuv[e] = (uint16_t)nv_src<1>(in_uv, a.in_pitch, y, x);
+            if (P) s_cuv[e] = (uint16_t)yuv_src<IS>(in_u, in_v, a.in_cp, y, x);
             else s_cy[e] = (uint8_t)nv_src<0>(in_y, a.in_pitch, y, x);
         }
         __syncthreads();
@@ -184,7 +222,7 @@ __global__ __launch_bounds__(256) void nv12_mosaic_kernel(Nv12MosaicArgs a) {
             int yy = y, xx = x;
             walk(P, nb, yy, xx);
             if (yy == y && xx == x) return srcv;
-            return P ? nv_src<1>(in_uv, a.in_pitch, yy, xx) : nv_src<0>(in_y, a.in_pitch, yy, xx);
+            return P ? yuv_src<IS>(in_u, in_v, a.in_cp, yy, xx) : nv_src<0>(in_y, a.in_pitch, yy, xx);
         }
         for (int i = nband - 1; i >= 0; --i) {
             const BandBox& b = s_band[i];
@@ -208,52 +246,112 @@ __global__ __launch_bounds__(256) void nv12_mosaic_kernel(Nv12MosaicArgs a) {
         return false;
     };
 
-#pragma unroll
-    for (int P = 0; P < 2; ++P) {
-        const uint8_t* ip = P ? in_uv : in_y;
-        uint8_t* op = P ? out_uv : out_y;
-        const int EP = P ? 8 : 16;                   // samples per 16-B chunk
-        const int nch = (pw[P] + EP - 1) / EP;
-        const int rows = r1[P] - r0[P];
+    // luma: 16 samples per 16-B chunk
+    {
+        const int nch = (a.w + 15) / 16;
+        const int rows = r1[0] - r0[0];
         for (int c = tid; c < rows * nch; c += 256) {
             const int row = c / nch, ch = c - row * nch;
-            const int y = r0[P] + row, x0 = ch * EP, npx = min(EP, pw[P] - x0);
-            const uint8_t* src = ip + (size_t)y * a.in_pitch + (size_t)ch * 16;
-            uint8_t* dst = op + (size_t)y * a.out_pitch + (size_t)ch * 16;
-            const bool hit = (nband || generic) && touched(P, y, x0, x0 + npx);
-            if (VEC && npx == EP) {
+            const int y = r0[0] + row, x0 = ch * 16, npx = min(16, a.w - x0);
+            const uint8_t* src = in_y + (size_t)y * a.in_pitch + (size_t)ch * 16;
+            uint8_t* dst = out_y + (size_t)y * a.out_pitch + (size_t)ch * 16;
+            const bool hit = (nband || generic) && touched(0, y, x0, x0 + npx);
+            if (VEC && npx == 16) {
                 uint4 v = *(const uint4*)src;
                 if (hit) {
                     uint32_t wd[4] = {v.x, v.y, v.z, v.w};
-                    if (P) {
 #pragma unroll
-                        for (int i = 0; i < 8; ++i) {
-                            const unsigned sv = (wd[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
-                            const unsigned nv = sample(1, y, x0 + i, sv);
-                            wd[i >> 1] = (wd[i >> 1] & ~(0xFFFFu << (16 * (i & 1)))) | (nv << (16 * (i & 1)));
-                        }
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) {
-                            const unsigned sv = (wd[i >> 2] >> (8 * (i & 3))) & 0xFFu;
-                            const unsigned nv = sample(0, y, x0 + i, sv);
-                            wd[i >> 2] = (wd[i >> 2] & ~(0xFFu << (8 * (i & 3)))) | (nv << (8 * (i & 3)));
-                        }
+                    for (int i = 0; i < 16; ++i) {
+                        const unsigned sv = (wd[i >> 2] >> (8 * (i & 3))) & 0xFFu;
+                        const unsigned nv = sample(0, y, x0 + i, sv);
+                        wd[i >> 2] = (wd[i >> 2] & ~(0xFFu << (8 * (i & 3)))) | (nv << (8 * (i & 3)));
                     }
                     v = make_uint4(wd[0], wd[1], wd[2], wd[3]);
                 }
                 *(uint4*)dst = v;
             } else {
                 for (int i = 0; i < npx; ++i) {
-                    if (P) {
-                        unsigned sv = (unsigned)src[2 * i] | ((unsigned)src[2 * i + 1] << 8);
-                        if (hit) sv = sample(1, y, x0 + i, sv);
-                        dst[2 * i] = (uint8_t)sv; dst[2 * i + 1] = (uint8_t)(sv >> 8);
-                    } else {
-                        unsigned sv = src[i];
-                        if (hit) sv = sample(0, y, x0 + i, sv);
-                        dst[i] = (uint8_t)sv;
+                    unsigned sv = src[i];
+                    if (hit) sv = sample(0, y, x0 + i, sv);
+                    dst[i] = (uint8_t)sv;
+                }
+            }
+        }
+    }
+    // chroma: a lane moves 8 pairs (16 B in, 16 B out) between two interleaved surfaces, else 16
+    // samples (16 B of each plane on a planar side, 32 B of pairs on an interleaved one)
+    {
+        constexpr int EP = (IS == 2 && OS == 2) ? 8 : 16;
+        const int cw = a.w / 2;
+        const int nch = (cw + EP - 1) / EP;
+        const int rows = r1[1] - r0[1];
+        for (int c = tid; c < rows * nch; c += 256) {
+            const int row = c / nch, ch = c - row * nch;
+            const int y = r0[1] + row, x0 = ch * EP, npx = min(EP, cw - x0);
+            const bool hit = (nband || generic) && touched(1, y, x0, x0 + npx);
+            const size_t irow = (size_t)y * a.in_cp, orow = (size_t)y * a.out_cp;
+            if (VEC && npx == EP) {
+                if constexpr (IS == 2 && OS == 2) {
+                    uint4 v = *(const uint4*)(in_c + irow + (size_t)ch * 16);
+                    uint32_t wd[4] = {v.x, v.y, v.z, v.w};
+                    if (hit) {
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) {
+                            unsigned sv = (wd[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
+                            if (isw) sv = yuv_swap16(sv) & 0xFFFFu;
+                            unsigned nv = sample(1, y, x0 + i, sv);
+                            if (osw) nv = yuv_swap16(nv) & 0xFFFFu;
+                            wd[i >> 1] = (wd[i >> 1] & ~(0xFFFFu << (16 * (i & 1)))) | (nv << (16 * (i & 1)));
+                        }
+                    } else if (isw != osw) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) wd[i] = yuv_swap16(wd[i]);
                     }
+                    *(uint4*)(out_c + orow + (size_t)ch * 16) = make_uint4(wd[0], wd[1], wd[2], wd[3]);
+                } else {
+                    uint32_t uu[4], vv[4];
+                    if constexpr (IS == 1) {
+                        const uint4 p = *(const uint4*)(in_u + irow + (size_t)ch * 16);
+                        const uint4 q = *(const uint4*)(in_v + irow + (size_t)ch * 16);
+                        uu[0] = p.x; uu[1] = p.y; uu[2] = p.z; uu[3] = p.w;
+                        vv[0] = q.x; vv[1] = q.y; vv[2] = q.z; vv[3] = q.w;
+                    } else {
+                        const uint4 p = *(const uint4*)(in_c + irow + (size_t)ch * 32);
+                        const uint4 q = *(const uint4*)(in_c + irow + (size_t)ch * 32 + 16);
+                        uint32_t* fa = isw ? vv : uu;       // the pairs' first bytes
+                        uint32_t* fb = isw ? uu : vv;
+                        yuv_split(p.x, p.y, fa[0], fb[0]); yuv_split(p.z, p.w, fa[1], fb[1]);
+                        yuv_split(q.x, q.y, fa[2], fb[2]); yuv_split(q.z, q.w, fa[3], fb[3]);
+                    }
+                    if (hit) {
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) {
+                            const int sh = 8 * (i & 3);
+                            const unsigned sv = ((uu[i >> 2] >> sh) & 0xFFu) | (((vv[i >> 2] >> sh) & 0xFFu) << 8);
+                            const unsigned nv = sample(1, y, x0 + i, sv);
+                            uu[i >> 2] = (uu[i >> 2] & ~(0xFFu << sh)) | ((nv & 0xFFu) << sh);
+                            vv[i >> 2] = (vv[i >> 2] & ~(0xFFu << sh)) | ((nv >> 8) << sh);
+                        }
+                    }
+                    if constexpr (OS == 1) {
+                        *(uint4*)(out_u + orow + (size_t)ch * 16) = make_uint4(uu[0], uu[1], uu[2], uu[3]);
+                        *(uint4*)(out_v + orow + (size_t)ch * 16) = make_uint4(vv[0], vv[1], vv[2], vv[3]);
+                    } else {
+                        const uint32_t* fa = osw ? vv : uu;
+                        const uint32_t* fb = osw ? uu : vv;
+                        uint32_t o[8];
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) yuv_join(fa[i], fb[i], o[2 * i], o[2 * i + 1]);
+                        *(uint4*)(out_c + orow + (size_t)ch * 32) = make_uint4(o[0], o[1], o[2], o[3]);
+                        *(uint4*)(out_c + orow + (size_t)ch * 32 + 16) = make_uint4(o[4], o[5], o[6], o[7]);
+                    }
+                }
+            } else {
+                for (int i = 0; i < npx; ++i) {
+                    const size_t xi = (size_t)(x0 + i) * IS, xo = (size_t)(x0 + i) * OS;
+                    unsigned sv = (unsigned)in_u[irow + xi] | ((unsigned)in_v[irow + xi] << 8);
+                    if (hit) sv = sample(1, y, x0 + i, sv);
+                    out_u[orow + xo] = (uint8_t)sv; out_v[orow + xo] = (uint8_t)(sv >> 8);
                 }
             }
         }
@@ -308,15 +406,31 @@ hipError_t vd_launch_nv12_pack(const Nv12PackArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// every 16-B access of the vector paths is aligned: base, pitches, plane offsets and the stride
+static bool yuv_vec_ok(const Yuv420Dev& d) {
+    const uintptr_t m = (uintptr_t)d.base | d.pitch | d.cpitch | d.stride | (d.step == 2 ? d.c0() : (d.u | d.v));
+    return (m & 15) == 0;
+}
+
+template <int IS, int OS, bool SW>
+static void launch_mosaic(const Nv12MosaicArgs& a, bool vec, dim3 grid, hipStream_t s) {
+    if (vec) hipLaunchKernelGGL((nv12_mosaic_kernel<true, IS, OS, SW>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((nv12_mosaic_kernel<false, IS, OS, SW>), grid, dim3(256), 0, s, a);
+}
+
 hipError_t vd_launch_mosaic_nv12(const Nv12MosaicArgs& a, hipStream_t s) {
-    // sw | sh << 16 holds 16 bits per axis; even sizes only (the chroma plane is (h/2) x (w/2) pairs)
+    // sw | sh << 16 holds 16 bits per axis; even sizes only (the chroma planes are (h/2) x (w/2) samples)
     if (a.n <= 0 || a.h <= 0 || a.w <= 0 || (a.h & 1) || (a.w & 1) || a.h > 65534 || a.w > 65534 || a.level < 1 ||
-        a.in_pitch < (size_t)a.w || a.out_pitch < (size_t)a.w)
+        a.in_pitch < (size_t)a.w || a.out_pitch < (size_t)a.w || (a.in_step != 1 && a.in_step != 2) ||
+        (a.out_step != 1 && a.out_step != 2) || a.in_cp < (size_t)(a.w / 2) * a.in_step ||
+        a.out_cp < (size_t)(a.w / 2) * a.out_step)
         return hipErrorInvalidValue;
-    const uintptr_t align = (uintptr_t)a.in | (uintptr_t)a.out | a.in_pitch | a.in_uv | a.in_stride | a.out_pitch |
-                            a.out_uv | a.out_stride;
+    const bool vec = yuv_vec_ok(a.src()) && yuv_vec_ok(a.dst());
     const dim3 grid((a.h + NV12_ROWS - 1) / NV12_ROWS, a.n);
-    if ((align & 15) == 0) hipLaunchKernelGGL(nv12_mosaic_kernel<true>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(nv12_mosaic_kernel<false>, grid, dim3(256), 0, s, a);
+    if (a.nv12()) launch_mosaic<2, 2, false>(a, vec, grid, s);
+    else if (a.in_step == 2 && a.out_step == 2) launch_mosaic<2, 2, true>(a, vec, grid, s);
+    else if (a.in_step == 2) launch_mosaic<2, 1, true>(a, vec, grid, s);
+    else if (a.out_step == 2) launch_mosaic<1, 2, true>(a, vec, grid, s);
+    else launch_mosaic<1, 1, true>(a, vec, grid, s);
     return hipGetLastError();
 }

@@ -70,13 +70,42 @@ struct RowNv12 {
     }
 };
 
-template <bool NV> struct SrcOf { using Frame = FrameRgb; using Row = RowRgb; };
-template <> struct SrcOf<true> { using Frame = FrameNv12; using Row = RowNv12; };
+// Any 8-bit 4:2:0 layout (include/vdmi.h at vd_yuv420): a luma row, a U row and a V row, chroma
+// samples `step` bytes apart (1: planar I420 / YV12; 2: interleaved, where NV21 is simply the V
+// pointer one byte below the U pointer). The same conversion at the tap.
+struct FrameYuv {
+    const uint8_t* y; const uint8_t* u; const uint8_t* v; size_t pitch, cpitch; int step; Nv12Coef k;
+    __device__ __forceinline__ void get(int yy, int x, int o[3]) const {
+        const size_t c = (size_t)(yy >> 1) * cpitch + (size_t)(x >> 1) * step;
+        vd_nv12_rgb(k, y[(size_t)yy * pitch + x], u[c], v[c], o);
+    }
+    // A staged row is three 16-B aligned segments: the luma row (iw bytes), then two of iw / 2 bytes
+    // rounded up -- planar: the U row and the V row; interleaved: both hold the pair row (iw bytes
+    // from the lower of the two pointers, which 2 * roundup16(iw / 2) >= roundup16(iw) has room for).
+    // At most 2 * iw + 45 bytes, within LB_LDS_MAX whenever iw * 3 <= LB_LDS_MAX (iw >= 46), and
+    // iw < 46 is 137 bytes at most.
+    __device__ __forceinline__ static int luma_bytes(int iw) { return (iw + 15) / 16 * 16; }
+    __device__ __forceinline__ static int row_bytes(int iw) { return luma_bytes(iw) + 2 * ((iw / 2 + 15) / 16 * 16); }
+};
+struct RowYuv {
+    const uint8_t* L; int uo, vo, step; Nv12Coef k;
+    __device__ __forceinline__ void get(int x, int o[3]) const {
+        const int c = (x >> 1) * step;
+        vd_nv12_rgb(k, L[x], L[uo + c], L[vo + c], o);
+    }
+};
+
+template <int NV> struct SrcOf { using Frame = FrameRgb; using Row = RowRgb; };          // LetterboxArgs::nv.on
+template <> struct SrcOf<1> { using Frame = FrameNv12; using Row = RowNv12; };
+template <> struct SrcOf<2> { using Frame = FrameYuv; using Row = RowYuv; };
 
 // frame f of the batch
-template <bool NV>
+template <int NV>
 __device__ __forceinline__ typename SrcOf<NV>::Frame lb_frame(const LetterboxArgs& a, int f) {
-    if constexpr (NV) {
+    if constexpr (NV == 2) {
+        const uint8_t* b = a.src + (size_t)f * a.nv.frame_stride;
+        return FrameYuv{b, b + a.nv.uv_offset, b + a.nv.v_offset, a.pitch, a.nv.cpitch, a.nv.step, a.nv.k};
+    } else if constexpr (NV == 1) {
         const uint8_t* b = a.src + (size_t)f * a.nv.frame_stride;
         return FrameNv12{b, b + a.nv.uv_offset, a.pitch, a.nv.k};
     } else {
@@ -85,10 +114,19 @@ __device__ __forceinline__ typename SrcOf<NV>::Frame lb_frame(const LetterboxArg
 }
 
 // staged row k of `lrow` (rows of RS bytes)
-template <bool NV>
+template <int NV>
 __device__ __forceinline__ typename SrcOf<NV>::Row lb_row(const LetterboxArgs& a, const uint8_t* lrow, int k, int RS) {
-    if constexpr (NV) return RowNv12{lrow + k * RS, RS / 2, a.nv.k};
-    else return RowRgb{lrow + k * RS};
+    if constexpr (NV == 2) {
+        const int c0 = FrameYuv::luma_bytes(a.iw);
+        if (a.nv.step == 2)   // the pair row from the lower pointer: the other channel is its next byte
+            return RowYuv{lrow + k * RS, c0 + (a.nv.uv_offset > a.nv.v_offset ? 1 : 0),
+                          c0 + (a.nv.v_offset > a.nv.uv_offset ? 1 : 0), 2, a.nv.k};
+        return RowYuv{lrow + k * RS, c0, c0 + (RS - c0) / 2, 1, a.nv.k};
+    } else if constexpr (NV == 1) {
+        return RowNv12{lrow + k * RS, RS / 2, a.nv.k};
+    } else {
+        return RowRgb{lrow + k * RS};
+    }
 }
 
 // The 3 channels of resized pixel (y, x) (interpolation taps computed once).
@@ -179,7 +217,7 @@ __device__ __forceinline__ void lb_s2d_block(const LetterboxArgs& a, const Frame
     store_s2d(a, ((size_t)f * OH + Y) * OW + X, t);
 }
 
-template <bool NV>
+template <int NV>
 __global__ __launch_bounds__(256) void letterbox_s2d_kernel(LetterboxArgs a) {
     const int f = blockIdx.z;
     lb_s2d_block(a, lb_frame<NV>(a, f), f, blockIdx.y, blockIdx.x * 256 + threadIdx.x);
@@ -265,9 +303,20 @@ __device__ __forceinline__ void lb_stage_row(const LetterboxArgs& a, const Frame
     lb_stage(dst, img.y + (size_t)row * a.pitch, a.iw);
     lb_stage(dst + FrameNv12::row_bytes(a.iw) / 2, img.uv + (size_t)(row >> 1) * a.pitch, a.iw);   // iw is even
 }
+__device__ __forceinline__ void lb_stage_row(const LetterboxArgs& a, const FrameYuv& img, int row, uint8_t* dst) {
+    const int c0 = FrameYuv::luma_bytes(a.iw);
+    const size_t cr = (size_t)(row >> 1) * img.cpitch;
+    lb_stage(dst, img.y + (size_t)row * a.pitch, a.iw);
+    if (img.step == 2) {
+        lb_stage(dst + c0, (img.u < img.v ? img.u : img.v) + cr, a.iw);
+    } else {
+        lb_stage(dst + c0, img.u + cr, a.iw / 2);
+        lb_stage(dst + c0 + (FrameYuv::row_bytes(a.iw) - c0) / 2, img.v + cr, a.iw / 2);
+    }
+}
 
 // block row Y of canvas f from the frame at img; lrow: 4 staged rows of RS bytes
-template <bool NV>
+template <int NV>
 __device__ __forceinline__ void lb_s2d_lds_row(const LetterboxArgs& a, const typename SrcOf<NV>::Frame& img, int f, int Y,
                                                uint8_t* lrow) {
     const int OW = a.ow / 2 + 1, OH = a.oh / 2 + 1;
@@ -301,7 +350,7 @@ __device__ __forceinline__ void lb_s2d_lds_row(const LetterboxArgs& a, const typ
     }
 }
 
-template <bool NV>
+template <int NV>
 __global__ __launch_bounds__(256) void letterbox_s2d_lds_kernel(LetterboxArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lrow[];   // 4 staged rows of RS bytes
     const int f = blockIdx.y;
@@ -314,7 +363,7 @@ __global__ __launch_bounds__(256) void letterbox_s2d_lds_kernel(LetterboxArgs a)
 // canvas b; each source row is staged once and both canvases are written from it.
 // Per pixel the arithmetic is exactly letterbox_s2d_lds_kernel's for each canvas.
 // Block rows Y run over the union [y0, y0 + gridDim.x), X over [x0, x0 + nx).
-template <bool NV>
+template <int NV>
 __global__ __launch_bounds__(256) void letterbox_s2d_pair_kernel(LetterboxArgs a, LetterboxArgs b, int dY, int dX,
                                                                  int y0, int x0, int nx) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lrow[];
@@ -397,7 +446,7 @@ __device__ __forceinline__ void lb_nhwc_px(const LetterboxArgs& a, const Frame& 
     }
 }
 
-template <bool NV>
+template <int NV>
 __global__ __launch_bounds__(256) void letterbox_kernel(LetterboxArgs a) {
     const int f = blockIdx.z;
     lb_nhwc_px(a, lb_frame<NV>(a, f), f, blockIdx.y, blockIdx.x * 256 + threadIdx.x);
@@ -414,7 +463,7 @@ __global__ __launch_bounds__(256) void letterbox_kernel(LetterboxArgs a) {
 // (block) row Y of canvas i from the rectangle at img, in the canvas form a asks for
 __device__ __forceinline__ void lb_rect_row(const LetterboxArgs& a, const FrameRgb& img, int i, int Y, uint8_t* lrow) {
     if (a.s2d && a.iw * 3 <= LB_LDS_MAX) {
-        lb_s2d_lds_row<false>(a, img, i, Y, lrow);
+        lb_s2d_lds_row<0>(a, img, i, Y, lrow);
     } else if (a.s2d) {
         for (int X = threadIdx.x; X < a.ow / 2 + 1; X += 256) lb_s2d_block(a, img, i, Y, X);
     } else {
@@ -501,8 +550,17 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const T* x, int xh, int
 // bytes of one staged source row (RGB: the pixels; NV12: the luma row and its chroma row, 16-B aligned each);
 // at most LB_LDS_MAX whenever iw * 3 <= LB_LDS_MAX
 static size_t lb_row_bytes(const LetterboxArgs& a) {
+    if (a.nv.on == 2) return (size_t)((a.iw + 15) / 16 * 16) + 2 * (size_t)((a.iw / 2 + 15) / 16 * 16);   // FrameYuv::row_bytes
     return a.nv.on ? 2 * (size_t)((a.iw + 15) / 16 * 16) : (size_t)((a.iw * 3 + 15) / 16 * 16);
 }
+
+// a launch of kernel K<nv.on>(args...): the instantiation for the frames' pixel source
+#define LB_LAUNCH(K, on, grid, lds, s, ...)                                                          \
+    do {                                                                                             \
+        if ((on) == 2) hipLaunchKernelGGL(K<2>, grid, dim3(256), lds, s, __VA_ARGS__);               \
+        else if ((on) == 1) hipLaunchKernelGGL(K<1>, grid, dim3(256), lds, s, __VA_ARGS__);          \
+        else hipLaunchKernelGGL(K<0>, grid, dim3(256), lds, s, __VA_ARGS__);                         \
+    } while (0)
 
 bool vd_letterbox_pair_ok(const LetterboxArgs& a, const LetterboxArgs& b) {
     return a.s2d && b.s2d && a.src == b.src && a.n == b.n && a.nv.on == b.nv.on &&
@@ -547,9 +605,11 @@ hipError_t vd_launch_letterbox_pair(const LetterboxArgs& a0, const LetterboxArgs
     lb_set_gather(b);
     if (!vd_letterbox_pair_ok(a, b)) return hipErrorInvalidValue;
     static const bool attr = [] {
-        (void)hipFuncSetAttribute((const void*)letterbox_s2d_pair_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute((const void*)letterbox_s2d_pair_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   4 * LB_LDS_MAX);
-        (void)hipFuncSetAttribute((const void*)letterbox_s2d_pair_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute((const void*)letterbox_s2d_pair_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  4 * LB_LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)letterbox_s2d_pair_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   4 * LB_LDS_MAX);
         return true;
     }();
@@ -558,10 +618,7 @@ hipError_t vd_launch_letterbox_pair(const LetterboxArgs& a0, const LetterboxArgs
     const int y0 = std::min(0, dY), y1 = std::max(a.oh / 2 + 1, b.oh / 2 + 1 + dY);
     const int x0 = std::min(0, dX), x1 = std::max(a.ow / 2 + 1, b.ow / 2 + 1 + dX);
     const size_t lds = 4 * lb_row_bytes(a);
-    if (a.nv.on)
-        hipLaunchKernelGGL(letterbox_s2d_pair_kernel<true>, dim3(y1 - y0, a.n), dim3(256), lds, s, a, b, dY, dX, y0, x0, x1 - x0);
-    else
-        hipLaunchKernelGGL(letterbox_s2d_pair_kernel<false>, dim3(y1 - y0, a.n), dim3(256), lds, s, a, b, dY, dX, y0, x0, x1 - x0);
+    LB_LAUNCH(letterbox_s2d_pair_kernel, a.nv.on, dim3(y1 - y0, a.n), lds, s, a, b, dY, dX, y0, x0, x1 - x0);
     return hipGetLastError();
 }
 
@@ -570,28 +627,27 @@ hipError_t vd_launch_letterbox(const LetterboxArgs& a0, hipStream_t s) {
     lb_set_gather(a);
     if (a.s2d && a.iw * 3 <= LB_LDS_MAX) {
         static const bool attr = [] {
-            (void)hipFuncSetAttribute((const void*)letterbox_s2d_lds_kernel<false>,
+            (void)hipFuncSetAttribute((const void*)letterbox_s2d_lds_kernel<0>,
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 4 * LB_LDS_MAX);
-            (void)hipFuncSetAttribute((const void*)letterbox_s2d_lds_kernel<true>,
+            (void)hipFuncSetAttribute((const void*)letterbox_s2d_lds_kernel<1>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 4 * LB_LDS_MAX);
+            (void)hipFuncSetAttribute((const void*)letterbox_s2d_lds_kernel<2>,
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 4 * LB_LDS_MAX);
             return true;
         }();
         (void)attr;
         const size_t lds = 4 * lb_row_bytes(a);
         dim3 grid(a.oh / 2 + 1, a.n);
-        if (a.nv.on) hipLaunchKernelGGL(letterbox_s2d_lds_kernel<true>, grid, dim3(256), lds, s, a);
-        else hipLaunchKernelGGL(letterbox_s2d_lds_kernel<false>, grid, dim3(256), lds, s, a);
+        LB_LAUNCH(letterbox_s2d_lds_kernel, a.nv.on, grid, lds, s, a);
         return hipGetLastError();
     }
     if (a.s2d) {
         dim3 grid((a.ow / 2 + 1 + 255) / 256, a.oh / 2 + 1, a.n);
-        if (a.nv.on) hipLaunchKernelGGL(letterbox_s2d_kernel<true>, grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(letterbox_s2d_kernel<false>, grid, dim3(256), 0, s, a);
+        LB_LAUNCH(letterbox_s2d_kernel, a.nv.on, grid, 0, s, a);
         return hipGetLastError();
     }
     dim3 grid((a.ow + 255) / 256, a.oh, a.n);
-    if (a.nv.on) hipLaunchKernelGGL(letterbox_kernel<true>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(letterbox_kernel<false>, grid, dim3(256), 0, s, a);
+    LB_LAUNCH(letterbox_kernel, a.nv.on, grid, 0, s, a);
     return hipGetLastError();
 }
 

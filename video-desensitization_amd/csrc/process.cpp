@@ -174,8 +174,7 @@ int Ctx::launch_nv12_pass(const Nv12Dev& in, const Nv12Dev& out, int n, int h, i
         cnt1 = xy1 = nullptr; cap1 = 0;
     }
     Nv12MosaicArgs a{};
-    a.in = in.base; a.in_pitch = in.pitch; a.in_uv = in.uv; a.in_stride = in.stride;
-    a.out = out.base; a.out_pitch = out.pitch; a.out_uv = out.uv; a.out_stride = out.stride;
+    a.set(in, out);
     a.n = n; a.h = h; a.w = w;
     a.cnt0 = cnt0; a.xy0 = xy0; a.cap0 = cap0;
     a.cnt1 = cnt1; a.xy1 = xy1; a.cap1 = cap1;
@@ -196,8 +195,9 @@ int Ctx::launch_nv12_pass(const Nv12Dev& in, const Nv12Dev& out, int n, int h, i
     }
     if (!(shaped && mask_shape == VD_MASK_ELLIPSE)) return VD_OK;
     MaskNv12Args m{};
-    m.in = in.base; m.in_pitch = in.pitch; m.in_uv = in.uv; m.in_stride = in.stride;
-    m.out = out.base; m.out_pitch = out.pitch; m.out_uv = out.uv; m.out_stride = out.stride;
+    m.in = in.base; m.in_pitch = in.pitch; m.in_uv = in.u; m.in_v = in.v; m.in_cp = in.cpitch; m.in_stride = in.stride;
+    m.out = out.base; m.out_pitch = out.pitch; m.out_uv = out.u; m.out_v = out.v; m.out_cp = out.cpitch; m.out_stride = out.stride;
+    m.in_step = in.step; m.out_step = out.step;
     m.n = n; m.h = h; m.w = w;
     m.m_cnt = mask_last.m_cnt; m.m_xy = mask_last.m_xy; m.mcap = mask_last.mcap;
     t_begin(1, 0);               // as the RGB restore: its bytes follow from the boxes
@@ -329,7 +329,7 @@ struct LeadCall {
 // point), so the letterbox and the output launches differ; `in` / `out` / `pitch` are not used. Together
 // with a LeadCall (vd_process_lead_nv12) `out` describes the m emitted surfaces, NULL when m == 0.
 struct Nv12Call {
-    const vd_nv12* in; const vd_nv12* out;
+    const vd_yuv420* in; const vd_yuv420* out;   // any layout of vd_yuv420 (the *_nv12 entries: the NV12 one)
 };
 
 static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh, int fw, size_t pitch, int where,
@@ -539,38 +539,55 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
     return process_impl(ctx, in, out, n, fh, fw, pitch, where, flags, faces, plates, nullptr);
 }
 
-// ---- NV12 frames (include/vdmi.h at vd_nv12) ----
-// what every NV12 blurring call checks before anything changes: the descriptors, the one blur mode
-// without an NV12 pass (`pass` < 0: Ctx::nv12_cfg_pass), and (device) that the whole n * frame_stride
-// ranges do not overlap
-static int nv12_blur_check(Ctx* ctx, const char* who, const vd_nv12* in, const vd_nv12* out, int n, int fh, int fw,
-                           int where, bool host_in_place, int pass) {
-    int rc = vd_nv12_check(who, out, n, fh, fw, false);
-    if (rc) return rc;
+// ---- 4:2:0 frames (include/vdmi.h at vd_nv12 and vd_yuv420) ----
+// One path serves both families of entries. A *_nv12 entry checks the vd_nv12 it was given (its own
+// rules and messages) and goes on with the NV12 descriptor of the general form; a *_yuv420 entry
+// checks the vd_yuv420. extent: the bytes the n frames span, for the overlap rule.
+struct YuvDesc { vd_yuv420 d; size_t extent; };
+static int yuv_desc(const char* who, const vd_nv12* nv, const vd_yuv420* yu, bool nv_entry, int n, int fh, int fw,
+                    bool colour, YuvDesc* o) {
+    int rc;
+    if (nv_entry) {
+        if ((rc = vd_nv12_check(who, nv, n, fh, fw, colour))) return rc;
+        o->d = vd_yuv420_of_nv12(*nv);
+        o->extent = (size_t)n * nv->frame_stride;
+        return VD_OK;
+    }
+    if ((rc = vd_yuv420_check(who, yu, n, fh, fw, colour, &o->extent))) return rc;
+    o->d = *yu;
+    return VD_OK;
+}
+
+// what every blurring call checks before anything changes, after the descriptors: the one blur mode
+// without a 4:2:0 pass (`pass` < 0: Ctx::nv12_cfg_pass), and (device) that the frames' whole extents
+// do not overlap
+static int nv12_blur_check(const char* who, const YuvDesc& in, const YuvDesc& out, int where, bool host_in_place, int pass) {
     if (pass < 0)
         return vd_set_error(VD_ERR_STATE, "%s: the fixed-kernel Gaussian (blur_mode VD_BLUR_GAUSSIAN with cells off) has "
                             "no NV12 pass: set cells (vd_cells) for the scaled smooth blur", who);
-    if (in->base == out->base && !(host_in_place && where == VD_HOST))   // host frames are staged in separate buffers
+    if (in.d.base == out.d.base && !(host_in_place && where == VD_HOST))   // host frames are staged in separate buffers
         return vd_set_error(VD_ERR_ARG, "%s: out-of-place only (out must not overlap in)", who);
     if (where == VD_DEVICE) {
-        const uintptr_t a = (uintptr_t)in->base, b = (uintptr_t)out->base;
-        if (a < b + (size_t)n * out->frame_stride && b < a + (size_t)n * in->frame_stride)
+        const uintptr_t a = (uintptr_t)in.d.base, b = (uintptr_t)out.d.base;
+        if (a < b + out.extent && b < a + in.extent)
             return vd_set_error(VD_ERR_ARG, "%s: out-of-place only (out must not overlap in)", who);
     }
     return VD_OK;
 }
 
-int vd_process_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n, int fh, int fw, int where, int flags,
-                    vd_boxes* faces, vd_boxes* plates) {
-    Ctx* ctx = (Ctx*)h;
-    VD_ENTRY(ctx);
-    const char* who = "vd_process_nv12";
+static int process_420(Ctx* ctx, const char* who, bool nv_entry, const vd_nv12* nin, const vd_nv12* nout,
+                       const vd_yuv420* yin, const vd_yuv420* yout, int n, int fh, int fw, int where, int flags,
+                       vd_boxes* faces, vd_boxes* plates) {
     if (where != VD_HOST && where != VD_DEVICE) return vd_set_error(VD_ERR_ARG, "%s: bad where", who);
-    int rc = vd_nv12_check(who, in, n, fh, fw, true);
+    YuvDesc in{}, out{};
+    int rc = yuv_desc(who, nin, yin, nv_entry, n, fh, fw, true, &in);
     if (rc) return rc;
-    if (flags & VD_PROC_MOSAIC) {
-        if (!out) return vd_set_error(VD_ERR_ARG, "%s: MOSAIC needs an output descriptor", who);
-        if ((rc = nv12_blur_check(ctx, who, in, out, n, fh, fw, where, true, ctx->nv12_cfg_pass()))) return rc;
+    const bool blur = flags & VD_PROC_MOSAIC;
+    if (blur) {
+        if (!(nv_entry ? (const void*)nout : (const void*)yout))
+            return vd_set_error(VD_ERR_ARG, "%s: MOSAIC needs an output descriptor", who);
+        if ((rc = yuv_desc(who, nout, yout, nv_entry, n, fh, fw, false, &out))) return rc;
+        if ((rc = nv12_blur_check(who, in, out, where, true, ctx->nv12_cfg_pass()))) return rc;
     }
     if (((flags & VD_PROC_FACES) && ctx->faces_tiled()) || ((flags & VD_PROC_PLATES) && ctx->plates_tiled()))
         return vd_set_error(VD_ERR_STATE, "%s: tiled detection (vd_tiles) reads RGB frames only", who);
@@ -580,31 +597,48 @@ int vd_process_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n, int
     if (ctx->lead.pend)
         return vd_set_error(VD_ERR_STATE, "%s: %d frames are pending in the look-ahead ring (flush first)", who,
                             ctx->lead.pend);
-    const Nv12Call nv{in, out};
+    const Nv12Call nv{&in.d, blur ? &out.d : nullptr};
     return process_impl(ctx, nullptr, nullptr, n, fh, fw, 0, where, flags, faces, plates, nullptr, &nv);
 }
 
-// The stand-alone NV12 blurring calls: pass `pass` over the caller's surfaces and one box list, with
+int vd_process_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n, int fh, int fw, int where, int flags,
+                    vd_boxes* faces, vd_boxes* plates) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    return process_420(ctx, "vd_process_nv12", true, in, out, nullptr, nullptr, n, fh, fw, where, flags, faces, plates);
+}
+
+int vd_process_yuv420(vd_ctx* h, const vd_yuv420* in, const vd_yuv420* out, int n, int fh, int fw, int where, int flags,
+                      vd_boxes* faces, vd_boxes* plates) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    return process_420(ctx, "vd_process_yuv420", false, nullptr, nullptr, in, out, n, fh, fw, where, flags, faces, plates);
+}
+
+// The stand-alone blurring calls: pass `pass` over the caller's surfaces and one box list, with
 // blur_entry's staging, capacity and overlap rules.
-static int nv12_blur_entry(Ctx* ctx, const char* who, const vd_nv12* in, const vd_nv12* out, int n, int fh, int fw,
+static int nv12_blur_entry(Ctx* ctx, const char* who, bool nv_entry, const vd_nv12* nin, const vd_nv12* nout,
+                           const vd_yuv420* yin, const vd_yuv420* yout, int n, int fh, int fw,
                            int where, const vd_boxes* boxes, int pass, int level, int cells) {
     if (where != VD_HOST && where != VD_DEVICE) return vd_set_error(VD_ERR_ARG, "%s: bad where", who);
     if (!boxes) return vd_set_error(VD_ERR_ARG, "%s: null argument", who);
     if (level <= 0) return vd_set_error(VD_ERR_ARG, "%s: bad geometry", who);
-    int rc = vd_nv12_check(who, in, n, fh, fw, false);
+    YuvDesc in{}, out{};
+    int rc = yuv_desc(who, nin, yin, nv_entry, n, fh, fw, false, &in);
     if (rc) return rc;
-    if ((rc = nv12_blur_check(ctx, who, in, out, n, fh, fw, where, false, pass))) return rc;
+    if ((rc = yuv_desc(who, nout, yout, nv_entry, n, fh, fw, false, &out))) return rc;
+    if ((rc = nv12_blur_check(who, in, out, where, false, pass))) return rc;
     if (pass == Ctx::RECT_SMOOTH && (fh > 32768 || fw > 32768 || level > 32768))
         return vd_set_error(VD_ERR_ARG, "%s: the smooth blur needs h, w <= 32768 and level in [1, 32768] (got %d x %d, "
                             "level %d)", who, fw, fh, level);
     BoxListIn b;
     if ((rc = ctx->box_list_in(who, boxes, n, false, 0, &b))) return rc;
-    Ctx::Nv12Dev nin{}, nout{};
-    if ((rc = ctx->nv12_in(*in, n, fh, fw, where, &nin))) return rc;
-    if ((rc = ctx->nv12_out_begin(*out, n, fh, fw, where, &nout))) return rc;
-    if ((rc = ctx->launch_nv12_pass(nin, nout, n, fh, fw, b.cnt, b.xy, boxes->cap, nullptr, nullptr, 0, pass, level, cells)))
+    Ctx::Nv12Dev din{}, dout{};
+    if ((rc = ctx->nv12_in(in.d, n, fh, fw, where, &din))) return rc;
+    if ((rc = ctx->nv12_out_begin(out.d, n, fh, fw, where, &dout))) return rc;
+    if ((rc = ctx->launch_nv12_pass(din, dout, n, fh, fw, b.cnt, b.xy, boxes->cap, nullptr, nullptr, 0, pass, level, cells)))
         return rc;
-    if ((rc = ctx->nv12_out_finish(*out, nout, n, fh, fw, where))) return rc;
+    if ((rc = ctx->nv12_out_finish(out.d, dout, n, fh, fw, where))) return rc;
     if (where == VD_HOST || b.staged) VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // host results; staging reused
     return VD_OK;
 }
@@ -614,17 +648,43 @@ int vd_mosaic_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n, int 
     Ctx* ctx = (Ctx*)h;
     VD_ENTRY(ctx);
     // the context's blur mode chooses the pass, as it does for vd_process_nv12
-    return nv12_blur_entry(ctx, "vd_mosaic_nv12", in, out, n, fh, fw, where, boxes, ctx->nv12_cfg_pass(), level, ctx->cells);
+    return nv12_blur_entry(ctx, "vd_mosaic_nv12", true, in, out, nullptr, nullptr, n, fh, fw, where, boxes,
+                           ctx->nv12_cfg_pass(), level, ctx->cells);
+}
+
+int vd_mosaic_yuv420(vd_ctx* h, const vd_yuv420* in, const vd_yuv420* out, int n, int fh, int fw, int where,
+                     const vd_boxes* boxes, int level) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    return nv12_blur_entry(ctx, "vd_mosaic_yuv420", false, nullptr, nullptr, in, out, n, fh, fw, where, boxes,
+                           ctx->nv12_cfg_pass(), level, ctx->cells);
+}
+
+static int smooth_420_args(const char* who, int level, int cells) {
+    if (cells < VD_CELLS_MIN || cells > VD_CELLS_MAX)
+        return vd_set_error(VD_ERR_ARG, "%s: cells %d outside [%d, %d]", who, cells, VD_CELLS_MIN, VD_CELLS_MAX);
+    if (level < 1 || level > 32768) return vd_set_error(VD_ERR_ARG, "%s: level %d outside [1, 32768]", who, level);
+    return VD_OK;
 }
 
 int vd_smooth_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n, int fh, int fw, int where,
                    const vd_boxes* boxes, int level, int cells) {
     Ctx* ctx = (Ctx*)h;
     VD_ENTRY(ctx);
-    if (cells < VD_CELLS_MIN || cells > VD_CELLS_MAX)
-        return vd_set_error(VD_ERR_ARG, "vd_smooth_nv12: cells %d outside [%d, %d]", cells, VD_CELLS_MIN, VD_CELLS_MAX);
-    if (level < 1 || level > 32768) return vd_set_error(VD_ERR_ARG, "vd_smooth_nv12: level %d outside [1, 32768]", level);
-    return nv12_blur_entry(ctx, "vd_smooth_nv12", in, out, n, fh, fw, where, boxes, Ctx::RECT_SMOOTH, level, cells);
+    int rc = smooth_420_args("vd_smooth_nv12", level, cells);
+    if (rc) return rc;
+    return nv12_blur_entry(ctx, "vd_smooth_nv12", true, in, out, nullptr, nullptr, n, fh, fw, where, boxes,
+                           Ctx::RECT_SMOOTH, level, cells);
+}
+
+int vd_smooth_yuv420(vd_ctx* h, const vd_yuv420* in, const vd_yuv420* out, int n, int fh, int fw, int where,
+                     const vd_boxes* boxes, int level, int cells) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    int rc = smooth_420_args("vd_smooth_yuv420", level, cells);
+    if (rc) return rc;
+    return nv12_blur_entry(ctx, "vd_smooth_yuv420", false, nullptr, nullptr, in, out, n, fh, fw, where, boxes,
+                           Ctx::RECT_SMOOTH, level, cells);
 }
 
 int vd_process_lead(vd_ctx* h, const uint8_t* in, int n, int fh, int fw, size_t pitch, int where, int flags,
@@ -718,15 +778,17 @@ int vd_process_lead_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n
     }
     const LeadCall lc{flush, m};
     if (n > 0) {
-        const Nv12Call nv{in, out};
+        const vd_yuv420 yin = vd_yuv420_of_nv12(*in), yout = out ? vd_yuv420_of_nv12(*out) : vd_yuv420{};
+        const Nv12Call nv{&yin, out ? &yout : nullptr};
         rc = process_impl(ctx, nullptr, nullptr, n, fh, fw, 0, where, flags, faces, plates, &lc, &nv);
     } else {      // flush alone: the pending surfaces leave, no detection
         Ctx::Nv12Dev nin{}, nout{};
-        if ((rc = ctx->nv12_out_begin(*out, m, fh, fw, where, &nout))) return rc;
+        const vd_yuv420 yout = vd_yuv420_of_nv12(*out);
+        if ((rc = ctx->nv12_out_begin(yout, m, fh, fw, where, &nout))) return rc;
         if ((rc = ctx->lead_step(VD_LEAD_MODE_NV12, nullptr, nullptr, 0, fh, fw, 0, 1, nullptr, nullptr, 0, nullptr, nullptr,
                                  0, &nin, &nout)))
             return rc;
-        if ((rc = ctx->nv12_out_finish(*out, nout, m, fh, fw, where))) return rc;
+        if ((rc = ctx->nv12_out_finish(yout, nout, m, fh, fw, where))) return rc;
         if (where == VD_HOST) VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     }
     if (rc) return rc;

@@ -67,6 +67,15 @@
 //   smooth_box_nv12_kernel   grid (SLOTS, frames, 2 * PARTS): the plane is the upper half of z.
 // HBM traffic = read + write of every frame at 1.5 B/px + one read and one write of every clipped
 // box per plane. No scratch memory.
+//
+// Other 4:2:0 layouts (include/vdmi.h at vd_yuv420: planar I420 / YV12, NV21, or layouts that differ
+// between `in` and `out`). Sums, means and interpolation are per channel, so the pair pass equals the
+// C = 1, CHROMA pass run once over U and once over V with the chroma geometry and the luma-level owner
+// rule unchanged; STEP gives the bytes between a row's samples on either side (1 planar, 2 one channel
+// of interleaved pairs).
+//   smooth_box_yuv420_kernel  grid (SLOTS, frames, 3 * PARTS): luma, U, V.
+//   the copy                  between two layouts is the pixelation launch of nv12.hip with no lists:
+//                             it already streams every sample from the one layout into the other.
 #include "vd_kernel.h"
 #include "vdmi.h"
 
@@ -89,7 +98,7 @@ struct SmoothPlane {
 };
 
 struct SmoothArgs {
-    SmoothPlane pl[2];                               // RGB: pl[0] alone; NV12: luma, chroma
+    SmoothPlane pl[2];                               // RGB: pl[0] alone; NV12: luma, chroma; any 4:2:0 layout: luma, U (V: its own argument)
     int n, h, w;                                     // frames; the frame's (luma) size, which boxes are clipped to
     const int* cnt0; const int* xy0; int cap0;      // list 0 (faces)
     const int* cnt1; const int* xy1; int cap1;      // list 1 (plates, optional)
@@ -195,9 +204,13 @@ __device__ __forceinline__ uint32_t across(const uint32_t* mean, int j, int sw, 
 // The box pass of one plane with C bytes per sample (3: RGB, 1: luma, 2 and CHROMA: the U, V pairs).
 // s_cell: [sh][sw][C] sums, then Q8.4 means; s_beat: this plane's rectangles of the boxes beating
 // the box in hand.
-template <int C, bool CHROMA>
+// STEP (C == 1): the plane's samples lie in_step / out_step bytes apart in a row -- a U or V
+// plane of any 4:2:0 layout, planar or the one channel of interleaved pairs. Sums, means and
+// interpolation are per channel in every form, so the C = 1, CHROMA, STEP pass over U and then over
+// V computes exactly the bytes of the C = 2 pass over the pairs.
+template <int C, bool CHROMA, bool STEP = false>
 __device__ __forceinline__ void smooth_box_body(const SmoothArgs& a, const SmoothPlane& pl, int part, uint32_t* s_cell,
-                                                int4* s_beat, int& s_nbeat) {
+                                                int4* s_beat, int& s_nbeat, int in_step = 1, int out_step = 1) {
     const int fr = blockIdx.y, tid = threadIdx.x;
     int n0;
     const int nb = frame_boxes(a, fr, n0);
@@ -260,8 +273,9 @@ __device__ __forceinline__ void smooth_box_body(const SmoothArgs& a, const Smoot
         const int jA = part * sh / nparts, jB = (part + 1) * sh / nparts;
         int ya, yb;
         my_rows(max(jA - 1, 0) * f, min((jB + 1) * f, bh), ya, yb);
-        const uint8_t* sbox = src + (size_t)c.y * pl.in_pitch + (size_t)c.x * C;
-        uint8_t* dbox = dst + (size_t)c.y * pl.out_pitch + (size_t)c.x * C;
+        const size_t is = STEP ? (size_t)in_step : 1, os = STEP ? (size_t)out_step : 1;   // C == 1 with STEP
+        const uint8_t* sbox = src + (size_t)c.y * pl.in_pitch + (size_t)c.x * C * is;
+        uint8_t* dbox = dst + (size_t)c.y * pl.out_pitch + (size_t)c.x * C * os;
 
         // (2) cell sums
         if (ya < yb)
@@ -270,7 +284,7 @@ __device__ __forceinline__ void smooth_box_body(const SmoothArgs& a, const Smoot
                 for (int j = ya / f; j * f < yb; ++j) {
                     const int y0 = max(ya, j * f), y1 = min(yb, j * f + f);
                     uint32_t acc = 0;                      // at most 255 * 32768
-                    const uint8_t* p = sbox + (size_t)y0 * pl.in_pitch + bc;
+                    const uint8_t* p = sbox + (size_t)y0 * pl.in_pitch + bc * is;
 #pragma unroll 8
                     for (int y = y0; y < y1; ++y, p += pl.in_pitch) acc += *p;
                     const int e = (j * sw + i) * C + ch;
@@ -328,7 +342,7 @@ __device__ __forceinline__ void smooth_box_body(const SmoothArgs& a, const Smoot
                 };
                 cell_rows();
                 const int gx = c.x + x;
-                uint8_t* p = dbox + (size_t)ya * pl.out_pitch + bc;
+                uint8_t* p = dbox + (size_t)ya * pl.out_pitch + bc * os;
                 for (int y = ya; y < yb; ++y, p += pl.out_pitch) {
                     bool mine = true;
                     if (nbeat) {
@@ -384,6 +398,17 @@ __global__ __launch_bounds__(THREADS) void smooth_box_nv12_kernel(SmoothArgs a) 
     else smooth_box_body<2, true>(a, a.pl[1], blockIdx.z - PARTS, s_cell, s_beat, s_nbeat);
 }
 
+// the three planes of 4:2:0 frames in any layout: grid z = plane * PARTS + part. a.pl: luma and U, v: the V
+// plane; the chroma steps ride beside SmoothArgs, which the RGB and NV12 kernels take as they always did
+__global__ __launch_bounds__(THREADS) void smooth_box_yuv420_kernel(SmoothArgs a, SmoothPlane v, int in_step, int out_step) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_cell[];
+    __shared__ int4 s_beat[BEAT_CAP];
+    __shared__ int s_nbeat;
+    const int P = blockIdx.z / PARTS, part = blockIdx.z - P * PARTS;
+    if (P == 0) smooth_box_body<1, false>(a, a.pl[0], part, s_cell, s_beat, s_nbeat);
+    else smooth_box_body<1, true, true>(a, P == 1 ? a.pl[1] : v, part, s_cell, s_beat, s_nbeat, in_step, out_step);
+}
+
 }  // namespace
 
 // The cell sums of one box: cells^2 * 3 (RGB) or (cells + 1)^2 * 2 (a chroma grid, header) uint32,
@@ -423,11 +448,22 @@ hipError_t vd_launch_smooth(const uint8_t* in, uint8_t* out, int n, int h, int w
 hipError_t vd_launch_smooth_nv12(const Nv12MosaicArgs& v, int stage, hipStream_t s) {
     if (v.n <= 0 || v.h <= 0 || v.w <= 0 || (v.h & 1) || (v.w & 1) || v.h > 32768 || v.w > 32768 || v.level < 1 ||
         v.level > 32768 || v.cells < VD_CELLS_MIN || v.cells > VD_CELLS_MAX || v.n > 65535 ||
-        v.in_pitch < (size_t)v.w || v.out_pitch < (size_t)v.w || !v.in || !v.out)
+        v.in_pitch < (size_t)v.w || v.out_pitch < (size_t)v.w || !v.in || !v.out ||
+        (v.in_step != 1 && v.in_step != 2) || (v.out_step != 1 && v.out_step != 2) ||
+        v.in_cp < (size_t)(v.w / 2) * v.in_step || v.out_cp < (size_t)(v.w / 2) * v.out_step)
         return hipErrorInvalidValue;
+    if (!v.nv12() && stage == 0) {
+        // any other layout pair: the copy is the pixelation launch with no lists (nv12.hip), which
+        // moves [0, w) of the luma rows and every chroma sample from the one layout into the other
+        Nv12MosaicArgs c = v;
+        c.cnt0 = c.cnt1 = nullptr; c.xy0 = c.xy1 = nullptr; c.cap0 = c.cap1 = 0;
+        c.level = 1; c.cells = 0;
+        return vd_launch_mosaic_nv12(c, s);
+    }
     SmoothArgs a{};
     a.pl[0] = SmoothPlane{v.in, v.out, v.in_pitch, v.in_stride, v.out_pitch, v.out_stride};
-    a.pl[1] = SmoothPlane{v.in + v.in_uv, v.out + v.out_uv, v.in_pitch, v.in_stride, v.out_pitch, v.out_stride};
+    a.pl[1] = SmoothPlane{v.in + v.in_uv, v.out + v.out_uv, v.in_cp, v.in_stride, v.out_cp, v.out_stride};
+    const SmoothPlane vp{v.in + v.in_v, v.out + v.out_v, v.in_cp, v.in_stride, v.out_cp, v.out_stride};
     a.n = v.n; a.h = v.h; a.w = v.w;
     a.cnt0 = v.cnt0; a.xy0 = v.xy0; a.cap0 = v.cap0;
     a.cnt1 = v.cnt1; a.xy1 = v.xy1; a.cap1 = v.cap1;
@@ -436,8 +472,12 @@ hipError_t vd_launch_smooth_nv12(const Nv12MosaicArgs& v, int stage, hipStream_t
         const int by = (v.h + CR - 1) / CR, bc = (v.h / 2 + CR - 1) / CR;
         hipLaunchKernelGGL(smooth_copy_nv12_kernel, dim3(by + bc, v.n), dim3(THREADS), 0, s, a, by);
     } else if (v.cnt0 || v.cnt1) {
-        hipLaunchKernelGGL(smooth_box_nv12_kernel, dim3(SLOTS, v.n, 2 * PARTS), dim3(THREADS),
-                           vd_smooth_lds_bytes(v.cells), s, a);
+        if (v.nv12())
+            hipLaunchKernelGGL(smooth_box_nv12_kernel, dim3(SLOTS, v.n, 2 * PARTS), dim3(THREADS),
+                               vd_smooth_lds_bytes(v.cells), s, a);
+        else
+            hipLaunchKernelGGL(smooth_box_yuv420_kernel, dim3(SLOTS, v.n, 3 * PARTS), dim3(THREADS),
+                               vd_smooth_lds_bytes(v.cells), s, a, vp, v.in_step, v.out_step);
     }
     return hipGetLastError();
 }

@@ -240,7 +240,7 @@ int Ctx::lead_step(int mode, const uint8_t* din, uint8_t* dout, int n, int h, in
     }
     if (nv12) {
         // the same on surfaces: a ring slot is itself a valid surface for the NV12 passes
-        const Nv12Dev ring{(uint8_t*)lead_pix, (size_t)w, (size_t)h * w, fb};
+        const Nv12Dev ring = vd_yuv420_packed(lead_pix, h, w, 2, false);   // NV12, stride fb
         const int mr = std::min(m, pend), mi = m - mr;
         const int pass = nv12_cfg_pass();
         if (mr && (rc = launch_nv12_pass(ring, *nvout, mr, h, w, a.m_count, a.m_xy, a.mcap, nullptr, nullptr, 0, pass,
@@ -266,9 +266,9 @@ int Ctx::lead_step(int mode, const uint8_t* din, uint8_t* dout, int n, int h, in
         if (push > 0) {
             Nv12PackArgs p{};
             p.src = nvin->base + (size_t)mi * nvin->stride;
-            p.src_pitch = nvin->pitch; p.src_uv = nvin->uv; p.src_stride = nvin->stride;
+            p.src_pitch = nvin->pitch; p.src_uv = nvin->u; p.src_stride = nvin->stride;   // the look-ahead entry takes NV12 only
             p.dst = ring.base + (size_t)stay * fb;
-            p.dst_pitch = ring.pitch; p.dst_uv = ring.uv; p.dst_stride = ring.stride;
+            p.dst_pitch = ring.pitch; p.dst_uv = ring.u; p.dst_stride = ring.stride;
             p.n = push; p.h = h; p.w = w;
             t_begin(4, (double)push * fb * 2);
             hipError_t e = vd_launch_nv12_pack(p, stream);

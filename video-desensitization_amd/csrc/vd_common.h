@@ -462,11 +462,22 @@ hipError_t vd_launch_mosaic(const uint8_t* in, uint8_t* out, int n, int h, int w
                             const int* cnt1, const int* xy1, int cap1, int level, void* table,
                             int stages, int map_on, int cell_blocks, hipStream_t s, int cells = 0);   // stages: 1 = cell table, 2 = output pass, 4 = copy; cells: vd_cells (0 = off)
 size_t vd_mosaic_table_bytes(int n, int tcap);
-// Pixelation of NV12 frames (nv12.hip; include/vdmi.h at vd_nv12): one launch, both planes. Luma at
-// in / out, chroma at + *_uv bytes, frame f at + f * *_stride; lists as vd_launch_mosaic takes them.
+// Pixelation of 4:2:0 frames (nv12.hip; include/vdmi.h at vd_nv12 and vd_yuv420): one launch, every
+// plane. Luma at in / out, U at + *_uv bytes, V at + *_v, chroma rows of *_cp bytes, samples *_step
+// apart (NV12: *_v = *_uv + 1, *_cp = *_pitch, *_step = 2), frame f at + f * *_stride; lists as
+// vd_launch_mosaic takes them (none: the launch is the copy in -> out between the two layouts).
 struct Nv12MosaicArgs {
     const uint8_t* in; uint8_t* out; int n, h, w;
     size_t in_pitch, in_uv, in_stride, out_pitch, out_uv, out_stride;
+    size_t in_v, in_cp, out_v, out_cp;
+    int in_step, out_step;
+    void set(const Yuv420Dev& i, const Yuv420Dev& o) {
+        in = i.base; in_pitch = i.pitch; in_uv = i.u; in_v = i.v; in_cp = i.cpitch; in_stride = i.stride; in_step = i.step;
+        out = o.base; out_pitch = o.pitch; out_uv = o.u; out_v = o.v; out_cp = o.cpitch; out_stride = o.stride; out_step = o.step;
+    }
+    Yuv420Dev src() const { return Yuv420Dev{(uint8_t*)in, in_pitch, in_uv, in_v, in_cp, in_stride, in_step}; }
+    Yuv420Dev dst() const { return Yuv420Dev{out, out_pitch, out_uv, out_v, out_cp, out_stride, out_step}; }
+    bool nv12() const { return src().nv12() && dst().nv12(); }   // the NV12-only kernels serve the call
     const int* cnt0; const int* xy0; int cap0;
     const int* cnt1; const int* xy1; int cap1;
     int level, cells;
@@ -603,7 +614,9 @@ hipError_t vd_launch_mask_restore(const MaskArgs& a, hipStream_t s);
 // their chroma rectangles none of whose four luma pixels lies in an ellipse, are copied in -> out.
 struct MaskNv12Args {
     const uint8_t* in; uint8_t* out; int n, h, w;
-    size_t in_pitch, in_uv, in_stride, out_pitch, out_uv, out_stride;
+    size_t in_pitch, in_uv, in_stride, out_pitch, out_uv, out_stride;   // U at + *_uv, V at + *_v, as Nv12MosaicArgs
+    size_t in_v, in_cp, out_v, out_cp;
+    int in_step, out_step;
     const int* m_cnt; const int* m_xy; int mcap;     // the grown merged rows (MaskArgs)
 };
 hipError_t vd_launch_mask_restore_nv12(const MaskNv12Args& a, hipStream_t s);

@@ -105,6 +105,91 @@ def nv12_to_rgb(frames, matrix="bt709", range="limited", height=None):
     return out
 
 
+class Yuv420:
+    """8-bit 4:2:0 frames anywhere in one buffer (the C-ABI's vd_yuv420): padded pools, planes in
+    separate regions of one allocation, any of I420 / YV12 / NV12 / NV21. buffer: a uint8 numpy array
+    or torch tensor (host or device), contiguous, of any shape; offsets in bytes from its first byte,
+    which is frame 0's first luma byte. Luma rows are `pitch` bytes apart; U / V sample (cy, cx) of a
+    frame is at u_offset / v_offset + cy * chroma_pitch + cx * chroma_step; frame i starts at
+    i * frame_stride. n defaults to the number of whole frames the buffer holds."""
+
+    def __init__(self, buffer, h, w, pitch, u_offset, v_offset, chroma_pitch, chroma_step, frame_stride, n=None):
+        if _is_torch(buffer):
+            if buffer.dtype.__str__() != "torch.uint8" or not buffer.is_contiguous():
+                raise ValueError("Yuv420: a contiguous uint8 buffer is needed")
+            nbytes, self._ptr = buffer.numel(), buffer.data_ptr()
+            self.where = _lib.VD_DEVICE if buffer.is_cuda else _lib.VD_HOST
+        else:
+            if not (isinstance(buffer, np.ndarray) and buffer.dtype == np.uint8 and buffer.flags.c_contiguous):
+                raise ValueError("Yuv420: a contiguous uint8 buffer is needed")
+            nbytes, self._ptr, self.where = buffer.size, buffer.ctypes.data, _lib.VD_HOST
+        self.buffer = buffer
+        self.h, self.w, self.pitch = int(h), int(w), int(pitch)
+        self.u_offset, self.v_offset = int(u_offset), int(v_offset)
+        self.chroma_pitch, self.chroma_step, self.frame_stride = int(chroma_pitch), int(chroma_step), int(frame_stride)
+        if min(self.h, self.w, self.pitch, self.chroma_pitch, self.frame_stride) <= 0 or min(self.u_offset, self.v_offset) < 0:
+            raise ValueError("Yuv420: positive sizes and pitches, non-negative offsets needed")
+        crow = self.w // 2 * max(self.chroma_step, 1)
+        cend = max(self.u_offset, self.v_offset) + (max(self.h // 2, 1) - 1) * self.chroma_pitch + \
+            (crow if self.chroma_step != 2 else crow - 1)
+        end = max((self.h - 1) * self.pitch + self.w, cend)
+        fit = 0 if nbytes < end else 1 + (nbytes - end) // self.frame_stride
+        self.n = fit if n is None else int(n)
+        if self.n < 1 or self.n > fit:
+            raise ValueError(f"Yuv420: the buffer of {nbytes} bytes holds {fit} such frames (n = {self.n})")
+
+    def struct(self, matrix="bt709", range="limited"):
+        return _lib.vd_yuv420(self._ptr, self.pitch, self.u_offset, self.v_offset, self.chroma_pitch, self.frame_stride,
+                              self.chroma_step, _lib.NV12_MATRICES[matrix], _lib.NV12_RANGES[range])
+
+
+def _yuv420_arg(frames, layout="i420", height=None, matrix="bt709", range="limited", writable=False):
+    """4:2:0 frames -> (vd_yuv420, n, h, w, where, keepalive). frames: a Yuv420, or uint8 [n, rows, w]
+    (or [rows, w]) in `layout`: "nv12" / "nv21" as _nv12_arg takes NV12 frames (interleaved U, V /
+    V, U pairs); "i420" / "yv12" packed planar, rows = 3h/2: h luma rows, then the first chroma
+    plane's h/2 * w/2 bytes, then the second's (U then V / V then U) -- the array PyAV's
+    to_ndarray(format="yuv420p") gives. With height=h a taller rows = 3H/2 is a luma plane padded to H
+    rows (each chroma plane then holds H/2 rows)."""
+    if matrix not in _lib.NV12_MATRICES:
+        raise ValueError(f"matrix {matrix!r}: expected 'bt601' or 'bt709'")
+    if range not in _lib.NV12_RANGES:
+        raise ValueError(f"range {range!r}: expected 'limited' or 'full'")
+    if isinstance(frames, Yuv420):
+        return frames.struct(matrix, range), frames.n, frames.h, frames.w, frames.where, frames
+    if layout not in _lib.YUV420_LAYOUTS:
+        raise ValueError(f"layout {layout!r}: expected one of {_lib.YUV420_LAYOUTS}")
+    planar = layout in ("i420", "yv12")
+    if planar and _is_torch(frames) and frames.dim() in (2, 3) and frames.stride(-2) != frames.shape[-1]:
+        if writable:
+            raise ValueError("planar 4:2:0 out: rows of exactly w bytes are needed (or pass a Yuv420)")
+        frames = frames.contiguous()
+    d, n, h, w, where, keep = _nv12_arg(frames, height, matrix, range, writable)
+    first, second = d.uv_offset, d.uv_offset + 1
+    cpitch, step = d.pitch, 2
+    if planar:
+        if w % 2 or (d.uv_offset // d.pitch) % 2:
+            raise ValueError("planar 4:2:0 frames: an even width and an even (padded) luma height are needed")
+        cpitch, step = w // 2, 1
+        second = first + (d.uv_offset // d.pitch // 2) * cpitch
+    u, v = (first, second) if layout in ("i420", "nv12") else (second, first)
+    y = _lib.vd_yuv420(d.base, d.pitch, u, v, cpitch, d.frame_stride, step, d.matrix, d.range)
+    return y, n, h, w, where, keep
+
+
+def yuv420_to_rgb(frames, layout="i420", matrix="bt709", range="limited", height=None):
+    """vd_yuv420_to_rgb (host only, no GPU: the routine the kernels' conversion is compiled from): host
+    4:2:0 frames in any layout (the forms of Context.process_yuv420) -> uint8 [n, h, w, 3]."""
+    if _is_torch(frames):
+        frames = frames.cpu()
+    d, n, h, w, where, keep = _yuv420_arg(frames, layout, height, matrix, range)
+    if where != _lib.VD_HOST:
+        raise ValueError("yuv420_to_rgb() converts host frames")
+    out = np.empty((n, max(h, 0), max(w, 0), 3), np.uint8)
+    check(_lib.load().vd_yuv420_to_rgb(ctypes.byref(d), n, h, w, ptr(out), w * 3))
+    del keep
+    return out
+
+
 def jpeg_info(data):
     """(h, w, components) of a baseline JPEG (host-only parse, no GPU). A bytes object is
     parsed in place (its own buffer: no copy -- a 2.4-MB frame copied under the GIL for every
@@ -613,6 +698,99 @@ class Context:
         d, n, h, w, where, keep = _nv12_arg(frames, height, matrix, range)
         out = np.zeros((n, self.cfg.input_h, self.cfg.input_w, cpad), np.float32)
         check(self._lib.vdt_letterbox_nv12(self._h, ctypes.byref(d), n, h, w, where, ptr(out), cpad))
+        del keep
+        return out
+
+    # -- 4:2:0 frames in any layout (I420, YV12, NV12, NV21) ------------------------------
+    @staticmethod
+    def _yuv420_out(frames, geo, out, out_layout, height):
+        """The output surfaces of a 4:2:0 blurring call: `out` (an array in out_layout, or a Yuv420),
+        or new packed frames [n, 3h/2, w] in out_layout where the input lives -> (out, vd_yuv420, geo, keep)."""
+        n, h, w, where = geo
+        if out is None:
+            src = frames.buffer if isinstance(frames, Yuv420) else frames
+            if _is_torch(src):
+                import torch
+                out = torch.empty((n, h // 2 * 3, w), dtype=torch.uint8, device=src.device)
+            else:
+                out = np.empty((n, h // 2 * 3, w), np.uint8)
+            height = None
+        d, on, oh, ow, owhere, keep = _yuv420_arg(out, out_layout, height, writable=True)
+        return out, d, (on, oh, ow, owhere), keep
+
+    def process_yuv420(self, frames, out=None, faces=None, plates=None, flags=None, layout="i420", out_layout=None,
+                       matrix="bt709", range="limited", height=None):
+        """vd_process_yuv420: process_nv12() on 8-bit 4:2:0 frames in any layout -- layout / out_layout
+        in "i420", "yv12", "nv12", "nv21" (out_layout defaults to layout), frames uint8 [n, 3h/2, w]
+        (_yuv420_arg) or a Yuv420. Lists are exactly process_nv12()'s on the NV12 frames with the same
+        samples, and so is every sample of `out`; in and out layouts may differ. max_batch, hold,
+        rescue, mask and cells act as in process_nv12(). -> (out, faces, plates)."""
+        d, n, h, w, where, keep = _yuv420_arg(frames, layout, height, matrix, range)
+        if flags is None:
+            flags = _lib.VD_PROC_FACES | _lib.VD_PROC_MOSAIC
+        od = None
+        if flags & _lib.VD_PROC_MOSAIC:
+            out, od, geo, okeep = self._yuv420_out(frames, (n, h, w, where), out, out_layout or layout, height)
+            if geo != (n, h, w, where):
+                raise ValueError("out must hold 4:2:0 frames of the input's n, h, w in the same memory (host / device)")
+        fs = ps = None
+        auto_f, auto_p = faces is None, plates is None
+        if flags & _lib.VD_PROC_FACES:
+            faces = self._boxes(faces, n)
+            fs = faces.struct()
+        if flags & _lib.VD_PROC_PLATES:
+            plates = self._boxes(plates, n)
+            ps = plates.struct()
+        check(self._lib.vd_process_yuv420(self._h, ctypes.byref(d), ctypes.byref(od) if od is not None else None, n, h, w,
+                                          where, flags, ctypes.byref(fs) if fs is not None else None,
+                                          ctypes.byref(ps) if ps is not None else None))
+        if flags & _lib.VD_PROC_FACES:
+            faces = self._complete(faces, _lib.VD_NET_RETINAFACE, auto_f)
+        if flags & _lib.VD_PROC_PLATES:
+            plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
+        return out, faces, plates
+
+    def _yuv420_blur(self, fn, frames, boxes_xyxy, counts, out, layout, out_layout, height, *tail):
+        """What mosaic_yuv420() / smooth_yuv420() share: fn(ctx, in, out, n, h, w, where, boxes, *tail)."""
+        d, n, h, w, where, keep = _yuv420_arg(frames, layout, height)
+        if isinstance(boxes_xyxy, (_lib.HostBoxes, DeviceBoxes)):
+            s = boxes_xyxy.struct()
+            bkeep = None
+        else:
+            xy = np.ascontiguousarray(boxes_xyxy, np.int32).reshape(n, -1, 4)
+            cnt = np.ascontiguousarray(counts if counts is not None else np.full(n, xy.shape[1]), np.int32)
+            cap = max(1, xy.shape[1])
+            if xy.shape[1] == 0:
+                xy = np.zeros((n, 1, 4), np.int32)
+            s = _lib.vd_boxes(cap, _lib.VD_HOST, ptr(cnt), ptr(xy), None, None, None)
+            bkeep = (xy, cnt)
+        out, od, geo, okeep = self._yuv420_out(frames, (n, h, w, where), out, out_layout or layout, height)
+        if geo != (n, h, w, where):
+            raise ValueError("out must hold 4:2:0 frames of the input's n, h, w in the same memory (host / device)")
+        check(fn(self._h, ctypes.byref(d), ctypes.byref(od), n, h, w, where, ctypes.byref(s), *tail))
+        del keep, bkeep, okeep
+        return out
+
+    def mosaic_yuv420(self, frames, boxes_xyxy, counts=None, level=None, out=None, layout="i420", out_layout=None,
+                      height=None):
+        """vd_mosaic_yuv420: mosaic_nv12() on 4:2:0 frames in any layout, in and out layouts independent."""
+        return self._yuv420_blur(self._lib.vd_mosaic_yuv420, frames, boxes_xyxy, counts, out, layout, out_layout, height,
+                                 int(level or self.cfg.mosaic_level))
+
+    def smooth_yuv420(self, frames, boxes_xyxy, counts=None, level=None, cells=None, out=None, layout="i420",
+                      out_layout=None, height=None):
+        """vd_smooth_yuv420: smooth_nv12() on 4:2:0 frames in any layout, in and out layouts independent."""
+        cells = _lib.check_cells(self.cells if cells is None else cells)
+        if cells == 0:
+            raise ValueError("smooth_yuv420() needs cells in 2 .. 64 (the context's setting is 0: off)")
+        return self._yuv420_blur(self._lib.vd_smooth_yuv420, frames, boxes_xyxy, counts, out, layout, out_layout, height,
+                                 int(level or self.cfg.mosaic_level), cells)
+
+    def letterbox_yuv420(self, frames, cpad=4, layout="i420", matrix="bt709", range="limited", height=None):
+        """vdt_letterbox_yuv420: the face canvas of 4:2:0 frames by the product path's kernel for the layout."""
+        d, n, h, w, where, keep = _yuv420_arg(frames, layout, height, matrix, range)
+        out = np.zeros((n, self.cfg.input_h, self.cfg.input_w, cpad), np.float32)
+        check(self._lib.vdt_letterbox_yuv420(self._h, ctypes.byref(d), n, h, w, where, ptr(out), cpad))
         del keep
         return out
 
