@@ -902,6 +902,14 @@ int vdt_letterbox_yuv420(vd_ctx* ctx, const vd_yuv420* frames, int n, int h, int
  * landm [n][A][10], A = number of anchors. */
 int vdt_forward_heads(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w, size_t pitch,
                       int where, float* loc, float* conf, float* landm);
+/* Letterbox bands (option face_bands). Host arithmetic only, no context: for a canvas of canvas_h
+ * rows with image rows [top, top + nh) and left margin `left`, per band op k (0 the fused stem +
+ * pool, 1-3 layer1.0-2) out[k] = {first row past the top band rows, first bottom band row,
+ * tile rows, lo, hi}: tile rows [0, lo) and [hi, tile rows) are band tiles (none: lo 0, hi = tile rows). */
+int vdt_face_band_rows(int canvas_h, int top, int nh, int left, int32_t out[4][5]);
+/* The last face forward of the context: out[k] = {lo, hi, tile rows, frames whose tag matched (band
+ * tiles left alone), frames whose tag did not}; all zero for a forward that ran without bands. */
+int vdt_face_band_stats(vd_ctx* ctx, int32_t out[4][5]);
 /* Post-processing only (decode, score, threshold, NMS, correction, int()) on
  * caller-provided host head outputs; img_hw = [n][2] source sizes. */
 int vdt_postprocess(vd_ctx* ctx, const float* loc, const float* conf, int n,

@@ -22,9 +22,9 @@ LIB = os.path.join(HERE, "vdmi", "libvdmi.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("VD_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = ["conv.hip", "conv1x1.hip", "conv_big.hip", "pre.hip", "post.hip", "hold.hip", "lead.hip", "rescue.hip", "mosaic.hip", "nv12.hip", "blur.hip", "smooth.hip", "mask.hip", "tiles.hip", "block.hip", "block32.hip", "block.cpp",
+SOURCES = ["conv.hip", "conv1x1.hip", "conv_big.hip", "pre.hip", "post.hip", "hold.hip", "lead.hip", "rescue.hip", "mosaic.hip", "nv12.hip", "blur.hip", "smooth.hip", "mask.hip", "tiles.hip", "block.hip", "block32.hip", "bands.hip", "block.cpp",
            "chain.hip", "chain32.hip", "stem.hip", "dwconv.hip", "conv_x6.hip", "conv_x6_halo.hip", "conv_x6_stream.hip", "jpeg.hip", "jpeg_dec.hip", "jpeg_host.cpp", "jpeg_enc.hip", "jpeg_enc.cpp", "runtime.cpp", "frames.cpp", "process.cpp", "track.cpp", "testhooks.cpp", "face_net.cpp", "plate_net.cpp", "record.cpp"]
-HEADERS = ["vd_common.h", "vd_kernel.h", "conv_x6.h", "vd_math.h", "nets.h", "hold_state.h", "lead_state.h", "box_match.h", "vd_nms.h", "nv12.h", "mosaic_map.h"]
+HEADERS = ["vd_common.h", "vd_kernel.h", "conv_x6.h", "vd_math.h", "nets.h", "hold_state.h", "lead_state.h", "box_match.h", "vd_nms.h", "nv12.h", "mosaic_map.h", "face_bands.h"]
 FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-ffp-contract=off",
          "-Wall", "-Wno-unused-function", f"-I{os.path.join(ROOT, 'include')}"]
 

@@ -292,6 +292,7 @@ int Ctx::run_block_op(const Op& op, int f0, int n, int fam) {
         a.pipe = tune.block32_pipe;
         a.pipe_ds = tune.block32_pipe_ds;
         a.dbg = tune.block32_dbg;
+        band_args(op.band, f0, &a.band);                  // face layer1 in a forward with bands; else off
         t_begin(fam, fpp * n * a.H * a.W);
         hipError_t e = vd_launch_block32(a, stream);
         t_end();
@@ -324,6 +325,7 @@ int Ctx::run_stem_pool_op(const Op& op, int f0, int n, int fam) {
     if (pair) {
         a.scale = cv.scale_x;                           // BN scale with the weights' power-of-two folded in
         a.ymax = op.y.amax ? op.y.amax + f0 : nullptr;
+        band_args(op.band, f0, &a.band);                  // the face stem in a forward with bands; else off
     }
     t_begin(fam, cv.flops_per_px * n * (double)(op.x.h - 1) * (op.x.w - 1));
     hipError_t e = pair ? vd_launch_stem_pool32(a, stream) : vd_launch_stem_pool(a, stream);

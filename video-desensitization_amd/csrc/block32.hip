@@ -480,6 +480,12 @@ __global__ __launch_bounds__(512, 1) void bottleneck32_kernel(Block32Args a) {
 //   Two more counters: xs ready (bumped by each Q wave after its two rows are written,
 //   every Q wave waits for 4 (j + 1)) and xs free (bumped after a wave's last xs read of
 //   tile j; a wave waits for 4 j before it writes tile j's rows).
+//
+// Letterbox bands (Block32Args::band, both forms; DESIGN.md "Letterbox bands"): the tile rows
+// of the face canvas's padding keep what an earlier call wrote when the frame's tag matches
+// the call's conditions. The three groups then walk the launch's live tiles only (a prefix of
+// live tile counts per frame in LDS, a wave-uniform cursor): a tile left alone costs nothing,
+// the groups stay on the same j-th tile, and a tile that runs is the tile it always was.
 
 __device__ __forceinline__ int lds_load_flag(int* f) {
     return __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -526,7 +532,14 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
         g0 = lane >> 4;
         lo16 = (unsigned)lane * 16u;
     };
-    const int tpf = a.tiles_x * a.tiles_y, T = a.B * tpf;
+    const int tpf = a.tiles_x * a.tiles_y;
+    // letterbox bands: the tile loops of the three groups walk the launch's live tiles only (the same
+    // j-th tile in each group, and the same loads and stores per tile as without bands)
+    int* s_pre = s_flag + 16;                             // [B + 1] live tiles before each frame (bands)
+    const bool bands = a.band.on != 0;
+    const int lo_tiles = a.band.lo * a.tiles_x;
+    if (bands) band_prefix(a.band, a.B, tpf, (a.band.lo + a.tiles_y - a.band.hi) * a.tiles_x, s_pre, a.ymax);
+    const int T = bands ? __builtin_amdgcn_readfirstlane(s_pre[a.B]) : a.B * tpf;
     const int G = gridDim.x, bid = blockIdx.x;
     int t0, tstep, tend;
     if (G >= 8) {
@@ -560,10 +573,16 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
         return __builtin_amdgcn_make_buffer_rsrc((void*)((const float*)a.x + (size_t)b * fpx * CIN), 0,
                                                  (int)(fpx * CIN * 4), 0x00020000);
     };
-    auto tile_of = [&](int j, int& b, int& oy0, int& ox0) {
+    auto tile_of = [&](BandWalk& wk, int j, int& b, int& oy0, int& ox0) {
         const int t = t0 + j * tstep;
-        b = t / tpf;
-        const int r0 = t - b * tpf, ty = r0 / a.tiles_x;
+        int r0;
+        if (bands) {
+            wk.at(s_pre, tpf, lo_tiles, t, b, r0);
+        } else {
+            b = t / tpf;
+            r0 = t - b * tpf;
+        }
+        const int ty = r0 / a.tiles_x;
         oy0 = ty * TH;
         ox0 = (r0 - ty * a.tiles_x) * TW;
     };
@@ -590,9 +609,11 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
         // XS x register sets: XS - 1 k-steps in flight; PRE of them issued before the hand-over
         static_assert(PRE >= 1 && PRE < XS && XS <= KS1, "stage-1 x depth");
         u32x4 xpre[PRE][NP][2];
+        BandWalk wk{};
+        if (bands) wk.init(s_pre);
         {
             int b, oy0, ox0;
-            tile_of(0, b, oy0, ox0);
+            tile_of(wk, 0, b, oy0, ox0);
             unsigned off[NP];
 #pragma unroll
             for (int i = 0; i < NP; ++i) off[i] = xoff(oy0, ox0, i, li0, g0);
@@ -604,7 +625,7 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
             {
                 // ---- stage 1: t1 of halo pixel tiles 3w..3w+2, all 64 channels ----
                 int b, oy0, ox0;
-                tile_of(j, b, oy0, ox0);
+                tile_of(wk, j, b, oy0, ox0);
                 const int kx = act_scale_exp_of(__uint_as_float(a.xmax[b]));
                 const float sax = __builtin_ldexpf(1.f, kx), invx = __builtin_ldexpf(1.f, -kx);
                 const __amdgpu_buffer_rsrc_t rx = frame_rsrc(b);
@@ -667,7 +688,7 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
                 // the next tile's first k-step, in flight across the t1 hand-over
                 if (j + 1 < ntile) {
                     int b2, oy2, ox2;
-                    tile_of(j + 1, b2, oy2, ox2);
+                    tile_of(wk, j + 1, b2, oy2, ox2);
                     unsigned off2[NP];
 #pragma unroll
                     for (int i = 0; i < NP; ++i) off2[i] = xoff(oy2, ox2, i, li, g);
@@ -714,10 +735,9 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
                     f[tp][p] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
                         rw2, lo, ((((jn * 2 + hf) * 9 + tp) * 2 + p) * 64) * 16, 0));
         };
+        // (the stage reads LDS only: a tile's place in the frame does not matter to it)
 #pragma unroll 1
         for (int j = 0; j < ntile; ++j) {
-            int b, oy0, ox0;
-            tile_of(j, b, oy0, ox0);
             if constexpr (DS) group_lanes(lane, li0, g0, lo16);   // per tile: not held beside two accumulator sets
             u32x4 w2f[9][2];
             ldw2(0, 0, 9, w2f);
@@ -812,10 +832,12 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
         const __amdgpu_buffer_rsrc_t rwd = __builtin_amdgcn_make_buffer_rsrc((void*)a.wd, 0, 0x7fffffff, 0x00020000);
         int ob = -1;
         float om = 0.f;
+        BandWalk wk{};
+        if (bands) wk.init(s_pre);
 #pragma unroll 1
         for (int j = 0; j < ntile; ++j) {
             int b, oy0, ox0;
-            tile_of(j, b, oy0, ox0);
+            tile_of(wk, j, b, oy0, ox0);
             const int kx = act_scale_exp_of(__uint_as_float(a.xmax[b]));   // this tile's frame (two behind P's)
             const float sax = __builtin_ldexpf(1.f, kx), invx = __builtin_ldexpf(1.f, -kx);
             const __amdgpu_buffer_rsrc_t rx = frame_rsrc(b);
@@ -952,6 +974,9 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
                 }
             }
             om_t = wave_max(om_t);
+            // a band tile run in this call (its frame's tag did not match): its maximum for the publish
+            if (bands && lane == 0 && om_t > 0.f && (oy0 < a.band.lo * TH || oy0 >= a.band.hi * TH))
+                atomicMax(a.band.scratch + b, __float_as_uint(om_t));
             if (b != ob) {
                 if (ob >= 0 && lane == 0 && om > 0.f) atomicMax(a.ymax + ob, __float_as_uint(om));
                 ob = b;
@@ -971,10 +996,12 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
         const __amdgpu_buffer_rsrc_t rw3 = __builtin_amdgcn_make_buffer_rsrc((void*)a.w3, 0, 0x7fffffff, 0x00020000);
         int ob = -1;
         float om = 0.f;
+        BandWalk wk{};
+        if (bands) wk.init(s_pre);
 #pragma unroll 1
         for (int j = 0; j < ntile; ++j) {
             int b, oy0, ox0;
-            tile_of(j, b, oy0, ox0);
+            tile_of(wk, j, b, oy0, ox0);
             int k2 = 0;
             float inv2 = 1.f;
             const __amdgpu_buffer_rsrc_t rx = frame_rsrc(b);
@@ -1060,6 +1087,9 @@ __global__ __launch_bounds__(768, 1) void bottleneck32p_kernel(Block32Args a) {
                 }
             }
             om_t = wave_max(om_t);
+            // a band tile run in this call (its frame's tag did not match): its maximum for the publish
+            if (bands && lane == 0 && om_t > 0.f && (oy0 < a.band.lo * TH || oy0 >= a.band.hi * TH))
+                atomicMax(a.band.scratch + b, __float_as_uint(om_t));
             if (b != ob) {
                 if (ob >= 0 && lane == 0 && om > 0.f) atomicMax(a.ymax + ob, __float_as_uint(om));
                 ob = b;
@@ -1078,15 +1108,17 @@ hipError_t launch_pipe(const Block32Args& a, hipStream_t s) {
                            (256 + 512 * (DS ? 2 : 1)) * 4 + 16 * 4;
     static const int cus = [] {
         (void)hipFuncSetAttribute((const void*)bottleneck32p_kernel<CIN, XS, PRE, DS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
+                                  (int)(lds + 4 * (VD_BAND_FRAMES + 1)));
         int dev = 0, n = 256;
         (void)hipGetDevice(&dev);
         (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
         return n > 0 ? n : 256;
     }();
+    if (a.band.on && a.B > VD_BAND_FRAMES) return hipErrorInvalidValue;
     const int tiles = a.B * a.tiles_x * a.tiles_y;
     const int grid = tiles < cus ? tiles : cus;
-    hipLaunchKernelGGL((bottleneck32p_kernel<CIN, XS, PRE, DS>), dim3(grid), dim3(768), lds, s, a);
+    const size_t lds_b = lds + (a.band.on ? 4 * ((size_t)a.B + 1) : 0);   // bands: the live-tile prefix
+    hipLaunchKernelGGL((bottleneck32p_kernel<CIN, XS, PRE, DS>), dim3(grid), dim3(768), lds_b, s, a);
     return hipGetLastError();
 }
 
@@ -1122,12 +1154,14 @@ hipError_t vd_launch_block32(const Block32Args& a, hipStream_t s) {
         if (a.pipe == 5) return launch_pipe<256, 5, 2, false>(a, s);
         if (a.pipe == 6) return launch_pipe<256, 6, 3, false>(a, s);
         if (a.pipe) return launch_pipe<256, 3, 1, false>(a, s);
+        if (a.band.on) return hipErrorInvalidValue;                    // bands: the pipelined forms only
         if (a.xdepth == 3) return launch<256, false, 3>(a, s);
         if (a.xdepth == 4) return launch<256, false, 4>(a, s);
         return launch<256, false, 2>(a, s);
     }
     if (a.cin == 64 && a.ds) {
         if (a.pipe_ds) return launch_pipe<64, 2, 1, true>(a, s);   // option block32_pipe_ds
+        if (a.band.on) return hipErrorInvalidValue;
         return launch<64, true, 2>(a, s);
     }
     return hipErrorInvalidValue;

@@ -381,6 +381,7 @@ int vd_build_face(Ctx& c, const WMap& W) {
     if ((rc = c.dalloc((void**)&F.anchors, anc.size() * 4))) return rc;
     VD_CHECK_HIP(hipMemcpy(F.anchors, anc.data(), anc.size() * 4, hipMemcpyHostToDevice));
     if ((rc = vd_alloc_post(c, F.post, A, A))) return rc;   // a frame keeps at most A faces
+    if ((rc = c.bands_alloc())) return rc;                  // letterbox bands: the stem's and layer1's tag state
     F.net.amax = c.amax_region(0);
     F.net.amax_bytes = F.net.amax ? c.amax_region_bytes() : 0;
     F.loaded = true;

@@ -280,10 +280,99 @@ void Ctx::face_letterbox_args(const uint8_t* dframes, int n, int h, int w, size_
     a.out = face.input.p; a.cpad = face.input.c; a.out_f32 = face.input.f32 ? 1 : 0;
     a.out_f16 = (f16 || (f32 && !face.input.f32)) ? 1 : 0;
     a.s2d = face.s2d ? 1 : 0;
+    const int geom[6] = {h, w, a.top, a.nh, a.left, a.nw};
+    memcpy(bands.geom, geom, sizeof geom);                // what the next plain forward's canvases look like
     *out = a;
 }
 
-int Ctx::face_forward(int n) {
+// ---- letterbox bands (face_bands.h, bands.hip) ----
+int Ctx::bands_alloc() {
+    bands.plan = false;
+    const Net& net = face.net;
+    if (!f32 || tune.f32_split != 2 || face.mnet || cfg.max_batch > VD_BAND_FRAMES) return VD_OK;
+    // the four band ops: the fused stem + pool, then layer1 as three fused fp32 bottlenecks
+    if (net.stage_end[0] != 1 || net.stage_end[1] != 4 || net.ops.size() < 4 || net.ops[0].kind != OP_STEMPOOL ||
+        !net.ops[0].y.f32 || !net.ops[0].y.amax)
+        return VD_OK;
+    for (int k = 1; k < VD_BAND_OPS; ++k)
+        if (net.ops[k].kind != OP_BLOCK || !blocks[net.ops[k].blk].f32 || net.ops[k].x.p != net.ops[k - 1].y.p) return VD_OK;
+    const size_t mb = cfg.max_batch;
+    const int rows = VD_BAND_OPS + (int)((2 * VD_BAND_OPS + mb - 1) / mb);   // scratch, then the stats
+    if (amax_next[0] + rows > kAmaxActs) return VD_OK;
+    int rc;
+    if ((rc = dalloc((void**)&bands.tag, VD_BAND_OPS * mb * 8))) return rc;
+    if ((rc = dalloc((void**)&bands.bmax, VD_BAND_OPS * mb * 4))) return rc;
+    VD_CHECK_HIP(hipMemset(bands.tag, 0, VD_BAND_OPS * mb * 8));
+    VD_CHECK_HIP(hipMemset(bands.bmax, 0, VD_BAND_OPS * mb * 4));
+    bands.scratch = amax_region(0) + (size_t)amax_next[0] * mb;
+    amax_next[0] += rows;
+    bands.stats = bands.scratch + VD_BAND_OPS * mb;
+    for (int k = 0; k < VD_BAND_OPS; ++k) {
+        bands.op[k] = k;
+        face.net.ops[k].band = k;
+    }
+    bands.plan = true;
+    return VD_OK;
+}
+
+bool Ctx::bands_begin(int n, bool plain) {
+    bands.active = bands.ran = false;
+    if (!bands.plan) return false;
+    const FaceBandPlan P = vd_face_band_plan(face.in_h, bands.geom[2], bands.geom[3], bands.geom[4]);
+    bool any = false;
+    for (int k = 0; k < VD_BAND_OPS; ++k) any |= P.lo[k] > 0 || P.hi[k] < P.tile_rows[k];
+    // the pipelined bottleneck forms and whole-batch launches only (vd_common.h BandArgs)
+    const bool on = plain && any && tune.face_bands && tune.block32_pipe && tune.block32_pipe_ds && cfg.microbatch <= 0 &&
+                    !tune.block32_dbg;
+    if (!on || memcmp(bands.geom, bands.last_geom, sizeof bands.geom)) bands.forget();
+    if (!on) return false;   // this forward rewrites every tile: no tag survives it (forgotten above)
+    memcpy(bands.last_geom, bands.geom, sizeof bands.geom);
+    bands.cur = P;
+    bands.active = bands.ran = true;
+    return true;
+}
+
+void Ctx::band_args(int k, int f0, BandArgs* a) const {
+    *a = BandArgs{};
+    const FaceBandPlan& P = bands.cur;
+    if (!bands.active || k < 0 || (P.lo[k] == 0 && P.hi[k] == P.tile_rows[k])) return;
+    const size_t mb = cfg.max_batch;
+    a->on = 1;
+    a->lo = P.lo[k];
+    a->hi = P.hi[k];
+    a->epoch = bands.epoch;
+    a->nchain = k;                                        // op k's tiles depend on the inputs' scales of ops 1..k
+    for (int i = 0; i < k; ++i) a->chain[i] = face.net.ops[bands.op[i + 1]].x.amax + f0;
+    a->tag = bands.tag + k * mb + f0;
+    a->bmax = bands.bmax + k * mb + f0;
+    a->scratch = bands.scratch + k * mb + f0;
+}
+
+int Ctx::bands_publish(int f0, int n) {
+    if (!bands.active) return VD_OK;
+    BandPublishArgs p{};
+    const size_t mb = cfg.max_batch;
+    for (int k = 0; k < VD_BAND_OPS; ++k) {
+        band_args(k, f0, &p.op[k]);
+        p.tag[k] = bands.tag + k * mb + f0;
+        p.bmax[k] = bands.bmax + k * mb + f0;
+    }
+    p.stats = bands.stats;
+    p.n = n;
+    hipError_t e = vd_launch_band_publish(p, stream);
+    if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "band publish: %s", hipGetErrorString(e));
+    return VD_OK;
+}
+
+int Ctx::face_forward(int n, bool plain) {
+    const bool with_bands = bands_begin(n, plain);
+    int rc = face_forward_run(n);
+    bands.active = false;
+    if (rc && with_bands) bands.forget();                 // some band tiles may have been left half written
+    return rc;
+}
+
+int Ctx::face_forward_run(int n) {
     const int mb = cfg.microbatch;                        // frames per micro-batch (0 = off)
     const int stage = cfg.microbatch_stage > 0 ? cfg.microbatch_stage : 2;   // micro-batch through layer<stage>
     const int split = face.net.stage_end[std::min(std::max(stage, 0), 4)];
@@ -313,6 +402,7 @@ int Ctx::face_forward(int n) {
             stream = g ? group_streams[g - 1] : main;
             if (g) VD_CHECK_HIP(hipStreamWaitEvent(stream, ev_half, 0));
             int rc = run_ops(net, 0, ne, f0, f1 - f0);
+            if (!rc) rc = bands_publish(f0, f1 - f0);
             if (!rc && g && hipEventRecord(group_events[g - 1], stream) != hipSuccess)
                 rc = vd_set_error(VD_ERR_HIP, "group event");
             stream = main;
@@ -321,7 +411,8 @@ int Ctx::face_forward(int n) {
         for (int g = 1; g < G; ++g) VD_CHECK_HIP(hipStreamWaitEvent(stream, group_events[g - 1], 0));
         return VD_OK;
     }
-    return run_net(face.net, n, mb, split);
+    const int rc = run_net(face.net, n, mb, split);
+    return rc ? rc : bands_publish(0, n);
 }
 
 int Ctx::face_post(int n, int img_h, int img_w, const BoxTargets& t, const TileGrid* tiles) {

@@ -4,6 +4,7 @@
 #include "vd_common.h"
 #include "hold_state.h"
 #include "lead_state.h"
+#include "face_bands.h"
 
 #include <cstring>
 #include <initializer_list>
@@ -130,6 +131,7 @@ struct Op {
     Act y2;                            // OP_CHAIN: conv = conv3 (x -> y, identity r), conv2 = next conv1 (y -> y2)
     int lane = 0;                      // 1: runs on Ctx::stream_side (face SSH levels 1-2)
     int dep = -1;                      // op index (other lane) whose completion this op waits for
+    int band = -1;                     // face stem / layer1 (fp32 pairs): index into FaceBands (letterbox band tiles)
 };
 
 struct Net {
@@ -161,6 +163,25 @@ struct PostScratch {   // per-net candidate / NMS scratch sized for max_batch x 
     float* kscore = nullptr;
     int* klabel = nullptr;
     int kn = 0;                        // frames in the last call
+};
+
+// Letterbox bands (face_bands.h, bands.hip): the band tiles of the stem's and layer1's
+// outputs stay in their buffers between face forwards; per band op and frame slot the device keeps
+// the conditions they were written under (tag) and their maximum (bmax).
+struct FaceBands {
+    bool plan = false;                 // the face plan has the four band ops (fp32 pairs, ResNet-50, fused stem + pool)
+    int op[VD_BAND_OPS] = {-1, -1, -1, -1};   // their indices in face.net.ops
+    unsigned long long* tag = nullptr; // [4][max_batch], zero: never written
+    unsigned* bmax = nullptr;          // [4][max_batch]
+    unsigned* scratch = nullptr;       // [4][max_batch], then stats [4][2]: in the face net's per-call zeroed slots
+    unsigned* stats = nullptr;
+    unsigned epoch = 1;                // nonzero; a new value forgets every tag
+    int geom[6] = {0, 0, 0, 0, 0, 0};  // the last letterbox: frame h, w, top, nh, left, nw (face_letterbox_args)
+    int last_geom[6] = {0, 0, 0, 0, 0, 0};    // ... of the last forward that ran with bands
+    bool active = false;               // a forward with bands is being queued (run_*_op fill BandArgs)
+    FaceBandPlan cur{};                // its tile rows
+    bool ran = false;                  // the last forward ran with bands (vdt_face_band_stats)
+    void forget() { if (!++epoch) ++epoch; }
 };
 
 struct FaceNet {
@@ -434,7 +455,14 @@ struct Ctx {
                     std::initializer_list<PlaneRows> planes, const char* what);
     int face_letterbox(const uint8_t* dframes, int n, int h, int w, size_t pitch);
     void face_letterbox_args(const uint8_t* dframes, int n, int h, int w, size_t pitch, LetterboxArgs* a);
-    int face_forward(int n);
+    // plain: the n canvases are whole frames of the last face_letterbox_args geometry (not tile inputs)
+    int face_forward(int n, bool plain = true);
+    int face_forward_run(int n);                  // the forward itself: frame groups, or one launch per op
+    FaceBands bands;
+    int bands_alloc();                            // vd_build_face: the band ops' state, when the plan has them
+    bool bands_begin(int n, bool plain);          // face_forward: does this forward run with bands?
+    void band_args(int k, int f0, BandArgs* a) const;
+    int bands_publish(int f0, int n);             // after a frame group's last op, on `stream`
     // tiles: net input b is a tile of tiles->th x tiles->tw source pixels unless b % tiles->T == 0
     int face_post(int n, int img_h, int img_w, const BoxTargets& t, const TileGrid* tiles = nullptr);
     int launch_mosaic(const uint8_t* in, uint8_t* out, int n, int h, int w, size_t pitch, const int* cnt0,

@@ -225,7 +225,7 @@ int vd_detect(vd_ctx* h, const uint8_t* frames, int n, int fh, int fw, size_t pi
     if (rc) return rc;
     if (tiled) {   // T net inputs per frame, merged into one list (tiles.hip)
         if ((rc = ctx->face_letterbox_tiles(d, n, fh, fw, pitch, g))) return rc;
-        if ((rc = ctx->face_forward(n * g.T))) return rc;
+        if ((rc = ctx->face_forward(n * g.T, false))) return rc;
         if ((rc = ctx->face_post_tiled(n, fh, fw, g, t))) return rc;
         return ctx->box_finish(faces, n, t);
     }
@@ -419,7 +419,7 @@ static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh
         } else if (!paired && (rc = ctx->face_letterbox(d, n, fh, fw, pitch))) {
             return rc;
         }
-        if ((rc = ctx->face_forward(tiled ? n * tg.T : n))) return rc;
+        if ((rc = ctx->face_forward(tiled ? n * tg.T : n, !tiled))) return rc;
         if (ctx->fork_at > 0) {
             ctx->fork_at = -1;
             VD_CHECK_HIP(hipStreamWaitEvent(plate_stream, ctx->ev_fork, 0));

@@ -876,6 +876,7 @@ int vd_load_weights(vd_ctx* h, int net, const void* blob, size_t bytes, int fmt)
     WMap W;
     int rc = vd_parse_vdw1(blob, bytes, W);
     if (rc) return rc;
+    ctx->bands.forget();                          // letterbox bands: nothing written before a load is kept
     if (net == VD_NET_RETINAFACE) {
         if (ctx->face.loaded) return vd_set_error(VD_ERR_STATE, "RetinaFace weights already loaded");
         return vd_build_face(*ctx, W);
@@ -908,7 +909,7 @@ int vd_set_option(vd_ctx* h, const char* name, int value) {
         {"plate_s2d", &VdTune::plate_s2d}, {"plate_s2d32", &VdTune::plate_s2d32},
         {"plate_stage", &VdTune::plate_stage}, {"plate_detect_early", &VdTune::plate_detect_early},
         {"mosaic_early", &VdTune::mosaic_early}, {"face_groups", &VdTune::face_groups},
-        {"det_group", &VdTune::det_group}, {"f32_split", &VdTune::f32_split},
+        {"det_group", &VdTune::det_group}, {"f32_split", &VdTune::f32_split}, {"face_bands", &VdTune::face_bands},
         {"x6_small_k", &VdTune::x6_small_k}, {"x6_small_k2", &VdTune::x6_small_k2},
         {"x6_small_tiles", &VdTune::x6_small_tiles}, {"x6_bn256", &VdTune::x6_bn256},
         {"x6_exact", &VdTune::x6_exact}, {"x6_mid", &VdTune::x6_mid}, {"x6_mf32", &VdTune::x6_mf32},
@@ -932,6 +933,7 @@ int vd_set_option(vd_ctx* h, const char* name, int value) {
             if (!strcmp(name, "x6_gemm_uni") && value != 0 && value != 2)
                 return vd_set_error(VD_ERR_ARG, "x6_gemm_uni must be 0 or 2");
             ctx->tune.*(o.f) = value;
+            ctx->bands.forget();                  // letterbox bands: a switch may change what a kernel writes
             return VD_OK;
         }
     return vd_set_error(VD_ERR_ARG, "unknown option '%s'", name);

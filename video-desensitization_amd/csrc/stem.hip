@@ -227,6 +227,8 @@ hipError_t vd_launch_stem_pool(const StemPoolArgs& a, hipStream_t s) {
 // first). The stem tile lives in LDS as f32 (64 channels x 4 B per pixel), so pool
 // tiles are 6x6 (13x13 stem pixels, 54 KB per workgroup, two per CU); the pooled
 // map is f32 and its per-frame max |y| goes to a.ymax for layer1's operand scale.
+// Letterbox bands (StemPoolArgs::band; DESIGN.md "Letterbox bands"): pool tiles whose inputs are
+// canvas padding only keep what an earlier call wrote; the tile loop walks the live tiles only.
 namespace {
 
 constexpr int PT3 = 6;                     // pool tile
@@ -264,7 +266,26 @@ __global__ __launch_bounds__(256, 2) void stem_pool32_kernel(StemPoolArgs a) {
     const int np = w & 1, gh = w >> 1;
     const int SH = a.xh - 1, SW = a.xw - 1;
     const int tpr = (a.ph + PT3 - 1) / PT3, tpc = (a.pw + PT3 - 1) / PT3, tpf = tpr * tpc;
-    const int T = a.B * tpf;
+    // letterbox bands: the tile loop walks the launch's live tiles only (the same DMAs and stores per tile)
+    unsigned* s_bandmax = s_amax + a.B;    // [B] max of the band tiles run in this call (bands)
+    int* s_pre = (int*)(s_bandmax + a.B);  // [B + 1] live tiles before each frame (bands)
+    const bool bands = a.band.on != 0;
+    const int lo_tiles = a.band.lo * tpc;
+    if (bands) band_prefix(a.band, a.B, tpf, (a.band.lo + tpr - a.band.hi) * tpc, s_pre, a.ymax);
+    const int T = bands ? __builtin_amdgcn_readfirstlane(s_pre[a.B]) : a.B * tpf;
+    BandWalk wk{};
+    if (bands) wk.init(s_pre);
+    auto tile_at = [&](int t, int& b, int& ty, int& tx) {
+        int r0;
+        if (bands) {
+            wk.at(s_pre, tpf, lo_tiles, t, b, r0);
+        } else {
+            b = t / tpf;
+            r0 = t - b * tpf;
+        }
+        ty = r0 / tpc;
+        tx = r0 - ty * tpc;
+    };
     const int G = gridDim.x, bid = blockIdx.x;
     int t0, tstep, tend;
     if (G >= 8) {
@@ -275,12 +296,12 @@ __global__ __launch_bounds__(256, 2) void stem_pool32_kernel(StemPoolArgs a) {
     } else {
         t0 = bid; tstep = G; tend = T;
     }
-    for (int f = tid; f < a.B; f += 256) s_amax[f] = 0u;
+    for (int f = tid; f < (bands ? 2 : 1) * a.B; f += 256) s_amax[f] = 0u;   // (and s_bandmax)
     const size_t fx = (size_t)a.xh * a.xw * 16;
 
     auto issue_x = [&](int t, int buf) {
-        const int b = t / tpf, r0 = t - b * tpf;
-        const int ty = r0 / tpc, tx = r0 - ty * tpc;
+        int b, ty, tx;
+        tile_at(t, b, ty, tx);
         const int xr0 = 2 * PT3 * ty - 2, xc0 = 2 * PT3 * tx - 2;
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
             (void*)((const _Float16*)a.x + (size_t)b * fx), 0, (int)(fx * 2), 0x00020000);
@@ -320,8 +341,8 @@ __global__ __launch_bounds__(256, 2) void stem_pool32_kernel(StemPoolArgs a) {
     int xb = 0;                            // X' buffer of this tile
 #pragma unroll 1
     for (int t = t0; t < tend; t += tstep, xb ^= 1) {
-        const int b = t / tpf, r0 = t - b * tpf;
-        const int ty = r0 / tpc, tx = r0 - ty * tpc;
+        int b, ty, tx;
+        tile_at(t, b, ty, tx);
         const int sy0 = 2 * PT3 * ty - 1, sx0 = 2 * PT3 * tx - 1;
         // this tile's X' (DMA, issued a whole tile ago); the previous tile's 4 stores per
         // thread are the only younger ops
@@ -402,11 +423,14 @@ __global__ __launch_bounds__(256, 2) void stem_pool32_kernel(StemPoolArgs a) {
                                          fmaxf(fmaxf(m1.x, m1.y), fmaxf(m1.z, m1.w))));
             }
             if (a.ymax) amax_lds_add(s_amax, b, tm);          // the tile's frame: block-uniform
+            // a band tile run in this call (its frame's tag did not match): its maximum for the publish
+            if (bands && (ty < a.band.lo || ty >= a.band.hi)) amax_lds_add(s_bandmax, b, tm);
         }
     }
     if (a.ymax) {
         __syncthreads();
         amax_lds_flush(s_amax, a.ymax, a.B);
+        if (bands) amax_lds_flush(s_bandmax, a.band.scratch, a.B);
     }
 }
 
@@ -414,11 +438,13 @@ __global__ __launch_bounds__(256, 2) void stem_pool32_kernel(StemPoolArgs a) {
 
 hipError_t vd_launch_stem_pool32(const StemPoolArgs& a, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
-    if (a.B > 1024) return hipErrorInvalidValue;
-    const size_t lds = 2 * XBUF3 + STB3 + 1024 + 4 * (size_t)a.B;
+    if (a.B > 1024 || (a.band.on && !a.ymax)) return hipErrorInvalidValue;
+    static_assert(VD_BAND_FRAMES <= 1024, "stem LDS is sized for 1024 frames");
+    // the frames' max slots; bands: the band maxima and the live-tile prefix behind them
+    const size_t lds = 2 * XBUF3 + STB3 + 1024 + 4 * (size_t)a.B * (a.band.on ? 3 : 1) + (a.band.on ? 4 : 0);
     static const int cus = [] {
         (void)hipFuncSetAttribute((const void*)stem_pool32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  2 * XBUF3 + STB3 + 1024 + 4 * 1024);
+                                  2 * XBUF3 + STB3 + 1024 + 3 * 4 * 1024 + 4);
         int dev = 0, n = 256;
         (void)hipGetDevice(&dev);
         (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);

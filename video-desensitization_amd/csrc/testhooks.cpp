@@ -22,6 +22,7 @@ int vdt_set_debug(vd_ctx* h, const char* name, int value) {
     Ctx* ctx = (Ctx*)h;
     VD_ENTRY(ctx);
     if (!name) return vd_set_error(VD_ERR_ARG, "null debug switch name");
+    ctx->bands.forget();   // letterbox bands: tiles written under a debug switch are not kept
     // timing-only stage skips: results are WRONG while set (tools/x6bench, tools/runs)
     if (!strcmp(name, "x6_dbg")) { ctx->tune.x6_dbg = value; return VD_OK; }
     if (!strcmp(name, "block32_dbg")) { ctx->tune.block32_dbg = value; return VD_OK; }
@@ -171,6 +172,33 @@ int vdt_forward_heads(vd_ctx* h, const uint8_t* frames, int n, int fh, int fw, s
                     if (conf) for (int j = 0; j < 2; ++j) conf[a * 2 + j] = src[8 + 2 * k + j];
                     if (landm) for (int j = 0; j < 10; ++j) landm[a * 10 + j] = src[12 + 10 * k + j];
                 }
+    }
+    return VD_OK;
+}
+
+int vdt_face_band_rows(int canvas_h, int top, int nh, int left, int32_t out[4][5]) {
+    if (!out || canvas_h <= 0 || canvas_h % 4) return vd_set_error(VD_ERR_ARG, "vdt_face_band_rows: canvas rows % 4, out");
+    const FaceBandPlan P = vd_face_band_plan(canvas_h, top, nh, left);
+    for (int k = 0; k < VD_BAND_OPS; ++k) {
+        out[k][0] = P.rows[k].top_end; out[k][1] = P.rows[k].bot_begin;
+        out[k][2] = P.tile_rows[k]; out[k][3] = P.lo[k]; out[k][4] = P.hi[k];
+    }
+    return VD_OK;
+}
+
+int vdt_face_band_stats(vd_ctx* h, int32_t out[4][5]) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (!out) return vd_set_error(VD_ERR_ARG, "vdt_face_band_stats: null out");
+    memset(out, 0, sizeof(int32_t) * VD_BAND_OPS * 5);
+    const FaceBands& B = ctx->bands;
+    if (!B.plan || !B.ran) return VD_OK;
+    VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    unsigned st[VD_BAND_OPS][2];
+    VD_CHECK_HIP(hipMemcpy(st, B.stats, sizeof st, hipMemcpyDeviceToHost));
+    for (int k = 0; k < VD_BAND_OPS; ++k) {
+        out[k][0] = B.cur.lo[k]; out[k][1] = B.cur.hi[k]; out[k][2] = B.cur.tile_rows[k];
+        out[k][3] = (int32_t)st[k][0]; out[k][4] = (int32_t)st[k][1];
     }
     return VD_OK;
 }

@@ -96,6 +96,9 @@ struct VdTune {
     int x6_dbg = 0;           // timing-only (vdt_set_debug / tools/x6bench, never vd_set_option; WRONG results): bit 0 = no
                               //   epilogue; halo tiles: bit 2 = no B DMA past the prologue, 3 = no halo reload, 5 = no
                               //   main-loop barriers
+    int face_bands = 1;       // fp32 pairs, ResNet-50: the stem's and layer1's tiles inside the letterbox bands keep
+                              //   what an earlier call wrote under the same conditions (0: every tile
+                              //   computed in every call; bit-identical)
     int f32_split = 2;        // plan (fp32, at weight load): 2 = operands scaled by powers of two
                               //   and split into fp16 pairs, 3 products on the f16 matrix cores;
                               //   1 = exact 3-term bf16 split, 6 products (conv_x6.hip);
@@ -162,6 +165,21 @@ struct BlockArgs {
     int f16;                     // fp16 plan: fp16 operands / activations (else bf16)
 };
 
+// Letterbox bands (face_bands.h): the tile rows of one op whose outputs depend on the
+// letterbox geometry, the weights and the op's input scale exponents only, and the state that says
+// under which of these the rows in the output buffer were last written. on = 0: every tile runs.
+constexpr int VD_BAND_FRAMES = 1024;   // frames of one launch with bands on (the kernels' LDS prefix)
+struct BandArgs {
+    int on;
+    int lo, hi;                        // tile rows [0, lo) and [hi, tile rows) are band tiles (lo < hi)
+    unsigned epoch;                    // host epoch (nonzero)
+    int nchain;                        // input scale exponents in the tag (0: the stem, static bound)
+    const unsigned* chain[3];          // max |x| slots of the band ops' inputs up to this op (frame 0 of this call)
+    const unsigned long long* tag;     // per frame: the conditions of the band tiles in y (0: none)
+    const unsigned* bmax;              // per frame: max |y| over those band tiles
+    unsigned* scratch;                 // per frame, zero at the start of the call: max |y| of the band tiles run now
+};
+
 // One fused layer1 bottleneck in the fp32 plan (block32.hip): x f32 [B][H][W][cin]
 // -> y f32 [B][H][W][256]; weights as fp16 hi / lo planes of the per-conv pair
 // packing (row scales folded into the BN scales), per-frame range slots of x / y.
@@ -180,6 +198,7 @@ struct Block32Args {
     int pipe;                    // producer / consumer wave groups on consecutive tiles (option block32_pipe)
     int pipe_ds;                 // ... for cin 64 + downsample (option block32_pipe_ds)
     int dbg;                     // timing-only stage skips (option block32_dbg; wrong results)
+    BandArgs band;               // pipelined forms only: letterbox band tiles left alone (on = 0: none)
 };
 
 // A bottleneck's conv3 (+ identity, ReLU) and the next bottleneck's conv1 in one
@@ -234,6 +253,7 @@ struct StemPoolArgs {
     const float* scale; const float* shift;
     unsigned* ymax;              // fp32 plan: per-frame max |y| slots of the pooled map
     int f16;                     // fp16 plan (stem_pool_kernel): fp16 canvas, weights and pooled map
+    BandArgs band;               // fp32 plan: letterbox band tiles (6 pool rows each) left alone (on = 0: none)
 };
 
 // Device buffers + parameters for one frame batch's detection post-processing.
@@ -437,6 +457,16 @@ void vd_pack_x3h(const float* w, int npad, int kpad, uint16_t* out, float* row_i
 bool vd_block_ok(int cin, bool ds, int h, int w);
 bool vd_block32_ok(int cin, bool ds, int h, int w);
 hipError_t vd_launch_block32(const Block32Args& a, hipStream_t s);
+// After the last band op of a forward (bands.hip): per op and frame of the call, a tag that differs
+// from the current conditions is replaced, with the band maximum the call's kernels left in scratch.
+struct BandPublishArgs {
+    BandArgs op[4];                    // as the kernels got them (on = 0: op without band tiles)
+    unsigned long long* tag[4];        // the writable tags / maxima behind op[k].tag / op[k].bmax
+    unsigned* bmax[4];
+    unsigned* stats;                   // [4][2] per op: frames that matched, frames that did not
+    int n;
+};
+hipError_t vd_launch_band_publish(const BandPublishArgs& a, hipStream_t s);
 bool vd_stem_pool_ok(int xh, int xw, int ph, int pw);
 hipError_t vd_launch_dwconv(const DwConvArgs& a, bool f32, bool f16, hipStream_t s);
 hipError_t vd_launch_stem_pool(const StemPoolArgs& a, hipStream_t s);

@@ -229,3 +229,69 @@ __device__ __forceinline__ void amax_lds_flush(const unsigned* s, unsigned* g, i
     for (int f = threadIdx.x; f < nframes; f += blockDim.x)
         if (s[f]) atomicMax(g + f, s[f]);
 }
+
+// ---- Letterbox bands (BandArgs in vd_common.h) --------------------------
+// The conditions frame f's band tiles of this op are computed under in this call: the
+// host epoch and the scale exponents of the band ops' inputs up to this op. The slots
+// behind `chain` are final when the op starts (their producers ran earlier on the stream).
+__device__ __forceinline__ unsigned long long band_tag(const BandArgs& d, int f) {
+    unsigned long long t = (unsigned long long)d.epoch << 32;
+    for (int i = 0; i < d.nchain; ++i)
+        t |= (unsigned long long)((act_scale_exp_of(__uint_as_float(d.chain[i][f])) + 128) & 0xff) << (8 * i);
+    return t;
+}
+
+// The launch's live tiles. A frame whose tag matches runs its tile rows [lo, hi) only;
+// s_pre[f] (B + 1 entries, LDS) = live tiles of the frames before f. Called by the whole
+// workgroup; the tags are not written by any kernel of the forward, so every workgroup
+// (and every launch of the op) decides alike. Workgroup 0 folds the kept band tiles'
+// maximum into the output's slots.
+__device__ __forceinline__ void band_prefix(const BandArgs& d, int B, int tpf, int band_tiles, int* s_pre,
+                                            unsigned* ymax) {
+    if (threadIdx.x < 64) {
+        const int lane = threadIdx.x;
+        int carry = 0;
+        for (int base = 0; base < B; base += 64) {
+            const int f = base + lane;
+            int c = 0;
+            if (f < B) {
+                const bool keep = d.tag[f] == band_tag(d, f);
+                c = keep ? tpf - band_tiles : tpf;
+                if (keep && blockIdx.x == 0 && ymax && d.bmax[f]) atomicMax(ymax + f, d.bmax[f]);
+            }
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int v = __shfl_up(c, o);
+                if (lane >= o) c += v;
+            }
+            if (f < B) s_pre[f + 1] = carry + c;
+            carry += __shfl(c, 63);
+        }
+        if (lane == 0) s_pre[0] = 0;
+    }
+    __syncthreads();
+}
+
+// A wave's position in s_pre (wave-uniform): live tile t -> frame b and tile r0 of the frame.
+struct BandWalk {
+    int cur, base, next;
+    __device__ __forceinline__ void init(const int* s_pre) {
+        cur = 0;
+        base = 0;
+        next = __builtin_amdgcn_readfirstlane(s_pre[1]);
+    }
+    __device__ __forceinline__ void at(const int* s_pre, int tpf, int lo_tiles, int t, int& b, int& r0) {
+        while (t >= next) {
+            ++cur;
+            base = next;
+            next = __builtin_amdgcn_readfirstlane(s_pre[cur + 1]);
+        }
+        while (t < base) {
+            --cur;
+            next = base;
+            base = __builtin_amdgcn_readfirstlane(s_pre[cur]);
+        }
+        b = cur;
+        r0 = t - base + (next - base != tpf ? lo_tiles : 0);
+    }
+};

@@ -182,6 +182,8 @@ SIGNATURES = [
     ("vdt_letterbox", _I, [_P, _P, _I, _I, _I, _SZ, _I, _P, _I]),
     ("vdt_letterbox_tiles", _I, [_P, _P, _I, _I, _I, _SZ, _I, _P, _I]),
     ("vdt_forward_heads", _I, [_P, _P, _I, _I, _I, _SZ, _I, _P, _P, _P]),
+    ("vdt_face_band_rows", _I, [_I, _I, _I, _I, _P]),
+    ("vdt_face_band_stats", _I, [_P, _P]),
     ("vdt_postprocess", _I, [_P, _P, _P, _I, _P, ctypes.POINTER(vd_boxes)]),
     ("vdt_conv2d", _I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _F, _P, _I, _P,
                         ctypes.POINTER(_I), ctypes.POINTER(_I)]),

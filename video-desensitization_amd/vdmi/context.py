@@ -1308,6 +1308,14 @@ class Context:
         check(self._lib.vdt_forward_heads(self._h, p, n, h, w, pitch, where, ptr(loc), ptr(conf), ptr(landm)))
         return loc, conf, landm
 
+    def face_band_stats(self):
+        """Letterbox bands of the last face forward (vdt_face_band_stats): int32 [4][5], per band op
+        (stem + pool, layer1.0-2) lo, hi, tile rows, frames whose band tiles were left alone, frames
+        whose band tiles ran; zeros for a forward that ran without bands."""
+        out = np.zeros((4, 5), np.int32)
+        check(self._lib.vdt_face_band_stats(self._h, ptr(out)))
+        return out
+
     def postprocess(self, loc, conf, img_hw, cap=None):
         loc = np.ascontiguousarray(loc, np.float32)
         conf = np.ascontiguousarray(conf, np.float32)
