@@ -37,6 +37,8 @@
  *                                   reference works on the RGB frames of ffmpeg-split images)
  *   vd_process_yuv420 / vd_mosaic_yuv420 / vd_smooth_yuv420 / vd_yuv420_to_rgb: the same path on 8-bit 4:2:0 frames in
  *                                   any layout (vd_yuv420: I420 / YV12 from a software decoder, NV12, NV21)
+ *   vd_process_yuv420_16 / vd_mosaic_yuv420_16 / vd_smooth_yuv420_16 / vd_yuv420_16_to_rgb: ... on 10- and 12-bit
+ *                                   4:2:0 frames (vd_yuv420_16: P010, P012, yuv420p10le, yuv420p12le)
  *   vd_read_boxes                <- the complete per-frame box lists the reference's
  *                                   loop iterates (combine_detect.py:241-249), past any cap
  *   vd_sync / vd_last_error / vd_destroy: runtime plumbing (no reference equivalent;
@@ -852,8 +854,8 @@ int vd_nv12_to_rgb(const vd_nv12* in, int n, int h, int w, uint8_t* rgb, size_t 
  * overlapping device `in` (the whole extents of the n frames). VD_ERR_STATE, with the messages of
  * vd_process_nv12: a VD_BLUR_GAUSSIAN context with cells off; a call that would run a tiled net;
  * VD_PROC_MOSAIC in a look-ahead context. Not in this version, and without an entry point: a
- * planar form of vd_process_lead_nv12 (the look-ahead ring stays NV12), 10-bit surfaces (P010,
- * yuv420p10), 4:2:2 and 4:4:4. */
+ * planar form of vd_process_lead_nv12 (the look-ahead ring stays NV12), 4:2:2 and 4:4:4. 10- and
+ * 12-bit surfaces (P010, yuv420p10le) have a descriptor of their own: vd_yuv420_16, below. */
 typedef struct vd_yuv420 {
     uint8_t* base;        /* first luma byte of frame 0 */
     size_t   pitch;       /* luma row pitch, bytes */
@@ -872,6 +874,75 @@ int vd_smooth_yuv420(vd_ctx* ctx, const vd_yuv420* in, const vd_yuv420* out, int
                      const vd_boxes* boxes, int level, int cells);
 /* vd_nv12_to_rgb for any layout: C(frame) of n frames (host only: no context, no GPU), by the same function. */
 int vd_yuv420_to_rgb(const vd_yuv420* in, int n, int h, int w, uint8_t* rgb, size_t rgb_pitch);
+
+/* ---- 10- and 12-bit 4:2:0 frames: P010, P012, yuv420p10le, yuv420p12le --------------
+ * Main10 HEVC leaves a hardware decoder as P010 and a software decoder as yuv420p10le. Such a
+ * surface goes in as it is: detection sees an 8-bit picture the library already defines, the blur
+ * acts on the 16-bit samples, and every sample outside a hidden box comes back bit for bit.
+ *   layout   vd_yuv420's fields, all offsets and pitches in BYTES, followed by depth and shift. A
+ *            sample is a little-endian uint16_t. chroma_step counts samples (1 planar, 2
+ *            interleaved pairs): a luma row holds w words (pitch >= 2*w), a chroma row
+ *            (w/2)*chroma_step words (chroma_pitch >= w*chroma_step), and
+ *              U(cy, cx) = word at frame + u_offset + cy*chroma_pitch + 2*cx*chroma_step
+ *            (V likewise). pitch, chroma_pitch, u_offset, v_offset and frame_stride are even and
+ *            base is 2-byte aligned. chroma_step 2: |u_offset - v_offset| = 2. depth is 10 or 12,
+ *            0 <= shift <= 16 - depth, and the value of a word is
+ *              v = (word >> shift) & ((1 << depth) - 1).
+ *            yuv420p10le / yuv420p12le: shift 0, step 1. P010: depth 10, shift 6, step 2, V after
+ *            U. P012: depth 12, shift 4. The V-first variants of all of these by the offsets. The
+ *            plane-overlap and frame_stride rules are vd_yuv420's on the byte extents (a luma row
+ *            is 2*w bytes, a chroma row w*chroma_step).
+ *   D(S)     the 8-bit surface with S's layout (pitches and offsets counted in samples) whose
+ *            samples are v >> (depth - 8). lo(S) / hi(S): the 8-bit surfaces of the low / high bytes
+ *            of S's words.
+ *   lists    nothing new is computed for detection: every list a *_yuv420_16 call returns or stores
+ *            (detections, vd_read_boxes, vd_read_held, vd_read_rescue, grown lists, the hold and
+ *            rescue history) is exactly what the *_yuv420 call gives on D(in).
+ *   pixelation  a pure copy of words: the output's low bytes are what vd_mosaic_yuv420 writes for
+ *            lo(in) with the same list, level and cells, its high bytes likewise for hi(in); unused
+ *            bits travel with their word.
+ *   smooth   the formulas of vd_cells, plane by plane as vd_smooth_nv12 defines them (owner by luma
+ *            level, chroma box cc, chroma grid of at most N + 1 cells), on the values v: means are
+ *            Q(depth).4, (16*S + n/2) / n; t, T and the result follow the same expressions. At depth
+ *            12 t <= 65520 and T + 16f <= 65536*65520 + 16*32768 < 2^32, which is why depth 16 is not
+ *            offered. A blurred sample is written as result << shift with its unused bits zero; a
+ *            sample owned by no box is out word = in word.
+ *   ellipse  the predicate and the chroma rule of vd_mask on NV12 frames (a chroma sample is hidden
+ *            iff one of its four luma pixels is); the restore copies words.
+ *   in/out   `in` and `out` may differ in layout, pitches and offsets; depth and shift of `out` must
+ *            equal `in`'s (VD_ERR_ARG: no depth conversion). matrix and range of an output
+ *            descriptor are ignored. Pad bytes, and bytes between planes and surfaces, are never
+ *            written.
+ * Flags, box contracts, capacity and overlap rules are those of the *_yuv420 calls; host frames are
+ * staged in their own layout, packed, at 3 B/px. VD_ERR_ARG, before any state changes, the message
+ * naming the field: every rule of vd_yuv420 on the byte extents; an odd pitch, chroma_pitch,
+ * u_offset, v_offset or frame_stride or a base that is not 2-byte aligned; pitch < 2*w; depth
+ * outside {10, 12}; shift outside [0, 16 - depth]; chroma_step 2 with |u_offset - v_offset| != 2.
+ * VD_ERR_STATE with the messages of vd_process_yuv420: a VD_BLUR_GAUSSIAN context with cells off; a
+ * call that would run a tiled net; VD_PROC_MOSAIC in a look-ahead context. Not in this version, and
+ * without an entry point: look-ahead on these surfaces (the ring stays 8-bit NV12), tiling, the
+ * fixed Gaussian, depth or shift conversion between in and out, 16-bit-deep samples, 4:2:2 and
+ * 4:4:4. */
+typedef struct vd_yuv420_16 {
+    uint8_t* base;        /* first luma word of frame 0 (2-byte aligned) */
+    size_t   pitch;       /* luma row pitch, bytes (even, >= 2*w) */
+    size_t   u_offset;    /* bytes from a frame's first luma word to its first U word */
+    size_t   v_offset;    /* ... to its first V word */
+    size_t   chroma_pitch;/* pitch of a chroma row, bytes (even) */
+    size_t   frame_stride;/* bytes (even) */
+    int32_t  chroma_step; /* in samples: 1 planar, 2 interleaved pairs */
+    int32_t  matrix, range;   /* VD_NV12_BT601|BT709, VD_NV12_LIMITED|FULL */
+    int32_t  depth;       /* 10 or 12 */
+    int32_t  shift;       /* position of the sample in the word, 0 .. 16 - depth */
+} vd_yuv420_16;
+int vd_process_yuv420_16(vd_ctx* ctx, const vd_yuv420_16* in, const vd_yuv420_16* out, int n, int h, int w, int where,
+                         int flags, vd_boxes* faces, vd_boxes* plates);
+int vd_mosaic_yuv420_16(vd_ctx* ctx, const vd_yuv420_16* in, const vd_yuv420_16* out, int n, int h, int w, int where,
+                        const vd_boxes* boxes, int level);
+int vd_smooth_yuv420_16(vd_ctx* ctx, const vd_yuv420_16* in, const vd_yuv420_16* out, int n, int h, int w, int where,
+                        const vd_boxes* boxes, int level, int cells);
+/* C(D(frame)) of n frames (host only: no context, no GPU), by the same conversion function. */
+int vd_yuv420_16_to_rgb(const vd_yuv420_16* in, int n, int h, int w, uint8_t* rgb, size_t rgb_pitch);
 
 /* ---- instrumentation (bench / profiling) ---------------------------------- */
 /* When enabled, every launch of kernel family `fam` is bracketed by HIP events
@@ -898,6 +969,9 @@ int vdt_letterbox_tiles(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w,
 int vdt_letterbox_nv12(vd_ctx* ctx, const vd_nv12* frames, int n, int h, int w, int where, float* out_nhwc, int cpad);
 /* ... for 4:2:0 frames in any layout (vd_yuv420), by the letterbox kernel the product path runs for that layout. */
 int vdt_letterbox_yuv420(vd_ctx* ctx, const vd_yuv420* frames, int n, int h, int w, int where, float* out_nhwc, int cpad);
+/* ... for 10- and 12-bit 4:2:0 frames (vd_yuv420_16), by the letterbox kernel the product path runs for them. */
+int vdt_letterbox_yuv420_16(vd_ctx* ctx, const vd_yuv420_16* frames, int n, int h, int w, int where, float* out_nhwc,
+                            int cpad);
 /* Raw head outputs after the forward, host f32: loc [n][A][4], conf logits [n][A][2],
  * landm [n][A][10], A = number of anchors. */
 int vdt_forward_heads(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w, size_t pitch,

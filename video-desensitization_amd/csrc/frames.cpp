@@ -85,20 +85,43 @@ int vd_yuv420_check(const char* who, const vd_yuv420* d, int n, int h, int w, bo
                         d->range);
 }
 
-// The planes of one frame between a caller's host layout d and its packed staging o (the same
-// step and plane order): the picture's bytes of every row only, 1.5 B/px.
-static int yuv420_copy_planes(const vd_yuv420& d, const Yuv420Dev& o, int n, int h, int w, bool to_device, hipStream_t stream) {
+int vd_yuv420_16_check(const char* who, const vd_yuv420_16* d, int n, int h, int w, bool colour, size_t* extent) {
+    static const char* const rule[] = {"", "null descriptor or base", "n > 0 and even, positive h and w required",
+                                       "pitch < 2 * w, odd (or >= 2^31)", "chroma_step outside {1, 2}",
+                                       "chroma_pitch < w * chroma_step, odd (or >= 2^31)",
+                                       "chroma_step 2 needs |u_offset - v_offset| == 2",
+                                       "u_offset: odd, or the U plane overlaps the luma plane (or >= 2^47)",
+                                       "v_offset: odd, or the V plane overlaps the luma or the U plane (or >= 2^47)",
+                                       "frame_stride: odd, or a plane reaches past it (or >= 2^47)", "unknown matrix",
+                                       "unknown range", "depth outside {10, 12}", "shift outside [0, 16 - depth]",
+                                       "base is not 2-byte aligned"};
+    size_t end = 0;
+    const int r = vd_yuv420_16_layout(d, n, h, w, colour, &end);
+    if (!r) {
+        if (extent) *extent = (size_t)(n - 1) * d->frame_stride + end;
+        return VD_OK;
+    }
+    if (r == 1) return vd_set_error(VD_ERR_ARG, "%s: 16-bit 4:2:0 frames: %s", who, rule[r]);
+    return vd_set_error(VD_ERR_ARG, "%s: 16-bit 4:2:0 frames: %s (n=%d, %d x %d, pitch %zu, u_offset %zu, v_offset %zu, "
+                        "chroma_pitch %zu, chroma_step %d, frame_stride %zu, matrix %d, range %d, depth %d, shift %d)", who,
+                        rule[r], n, w, h, d->pitch, d->u_offset, d->v_offset, d->chroma_pitch, d->chroma_step,
+                        d->frame_stride, d->matrix, d->range, d->depth, d->shift);
+}
+
+// The planes of one frame between a caller's host layout c and its packed staging o (the same
+// step and plane order): the picture's bytes of every row only, 1.5 B/px (16-bit words: 3 B/px).
+static int yuv420_copy_planes(const Yuv420Dev& c, const Yuv420Dev& o, int n, int h, int w, bool to_device, hipStream_t stream) {
     const hipMemcpyKind kind = to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
-    const Yuv420Dev c = vd_yuv420_dev(d);
+    const size_t es = (size_t)c.es();
     // interleaved: one chroma plane of w bytes a row from the lower offset; planar: U and V of w / 2
     const size_t coff[2][2] = {{c.step == 2 ? c.c0() : c.u, c.step == 2 ? o.c0() : o.u}, {c.v, o.v}};
     const int nchroma = c.step == 2 ? 1 : 2;
-    const size_t crow = c.step == 2 ? (size_t)w : (size_t)(w / 2);
+    const size_t crow = (c.step == 2 ? (size_t)w : (size_t)(w / 2)) * es, lrow = (size_t)w * es;
     for (int f = 0; f < n; ++f) {
         uint8_t* hp = c.base + (size_t)f * c.stride;
         uint8_t* dp = o.base + (size_t)f * o.stride;
-        if (to_device) VD_CHECK_HIP(hipMemcpy2DAsync(dp, o.pitch, hp, c.pitch, (size_t)w, h, kind, stream));
-        else VD_CHECK_HIP(hipMemcpy2DAsync(hp, c.pitch, dp, o.pitch, (size_t)w, h, kind, stream));
+        if (to_device) VD_CHECK_HIP(hipMemcpy2DAsync(dp, o.pitch, hp, c.pitch, lrow, h, kind, stream));
+        else VD_CHECK_HIP(hipMemcpy2DAsync(hp, c.pitch, dp, o.pitch, lrow, h, kind, stream));
         for (int p = 0; p < nchroma; ++p) {
             if (to_device)
                 VD_CHECK_HIP(hipMemcpy2DAsync(dp + coff[p][1], o.cpitch, hp + coff[p][0], c.cpitch, crow, h / 2, kind, stream));
@@ -109,29 +132,29 @@ static int yuv420_copy_planes(const vd_yuv420& d, const Yuv420Dev& o, int n, int
     return VD_OK;
 }
 
-int Ctx::nv12_in(const vd_yuv420& d, int n, int h, int w, int where, Nv12Dev* o) {
+int Ctx::nv12_in(const Nv12Dev& d, int n, int h, int w, int where, Nv12Dev* o) {
     if (where == VD_DEVICE) {
-        *o = vd_yuv420_dev(d);
+        *o = d;
         return VD_OK;
     }
-    int rc = ensure_staging(&stage_in, &stage_in_bytes, (size_t)n * h * w / 2 * 3);
+    int rc = ensure_staging(&stage_in, &stage_in_bytes, (size_t)n * h * w / 2 * 3 * d.es());
     if (rc) return rc;
-    *o = vd_yuv420_packed(stage_in, h, w, d.chroma_step, d.v_offset < d.u_offset);
+    *o = vd_yuv420_packed(stage_in, h, w, d.step, d.v < d.u, d.depth, d.shift);
     return yuv420_copy_planes(d, *o, n, h, w, true, stream);
 }
 
-int Ctx::nv12_out_begin(const vd_yuv420& d, int n, int h, int w, int where, Nv12Dev* o) {
+int Ctx::nv12_out_begin(const Nv12Dev& d, int n, int h, int w, int where, Nv12Dev* o) {
     if (where == VD_DEVICE) {
-        *o = vd_yuv420_dev(d);
+        *o = d;
         return VD_OK;
     }
-    int rc = ensure_staging(&stage_out, &stage_out_bytes, (size_t)n * h * w / 2 * 3);
+    int rc = ensure_staging(&stage_out, &stage_out_bytes, (size_t)n * h * w / 2 * 3 * d.es());
     if (rc) return rc;
-    *o = vd_yuv420_packed(stage_out, h, w, d.chroma_step, d.v_offset < d.u_offset);
+    *o = vd_yuv420_packed(stage_out, h, w, d.step, d.v < d.u, d.depth, d.shift);
     return VD_OK;
 }
 
-int Ctx::nv12_out_finish(const vd_yuv420& d, const Nv12Dev& o, int n, int h, int w, int where) {
+int Ctx::nv12_out_finish(const Nv12Dev& d, const Nv12Dev& o, int n, int h, int w, int where) {
     if (where == VD_DEVICE) return VD_OK;
     return yuv420_copy_planes(d, o, n, h, w, false, stream);   // pad bytes and the bytes between the planes are not written
 }
@@ -141,6 +164,14 @@ extern "C" int vd_yuv420_to_rgb(const vd_yuv420* in, int n, int h, int w, uint8_
     if (rc) return rc;
     if (!rgb || rgb_pitch < (size_t)w * 3) return vd_set_error(VD_ERR_ARG, "vd_yuv420_to_rgb: null rgb or rgb_pitch < 3 * w");
     vd_yuv420_to_rgb_host(in, n, h, w, rgb, rgb_pitch);
+    return VD_OK;
+}
+
+extern "C" int vd_yuv420_16_to_rgb(const vd_yuv420_16* in, int n, int h, int w, uint8_t* rgb, size_t rgb_pitch) {
+    int rc = vd_yuv420_16_check("vd_yuv420_16_to_rgb", in, n, h, w, true);
+    if (rc) return rc;
+    if (!rgb || rgb_pitch < (size_t)w * 3) return vd_set_error(VD_ERR_ARG, "vd_yuv420_16_to_rgb: null rgb or rgb_pitch < 3 * w");
+    vd_yuv420_16_to_rgb_host(in, n, h, w, rgb, rgb_pitch);
     return VD_OK;
 }
 

@@ -227,18 +227,31 @@ __global__ __launch_bounds__(THREADS) void mask_restore_kernel(MaskArgs a) {
 // row's two luma rows lie in one band), the same LDS list and spans; a wave takes a (box, luma
 // row) and then a (box, chroma row) at a time. Past BCAP the global row is walked with the
 // predicate as written, the four-pixel rule included.
+// ES: bytes per sample -- 1, or 2 for surfaces of 16-bit words (include/vdmi.h at vd_yuv420_16), whose
+// restore copies whole words (pitches and offsets stay in bytes, steps in samples)
+template <int ES>
 __device__ __forceinline__ void restore_y(const uint8_t* in_y, uint8_t* out_y, const MaskNv12Args& a, int x, int y) {
-    out_y[(size_t)y * a.out_pitch + x] = in_y[(size_t)y * a.in_pitch + x];
+    if constexpr (ES == 2)
+        *(uint16_t*)(out_y + (size_t)y * a.out_pitch + 2 * (size_t)x) = *(const uint16_t*)(in_y + (size_t)y * a.in_pitch + 2 * (size_t)x);
+    else
+        out_y[(size_t)y * a.out_pitch + x] = in_y[(size_t)y * a.in_pitch + x];
 }
 
 // U and V by their offsets and steps (include/vdmi.h at vd_yuv420; NV12: V the byte after U, step 2)
 struct ChromaPtrs { const uint8_t* in_u; const uint8_t* in_v; uint8_t* out_u; uint8_t* out_v; };
+template <int ES>
 __device__ __forceinline__ void restore_uv(const ChromaPtrs& c, const MaskNv12Args& a, int cx, int cy) {
-    const size_t i = (size_t)cy * a.in_cp + (size_t)cx * a.in_step, o = (size_t)cy * a.out_cp + (size_t)cx * a.out_step;
-    c.out_u[o] = c.in_u[i];
-    c.out_v[o] = c.in_v[i];
+    const size_t i = (size_t)cy * a.in_cp + (size_t)cx * a.in_step * ES, o = (size_t)cy * a.out_cp + (size_t)cx * a.out_step * ES;
+    if constexpr (ES == 2) {
+        *(uint16_t*)(c.out_u + o) = *(const uint16_t*)(c.in_u + i);
+        *(uint16_t*)(c.out_v + o) = *(const uint16_t*)(c.in_v + i);
+    } else {
+        c.out_u[o] = c.in_u[i];
+        c.out_v[o] = c.in_v[i];
+    }
 }
 
+template <int ES>
 __global__ __launch_bounds__(THREADS) void mask_restore_nv12_kernel(MaskNv12Args a) {
     __shared__ int4 s_box[BCAP];
     __shared__ __attribute__((aligned(16))) int s_xl[BR][BCAP], s_xr[BR][BCAP];
@@ -298,7 +311,7 @@ __global__ __launch_bounds__(THREADS) void mask_restore_nv12_kernel(MaskNv12Args
                     hidden |= (x >= l.x && x < h.x) | (x >= l.y && x < h.y) | (x >= l.z && x < h.z) |
                               (x >= l.w && x < h.w);
                 }
-                if (!hidden) restore_y(in_y, out_y, a, x, by0 + r);
+                if (!hidden) restore_y<ES>(in_y, out_y, a, x, by0 + r);
             }
         }
         // chroma: the samples of a box's chroma rectangle that no span of the two luma rows hides
@@ -324,7 +337,7 @@ __global__ __launch_bounds__(THREADS) void mask_restore_nv12_kernel(MaskNv12Args
                                   (l.w < h.w && x >= (l.w >> 1) && x < ((h.w + 1) >> 1));
                     }
                 }
-                if (!hidden) restore_uv(chroma, a, x, cy);
+                if (!hidden) restore_uv<ES>(chroma, a, x, cy);
             }
         }
         return;
@@ -350,7 +363,7 @@ __global__ __launch_bounds__(THREADS) void mask_restore_nv12_kernel(MaskNv12Args
         for (long long p = tid; p < npx; p += THREADS) {
             const int y = y0 + (int)(p / bw), x = c.x + (int)(p % bw);
             if (in_ellipse(b, x, y)) continue;
-            if (!in_some_ellipse(x, y, k)) restore_y(in_y, out_y, a, x, y);
+            if (!in_some_ellipse(x, y, k)) restore_y<ES>(in_y, out_y, a, x, y);
         }
         // the band's chroma rows of cc_k: by the four luma pixels of each sample
         const int ccx1 = c.x >> 1, cbw = ((c.z + 1) >> 1) - ccx1;
@@ -360,7 +373,7 @@ __global__ __launch_bounds__(THREADS) void mask_restore_nv12_kernel(MaskNv12Args
             const int cy = cy0 + (int)(p / cbw), cx = ccx1 + (int)(p % cbw);
             bool hidden = false;
             for (int q = 0; q < 4 && !hidden; ++q) hidden = in_some_ellipse(2 * cx + (q & 1), 2 * cy + (q >> 1), -1);
-            if (!hidden) restore_uv(chroma, a, cx, cy);
+            if (!hidden) restore_uv<ES>(chroma, a, cx, cy);
         }
     }
 }
@@ -388,14 +401,22 @@ hipError_t vd_launch_mask_restore(const MaskArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t vd_launch_mask_restore_nv12(const MaskNv12Args& a, hipStream_t s) {
-    if (a.n <= 0 || a.h <= 0 || a.w <= 0 || (a.h & 1) || (a.w & 1) || a.in_pitch < (size_t)a.w ||
-        a.out_pitch < (size_t)a.w || !a.in || !a.out || !a.m_cnt || !a.m_xy || a.mcap <= 0 ||
+hipError_t vd_launch_mask_restore_nv12(const MaskNv12Args& a, hipStream_t s, int es1) {
+    const size_t es = es1 == 2 ? 2 : 1;
+    if (a.n <= 0 || a.h <= 0 || a.w <= 0 || (a.h & 1) || (a.w & 1) || a.in_pitch < (size_t)a.w * es ||
+        a.out_pitch < (size_t)a.w * es || !a.in || !a.out || !a.m_cnt || !a.m_xy || a.mcap <= 0 ||
         (a.in_step != 1 && a.in_step != 2) || (a.out_step != 1 && a.out_step != 2) ||
-        a.in_cp < (size_t)(a.w / 2) * a.in_step || a.out_cp < (size_t)(a.w / 2) * a.out_step)
+        a.in_cp < (size_t)(a.w / 2) * a.in_step * es || a.out_cp < (size_t)(a.w / 2) * a.out_step * es)
         return hipErrorInvalidValue;
     const long long blocks = (long long)((a.h + BR - 1) / BR) * a.n;
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(mask_restore_nv12_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, s, a);
+    if (es == 2) {
+        const uintptr_t m = (uintptr_t)a.in | (uintptr_t)a.out | a.in_pitch | a.out_pitch | a.in_cp | a.out_cp | a.in_uv |
+                            a.in_v | a.out_uv | a.out_v | a.in_stride | a.out_stride;
+        if (m & 1) return hipErrorInvalidValue;           // words would straddle
+        hipLaunchKernelGGL(mask_restore_nv12_kernel<2>, dim3((unsigned)blocks), dim3(THREADS), 0, s, a);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(mask_restore_nv12_kernel<1>, dim3((unsigned)blocks), dim3(THREADS), 0, s, a);
     return hipGetLastError();
 }

@@ -315,12 +315,12 @@ struct Ctx {
     // pass the NV12 descriptor through the same path
     using Nv12Dev = Yuv420Dev;
     // the caller's input surfaces on the device: as they are, or (host) staged packed in their own
-    // layout in stage_in (1.5 B/px)
-    int nv12_in(const vd_yuv420& d, int n, int h, int w, int where, Nv12Dev* o);
+    // layout in stage_in (1.5 B/px; 16-bit words: 3 B/px). d: the caller's surfaces, host or device
+    int nv12_in(const Nv12Dev& d, int n, int h, int w, int where, Nv12Dev* o);
     // where the output pass writes: the caller's surfaces, or (host) packed surfaces in stage_out ...
-    int nv12_out_begin(const vd_yuv420& d, int n, int h, int w, int where, Nv12Dev* o);
+    int nv12_out_begin(const Nv12Dev& d, int n, int h, int w, int where, Nv12Dev* o);
     // ... copied back plane by plane, the picture's bytes of every row only (queued; the caller synchronises)
-    int nv12_out_finish(const vd_yuv420& d, const Nv12Dev& o, int n, int h, int w, int where);
+    int nv12_out_finish(const Nv12Dev& d, const Nv12Dev& o, int n, int h, int w, int where);
     // the NV12 output pass behind the mask setting, what launch_shaped is to RGB frames: grow, the
     // rectangular pass (RECT_MOSAIC: nv12.hip, one launch; RECT_SMOOTH: smooth.hip, copy + box pass),
     // then under VD_MASK_ELLIPSE the restore of both planes; all family 1
@@ -516,7 +516,8 @@ struct Nv12Scope {
     Ctx* c;
     Nv12Scope(Ctx* ctx, const Ctx::Nv12Dev& d, int matrix, int range, bool on = true) : c(ctx) {
         if (!on) return;
-        c->nv12_src.on = d.nv12() ? 1 : 2;      // the NV12 letterbox kernels, or the ones for any layout
+        c->nv12_src.on = d.depth ? 3 : (d.nv12() ? 1 : 2);   // the NV12 letterbox kernels, the ones for any layout, or for 16-bit words
+        c->nv12_src.sh16 = d.depth ? d.shift + d.depth - 8 : 0;
         c->nv12_src.uv_offset = d.u;
         c->nv12_src.v_offset = d.v;
         c->nv12_src.cpitch = d.cpitch;
@@ -530,8 +531,10 @@ struct Nv12Scope {
 int vd_nv12_check(const char* who, const vd_nv12* d, int n, int h, int w, bool colour);
 // ... of a vd_yuv420 descriptor (the message names the field); extent: the bytes the n frames span
 int vd_yuv420_check(const char* who, const vd_yuv420* d, int n, int h, int w, bool colour, size_t* extent = nullptr);
+// ... of a vd_yuv420_16 descriptor
+int vd_yuv420_16_check(const char* who, const vd_yuv420_16* d, int n, int h, int w, bool colour, size_t* extent = nullptr);
 // bytes of source a letterbox reads per pixel of the frame rows it touches (timing work)
-static inline double vd_src_bpp(const Nv12Src& nv) { return nv.on ? 1.5 : 3.0; }
+static inline double vd_src_bpp(const Nv12Src& nv) { return nv.on == 3 ? 3.0 : (nv.on ? 1.5 : 3.0); }   // 16-bit words: 3 B/px too
 
 // a host list whose count[i] exceeds cap names boxes the caller does not hold: refused, never skipped silently
 int vd_count_check(const char* who, const int* count, int rows, int cap);

@@ -34,6 +34,8 @@
 // parameters, so no streaming loop branches on the layout; the NV12 -> NV12 instantiation is the
 // kernel as it was. 16-B accesses need base, both pitches, the plane offsets and the stride of
 // a surface aligned; otherwise, and in row tails, samples go byte by byte.
+// 10- and 12-bit surfaces (include/vdmi.h at vd_yuv420_16): the same kernel with ES = 2, a sample being a
+// 16-bit word -- pixelation copies whole words, so depth and shift play no part; see at ld16 below.
 // Past the capacities below -- a frame of more than NV12_LDS_BOXES boxes, a band that more than
 // NV12_BAND_BOXES boxes meet, slices of more than NV12_CELLS cells in a plane -- the band's samples
 // walk the whole list themselves (the generic path; same result).
@@ -109,13 +111,32 @@ __device__ __forceinline__ uint32_t yuv_swap16(uint32_t w) { return ((w & 0x00FF
 
 __device__ __forceinline__ int up_index(int d, double f, int s) { return min((int)floor(VD_DMUL((double)d, f)), s - 1); }
 
-template <bool VEC, int IS, int OS, bool SW>
+// 16-bit words (include/vdmi.h at vd_yuv420_16; ES == 2 below): pixelation is a copy of whole words, so
+// the kernel is the one above with a sample of 2 bytes -- a luma word, or a chroma pair u | v << 16 --
+// and every offset and pitch still in bytes. A lane moves 16 B of luma (8 words) and 8 chroma samples:
+// 16 B of the U plane and 16 B of the V plane on a planar side, 32 B of pairs on an interleaved one.
+__device__ __forceinline__ unsigned ld16(const uint8_t* p) { return *(const uint16_t*)p; }
+// two words of interleaved pairs (a0 b0 | a1 b1) <-> a word of a's and a word of b's
+__device__ __forceinline__ void yuv_split16(uint32_t w0, uint32_t w1, uint32_t& a, uint32_t& b) {
+    a = (w0 & 0xFFFFu) | (w1 << 16);
+    b = (w0 >> 16) | (w1 & 0xFFFF0000u);
+}
+__device__ __forceinline__ void yuv_join16(uint32_t a, uint32_t b, uint32_t& w0, uint32_t& w1) {
+    w0 = (a & 0xFFFFu) | (b << 16);
+    w1 = (a >> 16) | (b & 0xFFFF0000u);
+}
+
+template <int ES> struct CellOf { using Y = uint8_t; using C = uint16_t; };
+template <> struct CellOf<2> { using Y = uint16_t; using C = uint32_t; };
+
+// ES: bytes per sample (1: the 8-bit kernels, 2: 16-bit words in and out, always with SW)
+template <bool VEC, int IS, int OS, bool SW, int ES = 1>
 __global__ __launch_bounds__(256) void nv12_mosaic_kernel(Nv12MosaicArgs a) {
     __shared__ int4 s_q[2][NV12_LDS_BOXES];
     __shared__ uint32_t s_sz[2][NV12_LDS_BOXES];
     __shared__ BandBox s_band[NV12_BAND_BOXES];
-    __shared__ uint8_t s_cy[NV12_CELLS];
-    __shared__ uint16_t s_cuv[NV12_CELLS];
+    __shared__ typename CellOf<ES>::Y s_cy[NV12_CELLS];
+    __shared__ typename CellOf<ES>::C s_cuv[NV12_CELLS];
     __shared__ int s_nband, s_generic, s_tot[2];
 
     const int f = blockIdx.y, band = blockIdx.x, tid = threadIdx.x;
@@ -183,6 +204,15 @@ __global__ __launch_bounds__(256) void nv12_mosaic_kernel(Nv12MosaicArgs a) {
         nv_clip(a, f, k, n0, qq, ss);
         q = qq[P]; sz = ss[P];
     };
+    // the source sample of plane P at (y, x)
+    auto gather = [&](int P, int y, int x) -> unsigned {
+        if constexpr (ES == 2) {
+            const size_t o = (size_t)y * a.in_cp + (size_t)x * (2 * IS);
+            return P ? ld16(in_u + o) | (ld16(in_v + o) << 16) : ld16(in_y + (size_t)y * a.in_pitch + 2 * (size_t)x);
+        } else {
+            return P ? yuv_src<IS>(in_u, in_v, a.in_cp, y, x) : nv_src<0>(in_y, a.in_pitch, y, x);
+        }
+    };
     // (y, x) of plane P walked back through boxes [0, from)
     auto walk = [&](int P, int from, int& y, int& x) {
         for (int k = from - 1; k >= 0; --k) {
@@ -210,8 +240,8 @@ __global__ __launch_bounds__(256) void nv12_mosaic_kernel(Nv12MosaicArgs a) {
             int x = q.x + min((int)floor(VD_DMUL((double)ux, down_factor(bw, sw))), bw - 1);
             int y = q.y + min((int)floor(VD_DMUL((double)uy, down_factor(bh, sh))), bh - 1);
             walk(P, b.idx, y, x);
-            if (P) s_cuv[e] = (uint16_t)yuv_src<IS>(in_u, in_v, a.in_cp, y, x);
-            else s_cy[e] = (uint8_t)nv_src<0>(in_y, a.in_pitch, y, x);
+            if (P) s_cuv[e] = (typename CellOf<ES>::C)gather(1, y, x);
+            else s_cy[e] = (typename CellOf<ES>::Y)gather(0, y, x);
         }
         __syncthreads();
     }
@@ -222,7 +252,7 @@ __global__ __launch_bounds__(256) void nv12_mosaic_kernel(Nv12MosaicArgs a) {
             int yy = y, xx = x;
             walk(P, nb, yy, xx);
             if (yy == y && xx == x) return srcv;
-            return P ? yuv_src<IS>(in_u, in_v, a.in_cp, yy, xx) : nv_src<0>(in_y, a.in_pitch, yy, xx);
+            return gather(P, yy, xx);
         }
         for (int i = nband - 1; i >= 0; --i) {
             const BandBox& b = s_band[i];
@@ -246,6 +276,95 @@ __global__ __launch_bounds__(256) void nv12_mosaic_kernel(Nv12MosaicArgs a) {
         return false;
     };
 
+    if constexpr (ES == 2) {
+        // luma: 8 words per 16-B chunk
+        const int nch = (a.w + 7) / 8;
+        const int rows = r1[0] - r0[0];
+        for (int c = tid; c < rows * nch; c += 256) {
+            const int row = c / nch, ch = c - row * nch;
+            const int y = r0[0] + row, x0 = ch * 8, npx = min(8, a.w - x0);
+            const uint8_t* src = in_y + (size_t)y * a.in_pitch + (size_t)ch * 16;
+            uint8_t* dst = out_y + (size_t)y * a.out_pitch + (size_t)ch * 16;
+            const bool hit = (nband || generic) && touched(0, y, x0, x0 + npx);
+            if (VEC && npx == 8) {
+                uint4 v = *(const uint4*)src;
+                if (hit) {
+                    uint32_t wd[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const int sh = 16 * (i & 1);
+                        const unsigned nv = sample(0, y, x0 + i, (wd[i >> 1] >> sh) & 0xFFFFu);
+                        wd[i >> 1] = (wd[i >> 1] & ~(0xFFFFu << sh)) | (nv << sh);
+                    }
+                    v = make_uint4(wd[0], wd[1], wd[2], wd[3]);
+                }
+                *(uint4*)dst = v;
+            } else {
+                for (int i = 0; i < npx; ++i) {
+                    unsigned sv = ld16(src + 2 * i);
+                    if (hit) sv = sample(0, y, x0 + i, sv);
+                    *(uint16_t*)(dst + 2 * i) = (uint16_t)sv;
+                }
+            }
+        }
+        // chroma: 8 samples per lane, as U words and V words in registers
+        const int cw = a.w / 2;
+        const int cch = (cw + 7) / 8;
+        const int crows = r1[1] - r0[1];
+        for (int c = tid; c < crows * cch; c += 256) {
+            const int row = c / cch, ch = c - row * cch;
+            const int y = r0[1] + row, x0 = ch * 8, npx = min(8, cw - x0);
+            const bool hit = (nband || generic) && touched(1, y, x0, x0 + npx);
+            const size_t irow = (size_t)y * a.in_cp, orow = (size_t)y * a.out_cp;
+            if (VEC && npx == 8) {
+                uint32_t uu[4], vv[4];
+                if constexpr (IS == 1) {
+                    const uint4 p = *(const uint4*)(in_u + irow + (size_t)ch * 16);
+                    const uint4 q = *(const uint4*)(in_v + irow + (size_t)ch * 16);
+                    uu[0] = p.x; uu[1] = p.y; uu[2] = p.z; uu[3] = p.w;
+                    vv[0] = q.x; vv[1] = q.y; vv[2] = q.z; vv[3] = q.w;
+                } else {
+                    const uint4 p = *(const uint4*)(in_c + irow + (size_t)ch * 32);
+                    const uint4 q = *(const uint4*)(in_c + irow + (size_t)ch * 32 + 16);
+                    uint32_t* fa = isw ? vv : uu;       // the pairs' first words
+                    uint32_t* fb = isw ? uu : vv;
+                    yuv_split16(p.x, p.y, fa[0], fb[0]); yuv_split16(p.z, p.w, fa[1], fb[1]);
+                    yuv_split16(q.x, q.y, fa[2], fb[2]); yuv_split16(q.z, q.w, fa[3], fb[3]);
+                }
+                if (hit) {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const int sh = 16 * (i & 1);
+                        const unsigned sv = ((uu[i >> 1] >> sh) & 0xFFFFu) | (((vv[i >> 1] >> sh) & 0xFFFFu) << 16);
+                        const unsigned nv = sample(1, y, x0 + i, sv);
+                        uu[i >> 1] = (uu[i >> 1] & ~(0xFFFFu << sh)) | ((nv & 0xFFFFu) << sh);
+                        vv[i >> 1] = (vv[i >> 1] & ~(0xFFFFu << sh)) | ((nv >> 16) << sh);
+                    }
+                }
+                if constexpr (OS == 1) {
+                    *(uint4*)(out_u + orow + (size_t)ch * 16) = make_uint4(uu[0], uu[1], uu[2], uu[3]);
+                    *(uint4*)(out_v + orow + (size_t)ch * 16) = make_uint4(vv[0], vv[1], vv[2], vv[3]);
+                } else {
+                    const uint32_t* fa = osw ? vv : uu;
+                    const uint32_t* fb = osw ? uu : vv;
+                    uint32_t o[8];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) yuv_join16(fa[i], fb[i], o[2 * i], o[2 * i + 1]);
+                    *(uint4*)(out_c + orow + (size_t)ch * 32) = make_uint4(o[0], o[1], o[2], o[3]);
+                    *(uint4*)(out_c + orow + (size_t)ch * 32 + 16) = make_uint4(o[4], o[5], o[6], o[7]);
+                }
+            } else {
+                for (int i = 0; i < npx; ++i) {
+                    const size_t xi = (size_t)(x0 + i) * (2 * IS), xo = (size_t)(x0 + i) * (2 * OS);
+                    unsigned sv = ld16(in_u + irow + xi) | (ld16(in_v + irow + xi) << 16);
+                    if (hit) sv = sample(1, y, x0 + i, sv);
+                    *(uint16_t*)(out_u + orow + xo) = (uint16_t)sv;
+                    *(uint16_t*)(out_v + orow + xo) = (uint16_t)(sv >> 16);
+                }
+            }
+        }
+        return;
+    }
     // luma: 16 samples per 16-B chunk
     {
         const int nch = (a.w + 15) / 16;
@@ -418,15 +537,32 @@ static void launch_mosaic(const Nv12MosaicArgs& a, bool vec, dim3 grid, hipStrea
     else hipLaunchKernelGGL((nv12_mosaic_kernel<false, IS, OS, SW>), grid, dim3(256), 0, s, a);
 }
 
-hipError_t vd_launch_mosaic_nv12(const Nv12MosaicArgs& a, hipStream_t s) {
+template <int IS, int OS>
+static void launch_mosaic16(const Nv12MosaicArgs& a, bool vec, dim3 grid, hipStream_t s) {
+    if (vec) hipLaunchKernelGGL((nv12_mosaic_kernel<true, IS, OS, true, 2>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((nv12_mosaic_kernel<false, IS, OS, true, 2>), grid, dim3(256), 0, s, a);
+}
+
+hipError_t vd_launch_mosaic_nv12(const Nv12MosaicArgs& a, hipStream_t s, int depth) {
     // sw | sh << 16 holds 16 bits per axis; even sizes only (the chroma planes are (h/2) x (w/2) samples)
+    const size_t es = depth ? 2 : 1;
     if (a.n <= 0 || a.h <= 0 || a.w <= 0 || (a.h & 1) || (a.w & 1) || a.h > 65534 || a.w > 65534 || a.level < 1 ||
-        a.in_pitch < (size_t)a.w || a.out_pitch < (size_t)a.w || (a.in_step != 1 && a.in_step != 2) ||
-        (a.out_step != 1 && a.out_step != 2) || a.in_cp < (size_t)(a.w / 2) * a.in_step ||
-        a.out_cp < (size_t)(a.w / 2) * a.out_step)
+        a.in_pitch < (size_t)a.w * es || a.out_pitch < (size_t)a.w * es || (a.in_step != 1 && a.in_step != 2) ||
+        (a.out_step != 1 && a.out_step != 2) || a.in_cp < (size_t)(a.w / 2) * a.in_step * es ||
+        a.out_cp < (size_t)(a.w / 2) * a.out_step * es)
         return hipErrorInvalidValue;
     const bool vec = yuv_vec_ok(a.src()) && yuv_vec_ok(a.dst());
     const dim3 grid((a.h + NV12_ROWS - 1) / NV12_ROWS, a.n);
+    if (depth) {   // words: every byte quantity even (the descriptor checks), or the word accesses would straddle
+        const uintptr_t m = (uintptr_t)a.in | (uintptr_t)a.out | a.in_pitch | a.out_pitch | a.in_cp | a.out_cp | a.in_uv |
+                            a.in_v | a.out_uv | a.out_v | a.in_stride | a.out_stride;
+        if (m & 1) return hipErrorInvalidValue;
+        if (a.in_step == 2 && a.out_step == 2) launch_mosaic16<2, 2>(a, vec, grid, s);
+        else if (a.in_step == 2) launch_mosaic16<2, 1>(a, vec, grid, s);
+        else if (a.out_step == 2) launch_mosaic16<1, 2>(a, vec, grid, s);
+        else launch_mosaic16<1, 1>(a, vec, grid, s);
+        return hipGetLastError();
+    }
     if (a.nv12()) launch_mosaic<2, 2, false>(a, vec, grid, s);
     else if (a.in_step == 2 && a.out_step == 2) launch_mosaic<2, 2, true>(a, vec, grid, s);
     else if (a.in_step == 2) launch_mosaic<2, 1, true>(a, vec, grid, s);

@@ -95,14 +95,32 @@ struct RowYuv {
     }
 };
 
+// 10- and 12-bit 4:2:0 (include/vdmi.h at vd_yuv420_16): FrameYuv over 16-bit words -- pitches and
+// offsets in bytes, `step` in samples. Detection sees D(S): the 8-bit sample (word >> sh) & 255 with
+// sh = shift + depth - 8, which also drops the unused bits. A staged row is reduced to those bytes on
+// its way into LDS, so the row slots and the tap code are FrameYuv's and RowYuv's.
+struct FrameYuv16 {
+    const uint8_t* y; const uint8_t* u; const uint8_t* v; size_t pitch, cpitch; int step, sh; Nv12Coef k;
+    __device__ __forceinline__ static int s8(const uint8_t* p, int sh) { return (int)(((unsigned)*(const uint16_t*)p >> sh) & 255u); }
+    __device__ __forceinline__ void get(int yy, int x, int o[3]) const {
+        const size_t c = (size_t)(yy >> 1) * cpitch + (size_t)(x >> 1) * step * 2;
+        vd_nv12_rgb(k, s8(y + (size_t)yy * pitch + 2 * (size_t)x, sh), s8(u + c, sh), s8(v + c, sh), o);
+    }
+    __device__ __forceinline__ static int row_bytes(int iw) { return FrameYuv::row_bytes(iw); }
+};
+
 template <int NV> struct SrcOf { using Frame = FrameRgb; using Row = RowRgb; };          // LetterboxArgs::nv.on
 template <> struct SrcOf<1> { using Frame = FrameNv12; using Row = RowNv12; };
 template <> struct SrcOf<2> { using Frame = FrameYuv; using Row = RowYuv; };
+template <> struct SrcOf<3> { using Frame = FrameYuv16; using Row = RowYuv; };
 
 // frame f of the batch
 template <int NV>
 __device__ __forceinline__ typename SrcOf<NV>::Frame lb_frame(const LetterboxArgs& a, int f) {
-    if constexpr (NV == 2) {
+    if constexpr (NV == 3) {
+        const uint8_t* b = a.src + (size_t)f * a.nv.frame_stride;
+        return FrameYuv16{b, b + a.nv.uv_offset, b + a.nv.v_offset, a.pitch, a.nv.cpitch, a.nv.step, a.nv.sh16, a.nv.k};
+    } else if constexpr (NV == 2) {
         const uint8_t* b = a.src + (size_t)f * a.nv.frame_stride;
         return FrameYuv{b, b + a.nv.uv_offset, b + a.nv.v_offset, a.pitch, a.nv.cpitch, a.nv.step, a.nv.k};
     } else if constexpr (NV == 1) {
@@ -116,7 +134,7 @@ __device__ __forceinline__ typename SrcOf<NV>::Frame lb_frame(const LetterboxArg
 // staged row k of `lrow` (rows of RS bytes)
 template <int NV>
 __device__ __forceinline__ typename SrcOf<NV>::Row lb_row(const LetterboxArgs& a, const uint8_t* lrow, int k, int RS) {
-    if constexpr (NV == 2) {
+    if constexpr (NV == 2 || NV == 3) {
         const int c0 = FrameYuv::luma_bytes(a.iw);
         if (a.nv.step == 2)   // the pair row from the lower pointer: the other channel is its next byte
             return RowYuv{lrow + k * RS, c0 + (a.nv.uv_offset > a.nv.v_offset ? 1 : 0),
@@ -312,6 +330,39 @@ __device__ __forceinline__ void lb_stage_row(const LetterboxArgs& a, const Frame
     } else {
         lb_stage(dst + c0, img.u + cr, a.iw / 2);
         lb_stage(dst + c0 + (FrameYuv::row_bytes(a.iw) - c0) / 2, img.v + cr, a.iw / 2);
+    }
+}
+
+// n words of a source row into LDS as the n bytes (word >> sh) & 255: 16-B loads (8 words, 8 bytes
+// out) where the row start is aligned
+__device__ __forceinline__ void lb_stage16(uint8_t* dst, const uint8_t* src, int n, int sh) {
+    if (((uintptr_t)src & 15) == 0) {
+        const int nch = (n + 7) / 8;
+        for (int i = threadIdx.x; i < nch; i += 256) {
+            if (8 * i + 8 <= n) {
+                const uint4 v = *(const uint4*)(src + 16 * i);
+                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+                uint32_t b[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) b[k] = ((w[k] >> sh) & 255u) | (((w[k] >> (16 + sh)) & 255u) << 8);
+                *(uint2*)(dst + 8 * i) = make_uint2(b[0] | (b[1] << 16), b[2] | (b[3] << 16));
+            } else {
+                for (int x = 8 * i; x < n; ++x) dst[x] = (uint8_t)FrameYuv16::s8(src + 2 * x, sh);
+            }
+        }
+    } else {
+        for (int i = threadIdx.x; i < n; i += 256) dst[i] = (uint8_t)FrameYuv16::s8(src + 2 * i, sh);
+    }
+}
+__device__ __forceinline__ void lb_stage_row(const LetterboxArgs& a, const FrameYuv16& img, int row, uint8_t* dst) {
+    const int c0 = FrameYuv::luma_bytes(a.iw);
+    const size_t cr = (size_t)(row >> 1) * img.cpitch;
+    lb_stage16(dst, img.y + (size_t)row * a.pitch, a.iw, img.sh);
+    if (img.step == 2) {
+        lb_stage16(dst + c0, (img.u < img.v ? img.u : img.v) + cr, a.iw, img.sh);
+    } else {
+        lb_stage16(dst + c0, img.u + cr, a.iw / 2, img.sh);
+        lb_stage16(dst + c0 + (FrameYuv::row_bytes(a.iw) - c0) / 2, img.v + cr, a.iw / 2, img.sh);
     }
 }
 
@@ -550,14 +601,15 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const T* x, int xh, int
 // bytes of one staged source row (RGB: the pixels; NV12: the luma row and its chroma row, 16-B aligned each);
 // at most LB_LDS_MAX whenever iw * 3 <= LB_LDS_MAX
 static size_t lb_row_bytes(const LetterboxArgs& a) {
-    if (a.nv.on == 2) return (size_t)((a.iw + 15) / 16 * 16) + 2 * (size_t)((a.iw / 2 + 15) / 16 * 16);   // FrameYuv::row_bytes
+    if (a.nv.on == 2 || a.nv.on == 3) return (size_t)((a.iw + 15) / 16 * 16) + 2 * (size_t)((a.iw / 2 + 15) / 16 * 16);   // FrameYuv::row_bytes
     return a.nv.on ? 2 * (size_t)((a.iw + 15) / 16 * 16) : (size_t)((a.iw * 3 + 15) / 16 * 16);
 }
 
 // a launch of kernel K<nv.on>(args...): the instantiation for the frames' pixel source
 #define LB_LAUNCH(K, on, grid, lds, s, ...)                                                          \
     do {                                                                                             \
-        if ((on) == 2) hipLaunchKernelGGL(K<2>, grid, dim3(256), lds, s, __VA_ARGS__);               \
+        if ((on) == 3) hipLaunchKernelGGL(K<3>, grid, dim3(256), lds, s, __VA_ARGS__);               \
+        else if ((on) == 2) hipLaunchKernelGGL(K<2>, grid, dim3(256), lds, s, __VA_ARGS__);          \
         else if ((on) == 1) hipLaunchKernelGGL(K<1>, grid, dim3(256), lds, s, __VA_ARGS__);          \
         else hipLaunchKernelGGL(K<0>, grid, dim3(256), lds, s, __VA_ARGS__);                         \
     } while (0)
@@ -611,6 +663,8 @@ hipError_t vd_launch_letterbox_pair(const LetterboxArgs& a0, const LetterboxArgs
                                   4 * LB_LDS_MAX);
         (void)hipFuncSetAttribute((const void*)letterbox_s2d_pair_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   4 * LB_LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)letterbox_s2d_pair_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  4 * LB_LDS_MAX);
         return true;
     }();
     (void)attr;
@@ -632,6 +686,8 @@ hipError_t vd_launch_letterbox(const LetterboxArgs& a0, hipStream_t s) {
             (void)hipFuncSetAttribute((const void*)letterbox_s2d_lds_kernel<1>,
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 4 * LB_LDS_MAX);
             (void)hipFuncSetAttribute((const void*)letterbox_s2d_lds_kernel<2>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 4 * LB_LDS_MAX);
+            (void)hipFuncSetAttribute((const void*)letterbox_s2d_lds_kernel<3>,
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 4 * LB_LDS_MAX);
             return true;
         }();

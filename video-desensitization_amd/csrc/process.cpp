@@ -182,14 +182,14 @@ int Ctx::launch_nv12_pass(const Nv12Dev& in, const Nv12Dev& out, int n, int h, i
     hipError_t e = hipSuccess;
     if (pass == RECT_SMOOTH) {   // the copy carries the frames' bytes, the box pass's follow from the boxes
         for (int stage = 0; stage < 2 && e == hipSuccess; ++stage) {
-            t_begin(1, stage == 0 ? 2.0 * 1.5 * n * (double)h * w : 0);
-            e = vd_launch_smooth_nv12(a, stage, stream);
+            t_begin(1, stage == 0 ? 2.0 * 1.5 * in.es() * n * (double)h * w : 0);
+            e = vd_launch_smooth_nv12(a, stage, stream, in.depth, in.shift);
             t_end();
         }
         if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "nv12 smooth: %s", hipGetErrorString(e));
     } else {
-        t_begin(1, 2.0 * 1.5 * n * (double)h * w);
-        e = vd_launch_mosaic_nv12(a, stream);
+        t_begin(1, 2.0 * 1.5 * in.es() * n * (double)h * w);
+        e = vd_launch_mosaic_nv12(a, stream, in.depth);
         t_end();
         if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "nv12 mosaic: %s", hipGetErrorString(e));
     }
@@ -201,7 +201,7 @@ int Ctx::launch_nv12_pass(const Nv12Dev& in, const Nv12Dev& out, int n, int h, i
     m.n = n; m.h = h; m.w = w;
     m.m_cnt = mask_last.m_cnt; m.m_xy = mask_last.m_xy; m.mcap = mask_last.mcap;
     t_begin(1, 0);               // as the RGB restore: its bytes follow from the boxes
-    e = vd_launch_mask_restore_nv12(m, stream);
+    e = vd_launch_mask_restore_nv12(m, stream, in.es());
     t_end();
     if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "nv12 mask restore: %s", hipGetErrorString(e));
     return VD_OK;
@@ -329,7 +329,8 @@ struct LeadCall {
 // point), so the letterbox and the output launches differ; `in` / `out` / `pitch` are not used. Together
 // with a LeadCall (vd_process_lead_nv12) `out` describes the m emitted surfaces, NULL when m == 0.
 struct Nv12Call {
-    const vd_yuv420* in; const vd_yuv420* out;   // any layout of vd_yuv420 (the *_nv12 entries: the NV12 one)
+    const Yuv420Dev* in; const Yuv420Dev* out;   // any layout of vd_yuv420 (the *_nv12 entries: the NV12 one) or vd_yuv420_16
+    int matrix, range;                           // of `in`
 };
 
 static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh, int fw, size_t pitch, int where,
@@ -380,7 +381,7 @@ static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh
         d = ctx->frames_to_device(in, n, fh, pitch, where, &rc);
         if (rc) return rc;
     }
-    const Nv12Scope nv_scope(ctx, nin, nv ? nv->in->matrix : 0, nv ? nv->in->range : 0, nv != nullptr);
+    const Nv12Scope nv_scope(ctx, nin, nv ? nv->matrix : 0, nv ? nv->range : 0, nv != nullptr);
     // Face and plate branches run concurrently (the reference submits them to two
     // threads, combine_detect.py:214-217): plates on stream2, forked/joined by events.
     const bool fork = do_faces && do_plates;
@@ -543,18 +544,35 @@ int vd_process(vd_ctx* h, const uint8_t* in, uint8_t* out, int n, int fh, int fw
 // One path serves both families of entries. A *_nv12 entry checks the vd_nv12 it was given (its own
 // rules and messages) and goes on with the NV12 descriptor of the general form; a *_yuv420 entry
 // checks the vd_yuv420. extent: the bytes the n frames span, for the overlap rule.
-struct YuvDesc { vd_yuv420 d; size_t extent; };
-static int yuv_desc(const char* who, const vd_nv12* nv, const vd_yuv420* yu, bool nv_entry, int n, int fh, int fw,
-                    bool colour, YuvDesc* o) {
+// A *_yuv420_16 entry checks the vd_yuv420_16 and goes on with its surfaces of 16-bit words (d.depth != 0).
+struct YuvDesc { Yuv420Dev d; int matrix, range; size_t extent; };
+// the descriptors a 4:2:0 entry was given: the one of its family is set
+struct YuvIn { const vd_nv12* nv; const vd_yuv420* yu; const vd_yuv420_16* y16; };
+static int yuv_desc(const char* who, const YuvIn& g, bool nv_entry, int n, int fh, int fw, bool colour, YuvDesc* o) {
     int rc;
     if (nv_entry) {
-        if ((rc = vd_nv12_check(who, nv, n, fh, fw, colour))) return rc;
-        o->d = vd_yuv420_of_nv12(*nv);
-        o->extent = (size_t)n * nv->frame_stride;
+        if ((rc = vd_nv12_check(who, g.nv, n, fh, fw, colour))) return rc;
+        o->d = vd_yuv420_dev(vd_yuv420_of_nv12(*g.nv));
+        o->matrix = g.nv->matrix; o->range = g.nv->range;
+        o->extent = (size_t)n * g.nv->frame_stride;
         return VD_OK;
     }
-    if ((rc = vd_yuv420_check(who, yu, n, fh, fw, colour, &o->extent))) return rc;
-    o->d = *yu;
+    if (g.y16) {
+        if ((rc = vd_yuv420_16_check(who, g.y16, n, fh, fw, colour, &o->extent))) return rc;
+        o->d = vd_yuv420_dev(*g.y16);
+        o->matrix = g.y16->matrix; o->range = g.y16->range;
+        return VD_OK;
+    }
+    if ((rc = vd_yuv420_check(who, g.yu, n, fh, fw, colour, &o->extent))) return rc;
+    o->d = vd_yuv420_dev(*g.yu);
+    o->matrix = g.yu ? g.yu->matrix : 0; o->range = g.yu ? g.yu->range : 0;
+    return VD_OK;
+}
+// a 16-bit call keeps its format: no depth or shift conversion between in and out
+static int yuv_same_format(const char* who, const YuvDesc& in, const YuvDesc& out) {
+    if (in.d.depth != out.d.depth || in.d.shift != out.d.shift)
+        return vd_set_error(VD_ERR_ARG, "%s: depth and shift of out (%d, %d) must equal in's (%d, %d): no depth conversion",
+                            who, out.d.depth, out.d.shift, in.d.depth, in.d.shift);
     return VD_OK;
 }
 
@@ -575,18 +593,18 @@ static int nv12_blur_check(const char* who, const YuvDesc& in, const YuvDesc& ou
     return VD_OK;
 }
 
-static int process_420(Ctx* ctx, const char* who, bool nv_entry, const vd_nv12* nin, const vd_nv12* nout,
-                       const vd_yuv420* yin, const vd_yuv420* yout, int n, int fh, int fw, int where, int flags,
-                       vd_boxes* faces, vd_boxes* plates) {
+static int process_420(Ctx* ctx, const char* who, bool nv_entry, const YuvIn& gin, const YuvIn& gout, int n, int fh, int fw,
+                       int where, int flags, vd_boxes* faces, vd_boxes* plates) {
     if (where != VD_HOST && where != VD_DEVICE) return vd_set_error(VD_ERR_ARG, "%s: bad where", who);
     YuvDesc in{}, out{};
-    int rc = yuv_desc(who, nin, yin, nv_entry, n, fh, fw, true, &in);
+    int rc = yuv_desc(who, gin, nv_entry, n, fh, fw, true, &in);
     if (rc) return rc;
     const bool blur = flags & VD_PROC_MOSAIC;
     if (blur) {
-        if (!(nv_entry ? (const void*)nout : (const void*)yout))
+        if (!gout.nv && !gout.yu && !gout.y16)
             return vd_set_error(VD_ERR_ARG, "%s: MOSAIC needs an output descriptor", who);
-        if ((rc = yuv_desc(who, nout, yout, nv_entry, n, fh, fw, false, &out))) return rc;
+        if ((rc = yuv_desc(who, gout, nv_entry, n, fh, fw, false, &out))) return rc;
+        if ((rc = yuv_same_format(who, in, out))) return rc;
         if ((rc = nv12_blur_check(who, in, out, where, true, ctx->nv12_cfg_pass()))) return rc;
     }
     if (((flags & VD_PROC_FACES) && ctx->faces_tiled()) || ((flags & VD_PROC_PLATES) && ctx->plates_tiled()))
@@ -597,7 +615,7 @@ static int process_420(Ctx* ctx, const char* who, bool nv_entry, const vd_nv12* 
     if (ctx->lead.pend)
         return vd_set_error(VD_ERR_STATE, "%s: %d frames are pending in the look-ahead ring (flush first)", who,
                             ctx->lead.pend);
-    const Nv12Call nv{&in.d, blur ? &out.d : nullptr};
+    const Nv12Call nv{&in.d, blur ? &out.d : nullptr, in.matrix, in.range};
     return process_impl(ctx, nullptr, nullptr, n, fh, fw, 0, where, flags, faces, plates, nullptr, &nv);
 }
 
@@ -605,28 +623,38 @@ int vd_process_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n, int
                     vd_boxes* faces, vd_boxes* plates) {
     Ctx* ctx = (Ctx*)h;
     VD_ENTRY(ctx);
-    return process_420(ctx, "vd_process_nv12", true, in, out, nullptr, nullptr, n, fh, fw, where, flags, faces, plates);
+    return process_420(ctx, "vd_process_nv12", true, YuvIn{in}, YuvIn{out}, n, fh, fw, where, flags, faces, plates);
 }
 
 int vd_process_yuv420(vd_ctx* h, const vd_yuv420* in, const vd_yuv420* out, int n, int fh, int fw, int where, int flags,
                       vd_boxes* faces, vd_boxes* plates) {
     Ctx* ctx = (Ctx*)h;
     VD_ENTRY(ctx);
-    return process_420(ctx, "vd_process_yuv420", false, nullptr, nullptr, in, out, n, fh, fw, where, flags, faces, plates);
+    return process_420(ctx, "vd_process_yuv420", false, YuvIn{nullptr, in}, YuvIn{nullptr, out}, n, fh, fw, where, flags, faces,
+                       plates);
+}
+
+int vd_process_yuv420_16(vd_ctx* h, const vd_yuv420_16* in, const vd_yuv420_16* out, int n, int fh, int fw, int where,
+                         int flags, vd_boxes* faces, vd_boxes* plates) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (!in) return vd_set_error(VD_ERR_ARG, "vd_process_yuv420_16: 16-bit 4:2:0 frames: null descriptor or base");
+    return process_420(ctx, "vd_process_yuv420_16", false, YuvIn{nullptr, nullptr, in}, YuvIn{nullptr, nullptr, out}, n, fh, fw,
+                       where, flags, faces, plates);
 }
 
 // The stand-alone blurring calls: pass `pass` over the caller's surfaces and one box list, with
 // blur_entry's staging, capacity and overlap rules.
-static int nv12_blur_entry(Ctx* ctx, const char* who, bool nv_entry, const vd_nv12* nin, const vd_nv12* nout,
-                           const vd_yuv420* yin, const vd_yuv420* yout, int n, int fh, int fw,
+static int nv12_blur_entry(Ctx* ctx, const char* who, bool nv_entry, const YuvIn& gin, const YuvIn& gout, int n, int fh, int fw,
                            int where, const vd_boxes* boxes, int pass, int level, int cells) {
     if (where != VD_HOST && where != VD_DEVICE) return vd_set_error(VD_ERR_ARG, "%s: bad where", who);
     if (!boxes) return vd_set_error(VD_ERR_ARG, "%s: null argument", who);
     if (level <= 0) return vd_set_error(VD_ERR_ARG, "%s: bad geometry", who);
     YuvDesc in{}, out{};
-    int rc = yuv_desc(who, nin, yin, nv_entry, n, fh, fw, false, &in);
+    int rc = yuv_desc(who, gin, nv_entry, n, fh, fw, false, &in);
     if (rc) return rc;
-    if ((rc = yuv_desc(who, nout, yout, nv_entry, n, fh, fw, false, &out))) return rc;
+    if ((rc = yuv_desc(who, gout, nv_entry, n, fh, fw, false, &out))) return rc;
+    if ((rc = yuv_same_format(who, in, out))) return rc;
     if ((rc = nv12_blur_check(who, in, out, where, false, pass))) return rc;
     if (pass == Ctx::RECT_SMOOTH && (fh > 32768 || fw > 32768 || level > 32768))
         return vd_set_error(VD_ERR_ARG, "%s: the smooth blur needs h, w <= 32768 and level in [1, 32768] (got %d x %d, "
@@ -648,7 +676,7 @@ int vd_mosaic_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n, int 
     Ctx* ctx = (Ctx*)h;
     VD_ENTRY(ctx);
     // the context's blur mode chooses the pass, as it does for vd_process_nv12
-    return nv12_blur_entry(ctx, "vd_mosaic_nv12", true, in, out, nullptr, nullptr, n, fh, fw, where, boxes,
+    return nv12_blur_entry(ctx, "vd_mosaic_nv12", true, YuvIn{in}, YuvIn{out}, n, fh, fw, where, boxes,
                            ctx->nv12_cfg_pass(), level, ctx->cells);
 }
 
@@ -656,8 +684,24 @@ int vd_mosaic_yuv420(vd_ctx* h, const vd_yuv420* in, const vd_yuv420* out, int n
                      const vd_boxes* boxes, int level) {
     Ctx* ctx = (Ctx*)h;
     VD_ENTRY(ctx);
-    return nv12_blur_entry(ctx, "vd_mosaic_yuv420", false, nullptr, nullptr, in, out, n, fh, fw, where, boxes,
+    return nv12_blur_entry(ctx, "vd_mosaic_yuv420", false, YuvIn{nullptr, in}, YuvIn{nullptr, out}, n, fh, fw, where, boxes,
                            ctx->nv12_cfg_pass(), level, ctx->cells);
+}
+
+// a NULL vd_yuv420_16 would read as "no descriptor of this family": refuse it here
+static int y16_null(const char* who, const vd_yuv420_16* in, const vd_yuv420_16* out) {
+    if (!in || !out) return vd_set_error(VD_ERR_ARG, "%s: 16-bit 4:2:0 frames: null descriptor or base", who);
+    return VD_OK;
+}
+
+int vd_mosaic_yuv420_16(vd_ctx* h, const vd_yuv420_16* in, const vd_yuv420_16* out, int n, int fh, int fw, int where,
+                        const vd_boxes* boxes, int level) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    int rc = y16_null("vd_mosaic_yuv420_16", in, out);
+    if (rc) return rc;
+    return nv12_blur_entry(ctx, "vd_mosaic_yuv420_16", false, YuvIn{nullptr, nullptr, in}, YuvIn{nullptr, nullptr, out}, n, fh,
+                           fw, where, boxes, ctx->nv12_cfg_pass(), level, ctx->cells);
 }
 
 static int smooth_420_args(const char* who, int level, int cells) {
@@ -673,7 +717,7 @@ int vd_smooth_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n, int 
     VD_ENTRY(ctx);
     int rc = smooth_420_args("vd_smooth_nv12", level, cells);
     if (rc) return rc;
-    return nv12_blur_entry(ctx, "vd_smooth_nv12", true, in, out, nullptr, nullptr, n, fh, fw, where, boxes,
+    return nv12_blur_entry(ctx, "vd_smooth_nv12", true, YuvIn{in}, YuvIn{out}, n, fh, fw, where, boxes,
                            Ctx::RECT_SMOOTH, level, cells);
 }
 
@@ -683,8 +727,19 @@ int vd_smooth_yuv420(vd_ctx* h, const vd_yuv420* in, const vd_yuv420* out, int n
     VD_ENTRY(ctx);
     int rc = smooth_420_args("vd_smooth_yuv420", level, cells);
     if (rc) return rc;
-    return nv12_blur_entry(ctx, "vd_smooth_yuv420", false, nullptr, nullptr, in, out, n, fh, fw, where, boxes,
+    return nv12_blur_entry(ctx, "vd_smooth_yuv420", false, YuvIn{nullptr, in}, YuvIn{nullptr, out}, n, fh, fw, where, boxes,
                            Ctx::RECT_SMOOTH, level, cells);
+}
+
+int vd_smooth_yuv420_16(vd_ctx* h, const vd_yuv420_16* in, const vd_yuv420_16* out, int n, int fh, int fw, int where,
+                        const vd_boxes* boxes, int level, int cells) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    int rc = smooth_420_args("vd_smooth_yuv420_16", level, cells);
+    if (rc) return rc;
+    if ((rc = y16_null("vd_smooth_yuv420_16", in, out))) return rc;
+    return nv12_blur_entry(ctx, "vd_smooth_yuv420_16", false, YuvIn{nullptr, nullptr, in}, YuvIn{nullptr, nullptr, out}, n, fh,
+                           fw, where, boxes, Ctx::RECT_SMOOTH, level, cells);
 }
 
 int vd_process_lead(vd_ctx* h, const uint8_t* in, int n, int fh, int fw, size_t pitch, int where, int flags,
@@ -778,12 +833,12 @@ int vd_process_lead_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n
     }
     const LeadCall lc{flush, m};
     if (n > 0) {
-        const vd_yuv420 yin = vd_yuv420_of_nv12(*in), yout = out ? vd_yuv420_of_nv12(*out) : vd_yuv420{};
-        const Nv12Call nv{&yin, out ? &yout : nullptr};
+        const Yuv420Dev yin = vd_yuv420_dev(vd_yuv420_of_nv12(*in)), yout = out ? vd_yuv420_dev(vd_yuv420_of_nv12(*out)) : Yuv420Dev{};
+        const Nv12Call nv{&yin, out ? &yout : nullptr, in->matrix, in->range};
         rc = process_impl(ctx, nullptr, nullptr, n, fh, fw, 0, where, flags, faces, plates, &lc, &nv);
     } else {      // flush alone: the pending surfaces leave, no detection
         Ctx::Nv12Dev nin{}, nout{};
-        const vd_yuv420 yout = vd_yuv420_of_nv12(*out);
+        const Yuv420Dev yout = vd_yuv420_dev(vd_yuv420_of_nv12(*out));
         if ((rc = ctx->nv12_out_begin(yout, m, fh, fw, where, &nout))) return rc;
         if ((rc = ctx->lead_step(VD_LEAD_MODE_NV12, nullptr, nullptr, 0, fh, fw, 0, 1, nullptr, nullptr, 0, nullptr, nullptr,
                                  0, &nin, &nout)))

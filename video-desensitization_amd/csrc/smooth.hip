@@ -76,6 +76,12 @@
 //   smooth_box_yuv420_kernel  grid (SLOTS, frames, 3 * PARTS): luma, U, V.
 //   the copy                  between two layouts is the pixelation launch of nv12.hip with no lists:
 //                             it already streams every sample from the one layout into the other.
+//
+// 10- and 12-bit 4:2:0 frames (include/vdmi.h at vd_yuv420_16): the formulas above on the values
+// v = (word >> shift) & (2^depth - 1) of 16-bit words, Q(depth).4 means, the result written as
+// result << shift. The widths are worked out at smooth_box_body (ES == 2) and in DESIGN.md.
+//   smooth_box_yuv16_kernel   grid (SLOTS, frames, 3 * PARTS): luma, U, V, each a C = 1 pass over words.
+//   the copy                  is the pixelation launch of words with no lists.
 #include "vd_kernel.h"
 #include "vdmi.h"
 
@@ -90,6 +96,7 @@ constexpr int PARTS = 8;         // workgroups a large box is shared among (band
 constexpr int PART_PX = 16384;   // ... one per this many pixels of the clipped box
 constexpr int BEAT_CAP = 128;    // beating boxes listed in LDS; more: the global list is walked per pixel
 constexpr int F32_MAX = 4096;    // largest f whose cell sums fit uint32
+constexpr int F16_MAX = 1024;    // ... for samples of up to 12 bits: 4095 * 1024^2 < 2^32
 
 // a plane of the batch: frame f at + f * stride, rows of `pitch` bytes
 struct SmoothPlane {
@@ -208,9 +215,17 @@ __device__ __forceinline__ uint32_t across(const uint32_t* mean, int j, int sw, 
 // plane of any 4:2:0 layout, planar or the one channel of interleaved pairs. Sums, means and
 // interpolation are per channel in every form, so the C = 1, CHROMA, STEP pass over U and then over
 // V computes exactly the bytes of the C = 2 pass over the pairs.
-template <int C, bool CHROMA, bool STEP = false>
+// ES == 2 (C == 1 with STEP): the plane holds 16-bit words (include/vdmi.h at vd_yuv420_16), a sample's
+// value is v = (word >> shift) & (2^depth - 1), depth <= 12. The same integers one size up: a column's
+// partial sum is at most 4095 * 32768 < 2^27, a cell's sum S <= 4095 * f^2 fits uint32 up to F16_MAX
+// (64-bit LDS sums above it, for any cell count), a mean is Q12.4 <= 65520, t <= 65520, and
+// T = (2f - s) t0 + s t1 + 16f <= 65536 * 65520 + 16 * 32768 < 2^32. A sample is written as
+// result << shift, its unused bits zero.
+template <int C, bool CHROMA, bool STEP = false, int ES = 1>
 __device__ __forceinline__ void smooth_box_body(const SmoothArgs& a, const SmoothPlane& pl, int part, uint32_t* s_cell,
-                                                int4* s_beat, int& s_nbeat, int in_step = 1, int out_step = 1) {
+                                                int4* s_beat, int& s_nbeat, int in_step = 1, int out_step = 1,
+                                                int depth = 8, int shift = 0) {
+    const uint32_t vmask = (1u << depth) - 1u;
     const int fr = blockIdx.y, tid = threadIdx.x;
     int n0;
     const int nb = frame_boxes(a, fr, n0);
@@ -229,9 +244,9 @@ __device__ __forceinline__ void smooth_box_body(const SmoothArgs& a, const Smoot
         const int bw = c.z - c.x, bh = c.w - c.y;
         const int sw = (bw + f - 1) / f, sh = (bh + f - 1) / f;
         const int ncell = sw * sh * C;
-        const bool wide = f > F32_MAX;                     // 64-bit sums, at most 8 x 8 cells
+        const bool wide = f > (ES == 2 ? F16_MAX : F32_MAX);   // 64-bit sums (8-bit samples: at most 8 x 8 cells)
         const int gmax = a.cells + (CHROMA ? 1 : 0);       // the chroma grid bound (header)
-        if (sw > gmax || sh > gmax || (wide && ncell > THREADS)) continue;   // the LDS holds that many: cannot happen for h, w <= 32768
+        if (sw > gmax || sh > gmax || (ES == 1 && wide && ncell > THREADS)) continue;   // the LDS holds that many: cannot happen for h, w <= 32768
         // a large box is cut into bands of whole cell rows, one per part (blockIdx.z)
         const int nparts = min(min(PARTS, sh), max(1, (int)(((long long)bw * bh) / PART_PX)));
         if (part >= nparts) continue;
@@ -273,7 +288,7 @@ __device__ __forceinline__ void smooth_box_body(const SmoothArgs& a, const Smoot
         const int jA = part * sh / nparts, jB = (part + 1) * sh / nparts;
         int ya, yb;
         my_rows(max(jA - 1, 0) * f, min((jB + 1) * f, bh), ya, yb);
-        const size_t is = STEP ? (size_t)in_step : 1, os = STEP ? (size_t)out_step : 1;   // C == 1 with STEP
+        const size_t is = STEP ? (size_t)in_step * ES : 1, os = STEP ? (size_t)out_step * ES : 1;   // C == 1 with STEP: bytes
         const uint8_t* sbox = src + (size_t)c.y * pl.in_pitch + (size_t)c.x * C * is;
         uint8_t* dbox = dst + (size_t)c.y * pl.out_pitch + (size_t)c.x * C * os;
 
@@ -286,7 +301,10 @@ __device__ __forceinline__ void smooth_box_body(const SmoothArgs& a, const Smoot
                     uint32_t acc = 0;                      // at most 255 * 32768
                     const uint8_t* p = sbox + (size_t)y0 * pl.in_pitch + bc * is;
 #pragma unroll 8
-                    for (int y = y0; y < y1; ++y, p += pl.in_pitch) acc += *p;
+                    for (int y = y0; y < y1; ++y, p += pl.in_pitch) {
+                        if constexpr (ES == 2) acc += ((uint32_t)*(const uint16_t*)p >> shift) & vmask;
+                        else acc += *p;
+                    }
                     const int e = (j * sw + i) * C + ch;
                     if (wide) atomicAdd(&s_cell64[e], (unsigned long long)acc);
                     else atomicAdd(&s_cell[e], acc);
@@ -301,7 +319,16 @@ __device__ __forceinline__ void smooth_box_body(const SmoothArgs& a, const Smoot
             if ((S >> 27) == 0) return (16u * (uint32_t)S + n / 2) / n;
             return (uint32_t)((16ULL * S + n / 2) / n);
         };
-        if (wide) {
+        if (ES == 2 && wide) {
+            // any cell count, THREADS sums at a time: mean e overwrites word e, below every unread sum
+            for (int e0 = 0; e0 < ncell; e0 += THREADS) {
+                const int e = e0 + tid;
+                const unsigned long long S = e < ncell ? s_cell64[e] : 0;
+                __syncthreads();
+                if (e < ncell) s_cell[e] = mean_of(e, S);
+                __syncthreads();
+            }
+        } else if (wide) {
             const unsigned long long S = tid < ncell ? s_cell64[tid] : 0;
             __syncthreads();
             if (tid < ncell) s_cell[tid] = mean_of(tid, S);
@@ -365,7 +392,10 @@ __device__ __forceinline__ void smooth_box_body(const SmoothArgs& a, const Smoot
                             }
                         }
                     }
-                    if (mine) *p = (uint8_t)o;
+                    if (mine) {
+                        if constexpr (ES == 2) *(uint16_t*)p = (uint16_t)(o << shift);
+                        else *p = (uint8_t)o;
+                    }
                     s += 2;
                     if (s >= f2) {                         // the next row lies past cell row j0 + 1's centre
                         s -= f2;
@@ -409,7 +439,25 @@ __global__ __launch_bounds__(THREADS) void smooth_box_yuv420_kernel(SmoothArgs a
     else smooth_box_body<1, true, true>(a, P == 1 ? a.pl[1] : v, part, s_cell, s_beat, s_nbeat, in_step, out_step);
 }
 
+// ... of 16-bit words (vd_yuv420_16): the same grid, every plane a C = 1 pass over words
+__global__ __launch_bounds__(THREADS) void smooth_box_yuv16_kernel(SmoothArgs a, SmoothPlane v, int in_step, int out_step,
+                                                                   int depth, int shift) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_cell[];
+    __shared__ int4 s_beat[BEAT_CAP];
+    __shared__ int s_nbeat;
+    const int P = blockIdx.z / PARTS, part = blockIdx.z - P * PARTS;
+    if (P == 0) smooth_box_body<1, false, true, 2>(a, a.pl[0], part, s_cell, s_beat, s_nbeat, 1, 1, depth, shift);
+    else smooth_box_body<1, true, true, 2>(a, P == 1 ? a.pl[1] : v, part, s_cell, s_beat, s_nbeat, in_step, out_step, depth, shift);
+}
+
 }  // namespace
+
+// ... of one plane of 16-bit words: (cells + 1)^2 uint32 sums, or 64-bit sums of the cells a level above
+// F16_MAX leaves (h, w <= 32768: at most 32 a side, 33 in a chroma grid)
+static size_t smooth_lds_bytes16(int cells) {
+    const size_t g = (size_t)cells + 1, g64 = std::min(g, (size_t)33);
+    return std::max(g * g * 4, g64 * g64 * 8);
+}
 
 // The cell sums of one box: cells^2 * 3 (RGB) or (cells + 1)^2 * 2 (a chroma grid, header) uint32,
 // or 64-bit sums of the few cells a level above F32_MAX leaves (RGB and luma: 8 x 8; chroma pairs:
@@ -445,20 +493,22 @@ hipError_t vd_launch_smooth(const uint8_t* in, uint8_t* out, int n, int h, int w
     return hipGetLastError();
 }
 
-hipError_t vd_launch_smooth_nv12(const Nv12MosaicArgs& v, int stage, hipStream_t s) {
+hipError_t vd_launch_smooth_nv12(const Nv12MosaicArgs& v, int stage, hipStream_t s, int depth, int shift) {
+    const size_t es = depth ? 2 : 1;
     if (v.n <= 0 || v.h <= 0 || v.w <= 0 || (v.h & 1) || (v.w & 1) || v.h > 32768 || v.w > 32768 || v.level < 1 ||
         v.level > 32768 || v.cells < VD_CELLS_MIN || v.cells > VD_CELLS_MAX || v.n > 65535 ||
-        v.in_pitch < (size_t)v.w || v.out_pitch < (size_t)v.w || !v.in || !v.out ||
+        v.in_pitch < (size_t)v.w * es || v.out_pitch < (size_t)v.w * es || !v.in || !v.out ||
         (v.in_step != 1 && v.in_step != 2) || (v.out_step != 1 && v.out_step != 2) ||
-        v.in_cp < (size_t)(v.w / 2) * v.in_step || v.out_cp < (size_t)(v.w / 2) * v.out_step)
+        v.in_cp < (size_t)(v.w / 2) * v.in_step * es || v.out_cp < (size_t)(v.w / 2) * v.out_step * es ||
+        (depth && (depth < 8 || depth > 12 || shift < 0 || shift + depth > 16)))
         return hipErrorInvalidValue;
-    if (!v.nv12() && stage == 0) {
+    if ((depth || !v.nv12()) && stage == 0) {
         // any other layout pair: the copy is the pixelation launch with no lists (nv12.hip), which
         // moves [0, w) of the luma rows and every chroma sample from the one layout into the other
         Nv12MosaicArgs c = v;
         c.cnt0 = c.cnt1 = nullptr; c.xy0 = c.xy1 = nullptr; c.cap0 = c.cap1 = 0;
         c.level = 1; c.cells = 0;
-        return vd_launch_mosaic_nv12(c, s);
+        return vd_launch_mosaic_nv12(c, s, depth);
     }
     SmoothArgs a{};
     a.pl[0] = SmoothPlane{v.in, v.out, v.in_pitch, v.in_stride, v.out_pitch, v.out_stride};
@@ -472,7 +522,10 @@ hipError_t vd_launch_smooth_nv12(const Nv12MosaicArgs& v, int stage, hipStream_t
         const int by = (v.h + CR - 1) / CR, bc = (v.h / 2 + CR - 1) / CR;
         hipLaunchKernelGGL(smooth_copy_nv12_kernel, dim3(by + bc, v.n), dim3(THREADS), 0, s, a, by);
     } else if (v.cnt0 || v.cnt1) {
-        if (v.nv12())
+        if (depth)   // (stage 0 was the pixelation launch of words with no lists, which also checked that every size is even)
+            hipLaunchKernelGGL(smooth_box_yuv16_kernel, dim3(SLOTS, v.n, 3 * PARTS), dim3(THREADS),
+                               smooth_lds_bytes16(v.cells), s, a, vp, v.in_step, v.out_step, depth, shift);
+        else if (v.nv12())
             hipLaunchKernelGGL(smooth_box_nv12_kernel, dim3(SLOTS, v.n, 2 * PARTS), dim3(THREADS),
                                vd_smooth_lds_bytes(v.cells), s, a);
         else

@@ -78,7 +78,7 @@ int vdt_letterbox_nv12(vd_ctx* h, const vd_nv12* frames, int n, int fh, int fw, 
     if (rc) return rc;
     if ((rc = ctx->check_frames(n, fh, fw, (size_t)fw * 3))) return rc;   // n within max_batch
     Ctx::Nv12Dev d{};
-    if ((rc = ctx->nv12_in(vd_yuv420_of_nv12(*frames), n, fh, fw, where, &d))) return rc;
+    if ((rc = ctx->nv12_in(vd_yuv420_dev(vd_yuv420_of_nv12(*frames)), n, fh, fw, where, &d))) return rc;
     const Nv12Scope scope(ctx, d, frames->matrix, frames->range);
     if ((rc = ctx->face_letterbox(d.base, n, fh, fw, d.pitch))) return rc;
     return letterbox_readback(ctx, n, out, cpad);
@@ -93,7 +93,22 @@ int vdt_letterbox_yuv420(vd_ctx* h, const vd_yuv420* frames, int n, int fh, int 
     if (rc) return rc;
     if ((rc = ctx->check_frames(n, fh, fw, (size_t)fw * 3))) return rc;   // n within max_batch
     Ctx::Nv12Dev d{};
-    if ((rc = ctx->nv12_in(*frames, n, fh, fw, where, &d))) return rc;
+    if ((rc = ctx->nv12_in(vd_yuv420_dev(*frames), n, fh, fw, where, &d))) return rc;
+    const Nv12Scope scope(ctx, d, frames->matrix, frames->range);
+    if ((rc = ctx->face_letterbox(d.base, n, fh, fw, d.pitch))) return rc;
+    return letterbox_readback(ctx, n, out, cpad);
+}
+
+int vdt_letterbox_yuv420_16(vd_ctx* h, const vd_yuv420_16* frames, int n, int fh, int fw, int where, float* out, int cpad) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (!ctx->face.loaded) return vd_set_error(VD_ERR_STATE, "RetinaFace weights not loaded");
+    if (where != VD_HOST && where != VD_DEVICE) return vd_set_error(VD_ERR_ARG, "vdt_letterbox_yuv420_16: bad where");
+    int rc = vd_yuv420_16_check("vdt_letterbox_yuv420_16", frames, n, fh, fw, true);
+    if (rc) return rc;
+    if ((rc = ctx->check_frames(n, fh, fw, (size_t)fw * 3))) return rc;   // n within max_batch
+    Ctx::Nv12Dev d{};
+    if ((rc = ctx->nv12_in(vd_yuv420_dev(*frames), n, fh, fw, where, &d))) return rc;
     const Nv12Scope scope(ctx, d, frames->matrix, frames->range);
     if ((rc = ctx->face_letterbox(d.base, n, fh, fw, d.pitch))) return rc;
     return letterbox_readback(ctx, n, out, cpad);

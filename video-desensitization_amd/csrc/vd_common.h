@@ -512,7 +512,9 @@ struct Nv12MosaicArgs {
     const int* cnt1; const int* xy1; int cap1;
     int level, cells;
 };
-hipError_t vd_launch_mosaic_nv12(const Nv12MosaicArgs& a, hipStream_t s);
+// depth != 0: both sides hold 16-bit words (include/vdmi.h at vd_yuv420_16) -- the sizes above stay in
+// bytes, the steps in samples -- and the launch is the kernel for words (a copy needs no more than that)
+hipError_t vd_launch_mosaic_nv12(const Nv12MosaicArgs& a, hipStream_t s, int depth = 0);
 // The look-ahead ring push of NV12 surfaces (nv12.hip): [0, w) of every row of both planes of n
 // surfaces, src layout -> dst layout, one launch. No alignment is assumed of either layout.
 struct Nv12PackArgs {
@@ -540,7 +542,8 @@ hipError_t vd_launch_smooth(const uint8_t* in, uint8_t* out, int n, int h, int w
                             hipStream_t s);
 // ... of NV12 frames, both planes (smooth.hip; include/vdmi.h at vd_nv12): stage 0 copies [0, w) of
 // every row of both planes, stage 1 is the box pass of both planes in one launch. Even h, w <= 32768.
-hipError_t vd_launch_smooth_nv12(const Nv12MosaicArgs& a, int stage, hipStream_t s);
+// depth != 0: 16-bit words whose value is (word >> shift) & (2^depth - 1), depth <= 12
+hipError_t vd_launch_smooth_nv12(const Nv12MosaicArgs& a, int stage, hipStream_t s, int depth = 0, int shift = 0);
 size_t vd_smooth_lds_bytes(int cells);   // dynamic LDS of either box pass (RGB cells^2 * 3, chroma (cells + 1)^2 * 2 sums)
 // Gaussian blur of box lists (blur.hip): plan + band pass + dependent-box pass on `s`.
 // q: the ksize Q20 weights of vd_blur_weights; table: vd_blur_table_bytes(n, h, pitch, tcap) bytes.
@@ -649,7 +652,8 @@ struct MaskNv12Args {
     int in_step, out_step;
     const int* m_cnt; const int* m_xy; int mcap;     // the grown merged rows (MaskArgs)
 };
-hipError_t vd_launch_mask_restore_nv12(const MaskNv12Args& a, hipStream_t s);
+// es: bytes per sample -- 1, or 2 for surfaces of 16-bit words (vd_yuv420_16: whole words are copied)
+hipError_t vd_launch_mask_restore_nv12(const MaskNv12Args& a, hipStream_t s, int es = 1);
 
 // Tiled face detection (include/vdmi.h at vd_tiles). T = 1 + rows * cols net inputs per frame:
 // input 0 the whole frame, input 1 + r * cols + c tile (r, c); every tile is tw x th pixels.

@@ -88,6 +88,10 @@ class vd_yuv420(ctypes.Structure):
                 ("chroma_step", ctypes.c_int32), ("matrix", ctypes.c_int32), ("range", ctypes.c_int32)]
 
 
+class vd_yuv420_16(ctypes.Structure):
+    _fields_ = vd_yuv420._fields_ + [("depth", ctypes.c_int32), ("shift", ctypes.c_int32)]
+
+
 YUV420_LAYOUTS = ("i420", "yv12", "nv12", "nv21")
 
 _P, _I, _SZ, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float, ctypes.c_double
@@ -175,6 +179,14 @@ SIGNATURES = [
                               ctypes.POINTER(vd_boxes), _I, _I]),
     ("vd_yuv420_to_rgb", _I, [ctypes.POINTER(vd_yuv420), _I, _I, _I, _P, _SZ]),
     ("vdt_letterbox_yuv420", _I, [_P, ctypes.POINTER(vd_yuv420), _I, _I, _I, _I, _P, _I]),
+    ("vd_process_yuv420_16", _I, [_P, ctypes.POINTER(vd_yuv420_16), ctypes.POINTER(vd_yuv420_16), _I, _I, _I, _I, _I,
+                                  ctypes.POINTER(vd_boxes), ctypes.POINTER(vd_boxes)]),
+    ("vd_mosaic_yuv420_16", _I, [_P, ctypes.POINTER(vd_yuv420_16), ctypes.POINTER(vd_yuv420_16), _I, _I, _I, _I,
+                                 ctypes.POINTER(vd_boxes), _I]),
+    ("vd_smooth_yuv420_16", _I, [_P, ctypes.POINTER(vd_yuv420_16), ctypes.POINTER(vd_yuv420_16), _I, _I, _I, _I,
+                                 ctypes.POINTER(vd_boxes), _I, _I]),
+    ("vd_yuv420_16_to_rgb", _I, [ctypes.POINTER(vd_yuv420_16), _I, _I, _I, _P, _SZ]),
+    ("vdt_letterbox_yuv420_16", _I, [_P, ctypes.POINTER(vd_yuv420_16), _I, _I, _I, _I, _P, _I]),
     ("vd_timing_enable", _I, [_P, _I]),
     ("vd_timing_reset", _I, [_P]),
     ("vd_timing_read", _I, [_P, _I, ctypes.POINTER(_D), ctypes.POINTER(ctypes.c_int64),

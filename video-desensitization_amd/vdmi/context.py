@@ -190,6 +190,119 @@ def yuv420_to_rgb(frames, layout="i420", matrix="bt709", range="limited", height
     return out
 
 
+class Yuv420_16:
+    """10- or 12-bit 4:2:0 frames anywhere in one buffer (the C-ABI's vd_yuv420_16): P010 / P012,
+    yuv420p10le / yuv420p12le and their V-first variants, padded or not. buffer: a contiguous numpy
+    array or torch tensor (host or device) of uint16 (torch: uint16 or int16), or of uint8 -- as Yuv420
+    takes buffers; all offsets and pitches are in BYTES from its first byte, which is frame 0's first
+    luma word; chroma_step counts samples (1 planar, 2 interleaved pairs). A word's value is
+    (word >> shift) & (2**depth - 1). n defaults to the number of whole frames the buffer holds."""
+
+    _TORCH = {"torch.uint8": 1, "torch.uint16": 2, "torch.int16": 2}
+
+    def __init__(self, buffer, h, w, pitch, u_offset, v_offset, chroma_pitch, chroma_step, frame_stride, depth=10,
+                 shift=0, n=None):
+        if _is_torch(buffer):
+            item = self._TORCH.get(buffer.dtype.__str__())
+            if item is None or not buffer.is_contiguous():
+                raise ValueError("Yuv420_16: a contiguous uint16 or uint8 buffer is needed")
+            nbytes, self._ptr = buffer.numel() * item, buffer.data_ptr()
+            self.where = _lib.VD_DEVICE if buffer.is_cuda else _lib.VD_HOST
+        else:
+            if not (isinstance(buffer, np.ndarray) and buffer.dtype in (np.uint8, np.uint16) and buffer.flags.c_contiguous):
+                raise ValueError("Yuv420_16: a contiguous uint16 or uint8 buffer is needed")
+            nbytes, self._ptr, self.where = buffer.nbytes, buffer.ctypes.data, _lib.VD_HOST
+        self.buffer = buffer
+        self.h, self.w, self.pitch = int(h), int(w), int(pitch)
+        self.u_offset, self.v_offset = int(u_offset), int(v_offset)
+        self.chroma_pitch, self.chroma_step, self.frame_stride = int(chroma_pitch), int(chroma_step), int(frame_stride)
+        self.depth, self.shift = int(depth), int(shift)
+        if min(self.h, self.w, self.pitch, self.chroma_pitch, self.frame_stride) <= 0 or min(self.u_offset, self.v_offset) < 0:
+            raise ValueError("Yuv420_16: positive sizes and pitches, non-negative offsets needed")
+        crow = self.w * max(self.chroma_step, 1)        # bytes of a chroma row
+        cend = max(self.u_offset, self.v_offset) + (max(self.h // 2, 1) - 1) * self.chroma_pitch + \
+            (crow if self.chroma_step != 2 else crow - 2)
+        end = max((self.h - 1) * self.pitch + 2 * self.w, cend)
+        fit = 0 if nbytes < end else 1 + (nbytes - end) // self.frame_stride
+        self.n = fit if n is None else int(n)
+        if self.n < 1 or self.n > fit:
+            raise ValueError(f"Yuv420_16: the buffer of {nbytes} bytes holds {fit} such frames (n = {self.n})")
+
+    def struct(self, matrix="bt709", range="limited"):
+        return _lib.vd_yuv420_16(self._ptr, self.pitch, self.u_offset, self.v_offset, self.chroma_pitch, self.frame_stride,
+                                 self.chroma_step, _lib.NV12_MATRICES[matrix], _lib.NV12_RANGES[range], self.depth,
+                                 self.shift)
+
+
+def _yuv420_16_arg(frames, layout="i420", depth=10, shift=None, height=None, matrix="bt709", range="limited",
+                   writable=False):
+    """10- / 12-bit 4:2:0 frames -> (vd_yuv420_16, n, h, w, where, keepalive). frames: a Yuv420_16, or
+    packed uint16 [n, rows, w] (or [rows, w]; torch: uint16 or int16) in `layout` as _yuv420_arg lays
+    8-bit frames out, a word per sample. shift None: 0 for the planar layouts, 16 - depth for the
+    interleaved ones (the P010 convention). height as in _yuv420_arg."""
+    if matrix not in _lib.NV12_MATRICES:
+        raise ValueError(f"matrix {matrix!r}: expected 'bt601' or 'bt709'")
+    if range not in _lib.NV12_RANGES:
+        raise ValueError(f"range {range!r}: expected 'limited' or 'full'")
+    if isinstance(frames, Yuv420_16):
+        return frames.struct(matrix, range), frames.n, frames.h, frames.w, frames.where, frames
+    if layout not in _lib.YUV420_LAYOUTS:
+        raise ValueError(f"layout {layout!r}: expected one of {_lib.YUV420_LAYOUTS}")
+    planar = layout in ("i420", "yv12")
+    if _is_torch(frames):
+        t = frames if frames.dim() == 3 else frames[None]
+        if t.dtype.__str__() not in ("torch.uint16", "torch.int16") or t.dim() != 3:
+            raise ValueError("16-bit 4:2:0 frames must be uint16 [n, rows, w]")
+        if not t.is_contiguous():
+            if writable:
+                raise ValueError("16-bit 4:2:0 out: a contiguous tensor is needed (or pass a Yuv420_16)")
+            t = t.contiguous()
+        base, where, keep = t.data_ptr(), (_lib.VD_DEVICE if t.is_cuda else _lib.VD_HOST), t
+        n, rows, w = t.shape
+    else:
+        a = np.ascontiguousarray(frames, dtype=np.uint16)
+        if writable and a is not frames:
+            raise ValueError("16-bit 4:2:0 out: a C-contiguous uint16 numpy array is needed")
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("16-bit 4:2:0 frames must be uint16 [n, rows, w]")
+        n, rows, w = a.shape
+        base, where, keep = a.ctypes.data, _lib.VD_HOST, a
+    if rows % 3 or w % 2 or (planar and (rows // 3 * 2) % 2):
+        raise ValueError(f"16-bit 4:2:0 frames of {rows} rows x {w}: expected 3/2 of an even (padded) height and an even width")
+    hpad = rows // 3 * 2
+    h = hpad if height is None else int(height)
+    if h > hpad:
+        raise ValueError(f"height {h} exceeds the {hpad} luma rows that {rows} rows hold")
+    pitch = 2 * w
+    first = hpad * pitch
+    if planar:
+        cpitch, step, second = w, 1, first + (hpad // 2) * w
+    else:
+        cpitch, step, second = pitch, 2, first + 2
+    u, v = (first, second) if layout in ("i420", "nv12") else (second, first)
+    if shift is None:
+        shift = 0 if planar else 16 - int(depth)
+    d = _lib.vd_yuv420_16(base, pitch, u, v, cpitch, rows * pitch, step, _lib.NV12_MATRICES[matrix],
+                          _lib.NV12_RANGES[range], int(depth), int(shift))
+    return d, n, h, w, where, keep
+
+
+def yuv420_16_to_rgb(frames, layout="i420", depth=10, shift=None, matrix="bt709", range="limited", height=None):
+    """vd_yuv420_16_to_rgb (host only, no GPU): host 10- / 12-bit 4:2:0 frames (the forms of
+    Context.process_yuv420_16) -> uint8 [n, h, w, 3], the conversion of their 8-bit picture D(S)."""
+    if _is_torch(frames):
+        frames = frames.cpu()
+    d, n, h, w, where, keep = _yuv420_16_arg(frames, layout, depth, shift, height, matrix, range)
+    if where != _lib.VD_HOST:
+        raise ValueError("yuv420_16_to_rgb() converts host frames")
+    out = np.empty((n, max(h, 0), max(w, 0), 3), np.uint8)
+    check(_lib.load().vd_yuv420_16_to_rgb(ctypes.byref(d), n, h, w, ptr(out), w * 3))
+    del keep
+    return out
+
+
 def jpeg_info(data):
     """(h, w, components) of a baseline JPEG (host-only parse, no GPU). A bytes object is
     parsed in place (its own buffer: no copy -- a 2.4-MB frame copied under the GIL for every
@@ -791,6 +904,102 @@ class Context:
         d, n, h, w, where, keep = _yuv420_arg(frames, layout, height, matrix, range)
         out = np.zeros((n, self.cfg.input_h, self.cfg.input_w, cpad), np.float32)
         check(self._lib.vdt_letterbox_yuv420(self._h, ctypes.byref(d), n, h, w, where, ptr(out), cpad))
+        del keep
+        return out
+
+    # -- 10- and 12-bit 4:2:0 frames (P010, P012, yuv420p10le, yuv420p12le) ---------------
+    @staticmethod
+    def _yuv420_16_out(frames, geo, out, out_layout, depth, shift, height):
+        """The output surfaces of a 16-bit 4:2:0 blurring call: `out` (a uint16 array in out_layout, or a
+        Yuv420_16), or new packed frames [n, 3h/2, w] in out_layout where the input lives, in the input's
+        depth and shift -> (out, vd_yuv420_16, geo, keep)."""
+        n, h, w, where = geo
+        if out is None:
+            src = frames.buffer if isinstance(frames, Yuv420_16) else frames
+            if _is_torch(src):
+                import torch
+                out = torch.empty((n, h // 2 * 3, w), dtype=torch.int16, device=src.device)
+            else:
+                out = np.empty((n, h // 2 * 3, w), np.uint16)
+            height = None
+        d, on, oh, ow, owhere, keep = _yuv420_16_arg(out, out_layout, depth, shift, height, writable=True)
+        return out, d, (on, oh, ow, owhere), keep
+
+    def process_yuv420_16(self, frames, out=None, faces=None, plates=None, flags=None, layout="i420", out_layout=None,
+                          depth=10, shift=None, matrix="bt709", range="limited", height=None):
+        """vd_process_yuv420_16: process_yuv420() on 10- or 12-bit 4:2:0 frames -- uint16 [n, 3h/2, w] in
+        `layout` (_yuv420_16_arg) or a Yuv420_16. Lists are exactly process_yuv420()'s on the 8-bit
+        picture of the frames (each value >> (depth - 8)); the blur acts on the 16-bit samples and every
+        word outside a hidden box comes back as it was. out keeps the input's depth and shift (an array:
+        those given here; a Yuv420_16: its own, which must match). -> (out, faces, plates)."""
+        d, n, h, w, where, keep = _yuv420_16_arg(frames, layout, depth, shift, height, matrix, range)
+        if flags is None:
+            flags = _lib.VD_PROC_FACES | _lib.VD_PROC_MOSAIC
+        od = None
+        if flags & _lib.VD_PROC_MOSAIC:
+            out, od, geo, okeep = self._yuv420_16_out(frames, (n, h, w, where), out, out_layout or layout, d.depth, d.shift,
+                                                      height)
+            if geo != (n, h, w, where):
+                raise ValueError("out must hold 4:2:0 frames of the input's n, h, w in the same memory (host / device)")
+        fs = ps = None
+        auto_f, auto_p = faces is None, plates is None
+        if flags & _lib.VD_PROC_FACES:
+            faces = self._boxes(faces, n)
+            fs = faces.struct()
+        if flags & _lib.VD_PROC_PLATES:
+            plates = self._boxes(plates, n)
+            ps = plates.struct()
+        check(self._lib.vd_process_yuv420_16(self._h, ctypes.byref(d), ctypes.byref(od) if od is not None else None, n, h,
+                                             w, where, flags, ctypes.byref(fs) if fs is not None else None,
+                                             ctypes.byref(ps) if ps is not None else None))
+        if flags & _lib.VD_PROC_FACES:
+            faces = self._complete(faces, _lib.VD_NET_RETINAFACE, auto_f)
+        if flags & _lib.VD_PROC_PLATES:
+            plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
+        return out, faces, plates
+
+    def _yuv420_16_blur(self, fn, frames, boxes_xyxy, counts, out, layout, out_layout, depth, shift, height, *tail):
+        """What mosaic_yuv420_16() / smooth_yuv420_16() share: fn(ctx, in, out, n, h, w, where, boxes, *tail)."""
+        d, n, h, w, where, keep = _yuv420_16_arg(frames, layout, depth, shift, height)
+        if isinstance(boxes_xyxy, (_lib.HostBoxes, DeviceBoxes)):
+            s = boxes_xyxy.struct()
+            bkeep = None
+        else:
+            xy = np.ascontiguousarray(boxes_xyxy, np.int32).reshape(n, -1, 4)
+            cnt = np.ascontiguousarray(counts if counts is not None else np.full(n, xy.shape[1]), np.int32)
+            cap = max(1, xy.shape[1])
+            if xy.shape[1] == 0:
+                xy = np.zeros((n, 1, 4), np.int32)
+            s = _lib.vd_boxes(cap, _lib.VD_HOST, ptr(cnt), ptr(xy), None, None, None)
+            bkeep = (xy, cnt)
+        out, od, geo, okeep = self._yuv420_16_out(frames, (n, h, w, where), out, out_layout or layout, d.depth, d.shift, height)
+        if geo != (n, h, w, where):
+            raise ValueError("out must hold 4:2:0 frames of the input's n, h, w in the same memory (host / device)")
+        check(fn(self._h, ctypes.byref(d), ctypes.byref(od), n, h, w, where, ctypes.byref(s), *tail))
+        del keep, bkeep, okeep
+        return out
+
+    def mosaic_yuv420_16(self, frames, boxes_xyxy, counts=None, level=None, out=None, layout="i420", out_layout=None,
+                         depth=10, shift=None, height=None):
+        """vd_mosaic_yuv420_16: mosaic_yuv420() on 10- or 12-bit 4:2:0 frames; whole words are copied."""
+        return self._yuv420_16_blur(self._lib.vd_mosaic_yuv420_16, frames, boxes_xyxy, counts, out, layout, out_layout,
+                                    depth, shift, height, int(level or self.cfg.mosaic_level))
+
+    def smooth_yuv420_16(self, frames, boxes_xyxy, counts=None, level=None, cells=None, out=None, layout="i420",
+                         out_layout=None, depth=10, shift=None, height=None):
+        """vd_smooth_yuv420_16: smooth_yuv420() on the values of 10- or 12-bit 4:2:0 frames."""
+        cells = _lib.check_cells(self.cells if cells is None else cells)
+        if cells == 0:
+            raise ValueError("smooth_yuv420_16() needs cells in 2 .. 64 (the context's setting is 0: off)")
+        return self._yuv420_16_blur(self._lib.vd_smooth_yuv420_16, frames, boxes_xyxy, counts, out, layout, out_layout,
+                                    depth, shift, height, int(level or self.cfg.mosaic_level), cells)
+
+    def letterbox_yuv420_16(self, frames, cpad=4, layout="i420", depth=10, shift=None, matrix="bt709", range="limited",
+                            height=None):
+        """vdt_letterbox_yuv420_16: the face canvas of 10- / 12-bit 4:2:0 frames by the product path's kernel."""
+        d, n, h, w, where, keep = _yuv420_16_arg(frames, layout, depth, shift, height, matrix, range)
+        out = np.zeros((n, self.cfg.input_h, self.cfg.input_w, cpad), np.float32)
+        check(self._lib.vdt_letterbox_yuv420_16(self._h, ctypes.byref(d), n, h, w, where, ptr(out), cpad))
         del keep
         return out
 
