@@ -378,7 +378,8 @@ int vd_read_held(vd_ctx* ctx, int n, vd_boxes* out);
  * of the pending frames. flags must include VD_PROC_MOSAIC (VD_ERR_ARG). Refusals, each checked
  * before any state changes: m > out_cap VD_ERR_CAPACITY; J == 0 VD_ERR_STATE; (h, w, pitch)
  * differing from the pending frames' VD_ERR_STATE (flush first); frames pending from
- * vd_lead_lists or vd_process_lead_nv12 VD_ERR_STATE; motion with h or w > 32768 VD_ERR_ARG.
+ * vd_lead_lists or vd_process_lead_nv12 (or its vd_yuv420 / vd_yuv420_16 forms) VD_ERR_STATE; motion with
+ * h or w > 32768 VD_ERR_ARG.
  *
  * vd_lead_lists: the same step for callers with their own detectors, lists only, by the same
  * kernel. det: the D lists of n consecutive h x w frames as for vd_hold (a host list with
@@ -853,8 +854,8 @@ int vd_nv12_to_rgb(const vd_nv12* in, int n, int h, int w, uint8_t* rgb, size_t 
  * frame_stride when n > 1; unknown matrix or range (detection and conversion); device `out`
  * overlapping device `in` (the whole extents of the n frames). VD_ERR_STATE, with the messages of
  * vd_process_nv12: a VD_BLUR_GAUSSIAN context with cells off; a call that would run a tiled net;
- * VD_PROC_MOSAIC in a look-ahead context. Not in this version, and without an entry point: a
- * planar form of vd_process_lead_nv12 (the look-ahead ring stays NV12), 4:2:2 and 4:4:4. 10- and
+ * VD_PROC_MOSAIC in a look-ahead context (the look-ahead call is vd_process_lead_yuv420, below). Not in
+ * this version: tiling and the fixed Gaussian on surfaces (both refused, above), 4:2:2 and 4:4:4. 10- and
  * 12-bit surfaces (P010, yuv420p10le) have a descriptor of their own: vd_yuv420_16, below. */
 typedef struct vd_yuv420 {
     uint8_t* base;        /* first luma byte of frame 0 */
@@ -872,6 +873,29 @@ int vd_mosaic_yuv420(vd_ctx* ctx, const vd_yuv420* in, const vd_yuv420* out, int
                      const vd_boxes* boxes, int level);
 int vd_smooth_yuv420(vd_ctx* ctx, const vd_yuv420* in, const vd_yuv420* out, int n, int h, int w, int where,
                      const vd_boxes* boxes, int level, int cells);
+/* vd_process_lead_nv12 on 8-bit 4:2:0 surfaces in any layout. Nothing new is defined: lists (faces / plates
+ * of the pushed frames), the hold history, m, *n_out and vd_read_lead are exactly vd_process_lead_nv12's on
+ * N(in), and for each emitted surface O, N(O) equals that call's output on every sample of the picture.
+ * `in` and `out` are independent descriptors and may differ in layout (I420 in, NV12 out costs no extra
+ * pass); either may change from call to call, h and w may not. Pad bytes, and bytes between the planes and
+ * surfaces of `out`, are never written. The pending surfaces live in vd_process_lead_nv12's ring -- packed
+ * NV12, whatever the callers' layouts -- under the same pending mode, so one stream may be pushed by
+ * vd_process_lead_nv12 and vd_process_lead_yuv420 in turn; per call one launch packs the kept surfaces
+ * from the input's layout into the ring (nv12.hip; timing family 4, work = bytes read + written). A
+ * descriptor that is NV12 gives byte for byte what vd_process_lead_nv12 gives, by the same kernels.
+ * Delay, flush, n == 0 (`in` may be NULL; h and w those of the pending surfaces) and the end of an empty
+ * stream (VD_OK, *n_out = 0) follow vd_process_lead_nv12. Refusals are vd_process_lead_nv12's with
+ * vd_process_yuv420's descriptor rules, each checked before any state changes and with *n_out untouched:
+ * a bad descriptor VD_ERR_ARG (the message names the field); J == 0 VD_ERR_STATE; flags without
+ * VD_PROC_MOSAIC, or with neither VD_PROC_FACES nor VD_PROC_MOSAIC_PLATES, VD_ERR_ARG; m > out_cap
+ * VD_ERR_CAPACITY; m > 0 with `out` NULL VD_ERR_ARG; device extents of `in` and `out` that overlap
+ * VD_ERR_ARG; a VD_BLUR_GAUSSIAN context with cells off VD_ERR_STATE; a call that would run a tiled net
+ * VD_ERR_STATE; h or w differing from the pending surfaces' VD_ERR_STATE (flush first); frames pending
+ * from vd_process_lead, vd_lead_lists or vd_process_lead_yuv420_16 VD_ERR_STATE, as are those calls while
+ * these surfaces are pending; motion with h or w > 32768 VD_ERR_ARG. vd_hold_reset abandons pending
+ * surfaces, and everything vd_lead refuses while frames are pending stays refused. */
+int vd_process_lead_yuv420(vd_ctx* ctx, const vd_yuv420* in, const vd_yuv420* out, int n, int h, int w, int where, int flags,
+                           vd_boxes* faces, vd_boxes* plates, int out_cap, int flush, int* n_out);
 /* vd_nv12_to_rgb for any layout: C(frame) of n frames (host only: no context, no GPU), by the same function. */
 int vd_yuv420_to_rgb(const vd_yuv420* in, int n, int h, int w, uint8_t* rgb, size_t rgb_pitch);
 
@@ -919,10 +943,9 @@ int vd_yuv420_to_rgb(const vd_yuv420* in, int n, int h, int w, uint8_t* rgb, siz
  * u_offset, v_offset or frame_stride or a base that is not 2-byte aligned; pitch < 2*w; depth
  * outside {10, 12}; shift outside [0, 16 - depth]; chroma_step 2 with |u_offset - v_offset| != 2.
  * VD_ERR_STATE with the messages of vd_process_yuv420: a VD_BLUR_GAUSSIAN context with cells off; a
- * call that would run a tiled net; VD_PROC_MOSAIC in a look-ahead context. Not in this version, and
- * without an entry point: look-ahead on these surfaces (the ring stays 8-bit NV12), tiling, the
- * fixed Gaussian, depth or shift conversion between in and out, 16-bit-deep samples, 4:2:2 and
- * 4:4:4. */
+ * call that would run a tiled net; VD_PROC_MOSAIC in a look-ahead context (the look-ahead call is
+ * vd_process_lead_yuv420_16, below). Not in this version: tiling and the fixed Gaussian on surfaces (both
+ * refused), depth or shift conversion between in and out, 16-bit-deep samples, 4:2:2 and 4:4:4. */
 typedef struct vd_yuv420_16 {
     uint8_t* base;        /* first luma word of frame 0 (2-byte aligned) */
     size_t   pitch;       /* luma row pitch, bytes (even, >= 2*w) */
@@ -941,6 +964,20 @@ int vd_mosaic_yuv420_16(vd_ctx* ctx, const vd_yuv420_16* in, const vd_yuv420_16*
                         const vd_boxes* boxes, int level);
 int vd_smooth_yuv420_16(vd_ctx* ctx, const vd_yuv420_16* in, const vd_yuv420_16* out, int n, int h, int w, int where,
                         const vd_boxes* boxes, int level, int cells);
+/* vd_process_lead_yuv420 on surfaces of 16-bit words. Lists are exactly vd_process_lead_yuv420's on D(in);
+ * emitted surface t is exactly what vd_mosaic_yuv420_16 (or, as the context's settings ask, the smooth blur
+ * and the ellipse restore above) writes for input surface t over B_t = D_t ++ H_t ++ A_t, and every word
+ * that no box owns comes back bit for bit, unused bits included. The pending surfaces live in a second
+ * form of the pixel ring: packed whole words, interleaved chroma with U first, luma pitch 2*w bytes, chroma
+ * at 2*h*w, 3*h*w bytes a slot (the size of the RGB ring's slot), under a pending mode of its own. depth
+ * and shift belong to the pending geometry: `out` must have `in`'s (VD_ERR_ARG, as above); a push whose
+ * depth or shift differs from the pending surfaces' is VD_ERR_STATE (flush first), as for h and w; a
+ * flush alone (n == 0) takes them from `out`, and they must equal the pending ones. Everything else --
+ * layouts that change from call to call, delay, flush, the refusals, vd_hold_reset -- is
+ * vd_process_lead_yuv420's with vd_process_yuv420_16's descriptor rules; 8-bit surfaces pending refuse
+ * this call and the reverse (VD_ERR_STATE). */
+int vd_process_lead_yuv420_16(vd_ctx* ctx, const vd_yuv420_16* in, const vd_yuv420_16* out, int n, int h, int w, int where,
+                              int flags, vd_boxes* faces, vd_boxes* plates, int out_cap, int flush, int* n_out);
 /* C(D(frame)) of n frames (host only: no context, no GPU), by the same conversion function. */
 int vd_yuv420_16_to_rgb(const vd_yuv420_16* in, int n, int h, int w, uint8_t* rgb, size_t rgb_pitch);
 

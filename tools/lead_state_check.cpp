@@ -2,7 +2,8 @@
 // (csrc/lead_state.h): the emission arithmetic and the window-to-slot mapping the kernel and
 // the runtime share, run over host arrays that stand for the two device buffers, against a
 // plain deque of the frames pushed and not yet emitted; and the rule that one stream is pushed
-// by one entry point (RGB frames, lists or NV12 surfaces). Stand-alone, no HIP:
+// by one entry point family (RGB frames, lists, 8-bit surfaces or surfaces of 16-bit words, whose
+// depth and shift belong to the pending geometry). Stand-alone, no HIP:
 //
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       tools/lead_state_check.cpp -o lead_state_check && ./lead_state_check
@@ -39,7 +40,8 @@ static int run(int J, int motion, long* checks) {
     std::vector<int> buf[2] = {std::vector<int>(D, -1), std::vector<int>(D, -1)};   // slot -> frame id
     std::deque<int> model;                                                         // oldest first
     int next_id = 0, emitted = 0;                                                  // frames leave in order
-    static const int MODES[3] = {VD_LEAD_MODE_PIXELS, VD_LEAD_MODE_LISTS, VD_LEAD_MODE_NV12};
+    static const int MODES[4] = {VD_LEAD_MODE_PIXELS, VD_LEAD_MODE_LISTS, VD_LEAD_MODE_NV12, VD_LEAD_MODE_YUV16};
+    int depth = 0, shift = 0;                                                      // of a stream of 16-bit words
     int mode = MODES[0];                                                           // the entry point pushing this stream
     for (int step = 0; step < 600; ++step) {
         int n = step < 13 ? step : (int)rnd(13);
@@ -53,7 +55,19 @@ static int run(int J, int motion, long* checks) {
         if (st.pend != (int)model.size()) return fail("pending count", D, step);
         if (st.pend > D) return fail("pending above delay", D, step);
         // a new stream may come through any entry point; a pending one takes its own alone
-        if (st.pend == 0) mode = MODES[rnd(3)];
+        if (st.pend == 0) {
+            mode = MODES[rnd(4)];
+            depth = mode == VD_LEAD_MODE_YUV16 ? (rnd(2) ? 10 : 12) : 0;
+            shift = depth ? (int)rnd(17 - depth) : 0;
+        }
+        // words stay as pushed: a 16-bit call joins pending surfaces of its own depth and shift only
+        for (int d : {10, 12})
+            for (int s = 0; s <= 16 - d; ++s) {
+                const bool want = st.pend == 0 || (d == depth && s == shift);
+                if (st.format_ok(VD_LEAD_MODE_YUV16, d, s) != want) return fail("depth / shift rule", D, step);
+                if (!st.format_ok(VD_LEAD_MODE_NV12, d, s)) return fail("depth / shift rule off 16-bit", D, step);
+                ++*checks;
+            }
         for (int cm : MODES) {
             const int want_ok = st.pend == 0 || cm == mode;
             if (vd_lead_mode_ok(st.pend, st.mode, cm) != want_ok) return fail("mode mismatch rule", D, step);
@@ -99,10 +113,11 @@ static int run(int J, int motion, long* checks) {
         model.assign(win.begin() + m, win.end());
         // the ring of NV12 surfaces is the library's own, packed: no pitch to remember
         const unsigned long long pitch = mode == VD_LEAD_MODE_PIXELS ? 300 : 0;
-        st.end(n, flush, mode, 100, 100, pitch);
+        st.end(n, flush, mode, 100, 100, pitch, depth, shift);
         if (st.pend != (int)model.size()) return fail("pending after the call", D, step);
         if (st.mode != (st.pend ? mode : VD_LEAD_MODE_NONE)) return fail("mode", D, step);
         if (st.pitch != (st.pend ? pitch : 0) || st.h != (st.pend ? 100 : 0)) return fail("pending geometry", D, step);
+        if (st.depth != (st.pend ? depth : 0) || st.shift != (st.pend ? shift : 0)) return fail("pending depth / shift", D, step);
         for (int j = 0; j < st.pend; ++j)
             if (buf[st.cur].at(j) != model[j]) return fail("shifted ring", D, step);
     }
@@ -113,7 +128,9 @@ int main() {
     long checks = 0;
     if (std::strcmp(vd_lead_mode_caller(VD_LEAD_MODE_PIXELS), "vd_process_lead") ||
         std::strcmp(vd_lead_mode_caller(VD_LEAD_MODE_LISTS), "vd_lead_lists") ||
-        std::strcmp(vd_lead_mode_caller(VD_LEAD_MODE_NV12), "vd_process_lead_nv12"))
+        std::strncmp(vd_lead_mode_caller(VD_LEAD_MODE_NV12), "vd_process_lead_nv12", 20) ||
+        !std::strstr(vd_lead_mode_caller(VD_LEAD_MODE_NV12), "vd_process_lead_yuv420") ||
+        std::strcmp(vd_lead_mode_caller(VD_LEAD_MODE_YUV16), "vd_process_lead_yuv420_16"))
         return fail("mode caller names", 0, 0);
     for (int motion = 0; motion <= 1; ++motion)
         for (int J = 1; J <= VD_LEAD_MAX; ++J)                // delays 1 .. 9

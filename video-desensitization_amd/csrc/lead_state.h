@@ -43,7 +43,8 @@ VD_LHD inline int vd_lead_source(int i, int pend, int n, int* idx) {
 #define VD_LEAD_MODE_NONE 0     // nothing pending
 #define VD_LEAD_MODE_PIXELS 1   // pending frames were pushed by vd_process_lead
 #define VD_LEAD_MODE_LISTS 2    // pending lists were pushed by vd_lead_lists
-#define VD_LEAD_MODE_NV12 3     // pending NV12 surfaces were pushed by vd_process_lead_nv12
+#define VD_LEAD_MODE_NV12 3     // pending 8-bit surfaces (a packed NV12 ring) were pushed by vd_process_lead_nv12 / vd_process_lead_yuv420
+#define VD_LEAD_MODE_YUV16 4    // pending surfaces of 16-bit words were pushed by vd_process_lead_yuv420_16
 
 // One stream is pushed by one entry point: a call of mode `call_mode` joins the pending frames
 // only when nothing is pending or they were pushed in the same mode (otherwise: flush first).
@@ -55,7 +56,8 @@ VD_LHD inline int vd_lead_mode_ok(int pend, int pending_mode, int call_mode) {
 inline const char* vd_lead_mode_caller(int mode) {
     return mode == VD_LEAD_MODE_PIXELS ? "vd_process_lead"
            : mode == VD_LEAD_MODE_LISTS ? "vd_lead_lists"
-           : mode == VD_LEAD_MODE_NV12 ? "vd_process_lead_nv12" : "nothing";
+           : mode == VD_LEAD_MODE_NV12 ? "vd_process_lead_nv12 / vd_process_lead_yuv420"
+           : mode == VD_LEAD_MODE_YUV16 ? "vd_process_lead_yuv420_16" : "nothing";
 }
 
 struct LeadState {
@@ -66,15 +68,20 @@ struct LeadState {
     int mode = VD_LEAD_MODE_NONE;
     int h = 0, w = 0;   // geometry of the pending frames
     unsigned long long pitch = 0;
+    int depth = 0, shift = 0;   // of pending 16-bit surfaces (VD_LEAD_MODE_YUV16), else 0
 
     int delay() const { return J + (motion ? 1 : 0); }
     int emit(int n, int flush) const { return vd_lead_emit(pend, n, delay(), flush); }
-    void reset() { pend = 0; mode = VD_LEAD_MODE_NONE; h = w = 0; pitch = 0; }
+    void reset() { pend = 0; mode = VD_LEAD_MODE_NONE; h = w = 0; pitch = 0; depth = shift = 0; }
+    // may a call of 16-bit surfaces (depth, shift) join the pending ones: the words stay as pushed
+    bool format_ok(int call_mode, int d, int s) const {
+        return pend == 0 || call_mode != VD_LEAD_MODE_YUV16 || (d == depth && s == shift);
+    }
     // after a launch over n pushed frames wrote the other buffer
-    void end(int n, int flush, int call_mode, int fh, int fw, unsigned long long fpitch) {
+    void end(int n, int flush, int call_mode, int fh, int fw, unsigned long long fpitch, int fdepth = 0, int fshift = 0) {
         pend = pend + n - emit(n, flush);
         cur ^= 1;
         if (pend == 0) { reset(); return; }
-        mode = call_mode; h = fh; w = fw; pitch = fpitch;
+        mode = call_mode; h = fh; w = fw; pitch = fpitch; depth = fdepth; shift = fshift;
     }
 };

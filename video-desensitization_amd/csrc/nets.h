@@ -282,7 +282,7 @@ struct Ctx {
     int* lead_ring[2] = {nullptr, nullptr};       // ping-pong pending lists (vd_common.h LeadArgs gives the layout)
     int lead_hcap = 0;                            // D-list capacity of a ring slot (boxes); rows: (K + 1) * lead_hcap
     int lead_slots = 0;                           // slots the ring buffers were sized for (= delay)
-    void* lead_pix = nullptr; size_t lead_pix_bytes = 0;     // pixel ring: delay frames (RGB, or packed NV12), oldest first
+    void* lead_pix = nullptr; size_t lead_pix_bytes = 0;     // pixel ring: delay frames (RGB, packed NV12, or packed 16-bit words U first), oldest first
     void* lead_rows = nullptr; size_t lead_rows_bytes = 0;   // the last call's merged rows, labels, |B|, |D|, |D ++ H|
     LeadArgs lead_last{};                         // the last launch (merged-row pointers for the readers)
     int lead_m = 0;                               // frames the last lead call emitted
@@ -496,7 +496,7 @@ struct Ctx {
     // look-ahead hold: the list capacity a lead call over lists of cap0 + cap1 needs, the refusals shared by
     // both lead calls, and the ring buffers (a narrower pair's pending slots are carried over)
     int lead_need(int cap0, int cap1) const;
-    int lead_check(const char* who, int mode, int n, int h, int w, size_t pitch, int flush);
+    int lead_check(const char* who, int mode, int n, int h, int w, size_t pitch, int flush, int depth = 0, int shift = 0);
     int lead_buffers(int need, size_t frame_bytes);
     void lead_free();                             // vd_lead: a change of setting drops the rings
     // One lead step: the n pushed frames' D lists (and, under hold, hold_last's rows) join the window, the m

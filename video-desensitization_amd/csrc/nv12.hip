@@ -1,6 +1,6 @@
 // nv12.hip — out-of-place pixelation of 8-bit 4:2:0 frames (NV12, and every layout of vd_yuv420), all
-// planes in one launch; and, at the end, the copy that packs NV12 surfaces into the look-ahead ring
-// (vd_launch_nv12_pack).
+// planes in one launch; and, at the end, the copies that pack surfaces into the look-ahead ring: NV12
+// (vd_launch_nv12_pack) and every other layout, 8-bit or 16-bit words (vd_launch_yuv420_pack).
 //
 // Definition (include/vdmi.h at vd_nv12): for box b of the list being blurred, c = b clipped to
 // the frame and L = L(b) (vd_cell_level_hd of the box as stored): the luma plane takes the mosaic
@@ -513,7 +513,173 @@ __global__ __launch_bounds__(64 * PACK_ROWS) void nv12_pack_kernel(Nv12PackArgs 
     }
 }
 
+// ---- the same push from the other layouts, and for 16-bit words ----
+// The target is always the ring's layout: interleaved pairs, U first. ES: bytes a sample (2: whole 16-bit
+// words); CS: the source's chroma step; VF: an interleaved source holds V first. The shape is the kernel's
+// above -- one wave a row, PACK_ROWS rows a workgroup, grid-stride over the row groups, grid-x over the
+// target row in steps of PACK_STEP bytes -- and so is every luma row and every chroma row of an
+// interleaved, U-first source (<1, 2, false> with NV12's pitches is served by the kernel above, not this one).
+//   interleaved, V first: the same traffic, the two samples of each pair swapped in registers; the head
+//     up to the first 16-B boundary is whole pairs, so a row whose start splits a pair goes pair by pair;
+//   planar: a lane reads 8 samples of the U row and 8 of the V row (8 B + 8 B, or 16 B + 16 B of words)
+//     and writes their 8 pairs (one or two 16-B stores), from the first 16-B boundary of the target
+//     row on, where both source rows are aligned for those loads there; the pairs before it, the
+//     pairs past the last whole group, and every pair of any other row go sample by sample.
+// Bytes outside a row's samples are neither read nor written.
+struct YuvPackArgs {
+    const uint8_t* src; uint8_t* dst; int n, h, w;
+    size_t src_pitch, src_u, src_v, src_cp, src_stride, dst_pitch, dst_uv, dst_stride;
+};
+
+// [0, nb) of a row as the kernel above moves it
+__device__ __forceinline__ void pack_copy_row(const uint8_t* s, uint8_t* d, int nb, int lane) {
+    const bool vec = (((uintptr_t)s ^ (uintptr_t)d) & 15) == 0;
+    const int head = vec ? min(nb, (int)((16 - ((uintptr_t)s & 15)) & 15)) : nb;
+    const int nvec = (nb - head) >> 4, tail0 = head + (nvec << 4);
+    const int v = blockIdx.x * 64 + lane;
+    if (v < nvec) *(uint4*)(d + head + ((size_t)v << 4)) = *(const uint4*)(s + head + ((size_t)v << 4));
+    const int nbytes = head + (nb - tail0);
+    const int b1 = min(nbytes, (int)(blockIdx.x + 1) * PACK_STEP);
+    for (int i = blockIdx.x * PACK_STEP + lane; i < b1; i += 64) {
+        const int x = i < head ? i : tail0 + (i - head);
+        d[x] = s[x];
+    }
+}
+
+// pair x of a target row from its two samples
+template <int ES>
+__device__ __forceinline__ void pack_pair(const uint8_t* su, const uint8_t* sv, uint8_t* d, int x) {
+    if constexpr (ES == 2) {
+        *(uint16_t*)(d + 4 * (size_t)x) = *(const uint16_t*)(su + 2 * (size_t)x);
+        *(uint16_t*)(d + 4 * (size_t)x + 2) = *(const uint16_t*)(sv + 2 * (size_t)x);
+    } else {
+        d[2 * (size_t)x] = su[x];
+        d[2 * (size_t)x + 1] = sv[x];
+    }
+}
+
+template <int ES, int CS, bool VF>
+__global__ __launch_bounds__(64 * PACK_ROWS) void yuv420_pack_kernel(YuvPackArgs a) {
+    constexpr int PB = 2 * ES;                      // bytes of a pair
+    const int lane = threadIdx.x, rows = a.h + a.h / 2, np = a.w / 2;
+    const long long total = (long long)a.n * rows;
+    for (long long r = (long long)blockIdx.y * PACK_ROWS + threadIdx.y; r < total; r += (long long)gridDim.y * PACK_ROWS) {
+        const int f = (int)(r / rows), y = (int)(r - (long long)f * rows);
+        const uint8_t* sf = a.src + (size_t)f * a.src_stride;
+        uint8_t* d = a.dst + (size_t)f * a.dst_stride + pack_row(y, a.h, a.dst_pitch, a.dst_uv);
+        if (y < a.h) {
+            pack_copy_row(sf + (size_t)y * a.src_pitch, d, a.w * ES, lane);
+            continue;
+        }
+        const size_t crow = (size_t)(y - a.h) * a.src_cp;
+        if constexpr (CS == 2 && !VF) {
+            pack_copy_row(sf + a.src_u + crow, d, a.w * ES, lane);
+        } else if constexpr (CS == 2) {             // pairs V, U -> U, V
+            const uint8_t* s = sf + a.src_v + crow;
+            const bool vec = (((uintptr_t)s ^ (uintptr_t)d) & 15) == 0 && ((uintptr_t)s & (PB - 1)) == 0;
+            const int head = vec ? min(np, (int)(((16 - ((uintptr_t)s & 15)) & 15) / PB)) : np;
+            const int nvec = (np - head) / (16 / PB), tail0 = head + nvec * (16 / PB);
+            const int v = blockIdx.x * 64 + lane;
+            if (v < nvec) {
+                uint4 q = *(const uint4*)(s + (size_t)head * PB + ((size_t)v << 4));
+                if constexpr (ES == 2) {
+                    q = make_uint4((q.x << 16) | (q.x >> 16), (q.y << 16) | (q.y >> 16), (q.z << 16) | (q.z >> 16),
+                                   (q.w << 16) | (q.w >> 16));
+                } else {
+                    q = make_uint4(yuv_swap16(q.x), yuv_swap16(q.y), yuv_swap16(q.z), yuv_swap16(q.w));
+                }
+                *(uint4*)(d + (size_t)head * PB + ((size_t)v << 4)) = q;
+            }
+            const int npair = head + (np - tail0);
+            const int p1 = min(npair, (int)(blockIdx.x + 1) * (PACK_STEP / PB));
+            for (int i = blockIdx.x * (PACK_STEP / PB) + lane; i < p1; i += 64) {
+                const int x = i < head ? i : tail0 + (i - head);
+                const size_t o = (size_t)x * PB;    // U is the pair's second sample
+                if constexpr (ES == 2) {
+                    const uint16_t sv = *(const uint16_t*)(s + o), su = *(const uint16_t*)(s + o + 2);
+                    *(uint16_t*)(d + o) = su; *(uint16_t*)(d + o + 2) = sv;
+                } else {
+                    const uint8_t sv = s[o], su = s[o + 1];
+                    d[o] = su; d[o + 1] = sv;
+                }
+            }
+        } else {                                    // planar: one U row and one V row -> one row of pairs
+            const uint8_t* su = sf + a.src_u + crow;
+            const uint8_t* sv = sf + a.src_v + crow;
+            int head = np;
+            if (((uintptr_t)d & (PB - 1)) == 0) {
+                const int hp = min(np, (int)(((16 - ((uintptr_t)d & 15)) & 15) / PB));
+                if ((((uintptr_t)(su + (size_t)hp * ES) | (uintptr_t)(sv + (size_t)hp * ES)) & (8 * ES - 1)) == 0) head = hp;
+            }
+            const int nvec = (np - head) >> 3, tail0 = head + (nvec << 3);
+            // a lane's group is 16 * ES target bytes: a grid-x step of PACK_STEP bytes holds 64 / ES groups
+            const int g0 = blockIdx.x * (64 / ES), g1 = min(nvec, g0 + 64 / ES);
+            const int v = g0 + lane;
+            if (lane < 64 / ES && v < g1) {
+                const uint8_t* pu = su + (size_t)(head + 8 * v) * ES;
+                const uint8_t* pv = sv + (size_t)(head + 8 * v) * ES;
+                uint8_t* o = d + (size_t)(head + 8 * v) * PB;
+                uint32_t w[8];
+                if constexpr (ES == 2) {
+                    const uint4 p = *(const uint4*)pu, q = *(const uint4*)pv;
+                    yuv_join16(p.x, q.x, w[0], w[1]); yuv_join16(p.y, q.y, w[2], w[3]);
+                    yuv_join16(p.z, q.z, w[4], w[5]); yuv_join16(p.w, q.w, w[6], w[7]);
+                    *(uint4*)o = make_uint4(w[0], w[1], w[2], w[3]);
+                    *(uint4*)(o + 16) = make_uint4(w[4], w[5], w[6], w[7]);
+                } else {
+                    const uint2 p = *(const uint2*)pu, q = *(const uint2*)pv;
+                    yuv_join(p.x, q.x, w[0], w[1]); yuv_join(p.y, q.y, w[2], w[3]);
+                    *(uint4*)o = make_uint4(w[0], w[1], w[2], w[3]);
+                }
+            }
+            const int npair = head + (np - tail0);
+            const int p1 = min(npair, (int)(blockIdx.x + 1) * (PACK_STEP / PB));
+            for (int i = blockIdx.x * (PACK_STEP / PB) + lane; i < p1; i += 64) {
+                const int x = i < head ? i : tail0 + (i - head);
+                pack_pair<ES>(su, sv, d, x);
+            }
+        }
+    }
+}
+
+template <int ES>
+static void launch_yuv420_pack(const YuvPackArgs& a, int step, bool vfirst, dim3 grid, hipStream_t s) {
+    const dim3 block(64, PACK_ROWS);
+    if (step == 1) hipLaunchKernelGGL((yuv420_pack_kernel<ES, 1, false>), grid, block, 0, s, a);   // U and V by their offsets
+    else if (vfirst) hipLaunchKernelGGL((yuv420_pack_kernel<ES, 2, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((yuv420_pack_kernel<ES, 2, false>), grid, block, 0, s, a);
+}
+
 }  // namespace
+
+hipError_t vd_launch_yuv420_pack(const Yuv420Dev& src, const Yuv420Dev& ring, int n, int h, int w, hipStream_t s) {
+    const size_t es = (size_t)src.es();
+    if (n <= 0 || h <= 0 || w <= 0 || (h & 1) || (w & 1) || !src.base || !ring.base || (src.step != 1 && src.step != 2) ||
+        src.pitch < (size_t)w * es || src.cpitch < (size_t)(w / 2) * src.step * es || ring.es() != src.es() ||
+        ring.step != 2 || ring.v != ring.u + es || ring.cpitch != ring.pitch || ring.pitch < (size_t)w * es ||
+        (size_t)w * es > 0x7fffffffu)
+        return hipErrorInvalidValue;
+    if (src.nv12()) {   // the kernel NV12 callers have always run
+        Nv12PackArgs p{};
+        p.src = src.base; p.src_pitch = src.pitch; p.src_uv = src.u; p.src_stride = src.stride;
+        p.dst = ring.base; p.dst_pitch = ring.pitch; p.dst_uv = ring.u; p.dst_stride = ring.stride;
+        p.n = n; p.h = h; p.w = w;
+        return vd_launch_nv12_pack(p, s);
+    }
+    const uintptr_t even = (uintptr_t)src.base | src.pitch | src.cpitch | src.u | src.v | src.stride | (uintptr_t)ring.base |
+                           ring.pitch | ring.u | ring.stride;
+    if (es == 2 && (even & 1)) return hipErrorInvalidValue;   // words: the descriptor checks keep every byte quantity even
+    if (src.step == 2 && src.u + src.v - 2 * src.c0() != es) return hipErrorInvalidValue;
+    YuvPackArgs a{};
+    a.src = src.base; a.src_pitch = src.pitch; a.src_u = src.u; a.src_v = src.v; a.src_cp = src.cpitch; a.src_stride = src.stride;
+    a.dst = ring.base; a.dst_pitch = ring.pitch; a.dst_uv = ring.u; a.dst_stride = ring.stride;
+    a.n = n; a.h = h; a.w = w;
+    const long long groups = ((long long)n * (h + h / 2) + PACK_ROWS - 1) / PACK_ROWS;
+    const dim3 grid((unsigned)(((size_t)w * es + PACK_STEP - 1) / PACK_STEP), (unsigned)(groups < 65535 ? groups : 65535));
+    if (es == 2) launch_yuv420_pack<2>(a, src.step, src.v < src.u, grid, s);
+    else launch_yuv420_pack<1>(a, src.step, src.v < src.u, grid, s);
+    return hipGetLastError();
+}
 
 hipError_t vd_launch_nv12_pack(const Nv12PackArgs& a, hipStream_t s) {
     if (a.n <= 0 || a.h <= 0 || a.w <= 0 || (a.h & 1) || (a.w & 1) || a.src_pitch < (size_t)a.w ||

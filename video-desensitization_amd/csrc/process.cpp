@@ -1,5 +1,5 @@
 // process.cpp — detection and blurring: the blur passes behind the mask setting, the stand-alone
-// blur entries, vd_detect*, vd_read_boxes and vd_process / vd_process_lead and their NV12 forms.
+// blur entries, vd_detect*, vd_read_boxes and vd_process / vd_process_lead and their 4:2:0 forms.
 
 #include "../../include/vdmi.h"
 #include "vd_common.h"
@@ -478,8 +478,8 @@ static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh
         if (nv && lc) {   // look-ahead hold on surfaces: the m emitted ones leave through the output side
             int r = lc->m ? ctx->nv12_out_begin(*nv->out, lc->m, fh, fw, where, &nout) : VD_OK;
             if (r) return r;
-            if ((r = ctx->lead_step(VD_LEAD_MODE_NV12, nullptr, nullptr, n, fh, fw, 0, lc->flush, dc0, dx0, dk0, dc1, dx1, dk1,
-                                    &nin, &nout)))
+            if ((r = ctx->lead_step(nin.depth ? VD_LEAD_MODE_YUV16 : VD_LEAD_MODE_NV12, nullptr, nullptr, n, fh, fw, 0, lc->flush,
+                                    dc0, dx0, dk0, dc1, dx1, dk1, &nin, &nout)))
                 return r;
             return lc->m ? ctx->nv12_out_finish(*nv->out, nout, lc->m, fh, fw, where) : VD_OK;
         }
@@ -849,6 +849,87 @@ int vd_process_lead_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n
     if (rc) return rc;
     if (n_out) *n_out = m;
     return VD_OK;
+}
+
+// vd_process_lead_nv12 on any layout of vd_yuv420, or on the 16-bit words of vd_yuv420_16: the same rules
+// with the descriptor checks of vd_process_yuv420 / vd_process_yuv420_16. The 8-bit family shares the NV12
+// entry's ring and pending mode; 16-bit words have a ring form and a mode of their own, with depth and
+// shift part of the pending geometry.
+static int process_lead_420(Ctx* ctx, const char* who, const YuvIn& gin, const YuvIn& gout, bool words, int n, int fh, int fw,
+                            int where, int flags, vd_boxes* faces, vd_boxes* plates, int out_cap, int flush, int* n_out) {
+    if (where != VD_HOST && where != VD_DEVICE) return vd_set_error(VD_ERR_ARG, "%s: bad where", who);
+    if (n < 0 || out_cap < 0) return vd_set_error(VD_ERR_ARG, "%s: negative n / out_cap", who);
+    int rc;
+    YuvDesc in{}, out{};
+    if (n > 0) {
+        if (words && !gin.y16) return vd_set_error(VD_ERR_ARG, "%s: 16-bit 4:2:0 frames: null descriptor or base", who);
+        if ((rc = yuv_desc(who, gin, false, n, fh, fw, true, &in))) return rc;
+    } else if (fh <= 0 || fw <= 0 || (fh & 1) || (fw & 1)) {
+        return vd_set_error(VD_ERR_ARG, "%s: 4:2:0 frames: even, positive h and w required (got %d x %d)", who, fw, fh);
+    }
+    if (!ctx->lead.J) return vd_set_error(VD_ERR_STATE, "%s: look-ahead hold is off (vd_lead)", who);
+    if (!(flags & VD_PROC_MOSAIC)) return vd_set_error(VD_ERR_ARG, "%s: flags must include VD_PROC_MOSAIC", who);
+    if (!(flags & VD_PROC_FACES) && !(flags & VD_PROC_MOSAIC_PLATES))
+        return vd_set_error(VD_ERR_ARG, "%s: nothing to blur (FACES or MOSAIC_PLATES needed)", who);
+    if (n == 0 && flush && !ctx->lead.pend) {      // the end of an empty stream
+        if (n_out) *n_out = 0;
+        return VD_OK;
+    }
+    if (ctx->nv12_cfg_pass() < 0)
+        return vd_set_error(VD_ERR_STATE, "%s: the fixed-kernel Gaussian (blur_mode VD_BLUR_GAUSSIAN with cells off) has "
+                            "no NV12 pass: set cells (vd_cells) for the scaled smooth blur", who);
+    if (n > 0 && (((flags & VD_PROC_FACES) && ctx->faces_tiled()) || ((flags & VD_PROC_PLATES) && ctx->plates_tiled())))
+        return vd_set_error(VD_ERR_STATE, "%s: tiled detection (vd_tiles) reads RGB frames only", who);
+    // the words' format: the input's, or for a flush alone the output's (none given: nothing to compare)
+    int depth = 0, shift = 0;
+    if (words) {
+        depth = n > 0 ? in.d.depth : gout.y16 ? gout.y16->depth : ctx->lead.depth;
+        shift = n > 0 ? in.d.shift : gout.y16 ? gout.y16->shift : ctx->lead.shift;
+    }
+    const int mode = words ? VD_LEAD_MODE_YUV16 : VD_LEAD_MODE_NV12;
+    if ((rc = ctx->lead_check(who, mode, n, fh, fw, 0, flush, depth, shift))) return rc;
+    const int m = ctx->lead.emit(n, flush);
+    if (m > out_cap) return vd_set_error(VD_ERR_CAPACITY, "%s: %d frames to emit, out holds %d", who, m, out_cap);
+    if (m > 0) {
+        if (!gout.yu && !gout.y16) return vd_set_error(VD_ERR_ARG, "%s: MOSAIC needs an output descriptor", who);
+        if ((rc = yuv_desc(who, gout, false, m, fh, fw, false, &out))) return rc;
+        if (n > 0 && (rc = yuv_same_format(who, in, out))) return rc;
+        if (where == VD_DEVICE && n > 0) {
+            const uintptr_t a = (uintptr_t)in.d.base, b = (uintptr_t)out.d.base;
+            if (a < b + out.extent && b < a + in.extent) return vd_set_error(VD_ERR_ARG, "%s: out must not overlap in", who);
+        }
+    }
+    const LeadCall lc{flush, m};
+    if (n > 0) {
+        const Nv12Call nv{&in.d, m > 0 ? &out.d : nullptr, in.matrix, in.range};
+        rc = process_impl(ctx, nullptr, nullptr, n, fh, fw, 0, where, flags, faces, plates, &lc, &nv);
+    } else {      // flush alone: the pending surfaces leave, no detection
+        Ctx::Nv12Dev nin{}, nout{};
+        if ((rc = ctx->nv12_out_begin(out.d, m, fh, fw, where, &nout))) return rc;
+        if ((rc = ctx->lead_step(mode, nullptr, nullptr, 0, fh, fw, 0, 1, nullptr, nullptr, 0, nullptr, nullptr, 0, &nin, &nout)))
+            return rc;
+        if ((rc = ctx->nv12_out_finish(out.d, nout, m, fh, fw, where))) return rc;
+        if (where == VD_HOST) VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    if (rc) return rc;
+    if (n_out) *n_out = m;
+    return VD_OK;
+}
+
+int vd_process_lead_yuv420(vd_ctx* h, const vd_yuv420* in, const vd_yuv420* out, int n, int fh, int fw, int where, int flags,
+                           vd_boxes* faces, vd_boxes* plates, int out_cap, int flush, int* n_out) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    return process_lead_420(ctx, "vd_process_lead_yuv420", YuvIn{nullptr, in}, YuvIn{nullptr, out}, false, n, fh, fw, where,
+                            flags, faces, plates, out_cap, flush, n_out);
+}
+
+int vd_process_lead_yuv420_16(vd_ctx* h, const vd_yuv420_16* in, const vd_yuv420_16* out, int n, int fh, int fw, int where,
+                              int flags, vd_boxes* faces, vd_boxes* plates, int out_cap, int flush, int* n_out) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    return process_lead_420(ctx, "vd_process_lead_yuv420_16", YuvIn{nullptr, nullptr, in}, YuvIn{nullptr, nullptr, out}, true, n,
+                            fh, fw, where, flags, faces, plates, out_cap, flush, n_out);
 }
 
 int vd_read_boxes(vd_ctx* h, int net, int n, vd_boxes* out) {

@@ -125,7 +125,7 @@ int Ctx::lead_need(int cap0, int cap1) const {
 }
 
 // Everything a lead call can be refused for, before any state changes.
-int Ctx::lead_check(const char* who, int mode, int n, int h, int w, size_t pitch, int flush) {
+int Ctx::lead_check(const char* who, int mode, int n, int h, int w, size_t pitch, int flush, int depth, int shift) {
     if (!lead.J) return vd_set_error(VD_ERR_STATE, "%s: look-ahead hold is off (vd_lead)", who);
     if (n < 0 || (n == 0 && !flush)) return vd_set_error(VD_ERR_ARG, "%s: n == 0 is allowed only with flush", who);
     if (h <= 0 || w <= 0) return vd_set_error(VD_ERR_ARG, "%s: bad geometry %dx%d", who, w, h);
@@ -138,6 +138,9 @@ int Ctx::lead_check(const char* who, int mode, int n, int h, int w, size_t pitch
         if (lead.h != h || lead.w != w || (mode == VD_LEAD_MODE_PIXELS && lead.pitch != (unsigned long long)pitch))
             return vd_set_error(VD_ERR_STATE, "%s: %d frames of %dx%d (pitch %llu) are pending; got %dx%d (pitch %zu): "
                                 "flush first", who, lead.pend, lead.w, lead.h, lead.pitch, w, h, pitch);
+        if (!lead.format_ok(mode, depth, shift))   // the ring holds the words as pushed
+            return vd_set_error(VD_ERR_STATE, "%s: %d frames of depth %d, shift %d are pending; got depth %d, shift %d: "
+                                "flush first", who, lead.pend, lead.depth, lead.shift, depth, shift);
     }
     return VD_OK;
 }
@@ -182,9 +185,11 @@ int Ctx::lead_buffers(int need, size_t frame_bytes) {
 int Ctx::lead_step(int mode, const uint8_t* din, uint8_t* dout, int n, int h, int w, size_t pitch, int flush,
                    const int* cnt0, const int* xy0, int cap0, const int* cnt1, const int* xy1, int cap1,
                    const Nv12Dev* nvin, const Nv12Dev* nvout) {
-    const bool pixels = mode == VD_LEAD_MODE_PIXELS, nv12 = mode == VD_LEAD_MODE_NV12;
-    // a ring slot: an RGB frame as pushed, or a packed NV12 surface (pitch w, chroma at h * w): half the bytes
-    const size_t fb = pixels ? (size_t)h * pitch : nv12 ? (size_t)h * w / 2 * 3 : 0;
+    const bool pixels = mode == VD_LEAD_MODE_PIXELS, nv12 = mode == VD_LEAD_MODE_NV12 || mode == VD_LEAD_MODE_YUV16;
+    // a ring slot: an RGB frame as pushed, or a packed NV12 surface (pitch w, chroma at h * w): half the bytes,
+    // or the same of 16-bit words (pitch 2w, chroma at 2 * h * w): 3 * h * w bytes
+    const size_t es = mode == VD_LEAD_MODE_YUV16 ? 2 : 1;
+    const size_t fb = pixels ? (size_t)h * pitch : nv12 ? (size_t)h * w / 2 * 3 * es : 0;
     int rc = lead_buffers(std::max(lead_hcap, lead_need(cnt0 ? cap0 : 0, cnt1 ? cap1 : 0)), fb);
     if (rc) return rc;
     const int delay = lead.delay(), pend = lead.pend, m = lead.emit(n, flush), keep = pend + n - m;
@@ -239,8 +244,10 @@ int Ctx::lead_step(int mode, const uint8_t* din, uint8_t* dout, int n, int h, in
         t_end();
     }
     if (nv12) {
-        // the same on surfaces: a ring slot is itself a valid surface for the NV12 passes
-        const Nv12Dev ring = vd_yuv420_packed(lead_pix, h, w, 2, false);   // NV12, stride fb
+        // the same on surfaces: a ring slot is itself a valid surface for the 4:2:0 passes, whatever
+        // layout the call's input and output have; 16-bit words keep the depth and shift they came with
+        const Nv12Dev& fmt = n > 0 ? *nvin : *nvout;   // a flush alone emits: out is described
+        const Nv12Dev ring = vd_yuv420_packed(lead_pix, h, w, 2, false, fmt.depth, fmt.shift);   // interleaved, U first, stride fb
         const int mr = std::min(m, pend), mi = m - mr;
         const int pass = nv12_cfg_pass();
         if (mr && (rc = launch_nv12_pass(ring, *nvout, mr, h, w, a.m_count, a.m_xy, a.mcap, nullptr, nullptr, 0, pass,
@@ -264,19 +271,17 @@ int Ctx::lead_step(int mode, const uint8_t* din, uint8_t* dout, int n, int h, in
             t_end();
         }
         if (push > 0) {
-            Nv12PackArgs p{};
-            p.src = nvin->base + (size_t)mi * nvin->stride;
-            p.src_pitch = nvin->pitch; p.src_uv = nvin->u; p.src_stride = nvin->stride;   // the look-ahead entry takes NV12 only
-            p.dst = ring.base + (size_t)stay * fb;
-            p.dst_pitch = ring.pitch; p.dst_uv = ring.u; p.dst_stride = ring.stride;
-            p.n = push; p.h = h; p.w = w;
+            Nv12Dev src = *nvin, dst = ring;      // any layout in, the ring's out
+            src.base += (size_t)mi * src.stride;
+            dst.base += (size_t)stay * fb;
             t_begin(4, (double)push * fb * 2);
-            hipError_t e = vd_launch_nv12_pack(p, stream);
+            hipError_t e = vd_launch_yuv420_pack(src, dst, push, h, w, stream);
             t_end();
             if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "nv12 ring push: %s", hipGetErrorString(e));
         }
     }
-    lead.end(n, flush, mode, h, w, nv12 ? 0 : pitch);
+    lead.end(n, flush, mode, h, w, nv12 ? 0 : pitch, mode == VD_LEAD_MODE_YUV16 ? (n > 0 ? nvin : nvout)->depth : 0,
+             mode == VD_LEAD_MODE_YUV16 ? (n > 0 ? nvin : nvout)->shift : 0);
     lead_last = a;
     lead_m = m;
     return VD_OK;

@@ -522,6 +522,11 @@ struct Nv12PackArgs {
     size_t src_pitch, src_uv, src_stride, dst_pitch, dst_uv, dst_stride;
 };
 hipError_t vd_launch_nv12_pack(const Nv12PackArgs& a, hipStream_t s);
+// The same push from any layout of vd_yuv420 / vd_yuv420_16 (src.depth != 0: 16-bit words, copied whole)
+// into the ring's layout: `ring` is interleaved, U first, of src's sample size. One launch; an NV12
+// source runs the kernel of vd_launch_nv12_pack. Nothing is assumed of src beyond its descriptor's
+// checks; of ring, that its pairs are aligned to their size.
+hipError_t vd_launch_yuv420_pack(const Yuv420Dev& src, const Yuv420Dev& ring, int n, int h, int w, hipStream_t s);
 // Box-scaled strength (include/vdmi.h at vd_cells): the cell level L of a box of unclipped size
 // W x H under the base level and the cells setting. cells == 0 or an empty box: the base level;
 // otherwise max(level, min(32768, ceil(max(W, H) / cells))). The one routine of the kernels

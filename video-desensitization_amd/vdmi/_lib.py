@@ -187,6 +187,10 @@ SIGNATURES = [
                                  ctypes.POINTER(vd_boxes), _I, _I]),
     ("vd_yuv420_16_to_rgb", _I, [ctypes.POINTER(vd_yuv420_16), _I, _I, _I, _P, _SZ]),
     ("vdt_letterbox_yuv420_16", _I, [_P, ctypes.POINTER(vd_yuv420_16), _I, _I, _I, _I, _P, _I]),
+    ("vd_process_lead_yuv420", _I, [_P, ctypes.POINTER(vd_yuv420), ctypes.POINTER(vd_yuv420), _I, _I, _I, _I, _I,
+                                    ctypes.POINTER(vd_boxes), ctypes.POINTER(vd_boxes), _I, _I, ctypes.POINTER(_I)]),
+    ("vd_process_lead_yuv420_16", _I, [_P, ctypes.POINTER(vd_yuv420_16), ctypes.POINTER(vd_yuv420_16), _I, _I, _I, _I, _I,
+                                       ctypes.POINTER(vd_boxes), ctypes.POINTER(vd_boxes), _I, _I, ctypes.POINTER(_I)]),
     ("vd_timing_enable", _I, [_P, _I]),
     ("vd_timing_reset", _I, [_P]),
     ("vd_timing_read", _I, [_P, _I, ctypes.POINTER(_D), ctypes.POINTER(ctypes.c_int64),

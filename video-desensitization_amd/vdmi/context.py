@@ -1230,7 +1230,7 @@ class Context:
         if flags & _lib.VD_PROC_PLATES:
             plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
         self._lead_geom = (h, w, pitch, where, getattr(frames, "device", None))
-        self._lead_nv12 = None
+        self._lead_nv12 = self._lead_yuv = None
         return out[:m.value], faces, plates
 
     def process_lead_nv12(self, frames, out=None, faces=None, plates=None, flags=None, flush=False, matrix="bt709",
@@ -1274,8 +1274,114 @@ class Context:
         if flags & _lib.VD_PROC_PLATES:
             plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
         self._lead_nv12 = (h, w, rows, where, dev)
+        self._lead_yuv = None
         del keep
         return out[:m.value], faces, plates
+
+    def _lead_420(self, words, frames, out, faces, plates, flags, flush, layout, out_layout, depth, shift, matrix, range,
+                  height):
+        """What process_lead_yuv420() / process_lead_yuv420_16() share."""
+        if flags is None:
+            flags = _lib.VD_PROC_FACES | _lib.VD_PROC_MOSAIC
+        if frames is None:
+            return self.lead_flush(out), faces, plates
+        if words:
+            d, n, h, w, where, keep = _yuv420_16_arg(frames, layout, depth, shift, height, matrix, range)
+            fmt = (d.depth, d.shift)
+            fn = self._lib.vd_process_lead_yuv420_16
+        else:
+            d, n, h, w, where, keep = _yuv420_arg(frames, layout, height, matrix, range)
+            fmt = ()
+            fn = self._lib.vd_process_lead_yuv420
+        olay = out_layout or layout
+        src = frames.buffer if isinstance(frames, (Yuv420, Yuv420_16)) else frames
+        dev = src.device if _is_torch(src) else None
+        if out is None:
+            out = self._yuv420_new(self.lead_pending() + n, h, w, dev, words)
+            oheight = None
+        else:
+            oheight = height
+        od, cap = None, (out.n if isinstance(out, (Yuv420, Yuv420_16)) else len(out))
+        if cap:
+            if words:
+                od, cap, oh, ow, owhere, okeep = _yuv420_16_arg(out, olay, *fmt, oheight, writable=True)
+            else:
+                od, cap, oh, ow, owhere, okeep = _yuv420_arg(out, olay, oheight, writable=True)
+            if (oh, ow, owhere) != (h, w, where):
+                raise ValueError("out must hold 4:2:0 frames of the input's h, w in the same memory (host / device)")
+        fs = ps = None
+        auto_f, auto_p = faces is None, plates is None
+        if flags & _lib.VD_PROC_FACES:
+            faces = self._boxes(faces, n)
+            fs = faces.struct()
+        if flags & _lib.VD_PROC_PLATES:
+            plates = self._boxes(plates, n)
+            ps = plates.struct()
+        m = ctypes.c_int(0)
+        check(fn(self._h, ctypes.byref(d), ctypes.byref(od) if od is not None else None, n, h, w, where, flags,
+                 ctypes.byref(fs) if fs is not None else None, ctypes.byref(ps) if ps is not None else None, cap,
+                 1 if flush else 0, ctypes.byref(m)))
+        if flags & _lib.VD_PROC_FACES:
+            faces = self._complete(faces, _lib.VD_NET_RETINAFACE, auto_f)
+        if flags & _lib.VD_PROC_PLATES:
+            plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
+        self._lead_yuv = (words, h, w, dev, olay, fmt)
+        self._lead_nv12 = None
+        del keep
+        return (out if isinstance(out, (Yuv420, Yuv420_16)) else out[:m.value]), faces, plates
+
+    def process_lead_yuv420(self, frames, out=None, faces=None, plates=None, flags=None, flush=False, layout="i420",
+                            out_layout=None, matrix="bt709", range="limited", height=None):
+        """vd_process_lead_yuv420: process_lead_nv12() on 8-bit 4:2:0 frames in any layout (the argument
+        forms of process_yuv420()). Lists and every emitted sample are exactly process_lead_nv12()'s on
+        the NV12 frames with the same samples; in and out layouts are independent and either may change
+        from call to call (h and w may not); one stream may be pushed by this call and
+        process_lead_nv12() in turn. out defaults to new packed surfaces for pending + n frames in
+        `out_layout or layout`, in the memory the input lives in. frames may be None with flush=True.
+        -> (out[:m], faces, plates); a Yuv420 out comes back whole, its first m surfaces written
+        (m = the drop in lead_pending() + n)."""
+        return self._lead_420(False, frames, out, faces, plates, flags, flush, layout, out_layout, None, None, matrix, range,
+                              height)
+
+    def process_lead_yuv420_16(self, frames, out=None, faces=None, plates=None, flags=None, flush=False, layout="i420",
+                               out_layout=None, matrix="bt709", range="limited", height=None, depth=10, shift=None):
+        """vd_process_lead_yuv420_16: process_lead_yuv420() on 10- or 12-bit 4:2:0 frames (the argument
+        forms of process_yuv420_16()). Lists are exactly process_lead_yuv420()'s on the frames' 8-bit
+        picture; the blur acts on the 16-bit samples and every word no box owns comes back as it was.
+        out keeps the input's depth and shift, which must not change while surfaces are pending.
+        -> (out[:m], faces, plates)."""
+        return self._lead_420(True, frames, out, faces, plates, flags, flush, layout, out_layout, depth, shift, matrix, range,
+                              height)
+
+    @staticmethod
+    def _yuv420_new(n, h, w, dev, words):
+        """n new packed 4:2:0 surfaces [n, 3h/2, w], 8-bit or 16-bit words, on the host or on `dev`."""
+        if dev is None:
+            return np.empty((n, h // 2 * 3, w), np.uint16 if words else np.uint8)
+        import torch
+        return torch.empty((n, h // 2 * 3, w), dtype=torch.int16 if words else torch.uint8, device=dev)
+
+    def _lead_flush_yuv(self, out, pend):
+        words, h, w, dev, olay, fmt = self._lead_yuv
+        if out is None:
+            out = self._yuv420_new(pend, h, w, dev, words)
+        whole = isinstance(out, (Yuv420, Yuv420_16))
+        cap = out.n if whole else len(out)
+        if pend == 0 or cap == 0:
+            if pend:
+                raise _lib.VdCapacityError(_lib.VD_ERR_CAPACITY, f"{pend} frames to emit, out holds 0")
+            return out if whole else out[:0]
+        if words:
+            od, cap, oh, ow, owhere, okeep = _yuv420_16_arg(out, olay, *fmt, h, writable=True)
+            fn = self._lib.vd_process_lead_yuv420_16
+        else:
+            od, cap, oh, ow, owhere, okeep = _yuv420_arg(out, olay, h, writable=True)
+            fn = self._lib.vd_process_lead_yuv420
+        m = ctypes.c_int(0)
+        check(fn(self._h, None, ctypes.byref(od), 0, h, w, owhere, _lib.VD_PROC_FACES | _lib.VD_PROC_MOSAIC, None, None, cap,
+                 1, ctypes.byref(m)))
+        del okeep
+        return out if whole else out[:m.value]
 
     @staticmethod
     def _nv12_new(n, rows, w, where, dev):
@@ -1305,8 +1411,12 @@ class Context:
         """End the stream: the pending frames of process_lead() leave, blurred with what is
         known (vd_process_lead with n == 0 and flush). -> out[:m]; out defaults to a new array
         / tensor like the frames pushed last. Pending frames of process_lead_nv12() leave as NV12
-        surfaces (vd_process_lead_nv12), host or device as they were pushed, with their luma height."""
+        surfaces (vd_process_lead_nv12), host or device as they were pushed, with their luma height;
+        those of process_lead_yuv420() / process_lead_yuv420_16() as packed surfaces in the family, the
+        (output) layout, depth and shift of the last push."""
         pend = self.lead_pending()
+        if getattr(self, "_lead_yuv", None) is not None:
+            return self._lead_flush_yuv(out, pend)
         if getattr(self, "_lead_nv12", None) is not None:
             return self._lead_flush_nv12(out, pend)
         geom = getattr(self, "_lead_geom", None)
