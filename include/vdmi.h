@@ -658,7 +658,8 @@ int vd_tiles_merge(vd_ctx* ctx, const vd_boxes* lists, int n, int h, int w, vd_b
  * vd_read_boxes(VD_NET_YOLOV8N), the plate part of D_t for hold, lead and the blur list under
  * VD_PROC_MOSAIC_PLATES. Capacity: a call that runs a tiled net needs n*T <= cfg.max_batch
  * (VD_ERR_ARG, the message names the largest n), whichever net is tiled. Rescue with tiling on stays
- * refused for any nets value, and an NV12 call that would run a tiled net is VD_ERR_STATE. */
+ * refused for any nets value, and a 4:2:0 surface call (the *_nv12, *_yuv420 and *_yuv420_16 entries)
+ * that would run a tiled net is VD_ERR_STATE unless vd_tiles_surfaces (below) has been turned on. */
 #define VD_TILE_FACES 1
 #define VD_TILE_PLATES 2
 /* Which nets the tiling applies to: nets in {VD_TILE_FACES, VD_TILE_PLATES, VD_TILE_FACES |
@@ -672,6 +673,27 @@ int vd_tiles_nets(vd_ctx* ctx, int nets);
  * keep capacity; `label` is read as the class (NULL: 0). VD_ERR_STATE with tiling off or before the
  * plate weights are loaded. */
 int vd_tiles_merge_plates(vd_ctx* ctx, const vd_boxes* lists, int n, int h, int w, vd_boxes* out);
+
+/* ---- tiled detection on 4:2:0 surfaces ----------------------------------------------
+ * 4K footage arrives as decoder surfaces, and tiling exists for 4K footage. With on = 1 the surface
+ * entries vd_process_nv12, vd_process_yuv420, vd_process_yuv420_16, vd_process_lead_nv12,
+ * vd_process_lead_yuv420 and vd_process_lead_yuv420_16 run the tiled nets of the context (vd_tiles,
+ * vd_tiles_nets) instead of refusing. Nothing new is computed: net input f*T + t (plates: f*R*C + t - 1)
+ * is bit-identical to the RGB tile letterbox of rectangle t of *_to_rgb(frame f), so every list
+ * (detected, merged, held, led) equals the RGB tiled call's on the converted frames and every output
+ * sample is what the surface pass writes for those lists. The conversion is per pixel with the chroma
+ * sample of (y >> 1, x >> 1) of the FRAME, so the tile letterbox reads a tile at origin (y0, x0) with
+ * its luma at (y0, x0), its chroma at (y0 >> 1, x0 >> 1) and the origin's parities (y0 & 1, x0 & 1):
+ * tile origins and extents are odd in ordinary settings (1920x1080, (3, 3, 15): y0 = 333). 16-bit
+ * surfaces: detection sees the 8-bit picture, as untiled. Capacity as for RGB: n*T <= cfg.max_batch
+ * (VD_ERR_ARG, the message names the largest n).
+ * Opt-in, because a caller of a surface entry in a tiling context was promised a refusal and must
+ * not silently get 1 + R*C net passes per frame: on = 0 (the default) keeps the refusal, VD_ERR_STATE
+ * with a message that names vd_tiles_surfaces. on outside {0, 1} is VD_ERR_ARG; VD_ERR_STATE while
+ * lead frames are pending; setting the value the context already has changes nothing. The hold
+ * history is kept (the merged rows' capacities depend on vd_tiles / vd_tiles_nets only). Rescue with
+ * tiling, the fixed 31-tap Gaussian on surfaces, 4:2:2 / 4:4:4 and depth conversion stay refused. */
+int vd_tiles_surfaces(vd_ctx* ctx, int on);
 
 /* ---- NV12 frames: detect and blur video surfaces directly -------------------------
  * A video decoder hands out NV12 surfaces and an encoder takes them back: a pitched luma plane
@@ -804,7 +826,7 @@ int vd_smooth_nv12(vd_ctx* ctx, const vd_nv12* in, const vd_nv12* out, int n, in
  * neither VD_PROC_FACES nor VD_PROC_MOSAIC_PLATES, VD_ERR_ARG; m > out_cap VD_ERR_CAPACITY; m > 0 with
  * `out` NULL VD_ERR_ARG; device in / out ranges (n * frame_stride, m * frame_stride) that overlap
  * VD_ERR_ARG; a VD_BLUR_GAUSSIAN context with cells off VD_ERR_STATE; a call that would run a tiled net
- * VD_ERR_STATE; h or w differing from the pending frames' VD_ERR_STATE (flush first); frames pending
+ * while vd_tiles_surfaces is off VD_ERR_STATE; h or w differing from the pending frames' VD_ERR_STATE (flush first); frames pending
  * from vd_process_lead or vd_lead_lists VD_ERR_STATE, as are those two calls while NV12 frames are
  * pending; motion with h or w > 32768 VD_ERR_ARG. Everything vd_lead lists as refused while frames are
  * pending is refused for pending NV12 frames too, and vd_hold_reset abandons them. */
@@ -853,9 +875,10 @@ int vd_nv12_to_rgb(const vd_nv12* in, int n, int h, int w, uint8_t* rgb, size_t 
  * overlap each other or the luma plane (u_offset / v_offset); a plane that reaches past
  * frame_stride when n > 1; unknown matrix or range (detection and conversion); device `out`
  * overlapping device `in` (the whole extents of the n frames). VD_ERR_STATE, with the messages of
- * vd_process_nv12: a VD_BLUR_GAUSSIAN context with cells off; a call that would run a tiled net;
+ * vd_process_nv12: a VD_BLUR_GAUSSIAN context with cells off; a call that would run a tiled net while
+ * vd_tiles_surfaces is off;
  * VD_PROC_MOSAIC in a look-ahead context (the look-ahead call is vd_process_lead_yuv420, below). Not in
- * this version: tiling and the fixed Gaussian on surfaces (both refused, above), 4:2:2 and 4:4:4. 10- and
+ * this version: rescue with tiling and the fixed Gaussian on surfaces (both refused), 4:2:2 and 4:4:4. 10- and
  * 12-bit surfaces (P010, yuv420p10le) have a descriptor of their own: vd_yuv420_16, below. */
 typedef struct vd_yuv420 {
     uint8_t* base;        /* first luma byte of frame 0 */
@@ -890,7 +913,7 @@ int vd_smooth_yuv420(vd_ctx* ctx, const vd_yuv420* in, const vd_yuv420* out, int
  * VD_PROC_MOSAIC, or with neither VD_PROC_FACES nor VD_PROC_MOSAIC_PLATES, VD_ERR_ARG; m > out_cap
  * VD_ERR_CAPACITY; m > 0 with `out` NULL VD_ERR_ARG; device extents of `in` and `out` that overlap
  * VD_ERR_ARG; a VD_BLUR_GAUSSIAN context with cells off VD_ERR_STATE; a call that would run a tiled net
- * VD_ERR_STATE; h or w differing from the pending surfaces' VD_ERR_STATE (flush first); frames pending
+ * while vd_tiles_surfaces is off VD_ERR_STATE; h or w differing from the pending surfaces' VD_ERR_STATE (flush first); frames pending
  * from vd_process_lead, vd_lead_lists or vd_process_lead_yuv420_16 VD_ERR_STATE, as are those calls while
  * these surfaces are pending; motion with h or w > 32768 VD_ERR_ARG. vd_hold_reset abandons pending
  * surfaces, and everything vd_lead refuses while frames are pending stays refused. */
@@ -943,9 +966,10 @@ int vd_yuv420_to_rgb(const vd_yuv420* in, int n, int h, int w, uint8_t* rgb, siz
  * u_offset, v_offset or frame_stride or a base that is not 2-byte aligned; pitch < 2*w; depth
  * outside {10, 12}; shift outside [0, 16 - depth]; chroma_step 2 with |u_offset - v_offset| != 2.
  * VD_ERR_STATE with the messages of vd_process_yuv420: a VD_BLUR_GAUSSIAN context with cells off; a
- * call that would run a tiled net; VD_PROC_MOSAIC in a look-ahead context (the look-ahead call is
- * vd_process_lead_yuv420_16, below). Not in this version: tiling and the fixed Gaussian on surfaces (both
- * refused), depth or shift conversion between in and out, 16-bit-deep samples, 4:2:2 and 4:4:4. */
+ * call that would run a tiled net while vd_tiles_surfaces is off; VD_PROC_MOSAIC in a look-ahead
+ * context (the look-ahead call is vd_process_lead_yuv420_16, below). Not in this version: rescue with
+ * tiling and the fixed Gaussian on surfaces (both refused), depth or shift conversion between in and
+ * out, 16-bit-deep samples, 4:2:2 and 4:4:4. */
 typedef struct vd_yuv420_16 {
     uint8_t* base;        /* first luma word of frame 0 (2-byte aligned) */
     size_t   pitch;       /* luma row pitch, bytes (even, >= 2*w) */
@@ -1002,6 +1026,14 @@ int vdt_letterbox(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w, size_
  * the tile letterbox kernel of the detect path: out_nhwc [n*T][H][W][cpad], canvas f*T+t. */
 int vdt_letterbox_tiles(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w, size_t pitch,
                         int where, float* out_nhwc, int cpad);
+/* vdt_letterbox_tiles for surfaces, by the tile letterbox kernel of the product path with the pixel
+ * source the entries of that family use (NV12: source 1; any vd_yuv420 layout: 2; 16-bit words: 3).
+ * The switch vd_tiles_surfaces is not read. */
+int vdt_letterbox_tiles_nv12(vd_ctx* ctx, const vd_nv12* frames, int n, int h, int w, int where, float* out_nhwc, int cpad);
+int vdt_letterbox_tiles_yuv420(vd_ctx* ctx, const vd_yuv420* frames, int n, int h, int w, int where, float* out_nhwc,
+                               int cpad);
+int vdt_letterbox_tiles_yuv420_16(vd_ctx* ctx, const vd_yuv420_16* frames, int n, int h, int w, int where, float* out_nhwc,
+                                  int cpad);
 /* vdt_letterbox for NV12 frames (vd_nv12), by the NV12 letterbox kernel of the product path. */
 int vdt_letterbox_nv12(vd_ctx* ctx, const vd_nv12* frames, int n, int h, int w, int where, float* out_nhwc, int cpad);
 /* ... for 4:2:0 frames in any layout (vd_yuv420), by the letterbox kernel the product path runs for that layout. */
@@ -1102,6 +1134,10 @@ int vdt_plate_raw(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w, size_
  * vdt_plate_raw's layout; out NULL queries A. n*T <= cfg.max_batch as for the detect calls. */
 int vdt_plate_raw_tiles(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w, size_t pitch,
                         int where, float* out, int* anchors);
+/* vdt_plate_raw_tiles for 4:2:0 frames in any layout (vd_yuv420), by the tile-only letterbox kernel with
+ * the surfaces' pixel source; the switch vd_tiles_surfaces is not read. */
+int vdt_plate_raw_tiles_yuv420(vd_ctx* ctx, const vd_yuv420* frames, int n, int h, int w, int where, float* out,
+                               int* anchors);
 /* Plate post-processing only (score, threshold, DFL decode, NMS, scale_boxes) on caller-provided raw
  * heads in vdt_plate_raw's layout, host f32 [n][64 + nc][A], for n frames of h x w whose canvas the
  * context's last plate forward (vdt_plate_raw, vd_detect_plates, vd_process) was run for; honours the

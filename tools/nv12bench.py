@@ -257,9 +257,124 @@ def modes(a):
     return res
 
 
+# ---- --tiles: tiled detection on 4:2:0 surfaces at 4K ------------------------------------------------
+TILES_NEW = ("vd_tiles_surfaces", "vdt_letterbox_tiles_nv12", "vdt_letterbox_tiles_yuv420", "vdt_letterbox_tiles_yuv420_16",
+             "vdt_plate_raw_tiles_yuv420")
+TILES_ROWS = ("rgb_tiled", "nv12", "i420", "p010", "nv12_tiled", "i420_tiled", "p010_tiled")
+
+
+def one_tiles(a):
+    """--one tiles-parent | tiles-this: every row this library has; an untiled and a tiled context."""
+    import torch
+    from vdmi import _lib
+    parent = a.one == "tiles-parent"
+    if parent:               # the parent's build has neither the switch nor the surface tile hooks
+        _lib.SIGNATURES = [s for s in _lib.SIGNATURES if s[0] not in TILES_NEW]
+    import vdmi
+    from vdmi import weights
+    B, H, W = 4, 2160, 3840
+    dev = torch.device("cuda:0")
+    nv = nv12_frames(B, H, W, dev)
+    host = nv.cpu().numpy()
+    rgb = torch.from_numpy(vdmi.nv12_to_rgb(host)).to(dev)
+    planes = host[:, H:].reshape(B, H // 2, W // 2, 2)
+    i420 = torch.from_numpy(host.copy()).to(dev)
+    i420[:, H:] = torch.from_numpy(planes.transpose(0, 3, 1, 2).copy().reshape(B, H // 2, W)).to(dev)
+    p010 = (nv.to(torch.int16) << 8)                       # 10 bits at shift 6: the 8-bit picture is nv
+    flags = _lib.VD_PROC_FACES | _lib.VD_PROC_PLATES | _lib.VD_PROC_MOSAIC
+    ctxs = {}
+    for tiled in (False, True):
+        kw = dict(tiles=(2, 2), tile_overlap=20) if tiled else {}
+        if tiled and not parent:
+            kw["tile_surfaces"] = True
+        c = vdmi.Context(device=0, precision="fp32", max_batch=20, **kw)
+        c.load_weights(_lib.VD_NET_RETINAFACE, weights.retinaface_state_dict(0))
+        c.load_weights(_lib.VD_NET_YOLOV8N, weights.yolov8n_state_dict(0))
+        ctxs[tiled] = c
+    faces, plates = vdmi.DeviceBoxes(B, 256, dev), vdmi.DeviceBoxes(B, 256, dev)
+    out = {"rgb": torch.empty_like(rgb), "nv12": torch.empty_like(nv), "i420": torch.empty_like(i420), "p010": torch.empty_like(p010)}
+    kw = dict(faces=faces, plates=plates, flags=flags)
+    calls = {"rgb": lambda c: c.process(rgb, out["rgb"], **kw), "nv12": lambda c: c.process_nv12(nv, out["nv12"], **kw),
+             "i420": lambda c: c.process_yuv420(i420, out["i420"], layout="i420", **kw),
+             "p010": lambda c: c.process_yuv420_16(p010, out["p010"], layout="nv12", depth=10, shift=6, **kw)}
+    torch.cuda.synchronize()
+    r = {"rows": {}}
+    for name in TILES_ROWS:
+        tiled = name.endswith("_tiled")
+        if parent and tiled and name != "rgb_tiled":
+            continue
+        ctx, step = ctxs[tiled], calls[name.split("_")[0]]
+        for _ in range(max(a.warmup, 1)):
+            step(ctx)
+        ctx.sync()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            step(ctx)
+        ctx.sync()
+        ms = (time.perf_counter() - t0) * 1e3 / a.steps
+        ctx.timing(True)
+        ctx.timing_reset()
+        for _ in range(a.fam_steps):
+            step(ctx)
+        ctx.sync()
+        t, launches, work = ctx.timing_read(_lib.FAM_LETTERBOX)
+        ctx.timing(False)
+        r["rows"][name] = {"ms_per_step": round(ms, 3), "letterbox_ms_per_step": round(t / a.fam_steps, 4),
+                           "letterbox_launches_per_step": launches / a.fam_steps,
+                           "letterbox_bytes_per_step": work / a.fam_steps,
+                           "faces_per_frame": float(faces.count.float().mean().item())}
+    for c in ctxs.values():
+        c.close()
+    print("NV12BENCH " + json.dumps(r), flush=True)
+
+
+def tiles(a):
+    import numpy as np
+    import vdmi
+    runs = {"parent": [], "this": []}
+    for _ in range(a.repeats):                   # parent, this, parent, this, ...
+        for which in ("parent", "this"):
+            runs[which].append(child(a, "tiles-" + which)["rows"])
+    col = lambda k, row, key: [r[row][key] for r in runs[k] if row in r]
+    mean = lambda v: round(sum(v) / len(v), 4)
+    res = {"what": "4-frame steps of 3840x2160 device frames (faces | plates | mosaic, fp32, max_batch 20); *_tiled: tiles "
+                   "(2, 2, 20) on the face net; nv12 / i420 / p010: surfaces, rgb: the converted frames; letterbox: "
+                   "timing family 2, event-timed in steps of their own",
+           "machine": "one MI355X, parent and this build alternating in one session, a process each",
+           "steps": a.steps, "warmup": a.warmup, "repeats": a.repeats, "fam_steps": a.fam_steps, "rows": {}}
+    for row in TILES_ROWS:
+        e = {}
+        for k in ("parent", "this"):
+            for key in ("ms_per_step", "letterbox_ms_per_step"):
+                v = col(k, row, key)
+                if v:
+                    e[f"{k}_{key}"] = v
+                    e[f"{k}_{key}_mean"] = mean(v)
+                    e[f"{k}_{key}_spread"] = round(max(v) - min(v), 4)
+        b = col("this", row, "letterbox_bytes_per_step")
+        e["letterbox_bytes_per_step"] = b[0] if b else None
+        e["faces_per_frame"] = col("this", row, "faces_per_frame")[0]
+        if "parent_ms_per_step_mean" in e:       # (a): this build minus the parent, beside the parent's own spread
+            e["this_minus_parent_ms"] = round(e["this_ms_per_step_mean"] - e["parent_ms_per_step_mean"], 4)
+        res["rows"][row] = e
+    t = res["rows"]
+    res["tiled_surface_over_tiled_rgb"] = {   # (b)
+        k: {"step": round(t[k + "_tiled"]["this_ms_per_step_mean"] / t["rgb_tiled"]["this_ms_per_step_mean"], 4),
+            "letterbox": round(t[k + "_tiled"]["this_letterbox_ms_per_step_mean"] /
+                               t["rgb_tiled"]["this_letterbox_ms_per_step_mean"], 4)} for k in ("nv12", "i420", "p010")}
+    nv = np.random.default_rng(0).integers(0, 256, (4, 2160 * 3 // 2, 3840), dtype=np.uint8)
+    t0 = time.perf_counter()                     # (c)
+    vdmi.nv12_to_rgb(nv)
+    res["host_nv12_to_rgb_4x4k_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+    res["staging_from_16B_rounded_down_address"] = (
+        "not tried: at 3840x2160 the tile origins of (2, 2, 20) and (3, 3, 15) (x0 = 1536; 1184 and 2368) are multiples of 16, so "
+        "their rows are staged with 16-B loads already; unaligned origins are staged byte-wise, as the RGB tile rows are (unmeasured)")
+    return res
+
+
 def child(a, which):
     env = dict(os.environ)
-    if which in ("parent", "modes-parent"):
+    if which in ("parent", "modes-parent", "tiles-parent"):
         env["VDMI_LIB"] = os.path.abspath(a.parent_lib)
     else:
         env.pop("VDMI_LIB", None)
@@ -285,7 +400,8 @@ def main():
     ap.add_argument("--fam-steps", type=int, default=5, help="event-timed steps behind the family figures")
     ap.add_argument("--child-timeout", type=int, default=240)
     ap.add_argument("--no-torch", action="store_true", help="skip the informational torch round trip")
-    ap.add_argument("--one", choices=KINDS + ("torch", "modes-parent", "modes-this"),
+    ap.add_argument("--tiles", action="store_true", help="tiled detection on 4:2:0 surfaces at 4K instead of the full step")
+    ap.add_argument("--one", choices=KINDS + ("torch", "modes-parent", "modes-this", "tiles-parent", "tiles-this"),
                     help="(internal) one measurement in this process")
     ap.add_argument("--modes", action="store_true", help="the smooth and ellipse passes instead of the full step")
     ap.add_argument("--level", type=int, default=8, help="--modes: the base level")
@@ -293,11 +409,11 @@ def main():
     ap.add_argument("--json", help="also write the result line to this file")
     a = ap.parse_args()
     if a.one:
-        return one_modes(a) if a.one.startswith("modes-") else one(a)
+        return one_tiles(a) if a.one.startswith("tiles-") else one_modes(a) if a.one.startswith("modes-") else one(a)
     if not a.parent_lib or not os.path.exists(a.parent_lib):
         ap.error("--parent-lib: the parent commit's libvdmi.so is needed for the comparison")
-    if a.modes:
-        line = json.dumps(modes(a))
+    if a.modes or a.tiles:
+        line = json.dumps(tiles(a) if a.tiles else modes(a))
         print(line, flush=True)
         if a.json:
             os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)

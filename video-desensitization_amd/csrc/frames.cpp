@@ -529,7 +529,8 @@ int Ctx::face_letterbox_tiles(const uint8_t* dframes, int n, int h, int w, size_
     face_letterbox_args(dframes, n, h, w, pitch, &wa);
     face_letterbox_args(dframes, n, g.th, g.tw, pitch, &ta);
     const double canvas = (double)wa.oh * wa.ow * wa.cpad * (f32 ? 4 : 2);
-    t_begin(2, (double)n * (wa.nh * (double)w * 3 + (g.T - 1) * (ta.nh * (double)g.tw * 3) + g.T * canvas));
+    const double bpp = vd_src_bpp(wa.nv);         // a surface call in flight: 1.5 B/px of source (16-bit words: 3)
+    t_begin(2, (double)n * (wa.nh * (double)w * bpp + (g.T - 1) * (ta.nh * (double)g.tw * bpp) + g.T * canvas));
     hipError_t e = vd_launch_letterbox_tiles(wa, ta, g, stream);
     t_end();
     if (e != hipSuccess) return vd_set_error(VD_ERR_HIP, "tile letterbox: %s", hipGetErrorString(e));
@@ -603,6 +604,24 @@ int Ctx::tiles_nets_set(int nets) {
         hold.reset();                                 // the merged rows change capacity: a new stream
     }
     tile_nets = nets;
+    return VD_OK;
+}
+
+int Ctx::tiles_surfaces_set(int on) {
+    if (on != 0 && on != 1) return vd_set_error(VD_ERR_ARG, "vd_tiles_surfaces: on %d (expected 0 or 1)", on);
+    if (on == tile_surfaces) return VD_OK;
+    if (lead.pend)
+        return vd_set_error(VD_ERR_STATE, "vd_tiles_surfaces: %d frames are pending in the look-ahead ring (flush first)",
+                            lead.pend);
+    tile_surfaces = on;
+    return VD_OK;
+}
+
+int Ctx::tiles_surfaces_check(const char* who, int flags) const {
+    if (tile_surfaces) return VD_OK;
+    if (((flags & VD_PROC_FACES) && faces_tiled()) || ((flags & VD_PROC_PLATES) && plates_tiled()))
+        return vd_set_error(VD_ERR_STATE, "%s: tiled detection (vd_tiles) reads RGB frames only while vd_tiles_surfaces "
+                            "is off", who);
     return VD_OK;
 }
 
@@ -684,6 +703,12 @@ int vd_tiles(vd_ctx* h, int rows, int cols, int overlap_pct) {
     Ctx* ctx = (Ctx*)h;
     VD_ENTRY(ctx);
     return ctx->tiles_set(rows, cols, overlap_pct);
+}
+
+int vd_tiles_surfaces(vd_ctx* h, int on) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    return ctx->tiles_surfaces_set(on);
 }
 
 int vd_tiles_merge(vd_ctx* h, const vd_boxes* lists, int n, int fh, int fw, vd_boxes* out) {

@@ -346,6 +346,12 @@ struct Ctx {
     bool faces_tiled() const { return tiles_on() && (tile_nets & VD_TILE_FACES); }
     bool plates_tiled() const { return tiles_on() && (tile_nets & VD_TILE_PLATES); }
     int tiles_nets_set(int nets);
+    // whether the 4:2:0 surface entries run a tiled net (vd_tiles_surfaces; 0: they refuse, as they always
+    // did). Read by those entries only: no capacity depends on it, so setting it keeps the hold history.
+    int tile_surfaces = 0;
+    int tiles_surfaces_set(int on);
+    // the surface entries' refusal of a call that would run a tiled net while the switch is off
+    int tiles_surfaces_check(const char* who, int flags) const;
     // tiled plate detection: the plate lists' merged rows + spill scratch (allocated by the first merge)
     void* ptiles_buf = nullptr; size_t ptiles_buf_bytes = 0;
     TileMergeArgs ptiles_last{};                  // the last plate merge (merged-row pointers for the readers)

@@ -536,6 +536,28 @@ extern "C" int vdt_plate_raw_tiles(vd_ctx* h, const uint8_t* frames, int n, int 
     return plate_heads_out(ctx, n * (g.T - 1), out, anchors);
 }
 
+extern "C" int vdt_plate_raw_tiles_yuv420(vd_ctx* h, const vd_yuv420* frames, int n, int fh, int fw, int where, float* out,
+                                          int* anchors) {
+    Ctx* ctx = (Ctx*)h;
+    if (!ctx) return vd_set_error(VD_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return vd_set_error(VD_ERR_HIP, "hipSetDevice");
+    const char* who = "vdt_plate_raw_tiles_yuv420";
+    if (!ctx->tiles_on()) return vd_set_error(VD_ERR_STATE, "%s: tiling is off (vd_tiles)", who);
+    if (!ctx->plate.loaded) return vd_set_error(VD_ERR_STATE, "plate weights not loaded");
+    if (where != VD_HOST && where != VD_DEVICE) return vd_set_error(VD_ERR_ARG, "%s: bad where", who);
+    int rc = vd_yuv420_check(who, frames, n, fh, fw, true);
+    if (rc) return rc;
+    if ((rc = ctx->check_frames(n, fh, fw, (size_t)fw * 3))) return rc;   // n within max_batch
+    TileGrid g;
+    if ((rc = ctx->tiles_check(n, fh, fw, &g))) return rc;
+    Ctx::Nv12Dev d{};
+    if ((rc = ctx->nv12_in(vd_yuv420_dev(*frames), n, fh, fw, where, &d))) return rc;
+    const Nv12Scope scope(ctx, d, frames->matrix, frames->range);
+    if ((rc = vd_plate_forward(*ctx, d.base, n, fh, fw, d.pitch, false, &g))) return rc;
+    return plate_heads_out(ctx, n * (g.T - 1), out, anchors);
+}
+
 extern "C" int vdt_plate_postprocess(vd_ctx* h, const float* raw, int n, int fh, int fw, vd_boxes* plates) {
     Ctx* ctx = (Ctx*)h;
     if (!ctx) return vd_set_error(VD_ERR_ARG, "null context");

@@ -49,85 +49,151 @@ struct FrameRgb {
     }
     __device__ __forceinline__ static int row_bytes(int iw) { return (iw * 3 + 15) / 16 * 16; }   // a staged row
 };
-struct FrameNv12 {
+// The 4:2:0 sources come in two forms. Whole: the frame, whose first luma pixel sits on a chroma sample
+// (no parity fields, the arithmetic of a standalone frame). Rect: a rectangle of a frame at origin
+// (y0, x0) -- the luma pointer at (y0, x0), the chroma pointers at (y0 >> 1, x0 >> 1) of the FRAME, and
+// the origin's parities (py, px) = (y0 & 1, x0 & 1): local pixel (yy, x) takes chroma row (py + yy) >> 1
+// and chroma sample (px + x) >> 1 from there. A rectangle of a 4:2:0 frame is NOT a 4:2:0 frame.
+// (cy / cx: a local row / column as counted from the chroma sample the chroma pointers point at)
+struct Whole {
+    static constexpr bool rect = false;
+    __device__ __forceinline__ static int cy(int yy) { return yy; }
+    __device__ __forceinline__ static int cx(int x) { return x; }
+};
+struct Rect {
+    static constexpr bool rect = true; int py, px;
+    __device__ __forceinline__ int cy(int yy) const { return py + yy; }
+    __device__ __forceinline__ int cx(int x) const { return px + x; }
+};
+
+__device__ __host__ __forceinline__ constexpr int lb_up16(int b) { return (b + 15) / 16 * 16; }
+// chroma samples a staged row of iw pixels can need: ((px + iw + 1) >> 1) <= iw / 2 + 1 in a rectangle
+template <typename P> __device__ __host__ __forceinline__ constexpr int lb_csamples_max(int iw) { return P::rect ? iw / 2 + 1 : iw / 2; }
+
+template <typename P>
+struct FrameNv12T : P {
     const uint8_t* y; const uint8_t* uv; size_t pitch; Nv12Coef k;
     __device__ __forceinline__ void get(int yy, int x, int o[3]) const {
-        const uint8_t* q = uv + (size_t)(yy >> 1) * pitch + (x & ~1);
+        const uint8_t* q = uv + (size_t)(P::cy(yy) >> 1) * pitch + (P::cx(x) & ~1);
         vd_nv12_rgb(k, y[(size_t)yy * pitch + x], q[0], q[1], o);
     }
-    // a staged row: the luma row, then (16-B aligned) its chroma row
-    __device__ __forceinline__ static int row_bytes(int iw) { return 2 * ((iw + 15) / 16 * 16); }
+    // a staged row: the luma row, then (16-B aligned) its chroma row. Rect: the chroma row is
+    // 2 * ((px + iw + 1) >> 1) <= 2 * (iw / 2 + 1) bytes from the pair of the first pixel, so
+    // up16(iw) + up16(2 * (iw / 2 + 1)) <= 2 * iw + 32 bytes: within LB_LDS_MAX whenever
+    // iw * 3 <= LB_LDS_MAX (iw >= 32), and iw < 32 is 94 bytes at most.
+    __device__ __forceinline__ static int luma_bytes(int iw) { return lb_up16(iw); }
+    __device__ __forceinline__ static int row_bytes(int iw) {
+        if constexpr (P::rect) return lb_up16(iw) + lb_up16(2 * (iw / 2 + 1));
+        else return 2 * ((iw + 15) / 16 * 16);
+    }
 };
+using FrameNv12 = FrameNv12T<Whole>;
 struct RowRgb {
     const uint8_t* L;
     __device__ __forceinline__ void get(int x, int o[3]) const { o[0] = L[x * 3]; o[1] = L[x * 3 + 1]; o[2] = L[x * 3 + 2]; }
 };
-struct RowNv12 {
+template <typename P>
+struct RowNv12T : P {
     const uint8_t* L; int uvo; Nv12Coef k;
     __device__ __forceinline__ void get(int x, int o[3]) const {
-        const int c = uvo + (x & ~1);
+        const int c = uvo + (P::cx(x) & ~1);
         vd_nv12_rgb(k, L[x], L[c], L[c + 1], o);
     }
 };
+using RowNv12 = RowNv12T<Whole>;
 
 // Any 8-bit 4:2:0 layout (include/vdmi.h at vd_yuv420): a luma row, a U row and a V row, chroma
 // samples `step` bytes apart (1: planar I420 / YV12; 2: interleaved, where NV21 is simply the V
 // pointer one byte below the U pointer). The same conversion at the tap.
-struct FrameYuv {
+template <typename P>
+struct FrameYuvT : P {
     const uint8_t* y; const uint8_t* u; const uint8_t* v; size_t pitch, cpitch; int step; Nv12Coef k;
     __device__ __forceinline__ void get(int yy, int x, int o[3]) const {
-        const size_t c = (size_t)(yy >> 1) * cpitch + (size_t)(x >> 1) * step;
+        const size_t c = (size_t)(P::cy(yy) >> 1) * cpitch + (size_t)(P::cx(x) >> 1) * step;
         vd_nv12_rgb(k, y[(size_t)yy * pitch + x], u[c], v[c], o);
     }
-    // A staged row is three 16-B aligned segments: the luma row (iw bytes), then two of iw / 2 bytes
-    // rounded up -- planar: the U row and the V row; interleaved: both hold the pair row (iw bytes
-    // from the lower of the two pointers, which 2 * roundup16(iw / 2) >= roundup16(iw) has room for).
-    // At most 2 * iw + 45 bytes, within LB_LDS_MAX whenever iw * 3 <= LB_LDS_MAX (iw >= 46), and
-    // iw < 46 is 137 bytes at most.
+    // A staged row is three 16-B aligned segments: the luma row (iw bytes), then two of cs bytes
+    // rounded up, cs = iw / 2 chroma samples (Rect: iw / 2 + 1, the most that ((px + iw + 1) >> 1)
+    // can be) -- planar: the U row and the V row; interleaved: both hold the pair row (2 * samples
+    // bytes from the lower of the two pointers, which 2 * up16(cs) >= 2 * cs has room for).
+    // Whole: at most 2 * iw + 45 bytes, within LB_LDS_MAX whenever iw * 3 <= LB_LDS_MAX (iw >= 46),
+    // and iw < 46 is 137 bytes at most. Rect: up16(iw) + 2 * up16(iw / 2 + 1) <= 2 * iw + 47 bytes,
+    // within LB_LDS_MAX whenever iw * 3 <= LB_LDS_MAX (iw >= 47), and iw < 47 is 139 bytes at most.
     __device__ __forceinline__ static int luma_bytes(int iw) { return (iw + 15) / 16 * 16; }
-    __device__ __forceinline__ static int row_bytes(int iw) { return luma_bytes(iw) + 2 * ((iw / 2 + 15) / 16 * 16); }
+    __device__ __forceinline__ static int row_bytes(int iw) { return luma_bytes(iw) + 2 * ((lb_csamples_max<P>(iw) + 15) / 16 * 16); }
 };
-struct RowYuv {
+using FrameYuv = FrameYuvT<Whole>;
+template <typename P>
+struct RowYuvT : P {
     const uint8_t* L; int uo, vo, step; Nv12Coef k;
     __device__ __forceinline__ void get(int x, int o[3]) const {
-        const int c = (x >> 1) * step;
+        const int c = (P::cx(x) >> 1) * step;
         vd_nv12_rgb(k, L[x], L[uo + c], L[vo + c], o);
     }
 };
+using RowYuv = RowYuvT<Whole>;
 
 // 10- and 12-bit 4:2:0 (include/vdmi.h at vd_yuv420_16): FrameYuv over 16-bit words -- pitches and
 // offsets in bytes, `step` in samples. Detection sees D(S): the 8-bit sample (word >> sh) & 255 with
 // sh = shift + depth - 8, which also drops the unused bits. A staged row is reduced to those bytes on
 // its way into LDS, so the row slots and the tap code are FrameYuv's and RowYuv's.
-struct FrameYuv16 {
+template <typename P>
+struct FrameYuv16T : P {
     const uint8_t* y; const uint8_t* u; const uint8_t* v; size_t pitch, cpitch; int step, sh; Nv12Coef k;
     __device__ __forceinline__ static int s8(const uint8_t* p, int sh) { return (int)(((unsigned)*(const uint16_t*)p >> sh) & 255u); }
     __device__ __forceinline__ void get(int yy, int x, int o[3]) const {
-        const size_t c = (size_t)(yy >> 1) * cpitch + (size_t)(x >> 1) * step * 2;
+        const size_t c = (size_t)(P::cy(yy) >> 1) * cpitch + (size_t)(P::cx(x) >> 1) * step * 2;
         vd_nv12_rgb(k, s8(y + (size_t)yy * pitch + 2 * (size_t)x, sh), s8(u + c, sh), s8(v + c, sh), o);
     }
-    __device__ __forceinline__ static int row_bytes(int iw) { return FrameYuv::row_bytes(iw); }
+    __device__ __forceinline__ static int luma_bytes(int iw) { return FrameYuvT<P>::luma_bytes(iw); }
+    __device__ __forceinline__ static int row_bytes(int iw) { return FrameYuvT<P>::row_bytes(iw); }
 };
+using FrameYuv16 = FrameYuv16T<Whole>;
 
-template <int NV> struct SrcOf { using Frame = FrameRgb; using Row = RowRgb; };          // LetterboxArgs::nv.on
-template <> struct SrcOf<1> { using Frame = FrameNv12; using Row = RowNv12; };
-template <> struct SrcOf<2> { using Frame = FrameYuv; using Row = RowYuv; };
-template <> struct SrcOf<3> { using Frame = FrameYuv16; using Row = RowYuv; };
+// LetterboxArgs::nv.on, and whether the source is a rectangle of the frame (the tile letterbox)
+template <int NV, bool R = false> struct SrcOf { using Frame = FrameRgb; using Row = RowRgb; };
+template <> struct SrcOf<1, false> { using Frame = FrameNv12; using Row = RowNv12; };
+template <> struct SrcOf<2, false> { using Frame = FrameYuv; using Row = RowYuv; };
+template <> struct SrcOf<3, false> { using Frame = FrameYuv16; using Row = RowYuv; };
+template <> struct SrcOf<1, true> { using Frame = FrameNv12T<Rect>; using Row = RowNv12T<Rect>; };
+template <> struct SrcOf<2, true> { using Frame = FrameYuvT<Rect>; using Row = RowYuvT<Rect>; };
+template <> struct SrcOf<3, true> { using Frame = FrameYuv16T<Rect>; using Row = RowYuvT<Rect>; };
 
 // frame f of the batch
 template <int NV>
 __device__ __forceinline__ typename SrcOf<NV>::Frame lb_frame(const LetterboxArgs& a, int f) {
     if constexpr (NV == 3) {
         const uint8_t* b = a.src + (size_t)f * a.nv.frame_stride;
-        return FrameYuv16{b, b + a.nv.uv_offset, b + a.nv.v_offset, a.pitch, a.nv.cpitch, a.nv.step, a.nv.sh16, a.nv.k};
+        return FrameYuv16{{}, b, b + a.nv.uv_offset, b + a.nv.v_offset, a.pitch, a.nv.cpitch, a.nv.step, a.nv.sh16, a.nv.k};
     } else if constexpr (NV == 2) {
         const uint8_t* b = a.src + (size_t)f * a.nv.frame_stride;
-        return FrameYuv{b, b + a.nv.uv_offset, b + a.nv.v_offset, a.pitch, a.nv.cpitch, a.nv.step, a.nv.k};
+        return FrameYuv{{}, b, b + a.nv.uv_offset, b + a.nv.v_offset, a.pitch, a.nv.cpitch, a.nv.step, a.nv.k};
     } else if constexpr (NV == 1) {
         const uint8_t* b = a.src + (size_t)f * a.nv.frame_stride;
-        return FrameNv12{b, b + a.nv.uv_offset, a.pitch, a.nv.k};
+        return FrameNv12{{}, b, b + a.nv.uv_offset, a.pitch, a.nv.k};
     } else {
         return FrameRgb{a.src + (size_t)f * a.ih * a.pitch, a.pitch};
+    }
+}
+
+// The rectangle at (y0, x0) of 4:2:0 frame f of the batch (its extent a.ih x a.iw is not read here).
+// RGB needs no such form: a rectangle of a pitched frame is a pitched frame.
+template <int NV>
+__device__ __forceinline__ typename SrcOf<NV, true>::Frame lb_rect(const LetterboxArgs& a, int f, int y0, int x0) {
+    const uint8_t* b = a.src + (size_t)f * a.nv.frame_stride;
+    const Rect par{y0 & 1, x0 & 1};
+    const size_t cy = (size_t)(y0 >> 1), cx = (size_t)(x0 >> 1);
+    if constexpr (NV == 3) {
+        const size_t c = cy * a.nv.cpitch + cx * a.nv.step * 2;
+        return FrameYuv16T<Rect>{par, b + (size_t)y0 * a.pitch + 2 * (size_t)x0, b + a.nv.uv_offset + c, b + a.nv.v_offset + c,
+                                 a.pitch, a.nv.cpitch, a.nv.step, a.nv.sh16, a.nv.k};
+    } else if constexpr (NV == 2) {
+        const size_t c = cy * a.nv.cpitch + cx * a.nv.step;
+        return FrameYuvT<Rect>{par, b + (size_t)y0 * a.pitch + x0, b + a.nv.uv_offset + c, b + a.nv.v_offset + c, a.pitch,
+                               a.nv.cpitch, a.nv.step, a.nv.k};
+    } else {
+        static_assert(NV == 1, "4:2:0 sources only");
+        return FrameNv12T<Rect>{par, b + (size_t)y0 * a.pitch + x0, b + a.nv.uv_offset + cy * a.pitch + 2 * cx, a.pitch, a.nv.k};
     }
 }
 
@@ -137,11 +203,27 @@ __device__ __forceinline__ typename SrcOf<NV>::Row lb_row(const LetterboxArgs& a
     if constexpr (NV == 2 || NV == 3) {
         const int c0 = FrameYuv::luma_bytes(a.iw);
         if (a.nv.step == 2)   // the pair row from the lower pointer: the other channel is its next byte
-            return RowYuv{lrow + k * RS, c0 + (a.nv.uv_offset > a.nv.v_offset ? 1 : 0),
+            return RowYuv{{}, lrow + k * RS, c0 + (a.nv.uv_offset > a.nv.v_offset ? 1 : 0),
                           c0 + (a.nv.v_offset > a.nv.uv_offset ? 1 : 0), 2, a.nv.k};
-        return RowYuv{lrow + k * RS, c0, c0 + (RS - c0) / 2, 1, a.nv.k};
+        return RowYuv{{}, lrow + k * RS, c0, c0 + (RS - c0) / 2, 1, a.nv.k};
     } else if constexpr (NV == 1) {
-        return RowNv12{lrow + k * RS, RS / 2, a.nv.k};
+        return RowNv12{{}, lrow + k * RS, RS / 2, a.nv.k};
+    } else {
+        return RowRgb{lrow + k * RS};
+    }
+}
+// ... of a rectangle whose origin has x parity px (the staged chroma row is already the pixel row's)
+template <int NV>
+__device__ __forceinline__ typename SrcOf<NV, true>::Row lb_rect_row_at(const LetterboxArgs& a, const uint8_t* lrow, int k, int RS,
+                                                                        int px) {
+    if constexpr (NV == 2 || NV == 3) {
+        const int c0 = FrameYuv::luma_bytes(a.iw);
+        if (a.nv.step == 2)
+            return RowYuvT<Rect>{{0, px}, lrow + k * RS, c0 + (a.nv.uv_offset > a.nv.v_offset ? 1 : 0),
+                                 c0 + (a.nv.v_offset > a.nv.uv_offset ? 1 : 0), 2, a.nv.k};
+        return RowYuvT<Rect>{{0, px}, lrow + k * RS, c0, c0 + (RS - c0) / 2, 1, a.nv.k};
+    } else if constexpr (NV == 1) {
+        return RowNv12T<Rect>{{0, px}, lrow + k * RS, FrameNv12T<Rect>::luma_bytes(a.iw), a.nv.k};
     } else {
         return RowRgb{lrow + k * RS};
     }
@@ -317,19 +399,40 @@ __device__ __forceinline__ void lb_stage(uint8_t* dst, const uint8_t* src, int r
 __device__ __forceinline__ void lb_stage_row(const LetterboxArgs& a, const FrameRgb& img, int row, uint8_t* dst) {
     lb_stage(dst, img.p + (size_t)row * a.pitch, a.iw * 3);
 }
-__device__ __forceinline__ void lb_stage_row(const LetterboxArgs& a, const FrameNv12& img, int row, uint8_t* dst) {
+// A rectangle's source row `row` takes chroma row (py + row) >> 1 from the chroma pointer, and its iw
+// pixels (iw odd or even) the cs = (px + iw + 1) >> 1 samples from the one of its first pixel: the
+// last is sample (x0 + iw - 1) >> 1 of the frame, inside it because the rectangle is.
+template <typename P>
+__device__ __forceinline__ void lb_stage_row(const LetterboxArgs& a, const FrameNv12T<P>& img, int row, uint8_t* dst) {
     lb_stage(dst, img.y + (size_t)row * a.pitch, a.iw);
-    lb_stage(dst + FrameNv12::row_bytes(a.iw) / 2, img.uv + (size_t)(row >> 1) * a.pitch, a.iw);   // iw is even
+    if constexpr (P::rect)
+        lb_stage(dst + FrameNv12T<P>::luma_bytes(a.iw), img.uv + (size_t)((img.py + row) >> 1) * a.pitch,
+                 2 * ((img.px + a.iw + 1) >> 1));
+    else
+        lb_stage(dst + FrameNv12::row_bytes(a.iw) / 2, img.uv + (size_t)(row >> 1) * a.pitch, a.iw);   // iw is even
 }
-__device__ __forceinline__ void lb_stage_row(const LetterboxArgs& a, const FrameYuv& img, int row, uint8_t* dst) {
+template <typename P>
+__device__ __forceinline__ void lb_stage_row(const LetterboxArgs& a, const FrameYuvT<P>& img, int row, uint8_t* dst) {
     const int c0 = FrameYuv::luma_bytes(a.iw);
-    const size_t cr = (size_t)(row >> 1) * img.cpitch;
-    lb_stage(dst, img.y + (size_t)row * a.pitch, a.iw);
-    if (img.step == 2) {
-        lb_stage(dst + c0, (img.u < img.v ? img.u : img.v) + cr, a.iw);
+    if constexpr (P::rect) {
+        const size_t cr = (size_t)((img.py + row) >> 1) * img.cpitch;
+        const int cs = (img.px + a.iw + 1) >> 1;
+        lb_stage(dst, img.y + (size_t)row * a.pitch, a.iw);
+        if (img.step == 2) {
+            lb_stage(dst + c0, (img.u < img.v ? img.u : img.v) + cr, 2 * cs);
+        } else {
+            lb_stage(dst + c0, img.u + cr, cs);
+            lb_stage(dst + c0 + (FrameYuvT<P>::row_bytes(a.iw) - c0) / 2, img.v + cr, cs);
+        }
     } else {
-        lb_stage(dst + c0, img.u + cr, a.iw / 2);
-        lb_stage(dst + c0 + (FrameYuv::row_bytes(a.iw) - c0) / 2, img.v + cr, a.iw / 2);
+        const size_t cr = (size_t)(row >> 1) * img.cpitch;
+        lb_stage(dst, img.y + (size_t)row * a.pitch, a.iw);
+        if (img.step == 2) {
+            lb_stage(dst + c0, (img.u < img.v ? img.u : img.v) + cr, a.iw);
+        } else {
+            lb_stage(dst + c0, img.u + cr, a.iw / 2);   // iw is even
+            lb_stage(dst + c0 + (FrameYuv::row_bytes(a.iw) - c0) / 2, img.v + cr, a.iw / 2);
+        }
     }
 }
 
@@ -354,21 +457,34 @@ __device__ __forceinline__ void lb_stage16(uint8_t* dst, const uint8_t* src, int
         for (int i = threadIdx.x; i < n; i += 256) dst[i] = (uint8_t)FrameYuv16::s8(src + 2 * i, sh);
     }
 }
-__device__ __forceinline__ void lb_stage_row(const LetterboxArgs& a, const FrameYuv16& img, int row, uint8_t* dst) {
+template <typename P>
+__device__ __forceinline__ void lb_stage_row(const LetterboxArgs& a, const FrameYuv16T<P>& img, int row, uint8_t* dst) {
     const int c0 = FrameYuv::luma_bytes(a.iw);
-    const size_t cr = (size_t)(row >> 1) * img.cpitch;
-    lb_stage16(dst, img.y + (size_t)row * a.pitch, a.iw, img.sh);
-    if (img.step == 2) {
-        lb_stage16(dst + c0, (img.u < img.v ? img.u : img.v) + cr, a.iw, img.sh);
+    if constexpr (P::rect) {   // as above, in words
+        const size_t cr = (size_t)((img.py + row) >> 1) * img.cpitch;
+        const int cs = (img.px + a.iw + 1) >> 1;
+        lb_stage16(dst, img.y + (size_t)row * a.pitch, a.iw, img.sh);
+        if (img.step == 2) {
+            lb_stage16(dst + c0, (img.u < img.v ? img.u : img.v) + cr, 2 * cs, img.sh);
+        } else {
+            lb_stage16(dst + c0, img.u + cr, cs, img.sh);
+            lb_stage16(dst + c0 + (FrameYuvT<P>::row_bytes(a.iw) - c0) / 2, img.v + cr, cs, img.sh);
+        }
     } else {
-        lb_stage16(dst + c0, img.u + cr, a.iw / 2, img.sh);
-        lb_stage16(dst + c0 + (FrameYuv::row_bytes(a.iw) - c0) / 2, img.v + cr, a.iw / 2, img.sh);
+        const size_t cr = (size_t)(row >> 1) * img.cpitch;
+        lb_stage16(dst, img.y + (size_t)row * a.pitch, a.iw, img.sh);
+        if (img.step == 2) {
+            lb_stage16(dst + c0, (img.u < img.v ? img.u : img.v) + cr, a.iw, img.sh);
+        } else {
+            lb_stage16(dst + c0, img.u + cr, a.iw / 2, img.sh);
+            lb_stage16(dst + c0 + (FrameYuv::row_bytes(a.iw) - c0) / 2, img.v + cr, a.iw / 2, img.sh);
+        }
     }
 }
 
 // block row Y of canvas f from the frame at img; lrow: 4 staged rows of RS bytes
-template <int NV>
-__device__ __forceinline__ void lb_s2d_lds_row(const LetterboxArgs& a, const typename SrcOf<NV>::Frame& img, int f, int Y,
+template <int NV, bool R = false>
+__device__ __forceinline__ void lb_s2d_lds_row(const LetterboxArgs& a, const typename SrcOf<NV, R>::Frame& img, int f, int Y,
                                                uint8_t* lrow) {
     const int OW = a.ow / 2 + 1, OH = a.oh / 2 + 1;
     int rows[4];
@@ -376,7 +492,11 @@ __device__ __forceinline__ void lb_s2d_lds_row(const LetterboxArgs& a, const typ
     bool rin[2];
     lb_src_rows(a, 2 * Y - 1, &rows[0], &rows[1], &ty[0], &rin[0]);
     lb_src_rows(a, 2 * Y, &rows[2], &rows[3], &ty[1], &rin[1]);
-    const int RS = SrcOf<NV>::Frame::row_bytes(a.iw);
+    const int RS = SrcOf<NV, R>::Frame::row_bytes(a.iw);
+    auto row_at = [&](int k) {
+        if constexpr (R && NV != 0) return lb_rect_row_at<NV>(a, lrow, k, RS, img.px);
+        else return lb_row<NV>(a, lrow, k, RS);
+    };
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         if (rows[k] < 0) continue;
@@ -392,7 +512,7 @@ __device__ __forceinline__ void lb_s2d_lds_row(const LetterboxArgs& a, const typ
             float v[3] = {0.f, 0.f, 0.f};   // conv zero padding outside the canvas
             const int y = 2 * Y + h - 1;
             if ((unsigned)y < (unsigned)a.oh && (unsigned)x < (unsigned)a.ow)
-                lb_px_lds(a, lb_row<NV>(a, lrow, 2 * h, RS), lb_row<NV>(a, lrow, 2 * h + (rows[2 * h + 1] >= 0 ? 1 : 0), RS),
+                lb_px_lds(a, row_at(2 * h), row_at(2 * h + (rows[2 * h + 1] >= 0 ? 1 : 0)),
                           ty[h], x, rin[h], v);
             t[4 * s + 0] = v[0]; t[4 * s + 1] = v[1]; t[4 * s + 2] = v[2];
             t[4 * s + 3] = 0.f;
@@ -506,15 +626,19 @@ __global__ __launch_bounds__(256) void letterbox_kernel(LetterboxArgs a) {
 // Tiled detection (tiles.hip, include/vdmi.h at vd_tiles): the n * T canvases of n frames in one
 // launch, the net input on grid axis y. Input i = f * T + t is frame f's rectangle t -- the
 // whole frame (t = 0, geometry w) or a tile (geometry tl, all tiles one size) -- read in place
-// at the frame's pitch: a rectangle of a pitched frame IS a pitched frame, so each canvas goes
+// at the frame's pitch: a rectangle of a pitched RGB frame IS a pitched frame, so each canvas goes
 // through the very device functions of the three kernels above and is bit-identical to what
-// they write for a standalone frame holding those pixels. Grid axis x: the canvas's block rows
+// they write for a standalone frame holding those pixels. A rectangle of a 4:2:0 surface is read
+// through the Rect form of its source (the origin's parities, above): its canvas is bit-identical
+// to the RGB canvas of the same rectangle of the converted frame. Grid axis x: the canvas's block rows
 // (space-to-depth) or rows; a workgroup walks its row 256 pixels at a time, so the source rows
 // are read along the row (staged in LDS with 16-B loads where the row start is aligned).
 // (block) row Y of canvas i from the rectangle at img, in the canvas form a asks for
-__device__ __forceinline__ void lb_rect_row(const LetterboxArgs& a, const FrameRgb& img, int i, int Y, uint8_t* lrow) {
+template <int NV>
+__device__ __forceinline__ void lb_rect_row(const LetterboxArgs& a, const typename SrcOf<NV, true>::Frame& img, int i, int Y,
+                                            uint8_t* lrow) {
     if (a.s2d && a.iw * 3 <= LB_LDS_MAX) {
-        lb_s2d_lds_row<0>(a, img, i, Y, lrow);
+        lb_s2d_lds_row<NV, true>(a, img, i, Y, lrow);
     } else if (a.s2d) {
         for (int X = threadIdx.x; X < a.ow / 2 + 1; X += 256) lb_s2d_block(a, img, i, Y, X);
     } else {
@@ -522,23 +646,33 @@ __device__ __forceinline__ void lb_rect_row(const LetterboxArgs& a, const FrameR
     }
 }
 
+template <int NV>
 __global__ __launch_bounds__(256) void letterbox_tiles_kernel(LetterboxArgs w, LetterboxArgs tl, TileGrid g) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lrow[];
     const int i = blockIdx.y, f = i / g.T, t = i - f * g.T;
     const LetterboxArgs& a = t ? tl : w;
-    const FrameRgb img{w.src + ((size_t)f * w.ih + g.y0[t]) * w.pitch + (size_t)g.x0[t] * 3, w.pitch};
-    lb_rect_row(a, img, i, blockIdx.x, lrow);
+    if constexpr (NV == 0) {
+        const FrameRgb img{w.src + ((size_t)f * w.ih + g.y0[t]) * w.pitch + (size_t)g.x0[t] * 3, w.pitch};
+        lb_rect_row<0>(a, img, i, blockIdx.x, lrow);
+    } else {
+        lb_rect_row<NV>(a, lb_rect<NV>(w, f, g.y0[t], g.x0[t]), i, blockIdx.x, lrow);
+    }
 }
 
 // The tile-only form (tiled plate detection: the plate letterbox's canvas size follows the
 // rectangle's aspect, so the whole frame's canvas can differ from the tiles' and is written by
 // the plain kernels): canvas i = f * (T - 1) + (t - 1) is tile t >= 1 of frame f (fh rows).
+template <int NV>
 __global__ __launch_bounds__(256) void letterbox_tile_inputs_kernel(LetterboxArgs tl, TileGrid g, int fh) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lrow[];
     const int RC = g.T - 1;
     const int i = blockIdx.y, f = i / RC, t = 1 + i - f * RC;
-    const FrameRgb img{tl.src + ((size_t)f * fh + g.y0[t]) * tl.pitch + (size_t)g.x0[t] * 3, tl.pitch};
-    lb_rect_row(tl, img, i, blockIdx.x, lrow);
+    if constexpr (NV == 0) {
+        const FrameRgb img{tl.src + ((size_t)f * fh + g.y0[t]) * tl.pitch + (size_t)g.x0[t] * 3, tl.pitch};
+        lb_rect_row<0>(tl, img, i, blockIdx.x, lrow);
+    } else {
+        lb_rect_row<NV>(tl, lb_rect<NV>(tl, f, g.y0[t], g.x0[t]), i, blockIdx.x, lrow);
+    }
 }
 
 // NHWC max-pool (torch semantics: padded taps ignored), vectorised 16 B per thread.
@@ -600,8 +734,11 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const T* x, int xh, int
 // (nw, nh, filter) and even relative offsets of the pasted images.
 // bytes of one staged source row (RGB: the pixels; NV12: the luma row and its chroma row, 16-B aligned each);
 // at most LB_LDS_MAX whenever iw * 3 <= LB_LDS_MAX
-static size_t lb_row_bytes(const LetterboxArgs& a) {
-    if (a.nv.on == 2 || a.nv.on == 3) return (size_t)((a.iw + 15) / 16 * 16) + 2 * (size_t)((a.iw / 2 + 15) / 16 * 16);   // FrameYuv::row_bytes
+// (rect: a rectangle source of the tile letterbox, whose chroma segments hold iw / 2 + 1 samples)
+static size_t lb_row_bytes(const LetterboxArgs& a, bool rect = false) {
+    const int cs = rect ? a.iw / 2 + 1 : a.iw / 2;
+    if (a.nv.on == 2 || a.nv.on == 3) return (size_t)((a.iw + 15) / 16 * 16) + 2 * (size_t)((cs + 15) / 16 * 16);   // FrameYuvT::row_bytes
+    if (a.nv.on && rect) return (size_t)((a.iw + 15) / 16 * 16) + (size_t)((2 * cs + 15) / 16 * 16);               // FrameNv12T<Rect>::row_bytes
     return a.nv.on ? 2 * (size_t)((a.iw + 15) / 16 * 16) : (size_t)((a.iw * 3 + 15) / 16 * 16);
 }
 
@@ -707,10 +844,20 @@ hipError_t vd_launch_letterbox(const LetterboxArgs& a0, hipStream_t s) {
     return hipGetLastError();
 }
 
+// a 4:2:0 source of the tile letterbox: both geometries read the same surfaces, frames of even h x w
+static bool lb_tiles_src_ok(const LetterboxArgs& t, int fh, int fw) {
+    if (t.nv.on < 0 || t.nv.on > 3) return false;
+    if (!t.nv.on) return true;
+    if ((fh & 1) || (fw & 1) || t.pitch < (size_t)fw * (t.nv.on == 3 ? 2 : 1)) return false;
+    if (t.nv.on == 1) return true;
+    return (t.nv.step == 1 || t.nv.step == 2) && t.nv.cpitch >= (size_t)(fw / 2) * t.nv.step * (t.nv.on == 3 ? 2 : 1);
+}
+
 hipError_t vd_launch_letterbox_tiles(const LetterboxArgs& w0, const LetterboxArgs& t0, const TileGrid& g,
                                      hipStream_t s) {
     LetterboxArgs w = w0, t = t0;
-    if (w.nv.on || t.nv.on) return hipErrorInvalidValue;   // the tile letterbox reads packed RGB
+    if (w.nv.on != t.nv.on || !lb_tiles_src_ok(w, w.ih, w.iw)) return hipErrorInvalidValue;
+    if (w.nv.on && (w.src != t.src || w.pitch != t.pitch)) return hipErrorInvalidValue;
     if (g.T < 2 || g.T > VD_TILE_INPUTS_MAX || w.n <= 0 || w.s2d != t.s2d || w.oh != t.oh || w.ow != t.ow ||
         t.ih != g.th || t.iw != g.tw)
         return hipErrorInvalidValue;
@@ -720,7 +867,13 @@ hipError_t vd_launch_letterbox_tiles(const LetterboxArgs& w0, const LetterboxArg
     lb_set_gather(w);
     lb_set_gather(t);
     static const bool attr = [] {
-        (void)hipFuncSetAttribute((const void*)letterbox_tiles_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute((const void*)letterbox_tiles_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  4 * LB_LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)letterbox_tiles_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  4 * LB_LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)letterbox_tiles_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  4 * LB_LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)letterbox_tiles_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   4 * LB_LDS_MAX);
         return true;
     }();
@@ -728,30 +881,37 @@ hipError_t vd_launch_letterbox_tiles(const LetterboxArgs& w0, const LetterboxArg
     size_t lds = 0;
     if (w.s2d)
         for (const LetterboxArgs* a : {&w, &t})
-            if (a->iw * 3 <= LB_LDS_MAX) lds = std::max(lds, 4 * (size_t)((a->iw * 3 + 15) / 16 * 16));
+            if (a->iw * 3 <= LB_LDS_MAX) lds = std::max(lds, 4 * lb_row_bytes(*a, true));
     const dim3 grid(w.s2d ? w.oh / 2 + 1 : w.oh, w.n * g.T);
-    hipLaunchKernelGGL(letterbox_tiles_kernel, grid, dim3(256), lds, s, w, t, g);
+    LB_LAUNCH(letterbox_tiles_kernel, w.nv.on, grid, lds, s, w, t, g);
     return hipGetLastError();
 }
 
 hipError_t vd_launch_letterbox_tile_inputs(const LetterboxArgs& t0, const TileGrid& g, int n, int fh, int fw,
                                            hipStream_t s) {
     LetterboxArgs t = t0;
-    if (t.nv.on) return hipErrorInvalidValue;   // the tile letterbox reads packed RGB
-    if (g.T < 2 || g.T > VD_TILE_INPUTS_MAX || n <= 0 || t.ih != g.th || t.iw != g.tw || t.pitch < (size_t)fw * 3)
+    if (!lb_tiles_src_ok(t, fh, fw)) return hipErrorInvalidValue;
+    if (g.T < 2 || g.T > VD_TILE_INPUTS_MAX || n <= 0 || t.ih != g.th || t.iw != g.tw ||
+        (!t.nv.on && t.pitch < (size_t)fw * 3))
         return hipErrorInvalidValue;
     for (int k = 1; k < g.T; ++k)   // every tile inside the frame
         if (g.x0[k] < 0 || g.y0[k] < 0 || g.x0[k] + g.tw > fw || g.y0[k] + g.th > fh) return hipErrorInvalidValue;
     lb_set_gather(t);
     static const bool attr = [] {
-        (void)hipFuncSetAttribute((const void*)letterbox_tile_inputs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute((const void*)letterbox_tile_inputs_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  4 * LB_LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)letterbox_tile_inputs_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  4 * LB_LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)letterbox_tile_inputs_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  4 * LB_LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)letterbox_tile_inputs_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   4 * LB_LDS_MAX);
         return true;
     }();
     (void)attr;
-    const size_t lds = t.s2d && t.iw * 3 <= LB_LDS_MAX ? 4 * (size_t)((t.iw * 3 + 15) / 16 * 16) : 0;
+    const size_t lds = t.s2d && t.iw * 3 <= LB_LDS_MAX ? 4 * lb_row_bytes(t, true) : 0;
     const dim3 grid(t.s2d ? t.oh / 2 + 1 : t.oh, n * (g.T - 1));
-    hipLaunchKernelGGL(letterbox_tile_inputs_kernel, grid, dim3(256), lds, s, t, g, fh);
+    LB_LAUNCH(letterbox_tile_inputs_kernel, t.nv.on, grid, lds, s, t, g, fh);
     return hipGetLastError();
 }
 

@@ -607,8 +607,7 @@ static int process_420(Ctx* ctx, const char* who, bool nv_entry, const YuvIn& gi
         if ((rc = yuv_same_format(who, in, out))) return rc;
         if ((rc = nv12_blur_check(who, in, out, where, true, ctx->nv12_cfg_pass()))) return rc;
     }
-    if (((flags & VD_PROC_FACES) && ctx->faces_tiled()) || ((flags & VD_PROC_PLATES) && ctx->plates_tiled()))
-        return vd_set_error(VD_ERR_STATE, "%s: tiled detection (vd_tiles) reads RGB frames only", who);
+    if ((rc = ctx->tiles_surfaces_check(who, flags))) return rc;
     if (ctx->lead.J && (flags & VD_PROC_MOSAIC))
         return vd_set_error(VD_ERR_STATE, "%s: MOSAIC in a look-ahead context would skip the led boxes (use "
                             "vd_process_lead_nv12)", who);
@@ -817,8 +816,7 @@ int vd_process_lead_nv12(vd_ctx* h, const vd_nv12* in, const vd_nv12* out, int n
     if (ctx->nv12_cfg_pass() < 0)
         return vd_set_error(VD_ERR_STATE, "%s: the fixed-kernel Gaussian (blur_mode VD_BLUR_GAUSSIAN with cells off) has "
                             "no NV12 pass: set cells (vd_cells) for the scaled smooth blur", who);
-    if (n > 0 && (((flags & VD_PROC_FACES) && ctx->faces_tiled()) || ((flags & VD_PROC_PLATES) && ctx->plates_tiled())))
-        return vd_set_error(VD_ERR_STATE, "%s: tiled detection (vd_tiles) reads RGB frames only", who);
+    if (n > 0 && (rc = ctx->tiles_surfaces_check(who, flags))) return rc;
     if ((rc = ctx->lead_check(who, VD_LEAD_MODE_NV12, n, fh, fw, 0, flush))) return rc;
     const int m = ctx->lead.emit(n, flush);
     if (m > out_cap) return vd_set_error(VD_ERR_CAPACITY, "%s: %d frames to emit, out holds %d", who, m, out_cap);
@@ -878,8 +876,7 @@ static int process_lead_420(Ctx* ctx, const char* who, const YuvIn& gin, const Y
     if (ctx->nv12_cfg_pass() < 0)
         return vd_set_error(VD_ERR_STATE, "%s: the fixed-kernel Gaussian (blur_mode VD_BLUR_GAUSSIAN with cells off) has "
                             "no NV12 pass: set cells (vd_cells) for the scaled smooth blur", who);
-    if (n > 0 && (((flags & VD_PROC_FACES) && ctx->faces_tiled()) || ((flags & VD_PROC_PLATES) && ctx->plates_tiled())))
-        return vd_set_error(VD_ERR_STATE, "%s: tiled detection (vd_tiles) reads RGB frames only", who);
+    if (n > 0 && (rc = ctx->tiles_surfaces_check(who, flags))) return rc;
     // the words' format: the input's, or for a flush alone the output's (none given: nothing to compare)
     int depth = 0, shift = 0;
     if (words) {

@@ -114,6 +114,57 @@ int vdt_letterbox_yuv420_16(vd_ctx* h, const vd_yuv420_16* frames, int n, int fh
     return letterbox_readback(ctx, n, out, cpad);
 }
 
+// vdt_letterbox_tiles on surfaces: the tile letterbox of the product path with the surfaces' pixel source
+// (the switch vd_tiles_surfaces is not read, as no hook reads a blur setting)
+static int letterbox_tiles_420(Ctx* ctx, const char* who, const Yuv420Dev& frames, int matrix, int range, int n, int fh, int fw,
+                               int where, float* out, int cpad) {
+    if (!ctx->tiles_on()) return vd_set_error(VD_ERR_STATE, "%s: tiling is off (vd_tiles)", who);
+    int rc = ctx->check_frames(n, fh, fw, (size_t)fw * 3);   // n within max_batch
+    if (rc) return rc;
+    TileGrid g;
+    if ((rc = ctx->tiles_check(n, fh, fw, &g))) return rc;
+    Ctx::Nv12Dev d{};
+    if ((rc = ctx->nv12_in(frames, n, fh, fw, where, &d))) return rc;
+    const Nv12Scope scope(ctx, d, matrix, range);
+    if ((rc = ctx->face_letterbox_tiles(d.base, n, fh, fw, d.pitch, g))) return rc;
+    return letterbox_readback(ctx, n * g.T, out, cpad);
+}
+
+int vdt_letterbox_tiles_nv12(vd_ctx* h, const vd_nv12* frames, int n, int fh, int fw, int where, float* out, int cpad) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    const char* who = "vdt_letterbox_tiles_nv12";
+    if (!ctx->face.loaded) return vd_set_error(VD_ERR_STATE, "RetinaFace weights not loaded");
+    if (where != VD_HOST && where != VD_DEVICE) return vd_set_error(VD_ERR_ARG, "%s: bad where", who);
+    int rc = vd_nv12_check(who, frames, n, fh, fw, true);
+    if (rc) return rc;
+    return letterbox_tiles_420(ctx, who, vd_yuv420_dev(vd_yuv420_of_nv12(*frames)), frames->matrix, frames->range, n, fh, fw,
+                               where, out, cpad);
+}
+
+int vdt_letterbox_tiles_yuv420(vd_ctx* h, const vd_yuv420* frames, int n, int fh, int fw, int where, float* out, int cpad) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    const char* who = "vdt_letterbox_tiles_yuv420";
+    if (!ctx->face.loaded) return vd_set_error(VD_ERR_STATE, "RetinaFace weights not loaded");
+    if (where != VD_HOST && where != VD_DEVICE) return vd_set_error(VD_ERR_ARG, "%s: bad where", who);
+    int rc = vd_yuv420_check(who, frames, n, fh, fw, true);
+    if (rc) return rc;
+    return letterbox_tiles_420(ctx, who, vd_yuv420_dev(*frames), frames->matrix, frames->range, n, fh, fw, where, out, cpad);
+}
+
+int vdt_letterbox_tiles_yuv420_16(vd_ctx* h, const vd_yuv420_16* frames, int n, int fh, int fw, int where, float* out,
+                                  int cpad) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    const char* who = "vdt_letterbox_tiles_yuv420_16";
+    if (!ctx->face.loaded) return vd_set_error(VD_ERR_STATE, "RetinaFace weights not loaded");
+    if (where != VD_HOST && where != VD_DEVICE) return vd_set_error(VD_ERR_ARG, "%s: bad where", who);
+    int rc = vd_yuv420_16_check(who, frames, n, fh, fw, true);
+    if (rc) return rc;
+    return letterbox_tiles_420(ctx, who, vd_yuv420_dev(*frames), frames->matrix, frames->range, n, fh, fw, where, out, cpad);
+}
+
 // the first n face canvases as host f32 [n][H][W][cpad], whatever form the plan keeps them in
 static int letterbox_readback(Ctx* ctx, int n, float* out, int cpad) {
     const Act& in = ctx->face.input;

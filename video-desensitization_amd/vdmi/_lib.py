@@ -158,6 +158,7 @@ SIGNATURES = [
     ("vd_tiles_merge", _I, [_P, ctypes.POINTER(vd_boxes), _I, _I, _I, ctypes.POINTER(vd_boxes)]),
     ("vd_tiles_nets", _I, [_P, _I]),
     ("vd_tiles_merge_plates", _I, [_P, ctypes.POINTER(vd_boxes), _I, _I, _I, ctypes.POINTER(vd_boxes)]),
+    ("vd_tiles_surfaces", _I, [_P, _I]),
     ("vd_jpeg_decode", _I, [_P, ctypes.POINTER(_P), ctypes.POINTER(_SZ), _I, _P, _I, _I, _SZ, _I]),
     ("vd_jpeg_info", _I, [_P, _SZ, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     ("vd_jpeg_encode", _I, [_P, _P, _I, _I, _I, _SZ, _I, _I, _I, _P, _SZ, ctypes.POINTER(_SZ)]),
@@ -197,6 +198,9 @@ SIGNATURES = [
                             ctypes.POINTER(_D)]),
     ("vdt_letterbox", _I, [_P, _P, _I, _I, _I, _SZ, _I, _P, _I]),
     ("vdt_letterbox_tiles", _I, [_P, _P, _I, _I, _I, _SZ, _I, _P, _I]),
+    ("vdt_letterbox_tiles_nv12", _I, [_P, ctypes.POINTER(vd_nv12), _I, _I, _I, _I, _P, _I]),
+    ("vdt_letterbox_tiles_yuv420", _I, [_P, ctypes.POINTER(vd_yuv420), _I, _I, _I, _I, _P, _I]),
+    ("vdt_letterbox_tiles_yuv420_16", _I, [_P, ctypes.POINTER(vd_yuv420_16), _I, _I, _I, _I, _P, _I]),
     ("vdt_forward_heads", _I, [_P, _P, _I, _I, _I, _SZ, _I, _P, _P, _P]),
     ("vdt_face_band_rows", _I, [_I, _I, _I, _I, _P]),
     ("vdt_face_band_stats", _I, [_P, _P]),
@@ -207,6 +211,7 @@ SIGNATURES = [
     ("vdt_bottleneck", _I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     ("vdt_plate_raw", _I, [_P, _P, _I, _I, _I, _SZ, _I, _P, ctypes.POINTER(_I)]),
     ("vdt_plate_raw_tiles", _I, [_P, _P, _I, _I, _I, _SZ, _I, _P, ctypes.POINTER(_I)]),
+    ("vdt_plate_raw_tiles_yuv420", _I, [_P, ctypes.POINTER(vd_yuv420), _I, _I, _I, _I, _P, ctypes.POINTER(_I)]),
     ("vdt_plate_postprocess", _I, [_P, _P, _I, _I, _I, ctypes.POINTER(vd_boxes)]),
     ("vdt_jpeg_coefficients", _I, [_P, _SZ, _P, _SZ, ctypes.POINTER(_I)]),
     ("vdt_jdec_stats", _I, [_P, ctypes.POINTER(_I)]),
@@ -351,6 +356,14 @@ def check_tile_nets(tile_nets):
     if not isinstance(tile_nets, str) or tile_nets not in TILE_NETS:
         raise ValueError(f"tile_nets {tile_nets!r}: expected 'faces', 'plates' or 'both'")
     return tile_nets
+
+
+def check_tile_surfaces(on):
+    """tile_surfaces as a bool (vd_tiles_surfaces: whether the 4:2:0 surface entries run a tiled net);
+    ValueError for anything but a bool or 0 / 1."""
+    if isinstance(on, bool) or (isinstance(on, int) and on in (0, 1)):
+        return bool(on)
+    raise ValueError(f"tile_surfaces {on!r}: expected False or True")
 
 
 def tile_rects(h, w, tiles, tile_overlap=20):

@@ -383,7 +383,8 @@ class Context:
                  plate_max_det=300, plate_imgsz=640, microbatch=0, microbatch_stage=2, options=None,
                  blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30,
                  hold_motion=False, mask="rect", mask_grow=0, tiles=(1, 1), tile_overlap=20, cells=0,
-                 lead=0, lead_motion=False, rescue=0.0, plate_rescue=0.0, rescue_span=60, tile_nets="faces"):
+                 lead=0, lead_motion=False, rescue=0.0, plate_rescue=0.0, rescue_span=60, tile_nets="faces",
+                 tile_surfaces=False):
         """blur: what process() applies to the kept boxes: "pixelate" (the reference's
         INTER_NEAREST mosaic, the default) or "gaussian" (GaussianBlur(region, (blur_ksize,
         blur_ksize), blur_sigma) per clipped box, in list order; blur_ksize odd in [3, 127],
@@ -417,6 +418,12 @@ class Context:
         cost) or "both". A tiled plate net gives T lists per frame, merged per class at plate_iou;
         the calls that run it carry max_batch // T frames and split a longer batch. No effect
         while tiles == (1, 1). Kept as self.tile_nets; set_tile_nets() changes it.
+        tile_surfaces: whether the 4:2:0 surface calls (process_nv12 / process_yuv420 /
+        process_yuv420_16 and their process_lead_* forms) run the tiled nets (include/vdmi.h at
+        vd_tiles_surfaces). False (the default): they refuse a call that would run a tiled net, as
+        they always did. True: every list equals the RGB tiled call's on the converted frames, and a
+        long batch is split into consecutive calls of frames_per_call() frames as process() splits
+        it. Kept as self.tile_surfaces; set_tile_surfaces() changes it.
         cells: box-scaled strength (include/vdmi.h at vd_cells): with cells = N in 2..64 every box
         is hidden with at most N cells along its longer side instead of a constant number of
         pixels -- pixelation picks its level per box (never below mosaic_level), and a
@@ -446,6 +453,7 @@ class Context:
         mask, mask_grow = _lib.check_mask(mask, mask_grow)
         tiles, tile_overlap = _lib.check_tiles(tiles, tile_overlap)
         tile_nets = _lib.check_tile_nets(tile_nets)
+        tile_surfaces = _lib.check_tile_surfaces(tile_surfaces)
         cells = _lib.check_cells(cells)
         lead, lead_motion = _lib.check_lead(lead, lead_motion)
         rescue, plate_rescue, rescue_span = _lib.check_rescue(rescue, plate_rescue, rescue_span)
@@ -495,6 +503,9 @@ class Context:
         self.tile_nets = "faces"
         if tile_nets != "faces":
             self.set_tile_nets(tile_nets)
+        self.tile_surfaces = False
+        if tile_surfaces:
+            self.set_tile_surfaces(True)
         self.cells = 0
         if cells:
             self.set_cells(cells)
@@ -721,6 +732,92 @@ class Context:
             plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
         return out, faces, plates
 
+    # -- 4:2:0 surfaces: what the process_* calls of every descriptor family share -------
+    @staticmethod
+    def _from_frame(d, s0):
+        """The descriptor of frames s0, s0 + 1, ... of the batch d describes (None stays None)."""
+        if d is None or s0 == 0:
+            return d
+        e = type(d).from_buffer_copy(d)
+        e.base = d.base + s0 * d.frame_stride
+        return e
+
+    def _surface_step(self, flags):
+        """Frames one surface call carries: frames_per_call() where tile_surfaces lets it run a tiled net."""
+        return self._step(flags) if self.tile_surfaces else self.cfg.max_batch
+
+    def _process_420(self, fn, d, od, n, h, w, where, flags, faces, plates):
+        """fn = vd_process_nv12 / _yuv420 / _yuv420_16 on checked descriptors -> (faces, plates). A tiled
+        net: consecutive calls of frames_per_call() frames, as process() (exact under hold: the history
+        carries across calls)."""
+        step = self._surface_step(flags)
+        if n > step and step < self.cfg.max_batch:
+            pf, pp = [], []
+            for s0 in range(0, n, step):
+                k = min(step, n - s0)
+                f, q = self._process_420(fn, self._from_frame(d, s0), self._from_frame(od, s0), k, h, w, where, flags,
+                                         _rows(faces, s0, k), _rows(plates, s0, k))
+                pf.append(f)
+                pp.append(q)
+            if faces is None:
+                faces = _host_concat(pf)
+            if plates is None and flags & _lib.VD_PROC_PLATES:
+                plates = _host_concat(pp)
+            return faces, plates
+        fs = ps = None
+        auto_f, auto_p = faces is None, plates is None
+        if flags & _lib.VD_PROC_FACES:
+            faces = self._boxes(faces, n)
+            fs = faces.struct()
+        if flags & _lib.VD_PROC_PLATES:
+            plates = self._boxes(plates, n)
+            ps = plates.struct()
+        check(fn(self._h, ctypes.byref(d), ctypes.byref(od) if od is not None else None, n, h, w, where, flags,
+                 ctypes.byref(fs) if fs is not None else None, ctypes.byref(ps) if ps is not None else None))
+        if flags & _lib.VD_PROC_FACES:
+            faces = self._complete(faces, _lib.VD_NET_RETINAFACE, auto_f)
+        if flags & _lib.VD_PROC_PLATES:
+            plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
+        return faces, plates
+
+    def _lead_calls_420(self, fn, d, od, cap, n, h, w, where, flags, faces, plates, flush):
+        """fn = vd_process_lead_nv12 / _yuv420 / _yuv420_16 on checked descriptors (od: room for cap
+        surfaces, None when cap is 0) -> (m, faces, plates). A tiled net: consecutive calls as
+        _process_420's, what they emit written one after the other; only the last one flushes."""
+        step = self._surface_step(flags)
+        if n > step and step < self.cfg.max_batch:
+            pf, pp, m = [], [], 0
+            for s0 in range(0, n, step):
+                k = min(step, n - s0)
+                mk, f, q = self._lead_calls_420(fn, self._from_frame(d, s0), self._from_frame(od, m) if cap > m else None,
+                                                cap - m, k, h, w, where, flags, _rows(faces, s0, k), _rows(plates, s0, k),
+                                                flush and s0 + k == n)
+                m += mk
+                pf.append(f)
+                pp.append(q)
+            if faces is None:
+                faces = _host_concat(pf)
+            if plates is None and flags & _lib.VD_PROC_PLATES:
+                plates = _host_concat(pp)
+            return m, faces, plates
+        fs = ps = None
+        auto_f, auto_p = faces is None, plates is None
+        if flags & _lib.VD_PROC_FACES:
+            faces = self._boxes(faces, n)
+            fs = faces.struct()
+        if flags & _lib.VD_PROC_PLATES:
+            plates = self._boxes(plates, n)
+            ps = plates.struct()
+        m = ctypes.c_int(0)
+        check(fn(self._h, ctypes.byref(d), ctypes.byref(od) if od is not None else None, n, h, w, where, flags,
+                 ctypes.byref(fs) if fs is not None else None, ctypes.byref(ps) if ps is not None else None, cap,
+                 1 if flush else 0, ctypes.byref(m)))
+        if flags & _lib.VD_PROC_FACES:
+            faces = self._complete(faces, _lib.VD_NET_RETINAFACE, auto_f)
+        if flags & _lib.VD_PROC_PLATES:
+            plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
+        return m.value, faces, plates
+
     # -- NV12 frames ---------------------------------------------------------------
     @staticmethod
     def _nv12_out(frames, out, height):
@@ -741,7 +838,9 @@ class Context:
         layouts). Detections are exactly process()'s on nv12_to_rgb(frames); with VD_PROC_MOSAIC
         both planes of `out` (default: new surfaces like the input) are blurred as the context's
         settings ask: pixelation, or with blur="gaussian" and cells on the scaled smooth blur, under
-        the mask setting (blur="gaussian" with cells=0 has no NV12 pass). -> (out, faces, plates)."""
+        the mask setting (blur="gaussian" with cells=0 has no NV12 pass). In a tiling context the call
+        is refused unless tile_surfaces is on; then the lists are process()'s of the tiled context on
+        nv12_to_rgb(frames) and a long batch is split as process() splits it. -> (out, faces, plates)."""
         d, n, h, w, where, keep = _nv12_arg(frames, height, matrix, range)
         if flags is None:
             flags = _lib.VD_PROC_FACES | _lib.VD_PROC_MOSAIC
@@ -750,21 +849,8 @@ class Context:
             out, od, geo, okeep = self._nv12_out(frames, out, height)
             if geo != (n, h, w, where):
                 raise ValueError("out must hold NV12 frames of the input's n, h, w in the same memory (host / device)")
-        fs = ps = None
-        auto_f, auto_p = faces is None, plates is None
-        if flags & _lib.VD_PROC_FACES:
-            faces = self._boxes(faces, n)
-            fs = faces.struct()
-        if flags & _lib.VD_PROC_PLATES:
-            plates = self._boxes(plates, n)
-            ps = plates.struct()
-        check(self._lib.vd_process_nv12(self._h, ctypes.byref(d), ctypes.byref(od) if od is not None else None, n, h, w,
-                                        where, flags, ctypes.byref(fs) if fs is not None else None,
-                                        ctypes.byref(ps) if ps is not None else None))
-        if flags & _lib.VD_PROC_FACES:
-            faces = self._complete(faces, _lib.VD_NET_RETINAFACE, auto_f)
-        if flags & _lib.VD_PROC_PLATES:
-            plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
+        faces, plates = self._process_420(self._lib.vd_process_nv12, d, od, n, h, w, where, flags, faces, plates)
+        del keep
         return out, faces, plates
 
     def _nv12_blur(self, fn, frames, boxes_xyxy, counts, out, height, *tail):
@@ -846,21 +932,8 @@ class Context:
             out, od, geo, okeep = self._yuv420_out(frames, (n, h, w, where), out, out_layout or layout, height)
             if geo != (n, h, w, where):
                 raise ValueError("out must hold 4:2:0 frames of the input's n, h, w in the same memory (host / device)")
-        fs = ps = None
-        auto_f, auto_p = faces is None, plates is None
-        if flags & _lib.VD_PROC_FACES:
-            faces = self._boxes(faces, n)
-            fs = faces.struct()
-        if flags & _lib.VD_PROC_PLATES:
-            plates = self._boxes(plates, n)
-            ps = plates.struct()
-        check(self._lib.vd_process_yuv420(self._h, ctypes.byref(d), ctypes.byref(od) if od is not None else None, n, h, w,
-                                          where, flags, ctypes.byref(fs) if fs is not None else None,
-                                          ctypes.byref(ps) if ps is not None else None))
-        if flags & _lib.VD_PROC_FACES:
-            faces = self._complete(faces, _lib.VD_NET_RETINAFACE, auto_f)
-        if flags & _lib.VD_PROC_PLATES:
-            plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
+        faces, plates = self._process_420(self._lib.vd_process_yuv420, d, od, n, h, w, where, flags, faces, plates)
+        del keep
         return out, faces, plates
 
     def _yuv420_blur(self, fn, frames, boxes_xyxy, counts, out, layout, out_layout, height, *tail):
@@ -941,21 +1014,8 @@ class Context:
                                                       height)
             if geo != (n, h, w, where):
                 raise ValueError("out must hold 4:2:0 frames of the input's n, h, w in the same memory (host / device)")
-        fs = ps = None
-        auto_f, auto_p = faces is None, plates is None
-        if flags & _lib.VD_PROC_FACES:
-            faces = self._boxes(faces, n)
-            fs = faces.struct()
-        if flags & _lib.VD_PROC_PLATES:
-            plates = self._boxes(plates, n)
-            ps = plates.struct()
-        check(self._lib.vd_process_yuv420_16(self._h, ctypes.byref(d), ctypes.byref(od) if od is not None else None, n, h,
-                                             w, where, flags, ctypes.byref(fs) if fs is not None else None,
-                                             ctypes.byref(ps) if ps is not None else None))
-        if flags & _lib.VD_PROC_FACES:
-            faces = self._complete(faces, _lib.VD_NET_RETINAFACE, auto_f)
-        if flags & _lib.VD_PROC_PLATES:
-            plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
+        faces, plates = self._process_420(self._lib.vd_process_yuv420_16, d, od, n, h, w, where, flags, faces, plates)
+        del keep
         return out, faces, plates
 
     def _yuv420_16_blur(self, fn, frames, boxes_xyxy, counts, out, layout, out_layout, depth, shift, height, *tail):
@@ -1256,27 +1316,12 @@ class Context:
             od, cap, oh, ow, owhere, okeep = _nv12_arg(out, height, writable=True)
             if (oh, ow, owhere) != (h, w, where):
                 raise ValueError("out must hold NV12 frames of the input's h, w in the same memory (host / device)")
-        fs = ps = None
-        auto_f, auto_p = faces is None, plates is None
-        if flags & _lib.VD_PROC_FACES:
-            faces = self._boxes(faces, n)
-            fs = faces.struct()
-        if flags & _lib.VD_PROC_PLATES:
-            plates = self._boxes(plates, n)
-            ps = plates.struct()
-        m = ctypes.c_int(0)
-        check(self._lib.vd_process_lead_nv12(self._h, ctypes.byref(d), ctypes.byref(od) if od is not None else None, n,
-                                             h, w, where, flags, ctypes.byref(fs) if fs is not None else None,
-                                             ctypes.byref(ps) if ps is not None else None, len(out), 1 if flush else 0,
-                                             ctypes.byref(m)))
-        if flags & _lib.VD_PROC_FACES:
-            faces = self._complete(faces, _lib.VD_NET_RETINAFACE, auto_f)
-        if flags & _lib.VD_PROC_PLATES:
-            plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
+        m, faces, plates = self._lead_calls_420(self._lib.vd_process_lead_nv12, d, od, len(out), n, h, w, where, flags, faces,
+                                                plates, flush)
         self._lead_nv12 = (h, w, rows, where, dev)
         self._lead_yuv = None
         del keep
-        return out[:m.value], faces, plates
+        return out[:m], faces, plates
 
     def _lead_420(self, words, frames, out, faces, plates, flags, flush, layout, out_layout, depth, shift, matrix, range,
                   height):
@@ -1309,26 +1354,11 @@ class Context:
                 od, cap, oh, ow, owhere, okeep = _yuv420_arg(out, olay, oheight, writable=True)
             if (oh, ow, owhere) != (h, w, where):
                 raise ValueError("out must hold 4:2:0 frames of the input's h, w in the same memory (host / device)")
-        fs = ps = None
-        auto_f, auto_p = faces is None, plates is None
-        if flags & _lib.VD_PROC_FACES:
-            faces = self._boxes(faces, n)
-            fs = faces.struct()
-        if flags & _lib.VD_PROC_PLATES:
-            plates = self._boxes(plates, n)
-            ps = plates.struct()
-        m = ctypes.c_int(0)
-        check(fn(self._h, ctypes.byref(d), ctypes.byref(od) if od is not None else None, n, h, w, where, flags,
-                 ctypes.byref(fs) if fs is not None else None, ctypes.byref(ps) if ps is not None else None, cap,
-                 1 if flush else 0, ctypes.byref(m)))
-        if flags & _lib.VD_PROC_FACES:
-            faces = self._complete(faces, _lib.VD_NET_RETINAFACE, auto_f)
-        if flags & _lib.VD_PROC_PLATES:
-            plates = self._complete(plates, _lib.VD_NET_YOLOV8N, auto_p)
+        m, faces, plates = self._lead_calls_420(fn, d, od, cap, n, h, w, where, flags, faces, plates, flush)
         self._lead_yuv = (words, h, w, dev, olay, fmt)
         self._lead_nv12 = None
         del keep
-        return (out if isinstance(out, (Yuv420, Yuv420_16)) else out[:m.value]), faces, plates
+        return (out if isinstance(out, (Yuv420, Yuv420_16)) else out[:m]), faces, plates
 
     def process_lead_yuv420(self, frames, out=None, faces=None, plates=None, flags=None, flush=False, layout="i420",
                             out_layout=None, matrix="bt709", range="limited", height=None):
@@ -1484,6 +1514,12 @@ class Context:
         check(self._lib.vd_tiles_nets(self._h, _lib.TILE_NETS[tile_nets]))
         self.tile_nets = tile_nets
 
+    def set_tile_surfaces(self, on=True):
+        """vd_tiles_surfaces: whether the 4:2:0 surface calls run the tiled nets (1) or refuse a call
+        that would (0, the default). Keeps the hold history; VdError while lead frames are pending."""
+        check(self._lib.vd_tiles_surfaces(self._h, int(on)))
+        self.tile_surfaces = bool(on)
+
     def tile_rects(self, h, w):
         """The net inputs' rectangles (x, y, w, h) of an h x w frame under the context's tiling
         (vd_tile_rects): int32 [T][4], row 0 the whole frame."""
@@ -1517,6 +1553,29 @@ class Context:
             return out
         check(self._lib.vd_tiles_merge_plates(self._h, ctypes.byref(ls), n, int(h), int(w), None))
         return self.read_boxes(_lib.VD_NET_YOLOV8N, n)
+
+    def _letterbox_tiles_420(self, fn, d, n, h, w, where, cpad):
+        T = 1 + self.tiles[0] * self.tiles[1]
+        out = np.zeros((n * T, self.cfg.input_h, self.cfg.input_w, cpad), np.float32)
+        check(fn(self._h, ctypes.byref(d), n, h, w, where, ptr(out), cpad))
+        return out
+
+    def letterbox_tiles_nv12(self, frames, cpad=4, matrix="bt709", range="limited", height=None):
+        """vdt_letterbox_tiles_nv12: letterbox_tiles() of NV12 frames by the tile letterbox kernel with the
+        NV12 pixel source (what the *_nv12 entries run); tile_surfaces is not read."""
+        d, n, h, w, where, keep = _nv12_arg(frames, height, matrix, range)
+        return self._letterbox_tiles_420(self._lib.vdt_letterbox_tiles_nv12, d, n, h, w, where, cpad)
+
+    def letterbox_tiles_yuv420(self, frames, cpad=4, layout="i420", matrix="bt709", range="limited", height=None):
+        """vdt_letterbox_tiles_yuv420: letterbox_tiles() of 4:2:0 frames in any layout."""
+        d, n, h, w, where, keep = _yuv420_arg(frames, layout, height, matrix, range)
+        return self._letterbox_tiles_420(self._lib.vdt_letterbox_tiles_yuv420, d, n, h, w, where, cpad)
+
+    def letterbox_tiles_yuv420_16(self, frames, cpad=4, layout="i420", depth=10, shift=None, matrix="bt709",
+                                  range="limited", height=None):
+        """vdt_letterbox_tiles_yuv420_16: letterbox_tiles() of 10- / 12-bit 4:2:0 frames."""
+        d, n, h, w, where, keep = _yuv420_16_arg(frames, layout, depth, shift, height, matrix, range)
+        return self._letterbox_tiles_420(self._lib.vdt_letterbox_tiles_yuv420_16, d, n, h, w, where, cpad)
 
     def letterbox_tiles(self, frames, cpad=4):
         """vdt_letterbox_tiles: letterbox() for the n * T canvases of a tiling context, canvas
@@ -1663,6 +1722,18 @@ class Context:
         check(self._lib.vdt_plate_raw_tiles(self._h, p, n, h, w, pitch, where, None, ctypes.byref(A)))
         out = np.zeros((ni, 64 + self.cfg.plate_nc, A.value), np.float32)
         check(self._lib.vdt_plate_raw_tiles(self._h, p, n, h, w, pitch, where, ptr(out), ctypes.byref(A)))
+        return out
+
+    def plate_raw_tiles_yuv420(self, frames, layout="i420", matrix="bt709", range="limited", height=None):
+        """vdt_plate_raw_tiles_yuv420: plate_raw_tiles() of 4:2:0 frames in any layout, by the tile-only
+        letterbox kernel with the surfaces' pixel source; tile_surfaces is not read."""
+        d, n, h, w, where, keep = _yuv420_arg(frames, layout, height, matrix, range)
+        ni = n * self.tiles[0] * self.tiles[1]
+        A = ctypes.c_int(0)
+        check(self._lib.vdt_plate_raw_tiles_yuv420(self._h, ctypes.byref(d), n, h, w, where, None, ctypes.byref(A)))
+        out = np.zeros((ni, 64 + self.cfg.plate_nc, A.value), np.float32)
+        check(self._lib.vdt_plate_raw_tiles_yuv420(self._h, ctypes.byref(d), n, h, w, where, ptr(out), ctypes.byref(A)))
+        del keep
         return out
 
     def plate_postprocess(self, raw, img_hw, cap=None):
