@@ -440,7 +440,8 @@ int vd_read_lead(vd_ctx* ctx, int n, int which, vd_boxes* out);   /* which 0: A_
  *
  * vd_rescue: the setting. VD_ERR_ARG: a low that is NaN, < 0 or >= that net's threshold
  * (cfg.confidence, cfg.plate_conf), S out of range. VD_ERR_STATE: a change while lead frames are
- * pending; rescue on while tiling is on (and vd_tiles in a rescue context). Each is checked before
+ * pending; rescue on while tiling is on (and vd_tiles in a rescue context) unless vd_rescue_tiles
+ * (below) has been turned on. Each is checked before
  * any state changes. A change forgets the rescue history and the hold history as vd_hold_reset
  * does (which clears the rescue history too); setting the value the context has changes nothing.
  *
@@ -459,6 +460,42 @@ int vd_read_lead(vd_ctx* ctx, int n, int which, vd_boxes* out);   /* which 0: A_
 int vd_rescue(vd_ctx* ctx, float face_low, float plate_low, int span);
 int vd_rescue_lists(vd_ctx* ctx, const vd_boxes* strong, const vd_boxes* weak, int n, int h, int w, vd_boxes* out);
 int vd_read_rescue(vd_ctx* ctx, int net, int n, int which, vd_boxes* out);   /* which 0: R_t, 1: W_t */
+
+/* ---- rescue on tiled nets ------------------------------------------------------------
+ * Tiling finds the 40-px face of a 4K frame, rescue keeps it hidden while its score sags: with on = 1
+ * a context takes both settings. Nothing new is defined. For a tiled net (vd_tiles, vd_tiles_nets)
+ * whose low is > 0 the T per-input keep lists are the lists at low (above), and the cross-tile merge
+ * runs over the whole of them, unchanged: map, key (~score bits, t * icap + pos), the greedy sweep at
+ * nms_iou (plates: per class at plate_iou), emit. The split is exact:
+ *   - strong boxes score >= confidence (plates > plate_conf), weak ones below, so in the merged order
+ *     every strong box precedes every weak box;
+ *   - each per-input list at low has that input's list at the threshold as its prefix (max_det
+ *     included), so a strong box has the position, and the key, it has with rescue off;
+ *   - whether the sweep keeps a box depends on the boxes before it only.
+ * So the merged list at low, cut where the score stops passing the net's threshold, is bit for bit
+ * the merged list with rescue off (count, xyxy, xyxy_f, score, label).
+ *   D_t      of a tiled net: that strong prefix. The caller's arrays, vd_read_boxes, totals and
+ *            records stay D_t.
+ *   W_t      the rest of the merged list, in merge order (label t*A + anchor for faces, the class for
+ *            plates); vd_read_rescue reads the merged rows for a tiled net.
+ *   From there the rescue definition applies unchanged: wherever it says keep list, the merged rows
+ *   stand for a tiled net; an untiled net keeps its own (vd_tiles_nets VD_TILE_PLATES: the faces of
+ *   the whole-frame net beside the merged plates, and the reverse). E_t = D_t ++ R_t feeds hold,
+ *   lead, mask, cells and the blur as it does untiled, on RGB frames and (vd_tiles_surfaces) surfaces.
+ * Opt-in, because vd_rescue in a tiling context and vd_tiles in a rescue context were promised a
+ * refusal, and at low every one of the T inputs sorts and sweeps several times the candidates: on = 0
+ * (the default) keeps both refusals, code and message. on outside {0, 1}: VD_ERR_ARG. Setting the
+ * value the context has changes nothing. VD_ERR_STATE while lead frames are pending, and for on = 0
+ * while rescue and tiling are both on (turn one off first; nothing changes). Otherwise it sets a flag
+ * and keeps every history. With on = 1 a vd_tiles / vd_tiles_nets call that changes the tiling of a
+ * rescue context forgets the rescue history with the hold history (the rows change capacity: a new
+ * stream); vd_rescue forgets as it always does. Memory: the E rows take n * ecap * 20 B with ecap the
+ * sum over the nets of (T or 1) * the keep capacity, n <= max_batch / T; the two history buffers take
+ * W * ecap * 20 B each. Nothing is allocated while rescue or the switch is off.
+ * vd_tiles_merge / vd_tiles_merge_plates on caller lists never split: their output is in descending
+ * score order, so a caller with their own detector merges the lists at their low threshold, cuts at
+ * their own threshold and hands both parts to vd_rescue_lists. */
+int vd_rescue_tiles(vd_ctx* ctx, int on);
 
 /* ---- mask shaping: grow the blurred boxes by a margin, blur ellipses -------------
  * A context has a mask setting (shape, g). The default (VD_MASK_RECT, 0) blurs the boxes as
@@ -611,7 +648,8 @@ int vd_cell_level(int W, int H, int level, int cells);
 int vd_tile_rects(int h, int w, int rows, int cols, int overlap_pct, int32_t* xywh, int* count);
 /* The context's tiling setting. Bad values: VD_ERR_ARG, setting unchanged. Takes effect from the
  * next call; a change forgets the hold history as vd_hold_reset does (the merged rows change
- * capacity); setting the value the context already has changes nothing. */
+ * capacity); setting the value the context already has changes nothing. In a rescue context:
+ * VD_ERR_STATE unless vd_rescue_tiles is on, and then the rescue history is forgotten too. */
 int vd_tiles(vd_ctx* ctx, int rows, int cols, int overlap_pct);
 /* The merge step alone on caller lists, by the kernel of the detect path. lists: n*T rows, frame
  * f's input t at row f*T+t, boxes relative to their rectangle of an h x w frame; xyxy_f and score
@@ -657,8 +695,9 @@ int vd_tiles_merge(vd_ctx* ctx, const vd_boxes* lists, int n, int h, int w, vd_b
  * the plate detections of the call: the caller's `plates` (vd_boxes contract, unchanged),
  * vd_read_boxes(VD_NET_YOLOV8N), the plate part of D_t for hold, lead and the blur list under
  * VD_PROC_MOSAIC_PLATES. Capacity: a call that runs a tiled net needs n*T <= cfg.max_batch
- * (VD_ERR_ARG, the message names the largest n), whichever net is tiled. Rescue with tiling on stays
- * refused for any nets value, and a 4:2:0 surface call (the *_nv12, *_yuv420 and *_yuv420_16 entries)
+ * (VD_ERR_ARG, the message names the largest n), whichever net is tiled. Rescue with tiling is
+ * refused for any nets value unless vd_rescue_tiles (above) is on, and a 4:2:0 surface call (the *_nv12,
+ * *_yuv420 and *_yuv420_16 entries)
  * that would run a tiled net is VD_ERR_STATE unless vd_tiles_surfaces (below) has been turned on. */
 #define VD_TILE_FACES 1
 #define VD_TILE_PLATES 2
@@ -692,7 +731,8 @@ int vd_tiles_merge_plates(vd_ctx* ctx, const vd_boxes* lists, int n, int h, int 
  * with a message that names vd_tiles_surfaces. on outside {0, 1} is VD_ERR_ARG; VD_ERR_STATE while
  * lead frames are pending; setting the value the context already has changes nothing. The hold
  * history is kept (the merged rows' capacities depend on vd_tiles / vd_tiles_nets only). Rescue with
- * tiling, the fixed 31-tap Gaussian on surfaces, 4:2:2 / 4:4:4 and depth conversion stay refused. */
+ * tiling is refused unless vd_rescue_tiles is on (then it runs on surfaces as on RGB frames); the fixed
+ * 31-tap Gaussian on surfaces, 4:2:2 / 4:4:4 and depth conversion stay refused. */
 int vd_tiles_surfaces(vd_ctx* ctx, int on);
 
 /* ---- NV12 frames: detect and blur video surfaces directly -------------------------
@@ -878,8 +918,8 @@ int vd_nv12_to_rgb(const vd_nv12* in, int n, int h, int w, uint8_t* rgb, size_t 
  * vd_process_nv12: a VD_BLUR_GAUSSIAN context with cells off; a call that would run a tiled net while
  * vd_tiles_surfaces is off;
  * VD_PROC_MOSAIC in a look-ahead context (the look-ahead call is vd_process_lead_yuv420, below). Not in
- * this version: rescue with tiling and the fixed Gaussian on surfaces (both refused), 4:2:2 and 4:4:4. 10- and
- * 12-bit surfaces (P010, yuv420p10le) have a descriptor of their own: vd_yuv420_16, below. */
+ * this version: rescue with tiling and the fixed Gaussian on surfaces (refused: the first unless
+ * vd_rescue_tiles is on, the second always), 4:2:2 and 4:4:4. 10- and 12-bit surfaces (P010, yuv420p10le) have a descriptor of their own: vd_yuv420_16, below. */
 typedef struct vd_yuv420 {
     uint8_t* base;        /* first luma byte of frame 0 */
     size_t   pitch;       /* luma row pitch, bytes */
@@ -968,8 +1008,8 @@ int vd_yuv420_to_rgb(const vd_yuv420* in, int n, int h, int w, uint8_t* rgb, siz
  * VD_ERR_STATE with the messages of vd_process_yuv420: a VD_BLUR_GAUSSIAN context with cells off; a
  * call that would run a tiled net while vd_tiles_surfaces is off; VD_PROC_MOSAIC in a look-ahead
  * context (the look-ahead call is vd_process_lead_yuv420_16, below). Not in this version: rescue with
- * tiling and the fixed Gaussian on surfaces (both refused), depth or shift conversion between in and
- * out, 16-bit-deep samples, 4:2:2 and 4:4:4. */
+ * tiling and the fixed Gaussian on surfaces (refused: the first unless vd_rescue_tiles is on, the second
+ * always), depth or shift conversion between in and out, 16-bit-deep samples, 4:2:2 and 4:4:4. */
 typedef struct vd_yuv420_16 {
     uint8_t* base;        /* first luma word of frame 0 (2-byte aligned) */
     size_t   pitch;       /* luma row pitch, bytes (even, >= 2*w) */
@@ -1138,6 +1178,14 @@ int vdt_plate_raw_tiles(vd_ctx* ctx, const uint8_t* frames, int n, int h, int w,
  * the surfaces' pixel source; the switch vd_tiles_surfaces is not read. */
 int vdt_plate_raw_tiles_yuv420(vd_ctx* ctx, const vd_yuv420* frames, int n, int h, int w, int where, float* out,
                                int* anchors);
+/* The cross-tile merge in its rescue form alone (vd_rescue_tiles), by the kernel of the detect path:
+ * vd_tiles_merge's (plates != 0: vd_tiles_merge_plates') layout, staging, capacity and state rules on
+ * caller lists read as the lists at low, cut at thr (faces score >= thr, plates score > thr). Neither
+ * the rescue setting nor the switch is read. out_strong (may be NULL): the strong prefix under the
+ * vd_boxes contract, exactly what the merge hands the caller in a rescue context. out_all (may be NULL):
+ * the whole merged rows, count = the whole merged count, arrays cut at cap. */
+int vdt_tiles_merge_low(vd_ctx* ctx, const vd_boxes* lists, int n, int h, int w, int plates, float thr,
+                        vd_boxes* out_strong, vd_boxes* out_all);
 /* Plate post-processing only (score, threshold, DFL decode, NMS, scale_boxes) on caller-provided raw
  * heads in vdt_plate_raw's layout, host f32 [n][64 + nc][A], for n frames of h x w whose canvas the
  * context's last plate forward (vdt_plate_raw, vd_detect_plates, vd_process) was run for; honours the

@@ -17,6 +17,15 @@ and the mosaic behind it blurs more boxes. The seeded weights fire all over the 
 box of the frame before by 30 % and is rescued -- the heavy case: the blur list grows from 30 to
 110 boxes per frame, mostly overlapping ones, which takes the mosaic off its fast path (at most 32
 boxes per band). A video rescues a box only where a track goes on.
+
+    python tools/rescuebench.py --tiles --parent-lib PATH/libvdmi.so [--json profiles/rescue_tiles_4k.json]
+
+--tiles: rescue on tiled nets (vd_rescue_tiles) at 3840 x 2160: tiles (2, 2, 20), a max_batch = 20 context,
+4-frame steps, faces | plates | mosaic. The three kinds are the parent build tiled without rescue, this build
+with the switch off (the same calls), and this build with rescue_tiles on at rescue=0.2. Besides the step time:
+the family-3 sum (post + merge + rescue), the mosaic's share of the step's event-timed sums, and how many
+frames' merged lists alone pass the 2048 boxes the merge sorts in LDS (a lower bound of the frames whose
+merge spilled to global scratch: the merge's input is never smaller than its output).
 """
 import argparse
 import json
@@ -30,6 +39,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "video-desensitization_amd"))
 
 RESCUE_ENTRIES = ("vd_rescue", "vd_rescue_lists", "vd_read_rescue", "vdt_plate_postprocess")
+TILES_ENTRIES = ("vd_rescue_tiles", "vdt_tiles_merge_low")      # what a parent of the --tiles mode lacks
+LDS_CAND = 2048        # csrc/vd_nms.h VD_NMS_LDS_CAND
 KINDS = ("parent", "off", "on")
 
 
@@ -38,15 +49,20 @@ def one(a):
     import torch
     from vdmi import _lib
     if a.one == "parent":    # the parent's build does not export the rescue entry points
-        _lib.SIGNATURES = [s for s in _lib.SIGNATURES if s[0] not in RESCUE_ENTRIES]
+        gone = TILES_ENTRIES if a.tiles else RESCUE_ENTRIES + TILES_ENTRIES
+        _lib.SIGNATURES = [s for s in _lib.SIGNATURES if s[0] not in gone]
     import vdmi
     from vdmi import synth, weights
-    B, H, W = a.batch, 1080, 1920
+    B, H, W = (4, 2160, 3840) if a.tiles else (a.batch, 1080, 1920)
     dev = torch.device("cuda:0")
     frames = torch.from_numpy(synth.frames(B, H, W, seed=0)).to(dev)
     flags = _lib.VD_PROC_FACES | _lib.VD_PROC_PLATES | _lib.VD_PROC_MOSAIC
     kw = {"rescue": a.rescue, "rescue_span": a.span} if a.one == "on" else {}
-    ctx = vdmi.Context(device=0, precision="fp32", max_batch=B, **kw)
+    if a.tiles:
+        kw.update(tiles=(2, 2), tile_overlap=20)
+        if a.one == "on":
+            kw["rescue_tiles"] = True
+    ctx = vdmi.Context(device=0, precision="fp32", max_batch=20 if a.tiles else B, **kw)
     ctx.load_weights(_lib.VD_NET_RETINAFACE, weights.retinaface_state_dict(0))
     ctx.load_weights(_lib.VD_NET_YOLOV8N, weights.yolov8n_state_dict(0))
     faces, plates = vdmi.DeviceBoxes(B, 256, dev), vdmi.DeviceBoxes(B, 256, dev)
@@ -68,6 +84,12 @@ def one(a):
     if a.one == "on":
         r["weak_per_frame"] = float(ctx.read_rescue(0, B, "weak", cap=1).count.mean())
         r["rescued_per_frame"] = float(ctx.read_rescue(0, B, "rescued", cap=1).count.mean())
+    if a.tiles:              # the merged face lists of the last step: strong, and with rescue the weak tail
+        merged = ctx.read_boxes(_lib.VD_NET_RETINAFACE, B, cap=1).count.astype("int64")
+        if a.one == "on":
+            merged = merged + ctx.read_rescue(0, B, "weak", cap=1).count
+        r["merged_per_frame"] = float(merged.mean())
+        r["frames_past_lds"] = int((merged > LDS_CAND).sum())
     ctx.timing(True)         # events around every launch slow the step: steps of their own
     ctx.timing_reset()
     for _ in range(a.post_steps):
@@ -78,6 +100,7 @@ def one(a):
     # every family's event-timed sum (conv, mosaic, letterbox, post, other, plate conv, mosaic cells): where
     # the rest of a difference lies (the families overlap on their streams, so the sums exceed the step)
     r["family_ms_per_step"] = [round(ctx.timing_read(f)[0] / a.post_steps, 4) for f in range(7)]
+    r["mosaic_share"] = round(r["family_ms_per_step"][1] / max(sum(r["family_ms_per_step"]), 1e-9), 4)
     ctx.timing(False)
     ctx.close()
     print("RESCUEBENCH " + json.dumps(r), flush=True)
@@ -91,7 +114,7 @@ def child(a, which):
         env.pop("VDMI_LIB", None)
     cmd = [sys.executable, os.path.abspath(__file__), "--one", which, "--steps", str(a.steps), "--warmup",
            str(a.warmup), "--batch", str(a.batch), "--rescue", str(a.rescue), "--span", str(a.span),
-           "--post-steps", str(a.post_steps)]
+           "--post-steps", str(a.post_steps)] + (["--tiles"] if a.tiles else [])
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=a.child_timeout)
     if p.returncode != 0:
         raise RuntimeError(f"{which} run failed ({p.returncode}):\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
@@ -112,6 +135,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--post-steps", type=int, default=5, help="event-timed steps behind the family figures")
     ap.add_argument("--child-timeout", type=int, default=240)
+    ap.add_argument("--tiles", action="store_true", help="rescue on tiled nets at 3840 x 2160 (see above)")
     ap.add_argument("--one", choices=KINDS, help="(internal) one measurement in this process")
     ap.add_argument("--json", help="also write the result line to this file")
     a = ap.parse_args()
@@ -127,10 +151,11 @@ def main():
     post = {k: [r["post_ms_per_step"] for r in runs[k]] for k in KINDS}
     mean = lambda v: round(sum(v) / len(v), 4)
     res = {"what": f"weak-detection rescue: process with rescue off / rescue={a.rescue} (span {a.span}) vs the "
-                   "parent commit's build",
+                   "parent commit's build" + (", tiles (2, 2, 20), max_batch 20, rescue_tiles on for `on`" if a.tiles else ""),
            "machine": "one MI355X, the runs alternating in one session, a process each",
-           "batch": a.batch, "frame": [1080, 1920], "precision": "fp32", "steps": a.steps, "warmup": a.warmup,
-           "note": "noise frames, seeded weights: ~250 weak boxes per frame, about a third rescued (heavy case)",
+           "batch": 4 if a.tiles else a.batch, "frame": [2160, 3840] if a.tiles else [1080, 1920], "precision": "fp32",
+           "steps": a.steps, "warmup": a.warmup,
+           "note": "noise frames, seeded weights" + ("" if a.tiles else ": ~250 weak boxes per frame, about a third rescued (heavy case)"),
            "parent_ms_per_step": ms["parent"], "off_ms_per_step": ms["off"], "on_ms_per_step": ms["on"],
            "parent_mean": mean(ms["parent"]), "off_mean": mean(ms["off"]), "on_mean": mean(ms["on"]),
            "parent_spread_ms": round(max(ms["parent"]) - min(ms["parent"]), 3),
@@ -142,6 +167,11 @@ def main():
            "family_ms_per_step": {k: [mean([r["family_ms_per_step"][f] for r in runs[k]]) for f in range(7)]
                                   for k in KINDS},
            "parent_runs": runs["parent"], "off_runs": runs["off"], "on_runs": runs["on"]}
+    if a.tiles:
+        res["not_measured"] = "real footage; tiles (4, 4)"
+        res["mosaic_share"] = {k: mean([r["mosaic_share"] for r in runs[k]]) for k in KINDS}
+        res["merged_per_frame"] = {k: mean([r["merged_per_frame"] for r in runs[k]]) for k in KINDS}
+        res["frames_past_lds_of_4"] = {k: [r["frames_past_lds"] for r in runs[k]] for k in KINDS}
     line = json.dumps(res)
     print(line, flush=True)
     if a.json:

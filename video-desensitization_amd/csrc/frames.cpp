@@ -501,7 +501,7 @@ int Ctx::tiles_set(int rows, int cols, int overlap_pct) {
         return vd_set_error(VD_ERR_ARG, "vd_tiles: rows, cols in [1, %d] and overlap_pct in [0, 50] required (got %d, "
                             "%d, %d)", VD_TILES_MAX, rows, cols, overlap_pct);
     if (rows == tile_rows && cols == tile_cols && overlap_pct == tile_overlap) return VD_OK;
-    if (rescue_on())
+    if (rescue_on() && !rescue_tiles)
         return vd_set_error(VD_ERR_STATE, "vd_tiles: tiled detection and rescue (vd_rescue) cannot be combined");
     if (lead.pend)
         return vd_set_error(VD_ERR_STATE, "vd_tiles: %d frames are pending in the look-ahead ring (flush first)", lead.pend);
@@ -510,6 +510,10 @@ int Ctx::tiles_set(int rows, int cols, int overlap_pct) {
     tiles_kn = ptiles_kn = 0;
     face_rows_merged = plate_rows_merged = false;
     hold.reset();                                 // the merged rows change capacity: a new stream
+    if (rescue_on()) {                            //   ... for the rescue too (vd_rescue_tiles)
+        rescue_hs.reset();
+        rescue_n = 0;
+    }
     return VD_OK;
 }
 
@@ -542,7 +546,7 @@ int Ctx::face_letterbox_tiles(const uint8_t* dframes, int n, int h, int w, size_
 // plates: the plate lists, class-aware at cfg.plate_iou, in a buffer of their own (both nets' rows
 // are live after a vd_process call).
 int Ctx::tiles_merge(int n, const TileGrid& g, const int* cnt, const float* xyxy_f, const float* score, const int* label,
-                     int icap, const BoxTargets& t, bool plates, bool split) {
+                     int icap, const BoxTargets& t, bool plates, bool split, bool low_on, float thr) {
     const int kcap = plates ? plate.post.kcap : face.post.kcap;
     const size_t F = std::max(cfg.max_batch / g.T, 1);
     const size_t mcap = (size_t)g.T * kcap;
@@ -552,7 +556,7 @@ int Ctx::tiles_merge(int n, const TileGrid& g, const int* cnt, const float* xyxy
     size_t sort_cap = 1;
     while (sort_cap < mcap) sort_cap <<= 1;
     const size_t rows = F * mcap;
-    const size_t need = rows * (16 + 16 + 16 + 4 + 4 + 4 + 1 + (plates ? 4 : 0)) + F * sort_cap * 8 + F * 4 + 256;
+    const size_t need = rows * (16 + 16 + 16 + 4 + 4 + 4 + 1 + (plates ? 4 : 0)) + F * sort_cap * 8 + 2 * (F * 4 + 16) + 256;
     int rc = plates ? ensure_staging(&ptiles_buf, &ptiles_buf_bytes, need) : ensure_staging(&tiles_buf, &tiles_buf_bytes, need);
     if (rc) return rc;
     TileMergeArgs a{};
@@ -569,7 +573,9 @@ int Ctx::tiles_merge(int n, const TileGrid& g, const int* cnt, const float* xyxy
     a.s_area = (float*)p; p += rows * 4;
     if (plates) { a.s_cls = (int*)p; p += rows * 4; }
     a.m_count = (int*)p; p += (F * 4 + 15) / 16 * 16;
+    a.m_all = (int*)p; p += (F * 4 + 15) / 16 * 16;   // the whole merged counts (low_on)
     a.s_supp = (uint8_t*)p;
+    a.low_on = low_on ? 1 : 0; a.thr = thr;
     a.sort_cap = (int)sort_cap; a.mcap = (int)mcap;
     a.cap = t.cap; a.out_count = t.count; a.out_xyxy = t.xyxy; a.out_xyxy_f = t.xyxy_f;
     a.out_score = t.score; a.out_label = t.label;
@@ -602,6 +608,10 @@ int Ctx::tiles_nets_set(int nets) {
         tiles_kn = ptiles_kn = 0;
         face_rows_merged = plate_rows_merged = false;
         hold.reset();                                 // the merged rows change capacity: a new stream
+        if (rescue_on()) {                            //   ... for the rescue too (vd_rescue_tiles)
+            rescue_hs.reset();
+            rescue_n = 0;
+        }
     }
     tile_nets = nets;
     return VD_OK;
@@ -614,6 +624,21 @@ int Ctx::tiles_surfaces_set(int on) {
         return vd_set_error(VD_ERR_STATE, "vd_tiles_surfaces: %d frames are pending in the look-ahead ring (flush first)",
                             lead.pend);
     tile_surfaces = on;
+    return VD_OK;
+}
+
+// The switch alone: no capacity depends on it, so every history stays. Off while both are on would leave a
+// combination the setters refuse.
+int Ctx::rescue_tiles_set(int on) {
+    if (on != 0 && on != 1) return vd_set_error(VD_ERR_ARG, "vd_rescue_tiles: on %d (expected 0 or 1)", on);
+    if (on == rescue_tiles) return VD_OK;
+    if (lead.pend)
+        return vd_set_error(VD_ERR_STATE, "vd_rescue_tiles: %d frames are pending in the look-ahead ring (flush first)",
+                            lead.pend);
+    if (!on && rescue_on() && tiles_on())
+        return vd_set_error(VD_ERR_STATE, "vd_rescue_tiles: rescue (vd_rescue) and tiled detection (vd_tiles) are both on: "
+                            "turn one off first");
+    rescue_tiles = on;
     return VD_OK;
 }
 
@@ -639,12 +664,14 @@ int Ctx::face_post_tiled(int n, int h, int w, const TileGrid& g, const BoxTarget
     int rc = face_post(n * g.T, h, w, BoxTargets{}, &g);
     if (rc) return rc;
     const PostScratch& ps = face.post;
-    return tiles_merge(n, g, ps.kcount, ps.kxyxy_f, ps.kscore, ps.klabel, ps.kcap, t);
+    const bool low = rescue_low[0] > 0.f;         // rescue: the inputs' lists at face_low, whole (kall)
+    return tiles_merge(n, g, low ? ps.kall : ps.kcount, ps.kxyxy_f, ps.kscore, ps.klabel, ps.kcap, t, false, false, low,
+                       cfg.confidence);
 }
 
 // vd_tiles_merge / vd_tiles_merge_plates: the merge step alone on caller lists
-static int tiles_merge_entry(Ctx* ctx, const char* who, bool plates, const vd_boxes* lists, int n, int fh, int fw,
-                             vd_boxes* out) {
+int vd_tiles_merge_lists(Ctx* ctx, const char* who, bool plates, const vd_boxes* lists, int n, int fh, int fw, vd_boxes* out,
+                         bool low_on, float thr) {
     if (!ctx->tiles_on()) return vd_set_error(VD_ERR_STATE, "%s: tiling is off (vd_tiles)", who);
     if (!(plates ? ctx->plate.loaded : ctx->face.loaded))
         return vd_set_error(VD_ERR_STATE, "%s: %s weights not loaded", who, plates ? "plate" : "RetinaFace");
@@ -682,7 +709,7 @@ static int tiles_merge_entry(Ctx* ctx, const char* who, bool plates, const vd_bo
         if (lab) VD_CHECK_HIP(hipMemcpyAsync(dl, lists->label, nb * 4, hipMemcpyHostToDevice, ctx->stream));
         cnt = dc; xf = dx; sc = ds; lab = lab ? dl : nullptr;
     }
-    if ((rc = ctx->tiles_merge(n, g, cnt, xf, sc, lab, lists->cap, t, plates))) return rc;
+    if ((rc = ctx->tiles_merge(n, g, cnt, xf, sc, lab, lists->cap, t, plates, false, low_on, thr))) return rc;
     if ((rc = ctx->box_finish(out, n, t))) return rc;
     if (host && !(out && out->where == VD_HOST))
         VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // staging reused by the next call
@@ -711,16 +738,22 @@ int vd_tiles_surfaces(vd_ctx* h, int on) {
     return ctx->tiles_surfaces_set(on);
 }
 
+int vd_rescue_tiles(vd_ctx* h, int on) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    return ctx->rescue_tiles_set(on);
+}
+
 int vd_tiles_merge(vd_ctx* h, const vd_boxes* lists, int n, int fh, int fw, vd_boxes* out) {
     Ctx* ctx = (Ctx*)h;
     VD_ENTRY(ctx);
-    return tiles_merge_entry(ctx, "vd_tiles_merge", false, lists, n, fh, fw, out);
+    return vd_tiles_merge_lists(ctx, "vd_tiles_merge", false, lists, n, fh, fw, out);
 }
 
 int vd_tiles_merge_plates(vd_ctx* h, const vd_boxes* lists, int n, int fh, int fw, vd_boxes* out) {
     Ctx* ctx = (Ctx*)h;
     VD_ENTRY(ctx);
-    return tiles_merge_entry(ctx, "vd_tiles_merge_plates", true, lists, n, fh, fw, out);
+    return vd_tiles_merge_lists(ctx, "vd_tiles_merge_plates", true, lists, n, fh, fw, out);
 }
 
 int vd_tiles_nets(vd_ctx* h, int nets) {

@@ -296,6 +296,10 @@ struct Ctx {
     RescueArgs rescue_last{};                     // the last launch (row pointers for the readers)
     int rescue_n = 0;                             // frames of the last rescue call (0: none)
     bool rescue_on() const { return rescue_low[0] > 0.f || rescue_low[1] > 0.f; }
+    // rescue on tiled nets (vd_rescue_tiles; 0: vd_rescue and vd_tiles refuse each other, as they always
+    // did). On: a tiled net's lists run at `low`, the merge makes the split (tiles.hip LOW form)
+    int rescue_tiles = 0;
+    int rescue_tiles_set(int on);
     int rescue_set(float face_low, float plate_low, int span);
     int rescue_history(int hcap);                 // history buffers of at least this row capacity
     // E = D ++ R of n consecutive frames into rescue_last's rows, and the history update (RescueArgs' lists)
@@ -363,8 +367,10 @@ struct Ctx {
     int face_letterbox_tiles(const uint8_t* dframes, int n, int h, int w, size_t pitch, const TileGrid& g);
     // the T lists of each of n frames (rows of icap, device) -> tiles_last's merged rows and the caller's targets
     // plates: the class-aware merge at cfg.plate_iou into ptiles_last's rows (split: TileMergeArgs)
+    // low_on: the lists are the lists at `low` and the merge cuts the strong prefix at thr (TileMergeArgs)
     int tiles_merge(int n, const TileGrid& g, const int* cnt, const float* xyxy_f, const float* score, const int* label,
-                    int icap, const BoxTargets& t, bool plates = false, bool split = false);
+                    int icap, const BoxTargets& t, bool plates = false, bool split = false, bool low_on = false,
+                    float thr = 0.f);
     int tiles_check(int n, int h, int w, TileGrid* g);   // the grid, and n * T <= max_batch
     // after face_forward(n * T): per-input post (sizes per input) + merge into the caller's targets
     int face_post_tiled(int n, int h, int w, const TileGrid& g, const BoxTargets& t);
@@ -559,3 +565,7 @@ int vd_plate_post(Ctx& ctx, int n, int img_h, int img_w, const BoxTargets& t, in
 // plate net is tiled) the tile inputs' forward + post and the merge into ptiles_last's rows.
 int vd_plate_detect(Ctx& ctx, const uint8_t* dframes, int n, int h, int w, size_t pitch, bool letterboxed,
                     const TileGrid* tiles, const BoxTargets& t);
+// vd_tiles_merge / vd_tiles_merge_plates: the merge step alone on caller lists (staging, checks, the caller's
+// `out`). low_on / thr: the test hook vdt_tiles_merge_low alone (TileMergeArgs); the entries keep 0.
+int vd_tiles_merge_lists(Ctx* ctx, const char* who, bool plates, const vd_boxes* lists, int n, int fh, int fw, vd_boxes* out,
+                         bool low_on = false, float thr = 0.f);

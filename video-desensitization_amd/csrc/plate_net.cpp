@@ -479,7 +479,9 @@ int vd_plate_detect(Ctx& c, const uint8_t* d, int n, int h, int w, size_t pitch,
     if ((rc = vd_plate_forward(c, d, n, h, w, pitch, false, tiles))) return rc;
     if ((rc = vd_plate_post(c, n * (tiles->T - 1), tiles->th, tiles->tw, BoxTargets{}, n))) return rc;
     const PostScratch& ps = c.plate.post;
-    return c.tiles_merge(n, *tiles, ps.kcount, ps.kxyxy_f, ps.kscore, ps.klabel, ps.kcap, t, true, true);
+    const bool low = c.rescue_low[1] > 0.f;      // rescue: the inputs' lists at plate_low, whole (kall)
+    return c.tiles_merge(n, *tiles, low ? ps.kall : ps.kcount, ps.kxyxy_f, ps.kscore, ps.klabel, ps.kcap, t, true, true, low,
+                         c.cfg.plate_conf);
 }
 
 // the raw head tensors of the last forward's n inputs -> [n][64 + nc][A] (box DFL logits, class

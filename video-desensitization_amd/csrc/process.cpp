@@ -456,8 +456,9 @@ static int process_impl(Ctx* ctx, const uint8_t* in, uint8_t* out, int n, int fh
     auto rescue = [&]() -> int {
         if (!ctx->rescue_on() || (!c0 && !c1)) return VD_OK;
         RescueArgs a{};
-        a.cnt0 = c0; a.xy0 = x0; a.cap0 = k0; a.all0 = c0 && ctx->rescue_low[0] > 0.f ? fp.kall : nullptr;
-        a.cnt1 = c1; a.xy1 = x1; a.cap1 = k1; a.all1 = c1 && ctx->rescue_low[1] > 0.f ? pp.kall : nullptr;
+        // a tiled net (vd_rescue_tiles): the merged rows hold the merged list at `low`, m_all its count
+        a.cnt0 = c0; a.xy0 = x0; a.cap0 = k0; a.all0 = c0 && ctx->rescue_low[0] > 0.f ? (tiled ? tm.m_all : fp.kall) : nullptr;
+        a.cnt1 = c1; a.xy1 = x1; a.cap1 = k1; a.all1 = c1 && ctx->rescue_low[1] > 0.f ? (ptiled ? pm.m_all : pp.kall) : nullptr;
         int r = ctx->launch_rescue(n, fh, fw, a);
         if (r) return r;
         dc0 = c0 = ctx->rescue_last.e_count; dx0 = x0 = ctx->rescue_last.e_xy; dk0 = k0 = ctx->rescue_last.ecap;

@@ -165,6 +165,32 @@ int vdt_letterbox_tiles_yuv420_16(vd_ctx* h, const vd_yuv420_16* frames, int n, 
     return letterbox_tiles_420(ctx, who, vd_yuv420_dev(*frames), frames->matrix, frames->range, n, fh, fw, where, out, cpad);
 }
 
+// the merge step of vd_tiles_merge / vd_tiles_merge_plates with low_on = 1: the strong prefix into
+// out_strong as the merge itself writes it, then the whole merged rows (count = m_all) into out_all
+int vdt_tiles_merge_low(vd_ctx* h, const vd_boxes* lists, int n, int fh, int fw, int plates, float thr, vd_boxes* out_strong,
+                        vd_boxes* out_all) {
+    Ctx* ctx = (Ctx*)h;
+    VD_ENTRY(ctx);
+    if (out_all && (!out_all->count || !out_all->xyxy || out_all->cap <= 0))
+        return vd_set_error(VD_ERR_ARG, "vd_boxes needs count, xyxy, cap>0");
+    int rc = vd_tiles_merge_lists(ctx, "vdt_tiles_merge_low", plates != 0, lists, n, fh, fw, out_strong, true, thr);
+    if (rc || !out_all) return rc;
+    const TileMergeArgs& tm = plates ? ctx->ptiles_last : ctx->tiles_last;
+    const hipMemcpyKind kind = out_all->where == VD_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const int w = std::min(out_all->cap, tm.mcap);
+    const size_t dp = (size_t)out_all->cap, sp = (size_t)tm.mcap;
+    VD_CHECK_HIP(hipMemcpyAsync(out_all->count, tm.m_all, (size_t)n * 4, kind, ctx->stream));
+    VD_CHECK_HIP(hipMemcpy2DAsync(out_all->xyxy, dp * 16, tm.m_xyxy, sp * 16, (size_t)w * 16, n, kind, ctx->stream));
+    if (out_all->xyxy_f)
+        VD_CHECK_HIP(hipMemcpy2DAsync(out_all->xyxy_f, dp * 16, tm.m_xyxy_f, sp * 16, (size_t)w * 16, n, kind, ctx->stream));
+    if (out_all->score)
+        VD_CHECK_HIP(hipMemcpy2DAsync(out_all->score, dp * 4, tm.m_score, sp * 4, (size_t)w * 4, n, kind, ctx->stream));
+    if (out_all->label)
+        VD_CHECK_HIP(hipMemcpy2DAsync(out_all->label, dp * 4, tm.m_label, sp * 4, (size_t)w * 4, n, kind, ctx->stream));
+    VD_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    return VD_OK;
+}
+
 // the first n face canvases as host f32 [n][H][W][cpad], whatever form the plan keeps them in
 static int letterbox_readback(Ctx* ctx, int n, float* out, int cpad) {
     const Act& in = ctx->face.input;

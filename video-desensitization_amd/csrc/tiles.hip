@@ -56,7 +56,12 @@ int vd_tile_rects_host(int h, int w, int rows, int cols, int overlap_pct, int32_
 
 namespace {
 
-template <bool PLATE>
+// LOW (rescue on a tiled net, p.low_on): the lists are the lists at `low`; the merged rows take the whole
+// merged list and m_all its count, m_count / out_count the length of the strong prefix, the caller's arrays
+// the strong boxes only -- the split of post.hip's emit(). The merged list is in descending score order, so
+// the strong boxes are a prefix of it and the prefix is the merge of the strong prefixes of the inputs. A
+// template parameter: the two forms without it keep their instruction streams.
+template <bool PLATE, bool LOW>
 __global__ __launch_bounds__(VD_NMS_THREADS) void tiles_merge_kernel(TileMergeArgs p) {
     __shared__ __attribute__((aligned(16))) float4 l_box[VD_NMS_LDS_CAND];
     __shared__ __attribute__((aligned(16))) uint64_t l_keys[VD_NMS_LDS_CAND];
@@ -65,6 +70,7 @@ __global__ __launch_bounds__(VD_NMS_THREADS) void tiles_merge_kernel(TileMergeAr
     __shared__ uint8_t l_supp[VD_NMS_LDS_CAND];
     __shared__ uint64_t s_chunk_keep;
     __shared__ int s_nkept;
+    __shared__ int s_nstrong;                              // LOW: 1 + the last strong position emitted
     __shared__ int s_off[VD_TILE_INPUTS_MAX + 1];
     const int tid = threadIdx.x;
     const int f = blockIdx.x, T = p.g.T;
@@ -86,6 +92,7 @@ __global__ __launch_bounds__(VD_NMS_THREADS) void tiles_merge_kernel(TileMergeAr
     if (M == 0) {
         if (tid == 0) {
             p.m_count[f] = 0;
+            if constexpr (LOW) p.m_all[f] = 0;
             if (p.out_count) p.out_count[f] = 0;
         }
         return;
@@ -121,7 +128,10 @@ __global__ __launch_bounds__(VD_NMS_THREADS) void tiles_merge_kernel(TileMergeAr
         supp[i] = 0;
         if constexpr (PLATE) cls[i] = p.label ? p.label[row(t) * p.icap + pos] : 0;
     }
-    if (tid == 0) s_nkept = 0;
+    if (tid == 0) {
+        s_nkept = 0;
+        if constexpr (LOW) s_nstrong = 0;
+    }
     __syncthreads();
 
     vd_nms_greedy_cls<PLATE>(M, box, area, supp, &s_chunk_keep, &s_nkept, p.iou, p.mcap, [&](int pos, int j, const float4& b) {
@@ -136,6 +146,10 @@ __global__ __launch_bounds__(VD_NMS_THREADS) void tiles_merge_kernel(TileMergeAr
         ((float4*)p.m_xyxy_f)[k] = b;
         p.m_score[k] = sc;
         p.m_label[k] = lab;
+        if constexpr (LOW) {                               // the net's own comparison (post.hip emit)
+            if (!(PLATE ? sc > p.thr : sc >= p.thr)) return;
+            atomicMax(&s_nstrong, pos + 1);
+        }
         if (pos >= p.cap || !p.out_xyxy) return;
         const size_t o = (size_t)f * p.cap + pos;
         p.out_xyxy[4 * o + 0] = ib.x; p.out_xyxy[4 * o + 1] = ib.y;
@@ -147,9 +161,16 @@ __global__ __launch_bounds__(VD_NMS_THREADS) void tiles_merge_kernel(TileMergeAr
         if (p.out_score) p.out_score[o] = sc;
         if (p.out_label) p.out_label[o] = lab;
     }, cls);
-    if (tid == 0) {
-        p.m_count[f] = s_nkept;
-        if (p.out_count) p.out_count[f] = s_nkept;
+    if (tid == 0) {                                        // behind the sweep's last barrier
+        if constexpr (LOW) {
+            const int own = min(s_nstrong, s_nkept);
+            p.m_all[f] = s_nkept;
+            p.m_count[f] = own;
+            if (p.out_count) p.out_count[f] = own;
+        } else {
+            p.m_count[f] = s_nkept;
+            if (p.out_count) p.out_count[f] = s_nkept;
+        }
     }
 }
 
@@ -160,7 +181,15 @@ hipError_t vd_launch_tiles_merge(const TileMergeArgs& a, hipStream_t s) {
         a.sort_cap < a.mcap || (a.sort_cap & (a.sort_cap - 1)) || (long long)a.g.T * a.icap > 0x7fffffffLL)
         return hipErrorInvalidValue;
     if (a.plate && !a.s_cls) return hipErrorInvalidValue;
-    if (a.plate) hipLaunchKernelGGL(tiles_merge_kernel<true>, dim3(a.n), dim3(VD_NMS_THREADS), 0, s, a);
-    else hipLaunchKernelGGL(tiles_merge_kernel<false>, dim3(a.n), dim3(VD_NMS_THREADS), 0, s, a);
+    if (a.low_on && !a.m_all) return hipErrorInvalidValue;
+    const dim3 grid(a.n), block(VD_NMS_THREADS);
+    if (a.low_on) {
+        if (a.plate) hipLaunchKernelGGL((tiles_merge_kernel<true, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((tiles_merge_kernel<false, true>), grid, block, 0, s, a);
+    } else if (a.plate) {
+        hipLaunchKernelGGL((tiles_merge_kernel<true, false>), grid, block, 0, s, a);
+    } else {
+        hipLaunchKernelGGL((tiles_merge_kernel<false, false>), grid, block, 0, s, a);
+    }
     return hipGetLastError();
 }

@@ -315,7 +315,7 @@ int Ctx::rescue_set(float face_low, float plate_low, int span) {
     if (on && face_low == rescue_low[0] && plate_low == rescue_low[1] && span == rescue_span) return VD_OK;
     if (lead.pend)
         return vd_set_error(VD_ERR_STATE, "vd_rescue: %d frames are pending in the look-ahead ring (flush first)", lead.pend);
-    if (on && tiles_on())
+    if (on && tiles_on() && !rescue_tiles)
         return vd_set_error(VD_ERR_STATE, "vd_rescue: rescue and tiled detection (vd_tiles) cannot be combined");
     VD_CHECK_HIP(hipStreamSynchronize(stream));   // a queued launch may still read the history
     rescue_low[0] = face_low; rescue_low[1] = plate_low;
@@ -344,7 +344,8 @@ int Ctx::launch_rescue(int n, int h, int w, RescueArgs a) {
     const size_t strong = (size_t)(a.cnt0 ? a.cap0 : 0) + (a.cnt1 ? a.cap1 : 0);
     const size_t weak = a.split ? (size_t)(a.wcnt ? a.wcap : 0) : strong;
     const size_t ecap = std::max(a.split ? strong + weak : strong, (size_t)1), wtot = std::max(weak, (size_t)1);
-    const size_t nets = (size_t)(face.loaded ? face.post.kcap : 0) + (plate.loaded ? plate.post.kcap : 0);
+    // the loaded nets' complete lists: T * kcap merged rows for a tiled net (vd_rescue_tiles)
+    const size_t nets = (size_t)(face.loaded ? face_rows_cap() : 0) + (plate.loaded ? plate_rows_cap() : 0);
     if (std::max(ecap, nets) > 0x3fffffffu) return vd_set_error(VD_ERR_ARG, "rescue: list capacity too large");
     int rc = rescue_history((int)std::max(ecap, nets));
     if (rc) return rc;
@@ -548,11 +549,16 @@ int vd_read_rescue(vd_ctx* h, int net, int n, int which, vd_boxes* out) {
     const bool plate = net == VD_NET_YOLOV8N;
     const PostScratch& ps = plate ? ctx->plate.post : ctx->face.post;
     if (!ps.kcount) return vd_set_error(VD_ERR_STATE, "net %d not loaded", net);
+    // a tiled net (vd_rescue_tiles): its lists are the merged rows, cut by the merge (tiles.hip)
+    const bool mg = plate ? ctx->plate_rows_merged : ctx->face_rows_merged;
+    const TileMergeArgs& tm = plate ? ctx->ptiles_last : ctx->tiles_last;
+    const int* kcount = mg ? tm.m_count : ps.kcount;
+    const int* kall = mg ? (tm.low_on ? tm.m_all : tm.m_count) : (ctx->rescue_low[plate ? 1 : 0] > 0.f ? ps.kall : ps.kcount);
     // W_t is a property of the net's keep list alone; R_t needs the rescue step of vd_process
-    const bool stepped = ctx->rescue_n && !r.split && (plate ? r.cnt1 : r.cnt0) == ps.kcount;
+    const bool stepped = ctx->rescue_n && !r.split && (plate ? r.cnt1 : r.cnt0) == kcount;
     if (which == 0 && !stepped)
         return vd_set_error(VD_ERR_STATE, "vd_read_rescue: net %d took no part in a rescue step of vd_process yet", net);
-    const int frames = which == 0 ? ctx->rescue_n : ps.kn;
+    const int frames = which == 0 ? ctx->rescue_n : (mg ? (plate ? ctx->ptiles_kn : ctx->tiles_kn) : ps.kn);
     if (n <= 0 || n > frames) return vd_set_error(VD_ERR_ARG, "n=%d outside [1, %d frames of the last call]", n, frames);
     BoxTargets t{};
     int rc;
@@ -566,8 +572,9 @@ int vd_read_rescue(vd_ctx* h, int net, int n, int which, vd_boxes* out) {
     }
     RescueReadArgs a{};
     a.which = which; a.list = plate ? 1 : 0;
-    a.cnt = ps.kcount; a.all = ctx->rescue_low[plate ? 1 : 0] > 0.f ? ps.kall : ps.kcount; a.kcap = ps.kcap;   // low == 0: no weak boxes
-    a.xy = ps.kxyxy; a.xy_f = ps.kxyxy_f; a.score = ps.kscore; a.label = ps.klabel;
+    a.cnt = kcount; a.all = kall; a.kcap = mg ? tm.mcap : ps.kcap;   // low == 0: no weak boxes
+    a.xy = mg ? tm.m_xyxy : ps.kxyxy; a.xy_f = mg ? tm.m_xyxy_f : ps.kxyxy_f;
+    a.score = mg ? tm.m_score : ps.kscore; a.label = mg ? tm.m_label : ps.klabel;
     if (plate && r.cnt0 && r.all0) { a.cnt_o = r.cnt0; a.all_o = r.all0; a.kcap_o = r.cap0; }
     a.w_since = which == 0 ? r.w_since : ps.kcount; a.wtot = which == 0 ? r.wtot : 0;   // which 1 never reads it
     a.cap = out->cap; a.out_count = t.count; a.out_xyxy = t.xyxy; a.out_xyxy_f = t.xyxy_f; a.out_score = t.score;

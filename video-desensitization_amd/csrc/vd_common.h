@@ -702,6 +702,12 @@ struct TileMergeArgs {
     int split;                                       // plate: frame f's input 0 at row f, input t > 0 at row
                                                      //   n + f * (T - 1) + (t - 1) (two forwards); 0: row f * T + t
     int* s_cls;                                      // plate: spill scratch [n][mcap]
+    // rescue on a tiled net (include/vdmi.h at vd_rescue_tiles): the input lists are the lists at `low`, the
+    // merged rows hold the whole merged list and m_all its count; m_count / out_count get the length of the
+    // strong prefix (score >= thr, plates score > thr) and the caller's out_* arrays the strong boxes only.
+    // low_on == 0: nothing below is read (appended last: the fields above keep their offsets)
+    int low_on; float thr;
+    int* m_all;                                      // [n] whole merged counts (low_on)
 };
 hipError_t vd_launch_tiles_merge(const TileMergeArgs& a, hipStream_t s);
 

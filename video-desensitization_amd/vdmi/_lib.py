@@ -159,6 +159,7 @@ SIGNATURES = [
     ("vd_tiles_nets", _I, [_P, _I]),
     ("vd_tiles_merge_plates", _I, [_P, ctypes.POINTER(vd_boxes), _I, _I, _I, ctypes.POINTER(vd_boxes)]),
     ("vd_tiles_surfaces", _I, [_P, _I]),
+    ("vd_rescue_tiles", _I, [_P, _I]),
     ("vd_jpeg_decode", _I, [_P, ctypes.POINTER(_P), ctypes.POINTER(_SZ), _I, _P, _I, _I, _SZ, _I]),
     ("vd_jpeg_info", _I, [_P, _SZ, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     ("vd_jpeg_encode", _I, [_P, _P, _I, _I, _I, _SZ, _I, _I, _I, _P, _SZ, ctypes.POINTER(_SZ)]),
@@ -212,6 +213,8 @@ SIGNATURES = [
     ("vdt_plate_raw", _I, [_P, _P, _I, _I, _I, _SZ, _I, _P, ctypes.POINTER(_I)]),
     ("vdt_plate_raw_tiles", _I, [_P, _P, _I, _I, _I, _SZ, _I, _P, ctypes.POINTER(_I)]),
     ("vdt_plate_raw_tiles_yuv420", _I, [_P, ctypes.POINTER(vd_yuv420), _I, _I, _I, _I, _P, ctypes.POINTER(_I)]),
+    ("vdt_tiles_merge_low", _I, [_P, ctypes.POINTER(vd_boxes), _I, _I, _I, _I, ctypes.c_float, ctypes.POINTER(vd_boxes),
+                                 ctypes.POINTER(vd_boxes)]),
     ("vdt_plate_postprocess", _I, [_P, _P, _I, _I, _I, ctypes.POINTER(vd_boxes)]),
     ("vdt_jpeg_coefficients", _I, [_P, _SZ, _P, _SZ, ctypes.POINTER(_I)]),
     ("vdt_jdec_stats", _I, [_P, ctypes.POINTER(_I)]),
@@ -364,6 +367,14 @@ def check_tile_surfaces(on):
     if isinstance(on, bool) or (isinstance(on, int) and on in (0, 1)):
         return bool(on)
     raise ValueError(f"tile_surfaces {on!r}: expected False or True")
+
+
+def check_rescue_tiles(on):
+    """rescue_tiles as a bool (vd_rescue_tiles: whether rescue and tiling may be combined); ValueError for
+    anything but a bool or 0 / 1."""
+    if isinstance(on, bool) or (isinstance(on, int) and on in (0, 1)):
+        return bool(on)
+    raise ValueError(f"rescue_tiles {on!r}: expected False or True")
 
 
 def tile_rects(h, w, tiles, tile_overlap=20):

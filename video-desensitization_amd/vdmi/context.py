@@ -384,7 +384,7 @@ class Context:
                  blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30,
                  hold_motion=False, mask="rect", mask_grow=0, tiles=(1, 1), tile_overlap=20, cells=0,
                  lead=0, lead_motion=False, rescue=0.0, plate_rescue=0.0, rescue_span=60, tile_nets="faces",
-                 tile_surfaces=False):
+                 tile_surfaces=False, rescue_tiles=False):
         """blur: what process() applies to the kept boxes: "pixelate" (the reference's
         INTER_NEAREST mosaic, the default) or "gaussian" (GaussianBlur(region, (blur_ksize,
         blur_ksize), blur_sigma) per clipped box, in list order; blur_ksize odd in [3, 127],
@@ -444,9 +444,16 @@ class Context:
         matches, under hold_iou_pct, a box blurred in one of the last max(1, hold) frames is blurred
         too, for at most rescue_span frames (1..255; the default 60 is one second at the
         reference's output rate) after the track's last strong detection. The detections that
-        process() returns stay the strong ones. 0.0 / 0.0 (the default) is off. Not with tiles.
-        Kept as self.rescue_low / self.plate_rescue_low / self.rescue_span; rescue() changes
-        them."""
+        process() returns stay the strong ones. 0.0 / 0.0 (the default) is off. With tiles only
+        under rescue_tiles. Kept as self.rescue_low / self.plate_rescue_low / self.rescue_span;
+        rescue() changes them.
+        rescue_tiles: whether rescue and tiling may be combined (include/vdmi.h at vd_rescue_tiles).
+        False (the default): rescue() in a tiling context and set_tiles() in a rescue context are
+        refused, as they always were. True: a tiled net's per-input lists run at the low threshold
+        and the cross-tile merge makes the split, so the detections stay bit for bit those of the
+        tiled context without rescue, and the weak boxes of the merged list take part in the rescue
+        like an untiled net's. Applied before tiles and rescue. Kept as self.rescue_tiles;
+        set_rescue_tiles() changes it."""
         if blur not in BLUR_MODES:
             raise ValueError(f"blur {blur!r}: expected 'pixelate' or 'gaussian'")
         hold, hold_iou_pct = _lib.check_hold(hold, hold_iou_pct, hold_motion)   # before the library is touched
@@ -454,6 +461,7 @@ class Context:
         tiles, tile_overlap = _lib.check_tiles(tiles, tile_overlap)
         tile_nets = _lib.check_tile_nets(tile_nets)
         tile_surfaces = _lib.check_tile_surfaces(tile_surfaces)
+        rescue_tiles = _lib.check_rescue_tiles(rescue_tiles)
         cells = _lib.check_cells(cells)
         lead, lead_motion = _lib.check_lead(lead, lead_motion)
         rescue, plate_rescue, rescue_span = _lib.check_rescue(rescue, plate_rescue, rescue_span)
@@ -497,6 +505,9 @@ class Context:
         self.mask, self.mask_grow = "rect", 0
         if (mask, mask_grow) != ("rect", 0):
             self.set_mask(mask, mask_grow)
+        self.rescue_tiles = False
+        if rescue_tiles:                                # before tiles and rescue: it lets them combine
+            self.set_rescue_tiles(True)
         self.tiles, self.tile_overlap = (1, 1), tile_overlap
         if tiles != (1, 1):
             self.set_tiles(tiles, tile_overlap)
@@ -1132,11 +1143,19 @@ class Context:
     # -- weak-detection rescue ------------------------------------------------------
     def rescue(self, rescue=0.0, plate_rescue=0.0, rescue_span=60):
         """vd_rescue: the low thresholds (0.0 / 0.0 = off) and the span. A change forgets the
-        rescue and the hold history; it is refused while lead frames are pending and in a tiling
-        context."""
+        rescue and the hold history; it is refused while lead frames are pending and, unless
+        rescue_tiles is on, in a tiling context."""
         lo, plo, span = _lib.check_rescue(rescue, plate_rescue, rescue_span)
         check(self._lib.vd_rescue(self._h, lo, plo, span))
         self.rescue_low, self.plate_rescue_low, self.rescue_span = lo, plo, span
+
+    def set_rescue_tiles(self, on=True):
+        """vd_rescue_tiles: whether rescue and tiling may be combined (1) or refuse each other (0, the
+        default). Keeps every history; VdError while lead frames are pending, and for off while
+        rescue and tiling are both on."""
+        on = _lib.check_rescue_tiles(on)
+        check(self._lib.vd_rescue_tiles(self._h, int(on)))
+        self.rescue_tiles = on
 
     @staticmethod
     def _box_lists(boxes, none_if_empty=False):
@@ -1502,7 +1521,8 @@ class Context:
     # -- tiled detection -----------------------------------------------------------
     def set_tiles(self, tiles=(1, 1), tile_overlap=20):
         """vd_tiles: the tiling (rows, cols) and the overlap percentage (0..50) of the face
-        detection from the next call on; (1, 1) is off. A change forgets the hold history."""
+        detection from the next call on; (1, 1) is off. A change forgets the hold history (and,
+        with rescue_tiles in a rescue context, the rescue history)."""
         tiles, tile_overlap = _lib.check_tiles(tiles, tile_overlap)
         check(self._lib.vd_tiles(self._h, tiles[0], tiles[1], tile_overlap))
         self.tiles, self.tile_overlap = tiles, tile_overlap
@@ -1553,6 +1573,24 @@ class Context:
             return out
         check(self._lib.vd_tiles_merge_plates(self._h, ctypes.byref(ls), n, int(h), int(w), None))
         return self.read_boxes(_lib.VD_NET_YOLOV8N, n)
+
+    def tiles_merge_low(self, lists, h, w, thr, plates=False, cap=None, strong=None):
+        """vdt_tiles_merge_low: the merge in its rescue form alone. lists: as tiles_merge() /
+        tiles_merge_plates() take them, read as the lists at the low threshold; thr: the net's
+        threshold (faces score >= thr, plates score > thr are strong). Returns (strong, whole): the
+        caller-shaped strong list exactly as the merge writes it (a HostBoxes to fill, or a new one
+        of cap boxes per frame, default: room for every box; count complete) and the whole merged
+        rows with the whole merged count."""
+        T = 1 + self.tiles[0] * self.tiles[1]
+        n = lists.n // T
+        full = max(1, T * lists.cap)
+        if strong is None:
+            strong = _lib.HostBoxes(n, full if cap is None else cap)
+        whole = _lib.HostBoxes(n, full)
+        ls, ss, ws = lists.struct(), strong.struct(), whole.struct()
+        check(self._lib.vdt_tiles_merge_low(self._h, ctypes.byref(ls), n, int(h), int(w), 1 if plates else 0, float(thr),
+                                            ctypes.byref(ss), ctypes.byref(ws)))
+        return strong, whole
 
     def _letterbox_tiles_420(self, fn, d, n, h, w, where, cpad):
         T = 1 + self.tiles[0] * self.tiles[1]

@@ -119,6 +119,8 @@ class Retinaface(object):
         # threshold is the plate detector's (YOLO(rescue=...))
         "rescue": 0.0,
         "rescue_span": 60,
+        # whether rescue and tiles may be combined: Context(rescue_tiles=...)
+        "rescue_tiles": False,
     }
 
     @classmethod
@@ -137,6 +139,7 @@ class Retinaface(object):
         self.cells = _lib.check_cells(self.cells)
         self.lead, self.lead_motion = _lib.check_lead(self.lead, self.lead_motion)
         self.rescue, _, self.rescue_span = _lib.check_rescue(self.rescue, 0.0, self.rescue_span)
+        self.rescue_tiles = _lib.check_rescue_tiles(self.rescue_tiles)
         if not self.letterbox_image:
             raise ValueError("Batch inference requires letterbox_image=True for shape alignment.")  # face.py:80
         if not self.cuda:
@@ -157,7 +160,7 @@ class Retinaface(object):
                              mask=self.mask, mask_grow=self.mask_grow, tiles=self.tiles,
                              tile_overlap=self.tile_overlap, cells=self.cells, lead=self.lead,
                              lead_motion=self.lead_motion, rescue=self.rescue, rescue_span=self.rescue_span,
-                             tile_nets=self.tile_nets)
+                             tile_nets=self.tile_nets, rescue_tiles=self.rescue_tiles)
                      for d in self.device_ids]
         self.ctx = self.ctxs[0]
         self.generate()

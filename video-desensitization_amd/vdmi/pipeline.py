@@ -530,7 +530,7 @@ def fused_context(face_detector, plate_detector, batch_size, device=None, slot=0
     key = (id(plate_detector), int(batch_size), dev, int(slot), fd.ctx.mask, fd.ctx.mask_grow, fd.ctx.tiles,
            fd.ctx.tile_overlap, fd.ctx.cells, fd.ctx.lead, fd.ctx.lead_motion, fd.ctx.rescue_low,
            pd.ctx.plate_rescue_low, fd.ctx.rescue_span,   # ... and the rescue setting (Context.rescue)
-           fd.ctx.tile_nets)
+           fd.ctx.tile_nets, fd.ctx.rescue_tiles)
     with _FUSED_LOCK:
         cache = fd.__dict__.setdefault("_fused_ctx", {})
         if key in cache:
@@ -555,7 +555,8 @@ def _new_fused_context(fd, pd, batch_size, dev):
                   hold_motion=fd.ctx.hold_motion, mask=fd.ctx.mask, mask_grow=fd.ctx.mask_grow,
                   tiles=fd.ctx.tiles, tile_overlap=fd.ctx.tile_overlap, cells=fd.ctx.cells,
                   lead=fd.ctx.lead, lead_motion=fd.ctx.lead_motion, rescue=fd.ctx.rescue_low,
-                  plate_rescue=pd.ctx.plate_rescue_low, rescue_span=fd.ctx.rescue_span, tile_nets=fd.ctx.tile_nets)
+                  plate_rescue=pd.ctx.plate_rescue_low, rescue_span=fd.ctx.rescue_span, tile_nets=fd.ctx.tile_nets,
+                  rescue_tiles=fd.ctx.rescue_tiles)
     ctx.load_weights(_lib.VD_NET_RETINAFACE, fd.state_dict)
     ctx.load_weights(_lib.VD_NET_YOLOV8N, pd.state_dict)
     return ctx
@@ -652,7 +653,8 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
                          gpu_codec="auto", jpeg_quality=95, shard="auto", group=None, records=None,
                          blur="pixelate", blur_ksize=31, blur_sigma=0.0, hold=0, hold_iou_pct=30,
                          hold_motion=False, mask="rect", mask_grow=0, tiles=(1, 1), tile_overlap=20, cells=0,
-                         lead=0, lead_motion=False, rescue=0.0, plate_rescue=0.0, rescue_span=60, tile_nets="faces"):
+                         lead=0, lead_motion=False, rescue=0.0, plate_rescue=0.0, rescue_span=60, tile_nets="faces",
+                         rescue_tiles=False):
     """combine_detect.py:183-277. Returns (total_processed, total_faces, total_plates).
 
     gpu_codec ("auto" | True | False): with vdmi detectors, no custom loader/saver and
@@ -718,6 +720,11 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     returned totals and `records` are the detections only. A shard that starts at frame b > 0
     warms up on the rescue_span + hold (+ 1 with hold_motion) frames before it; a dropped batch
     resets the history. 0.0 / 0.0 (the default) is off.
+    rescue_tiles: whether rescue and tiles may be combined (include/vdmi.h at vd_rescue_tiles,
+    Context(rescue_tiles=...)); it must be what the detectors were built with
+    (Retinaface(rescue_tiles=...), YOLO(rescue_tiles=...)), else ValueError. The warm-up stays
+    rescue_span + hold (+ 1) frames and batches are split by frames_per_call() as tiling splits
+    them: E_t does not depend on how the stream is cut.
     hold (0..8) / hold_iou_pct (1..100): box hold (include/vdmi.h, Context(hold=...)): the
     frames are ONE video in the order of their sorted names, and a box stays blurred for up to
     `hold` frames after the last frame in which a detection matched it, so a single missed
@@ -767,6 +774,12 @@ def batch_process_images(input_dir, output_dir, face_detector, plate_detector, b
     lead, lead_motion = _lib.check_lead(lead, lead_motion)
     rescue, plate_rescue, rescue_span = _lib.check_rescue(rescue, plate_rescue, rescue_span)
     rescue_on = bool(rescue or plate_rescue)
+    rescue_tiles = _lib.check_rescue_tiles(rescue_tiles)
+    for det in (face_detector, plate_detector):
+        dctx = getattr(det, "ctx", None)
+        if hasattr(dctx, "rescue_tiles") and bool(dctx.rescue_tiles) != rescue_tiles:
+            raise ValueError("rescue_tiles needs the vdmi Retinaface / YOLO drop-ins built with the same setting "
+                             "(Retinaface(rescue_tiles=...), YOLO(rescue_tiles=...))")
     if lead and gpu_codec is True:
         raise ValueError("lead > 0: the GPU JPEG codec path is out of scope (use gpu_codec='auto' or False)")
     fctx = getattr(face_detector, "ctx", None)

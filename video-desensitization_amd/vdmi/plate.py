@@ -90,7 +90,7 @@ class YOLO:
 
     def __init__(self, model="best.pt", nc=1, weights=None, precision="fp32", max_batch=64, device_index=None,
                  seed=0, imgsz=640, iou=0.7, max_det=300, names=None, device_ids=None, rescue=0.0, tiles=(1, 1),
-                 tile_overlap=20):
+                 tile_overlap=20, rescue_tiles=False):
         from .face import resolve_devices
         self.nc = nc
         self.names = names or {i: f"plate{i}" if nc > 1 else "plate" for i in range(nc)}
@@ -106,9 +106,12 @@ class YOLO:
         # tile_nets="plates")): every image also goes through the net as R x C overlapping crops, merged per
         # class, so plates too small for the letterboxed image are found; a call carries max_batch // T images
         self.tiles, self.tile_overlap = _lib.check_tiles(tiles, tile_overlap)
+        # rescue_tiles: whether rescue and tiles may be combined (Context(rescue_tiles=...)); off, a detector
+        # with both is refused by its contexts as it always was
+        self.rescue_tiles = _lib.check_rescue_tiles(rescue_tiles)
         self.ctxs = [Context(device=d, precision=precision, max_batch=max_batch, plate_nc=nc, plate_iou=iou,
                              plate_max_det=max_det, plate_imgsz=imgsz, plate_rescue=self.rescue, tiles=self.tiles,
-                             tile_overlap=self.tile_overlap, tile_nets="plates")
+                             tile_overlap=self.tile_overlap, tile_nets="plates", rescue_tiles=self.rescue_tiles)
                      for d in self.device_ids]
         self.ctx = self.ctxs[0]
         if isinstance(weights, str) and weights == "random":   # explicit opt-in (tests, bench)
